@@ -19,9 +19,14 @@ into contiguous ranges (strong scaling), every rank scans its shard for the same
 the per-shard top-k are all-gathered over RCCL and merged.
 
 Rank 0 prints ONE JSON line.  `roofline` is measured live with HIP events recorded by the
-library on its own stream around every launch of the dominant scan kernel; `cpu_baseline`
-is the CPU oracle (a build-authored restatement: vRod itself has no scan) timed on this
-host on a bounded sample.
+library on its own stream around every launch of the dominant scan kernel.
+
+A plain run sets up, warms up, times the K steps and prints the line; nothing else.  `--full`
+adds what takes runs or host work of its own, all outside the timed region: `cpu_baseline`
+(the CPU oracle -- a build-authored restatement, vRod itself has no scan -- timed on this host
+on a bounded sample) with recall@k and bit-exactness of the HIP path on that sample, the
+host-pointer probe, the 1-query HBM probe (cfg2), and for N > 1 the merged-equals-single-device
+and oracle checks.  `--dump-outputs DIR` writes the last timed step's result (ids.npy, scores.npy).
 """
 from __future__ import annotations
 
@@ -65,12 +70,20 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="cfg3", choices=sorted(WORKLOADS))
     ap.add_argument("--rows", type=int, default=0, help="override total corpus rows (debug)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-hbm-probe", action="store_true", help="skip the extra 1-query HBM-roofline probe (cfg2)")
-    ap.add_argument("--no-host-probe", action="store_true", help="skip the host-pointer (vrod_search, PCIe-inclusive) probe")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline + recall vs the oracle, the host-pointer probe, the 1-query HBM probe (cfg2, beside cfg3) "
+                         "and, for N > 1, the merged-equals-single-device / oracle checks")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-hbm-probe", action="store_true", help="--full without the extra 1-query HBM-roofline probe (cfg2)")
+    ap.add_argument("--no-host-probe", action="store_true", help="--full without the host-pointer (vrod_search, PCIe-inclusive) probe")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result to DIR/ids.npy (float64) and DIR/scores.npy (float32)")
     ap.add_argument("--inprocess", action="store_true",
                     help="one process, one handle over --gpus devices (vrod_index_create n_devices > 1, RCCL inside the library)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def self_launch(args) -> None:
@@ -84,8 +97,10 @@ def self_launch(args) -> None:
         port = sk.getsockname()[1]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    # the ranks run in ROOT: a relative --dump-outputs is resolved here (the last occurrence of an option wins)
+    dump = ["--dump-outputs", os.path.abspath(args.dump_outputs)] if args.dump_outputs else []
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:] + dump
     p = subprocess.run(cmd, stdout=subprocess.PIPE, env=env, cwd=ROOT)
     lines = [l for l in p.stdout.decode("utf-8", "replace").splitlines() if l.startswith("{")]
     if p.returncode != 0 or len(lines) != 1:
@@ -164,6 +179,16 @@ def run_steps(ix, wl, steps, first_step, world, rank, dist, va, torch, dev, coll
         acc["exchange_ms"] = sum(a.elapsed_time(b) for a, b in ex_events)
     final = (mi, ms) if collective else (bufs[(steps - 1) % depth][1], bufs[(steps - 1) % depth][2])
     return acc, final
+
+
+def dump_outputs(dirname, final) -> None:
+    """--dump-outputs: the last timed step's result as the caller of the search receives it, one row per query.
+    ids: uint64 on the device, stored as float64 (exact below 2**53; ID_NONE, all ones, reads as -1); scores: float32."""
+    import numpy as np
+    ids, scores = final
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "ids.npy"), ids.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(dirname, "scores.npy"), scores.cpu().numpy().astype(np.float32))
 
 
 def baseline_metric() -> str:
@@ -380,8 +405,10 @@ def main_inprocess(args):
         out["per_device"] = [{"shard": g, "device": devs[g], "scan_ms_per_step": round(acc["dev_ms"][g] / max(args.steps, 1), 4)} for g in range(len(devs))]
     final = tuple(t.clone() for t in outs[(args.steps - 1) % 2])
     ix.close()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, final)
     checks_ok = True
-    if len(devs) > 1 and os.environ.get("VROD_BENCH_VERIFY") != "0":
+    if args.full and len(devs) > 1 and os.environ.get("VROD_BENCH_VERIFY") != "0":
         checks_ok = multi_gpu_checks(out, wl, va, torch, devs[0], n_total, final, args.warmup + args.steps - 1)
     sys.stdout.flush()
     os.dup2(real_stdout, 1)
@@ -585,12 +612,14 @@ def main():
                 "wall_ms_per_step": {"min": round(min(col(3)), 4), "max": round(max(col(3)), 4)},
                 "roofline_rank": 0,
             }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, final)
         checks_ok = True
-        if coll and not wl.get("dup_groups") and os.environ.get("VROD_BENCH_VERIFY") != "0":
+        if args.full and coll and not wl.get("dup_groups") and os.environ.get("VROD_BENCH_VERIFY") != "0":
             # N > 1: recall / exactness fields of the metric, outside the timed region (VROD_BENCH_VERIFY=0 skips them)
             ix.close()
             checks_ok = multi_gpu_checks(out, wl, va, torch, dev_index, n_total, final, args.warmup + args.steps - 1)
-        if world == 1 and not args.no_cpu_baseline and not wl.get("dup_groups"):
+        if args.full and world == 1 and not args.no_cpu_baseline and not wl.get("dup_groups"):
             cb, recall, bit_exact, rs, extra = cpu_baseline(wl, va, torch, dev, n_total)
             out["cpu_baseline"] = cb
             out[f"recall_at_{wl['k']}"] = round(recall, 6)
@@ -598,7 +627,7 @@ def main():
             out["bit_exact_vs_oracle_on_sample"] = bit_exact
             out["parity"] = "unpinned by the reference (vRod holds no scan, tests or vectors): the oracle is a build-authored restatement"
             out.update(extra)
-        if world == 1 and not args.no_host_probe and not wl.get("dup_groups"):
+        if args.full and world == 1 and not args.no_host_probe and not wl.get("dup_groups"):
             # the boundary as SURVEY.md 8(b) specifies it: vrod_search, host pointers in, results in host
             # memory, synchronous (PCIe both ways inside the call).  Reported beside `value`, never as it.
             hq = va.synth_rows_device(dev_index, QUERY_SEED, 0, nq, wl["dim"]).cpu().numpy()
@@ -612,7 +641,7 @@ def main():
             out["host_pointer_qps"] = {"value": round(nq * hsteps / th, 2), "unit": "queries/s", "ms_per_batch": round(th / hsteps * 1e3, 4),
                                        "batches": hsteps, "entry_point": "vrod_search (host fp32 queries in, host ids + scores out, synchronous; "
                                        "one batch at a time, nothing in flight across calls)"}
-        if world == 1 and not args.no_hbm_probe and args.workload == "cfg3":
+        if args.full and world == 1 and not args.no_hbm_probe and args.workload == "cfg3":
             # the north_star's second roofline: the memory-bound 1-query scan (configs[1])
             ix.close()
             w2 = WORKLOADS["cfg2"]

@@ -5,14 +5,14 @@ set -o pipefail
 O=gpurun_out/final; mkdir -p $O
 B="--no-cpu-baseline --no-hbm-probe --no-host-probe"
 python -c "import __graft_entry__ as g; g.smoke()" > $O/k_smoke.log 2>&1 &&
-python bench.py --steps 20 --warmup 5 > $O/k_bench_default.json 2> $O/k_bench_default.err &&
+python bench.py --full --steps 20 --warmup 5 > $O/k_bench_default.json 2> $O/k_bench_default.err &&
 python bench.py --steps 400 --warmup 5 $B > $O/k_sustained_400_batches.json 2> $O/s.err &&
 VROD_BENCH_FORCE_COLLECTIVE=1 VROD_BENCH_VERIFY=0 python bench.py --rows 1250000 --steps 200 --warmup 10 $B > $O/k_shard_1p25M_with_exchange.json 2> $O/sh.err &&
 python bench.py --rows 1250000 --steps 200 --warmup 10 $B > $O/k_shard_1p25M.json 2> $O/sh1.err &&
 python bench.py --rows 2500000 --steps 100 --warmup 10 $B > $O/k_shard_2p5M.json 2> $O/sh2.err &&
 python bench.py --rows 5000000 --steps 60 --warmup 5 $B > $O/k_shard_5M.json 2> $O/sh5.err &&
-python bench.py --workload cfg2 --steps 60 --warmup 5 --no-cpu-baseline > $O/k_bench_cfg2.json 2> $O/c2.err &&
-python bench.py --workload cfg5 --steps 8 --warmup 2 --no-cpu-baseline > $O/k_bench_cfg5_split.json 2> $O/c5.err &&
+python bench.py --full --workload cfg2 --steps 60 --warmup 5 --no-cpu-baseline > $O/k_bench_cfg2.json 2> $O/c2.err &&
+python bench.py --full --workload cfg5 --steps 8 --warmup 2 --no-cpu-baseline > $O/k_bench_cfg5_split.json 2> $O/c5.err &&
 python bench.py --rows 40000000 --steps 8 --warmup 2 $B > $O/k_cfg4_on_one_gpu_40M.json 2> $O/c4.err &&
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT &&
 rocprofv3 --kernel-trace --output-format csv -d $O/t10 -- python3 scripts/ab_probe.py 10000000 1024 4 > $O/t10.log 2>&1 &&

@@ -1,6 +1,6 @@
 set -o pipefail
 O=gpurun_out/final; mkdir -p $O
-python bench.py --steps 20 --warmup 5 > $O/k_bench_default.json 2> $O/k_bench_default.err &&
+python bench.py --full --steps 20 --warmup 5 > $O/k_bench_default.json 2> $O/k_bench_default.err &&
 python bench.py --steps 400 --warmup 5 --no-cpu-baseline --no-hbm-probe --no-host-probe > $O/k_sustained_400_batches.json 2> $O/s.err &&
 VROD_BENCH_FORCE_COLLECTIVE=1 python bench.py --rows 1250000 --steps 200 --warmup 10 --no-cpu-baseline --no-hbm-probe --no-host-probe > $O/k_shard_1p25M_with_exchange.json 2> $O/sh.err &&
 python bench.py --rows 2500000 --steps 100 --warmup 10 --no-cpu-baseline --no-hbm-probe --no-host-probe > $O/k_shard_2p5M.json 2> $O/sh2.err &&

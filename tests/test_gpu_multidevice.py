@@ -220,7 +220,7 @@ def test_a_device_that_does_not_exist_is_an_error_not_an_abort(va):
     assert "out of range" in str(e.value)
 
 
-def test_without_librccl_the_exchange_falls_back_to_peer_copies(va, oracle):
+def test_without_librccl_the_exchange_falls_back_to_peer_copies(va, oracle, tmp_path):
     """VROD_RCCL_LIB pointing at something that is no library: a one-time warning, stats.exchange = 2, same bits.
     (Own process: the library binds librccl once per process.)"""
     import subprocess
@@ -241,7 +241,9 @@ assert np.array_equal(ids, oi) and np.array_equal(sc.view(np.uint32), osc.view(n
 print("ok")
 '''
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, VROD_RCCL_LIB="/etc/hostname")
+    not_a_library = tmp_path / "librccl.so"
+    not_a_library.write_text("not a shared object\n")
+    env = dict(os.environ, VROD_RCCL_LIB=str(not_a_library))
     env.pop("VROD_RCCL", None)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=root, env=env, timeout=600)
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stderr[-2000:]
