@@ -47,6 +47,11 @@ def run_case(va, O, raw, rq, k, dtype, metric, path, id_offset=0):
         assert_same(ids, sc, oi, osc, f"{dtype}/{metric}/path{path}/split={mode}")
         if mode == "0":
             assert st["split_pass"] == 0
+        # the certificate's premise, whether or not some certificates failed; only a bound that overflowed fp32
+        # (squared L2 distances beyond FLT_MAX: the certificate refuses) says nothing
+        if st["path"] != 3 and np.isfinite(st["eps_bound"]):
+            assert st["max_fast_err"] <= st["eps_bound"], \
+                f"{dtype}/{metric}/path{path}/split={mode}: max_fast_err / eps_bound = {st['max_fast_err'] / st['eps_bound']:.3g}, {st}"
     return st
 
 

@@ -59,5 +59,5 @@ def test_random_case_matches_oracle(va, oracle, case):
     oi, osc = oracle.search(raw, rq, k, DT[dtype], ME[metric], threads=8)
     assert np.array_equal(ids, oi), f"ids differ: {np.argwhere(ids != oi)[:4]} stats={st}"
     assert np.array_equal(sc.view(np.uint32), osc.view(np.uint32)), f"score bits differ, stats={st}"
-    if st["fallback_queries"] == 0 and st["path"] != 3:
+    if st["path"] != 3 and np.isfinite(st["eps_bound"]):     # failed certificates included: the premise holds for every row
         assert st["max_fast_err"] <= st["eps_bound"] * 1.0001, st

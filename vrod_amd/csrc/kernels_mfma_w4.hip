@@ -2,6 +2,7 @@
 // SPLIT form over the [hi | lo] planes of fp32 rows (cfg5).  Family overview: kernels_mfma.hip.  The accumulator file
 // a[0:255] is owned by the inline asm of this file: scripts/audit_w4.py runs on its assembly in the build (Makefile).
 #include "mfma_common.h"
+#include "w4_steal.h"
 
 namespace vrod {
 
@@ -419,20 +420,10 @@ __device__ __forceinline__ const char* w4_uniform_ptr(const char* p) {
 // the result is needed), published to the other waves through two words of LDS, and the staging pointers jump there
 // without draining the pipeline.  A stolen chunk is scanned without its three sibling query blocks beside it (its corpus
 // tiles are not shared through the XCD's L2): measured, no extra HBM reads to speak of (profiles/r03/x_traffic_sweep.txt:
-// 18.48 GB per cfg3 batch against 18.43 with static shares).
+// 18.48 GB per cfg3 batch against 18.43 with static shares).  The partition of a tail into chunks (an odd remainder goes
+// into the last chunk: no range is shorter than 2 tiles) is w4_steal.h, checked on the host by
+// tests/test_w4_steal_partition.py.
 // ---------------------------------------------------------------------------------------------
-#ifndef VROD_W4_STEAL_CHUNK
-#define VROD_W4_STEAL_CHUNK 2
-#endif
-#ifndef VROD_W4_STEAL_DIV
-#define VROD_W4_STEAL_DIV 16
-#endif
-constexpr uint32_t kStealChunk = VROD_W4_STEAL_CHUNK;     // tiles per claimable chunk
-__host__ __device__ inline uint32_t w4_tail_tiles(uint32_t strip_tiles) {   // tiles of a strip that are handed out dynamically
-    if (strip_tiles < 48u) return 0u;                                       // short launches (first stages, shards of small corpora): static
-    const uint32_t t = strip_tiles / (uint32_t)VROD_W4_STEAL_DIV;
-    return t > 32u * kStealChunk ? 32u * kStealChunk : t;                   // one 32-bit word of claim bits per (query block, strip)
-}
 __device__ __forceinline__ void w4_strip_range(const MfmaKernelArgs& a, uint32_t s, uint32_t& b, uint32_t& e) {
     b = a.tile_first + (uint32_t)((uint64_t)a.ntiles * s / a.nstrips);
     e = a.tile_first + (uint32_t)((uint64_t)a.ntiles * (s + 1) / a.nstrips);
@@ -443,13 +434,12 @@ __device__ __forceinline__ bool w4_claim(const MfmaKernelArgs& a, uint32_t strip
     auto chunk = [&](uint32_t s, uint32_t j) {
         uint32_t b, e;
         w4_strip_range(a, s, b, e);
-        cb = e - w4_tail_tiles(e - b) + j * kStealChunk;
-        ce = cb + kStealChunk < e ? cb + kStealChunk : e;
+        w4_chunk_range(b, e, j, cb, ce);
     };
     {   // own chunks, ascending (a thief may have taken some: it starts from the top)
         uint32_t b, e;
         w4_strip_range(a, strip, b, e);
-        const uint32_t cpt = (w4_tail_tiles(e - b) + kStealChunk - 1u) / kStealChunk;
+        const uint32_t cpt = w4_tail_chunks(e - b);
         while (own_next < cpt) {
             const uint32_t j = own_next++;
             uint32_t old = 0u;
@@ -466,7 +456,7 @@ __device__ __forceinline__ bool w4_claim(const MfmaKernelArgs& a, uint32_t strip
         if (v < a.nstrips) {
             uint32_t b, e;
             w4_strip_range(a, s, b, e);
-            const uint32_t cpt = (w4_tail_tiles(e - b) + kStealChunk - 1u) / kStealChunk;
+            const uint32_t cpt = w4_tail_chunks(e - b);
             const uint32_t w = __hip_atomic_load(&words[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             free_bits = ~w & (cpt >= 32u ? 0xFFFFFFFFu : ((1u << cpt) - 1u));
         }
@@ -593,8 +583,12 @@ __global__ __launch_bounds__(256) void scan_mfma_w4_kernel(const MfmaKernelArgs 
                     st_kt = 0u;
                     st_tile = nt;
                     // The cursor has entered the LAST tile of the range in hand: wave 0 claims the range that follows and leaves
-                    // it in LDS for everybody's advance out of this tile, KT K-tiles from now (their barriers order the write
-                    // before the reads).  The third word is wave 0's own bookkeeping: its next own chunk.
+                    // it in LDS for everybody's advance out of this tile, KT K-tiles from now (KT >= 3: their barriers order the
+                    // write before the reads).  Invariant: a range read from LDS at a tile boundary is never overwritten in the
+                    // same advance.  Every range is at least 2 tiles long (the static share, and every chunk by w4_steal.h),
+                    // so the advance that enters a range -- where the other waves may still be reading its {begin, end} --
+                    // enters its first tile, not its last, and wave 0 does not claim there.  The third word is wave 0's own
+                    // bookkeeping: its next own chunk.
                     if (DENSE == 0 && nt + 1u == st_end && wave == 0 && t1s != t1) {
                         uint32_t cb = 0u, ce = 0u;
                         uint32_t own_next = *reinterpret_cast<const uint32_t*>(lds + kLdsNext + 8);
