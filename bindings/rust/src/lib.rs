@@ -17,6 +17,7 @@ pub const VROD_DTYPE_F32: c_int = 0;
 pub const VROD_DTYPE_BF16: c_int = 1;
 pub const VROD_METRIC_COSINE: c_int = 0;
 pub const VROD_METRIC_L2: c_int = 1;
+pub const VROD_METRIC_IP: c_int = 2;
 pub const VROD_ID_NONE: u64 = u64::MAX;
 pub const VROD_MAX_K: u32 = 3584;
 
@@ -101,7 +102,7 @@ fn check(rc: c_int) -> Result<(), ScanError> {
 }
 
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
-pub enum Metric { Cosine, L2 }
+pub enum Metric { Cosine, L2, InnerProduct }
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
 pub enum Dtype { F32, Bf16 }
 
@@ -116,7 +117,11 @@ impl Collection {
     pub fn new(dim: usize, dtype: Dtype, metric: Metric) -> Result<Self, ScanError> {
         let mut idx = std::ptr::null_mut();
         let dt = if dtype == Dtype::Bf16 { VROD_DTYPE_BF16 } else { VROD_DTYPE_F32 };
-        let me = if metric == Metric::L2 { VROD_METRIC_L2 } else { VROD_METRIC_COSINE };
+        let me = match metric {
+            Metric::Cosine => VROD_METRIC_COSINE,
+            Metric::L2 => VROD_METRIC_L2,
+            Metric::InnerProduct => VROD_METRIC_IP,
+        };
         check(unsafe { vrod_index_create(&mut idx, dim as u32, dt, me, std::ptr::null(), 0) })?;
         Ok(Self { idx, dim })
     }

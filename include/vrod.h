@@ -26,9 +26,13 @@
  *
  * Semantics (frozen; DESIGN.md "Scan spec"): ids are row indices in insertion order
  * (+ id_offset); COSINE scores are dot products of L2-normalised vectors (higher is
- * better), L2 scores are squared Euclidean distances (lower is better); results are
- * best-first, ties broken by smaller id; unfilled slots (k > count) are
- * (VROD_ID_NONE, NaN).  Results are bit-identical to the CPU oracle (oracle/).
+ * better), L2 scores are squared Euclidean distances (lower is better), IP (maximum
+ * inner product) scores are dot products of the prepared vectors -- stored as given,
+ * bf16-rounded on BF16 handles, never normalised (higher is better); results are
+ * best-first, ties broken by smaller id, a NaN score (an IP dot product whose terms
+ * overflow to +inf and -inf) ranks last and still carries its row's id; unfilled slots
+ * (k > count) are (VROD_ID_NONE, NaN).  Results are bit-identical to the CPU oracle
+ * (oracle/), except that a NaN score matches any NaN.
  *
  * Environment (read once per process; everything else the library reads is
  * VROD_DEBUG_*: A/B switches of the build's own experiments):
@@ -62,7 +66,7 @@ typedef enum {
 } vrod_status;
 
 enum { VROD_DTYPE_F32 = 0, VROD_DTYPE_BF16 = 1 };  /* storage + fast-pass type */
-enum { VROD_METRIC_COSINE = 0, VROD_METRIC_L2 = 1 };
+enum { VROD_METRIC_COSINE = 0, VROD_METRIC_L2 = 1, VROD_METRIC_IP = 2 };
 
 #define VROD_ID_NONE UINT64_MAX
 #define VROD_MAX_K 3584u
@@ -119,7 +123,7 @@ int vrod_index_destroy(vrod_index *idx);
 
 /* --- corpus ---------------------------------------------------------------- */
 int vrod_index_reserve(vrod_index *idx, uint64_t n_rows);
-/* rows: n x dim fp32, row-major, host memory. Normalised (COSINE) and converted
+/* rows: n x dim fp32, row-major, host memory. Normalised (COSINE only) and converted
  * (BF16) on the device. Ids continue from the current count. */
 int vrod_index_add(vrod_index *idx, const float *rows, uint64_t n);
 /* Append rows [first_row, first_row+n) of the synthetic stream `seed`

@@ -510,11 +510,15 @@ __global__ __launch_bounds__(kSortThreads) void final_topk_kernel(
     if (threadIdx.x == 0) {
         const float t = T[q];
         bool ok;
-        // norms so large that the bound itself overflows (squared L2 distances beyond FLT_MAX):
-        // fast scores are inf / NaN there and T = +inf no longer means "nothing was left out"
+        // norms so large that the bound itself overflows (squared L2 distances beyond FLT_MAX, IP dot products
+        // beyond it): fast and canonical scores are inf / NaN there and T = +-inf no longer means "nothing was left
+        // out".  The test is on the bound's reach PLUS its eps, and it is NaN-safe: a zero query against a row whose
+        // squared norm overflowed gives 0 * inf = NaN, which must refuse too.  While the reach is finite,
+        // Cauchy-Schwarz keeps every fast and canonical partial sum inside it: no score here is inf or NaN.
         const float qn_ = __builtin_sqrtf(__uint_as_float(*max_qn2_bits)), xn_ = __builtin_sqrtf(__uint_as_float(*max_xn2_bits));
         const float span = metric == M_COSINE ? qn_ * xn_ : (qn_ + xn_) * (qn_ + xn_);
-        if (!(span < 3.0e38f)) {
+        const float span_eps = eps_mode == 1 ? 0.0f : eps_c * span + eps_c * 2.3509887e-38f;   // (relative mode: no norm term)
+        if (!(span < 3.0e38f) || !(span + span_eps <= 3.4028234663852886e38f)) {
             ok = false;
         } else if (t == worst_score(metric)) {
             ok = true;  // every row of the shard was a candidate
@@ -598,10 +602,14 @@ __global__ __launch_bounds__(256) void band_prepare_kernel(const uint32_t* __res
     const float ck = out_scores[(uint64_t)q * k + (k - 1)];
     const float qn = __builtin_sqrtf(__uint_as_float(*max_qn2_bits)), xn = __builtin_sqrtf(__uint_as_float(*max_xn2_bits));
     const float span = metric == M_COSINE ? qn * xn : (qn + xn) * (qn + xn);
+    // (NaN-safe like the certificate: a NaN span -- zero query, overflowed row norm -- refuses)
     if (!(ck == ck) || !(span < 3.0e38f) || eps_mode == 1) { thr[f] = never; ok[f] = 0u; return; }
     const float eps = (eps_mode == 0 ? eps_c * qn * xn : eps_c * (qn + xn) * (qn + xn)) + eps_c * 2.3509887e-38f;
     const float slack = 1.01f * eps + 1e-37f;
-    thr[f] = metric == M_COSINE ? ck - slack : ck + slack;
+    const float t = metric == M_COSINE ? ck - slack : ck + slack;
+    // the bound + eps and the threshold itself must be finite, else the band is no superset of the answer
+    if (!(span + eps <= 3.4028234663852886e38f) || !(__builtin_fabsf(t) <= 3.4028234663852886e38f)) { thr[f] = never; ok[f] = 0u; return; }
+    thr[f] = t;
     ok[f] = 1u;
 }
 

@@ -244,6 +244,15 @@ static IdMap idmap_of(const vrod_index* idx) {
     return m;
 }
 
+// The kernels know two score forms: a dot product, higher is better (M_COSINE: COSINE and IP), and the squared L2
+// distance (M_L2).  The handle keeps the public metric; a kernel gets its score form, and preparation is told whether
+// it normalises (M_COSINE) or only stores and rounds (M_L2: L2 and IP).  A raw VROD_METRIC_IP never reaches a kernel.
+static int score_form(int metric) { return metric == VROD_METRIC_L2 ? M_L2 : M_COSINE; }
+static int prep_form(int metric) { return metric == VROD_METRIC_COSINE ? M_COSINE : M_L2; }
+static bool valid_metric(int metric) {
+    return metric == VROD_METRIC_COSINE || metric == VROD_METRIC_L2 || metric == VROD_METRIC_IP;
+}
+
 static int index_reserve(vrod_index* idx, uint64_t n_rows) {
     const uint64_t want = round_up(std::max<uint64_t>(n_rows, 1), kRowTile);
     if (want <= idx->capacity) return VROD_OK;
@@ -281,7 +290,7 @@ static int index_reserve(vrod_index* idx, uint64_t n_rows) {
 static int append_prepared(vrod_index* idx, const float* d_raw, uint64_t n) {
     VROD_TRY(idx->nrm_ws.ensure(n * sizeof(double)));
     char* dst = (char*)idx->corpus + idx->count * idx->row_bytes();
-    launch_prepare_rows(d_raw, n, idx->dim, idx->ld, idx->metric, idx->dtype, idx->nrm_ws.as<double>(),
+    launch_prepare_rows(d_raw, n, idx->dim, idx->ld, prep_form(idx->metric), idx->dtype, idx->nrm_ws.as<double>(),
                         &idx->flags[0], idx->dtype == VROD_DTYPE_F32 ? (float*)dst : nullptr,
                         idx->dtype == VROD_DTYPE_BF16 ? dst : nullptr, idx->stream);
     launch_row_fastnorm(dst, idx->dtype, n, idx->ld, idx->xnorm2 + idx->count, idx->max_xn2_bits, idx->stream);
@@ -451,7 +460,7 @@ static int select_chain(vrod_index* idx, Pending& P, const float* d_scores, uint
     const uint64_t nch0 = (n + kSelectChunk - 1) / kSelectChunk;
     const uint64_t ld_a = nch0 * kp;
     VROD_TRY(P.keys_a.ensure((size_t)nq * ld_a * 8));
-    uint64_t cur_n = launch_select_from_scores(d_scores, score_ld, n, nq, idx->metric, kp, P.keys_a.as<uint64_t>(), ld_a, P.stream);
+    uint64_t cur_n = launch_select_from_scores(d_scores, score_ld, n, nq, score_form(idx->metric), kp, P.keys_a.as<uint64_t>(), ld_a, P.stream);
     const uint64_t* cur = P.keys_a.as<uint64_t>();
     uint64_t cur_ld = ld_a;
     bool a_is_cur = true;
@@ -584,14 +593,16 @@ static int search_enqueue_body(vrod_index* idx, Pending& P, const float* d_queri
     if (split) {
         // the split pass's certificate bound is ~3x the fp32 MFMA pass's: more candidates per query
         kp = (uint32_t)std::min<uint64_t>(N, (uint64_t)k + std::max<uint32_t>(32, k / 2));
-    } else if (path == VROD_PATH_MFMA && idx->metric == VROD_METRIC_COSINE) {
+    } else if (path == VROD_PATH_MFMA && score_form(idx->metric) == M_COSINE) {
         // Every stage of the batched scan appends ~k' (g - 1) rows per query, and a hit costs its work-group
         // ~0.35 us (profiles/r02/mfma_experiments.md): fewer candidates, fewer hits.  The margin only has to keep
         // the k-th canonical score clear of the k'-th fast score by the error bound (1.8e-4 at d = 768 against
         // ~8e-4 per rank at 10M rows); margins 16 / 10 / 6 / 4 / 2 gave 0 / 0 / 0 / 11 / 937 failed certificates in
         // 30 720 queries and 12.58-12.65 / 12.53 / 12.51 / 13.27 / 15.44 ms per batch (1.25M-row shard: 1.82 / - /
         // 1.75 / 1.80 ms); a failed certificate costs a band pass, not a wrong result.  (The L2 bound through the
-        // norm expansion is ~4x wider relative to the gaps: it keeps 16.)
+        // norm expansion is ~4x wider relative to the gaps: it keeps 16.  IP takes this branch: its bound is the same
+        // dot-form bound, scaled by the real norms as its gaps are: rows with norms spread by exp(U(-1, 1)) failed no
+        // certificate at 2M x 768, profiles/ip/.)
         const uint32_t margin_env = debug_env().kp_margin;
         kp = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(N, kSelectChunk / 2), (uint64_t)k + (uint64_t)std::max<uint32_t>(margin_env ? margin_env : 8, k / 8) * idx->kp_boost);
     } else if (path == VROD_PATH_MFMA) {
@@ -651,7 +662,7 @@ static int search_enqueue_body(vrod_index* idx, Pending& P, const float* d_queri
         d_lists = P.lists.as<uint2>();
         d_counts = (uint32_t*)((char*)P.lists.p + (size_t)nq_pad * cap * 8);
     }
-    const uint32_t worst_bits = idx->metric == VROD_METRIC_COSINE ? 0xFF800000u : 0x7F800000u;  // -inf / +inf
+    const uint32_t worst_bits = score_form(idx->metric) == M_COSINE ? 0xFF800000u : 0x7F800000u;  // -inf / +inf
     QueryInit qi{};
     qi.status = d_status;
     qi.counts = d_counts;
@@ -676,7 +687,7 @@ static int search_enqueue_body(vrod_index* idx, Pending& P, const float* d_queri
         qi.n_zero_words2 = (uint32_t)hist_words;
     }
     uint32_t pace_launch = 0;
-    launch_prep_queries(d_queries_raw, nq, nq_pad, idx->dim, idx->ld, idx->metric, idx->dtype, P.q_f32.as<float>(),
+    launch_prep_queries(d_queries_raw, nq, nq_pad, idx->dim, idx->ld, prep_form(idx->metric), idx->dtype, P.q_f32.as<float>(),
                         q_lp, d_qn2, &P.flags[0], &P.flags[1], qi, s);
     HIP_TRY(hipGetLastError());
 
@@ -692,7 +703,9 @@ static int search_enqueue_body(vrod_index* idx, Pending& P, const float* d_queri
 
     if (path == VROD_PATH_STREAM) {
         // -------- fast pass A: HBM-bound scan of <= 8 queries at a time, all N fast scores kept
-        if (idx->metric == VROD_METRIC_COSINE) { eps_mode = 0; eps_c = 4.f * idx->dim * u; }
+        // (dot form, COSINE and IP: |fast - canonical| <= eps_c * |q| * max|x| with the batch's largest query norm and
+        // the corpus's largest row norm -- final_topk_kernel reads both on the device; unit norms only for COSINE)
+        if (score_form(idx->metric) == M_COSINE) { eps_mode = 0; eps_c = 4.f * idx->dim * u; }
         else { eps_mode = 1; eps_c = 4.f * (idx->dim + 2) * u; }
         const uint64_t score_ld = round_up(N, 64);
         VROD_TRY(P.scores.ensure((size_t)8 * score_ld * 4));
@@ -714,7 +727,7 @@ static int search_enqueue_body(vrod_index* idx, Pending& P, const float* d_queri
             if (q0 > 0) HIP_TRY(hipMemsetAsync(d_hist, 0, hist_words * 4, s));
             size_t a, b;
             tm.arm(a, b);
-            launch_scan_stream(idx->corpus, idx->dtype, idx->metric, idx->ld, N,
+            launch_scan_stream(idx->corpus, idx->dtype, score_form(idx->metric), idx->ld, N,
                                P.q_f32.as<float>() + (size_t)q0 * idx->ld, nqp, P.scores.as<float>(), score_ld,
                                d_hist, kp, s);
             P.scan_pairs.push_back({a, b});
@@ -722,9 +735,9 @@ static int search_enqueue_body(vrod_index* idx, Pending& P, const float* d_queri
             st.scan_launches++;
             st.scan_bytes += (double)N * row_bytes_alg;
             st.scan_flops += 2.0 * nqc * (double)N * idx->dim;
-            launch_hist_compact(P.scores.as<float>(), score_ld, N, nqc, idx->metric, d_hist, stream_hist_bits(nqp), kp,
+            launch_hist_compact(P.scores.as<float>(), score_ld, N, nqc, score_form(idx->metric), d_hist, stream_hist_bits(nqp), kp,
                                 P.keys_a.as<uint64_t>(), kSelectChunk, d_cnt, d_status + q0, s);
-            launch_keys_to_candidates(P.keys_a.as<uint64_t>(), kSelectChunk, kSelectChunk, nqc, idx->metric, kp,
+            launch_keys_to_candidates(P.keys_a.as<uint64_t>(), kSelectChunk, kSelectChunk, nqc, score_form(idx->metric), kp,
                                       P.cand_rows.as<uint32_t>() + (size_t)q0 * kp, P.cand_fast.as<float>() + (size_t)q0 * kp,
                                       d_T + q0, d_cnt, s);
         }
@@ -733,14 +746,14 @@ static int search_enqueue_body(vrod_index* idx, Pending& P, const float* d_queri
         // -------- fast pass B: batched MFMA scan.  (1) dense sample pass over the first S rows,
         // (2) exact j-th best per query = threshold, (3) ONE filtered launch over all rows,
         // (4) keep the best k' of every list.
-        if (idx->metric == VROD_METRIC_COSINE) { eps_mode = 0; eps_c = 4.f * idx->dim * u; }
+        if (score_form(idx->metric) == M_COSINE) { eps_mode = 0; eps_c = 4.f * idx->dim * u; }
         else { eps_mode = 2; eps_c = 4.f * (idx->dim + 4) * u; }
         if (split) {
             // |fast - exact dot|: representation (x = hi + lo + r, |r| <= 2^-16 |x|, the lo.lo term
             // dropped) <= 3.1 * 2^-16 |q||x|; fp32 accumulation of 3*dim exact bf16 products in any
             // order <= 4.1 * 3*dim * 2^-24 |q||x|.  (L2 = |q|^2 + |x|^2 - 2 q.x on the same dot.)
             const float repr = 3.1f * 1.52587890625e-5f;
-            if (idx->metric == VROD_METRIC_COSINE) eps_c = 4.1f * 3.f * idx->dim * u + repr;
+            if (score_form(idx->metric) == M_COSINE) eps_c = 4.1f * 3.f * idx->dim * u + repr;
             else eps_c = 4.1f * (3.f * idx->dim + 4) * u + repr;
         }
         // The MFMA scans own the whole chip.  Two orders of the two searches in flight:
@@ -761,7 +774,7 @@ static int search_enqueue_body(vrod_index* idx, Pending& P, const float* d_queri
         const void* qmat = idx->dtype == VROD_DTYPE_BF16 ? q_lp : P.q_f32.p;
         MfmaScanArgs a{};
         a.corpus = idx->corpus; a.queries = qmat; a.xnorm2 = idx->xnorm2; a.qnorm2 = d_qn2; a.thr = d_thr;
-        a.lists = d_lists; a.counts = d_counts; a.cap = cap; a.ld = idx->ld; a.nq_pad = nq_pad; a.nq = nq; a.metric = idx->metric;
+        a.lists = d_lists; a.counts = d_counts; a.cap = cap; a.ld = idx->ld; a.nq_pad = nq_pad; a.nq = nq; a.metric = score_form(idx->metric);
         VROD_TRY(P.dump.ensure(mfma_dump_bytes(idx->num_cus)));
         a.dump = P.dump.p;
         int scan_dtype = idx->dtype;
@@ -810,7 +823,7 @@ static int search_enqueue_body(vrod_index* idx, Pending& P, const float* d_queri
             st.scan_launches++;
             // (the sample rows are scanned again by the first filtered stage: their time counts, their flops and
             // bytes do not -- algorithmic work is 2 * nq * N * d and N * row bytes, each row once)
-            launch_sample_select(P.scores.as<float>(), dense_ld, n_sel, (int)nq, idx->metric, sp.j, d_thr, s);
+            launch_sample_select(P.scores.as<float>(), dense_ld, n_sel, (int)nq, score_form(idx->metric), sp.j, d_thr, s);
         }
         HIP_TRY(hipStreamWaitEvent(s, early ? O.scans_done : O.done, 0));
         uint64_t lo = 0;
@@ -837,7 +850,7 @@ static int search_enqueue_body(vrod_index* idx, Pending& P, const float* d_queri
             const bool last = li + 1 == bounds.size();
             if (li + 2 == bounds.size()) { HIP_TRY(hipEventRecord(P.mid_done, s)); P.mid_recorded = true; }
             if (last) VROD_TRY(record_scans_done(P, s));
-            launch_list_compact(d_lists, d_counts, cap, (int)nq, idx->metric, kp, d_thr, d_status,
+            launch_list_compact(d_lists, d_counts, cap, (int)nq, score_form(idx->metric), kp, d_thr, d_status,
                                 last ? P.cand_rows.as<uint32_t>() : nullptr, last ? P.cand_fast.as<float>() : nullptr,
                                 last ? d_T : nullptr, s);
         }
@@ -849,10 +862,10 @@ static int search_enqueue_body(vrod_index* idx, Pending& P, const float* d_queri
     P.eps_c = eps_c;
     if (path != VROD_PATH_EXACT) {
         // -------- canonical re-score + final ordering + certificate
-        launch_rescore_candidates(idx->corpus, idx->dtype, idx->metric, idx->dim, idx->ld, P.q_f32.as<float>(), (int)nq,
+        launch_rescore_candidates(idx->corpus, idx->dtype, score_form(idx->metric), idx->dim, idx->ld, P.q_f32.as<float>(), (int)nq,
                                   P.cand_rows.as<uint32_t>(), kp, P.cand_canon.as<float>(), s);
         launch_final_topk(P.cand_rows.as<uint32_t>(), P.cand_fast.as<float>(), P.cand_canon.as<float>(), d_T, (int)nq, kp, k,
-                          idx->metric, idmap_of(idx), eps_mode, eps_c, &P.flags[1], idx->max_xn2_bits, d_out_ids, d_out_scores,
+                          score_form(idx->metric), idmap_of(idx), eps_mode, eps_c, &P.flags[1], idx->max_xn2_bits, d_out_ids, d_out_scores,
                           d_status, (float*)&P.flags[2], s);
     }
     launch_gather_readback(d_status, nq, P.flags, idx->max_xn2_bits, d_readback, s);
@@ -991,11 +1004,11 @@ static int band_pass(vrod_index* idx, Pending& P, std::vector<uint32_t>& failed,
     // the batch's max |q|^2 (the bound's norm): the device copy was consumed with the read-back, flags[3] holds it for this pass
     HIP_TRY(hipMemcpyAsync(&P.flags[3], &max_qn2_bits, 4, hipMemcpyHostToDevice, s));
     launch_gather_query_rows(P.q_f32.as<float>(), P.band_idx.as<uint32_t>(), nf, nf_pad, idx->ld, P.band_q.as<float>(), bq_lp, s);
-    launch_band_prepare(P.band_idx.as<uint32_t>(), nf, nf_pad, P.out_scores, k, idx->metric, P.eps_mode, P.eps_c, &P.flags[3], idx->max_xn2_bits,
+    launch_band_prepare(P.band_idx.as<uint32_t>(), nf, nf_pad, P.out_scores, k, score_form(idx->metric), P.eps_mode, P.eps_c, &P.flags[3], idx->max_xn2_bits,
                         d_qn2_all, b_thr, b_qn2, d_counts, b_ok, s);
     MfmaScanArgs a{};
     a.corpus = idx->corpus; a.queries = idx->dtype == VROD_DTYPE_BF16 ? bq_lp : P.band_q.p; a.xnorm2 = idx->xnorm2; a.qnorm2 = b_qn2; a.thr = b_thr;
-    a.lists = d_lists; a.counts = d_counts; a.cap = cap; a.ld = idx->ld; a.nq_pad = nf_pad; a.nq = nf; a.metric = idx->metric;
+    a.lists = d_lists; a.counts = d_counts; a.cap = cap; a.ld = idx->ld; a.nq_pad = nf_pad; a.nq = nf; a.metric = score_form(idx->metric);
     VROD_TRY(P.dump.ensure(mfma_dump_bytes(idx->num_cus)));
     a.dump = P.dump.p;
     int scan_dtype = idx->dtype;
@@ -1050,14 +1063,14 @@ static int band_pass(vrod_index* idx, Pending& P, std::vector<uint32_t>& failed,
         HIP_TRY(hipMemcpyAsync(b_res, hres.data(), (size_t)nf_pad * 4, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemsetAsync(b_status, 0, (size_t)nf_pad * 4, s));
         // every band row of a resolved query is kept (count <= kpb): sorted by fast score, padded with empty slots
-        launch_list_compact(d_lists, d_counts, cap, (int)nf, idx->metric, kpb, b_thr, b_status, P.cand_rows.as<uint32_t>(), P.cand_fast.as<float>(),
+        launch_list_compact(d_lists, d_counts, cap, (int)nf, score_form(idx->metric), kpb, b_thr, b_status, P.cand_rows.as<uint32_t>(), P.cand_fast.as<float>(),
                             b_qn2 /* T: unused */, s);
-        launch_rescore_candidates(idx->corpus, idx->dtype, idx->metric, idx->dim, idx->ld, P.band_q.as<float>(), (int)nf, P.cand_rows.as<uint32_t>(), kpb,
+        launch_rescore_candidates(idx->corpus, idx->dtype, score_form(idx->metric), idx->dim, idx->ld, P.band_q.as<float>(), (int)nf, P.cand_rows.as<uint32_t>(), kpb,
                                   P.cand_canon.as<float>(), s);
         // flags[4]: the band's own observed |fast - canonical| (folded into max_fast_err by search_complete: the band is a
         // superset of the true top-k only while that stays inside the bound)
         HIP_TRY(hipMemsetAsync(&P.flags[4], 0, 4, s));
-        launch_final_topk(P.cand_rows.as<uint32_t>(), P.cand_fast.as<float>(), P.cand_canon.as<float>(), b_qn2, (int)nf, kpb, k, idx->metric, idmap_of(idx),
+        launch_final_topk(P.cand_rows.as<uint32_t>(), P.cand_fast.as<float>(), P.cand_canon.as<float>(), b_qn2, (int)nf, kpb, k, score_form(idx->metric), idmap_of(idx),
                           P.eps_mode, P.eps_c, &P.flags[3], idx->max_xn2_bits, P.band_ids.as<uint64_t>(), P.band_scores.as<float>(), b_status,
                           (float*)&P.flags[4], s);
         launch_scatter_results(P.band_ids.as<uint64_t>(), P.band_scores.as<float>(), P.band_idx.as<uint32_t>(), b_res, nf, k, P.out_ids, P.out_scores, s);
@@ -1130,13 +1143,13 @@ static int search_complete(vrod_index* idx, Pending& P) {
             int g = gmax;
             while ((size_t)g > failed.size() - f0) g >>= 1;
             VROD_TRY(P.scores.ensure((size_t)g * score_ld * 4));
-            launch_rescore_all(idx->corpus, idx->dtype, idx->metric, idx->dim, idx->ld, P.q_f32.as<float>(), &failed[f0], g, N,
+            launch_rescore_all(idx->corpus, idx->dtype, score_form(idx->metric), idx->dim, idx->ld, P.q_f32.as<float>(), &failed[f0], g, N,
                                P.scores.as<float>(), score_ld, s);
             const uint64_t* keys; uint64_t kld, kn;
             VROD_TRY(select_chain(idx, P, P.scores.as<float>(), score_ld, N, g, kx, &keys, &kld, &kn));
             for (int i = 0; i < g; ++i) {
                 const uint32_t qi = failed[f0 + i];
-                launch_keys_to_output(keys + (size_t)i * kld, kn, idx->metric, k, idmap_of(idx), P.out_ids + (size_t)qi * k,
+                launch_keys_to_output(keys + (size_t)i * kld, kn, score_form(idx->metric), k, idmap_of(idx), P.out_ids + (size_t)qi * k,
                                       P.out_scores + (size_t)qi * k, s);
             }
             HIP_TRY(hipGetLastError());
@@ -1556,7 +1569,7 @@ static int composite_end(vrod_index* idx, uint64_t* host_ids, float* host_scores
         oi = idx->out_ids.as<uint64_t>();
         os = idx->out_scores.as<float>();
     }
-    launch_merge_topk(idx->metric, (const uint64_t*)D0.recv[c].p, (const float*)((const char*)D0.recv[c].p + nk * 8), block / 8, block / 4,
+    launch_merge_topk(score_form(idx->metric), (const uint64_t*)D0.recv[c].p, (const float*)((const char*)D0.recv[c].p + nk * 8), block / 8, block / 4,
                       (uint32_t)(U * M), nq, k, oi, os, D0.xstream);
     HIP_TRY(hipGetLastError());
     if (host_ids) {
@@ -1594,7 +1607,7 @@ int vrod_index_create(vrod_index** out, uint32_t dim, int dtype, int metric, con
     *out = nullptr;
     if (dim == 0 || dim > VROD_MAX_DIM) return fail(VROD_ERR_INVALID_ARG, "dim must be in 1..%u", VROD_MAX_DIM);
     if (dtype != VROD_DTYPE_F32 && dtype != VROD_DTYPE_BF16) return fail(VROD_ERR_INVALID_ARG, "bad dtype %d", dtype);
-    if (metric != VROD_METRIC_COSINE && metric != VROD_METRIC_L2) return fail(VROD_ERR_INVALID_ARG, "bad metric %d", metric);
+    if (!valid_metric(metric)) return fail(VROD_ERR_INVALID_ARG, "bad metric %d", metric);
     if (n_devices < 0 || (n_devices > 0 && !device_ids)) return fail(VROD_ERR_INVALID_ARG, "bad device list");
     if (n_devices > 1) {
         if (n_devices > 64) return fail(VROD_ERR_INVALID_ARG, "at most 64 devices per handle");
@@ -1862,9 +1875,9 @@ int vrod_merge_topk_device(int device, int metric, const uint64_t* d_ids, const 
                            uint32_t n_lists, uint32_t nq, uint32_t k, uint64_t* d_out_ids,
                            float* d_out_scores, void* stream) {
     if ((nq && k && n_lists) && (!d_ids || !d_scores || !d_out_ids || !d_out_scores)) return fail(VROD_ERR_INVALID_ARG, "null buffer");
-    if (metric != VROD_METRIC_COSINE && metric != VROD_METRIC_L2) return fail(VROD_ERR_INVALID_ARG, "bad metric %d", metric);
+    if (!valid_metric(metric)) return fail(VROD_ERR_INVALID_ARG, "bad metric %d", metric);
     HIP_TRY(hipSetDevice(device));
-    launch_merge_topk(metric, d_ids, d_scores, (uint64_t)nq * k, (uint64_t)nq * k, n_lists, nq, k, d_out_ids, d_out_scores, (hipStream_t)stream);
+    launch_merge_topk(score_form(metric), d_ids, d_scores, (uint64_t)nq * k, (uint64_t)nq * k, n_lists, nq, k, d_out_ids, d_out_scores, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return VROD_OK;
@@ -1873,7 +1886,7 @@ int vrod_merge_topk_device(int device, int metric, const uint64_t* d_ids, const 
 int vrod_merge_topk_packed_device(int device, int metric, const void* d_packed, uint32_t n_lists, uint32_t nq,
                                   uint32_t k, uint64_t* d_out_ids, float* d_out_scores, void* stream) {
     if ((nq && k && n_lists) && (!d_packed || !d_out_ids || !d_out_scores)) return fail(VROD_ERR_INVALID_ARG, "null buffer");
-    if (metric != VROD_METRIC_COSINE && metric != VROD_METRIC_L2) return fail(VROD_ERR_INVALID_ARG, "bad metric %d", metric);
+    if (!valid_metric(metric)) return fail(VROD_ERR_INVALID_ARG, "bad metric %d", metric);
     HIP_TRY(hipSetDevice(device));
     // one rank's block = nq*k ids (u64) followed by nq*k scores (f32): 12*nq*k bytes, 8-B aligned
     // as long as nq*k is even; the stride is given in elements of each array
@@ -1881,7 +1894,7 @@ int vrod_merge_topk_packed_device(int device, int metric, const void* d_packed, 
     if (block_bytes % 8 != 0) return fail(VROD_ERR_INVALID_ARG, "nq*k must be even for the packed layout");
     const uint64_t* ids = (const uint64_t*)d_packed;
     const float* scores = (const float*)((const char*)d_packed + (uint64_t)nq * k * 8);
-    launch_merge_topk(metric, ids, scores, block_bytes / 8, block_bytes / 4, n_lists, nq, k, d_out_ids, d_out_scores, (hipStream_t)stream);
+    launch_merge_topk(score_form(metric), ids, scores, block_bytes / 8, block_bytes / 4, n_lists, nq, k, d_out_ids, d_out_scores, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return VROD_OK;

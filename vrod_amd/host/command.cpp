@@ -49,7 +49,7 @@ bool parse_vector_line(const std::string& line, std::vector<float>& values, std:
     return !values.empty();
 }
 
-// CREATE: arg = "NAME [metric=cosine|l2] [dtype=f32|bf16] [dim=N]"
+// CREATE: arg = "NAME [metric=cosine|l2|ip] [dtype=f32|bf16] [dim=N]" (any other metric word: cosine)
 void CreateCollectionCommand::execute() {
     std::istringstream in(need(collection_name, "collection name"));
     std::string name, tok;
@@ -58,7 +58,7 @@ void CreateCollectionCommand::execute() {
     while (in >> tok) {
         const size_t eq = tok.find('=');
         const std::string k = tok.substr(0, eq), v = eq == std::string::npos ? "" : tok.substr(eq + 1);
-        if (k == "metric") cfg.metric = (v == "l2" || v == "L2") ? VROD_METRIC_L2 : VROD_METRIC_COSINE;
+        if (k == "metric") cfg.metric = (v == "l2" || v == "L2") ? VROD_METRIC_L2 : (v == "ip" || v == "IP") ? VROD_METRIC_IP : VROD_METRIC_COSINE;
         else if (k == "dtype") cfg.dtype = v == "bf16" ? VROD_DTYPE_BF16 : VROD_DTYPE_F32;
         else if (k == "dim") cfg.dim = (uint32_t)std::stoul(v);
         else throw IoError(IoError::InvalidData, "unknown CREATE option '" + tok + "'");

@@ -41,7 +41,7 @@ void touch(const std::string& p) {
 void check(int rc, const char* what) {
     if (rc != VROD_OK) throw DeviceError(rc, std::string(what) + ": " + vrod_last_error());
 }
-const char* metric_name(int m) { return m == VROD_METRIC_L2 ? "l2" : "cosine"; }
+const char* metric_name(int m) { return m == VROD_METRIC_L2 ? "l2" : m == VROD_METRIC_IP ? "ip" : "cosine"; }
 const char* dtype_name(int d) { return d == VROD_DTYPE_BF16 ? "bf16" : "f32"; }
 
 }  // namespace
@@ -120,7 +120,7 @@ void Collection::load_config() {
         if (eq == std::string::npos) continue;
         const std::string k = line.substr(0, eq), v = line.substr(eq + 1);
         if (k == "dim") cfg_.dim = (uint32_t)std::stoul(v);
-        else if (k == "metric") cfg_.metric = v == "l2" ? VROD_METRIC_L2 : VROD_METRIC_COSINE;
+        else if (k == "metric") cfg_.metric = v == "l2" ? VROD_METRIC_L2 : v == "ip" ? VROD_METRIC_IP : VROD_METRIC_COSINE;
         else if (k == "dtype") cfg_.dtype = v == "bf16" ? VROD_DTYPE_BF16 : VROD_DTYPE_F32;
         else if (k == "count") cfg_.count = std::stoull(v);
     }

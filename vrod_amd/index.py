@@ -14,13 +14,14 @@ from . import _lib
 from ._lib import SearchStats, VrodError, check
 
 DTYPE_F32, DTYPE_BF16 = 0, 1
-METRIC_COSINE, METRIC_L2 = 0, 1
+METRIC_COSINE, METRIC_L2, METRIC_IP = 0, 1, 2
 PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT = 0, 1, 2, 3
 ID_NONE = np.uint64(0xFFFFFFFFFFFFFFFF)
 MAX_K = 3584
 
 _DTYPES = {"f32": DTYPE_F32, "fp32": DTYPE_F32, "float32": DTYPE_F32, "bf16": DTYPE_BF16, "bfloat16": DTYPE_BF16}
-_METRICS = {"cosine": METRIC_COSINE, "cos": METRIC_COSINE, "l2": METRIC_L2, "euclidean": METRIC_L2}
+_METRICS = {"cosine": METRIC_COSINE, "cos": METRIC_COSINE, "l2": METRIC_L2, "euclidean": METRIC_L2,
+            "ip": METRIC_IP, "dot": METRIC_IP, "inner_product": METRIC_IP}
 
 
 def _enum(v, table, what):
