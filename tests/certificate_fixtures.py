@@ -14,7 +14,7 @@ aim at it (tests/test_certificate_fixtures.py) and the GPU tests that run every 
 import numpy as np
 
 U = 2.0 ** -24
-SPLIT_REPR = 3.1 * 2.0 ** -16          # the split pass's representation term (vrod_index.hip)
+SPLIT_REPR = 3.1 * 2.0 ** -16          # the split pass's representation term (search_plan.h)
 
 
 def bf16_rne(a):
@@ -32,7 +32,8 @@ def split_planes(a):
 
 
 def mfma_eps(dim, metric, split, qn, xn):
-    """The batched scan's certificate bound for query norm qn and largest row norm xn (vrod_index.hip eps_c)."""
+    """The batched scan's certificate bound for query norm qn and largest row norm xn (search_plan.h fast_bound and
+    eps_bound; test_search_plan.py checks that they agree)."""
     if split:
         c = 4.1 * (3 * dim + (0 if metric == "cosine" else 4)) * U + SPLIT_REPR
     else:

@@ -15,8 +15,8 @@ pytestmark = pytest.mark.gpu
 DT = {"f32": 0, "bf16": 1}
 ME = {"cosine": 0, "l2": 1}
 
-# Which kernel a batch reaches, by the dispatcher's rule (vrod_index.hip search_enqueue_body, kernels_mfma.hip
-# launch_scan_mfma, kernels_mfma_skinny.hip mfma_skinny_max_queries):
+# Which kernel a batch reaches, by the dispatcher's rule (search_plan.h route -- checked on the CPU by
+# test_search_plan.py --, kernels_mfma.hip launch_scan_mfma, kernels_mfma_skinny.hip mfma_skinny_max_queries):
 #   stream       path STREAM forced, <= 4 queries: kernels_stream.hip, one pass per 8 queries
 #   skinny       bf16 rows, path MFMA, 5..64 queries, the queries fit in LDS (64-query form at d = 768; not at d = 3072)
 #   w4           bf16 rows, path MFMA, > 64 queries: the 4-wave kernel

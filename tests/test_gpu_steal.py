@@ -24,11 +24,10 @@ def bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
-def last_stage_plan(n, nq, k, metric, num_cus):
-    """Restated from the library for a bf16 batch of the 4-wave kernel on a fresh handle (candidate margin x1):
-    choose k' (vrod_index.hip search_enqueue_body), plan_stages, the launch geometry of launch_scan_mfma, and
-    w4_tail_tiles (w4_steal.h, default VROD_W4_STEAL_DIV 16 / VROD_W4_STEAL_CHUNK 2).  Returns (scan launches, the
-    set of tails of the last filtered launch's strips)."""
+def stage_plan(n, nq, k, metric, num_cus):
+    """Restated from the library for a bf16 batch on a fresh handle (candidate margin x1): k' (search_plan.h
+    choose_kp), the sample rows S and the stage bounds (search_plan.h plan_stages).  tests/test_search_plan.py checks
+    this restatement against the header on the CPU.  Returns (k', S, bounds)."""
     tile, cap = 256, 8192
     kp = min(n, cap // 2, k + max(8 if metric == "cosine" else 16, k // 8))
     nqb = (nq + 255) // 256
@@ -44,6 +43,16 @@ def last_stage_plan(n, nq, k, metric, num_cus):
         bounds.append(b // tile * tile)
         b *= g
     bounds.append(n)
+    return kp, S, bounds
+
+
+def last_stage_plan(n, nq, k, metric, num_cus):
+    """stage_plan, the launch geometry of launch_scan_mfma for the 4-wave kernel, and w4_tail_tiles (w4_steal.h,
+    default VROD_W4_STEAL_DIV 16 / VROD_W4_STEAL_CHUNK 2).  Returns (scan launches, the set of tails of the last
+    filtered launch's strips, the strip lengths)."""
+    tile = 256
+    _, _, bounds = stage_plan(n, nq, k, metric, num_cus)
+    nqb = (nq + 255) // 256
     grid = max(8, num_cus // 8 * 8)
     nstrips = 8 * ((grid // 8) // nqb)
     first = bounds[-2] // tile

@@ -3,14 +3,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "search_plan.h"   // kRowTile, the score forms (M_COSINE / M_L2)
+
 namespace vrod {
 
 constexpr int kWave = 64;             // CDNA wavefront
-constexpr uint32_t kRowTile = 256;    // corpus capacity granularity (rows)
 constexpr uint32_t kScoreNoneBits = 0x7FC00000u;
 
 enum : int { DT_F32 = 0, DT_BF16 = 1 };
-enum : int { M_COSINE = 0, M_L2 = 1 };
 
 typedef uint16_t bf16_t;
 

@@ -30,6 +30,7 @@
 #include "../../include/vrod.h"
 #include "vrod_common.h"
 #include "vrod_kernels.h"
+#include "search_plan.h"
 
 using namespace vrod;
 
@@ -81,8 +82,6 @@ struct DevBuf {
     template <typename T> T* as() const { return (T*)p; }
 };
 
-static inline uint64_t round_up(uint64_t x, uint64_t m) { return (x + m - 1) / m * m; }
-
 // a search slot's block of device words: 64 scalars, then one region of sibling-pacing counters and one of work-stealing
 // claim bits per scan launch of the search (8 of each; a search with more launches reuses them behind a memset)
 constexpr uint32_t kPaceRegions = 8, kPaceWords = 192, kClaimWords = (uint32_t)kMfmaClaimWords;
@@ -97,11 +96,8 @@ constexpr size_t kSlotFlagBytes = (64 + kPaceRegions * (kPaceWords + kClaimWords
 struct Pending {
     bool active = false;
     bool trivial = false;          // nq == 0 or empty corpus: the outputs are already final
-    uint32_t nq = 0, k = 0, kp = 0;
-    int path = 0, eps_mode = 0;
-    bool split = false;            // the fast pass of this search ran on the bf16 planes
-    float eps_c = 0.f;
-    uint64_t N = 0;
+    uint32_t nq = 0, k = 0;
+    SearchPlan plan{};             // route, k', bound, nq_pad, N of this search (search_plan.h)
     uint64_t* out_ids = nullptr;
     float* out_scores = nullptr;
     // Each slot has its own stream and its own workspaces, so the tail of search s (compaction,
@@ -115,7 +111,6 @@ struct Pending {
     DevBuf q_planes;               // split pass: [nq_pad][3 * ldp] bf16, [hi_j | lo_j | hi_j] per K-tile j
     // band pass (second chance of the queries whose certificate failed, search_complete)
     DevBuf band_idx, band_q, band_q_lp, band_planes, band_small, band_ids, band_scores;
-    uint32_t nq_pad = 0;           // of the enqueued search (the list / counter / threshold blocks are sized by it)
     uint32_t pace_launches = 0;    // scan launches of this search so far (pacing-counter regions)
     uint32_t* h_readback = nullptr;   // pinned host block: status[nq] + 4 scalars, one D2H per search
     size_t h_readback_words = 0;
@@ -149,7 +144,8 @@ struct Pending {
     GraphKey gkey_graph{};
     bool graph_off = false;        // a capture failed once: this slot stays on plain launches
     // what a replay must restore of the enqueue's host-side results
-    uint32_t g_kp = 0; int g_path = 0, g_eps_mode = 0; float g_eps_c = 0.f; vrod_search_stats g_st{};
+    SearchPlan g_plan{};
+    vrod_search_stats g_st{};
 };
 
 // ------------------------------------------------------------------ the index
@@ -187,12 +183,9 @@ struct vrod_index {
     // sample launch may overlap it, and measures by how much when it completes
     struct TailEv { hipEvent_t start = nullptr, stop = nullptr; bool armed = false; };
     TailEv tail_ev[4];
-    // Self-tuning candidate margin of the batched scan (search_enqueue_body / search_complete): k' = k + margin * kp_boost.
-    // A failed certificate costs a band pass (one more scan of the corpus); doubling the margin costs a few per cent
-    // of hits.  kp_boost doubles (up to 8) after a search with failures, halves after 64 clean ones; failures AT 8 mean
-    // the margin is not what those queries lack (exact duplicates): back to 1 and left alone for 256 searches.
-    static constexpr uint32_t kMaxKpBoost = 8;
-    uint32_t kp_boost = 1, kp_clean = 0, kp_hold = 0;
+    // Self-tuning candidate margin of the batched scan: k' = k + margin * kp_boost.boost (search_plan.h choose_kp,
+    // kp_boost_step; stepped by search_complete)
+    KpBoost kp_boost{};
     uint32_t n_begun = 0, n_ended = 0;   // searches enqueued / completed: slot = counter & 1
     hipEvent_t caller_ev = nullptr;      // orders the caller's stream before ours
 
@@ -244,11 +237,6 @@ static IdMap idmap_of(const vrod_index* idx) {
     return m;
 }
 
-// The kernels know two score forms: a dot product, higher is better (M_COSINE: COSINE and IP), and the squared L2
-// distance (M_L2).  The handle keeps the public metric; a kernel gets its score form, and preparation is told whether
-// it normalises (M_COSINE) or only stores and rounds (M_L2: L2 and IP).  A raw VROD_METRIC_IP never reaches a kernel.
-static int score_form(int metric) { return metric == VROD_METRIC_L2 ? M_L2 : M_COSINE; }
-static int prep_form(int metric) { return metric == VROD_METRIC_COSINE ? M_COSINE : M_L2; }
 static bool valid_metric(int metric) {
     return metric == VROD_METRIC_COSINE || metric == VROD_METRIC_L2 || metric == VROD_METRIC_IP;
 }
@@ -446,13 +434,6 @@ struct Timer {
     }
 };
 
-static uint32_t choose_kp(uint64_t count, uint32_t k) {
-    uint64_t kp = (uint64_t)k + std::max<uint32_t>(16, k / 8);
-    if (kp > count) kp = count;
-    if (kp > kSelectChunk / 2) kp = kSelectChunk / 2;
-    return (uint32_t)kp;
-}
-
 // select chain over fast (or canonical) scores of `nq` queries -> keys of <= kSelectChunk per query
 // returns pointer/ld/n of the final key set through out params.
 static int select_chain(vrod_index* idx, Pending& P, const float* d_scores, uint64_t score_ld, uint64_t n, int nq,
@@ -480,47 +461,83 @@ static int select_chain(vrod_index* idx, Pending& P, const float* d_scores, uint
     return VROD_OK;
 }
 
-// Stage plan of the MFMA path (DESIGN.md "Kernels").  Stage 0 is a DENSE sample (all scores of
-// the first S rows written out, threshold = exact k'-th best of them); every later stage is a
-// filtered launch over g times more rows than everything before it, followed by a compaction
-// (keep the best k', publish the k'-th score as the next threshold).  Each filtered stage thus
-// expects about g*k' rows per query to beat its threshold: enough that a list cannot come up
-// short, far too few to overflow it or to slow the scan.
-struct StagePlan { uint32_t S, j; std::vector<uint64_t> bounds; };
-static StagePlan plan_stages(uint64_t N, uint32_t kp, uint32_t cap, uint32_t max_sample_rows) {
-    StagePlan p;
-    // Growth per filtered stage.  A stage over rows (b, g*b] runs against the k'-th best of the
-    // first b rows, so about k'*(g-1) rows per query beat its threshold: that must stay well under
-    // the list capacity, and -- measured -- appends are not free: the first stage after the
-    // 16K-row sample appends one row in 630 per query (~100 per 256x256 tile) and runs at 1.9 us
-    // per 1000 rows against 1.3 once appends are rare.  The extra time of a stage is ~ (g-1), the
-    // number of stages ~ 1/ln g, each costing a launch ramp and a compaction (~40 us): the total is
-    // flat between g = 4 and 8 and twice as large at g = 25 (two stages at 10M rows: tried,
-    // +0.25 ms per batch).
-    // Round 2, same box, batch 1024 x 768 (profiles/r02/mfma_experiments.md): 10M rows, g = 3 / 4 / 5 / 6 / 8 -> 12.69 / 12.70 /
-    // 12.70 / 12.75 / 12.77-12.87 ms per batch; with the candidate margin at 8, 5M rows g = 4 / 5 / 6 / 8 -> 6.47 / 6.41 / 6.48 /
-    // 6.49, 2.5M -> 3.24 / 3.26 / 3.27 / 3.25, 1.25M -> 1.759 / 1.755 / 1.757 / 1.790.  What a stage pays per hit is the OTHER
-    // three waves of the work-group waiting at the next barrier for the wave that walks a hit column (~0.35 us of
-    // work-group time per append, not 0.1), against ~40 us of ramp + compaction per extra stage: g = 5 at every size.
-    // VROD_DEBUG_STAGE_GROWTH overrides (tuning).
-    const uint64_t g_env = debug_env().stage_growth;
-    const uint64_t g_auto = 5;
-    const uint64_t g = std::max<uint64_t>(2, std::min<uint64_t>(g_env ? g_env : g_auto, cap / (3ull * kp)));
-    // sample: N/g^2 rows, at most one round of work-groups (one 256-row tile per work-group of
-    // the dense launch)
-    const uint64_t s_env = debug_env().sample_rows;   // tuning knob
-    if (s_env) max_sample_rows = (uint32_t)std::min<uint64_t>(s_env, max_sample_rows);
-    uint64_t S = std::min<uint64_t>(N / (g * g), max_sample_rows);
-    S = std::max<uint64_t>(S, std::min<uint64_t>(N, std::max<uint64_t>(4ull * kp, kRowTile)));
-    S = std::min<uint64_t>(round_up(S, kRowTile), N);
-    p.S = (uint32_t)S;
-    p.j = (uint32_t)std::min<uint64_t>(kp, S);
-    for (uint64_t b = S * g; b < N; b *= g) {
-        if (N - b < b / 2) break;                    // the tail would be a sliver: fold it in
-        p.bounds.push_back(b / kRowTile * kRowTile);
+// ------------------------------------------------------------------ workspace layout of a slot
+// P.small: [nq_pad] words each of fast query norms^2 | T (bound on the fast score of what a query left out) | thresholds
+// | status, then the read-back block [nq + 4]
+struct SmallBlock { float* qn2; float* T; float* thr; uint32_t* status; uint32_t* readback; };
+static size_t small_bytes(uint32_t nq_pad) { return (size_t)nq_pad * 4 * 5 + 64; }
+static SmallBlock small_block(const Pending& P) {
+    const size_t n = P.plan.nq_pad;
+    float* f = P.small.as<float>();
+    uint32_t* status = (uint32_t*)(f + 3 * n);
+    return {f, f + n, f + 2 * n, status, status + n};
+}
+// P.lists (MFMA path): [nq_pad][kSelectChunk] hit lists {score bits, row}, the per-query counters behind them
+struct ListBlock { uint2* lists; uint32_t* counts; };
+static size_t list_bytes(uint32_t nq_pad) { return (size_t)nq_pad * kSelectChunk * 8 + (size_t)nq_pad * 4; }
+static ListBlock list_block(const Pending& P) {
+    return {P.lists.as<uint2>(), (uint32_t*)((char*)P.lists.p + (size_t)P.plan.nq_pad * kSelectChunk * 8)};
+}
+// the slot's pacing-counter and claim-bit regions of scan launch `launch` (kSlotFlagBytes: behind the 64 scalars)
+static uint32_t* pace_region(const Pending& P, uint32_t launch) { return P.flags + 64 + (launch % kPaceRegions) * kPaceWords; }
+static uint32_t* claim_region(const Pending& P, uint32_t launch) {
+    return P.flags + 64 + kPaceRegions * kPaceWords + (launch % kPaceRegions) * kClaimWords;
+}
+static const size_t kHistWords = 8 * 4096 + 8;   // stream path: [8][<=4096] bin counters + 8 key counters
+
+// ------------------------------------------------------------------ MFMA launches
+// Scan arguments of a block of `nq` queries (`nq_pad` rows of `queries`) over the corpus, appending to the slot's list block
+static int mfma_args(vrod_index* idx, Pending& P, MfmaScanArgs& a, const void* queries, const float* qn2, const float* thr,
+                     uint32_t nq, uint32_t nq_pad) {
+    const ListBlock L = list_block(P);
+    a = MfmaScanArgs{};
+    a.corpus = idx->corpus; a.queries = queries; a.xnorm2 = idx->xnorm2; a.qnorm2 = qn2; a.thr = thr;
+    a.lists = L.lists; a.counts = L.counts; a.cap = kSelectChunk; a.ld = idx->ld; a.nq_pad = nq_pad; a.nq = nq;
+    a.metric = score_form(idx->metric);
+    VROD_TRY(P.dump.ensure(mfma_dump_bytes(idx->num_cus)));
+    a.dump = P.dump.p;
+    return VROD_OK;
+}
+
+// Point `a` at the bf16 planes (SPLIT form of the kernels): the corpus's [hi_j | lo_j], and the [hi_j | lo_j | hi_j]
+// planes of the block's queries, made here into `q_planes` from their `nq_pad` prepared fp32 rows.
+static int use_split_planes(vrod_index* idx, MfmaScanArgs& a, const float* q_f32, uint32_t nq_pad, DevBuf& q_planes, hipStream_t s) {
+    VROD_TRY(q_planes.ensure((size_t)nq_pad * 3 * idx->ldp * 2));
+    launch_split_rows(q_f32, nq_pad, idx->ld, idx->ldp, q_planes.p, true, s);
+    a.corpus = idx->planes; a.queries = q_planes.p;
+    a.ld = 3 * idx->ldp;                          // K extent = query row
+    a.lda_bytes = 2 * idx->ldp * 2;               // corpus row [hi_j | lo_j] per K-tile
+    a.a_wrap = 1;                                 // SPLIT form of the kernel
+    return VROD_OK;
+}
+
+// Filtered launches of `a` over rows [lo, end).  A launch addresses rows relative to its first tile with 24 bits: the
+// range is cut at 2^24 rows.  Every launch takes the slot's next pacing / claim region (P.pace_launches); the search's
+// own launches (`fresh`) find the first kPaceRegions of them zeroed by the query preparation, later ones -- and every
+// launch of the band pass -- reuse a region behind a memset.  `tail`: the last launch is the search's last filtered
+// launch (Timer::arm_tail).
+static void launch_filtered(vrod_index* idx, Pending& P, Timer& tm, MfmaScanArgs& a, int scan_dtype, uint64_t lo, uint64_t end,
+                            bool fresh, bool tail) {
+    vrod_search_stats& st = P.st;
+    const double row_bytes_alg = (double)idx->ld * idx->esize;
+    while (lo < end) {
+        const uint64_t e = std::min<uint64_t>(end, lo / kRowTile * kRowTile + (1ull << 24));
+        a.row_begin = (uint32_t)lo; a.row_end = (uint32_t)e;
+        a.pace = pace_region(P, P.pace_launches);
+        a.pace_is_zero = fresh && P.pace_launches < kPaceRegions;
+        a.claims = claim_region(P, P.pace_launches);
+        a.claims_is_zero = a.pace_is_zero;
+        ++P.pace_launches;
+        size_t e0, e1;
+        tm.arm(e0, e1);
+        if (tail && e == end) tm.arm_tail();
+        launch_scan_mfma(a, scan_dtype, idx->num_cus, P.stream);
+        P.scan_pairs.push_back({e0, e1});
+        st.scan_launches++;
+        st.scan_bytes += (double)(e - lo / kRowTile * kRowTile) * row_bytes_alg;
+        st.scan_flops += 2.0 * a.nq * (double)(e - lo) * idx->dim;
+        lo = e;
     }
-    p.bounds.push_back(N);
-    return p;
 }
 
 // The event behind a search's last scan launch; a search that did not mark an earlier point (mid_done: behind the
@@ -528,6 +545,160 @@ static StagePlan plan_stages(uint64_t N, uint32_t kp, uint32_t cap, uint32_t max
 static int record_scans_done(Pending& P, hipStream_t s) {
     if (!P.mid_recorded) { HIP_TRY(hipEventRecord(P.mid_done, s)); P.mid_recorded = true; }
     HIP_TRY(hipEventRecord(P.scans_done, s));
+    return VROD_OK;
+}
+
+static Pending& other_slot(vrod_index* idx, Pending& P) { return idx->slot[&P == &idx->slot[0] ? 1 : 0]; }
+
+// The bf16 planes of an fp32 corpus are a second copy of it, allocated for the whole capacity: without room for them
+// the handle switches the split pass off and quietly keeps the fp32 pass.
+static bool planes_ready(vrod_index* idx) {
+    if (idx->planes_cap >= idx->capacity) return true;
+    if (idx->planes) { (void)hipFree(idx->planes); idx->planes = nullptr; idx->planes_cap = idx->planes_rows = 0; }
+    const size_t want = idx->capacity * 2ull * idx->ldp * 2ull;
+    bool room = true;
+    if (!idx->split_forced) {
+        // by default the planes must leave the caller a margin: 1/8 of the device or 4 GiB
+        size_t free_b = 0, total_b = 0;
+        room = hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b >= want + std::max<size_t>(total_b / 8, (size_t)4 << 30);
+    }
+    if (room && hipMalloc(&idx->planes, want) == hipSuccess) {
+        idx->planes_cap = idx->capacity;
+        return true;
+    }
+    (void)hipGetLastError();
+    idx->planes = nullptr;
+    idx->split_enabled = false;
+    return false;
+}
+
+// -------- fast pass A: HBM-bound scan of <= 8 queries at a time, all N fast scores kept, radix select (pass 1 fused
+// into the scan; its histogram block was cleared by the query preparation)
+static int stream_pass(vrod_index* idx, Pending& P, Timer& tm, bool in_graph) {
+    const uint64_t N = P.plan.N;
+    const uint32_t nq = P.nq, kp = P.plan.kp;
+    const int form = score_form(idx->metric);
+    const SmallBlock B = small_block(P);
+    vrod_search_stats& st = P.st;
+    hipStream_t s = P.stream;
+    const uint64_t score_ld = round_up(N, 64);
+    VROD_TRY(P.scores.ensure((size_t)8 * score_ld * 4));
+    VROD_TRY(P.keys_a.ensure((size_t)8 * kSelectChunk * 8));
+    uint32_t* d_hist = P.hist.as<uint32_t>();
+    uint32_t* d_cnt = d_hist + 8 * 4096;
+    // one HBM-bound scan at a time (two would only share the bandwidth and stretch each
+    // other); everything behind the scan overlaps the other slot's scan
+    if (!in_graph) HIP_TRY(hipStreamWaitEvent(s, other_slot(idx, P).scans_done, 0));
+    const double row_bytes_alg = (double)idx->ld * idx->esize;
+    const uint32_t qpp = (uint32_t)stream_max_queries_per_pass(idx->ld);   // queries per pass: 8, fewer for long rows
+    for (uint32_t q0 = 0; q0 < nq; q0 += qpp) {
+        const int nqc = (int)std::min<uint32_t>(qpp, nq - q0);
+        int nqp = 1;
+        while (nqp < nqc) nqp <<= 1;
+        if (q0 > 0) HIP_TRY(hipMemsetAsync(d_hist, 0, kHistWords * 4, s));
+        size_t a, b;
+        tm.arm(a, b);
+        launch_scan_stream(idx->corpus, idx->dtype, form, idx->ld, N, P.q_f32.as<float>() + (size_t)q0 * idx->ld, nqp,
+                           P.scores.as<float>(), score_ld, d_hist, kp, s);
+        P.scan_pairs.push_back({a, b});
+        if (q0 + qpp >= nq && !in_graph) VROD_TRY(record_scans_done(P, s));
+        st.scan_launches++;
+        st.scan_bytes += (double)N * row_bytes_alg;
+        st.scan_flops += 2.0 * nqc * (double)N * idx->dim;
+        launch_hist_compact(P.scores.as<float>(), score_ld, N, nqc, form, d_hist, stream_hist_bits(nqp), kp,
+                            P.keys_a.as<uint64_t>(), kSelectChunk, d_cnt, B.status + q0, s);
+        launch_keys_to_candidates(P.keys_a.as<uint64_t>(), kSelectChunk, kSelectChunk, nqc, form, kp,
+                                  P.cand_rows.as<uint32_t>() + (size_t)q0 * kp, P.cand_fast.as<float>() + (size_t)q0 * kp,
+                                  B.T + q0, d_cnt, s);
+    }
+    HIP_TRY(hipGetLastError());
+    return VROD_OK;
+}
+
+// -------- fast pass B: batched MFMA scan.  (1) dense sample pass over the first S rows, (2) exact j-th best per query =
+// threshold, (3) filtered launches over the stages of plan_stages, (4) after each stage keep the best k' of every list.
+static int mfma_pass(vrod_index* idx, Pending& P, Timer& tm, const void* q_lp) {
+    const SearchPlan& plan = P.plan;
+    const uint64_t N = plan.N;
+    const uint32_t nq = P.nq, kp = plan.kp, cap = kSelectChunk;
+    const int form = score_form(idx->metric);
+    const SmallBlock B = small_block(P);
+    const ListBlock L = list_block(P);
+    vrod_search_stats& st = P.st;
+    hipStream_t s = P.stream;
+    // The MFMA scans own the whole chip.  Two orders of the two searches in flight:
+    //  late : the sample pass behind the other slot's last scan, the first filtered stage behind its read-back --
+    //         the other search's tail (compaction, re-score, certificate, read-back) and this one's sample + select
+    //         side by side, ~95 us per batch in which nothing else runs (profiles/r02/s_pipeline_timeline_shard.txt);
+    //  early: the sample pass + select (~50 us) in front of the other slot's LAST stage (behind its second-to-last:
+    //         mid_done), the first filtered stage behind that last stage: it starts the moment the other search's
+    //         scans are through and runs beside that search's tail.
+    // Same box, batch 1024 x 768 bf16, early against late: 1.25M rows 1.84-1.85 / 1.87 ms, 2.5M 3.52 / 3.56-3.58,
+    // 5M 6.76 / 6.83, 10M 13.28-13.32 / 13.40-13.41 (-1.4 / -1.5 / -1.0 / -0.7 %).  Early is taken up to 6M rows per
+    // handle: beyond, the gain is under 1 % and the sample pass squeezed beside a 7-ms stage makes that stage's own
+    // launch time (what bench.py's roofline divides by) unreadable.  VROD_DEBUG_EARLY_SAMPLE=0 / 1 forces late / early.
+    const int early_env = debug_env().early_sample;
+    const bool early = early_env >= 0 ? early_env == 1 : N <= 6000000ull;
+    Pending& O = other_slot(idx, P);
+    HIP_TRY(hipStreamWaitEvent(s, early ? O.mid_done : O.scans_done, 0));
+    MfmaScanArgs a;
+    VROD_TRY(mfma_args(idx, P, a, idx->dtype == VROD_DTYPE_BF16 ? q_lp : P.q_f32.p, B.qn2, B.thr, nq, plan.nq_pad));
+    if (plan.split) {
+        // planes of the rows added since the last batched search, and of this batch's queries
+        if (idx->planes_rows < N) {
+            launch_split_rows((const float*)idx->corpus + idx->planes_rows * idx->ld, N - idx->planes_rows, idx->ld, idx->ldp,
+                              (char*)idx->planes + idx->planes_rows * 2ull * idx->ldp * 2ull, false, s);
+            if (round_up(N, kRowTile) > N)   // the tile padding rows stay zero
+                HIP_TRY(hipMemsetAsync((char*)idx->planes + N * 2ull * idx->ldp * 2ull, 0, (round_up(N, kRowTile) - N) * 2ull * idx->ldp * 2ull, s));
+            idx->planes_rows = N;
+        }
+        VROD_TRY(use_split_planes(idx, a, P.q_f32.as<float>(), plan.nq_pad, P.q_planes, s));
+    }
+    const int scan_dtype = plan.split ? VROD_DTYPE_BF16 : idx->dtype;
+    P.pace_launches = 0;
+    std::vector<uint64_t> bounds{N};
+    if (N > cap) {
+        const uint32_t nqb = plan.nq_pad / 256;
+        const StagePlan sp = plan_stages(N, kp, cap, std::max<uint32_t>(1, (uint32_t)idx->num_cus / nqb) * kRowTile,
+                                         debug_env().stage_growth, debug_env().sample_rows);
+        bounds = sp.bounds;
+        MfmaScanArgs d = a;
+        d.row_begin = 0; d.row_end = sp.S;
+        // Grouped form where the kernel has it: the threshold is the j-th best of the per-group bests (groups of 32
+        // rows: valid -- at least j rows are that good -- and exact unless two of the j best share a group), 1/32 of
+        // the dense block to write and to select from.  Only while the groups outnumber j by 8x (else: every score).
+        const bool group_env = debug_env().sample_grouped;
+        const uint32_t grows = group_env ? mfma_dense_group_rows(d, scan_dtype) : 0u;
+        const uint32_t n_groups = grows ? (uint32_t)(round_up(sp.S, kRowTile) / grows) : 0u;
+        const bool grouped = grows && (uint64_t)sp.j * 8 <= n_groups && sp.S % kRowTile == 0;   // whole tiles of real rows
+        const uint32_t dense_ld = grouped ? (uint32_t)round_up(n_groups, 64) : (uint32_t)round_up(sp.S, kRowTile);
+        const uint32_t n_sel = grouped ? n_groups : sp.S;
+        VROD_TRY(P.scores.ensure((size_t)plan.nq_pad * dense_ld * 4));
+        d.dense_out = P.scores.as<float>(); d.dense_ld = dense_ld; d.dense_grouped = grouped;
+        d.pace = pace_region(P, P.pace_launches++); d.pace_is_zero = true;
+        size_t e0, e1;
+        tm.arm(e0, e1);
+        launch_scan_mfma(d, scan_dtype, idx->num_cus, s);
+        P.sample_pair = (int)P.scan_pairs.size();
+        P.early_sample = early;
+        P.scan_pairs.push_back({e0, e1});
+        st.scan_launches++;
+        // (the sample rows are scanned again by the first filtered stage: their time counts, their flops and
+        // bytes do not -- algorithmic work is 2 * nq * N * d and N * row bytes, each row once)
+        launch_sample_select(P.scores.as<float>(), dense_ld, n_sel, (int)nq, form, sp.j, B.thr, s);
+    }
+    HIP_TRY(hipStreamWaitEvent(s, early ? O.scans_done : O.done, 0));
+    uint64_t lo = 0;
+    for (size_t li = 0; li < bounds.size(); ++li) {
+        const bool last = li + 1 == bounds.size();
+        launch_filtered(idx, P, tm, a, scan_dtype, lo, bounds[li], true, last);
+        lo = std::max(lo, bounds[li]);
+        if (li + 2 == bounds.size()) { HIP_TRY(hipEventRecord(P.mid_done, s)); P.mid_recorded = true; }
+        if (last) VROD_TRY(record_scans_done(P, s));
+        launch_list_compact(L.lists, L.counts, cap, (int)nq, form, kp, B.thr, B.status, last ? P.cand_rows.as<uint32_t>() : nullptr,
+                            last ? P.cand_fast.as<float>() : nullptr, last ? B.T : nullptr, s);
+    }
+    HIP_TRY(hipGetLastError());
     return VROD_OK;
 }
 
@@ -550,70 +721,17 @@ static int search_enqueue_body(vrod_index* idx, Pending& P, const float* d_queri
     Timer tm(idx, P);
     P.t0 = tm.mark();
 
+    // ---- plan (search_plan.h)
     const uint64_t N = idx->count;
-    uint32_t kp = choose_kp(N, k);
-
-    // ---- path
-    int path = idx->path;
-    // AUTO routing, measured on MI355X at 2M x 768 (scripts/route_probe.py): the stream scan costs
-    // about one HBM pass per 8 queries (bf16: 0.63 / 0.69 / 2.0 ms at 1 / 4 / 8 queries, fp32:
-    // 1.09 / 1.21 / 1.47 / 2.85 ms at 1 / 4 / 8 / 16); an MFMA batch costs the same for any
-    // nq <= 256 (bf16 0.85 ms, fp32 5.97 ms: the fp32 MFMA rate is 16x lower).
-    // (opt-in split pass over an fp32 corpus: ~1.5 HBM passes + 3 bf16 MFMA products, cheaper
-    // than the stream scan from ~12 queries on)
-    const bool can_split = idx->split_enabled && idx->dtype == VROD_DTYPE_F32 && N > 0 &&
-                           (uint64_t)k + std::max<uint32_t>(32, k / 2) <= kSelectChunk / 2;
-    // (5-32 queries over the planes take the skinny form where the queries' [hi | lo] fit in LDS: one HBM pass
-    // over the planes, 1.30 ms at 2M x 768 against 1.34-1.36 for a stream pass of 5-8 queries and 1.85 tiled)
-    const bool skinny_split = can_split && nq <= mfma_skinny_max_queries(true, 2u * idx->ldp * 2u);
-    if (path == VROD_PATH_AUTO)
-        path = nq <= (idx->dtype == VROD_DTYPE_BF16 ? 4u : skinny_split ? 4u : can_split ? 12u : 32u) ? VROD_PATH_STREAM : VROD_PATH_MFMA;
-    bool split = can_split && path == VROD_PATH_MFMA;
-    if (split && idx->planes_cap < idx->capacity) {
-        // the planes are a second copy of the corpus: without room for them the handle quietly
-        // keeps the fp32 pass
-        if (idx->planes) { (void)hipFree(idx->planes); idx->planes = nullptr; idx->planes_cap = idx->planes_rows = 0; }
-        const size_t want = idx->capacity * 2ull * idx->ldp * 2ull;
-        bool room = true;
-        if (!idx->split_forced) {
-            // by default the planes must leave the caller a margin: 1/8 of the device or 4 GiB
-            size_t free_b = 0, total_b = 0;
-            room = hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b >= want + std::max<size_t>(total_b / 8, (size_t)4 << 30);
-        }
-        if (room && hipMalloc(&idx->planes, want) == hipSuccess) {
-            idx->planes_cap = idx->capacity;
-        } else {
-            (void)hipGetLastError();
-            idx->planes = nullptr;
-            idx->split_enabled = false;
-            split = false;
-        }
-    }
-    P.split = split;
-    if (split) {
-        // the split pass's certificate bound is ~3x the fp32 MFMA pass's: more candidates per query
-        kp = (uint32_t)std::min<uint64_t>(N, (uint64_t)k + std::max<uint32_t>(32, k / 2));
-    } else if (path == VROD_PATH_MFMA && score_form(idx->metric) == M_COSINE) {
-        // Every stage of the batched scan appends ~k' (g - 1) rows per query, and a hit costs its work-group
-        // ~0.35 us (profiles/r02/mfma_experiments.md): fewer candidates, fewer hits.  The margin only has to keep
-        // the k-th canonical score clear of the k'-th fast score by the error bound (1.8e-4 at d = 768 against
-        // ~8e-4 per rank at 10M rows); margins 16 / 10 / 6 / 4 / 2 gave 0 / 0 / 0 / 11 / 937 failed certificates in
-        // 30 720 queries and 12.58-12.65 / 12.53 / 12.51 / 13.27 / 15.44 ms per batch (1.25M-row shard: 1.82 / - /
-        // 1.75 / 1.80 ms); a failed certificate costs a band pass, not a wrong result.  (The L2 bound through the
-        // norm expansion is ~4x wider relative to the gaps: it keeps 16.  IP takes this branch: its bound is the same
-        // dot-form bound, scaled by the real norms as its gaps are: rows with norms spread by exp(U(-1, 1)) failed no
-        // certificate at 2M x 768, profiles/ip/.)
-        const uint32_t margin_env = debug_env().kp_margin;
-        kp = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(N, kSelectChunk / 2), (uint64_t)k + (uint64_t)std::max<uint32_t>(margin_env ? margin_env : 8, k / 8) * idx->kp_boost);
-    } else if (path == VROD_PATH_MFMA) {
-        kp = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(N, kSelectChunk / 2), (uint64_t)k + (uint64_t)std::max<uint32_t>(16, k / 8) * idx->kp_boost);
-    }
-    st.kprime = kp;
-    P.kp_boost_used = idx->kp_boost;
-    P.N = N; P.kp = kp;
-    st.path = path;
-    st.split_pass = split ? 1u : 0u;
-    P.path = path;
+    const int form = score_form(idx->metric);
+    Route r = route(idx->path, idx->dtype, idx->split_enabled, mfma_skinny_max_queries(true, 2u * idx->ldp * 2u), N, nq, k);
+    if (r.split && !planes_ready(idx)) r.split = false;
+    P.plan = make_plan(r.path, r.split, form, idx->dim, N, nq, k, idx->kp_boost.boost, debug_env().kp_margin);
+    const SearchPlan& plan = P.plan;
+    P.kp_boost_used = idx->kp_boost.boost;
+    st.kprime = plan.kp;
+    st.path = plan.path;
+    st.split_pass = plan.split ? 1u : 0u;
 
     if (N == 0) {  // empty corpus: every slot unfilled
         std::vector<uint64_t> hi((size_t)nq * k, UINT64_MAX);
@@ -627,8 +745,8 @@ static int search_enqueue_body(vrod_index* idx, Pending& P, const float* d_queri
     // ---- prepare queries (one launch): q_f32 [nq_pad][ld] fp32 (zero padded), q_lp bf16 copy,
     // fast norms, NaN/Inf flag, max |q|^2.  No host round trip: the certificate forms its bound
     // on the device and the flag is read with the results.
-    const uint32_t nq_pad = (uint32_t)round_up(nq, path == VROD_PATH_MFMA ? 256 : 8);
-    P.nq_pad = nq_pad;
+    const uint32_t nq_pad = plan.nq_pad;
+    const bool mfma = plan.path == VROD_PATH_MFMA;
     P.trivial = false;
     if (!P.done) HIP_TRY(hipEventCreateWithFlags(&P.done, hipEventDisableTiming));
     VROD_TRY(P.q_f32.ensure((size_t)nq_pad * idx->ld * 4));
@@ -637,12 +755,7 @@ static int search_enqueue_body(vrod_index* idx, Pending& P, const float* d_queri
         VROD_TRY(P.q_lp.ensure((size_t)nq_pad * idx->ld * 2));
         q_lp = P.q_lp.p;
     }
-    VROD_TRY(P.small.ensure((size_t)nq_pad * 4 * 5 + 64));  // qnorm2 | T | thr | status | readback
-    float* d_qn2 = P.small.as<float>();
-    float* d_T = d_qn2 + nq_pad;
-    float* d_thr = d_T + nq_pad;
-    uint32_t* d_status = (uint32_t*)(d_thr + nq_pad);
-    uint32_t* d_readback = d_status + nq_pad;   // [nq + 4]
+    VROD_TRY(P.small.ensure(small_bytes(nq_pad)));
     if (P.h_readback_words < (size_t)nq + 4) {
         if (P.h_readback) (void)hipHostFree(P.h_readback);
         P.h_readback = nullptr;
@@ -650,227 +763,52 @@ static int search_enqueue_body(vrod_index* idx, Pending& P, const float* d_queri
         HIP_TRY(hipHostMalloc((void**)&P.h_readback, ((size_t)nq + 4 + 1024) * 4, hipHostMallocDefault));
         P.h_readback_words = (size_t)nq + 4 + 1024;
     }
-    // the MFMA path's per-query list counters / thresholds live behind the lists; they are reset
-    // by the same launch that prepares the queries (padding queries get the BEST score as
-    // threshold so that they never append)
-    const bool mfma = path == VROD_PATH_MFMA;
-    const uint32_t cap = kSelectChunk;
-    uint2* d_lists = nullptr;
-    uint32_t* d_counts = nullptr;
-    if (mfma) {
-        VROD_TRY(P.lists.ensure((size_t)nq_pad * cap * 8 + (size_t)nq_pad * 4));
-        d_lists = P.lists.as<uint2>();
-        d_counts = (uint32_t*)((char*)P.lists.p + (size_t)nq_pad * cap * 8);
-    }
-    const uint32_t worst_bits = score_form(idx->metric) == M_COSINE ? 0xFF800000u : 0x7F800000u;  // -inf / +inf
+    if (mfma) VROD_TRY(P.lists.ensure(list_bytes(nq_pad)));
+    const SmallBlock B = small_block(P);
+    // the MFMA path's per-query list counters / thresholds are reset by the same launch that prepares the queries
+    // (padding queries get the BEST score as threshold so that they never append)
+    const uint32_t worst_bits = form == M_COSINE ? 0xFF800000u : 0x7F800000u;  // -inf / +inf
     QueryInit qi{};
-    qi.status = d_status;
-    qi.counts = d_counts;
-    qi.thr = mfma ? d_thr : nullptr;
+    qi.status = B.status;
+    qi.counts = mfma ? list_block(P).counts : nullptr;
+    qi.thr = mfma ? B.thr : nullptr;
     qi.thr_live_bits = worst_bits;
     qi.thr_pad_bits = worst_bits ^ 0x80000000u;
     // (flags[0..2] -- bad-value flag, max |q|^2 bits, max err bits -- are zero here: cleared by the
     // read-back launch of the slot's previous search, never by the launch that accumulates into them)
     qi.zero_words = nullptr;
     qi.n_zero_words = 0;
-    // pacing counters: 8 regions of 192 words behind the scalars, one per scan launch of this search
-    // and behind them the claim bits of the 4-wave kernel's work stealing, one region per scan launch likewise: both are
-    // zeroed by the launch that prepares the queries (no memset node per scan launch)
-    uint32_t* pace_base = P.flags + 64;
-    uint32_t* claim_base = pace_base + kPaceRegions * kPaceWords;
-    qi.zero_words2 = mfma ? pace_base : nullptr;
+    // MFMA path: the pacing-counter and claim-bit regions of the first kPaceRegions scan launches (stream path: the
+    // histogram block of the first pass of 8 queries) are zeroed by the launch that prepares the queries
+    qi.zero_words2 = mfma ? pace_region(P, 0) : nullptr;
     qi.n_zero_words2 = kPaceRegions * (kPaceWords + kClaimWords);
-    const size_t hist_words = 8 * 4096 + 8;   // stream path: [8][<=4096] bin counters + 8 key counters
-    if (path == VROD_PATH_STREAM) {
-        VROD_TRY(P.hist.ensure(hist_words * 4));
-        qi.zero_words2 = P.hist.as<uint32_t>();   // first pass of 8 queries: cleared by the prep launch
-        qi.n_zero_words2 = (uint32_t)hist_words;
+    if (plan.path == VROD_PATH_STREAM) {
+        VROD_TRY(P.hist.ensure(kHistWords * 4));
+        qi.zero_words2 = P.hist.as<uint32_t>();
+        qi.n_zero_words2 = (uint32_t)kHistWords;
     }
-    uint32_t pace_launch = 0;
     launch_prep_queries(d_queries_raw, nq, nq_pad, idx->dim, idx->ld, prep_form(idx->metric), idx->dtype, P.q_f32.as<float>(),
-                        q_lp, d_qn2, &P.flags[0], &P.flags[1], qi, s);
+                        q_lp, B.qn2, &P.flags[0], &P.flags[1], qi, s);
     HIP_TRY(hipGetLastError());
 
-    const float u = 5.9604645e-8f;  // 2^-24
-    int eps_mode = 0;
-    float eps_c = 0.f;
+    // ---- fast pass: k' candidates per query + T
+    VROD_TRY(P.cand_rows.ensure((size_t)nq * plan.kp * 4));
+    VROD_TRY(P.cand_fast.ensure((size_t)nq * plan.kp * 4));
+    VROD_TRY(P.cand_canon.ensure((size_t)nq * plan.kp * 4));
+    if (plan.path == VROD_PATH_STREAM) VROD_TRY(stream_pass(idx, P, tm, in_graph));
+    else if (mfma) VROD_TRY(mfma_pass(idx, P, tm, q_lp));
 
-    VROD_TRY(P.cand_rows.ensure((size_t)nq * kp * 4));
-    VROD_TRY(P.cand_fast.ensure((size_t)nq * kp * 4));
-    VROD_TRY(P.cand_canon.ensure((size_t)nq * kp * 4));
-
-    const double row_bytes_alg = (double)idx->ld * idx->esize;
-
-    if (path == VROD_PATH_STREAM) {
-        // -------- fast pass A: HBM-bound scan of <= 8 queries at a time, all N fast scores kept
-        // (dot form, COSINE and IP: |fast - canonical| <= eps_c * |q| * max|x| with the batch's largest query norm and
-        // the corpus's largest row norm -- final_topk_kernel reads both on the device; unit norms only for COSINE)
-        if (score_form(idx->metric) == M_COSINE) { eps_mode = 0; eps_c = 4.f * idx->dim * u; }
-        else { eps_mode = 1; eps_c = 4.f * (idx->dim + 2) * u; }
-        const uint64_t score_ld = round_up(N, 64);
-        VROD_TRY(P.scores.ensure((size_t)8 * score_ld * 4));
-        // radix select, pass 1 fused into the scan (histogram buffer prepared above)
-        VROD_TRY(P.keys_a.ensure((size_t)8 * kSelectChunk * 8));
-        uint32_t* d_hist = P.hist.as<uint32_t>();
-        uint32_t* d_cnt = d_hist + 8 * 4096;
-        // one HBM-bound scan at a time (two would only share the bandwidth and stretch each
-        // other); everything behind the scan overlaps the other slot's scan
-        if (!in_graph) {
-            Pending& O = idx->slot[&P == &idx->slot[0] ? 1 : 0];
-            HIP_TRY(hipStreamWaitEvent(s, O.scans_done, 0));
-        }
-        const uint32_t qpp = (uint32_t)stream_max_queries_per_pass(idx->ld);   // queries per pass: 8, fewer for long rows
-        for (uint32_t q0 = 0; q0 < nq; q0 += qpp) {
-            const int nqc = (int)std::min<uint32_t>(qpp, nq - q0);
-            int nqp = 1;
-            while (nqp < nqc) nqp <<= 1;
-            if (q0 > 0) HIP_TRY(hipMemsetAsync(d_hist, 0, hist_words * 4, s));
-            size_t a, b;
-            tm.arm(a, b);
-            launch_scan_stream(idx->corpus, idx->dtype, score_form(idx->metric), idx->ld, N,
-                               P.q_f32.as<float>() + (size_t)q0 * idx->ld, nqp, P.scores.as<float>(), score_ld,
-                               d_hist, kp, s);
-            P.scan_pairs.push_back({a, b});
-            if (q0 + qpp >= nq && !in_graph) VROD_TRY(record_scans_done(P, s));
-            st.scan_launches++;
-            st.scan_bytes += (double)N * row_bytes_alg;
-            st.scan_flops += 2.0 * nqc * (double)N * idx->dim;
-            launch_hist_compact(P.scores.as<float>(), score_ld, N, nqc, score_form(idx->metric), d_hist, stream_hist_bits(nqp), kp,
-                                P.keys_a.as<uint64_t>(), kSelectChunk, d_cnt, d_status + q0, s);
-            launch_keys_to_candidates(P.keys_a.as<uint64_t>(), kSelectChunk, kSelectChunk, nqc, score_form(idx->metric), kp,
-                                      P.cand_rows.as<uint32_t>() + (size_t)q0 * kp, P.cand_fast.as<float>() + (size_t)q0 * kp,
-                                      d_T + q0, d_cnt, s);
-        }
-        HIP_TRY(hipGetLastError());
-    } else if (path == VROD_PATH_MFMA) {
-        // -------- fast pass B: batched MFMA scan.  (1) dense sample pass over the first S rows,
-        // (2) exact j-th best per query = threshold, (3) ONE filtered launch over all rows,
-        // (4) keep the best k' of every list.
-        if (score_form(idx->metric) == M_COSINE) { eps_mode = 0; eps_c = 4.f * idx->dim * u; }
-        else { eps_mode = 2; eps_c = 4.f * (idx->dim + 4) * u; }
-        if (split) {
-            // |fast - exact dot|: representation (x = hi + lo + r, |r| <= 2^-16 |x|, the lo.lo term
-            // dropped) <= 3.1 * 2^-16 |q||x|; fp32 accumulation of 3*dim exact bf16 products in any
-            // order <= 4.1 * 3*dim * 2^-24 |q||x|.  (L2 = |q|^2 + |x|^2 - 2 q.x on the same dot.)
-            const float repr = 3.1f * 1.52587890625e-5f;
-            if (score_form(idx->metric) == M_COSINE) eps_c = 4.1f * 3.f * idx->dim * u + repr;
-            else eps_c = 4.1f * (3.f * idx->dim + 4) * u + repr;
-        }
-        // The MFMA scans own the whole chip.  Two orders of the two searches in flight:
-        //  late : the sample pass behind the other slot's last scan, the first filtered stage behind its read-back --
-        //         the other search's tail (compaction, re-score, certificate, read-back) and this one's sample + select
-        //         side by side, ~95 us per batch in which nothing else runs (profiles/r02/s_pipeline_timeline_shard.txt);
-        //  early: the sample pass + select (~50 us) in front of the other slot's LAST stage (behind its second-to-last:
-        //         mid_done), the first filtered stage behind that last stage: it starts the moment the other search's
-        //         scans are through and runs beside that search's tail.
-        // Same box, batch 1024 x 768 bf16, early against late: 1.25M rows 1.84-1.85 / 1.87 ms, 2.5M 3.52 / 3.56-3.58,
-        // 5M 6.76 / 6.83, 10M 13.28-13.32 / 13.40-13.41 (-1.4 / -1.5 / -1.0 / -0.7 %).  Early is taken up to 6M rows per
-        // handle: beyond, the gain is under 1 % and the sample pass squeezed beside a 7-ms stage makes that stage's own
-        // launch time (what bench.py's roofline divides by) unreadable.  VROD_DEBUG_EARLY_SAMPLE=0 / 1 forces late / early.
-        const int early_env = debug_env().early_sample;
-        const bool early = early_env >= 0 ? early_env == 1 : N <= 6000000ull;
-        Pending& O = idx->slot[&P == &idx->slot[0] ? 1 : 0];
-        HIP_TRY(hipStreamWaitEvent(s, early ? O.mid_done : O.scans_done, 0));
-        const void* qmat = idx->dtype == VROD_DTYPE_BF16 ? q_lp : P.q_f32.p;
-        MfmaScanArgs a{};
-        a.corpus = idx->corpus; a.queries = qmat; a.xnorm2 = idx->xnorm2; a.qnorm2 = d_qn2; a.thr = d_thr;
-        a.lists = d_lists; a.counts = d_counts; a.cap = cap; a.ld = idx->ld; a.nq_pad = nq_pad; a.nq = nq; a.metric = score_form(idx->metric);
-        VROD_TRY(P.dump.ensure(mfma_dump_bytes(idx->num_cus)));
-        a.dump = P.dump.p;
-        int scan_dtype = idx->dtype;
-        if (split) {
-            // planes of the rows added since the last batched search, and of this batch's queries
-            if (idx->planes_rows < N) {
-                launch_split_rows((const float*)idx->corpus + idx->planes_rows * idx->ld, N - idx->planes_rows, idx->ld, idx->ldp,
-                                  (char*)idx->planes + idx->planes_rows * 2ull * idx->ldp * 2ull, false, s);
-                if (round_up(N, kRowTile) > N)   // the tile padding rows stay zero
-                    HIP_TRY(hipMemsetAsync((char*)idx->planes + N * 2ull * idx->ldp * 2ull, 0, (round_up(N, kRowTile) - N) * 2ull * idx->ldp * 2ull, s));
-                idx->planes_rows = N;
-            }
-            VROD_TRY(P.q_planes.ensure((size_t)nq_pad * 3 * idx->ldp * 2));
-            launch_split_rows(P.q_f32.as<float>(), nq_pad, idx->ld, idx->ldp, P.q_planes.p, true, s);
-            a.corpus = idx->planes; a.queries = P.q_planes.p;
-            a.ld = 3 * idx->ldp;                          // K extent = query row
-            a.lda_bytes = 2 * idx->ldp * 2;               // corpus row [hi_j | lo_j] per K-tile
-            a.a_wrap = 1;                                 // SPLIT form of the kernel
-            scan_dtype = VROD_DTYPE_BF16;
-        }
-        std::vector<uint64_t> bounds{N};
-        if (N > cap) {
-            const uint32_t nqb = nq_pad / 256;
-            const StagePlan sp = plan_stages(N, kp, cap, std::max<uint32_t>(1, (uint32_t)idx->num_cus / nqb) * kRowTile);
-            bounds = sp.bounds;
-            MfmaScanArgs d = a;
-            d.row_begin = 0; d.row_end = sp.S;
-            // Grouped form where the kernel has it: the threshold is the j-th best of the per-group bests (groups of 32
-            // rows: valid -- at least j rows are that good -- and exact unless two of the j best share a group), 1/32 of
-            // the dense block to write and to select from.  Only while the groups outnumber j by 8x (else: every score).
-            const bool group_env = debug_env().sample_grouped;
-            const uint32_t grows = group_env ? mfma_dense_group_rows(d, scan_dtype) : 0u;
-            const uint32_t n_groups = grows ? (uint32_t)(round_up(sp.S, kRowTile) / grows) : 0u;
-            const bool grouped = grows && (uint64_t)sp.j * 8 <= n_groups && sp.S % kRowTile == 0;   // whole tiles of real rows
-            const uint32_t dense_ld = grouped ? (uint32_t)round_up(n_groups, 64) : (uint32_t)round_up(sp.S, kRowTile);
-            const uint32_t n_sel = grouped ? n_groups : sp.S;
-            VROD_TRY(P.scores.ensure((size_t)nq_pad * dense_ld * 4));
-            d.dense_out = P.scores.as<float>(); d.dense_ld = dense_ld; d.dense_grouped = grouped;
-            d.pace = pace_base; d.pace_is_zero = true; ++pace_launch;
-            size_t e0, e1;
-            tm.arm(e0, e1);
-            launch_scan_mfma(d, scan_dtype, idx->num_cus, s);
-            P.sample_pair = (int)P.scan_pairs.size();
-            P.early_sample = early;
-            P.scan_pairs.push_back({e0, e1});
-            st.scan_launches++;
-            // (the sample rows are scanned again by the first filtered stage: their time counts, their flops and
-            // bytes do not -- algorithmic work is 2 * nq * N * d and N * row bytes, each row once)
-            launch_sample_select(P.scores.as<float>(), dense_ld, n_sel, (int)nq, score_form(idx->metric), sp.j, d_thr, s);
-        }
-        HIP_TRY(hipStreamWaitEvent(s, early ? O.scans_done : O.done, 0));
-        uint64_t lo = 0;
-        for (size_t li = 0; li < bounds.size(); ++li) {
-            while (lo < bounds[li]) {
-                // a launch addresses rows relative to its first tile with 24 bits
-                const uint64_t end = std::min<uint64_t>(bounds[li], lo / kRowTile * kRowTile + (1ull << 24));
-                a.row_begin = (uint32_t)lo; a.row_end = (uint32_t)end;
-                a.pace = pace_base + (pace_launch % kPaceRegions) * kPaceWords;
-                a.pace_is_zero = pace_launch < kPaceRegions;   // later launches reuse a region: memset
-                a.claims = claim_base + (pace_launch % kPaceRegions) * kClaimWords;
-                a.claims_is_zero = a.pace_is_zero;
-                ++pace_launch;
-                size_t e0, e1;
-                tm.arm(e0, e1);
-                if (li + 1 == bounds.size() && end == bounds[li]) tm.arm_tail();
-                launch_scan_mfma(a, scan_dtype, idx->num_cus, s);
-                P.scan_pairs.push_back({e0, e1});
-                st.scan_launches++;
-                st.scan_bytes += (double)(end - lo / kRowTile * kRowTile) * row_bytes_alg;
-                st.scan_flops += 2.0 * nq * (double)(end - lo) * idx->dim;
-                lo = end;
-            }
-            const bool last = li + 1 == bounds.size();
-            if (li + 2 == bounds.size()) { HIP_TRY(hipEventRecord(P.mid_done, s)); P.mid_recorded = true; }
-            if (last) VROD_TRY(record_scans_done(P, s));
-            launch_list_compact(d_lists, d_counts, cap, (int)nq, score_form(idx->metric), kp, d_thr, d_status,
-                                last ? P.cand_rows.as<uint32_t>() : nullptr, last ? P.cand_fast.as<float>() : nullptr,
-                                last ? d_T : nullptr, s);
-        }
-        HIP_TRY(hipGetLastError());
-        P.pace_launches = pace_launch;
-    }
-
-    P.eps_mode = eps_mode;
-    P.eps_c = eps_c;
-    if (path != VROD_PATH_EXACT) {
+    if (plan.path != VROD_PATH_EXACT) {
         // -------- canonical re-score + final ordering + certificate
-        launch_rescore_candidates(idx->corpus, idx->dtype, score_form(idx->metric), idx->dim, idx->ld, P.q_f32.as<float>(), (int)nq,
-                                  P.cand_rows.as<uint32_t>(), kp, P.cand_canon.as<float>(), s);
-        launch_final_topk(P.cand_rows.as<uint32_t>(), P.cand_fast.as<float>(), P.cand_canon.as<float>(), d_T, (int)nq, kp, k,
-                          score_form(idx->metric), idmap_of(idx), eps_mode, eps_c, &P.flags[1], idx->max_xn2_bits, d_out_ids, d_out_scores,
-                          d_status, (float*)&P.flags[2], s);
+        launch_rescore_candidates(idx->corpus, idx->dtype, form, idx->dim, idx->ld, P.q_f32.as<float>(), (int)nq,
+                                  P.cand_rows.as<uint32_t>(), plan.kp, P.cand_canon.as<float>(), s);
+        launch_final_topk(P.cand_rows.as<uint32_t>(), P.cand_fast.as<float>(), P.cand_canon.as<float>(), B.T, (int)nq, plan.kp, k,
+                          form, idmap_of(idx), plan.eps_mode, plan.eps_c, &P.flags[1], idx->max_xn2_bits, d_out_ids, d_out_scores,
+                          B.status, (float*)&P.flags[2], s);
     }
-    launch_gather_readback(d_status, nq, P.flags, idx->max_xn2_bits, d_readback, s);
+    launch_gather_readback(B.status, nq, P.flags, idx->max_xn2_bits, B.readback, s);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(P.h_readback, d_readback, ((size_t)nq + 4) * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(P.h_readback, B.readback, ((size_t)nq + 4) * 4, hipMemcpyDeviceToHost, s));
     P.t1 = tm.mark();
     if (!in_graph) HIP_TRY(hipEventRecord(P.done, s));
     return VROD_OK;
@@ -886,13 +824,11 @@ static int search_enqueue(vrod_index* idx, Pending& P, const float* d_queries_ra
                           uint64_t* d_out_ids, float* d_out_scores) {
     const bool graphs_on = debug_env().graph;
     const uint64_t N = idx->count;
-    int path = idx->path;
-    if (path == VROD_PATH_AUTO && nq <= 4) path = VROD_PATH_STREAM;
     // (measured at 10k x 128, one query: a replay costs the HOST less -- 50 vs 65 us per search with two
     // in flight -- but is no faster end to end than plain launches, 91 vs 82 us synchronous: only
     // searches begun while another one is pending, i.e. host-bound pipelines, take it)
     const bool graphable = graphs_on && !P.graph_off && idx->profiling == 0 && nq >= 1 && nq <= 8 && N > 0 && idx->n_pending() >= 1 &&
-                           path == VROD_PATH_STREAM && (double)N * idx->ld * idx->esize <= 64.0 * 1048576.0;
+                           graph_route(idx->path, nq) && (double)N * idx->ld * idx->esize <= 64.0 * 1048576.0;
     Pending::GraphKey key{};
     if (graphable) {
         key.q = d_queries_raw; key.oi = d_out_ids; key.os = d_out_scores; key.corpus = idx->corpus; key.xn = idx->xnorm2;
@@ -901,14 +837,14 @@ static int search_enqueue(vrod_index* idx, Pending& P, const float* d_queries_ra
         memcpy(key.bufs, bufs, sizeof bufs);
         key.N = N; key.id_offset = idmap_of(idx).offset; key.nq = nq; key.k = k; key.path = idx->path;
     }
-    Pending& O = idx->slot[&P == &idx->slot[0] ? 1 : 0];
+    Pending& O = other_slot(idx, P);
     hipStream_t s = P.stream;
     if (graphable && P.gexec && P.gkey_graph == key) {
         // ---- replay
         P.st = P.g_st;
         P.nq = nq; P.k = k; P.out_ids = d_out_ids; P.out_scores = d_out_scores;
         P.trivial = false; P.ev_used = 0; P.t0 = P.t1 = 0; P.scan_pairs.clear();
-        P.N = N; P.kp = P.g_kp; P.path = P.g_path; P.eps_mode = P.g_eps_mode; P.eps_c = P.g_eps_c; P.split = false;
+        P.plan = P.g_plan;
         HIP_TRY(hipStreamWaitEvent(s, O.scans_done, 0));
         HIP_TRY(hipGraphLaunch(P.gexec, s));
         P.mid_recorded = false;
@@ -928,7 +864,7 @@ static int search_enqueue(vrod_index* idx, Pending& P, const float* d_queries_ra
             if (g) (void)hipGraphDestroy(g);
             if (rc == VROD_OK && e1 == hipSuccess && e2 == hipSuccess) {
                 P.gkey_graph = key;
-                P.g_kp = P.kp; P.g_path = P.path; P.g_eps_mode = P.eps_mode; P.g_eps_c = P.eps_c; P.g_st = P.st;
+                P.g_plan = P.plan; P.g_st = P.st;
                 HIP_TRY(hipStreamWaitEvent(s, O.scans_done, 0));
                 HIP_TRY(hipGraphLaunch(P.gexec, s));
                 VROD_TRY(record_scans_done(P, s));
@@ -964,20 +900,13 @@ static int search_enqueue(vrod_index* idx, Pending& P, const float* d_queries_ra
 // score the first pass found (kernels_select.hip band_prepare_kernel: a superset of the true top-k, boundary ties
 // included); their canonical re-score and an exact select by (score, id) is the answer -- no certificate needed.
 // A query whose band holds more than kBandKeep rows (thousands of exact duplicates) stays on the exact path.
-// From how many failed queries on the band pass beats the exact path.  On bf16 rows (or the bf16 planes of an fp32
-// corpus) a band pass of <= 64 queries is the skinny kernel, ONE HBM-bound pass over the corpus (2.8 ms at 15.4 GB),
-// while the exact path's pass of 8 queries is VALU-bound (9 ms there; cfg3dup, 8 failed queries per batch: 22.2 ms
-// per batch through the exact path, 15.9 through the band pass): from 2 queries on.  An fp32 corpus without planes
-// scans at the fp32 matrix rate (16x lower), several exact passes long: only for batches of failures.
-static const uint32_t kBandMinQueriesFast = 2, kBandMinQueriesF32 = 48;
+// (From how many failed queries on: kBandMinQueries*, search_plan.h band_eligible.)
 static const uint32_t kBandKeep = kSelectChunk / 2;
 
 static int band_pass(vrod_index* idx, Pending& P, std::vector<uint32_t>& failed, uint32_t max_qn2_bits) {
-    const bool band_on = debug_env().band;
     const uint32_t nf = (uint32_t)failed.size(), k = P.k;
-    const uint64_t N = P.N;
-    const uint32_t min_q = (idx->dtype == VROD_DTYPE_BF16 || P.split) ? kBandMinQueriesFast : kBandMinQueriesF32;
-    if (!band_on || P.path != VROD_PATH_MFMA || P.eps_mode == 1 || nf < min_q || N < k || P.nq_pad == 0) return VROD_OK;
+    const uint64_t N = P.plan.N;
+    if (!debug_env().band || !band_eligible(P.plan, idx->dtype, nf, k)) return VROD_OK;
     vrod_search_stats& st = P.st;
     hipStream_t s = P.stream;
     Timer tm(idx, P);
@@ -996,52 +925,22 @@ static int band_pass(vrod_index* idx, Pending& P, std::vector<uint32_t>& failed,
     uint32_t* b_ok = (uint32_t*)(b_qn2 + nf_pad);
     uint32_t* b_res = b_ok + nf_pad;
     uint32_t* b_status = b_res + nf_pad;
-    // the list block of the search ([nq_pad][cap] entries, counters behind it) is free again: its candidates were emitted
-    uint2* d_lists = P.lists.as<uint2>();
-    uint32_t* d_counts = (uint32_t*)((char*)P.lists.p + (size_t)P.nq_pad * cap * 8);
-    float* d_qn2_all = P.small.as<float>();
+    // the list block of the search is free again: its candidates were emitted
+    const ListBlock L = list_block(P);
     HIP_TRY(hipMemcpyAsync(P.band_idx.p, failed.data(), (size_t)nf * 4, hipMemcpyHostToDevice, s));
     // the batch's max |q|^2 (the bound's norm): the device copy was consumed with the read-back, flags[3] holds it for this pass
     HIP_TRY(hipMemcpyAsync(&P.flags[3], &max_qn2_bits, 4, hipMemcpyHostToDevice, s));
     launch_gather_query_rows(P.q_f32.as<float>(), P.band_idx.as<uint32_t>(), nf, nf_pad, idx->ld, P.band_q.as<float>(), bq_lp, s);
-    launch_band_prepare(P.band_idx.as<uint32_t>(), nf, nf_pad, P.out_scores, k, score_form(idx->metric), P.eps_mode, P.eps_c, &P.flags[3], idx->max_xn2_bits,
-                        d_qn2_all, b_thr, b_qn2, d_counts, b_ok, s);
-    MfmaScanArgs a{};
-    a.corpus = idx->corpus; a.queries = idx->dtype == VROD_DTYPE_BF16 ? bq_lp : P.band_q.p; a.xnorm2 = idx->xnorm2; a.qnorm2 = b_qn2; a.thr = b_thr;
-    a.lists = d_lists; a.counts = d_counts; a.cap = cap; a.ld = idx->ld; a.nq_pad = nf_pad; a.nq = nf; a.metric = score_form(idx->metric);
-    VROD_TRY(P.dump.ensure(mfma_dump_bytes(idx->num_cus)));
-    a.dump = P.dump.p;
-    int scan_dtype = idx->dtype;
-    if (P.split) {
-        VROD_TRY(P.band_planes.ensure((size_t)nf_pad * 3 * idx->ldp * 2));
-        launch_split_rows(P.band_q.as<float>(), nf_pad, idx->ld, idx->ldp, P.band_planes.p, true, s);
-        a.corpus = idx->planes; a.queries = P.band_planes.p;
-        a.ld = 3 * idx->ldp; a.lda_bytes = 2 * idx->ldp * 2; a.a_wrap = 1;
-        scan_dtype = VROD_DTYPE_BF16;
-    }
-    uint32_t* pace_base = P.flags + 64;
-    uint32_t* claim_base = pace_base + kPaceRegions * kPaceWords;
-    const double row_bytes_alg = (double)idx->ld * idx->esize;
-    for (uint64_t lo = 0; lo < N;) {
-        const uint64_t end = std::min<uint64_t>(N, lo / kRowTile * kRowTile + (1ull << 24));
-        a.row_begin = (uint32_t)lo; a.row_end = (uint32_t)end;
-        a.pace = pace_base + (P.pace_launches % kPaceRegions) * kPaceWords;
-        a.pace_is_zero = false;   // the regions were used by the search's own launches
-        a.claims = claim_base + (P.pace_launches % kPaceRegions) * kClaimWords;
-        a.claims_is_zero = false;
-        ++P.pace_launches;
-        size_t e0, e1;
-        tm.arm(e0, e1);
-        launch_scan_mfma(a, scan_dtype, idx->num_cus, s);
-        P.scan_pairs.push_back({e0, e1});
-        st.scan_launches++;
-        st.scan_bytes += (double)(end - lo / kRowTile * kRowTile) * row_bytes_alg;
-        st.scan_flops += 2.0 * nf * (double)(end - lo) * idx->dim;
-        lo = end;
-    }
+    launch_band_prepare(P.band_idx.as<uint32_t>(), nf, nf_pad, P.out_scores, k, score_form(idx->metric), P.plan.eps_mode, P.plan.eps_c, &P.flags[3],
+                        idx->max_xn2_bits, small_block(P).qn2, b_thr, b_qn2, L.counts, b_ok, s);
+    MfmaScanArgs a;
+    VROD_TRY(mfma_args(idx, P, a, idx->dtype == VROD_DTYPE_BF16 ? bq_lp : P.band_q.p, b_qn2, b_thr, nf, nf_pad));
+    if (P.plan.split) VROD_TRY(use_split_planes(idx, a, P.band_q.as<float>(), nf_pad, P.band_planes, s));
+    // (the pacing / claim regions were used by the search's own launches: never taken as zeroed)
+    launch_filtered(idx, P, tm, a, P.plan.split ? VROD_DTYPE_BF16 : idx->dtype, 0, N, false, false);
     HIP_TRY(hipGetLastError());
     std::vector<uint32_t> hcnt(nf), hok(nf);
-    HIP_TRY(hipMemcpyAsync(hcnt.data(), d_counts, (size_t)nf * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(hcnt.data(), L.counts, (size_t)nf * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(hok.data(), b_ok, (size_t)nf * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     const uint32_t need = (uint32_t)std::min<uint64_t>(k, N);
@@ -1063,7 +962,7 @@ static int band_pass(vrod_index* idx, Pending& P, std::vector<uint32_t>& failed,
         HIP_TRY(hipMemcpyAsync(b_res, hres.data(), (size_t)nf_pad * 4, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemsetAsync(b_status, 0, (size_t)nf_pad * 4, s));
         // every band row of a resolved query is kept (count <= kpb): sorted by fast score, padded with empty slots
-        launch_list_compact(d_lists, d_counts, cap, (int)nf, score_form(idx->metric), kpb, b_thr, b_status, P.cand_rows.as<uint32_t>(), P.cand_fast.as<float>(),
+        launch_list_compact(L.lists, L.counts, cap, (int)nf, score_form(idx->metric), kpb, b_thr, b_status, P.cand_rows.as<uint32_t>(), P.cand_fast.as<float>(),
                             b_qn2 /* T: unused */, s);
         launch_rescore_candidates(idx->corpus, idx->dtype, score_form(idx->metric), idx->dim, idx->ld, P.band_q.as<float>(), (int)nf, P.cand_rows.as<uint32_t>(), kpb,
                                   P.cand_canon.as<float>(), s);
@@ -1071,7 +970,7 @@ static int band_pass(vrod_index* idx, Pending& P, std::vector<uint32_t>& failed,
         // superset of the true top-k only while that stays inside the bound)
         HIP_TRY(hipMemsetAsync(&P.flags[4], 0, 4, s));
         launch_final_topk(P.cand_rows.as<uint32_t>(), P.cand_fast.as<float>(), P.cand_canon.as<float>(), b_qn2, (int)nf, kpb, k, score_form(idx->metric), idmap_of(idx),
-                          P.eps_mode, P.eps_c, &P.flags[3], idx->max_xn2_bits, P.band_ids.as<uint64_t>(), P.band_scores.as<float>(), b_status,
+                          P.plan.eps_mode, P.plan.eps_c, &P.flags[3], idx->max_xn2_bits, P.band_ids.as<uint64_t>(), P.band_scores.as<float>(), b_status,
                           (float*)&P.flags[4], s);
         launch_scatter_results(P.band_ids.as<uint64_t>(), P.band_scores.as<float>(), P.band_idx.as<uint32_t>(), b_res, nf, k, P.out_ids, P.out_scores, s);
         HIP_TRY(hipGetLastError());
@@ -1091,7 +990,7 @@ static int search_complete(vrod_index* idx, Pending& P) {
     hipStream_t s = P.stream;
     Timer tm(idx, P);
     const uint32_t nq = P.nq, k = P.k;
-    const uint64_t N = P.N;
+    const uint64_t N = P.plan.N;
     if (P.trivial) {
         idx->stats = st;
         return VROD_OK;
@@ -1101,18 +1000,14 @@ static int search_complete(vrod_index* idx, Pending& P) {
     uint32_t hflags[3];
     memcpy(hflags, P.h_readback + nq, 12);
     const uint32_t hmaxx = P.h_readback[nq + 3];
-    if (P.path == VROD_PATH_EXACT) {
+    if (P.plan.path == VROD_PATH_EXACT) {
         std::fill(hstatus.begin(), hstatus.end(), 1u);
     } else {
-        const int eps_mode = P.eps_mode;
-        const float eps_c = P.eps_c;
         memcpy(&st.max_fast_err, &hflags[2], 4);
         float qn2, xn2;
         memcpy(&qn2, &hflags[1], 4);
         memcpy(&xn2, &hmaxx, 4);
-        const float qn = std::sqrt(qn2), xn = std::sqrt(xn2);
-        st.eps_bound = (eps_mode == 0 ? eps_c * qn * xn : eps_mode == 1 ? eps_c /* relative */ : eps_c * (qn + xn) * (qn + xn)) +
-                       (eps_mode == 1 ? 0.f : eps_c * 2.3509887e-38f);   // + the absolute slack of the denormal range
+        st.eps_bound = eps_bound(P.plan.eps_mode, P.plan.eps_c, qn2, xn2);
     }
     if (hflags[0]) {  // NaN/Inf in the queries: whatever was computed is void (flag reset on device)
         idx->stats = st;
@@ -1128,7 +1023,7 @@ static int search_complete(vrod_index* idx, Pending& P) {
     st.fallback_queries = (uint32_t)failed.size();
     if (!failed.empty()) VROD_TRY(band_pass(idx, P, failed, hflags[1]));   // resolves most of them with one more shared scan
     const bool many_failed = failed.size() * 8 > nq;   // what the band pass could not resolve (duplicates it handled cheaply do not count)
-    if (P.split && many_failed && !idx->split_forced && ++idx->split_bad >= 2) {
+    if (P.plan.split && many_failed && !idx->split_forced && ++idx->split_bad >= 2) {
         // the split pass's bound is ~3x wider than the fp32 pass's: on a corpus whose gaps sit
         // inside it (twice now) the fp32 pass is the better fast pass.  The planes are released by
         // the next search that finds the handle idle.
@@ -1165,18 +1060,8 @@ static int search_complete(vrod_index* idx, Pending& P) {
             st.max_fast_err = std::max(st.max_fast_err, band_err);
         }
     }
-    if (P.path == VROD_PATH_MFMA && !P.split && P.nq) {   // the margin follows what the certificates say (vrod_index::kp_boost)
-        // (two searches may be in flight: a verdict counts only for the multiplier the search itself ran with)
-        if (idx->kp_hold) --idx->kp_hold;
-        if (st.fallback_queries) {
-            idx->kp_clean = 0;
-            if (P.kp_boost_used >= vrod_index::kMaxKpBoost) { idx->kp_boost = 1; idx->kp_hold = 256; }
-            else if (!idx->kp_hold && P.kp_boost_used == idx->kp_boost) idx->kp_boost *= 2;
-        } else if (P.kp_boost_used == idx->kp_boost && ++idx->kp_clean >= 64 && idx->kp_boost > 1) {
-            idx->kp_boost /= 2;
-            idx->kp_clean = 0;
-        }
-    }
+    if (kp_boost_applies(P.plan, nq))   // the margin follows what the certificates say
+        kp_boost_step(idx->kp_boost, P.kp_boost_used, st.fallback_queries != 0);
     if (idx->profiling) {
         for (size_t i = 0; i < P.scan_pairs.size(); ++i) st.scan_ms += tm.pair_ms(i);
         if (P.sample_pair >= 0 && (size_t)P.sample_pair < P.scan_pairs.size()) {

@@ -4,6 +4,8 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
+#include "search_plan.h"   // kSelectChunk
+
 namespace vrod {
 
 // How a shard's local row index becomes the id the caller sees.  Single-device index: row + offset.
@@ -76,8 +78,7 @@ void launch_hist_compact(const float* d_scores, uint64_t score_ld, uint64_t n, i
 // ---- kernels_select.hip
 // Level 0: fast scores (implicit ids = column index) -> per-chunk top-kp composite keys.
 // Later levels: keys -> keys.  Returns the number of keys per query written to d_out.
-// chunk capacity is kSelectChunk; kp <= kSelectChunk/2.
-constexpr uint32_t kSelectChunk = 8192;
+// chunk capacity is kSelectChunk (search_plan.h); kp <= kSelectChunk/2.
 uint64_t launch_select_from_scores(const float* d_scores, uint64_t score_ld, uint64_t n, int nq,
                                    int metric, uint32_t kp, uint64_t* d_out, uint64_t out_ld,
                                    hipStream_t s);
