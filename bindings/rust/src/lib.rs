@@ -54,6 +54,8 @@ extern "C" {
     pub fn vrod_index_count(idx: *const vrod_index, out_count: *mut u64) -> c_int;
     pub fn vrod_index_set_id_offset(idx: *mut vrod_index, offset: u64) -> c_int;
     pub fn vrod_index_get_rows(idx: *mut vrod_index, first: u64, n: u64, out_rows: *mut f32) -> c_int;
+    pub fn vrod_index_delete(idx: *mut vrod_index, ids: *const u64, n: u64) -> c_int;
+    pub fn vrod_index_live_count(idx: *const vrod_index, out: *mut u64) -> c_int;
     pub fn vrod_search(idx: *mut vrod_index, queries: *const f32, nq: u32, k: u32,
                        out_ids: *mut u64, out_scores: *mut f32) -> c_int;
     pub fn vrod_search_device(idx: *mut vrod_index, d_queries: *const f32, nq: u32, k: u32,
@@ -144,7 +146,20 @@ impl Collection {
         n
     }
 
-    /// Best-first `(ids, scores)`, `queries.len() * k` each; slots past `len()` are `(u64::MAX, NaN)`.
+    /// Deletes rows by the ids `search` reports (`DeleteCommand::execute`).  An id that is not a row fails the whole
+    /// call and deletes nothing; deleting a row twice is fine.  Ids are never reused: `len()` still counts them.
+    pub fn delete(&mut self, ids: &[u64]) -> Result<(), ScanError> {
+        check(unsafe { vrod_index_delete(self.idx, ids.as_ptr(), ids.len() as u64) })
+    }
+
+    /// Rows added minus rows deleted.
+    pub fn live_len(&self) -> u64 {
+        let mut n = 0u64;
+        unsafe { vrod_index_live_count(self.idx, &mut n) };
+        n
+    }
+
+    /// Best-first `(ids, scores)`, `queries.len() * k` each; slots past `live_len()` are `(u64::MAX, NaN)`.
     pub fn search(&self, queries: &[Vec<f32>], k: usize) -> Result<(Vec<u64>, Vec<f32>), ScanError> {
         for q in queries {
             if q.len() != self.dim {

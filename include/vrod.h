@@ -9,6 +9,7 @@
  *   vrod_index_add                 <- BulkInsertCommand::execute / InsertCommand::execute
  *                                     (src/command/types.rs:56-80), rows are the
  *                                     Vec<Vec<f32>> of src/utils/embeddings.rs:29
+ *   vrod_index_delete              <- the DELETE command CommandBuilder names (src/command/types.rs, builder.rs)
  *   vrod_search                    <- SearchSimilarCommand::execute
  *                                     (src/command/types.rs:121-132), built by
  *                                     CommandBuilder::build "SEARCHSIMILAR"
@@ -30,8 +31,8 @@
  * inner product) scores are dot products of the prepared vectors -- stored as given,
  * bf16-rounded on BF16 handles, never normalised (higher is better); results are
  * best-first, ties broken by smaller id, a NaN score (an IP dot product whose terms
- * overflow to +inf and -inf) ranks last and still carries its row's id; unfilled slots
- * (k > count) are (VROD_ID_NONE, NaN).  Results are bit-identical to the CPU oracle
+ * overflow to +inf and -inf) ranks last and still carries its row's id; deleted rows are absent (vrod_index_delete);
+ * unfilled slots (k > live rows) are (VROD_ID_NONE, NaN).  Results are bit-identical to the CPU oracle
  * (oracle/), except that a NaN score matches any NaN.
  *
  * Environment (read once per process; everything else the library reads is
@@ -132,6 +133,17 @@ int vrod_index_add_synthetic(vrod_index *idx, uint64_t seed, uint64_t first_row,
 int vrod_index_count(const vrod_index *idx, uint64_t *out_count);
 /* Shard support: reported id = local row index + offset. */
 int vrod_index_set_id_offset(vrod_index *idx, uint64_t offset);
+/* Delete rows (<- vRod's DELETE, src/command/types.rs, builder.rs): `ids` (host memory, n of them) are ids as searches
+ * report them, id_offset applied.  Afterwards no search on the handle -- any path, dtype or metric, pipelined,
+ * replayed, multi-device, band or exact -- returns those rows: the results are bit for bit those of the same search
+ * over the live rows alone (ties still broken by smaller id; slots beyond the live rows are (VROD_ID_NONE, NaN)).
+ * Deleting a row again, or naming it twice in one call, is fine.  An id that is not a current row (below the offset,
+ * or id - offset >= count) fails the whole call with VROD_ERR_INVALID_ARG and deletes nothing; n == 0 does nothing.
+ * Ids are never reused: vrod_index_count still counts every row ever added (and is the next id), vrod_index_get_rows
+ * still reads deleted rows back, and vrod_search_stats scan_bytes / scan_flops still count every stored row. */
+int vrod_index_delete(vrod_index *idx, const uint64_t *ids, uint64_t n);
+/* Rows added minus rows deleted. */
+int vrod_index_live_count(const vrod_index *idx, uint64_t *out);
 /* Copy prepared rows [first, first+n) back as fp32 (bf16 widened): n x dim. */
 int vrod_index_get_rows(vrod_index *idx, uint64_t first, uint64_t n, float *out_rows);
 

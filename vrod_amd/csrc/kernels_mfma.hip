@@ -58,6 +58,7 @@ void launch_scan_mfma(const MfmaScanArgs& h, int dtype, int num_cus, hipStream_t
     a.dense_ld = h.dense_ld;
     a.dense_group = (h.dense_out && h.dense_grouped) ? 1u : 0u;   // only ever set by a caller that asked mfma_dense_group_rows()
     a.pace = h.pace;
+    a.row_mask = h.dense_out ? nullptr : h.row_mask;   // (a sample pass writes every score: launch_mask_sample)
     const int grid = mfma_grid(num_cus);
     a.dump = (char*)h.dump;
     a.slots = grid / 8;

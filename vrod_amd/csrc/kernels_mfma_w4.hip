@@ -200,6 +200,8 @@ __device__ __forceinline__ void w4_process_region(const MfmaKernelArgs& a, const
                 sc[u][r] = METRIC == M_COSINE ? v[u][r] : __builtin_fmaf(-2.0f, v[u][r], a.xnorm2[row] + qn2);
                 h |= (better<METRIC>(sc[u][r], thr) && row >= a.row_lo && row < a.row_end) ? 1u << r : 0u;
             }
+            // deleted rows leave before the list atomic: the 4 rows of a quad share one mask word (row0 % 4 == 0)
+            if (a.row_mask) h &= ~(a.row_mask[row0[u] >> 5] >> (row0[u] & 31u));
             hits[u] = i < nquads ? h : 0u;
         }
 #pragma unroll

@@ -93,10 +93,11 @@ __device__ __forceinline__ uint32_t pow2_ceil(uint32_t n) {
 // grid = (nchunks, nq).  Chunk c of query q: elements [c*C, min((c+1)*C, n)).
 // FROM_SCORES: element i is (score[q][i], row i).  Else: element i is key[q][i].
 // Writes the chunk's best `kp` keys (descending, zero-padded) to out[q][c*kp ...].
+// FROM_SCORES with row_mask: a row whose bit is set is absent (key 0, the padding key).
 template <int METRIC, bool FROM_SCORES>
 __global__ __launch_bounds__(kSortThreads) void select_chunk_kernel(
     const float* __restrict__ scores, const uint64_t* __restrict__ keys_in, uint64_t in_ld,
-    uint64_t n, uint32_t kp, uint64_t* __restrict__ out, uint64_t out_ld) {
+    uint64_t n, uint32_t kp, uint64_t* __restrict__ out, uint64_t out_ld, const uint32_t* __restrict__ row_mask) {
     extern __shared__ __attribute__((aligned(16))) uint64_t skeys[];
     const uint32_t q = blockIdx.y;
     const uint64_t c0 = (uint64_t)blockIdx.x * kSelectChunk;
@@ -105,9 +106,11 @@ __global__ __launch_bounds__(kSortThreads) void select_chunk_kernel(
     for (uint32_t i = threadIdx.x; i < np2; i += kSortThreads) {
         uint64_t key = 0;
         if (i < cnt) {
-            if constexpr (FROM_SCORES)
-                key = make_key(score_key<METRIC>(scores[(uint64_t)q * in_ld + c0 + i]), (uint32_t)(c0 + i));
-            else
+            if constexpr (FROM_SCORES) {
+                const uint64_t r = c0 + i;
+                if (!row_mask || !((row_mask[r >> 5] >> (r & 31u)) & 1u))
+                    key = make_key(score_key<METRIC>(scores[(uint64_t)q * in_ld + r]), (uint32_t)r);
+            } else
                 key = keys_in[(uint64_t)q * in_ld + c0 + i];
         }
         skeys[i] = key;
@@ -127,14 +130,14 @@ static inline size_t sort_lds_bytes(uint64_t n) {
 
 uint64_t launch_select_from_scores(const float* d_scores, uint64_t score_ld, uint64_t n, int nq,
                                    int metric, uint32_t kp, uint64_t* d_out, uint64_t out_ld,
-                                   hipStream_t s) {
+                                   const uint32_t* d_row_mask, hipStream_t s) {
     const uint64_t nchunks = (n + kSelectChunk - 1) / kSelectChunk;
     dim3 grid((unsigned)nchunks, nq);
     const size_t lds = sort_lds_bytes(n);
     if (metric == M_COSINE)
-        select_chunk_kernel<M_COSINE, true><<<grid, kSortThreads, lds, s>>>(d_scores, nullptr, score_ld, n, kp, d_out, out_ld);
+        select_chunk_kernel<M_COSINE, true><<<grid, kSortThreads, lds, s>>>(d_scores, nullptr, score_ld, n, kp, d_out, out_ld, d_row_mask);
     else
-        select_chunk_kernel<M_L2, true><<<grid, kSortThreads, lds, s>>>(d_scores, nullptr, score_ld, n, kp, d_out, out_ld);
+        select_chunk_kernel<M_L2, true><<<grid, kSortThreads, lds, s>>>(d_scores, nullptr, score_ld, n, kp, d_out, out_ld, d_row_mask);
     return nchunks * kp;
 }
 
@@ -142,7 +145,7 @@ uint64_t launch_select_from_keys(const uint64_t* d_in, uint64_t in_ld, uint64_t 
                                  uint32_t kp, uint64_t* d_out, uint64_t out_ld, hipStream_t s) {
     const uint64_t nchunks = (n + kSelectChunk - 1) / kSelectChunk;
     dim3 grid((unsigned)nchunks, nq);
-    select_chunk_kernel<M_COSINE, false><<<grid, kSortThreads, sort_lds_bytes(n), s>>>(nullptr, d_in, in_ld, n, kp, d_out, out_ld);
+    select_chunk_kernel<M_COSINE, false><<<grid, kSortThreads, sort_lds_bytes(n), s>>>(nullptr, d_in, in_ld, n, kp, d_out, out_ld, nullptr);
     return nchunks * kp;
 }
 
@@ -205,7 +208,7 @@ __global__ __launch_bounds__(256) void hist_compact_kernel(const float* __restri
                                                            uint64_t n, const uint32_t* __restrict__ ghist,
                                                            int hist_bits, uint32_t kp, uint64_t* __restrict__ keys,
                                                            uint32_t cap, uint32_t* __restrict__ cnt,
-                                                           uint32_t* __restrict__ status) {
+                                                           uint32_t* __restrict__ status, const uint32_t* __restrict__ row_mask) {
     __shared__ uint32_t ctl[8];
     const uint32_t q = blockIdx.y;
     const int nbins = 1 << hist_bits;
@@ -223,7 +226,7 @@ __global__ __launch_bounds__(256) void hist_compact_kernel(const float* __restri
         const uint64_t i = i0 + off;
         uint32_t skey = 0;
         bool take = false;
-        if (i < n) {
+        if (i < n && !(row_mask && ((row_mask[i >> 5] >> (i & 31u)) & 1u))) {   // (deleted rows were not counted either)
             skey = score_key<METRIC>(sc[i]);
             take = skey >= thr_key;
         }
@@ -242,12 +245,12 @@ __global__ __launch_bounds__(256) void hist_compact_kernel(const float* __restri
 
 void launch_hist_compact(const float* d_scores, uint64_t score_ld, uint64_t n, int nq, int metric,
                          const uint32_t* d_hist, int hist_bits, uint32_t kp, uint64_t* d_keys,
-                         uint32_t cap, uint32_t* d_cnt, uint32_t* d_status, hipStream_t s) {
+                         uint32_t cap, uint32_t* d_cnt, uint32_t* d_status, const uint32_t* d_row_mask, hipStream_t s) {
     dim3 grid((unsigned)((n + kCompactSlice - 1) / kCompactSlice), nq);
     if (metric == M_COSINE)
-        hist_compact_kernel<M_COSINE><<<grid, 256, 0, s>>>(d_scores, score_ld, n, d_hist, hist_bits, kp, d_keys, cap, d_cnt, d_status);
+        hist_compact_kernel<M_COSINE><<<grid, 256, 0, s>>>(d_scores, score_ld, n, d_hist, hist_bits, kp, d_keys, cap, d_cnt, d_status, d_row_mask);
     else
-        hist_compact_kernel<M_L2><<<grid, 256, 0, s>>>(d_scores, score_ld, n, d_hist, hist_bits, kp, d_keys, cap, d_cnt, d_status);
+        hist_compact_kernel<M_L2><<<grid, 256, 0, s>>>(d_scores, score_ld, n, d_hist, hist_bits, kp, d_keys, cap, d_cnt, d_status, d_row_mask);
 }
 
 // ------------------------------------------------------------------ candidate lists (MFMA path)
@@ -457,6 +460,25 @@ void launch_sample_select(const float* d_scores, uint64_t score_ld, uint32_t n_s
     }
     if (metric == M_COSINE) sample_select_kernel<M_COSINE><<<nq, 256, 0, s>>>(d_scores, score_ld, n_sample, j, d_thr);
     else sample_select_kernel<M_L2><<<nq, 256, 0, s>>>(d_scores, score_ld, n_sample, j, d_thr);
+}
+
+// Sample block of a handle with deleted rows: the deleted rows' columns get the worst score, so that they cannot be the
+// j-th best -- the threshold then holds for the live rows (at worst it filters nothing).  grid = (column blocks, query
+// groups); only deleted columns are written.
+__global__ __launch_bounds__(256) void mask_sample_kernel(float* __restrict__ scores, uint64_t score_ld, uint32_t n, uint32_t nq,
+                                                          uint64_t row0, const uint32_t* __restrict__ row_mask, float worst) {
+    const uint32_t c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= n) return;
+    const uint64_t r = row0 + c;
+    if (!((row_mask[r >> 5] >> (r & 31u)) & 1u)) return;
+    for (uint32_t q = blockIdx.y; q < nq; q += gridDim.y) scores[(uint64_t)q * score_ld + c] = worst;
+}
+
+void launch_mask_sample(float* d_scores, uint64_t score_ld, uint32_t n_sample, int nq, uint64_t row0,
+                        const uint32_t* d_row_mask, int metric, hipStream_t s) {
+    if (!nq || !n_sample || !d_row_mask) return;
+    const dim3 grid((n_sample + 255) / 256, (unsigned)std::min(nq, 64));
+    mask_sample_kernel<<<grid, 256, 0, s>>>(d_scores, score_ld, n_sample, (uint32_t)nq, row0, d_row_mask, worst_score(metric));
 }
 
 // ------------------------------------------------------------------ final ordering + certificate

@@ -72,14 +72,16 @@ int stream_max_queries_per_pass(uint32_t ld) {
 
 // IT > 0: loads per lane per row known at compile time, UNROLL row-steps in flight.
 // IT == 0: runtime `it` (any ld), one row-step at a time.
-template <typename T, int METRIC, int NQ, int IT, int UNROLL>
+// MASK: a handle with deleted rows -- a row whose bit is set in row_mask is neither written nor counted in the
+// histogram (the cut bin must leave k' LIVE rows above it).  Launched only with a mask: the default form is unchanged.
+template <typename T, int METRIC, int NQ, int IT, int UNROLL, bool MASK>
 __global__ __launch_bounds__(256) void scan_stream_kernel(const T* __restrict__ corpus,
                                                           uint32_t ld, uint64_t nrows,
                                                           const float* __restrict__ q,
                                                           float* __restrict__ scores,
                                                           uint64_t score_ld, int lpr_log2,
                                                           int it_rt, uint32_t* __restrict__ ghist,
-                                                          uint32_t kp) {
+                                                          uint32_t kp, const uint32_t* __restrict__ row_mask) {
     typedef typename Unit<T>::vec vec_t;
     constexpr int EPU = Unit<T>::EPU;
     constexpr int HB = StreamHist<NQ>::HB;          // histogram bits of the score key
@@ -171,7 +173,10 @@ __global__ __launch_bounds__(256) void scan_stream_kernel(const T* __restrict__ 
         }
         // lane (grp, pos0) holds row base + pos0*R + grp: one 256-B segment per query
         const uint64_t orow = base + (uint64_t)pos0 * R + grp;
-        if (orow < nrows) {
+        bool live = orow < nrows;
+        // (a deleted row's score is not needed: hist_compact never reads it)
+        if constexpr (MASK) live = live && !((row_mask[orow >> 5] >> (orow & 31u)) & 1u);
+        if (live) {
 #pragma unroll
             for (int qi = 0; qi < NQ; ++qi) {
                 scores[(uint64_t)qi * score_ld + orow] = keep[qi];
@@ -203,9 +208,9 @@ __global__ __launch_bounds__(256) void scan_stream_kernel(const T* __restrict__ 
     }
 }
 
-template <typename T, int METRIC, int NQ>
+template <typename T, int METRIC, int NQ, bool MASK>
 static void dispatch_it(const T* corpus, uint32_t ld, uint64_t nrows, const float* q, float* scores,
-                        uint64_t score_ld, int num_blocks, uint32_t* ghist, uint32_t kp, hipStream_t s) {
+                        uint64_t score_ld, int num_blocks, uint32_t* ghist, uint32_t kp, const uint32_t* mask, hipStream_t s) {
     constexpr int EPU = Unit<T>::EPU;
     const uint32_t upr = ld / EPU;  // ld is a multiple of 32 (f32) / 64 (bf16): upr % 8 == 0
     int lpr_log2 = 6;
@@ -215,8 +220,8 @@ static void dispatch_it(const T* corpus, uint32_t ld, uint64_t nrows, const floa
     const LaunchEvents lev = g_launch_events;
     g_launch_events = LaunchEvents{};
 #define VROD_LAUNCH(ITV, UNR)                                                                   \
-    hipExtLaunchKernelGGL((scan_stream_kernel<T, METRIC, NQ, ITV, UNR>), dim3(num_blocks), dim3(256), lds, s, \
-                          lev.start, lev.stop, 0, corpus, ld, nrows, q, scores, score_ld, lpr_log2, it, ghist, kp)
+    hipExtLaunchKernelGGL((scan_stream_kernel<T, METRIC, NQ, ITV, UNR, MASK>), dim3(num_blocks), dim3(256), lds, s, \
+                          lev.start, lev.stop, 0, corpus, ld, nrows, q, scores, score_ld, lpr_log2, it, ghist, kp, mask)
     switch (it) {
         case 1: VROD_LAUNCH(1, 8); break;
         case 2: VROD_LAUNCH(2, 4); break;
@@ -228,21 +233,29 @@ static void dispatch_it(const T* corpus, uint32_t ld, uint64_t nrows, const floa
 #undef VROD_LAUNCH
 }
 
-template <typename T, int METRIC>
+template <typename T, int METRIC, bool MASK>
 static void dispatch_nq(const T* corpus, uint32_t ld, uint64_t nrows, const float* q, int nq_pad,
                         float* scores, uint64_t score_ld, int num_blocks, uint32_t* ghist, uint32_t kp,
-                        hipStream_t s) {
+                        const uint32_t* mask, hipStream_t s) {
     switch (nq_pad) {
-        case 1: dispatch_it<T, METRIC, 1>(corpus, ld, nrows, q, scores, score_ld, num_blocks, ghist, kp, s); break;
-        case 2: dispatch_it<T, METRIC, 2>(corpus, ld, nrows, q, scores, score_ld, num_blocks, ghist, kp, s); break;
-        case 4: dispatch_it<T, METRIC, 4>(corpus, ld, nrows, q, scores, score_ld, num_blocks, ghist, kp, s); break;
-        default: dispatch_it<T, METRIC, 8>(corpus, ld, nrows, q, scores, score_ld, num_blocks, ghist, kp, s); break;
+        case 1: dispatch_it<T, METRIC, 1, MASK>(corpus, ld, nrows, q, scores, score_ld, num_blocks, ghist, kp, mask, s); break;
+        case 2: dispatch_it<T, METRIC, 2, MASK>(corpus, ld, nrows, q, scores, score_ld, num_blocks, ghist, kp, mask, s); break;
+        case 4: dispatch_it<T, METRIC, 4, MASK>(corpus, ld, nrows, q, scores, score_ld, num_blocks, ghist, kp, mask, s); break;
+        default: dispatch_it<T, METRIC, 8, MASK>(corpus, ld, nrows, q, scores, score_ld, num_blocks, ghist, kp, mask, s); break;
     }
+}
+
+template <typename T, int METRIC>
+static void dispatch_mask(const T* corpus, uint32_t ld, uint64_t nrows, const float* q, int nq_pad,
+                          float* scores, uint64_t score_ld, int num_blocks, uint32_t* ghist, uint32_t kp,
+                          const uint32_t* mask, hipStream_t s) {
+    if (mask) dispatch_nq<T, METRIC, true>(corpus, ld, nrows, q, nq_pad, scores, score_ld, num_blocks, ghist, kp, mask, s);
+    else dispatch_nq<T, METRIC, false>(corpus, ld, nrows, q, nq_pad, scores, score_ld, num_blocks, ghist, kp, nullptr, s);
 }
 
 void launch_scan_stream(const void* d_corpus, int dtype, int metric, uint32_t ld, uint64_t nrows,
                         const float* d_q, int nq_pad, float* d_scores, uint64_t score_ld,
-                        uint32_t* d_hist, uint32_t kp, hipStream_t s) {
+                        uint32_t* d_hist, uint32_t kp, const uint32_t* d_row_mask, hipStream_t s) {
     if (!nrows) { g_launch_events = LaunchEvents{}; return; }
     // 64 rows per wave step, 4 waves per block.  2 blocks per CU (8 waves x 12 KB of loads in
     // flight) measured best on MI355X: 6.46 TB/s at 1M x 768 fp32 vs 5.9 TB/s with 8 blocks per
@@ -251,11 +264,11 @@ void launch_scan_stream(const void* d_corpus, int dtype, int metric, uint32_t ld
     if (blocks > 256 * 2) blocks = 256 * 2;
     const int nb = (int)blocks;
     if (dtype == DT_BF16) {
-        if (metric == M_COSINE) dispatch_nq<bf16_t, M_COSINE>((const bf16_t*)d_corpus, ld, nrows, d_q, nq_pad, d_scores, score_ld, nb, d_hist, kp, s);
-        else dispatch_nq<bf16_t, M_L2>((const bf16_t*)d_corpus, ld, nrows, d_q, nq_pad, d_scores, score_ld, nb, d_hist, kp, s);
+        if (metric == M_COSINE) dispatch_mask<bf16_t, M_COSINE>((const bf16_t*)d_corpus, ld, nrows, d_q, nq_pad, d_scores, score_ld, nb, d_hist, kp, d_row_mask, s);
+        else dispatch_mask<bf16_t, M_L2>((const bf16_t*)d_corpus, ld, nrows, d_q, nq_pad, d_scores, score_ld, nb, d_hist, kp, d_row_mask, s);
     } else {
-        if (metric == M_COSINE) dispatch_nq<float, M_COSINE>((const float*)d_corpus, ld, nrows, d_q, nq_pad, d_scores, score_ld, nb, d_hist, kp, s);
-        else dispatch_nq<float, M_L2>((const float*)d_corpus, ld, nrows, d_q, nq_pad, d_scores, score_ld, nb, d_hist, kp, s);
+        if (metric == M_COSINE) dispatch_mask<float, M_COSINE>((const float*)d_corpus, ld, nrows, d_q, nq_pad, d_scores, score_ld, nb, d_hist, kp, d_row_mask, s);
+        else dispatch_mask<float, M_L2>((const float*)d_corpus, ld, nrows, d_q, nq_pad, d_scores, score_ld, nb, d_hist, kp, d_row_mask, s);
     }
 }
 

@@ -76,7 +76,13 @@ struct MfmaKernelArgs {
     uint32_t* claims;       // 4-wave kernel, filtered launches: [nqb][nstrips] claim bits of the strips' tail chunks (work stealing), zeroed per launch; null: static shares only
     uint32_t dense_group;   // DENSE launch of the 2 x 2 4-wave kernel: write one score per (query, group of 32 rows) -- the
                             // best of the group -- to dense_out[query][group], dense_ld groups per query
+    const uint32_t* row_mask;   // filtered launches: rows whose bit is set are dropped before the list atomic (null: none)
 };
+
+// row `row` is excluded by the launch's row mask (deleted)
+__device__ __forceinline__ bool row_masked(const MfmaKernelArgs& a, uint32_t row) {
+    return a.row_mask && ((a.row_mask[row >> 5] >> (row & 31u)) & 1u);
+}
 
 template <int METRIC>
 __device__ __forceinline__ bool better(float a, float b) {
@@ -84,6 +90,7 @@ __device__ __forceinline__ bool better(float a, float b) {
 }
 
 __device__ __forceinline__ void global_append(const MfmaKernelArgs& a, uint32_t gq, uint32_t bits, uint32_t row) {
+    if (row_masked(a, row)) return;
     const uint32_t pos = atomicAdd(&a.counts[gq], 1u);
     if (pos < a.cap) a.lists[(uint64_t)gq * a.cap + pos] = make_uint2(bits, row);
 }

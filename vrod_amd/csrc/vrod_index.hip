@@ -131,7 +131,7 @@ struct Pending {
     // hipGraph replay of small, launch-bound searches (search_enqueue): the launches of a search
     // whose every pointer and size equals the captured one are replayed as one graph launch
     struct GraphKey {
-        const void *q = nullptr, *oi = nullptr, *os = nullptr, *corpus = nullptr, *xn = nullptr;
+        const void *q = nullptr, *oi = nullptr, *os = nullptr, *corpus = nullptr, *xn = nullptr, *mask = nullptr;
         const void* bufs[12] = {};
         uint64_t N = 0, id_offset = 0;
         uint32_t nq = 0, k = 0;
@@ -174,6 +174,15 @@ struct vrod_index {
     void* planes = nullptr;        // [planes_cap][2 * ldp] bf16, [hi_j | lo_j] per 64-element K-tile j
     uint64_t planes_cap = 0, planes_rows = 0;
     uint32_t ldp = 0;              // dim rounded up to 64 (bf16 128-B lines)
+
+    // deleted rows (vrod_index_delete): one bit per row of the capacity, bit r % 32 of word r / 32 set = row r deleted.
+    // The host mirror is the truth; the device copy is allocated at the first delete and the kernels see it only
+    // while some row is deleted (row_mask()), so a handle that never deleted runs exactly the launches it ran before.
+    std::vector<uint32_t> del_bits;    // [capacity / 32]
+    uint32_t* del_dev = nullptr;       // [capacity / 32] on the device, or null
+    uint64_t n_deleted = 0;
+    uint64_t del_gen = 0;              // bumped by every delete that changes the bitmap
+    struct SampleWindow { uint64_t S = 0, N = 0, gen = 0, first = 0; bool valid = false; } sample_win;
 
     // workspaces
     DevBuf raw_stage, nrm_ws, out_ids, out_scores;
@@ -223,6 +232,9 @@ struct vrod_index {
     bool composite() const { return !shards.empty(); }
 
     size_t row_bytes() const { return (size_t)ld * esize; }
+    uint64_t live() const { return count - n_deleted; }
+    // what the kernels get as their row mask: null while nothing is deleted
+    const uint32_t* row_mask() const { return n_deleted ? del_dev : nullptr; }
 };
 
 static int set_device(const vrod_index* idx) {
@@ -265,9 +277,25 @@ static int index_reserve(vrod_index* idx, uint64_t n_rows) {
         (void)hipFree(nx);
         return fail(VROD_ERR_HIP, "growing the corpus failed: %s", hipGetErrorString(ce));
     }
+    uint32_t* nd = nullptr;   // the deleted-row bitmap follows the capacity (once it exists)
+    if (idx->del_dev) {
+        hipError_t de = hipMalloc((void**)&nd, want / 32 * 4);
+        if (de == hipSuccess) de = hipMemsetAsync(nd, 0, want / 32 * 4, idx->stream);
+        if (de == hipSuccess) de = hipMemcpyAsync(nd, idx->del_bits.data(), idx->del_bits.size() * 4, hipMemcpyHostToDevice, idx->stream);
+        if (de == hipSuccess) de = hipStreamSynchronize(idx->stream);
+        if (de != hipSuccess) {
+            (void)hipStreamSynchronize(idx->stream);
+            if (nd) (void)hipFree(nd);
+            (void)hipFree(nc);
+            (void)hipFree(nx);
+            return fail(VROD_ERR_HIP, "growing the deleted-row bitmap failed: %s", hipGetErrorString(de));
+        }
+    }
     if (idx->corpus) (void)hipFree(idx->corpus);
     if (idx->xnorm2) (void)hipFree(idx->xnorm2);
     if (idx->planes) { (void)hipFree(idx->planes); idx->planes = nullptr; idx->planes_cap = idx->planes_rows = 0; }   // rebuilt lazily
+    if (idx->del_dev) { (void)hipFree(idx->del_dev); idx->del_dev = nd; }
+    idx->del_bits.resize(want / 32, 0u);
     idx->corpus = nc;
     idx->xnorm2 = nx;
     idx->capacity = want;
@@ -436,12 +464,14 @@ struct Timer {
 
 // select chain over fast (or canonical) scores of `nq` queries -> keys of <= kSelectChunk per query
 // returns pointer/ld/n of the final key set through out params.
+// (the handle's deleted rows are left out at the first level: they never reach the keys)
 static int select_chain(vrod_index* idx, Pending& P, const float* d_scores, uint64_t score_ld, uint64_t n, int nq,
                         uint32_t kp, const uint64_t** out_keys, uint64_t* out_ld, uint64_t* out_n) {
     const uint64_t nch0 = (n + kSelectChunk - 1) / kSelectChunk;
     const uint64_t ld_a = nch0 * kp;
     VROD_TRY(P.keys_a.ensure((size_t)nq * ld_a * 8));
-    uint64_t cur_n = launch_select_from_scores(d_scores, score_ld, n, nq, score_form(idx->metric), kp, P.keys_a.as<uint64_t>(), ld_a, P.stream);
+    uint64_t cur_n = launch_select_from_scores(d_scores, score_ld, n, nq, score_form(idx->metric), kp, P.keys_a.as<uint64_t>(), ld_a,
+                                               idx->row_mask(), P.stream);
     const uint64_t* cur = P.keys_a.as<uint64_t>();
     uint64_t cur_ld = ld_a;
     bool a_is_cur = true;
@@ -494,6 +524,7 @@ static int mfma_args(vrod_index* idx, Pending& P, MfmaScanArgs& a, const void* q
     a.corpus = idx->corpus; a.queries = queries; a.xnorm2 = idx->xnorm2; a.qnorm2 = qn2; a.thr = thr;
     a.lists = L.lists; a.counts = L.counts; a.cap = kSelectChunk; a.ld = idx->ld; a.nq_pad = nq_pad; a.nq = nq;
     a.metric = score_form(idx->metric);
+    a.row_mask = idx->row_mask();
     VROD_TRY(P.dump.ensure(mfma_dump_bytes(idx->num_cus)));
     a.dump = P.dump.p;
     return VROD_OK;
@@ -599,20 +630,50 @@ static int stream_pass(vrod_index* idx, Pending& P, Timer& tm, bool in_graph) {
         size_t a, b;
         tm.arm(a, b);
         launch_scan_stream(idx->corpus, idx->dtype, form, idx->ld, N, P.q_f32.as<float>() + (size_t)q0 * idx->ld, nqp,
-                           P.scores.as<float>(), score_ld, d_hist, kp, s);
+                           P.scores.as<float>(), score_ld, d_hist, kp, idx->row_mask(), s);
         P.scan_pairs.push_back({a, b});
         if (q0 + qpp >= nq && !in_graph) VROD_TRY(record_scans_done(P, s));
         st.scan_launches++;
         st.scan_bytes += (double)N * row_bytes_alg;
         st.scan_flops += 2.0 * nqc * (double)N * idx->dim;
         launch_hist_compact(P.scores.as<float>(), score_ld, N, nqc, form, d_hist, stream_hist_bits(nqp), kp,
-                            P.keys_a.as<uint64_t>(), kSelectChunk, d_cnt, B.status + q0, s);
+                            P.keys_a.as<uint64_t>(), kSelectChunk, d_cnt, B.status + q0, idx->row_mask(), s);
         launch_keys_to_candidates(P.keys_a.as<uint64_t>(), kSelectChunk, kSelectChunk, nqc, form, kp,
                                   P.cand_rows.as<uint32_t>() + (size_t)q0 * kp, P.cand_fast.as<float>() + (size_t)q0 * kp,
                                   B.T + q0, d_cnt, s);
     }
     HIP_TRY(hipGetLastError());
     return VROD_OK;
+}
+
+// First row of the sample pass's S rows on a handle with deleted rows.  Any window gives a valid threshold (its deleted
+// rows are masked to the worst score, and every window row is scanned again by the filtered stages), but one made of
+// deleted rows gives none: the first stage would then append every row, overflow its lists and send every query to the
+// exact path.  The window stays at row 0 while at least 7/8 of it is live; else it moves to the tile-aligned window
+// with the most live rows (first of equals).  Cached until the bitmap or the stage plan changes.
+static uint64_t sample_window(vrod_index* idx, uint64_t S, uint64_t N) {
+    if (!idx->n_deleted || S >= N) return 0;
+    vrod_index::SampleWindow& W = idx->sample_win;
+    if (W.valid && W.S == S && W.N == N && W.gen == idx->del_gen) return W.first;
+    const uint64_t tiles = N / kRowTile, wt = S / kRowTile;   // S < N is a whole number of tiles (plan_stages)
+    std::vector<uint32_t> live(tiles);
+    for (uint64_t t = 0; t < tiles; ++t) {
+        uint32_t dead = 0;
+        for (uint32_t w = 0; w < kRowTile / 32; ++w) dead += (uint32_t)__builtin_popcount(idx->del_bits[t * (kRowTile / 32) + w]);
+        live[t] = kRowTile - dead;
+    }
+    uint64_t cur = 0;
+    for (uint64_t t = 0; t < wt; ++t) cur += live[t];
+    uint64_t best = cur, first = 0;
+    if (cur * 8 < S * 7) {
+        for (uint64_t t = 1; t + wt <= tiles; ++t) {
+            cur += live[t + wt - 1];
+            cur -= live[t - 1];
+            if (cur > best) { best = cur; first = t * kRowTile; }
+        }
+    }
+    W = {S, N, idx->del_gen, first, true};
+    return first;
 }
 
 // -------- fast pass B: batched MFMA scan.  (1) dense sample pass over the first S rows, (2) exact j-th best per query =
@@ -663,11 +724,14 @@ static int mfma_pass(vrod_index* idx, Pending& P, Timer& tm, const void* q_lp) {
                                          debug_env().stage_growth, debug_env().sample_rows);
         bounds = sp.bounds;
         MfmaScanArgs d = a;
-        d.row_begin = 0; d.row_end = sp.S;
+        const uint64_t w0 = sample_window(idx, sp.S, N);
+        d.row_begin = (uint32_t)w0; d.row_end = (uint32_t)(w0 + sp.S);
         // Grouped form where the kernel has it: the threshold is the j-th best of the per-group bests (groups of 32
         // rows: valid -- at least j rows are that good -- and exact unless two of the j best share a group), 1/32 of
         // the dense block to write and to select from.  Only while the groups outnumber j by 8x (else: every score).
-        const bool group_env = debug_env().sample_grouped;
+        // A handle with deleted rows takes every score: a group's best may be a deleted row, and at 10 % deleted rows
+        // nearly every group holds one.
+        const bool group_env = debug_env().sample_grouped && !idx->row_mask();
         const uint32_t grows = group_env ? mfma_dense_group_rows(d, scan_dtype) : 0u;
         const uint32_t n_groups = grows ? (uint32_t)(round_up(sp.S, kRowTile) / grows) : 0u;
         const bool grouped = grows && (uint64_t)sp.j * 8 <= n_groups && sp.S % kRowTile == 0;   // whole tiles of real rows
@@ -685,6 +749,7 @@ static int mfma_pass(vrod_index* idx, Pending& P, Timer& tm, const void* q_lp) {
         st.scan_launches++;
         // (the sample rows are scanned again by the first filtered stage: their time counts, their flops and
         // bytes do not -- algorithmic work is 2 * nq * N * d and N * row bytes, each row once)
+        launch_mask_sample(P.scores.as<float>(), dense_ld, n_sel, (int)nq, w0, idx->row_mask(), form, s);   // (no mask: nothing)
         launch_sample_select(P.scores.as<float>(), dense_ld, n_sel, (int)nq, form, sp.j, B.thr, s);
     }
     HIP_TRY(hipStreamWaitEvent(s, early ? O.scans_done : O.done, 0));
@@ -733,7 +798,7 @@ static int search_enqueue_body(vrod_index* idx, Pending& P, const float* d_queri
     st.path = plan.path;
     st.split_pass = plan.split ? 1u : 0u;
 
-    if (N == 0) {  // empty corpus: every slot unfilled
+    if (N == 0 || idx->live() == 0) {  // empty corpus, or every row deleted: every slot unfilled
         std::vector<uint64_t> hi((size_t)nq * k, UINT64_MAX);
         std::vector<uint32_t> hs((size_t)nq * k, kScoreNoneBits);
         HIP_TRY(hipMemcpyAsync(d_out_ids, hi.data(), hi.size() * 8, hipMemcpyHostToDevice, s));
@@ -827,11 +892,12 @@ static int search_enqueue(vrod_index* idx, Pending& P, const float* d_queries_ra
     // (measured at 10k x 128, one query: a replay costs the HOST less -- 50 vs 65 us per search with two
     // in flight -- but is no faster end to end than plain launches, 91 vs 82 us synchronous: only
     // searches begun while another one is pending, i.e. host-bound pipelines, take it)
-    const bool graphable = graphs_on && !P.graph_off && idx->profiling == 0 && nq >= 1 && nq <= 8 && N > 0 && idx->n_pending() >= 1 &&
+    const bool graphable = graphs_on && !P.graph_off && idx->profiling == 0 && nq >= 1 && nq <= 8 && idx->live() > 0 && idx->n_pending() >= 1 &&
                            graph_route(idx->path, nq) && (double)N * idx->ld * idx->esize <= 64.0 * 1048576.0;
     Pending::GraphKey key{};
     if (graphable) {
         key.q = d_queries_raw; key.oi = d_out_ids; key.os = d_out_scores; key.corpus = idx->corpus; key.xn = idx->xnorm2;
+        key.mask = idx->row_mask();
         const void* bufs[12] = {P.q_f32.p, P.q_lp.p, P.small.p, P.hist.p, P.scores.p, P.keys_a.p, P.cand_rows.p, P.cand_fast.p,
                                 P.cand_canon.p, P.h_readback, P.flags, idx->max_xn2_bits};
         memcpy(key.bufs, bufs, sizeof bufs);
@@ -943,7 +1009,7 @@ static int band_pass(vrod_index* idx, Pending& P, std::vector<uint32_t>& failed,
     HIP_TRY(hipMemcpyAsync(hcnt.data(), L.counts, (size_t)nf * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(hok.data(), b_ok, (size_t)nf * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    const uint32_t need = (uint32_t)std::min<uint64_t>(k, N);
+    const uint32_t need = (uint32_t)std::min<uint64_t>(k, idx->live());
     uint32_t maxc = 0, n_res = 0;
     std::vector<uint32_t> hres(nf_pad, 0u);
     for (uint32_t f = 0; f < nf; ++f) {
@@ -1033,7 +1099,7 @@ static int search_complete(vrod_index* idx, Pending& P) {
         const uint64_t score_ld = round_up(N, 64);
         int gmax = rescore_all_max_queries(idx->ld);
         while (gmax > 1 && (uint64_t)gmax * score_ld * 4 > (1ull << 30)) gmax >>= 1;
-        const uint32_t kx = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(k, N), kSelectChunk / 2);
+        const uint32_t kx = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(k, idx->live()), kSelectChunk / 2);   // (the rest: unfilled)
         for (size_t f0 = 0; f0 < failed.size();) {
             int g = gmax;
             while ((size_t)g > failed.size() - f0) g >>= 1;
@@ -1180,6 +1246,58 @@ static int composite_add(vrod_index* idx, const float* rows, uint64_t n, bool sy
         return rc;
     }
     idx->count = count0 + n;
+    return VROD_OK;
+}
+
+// Mark local rows (each < count) deleted: the host mirror, then the changed words on the device (allocated for the whole
+// capacity at the first delete).  A graph captured before holds the old row mask, or none: both slots drop theirs.
+static int index_delete_rows(vrod_index* idx, const std::vector<uint64_t>& rows) {
+    std::vector<uint64_t> fresh;   // rows this call deletes (repeats and rows deleted before are no-ops)
+    uint64_t wlo = UINT64_MAX, whi = 0;
+    for (uint64_t r : rows) {
+        uint32_t& w = idx->del_bits[r / 32];
+        const uint32_t bit = 1u << (r % 32);
+        if (w & bit) continue;
+        w |= bit;
+        fresh.push_back(r);
+        wlo = std::min(wlo, r / 32);
+        whi = std::max(whi, r / 32);
+    }
+    if (fresh.empty()) return VROD_OK;
+    int rc = set_device(idx);
+    hipError_t e = hipSuccess;
+    const bool first = !idx->del_dev;
+    if (rc == VROD_OK && first) {
+        e = hipMalloc((void**)&idx->del_dev, idx->del_bits.size() * 4);
+        if (e != hipSuccess) idx->del_dev = nullptr;
+        wlo = 0; whi = idx->del_bits.size() - 1;   // the whole bitmap
+    }
+    if (rc == VROD_OK && e == hipSuccess)
+        e = hipMemcpyAsync(idx->del_dev + wlo, idx->del_bits.data() + wlo, (whi - wlo + 1) * 4, hipMemcpyHostToDevice, idx->stream);
+    if (rc == VROD_OK && e == hipSuccess) e = hipStreamSynchronize(idx->stream);
+    if (rc != VROD_OK || e != hipSuccess) {   // nothing changes: the mirror forgets this call's rows
+        for (uint64_t r : fresh) idx->del_bits[r / 32] &= ~(1u << (r % 32));
+        if (first && idx->del_dev) { (void)hipFree(idx->del_dev); idx->del_dev = nullptr; }
+        return rc != VROD_OK ? rc : fail(e == hipErrorOutOfMemory ? VROD_ERR_OUT_OF_MEMORY : VROD_ERR_HIP, "uploading the deleted rows: %s", hipGetErrorString(e));
+    }
+    idx->n_deleted += fresh.size();
+    idx->del_gen++;
+    for (Pending& P : idx->slot) {
+        if (P.gexec) { (void)hipGraphExecDestroy(P.gexec); P.gexec = nullptr; }
+        P.gkey_valid = false;
+    }
+    return VROD_OK;
+}
+
+// ids -> (shard, local row) of a composite handle, every id checked before any shard changes
+static int composite_delete(vrod_index* idx, const uint64_t* ids, uint64_t n) {
+    std::vector<std::vector<uint64_t>> local(idx->shards.size());
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t r = ids[i] - idx->id_offset;
+        local[(size_t)((r / kShardBlock) % idx->shards.size())].push_back(local_row_of(idx, r));
+    }
+    for (size_t g = 0; g < idx->shards.size(); ++g)
+        if (!local[g].empty()) VROD_TRY(index_delete_rows(idx->shards[g], local[g]));
     return VROD_OK;
 }
 
@@ -1608,6 +1726,7 @@ int vrod_index_destroy(vrod_index* idx) {
     if (idx->corpus) (void)hipFree(idx->corpus);
     if (idx->planes) (void)hipFree(idx->planes);
     if (idx->xnorm2) (void)hipFree(idx->xnorm2);
+    if (idx->del_dev) (void)hipFree(idx->del_dev);
     if (idx->flags) (void)hipFree(idx->flags);
     if (idx->stream) (void)hipStreamDestroy(idx->stream);
     delete idx;
@@ -1644,6 +1763,28 @@ int vrod_index_add_synthetic(vrod_index* idx, uint64_t seed, uint64_t first_row,
 int vrod_index_count(const vrod_index* idx, uint64_t* out_count) {
     if (!idx || !out_count) return fail(VROD_ERR_INVALID_ARG, "null argument");
     *out_count = idx->count;
+    return VROD_OK;
+}
+
+int vrod_index_delete(vrod_index* idx, const uint64_t* ids, uint64_t n) {
+    if (!idx || (!ids && n)) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    VROD_TRY(require_idle(idx, "vrod_index_delete"));
+    for (uint64_t i = 0; i < n; ++i)   // the whole call or nothing
+        if (ids[i] < idx->id_offset || ids[i] - idx->id_offset >= idx->count)
+            return fail(VROD_ERR_INVALID_ARG, "id %llu is not a row of this handle (ids %llu..%llu)", (unsigned long long)ids[i],
+                        (unsigned long long)idx->id_offset, (unsigned long long)(idx->id_offset + idx->count));
+    if (!n) return VROD_OK;
+    if (idx->composite()) return composite_delete(idx, ids, n);
+    std::vector<uint64_t> rows(ids, ids + n);
+    for (uint64_t& r : rows) r -= idx->id_offset;
+    return index_delete_rows(idx, rows);
+}
+
+int vrod_index_live_count(const vrod_index* idx, uint64_t* out) {
+    if (!idx || !out) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    uint64_t dead = idx->n_deleted;
+    for (const vrod_index* sh : idx->shards) dead += sh->n_deleted;
+    *out = idx->count - dead;
     return VROD_OK;
 }
 

@@ -63,25 +63,31 @@ void launch_rows_get(const void* d_rows, int dtype, uint64_t n, uint32_t dim, ui
 // Also accumulates, per query, a histogram of the top stream_hist_bits(nq_pad) bits of the
 // score keys into d_hist [nq_pad][1 << bits] (must be zeroed by the caller): only the bins at
 // or above each block's own kp-th best are published, which is all the global select needs.
+// d_row_mask (may be null): bit r of word r / 32 set = row r is excluded (deleted): neither its score is written nor is
+// it counted in the histogram (a separate kernel instantiation, launched only with a mask).
 void launch_scan_stream(const void* d_corpus, int dtype, int metric, uint32_t ld, uint64_t nrows,
                         const float* d_q, int nq_pad, float* d_scores, uint64_t score_ld,
-                        uint32_t* d_hist, uint32_t kp, hipStream_t s);
+                        uint32_t* d_hist, uint32_t kp, const uint32_t* d_row_mask, hipStream_t s);
 int stream_hist_bits(int nq_pad);
 int stream_max_queries_per_pass(uint32_t ld);   // 8 .. 1 by LDS capacity, 0: the row does not fit
 // Radix-select step 2: find the histogram bin holding the kp-th best score, then compact
 // every row whose key falls in that bin or a better one into d_keys[q][...] (composite keys,
-// unordered), counting into d_cnt[q].  More than `cap` such rows -> d_status[q] bit 1.
+// unordered), counting into d_cnt[q].  More than `cap` such rows -> d_status[q] bit 1.  Rows set in d_row_mask (may be
+// null) are never collected.
 void launch_hist_compact(const float* d_scores, uint64_t score_ld, uint64_t n, int nq, int metric,
                          const uint32_t* d_hist, int hist_bits, uint32_t kp, uint64_t* d_keys,
-                         uint32_t cap, uint32_t* d_cnt, uint32_t* d_status, hipStream_t s);
+                         uint32_t cap, uint32_t* d_cnt, uint32_t* d_status, const uint32_t* d_row_mask,
+                         hipStream_t s);
 
 // ---- kernels_select.hip
 // Level 0: fast scores (implicit ids = column index) -> per-chunk top-kp composite keys.
 // Later levels: keys -> keys.  Returns the number of keys per query written to d_out.
-// chunk capacity is kSelectChunk (search_plan.h); kp <= kSelectChunk/2.
+// chunk capacity is kSelectChunk (search_plan.h); kp <= kSelectChunk/2.  Level 0 leaves the rows set in d_row_mask
+// (may be null) out: they become the empty key 0, which ranks below every row (a NaN score included) and is emitted as
+// an unfilled slot.
 uint64_t launch_select_from_scores(const float* d_scores, uint64_t score_ld, uint64_t n, int nq,
                                    int metric, uint32_t kp, uint64_t* d_out, uint64_t out_ld,
-                                   hipStream_t s);
+                                   const uint32_t* d_row_mask, hipStream_t s);
 uint64_t launch_select_from_keys(const uint64_t* d_in, uint64_t in_ld, uint64_t n, int nq,
                                  uint32_t kp, uint64_t* d_out, uint64_t out_ld, hipStream_t s);
 // Final step of a select chain: keys (n <= kSelectChunk per query, sorted or not) ->
@@ -105,6 +111,10 @@ void launch_list_compact(uint2* d_lists, uint32_t* d_counts, uint32_t cap, int n
 // (exact, 3-pass radix select on the order-preserving key).  One block per query.
 void launch_sample_select(const float* d_scores, uint64_t score_ld, uint32_t n_sample, int nq,
                           int metric, uint32_t j, float* d_thr, hipStream_t s);
+// Dense sample block of a handle with deleted rows: column c of every query (c < n_sample) becomes the worst score when
+// row row0 + c is set in d_row_mask, so that the sample's j-th best is that of live rows only.
+void launch_mask_sample(float* d_scores, uint64_t score_ld, uint32_t n_sample, int nq, uint64_t row0,
+                        const uint32_t* d_row_mask, int metric, hipStream_t s);
 // Final: canonical scores of the kp candidates -> sorted top-k (ids u64 = idmap(row)),
 // certificate per query in d_status bit 0 (1 = NOT certified).
 // The certificate's bound on |fast - canonical| is formed on the device from the max squared
@@ -189,6 +199,7 @@ struct MfmaScanArgs {
     void* dump;             // mfma_dump_bytes(num_cus) bytes of scratch: where the 4-wave kernel spills full hit logs (filtered launches)
     uint32_t* claims;       // kMfmaClaimWords words: claim bits of the 4-wave kernel's work stealing for THIS launch; null: off
     bool claims_is_zero;    // the caller already cleared them (else the launcher issues a memset)
+    const uint32_t* row_mask;   // filtered launches: bit r of word r / 32 set = row r is never appended (deleted); null: none
 };
 void launch_scan_mfma(const MfmaScanArgs& a, int dtype, int num_cus, hipStream_t s);
 

@@ -86,6 +86,25 @@ class Index:
         check(self._L.vrod_index_count(self._h, C.byref(out)))
         return out.value
 
+    def delete(self, ids):
+        """Delete rows by the ids searches report (vrod_index_delete): any integer array-like, all or nothing."""
+        a = np.asarray(ids)
+        if a.size and a.dtype.kind not in "iu" and not isinstance(ids, np.ndarray):
+            # a sequence of Python ints that numpy could not give one integer dtype (e.g. 1 and 2**63 together)
+            flat = list(np.asarray(ids, dtype=object).reshape(-1))
+            if all(isinstance(x, (int, np.integer)) and not isinstance(x, bool) for x in flat):
+                a = np.array([int(x) for x in flat], dtype=np.uint64)
+        if a.size and a.dtype.kind not in "iu":
+            raise TypeError(f"ids must be integers, got {a.dtype}")
+        a = np.ascontiguousarray(a.astype(np.uint64, copy=False).reshape(-1))
+        check(self._L.vrod_index_delete(self._h, a.ctypes.data_as(C.c_void_p), a.size))
+
+    def live_count(self) -> int:
+        """Rows added minus rows deleted."""
+        out = C.c_uint64()
+        check(self._L.vrod_index_live_count(self._h, C.byref(out)))
+        return out.value
+
     def set_id_offset(self, off: int):
         check(self._L.vrod_index_set_id_offset(self._h, int(off)))
 
