@@ -20,6 +20,12 @@ pub const VROD_METRIC_L2: c_int = 1;
 pub const VROD_METRIC_IP: c_int = 2;
 pub const VROD_ID_NONE: u64 = u64::MAX;
 pub const VROD_MAX_K: u32 = 3584;
+pub const VROD_PATH_AUTO: c_int = 0;
+pub const VROD_PATH_STREAM: c_int = 1;
+pub const VROD_PATH_MFMA: c_int = 2;
+pub const VROD_PATH_EXACT: c_int = 3;
+/// Filtered searches: canonical scores of the eligible rows only.
+pub const VROD_PATH_GATHER: c_int = 4;
 
 #[repr(C)]
 #[derive(Debug, Default, Clone, Copy)]
@@ -56,6 +62,8 @@ extern "C" {
     pub fn vrod_index_get_rows(idx: *mut vrod_index, first: u64, n: u64, out_rows: *mut f32) -> c_int;
     pub fn vrod_index_delete(idx: *mut vrod_index, ids: *const u64, n: u64) -> c_int;
     pub fn vrod_index_live_count(idx: *const vrod_index, out: *mut u64) -> c_int;
+    pub fn vrod_index_set_filter(idx: *mut vrod_index, allow_words: *const u32, n_rows: u64) -> c_int;
+    pub fn vrod_index_filter_count(idx: *const vrod_index, out: *mut u64) -> c_int;
     pub fn vrod_search(idx: *mut vrod_index, queries: *const f32, nq: u32, k: u32,
                        out_ids: *mut u64, out_scores: *mut f32) -> c_int;
     pub fn vrod_search_device(idx: *mut vrod_index, d_queries: *const f32, nq: u32, k: u32,
@@ -159,7 +167,32 @@ impl Collection {
         n
     }
 
-    /// Best-first `(ids, scores)`, `queries.len() * k` each; slots past `live_len()` are `(u64::MAX, NaN)`.
+    /// Allow-list filter for every later search: `Some(allowed)` -- entry i true = id offset + i may be returned, rows
+    /// past `allowed.len()` (rows added later included) may not -- or `None` to clear.  `allowed.len()` must not exceed
+    /// `len()`.  Results are those of the same search over the rows that are live and allowed.
+    pub fn set_filter(&mut self, allowed: Option<&[bool]>) -> Result<(), ScanError> {
+        match allowed {
+            None => check(unsafe { vrod_index_set_filter(self.idx, std::ptr::null(), 0) }),
+            Some(a) => {
+                let mut words = vec![0u32; a.len() / 32 + 1];
+                for (i, &b) in a.iter().enumerate() {
+                    if b {
+                        words[i / 32] |= 1u32 << (i % 32);
+                    }
+                }
+                check(unsafe { vrod_index_set_filter(self.idx, words.as_ptr(), a.len() as u64) })
+            }
+        }
+    }
+
+    /// Rows the next search may return: live and allowed (`live_len()` without a filter).
+    pub fn filter_len(&self) -> u64 {
+        let mut n = 0u64;
+        unsafe { vrod_index_filter_count(self.idx, &mut n) };
+        n
+    }
+
+    /// Best-first `(ids, scores)`, `queries.len() * k` each; slots past `filter_len()` are `(u64::MAX, NaN)`.
     pub fn search(&self, queries: &[Vec<f32>], k: usize) -> Result<(Vec<u64>, Vec<f32>), ScanError> {
         for q in queries {
             if q.len() != self.dim {

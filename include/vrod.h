@@ -74,7 +74,8 @@ enum { VROD_METRIC_COSINE = 0, VROD_METRIC_L2 = 1, VROD_METRIC_IP = 2 };
 #define VROD_MAX_DIM 32768u   /* one prepared row (fp32) must fit in a work-group's LDS next to its tiles */
 
 /* Which fast pass vrod_search uses. AUTO picks by batch size and dtype. */
-enum { VROD_PATH_AUTO = 0, VROD_PATH_STREAM = 1, VROD_PATH_MFMA = 2, VROD_PATH_EXACT = 3 };
+enum { VROD_PATH_AUTO = 0, VROD_PATH_STREAM = 1, VROD_PATH_MFMA = 2, VROD_PATH_EXACT = 3,
+       VROD_PATH_GATHER = 4 };   /* filtered searches: canonical scores of the eligible rows only */
 
 /* Counters of the most recently COMPLETED search on a handle (bench.py / tests read these). */
 typedef struct {
@@ -144,6 +145,17 @@ int vrod_index_set_id_offset(vrod_index *idx, uint64_t offset);
 int vrod_index_delete(vrod_index *idx, const uint64_t *ids, uint64_t n);
 /* Rows added minus rows deleted. */
 int vrod_index_live_count(const vrod_index *idx, uint64_t *out);
+/* Allow-list filter (one per handle): every search after this call -- any entry point, path, dtype or metric,
+ * pipelined, replayed, multi-device -- returns bit for bit what the same search returns over the ELIGIBLE rows alone
+ * (live and allowed; ties still broken by smaller id; slots beyond the eligible rows are (VROD_ID_NONE, NaN)), until
+ * the filter is cleared or replaced.  allow_words: host memory, ceil(n_rows/32) words in the deleted-row layout: bit
+ * i % 32 of word i / 32 set = id offset + i is allowed.  Rows at index >= n_rows are not allowed, rows added later
+ * included.  n_rows > count: VROD_ERR_INVALID_ARG, nothing changes.  (NULL, 0) clears the filter.  Deletes made
+ * after the call are honoured.  A multi-device handle routes the bits to its shards (global ids, as deletes).
+ * While a search is pending: VROD_ERR_INVALID_ARG. */
+int vrod_index_set_filter(vrod_index *idx, const uint32_t *allow_words, uint64_t n_rows);
+/* Rows the next search may return: live and allowed (= vrod_index_live_count without a filter). */
+int vrod_index_filter_count(const vrod_index *idx, uint64_t *out);
 /* Copy prepared rows [first, first+n) back as fp32 (bf16 widened): n x dim. */
 int vrod_index_get_rows(vrod_index *idx, uint64_t first, uint64_t n, float *out_rows);
 

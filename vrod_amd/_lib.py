@@ -16,7 +16,8 @@ LIB_PATH = os.environ.get("VROD_HIP_LIB") or os.path.join(_HERE, "libvrod_hip.so
 SYMBOLS = [
     "vrod_index_create", "vrod_index_destroy", "vrod_index_reserve", "vrod_index_add",
     "vrod_index_add_synthetic", "vrod_index_count", "vrod_index_set_id_offset",
-    "vrod_index_get_rows", "vrod_index_delete", "vrod_index_live_count", "vrod_search", "vrod_search_device", "vrod_search_synthetic_device",
+    "vrod_index_get_rows", "vrod_index_delete", "vrod_index_live_count",
+    "vrod_index_set_filter", "vrod_index_filter_count", "vrod_search", "vrod_search_device", "vrod_search_synthetic_device",
     "vrod_search_begin_device", "vrod_search_begin_synthetic_device", "vrod_search_end", "vrod_search_pending",
     "vrod_merge_topk_device", "vrod_merge_topk_packed_device", "vrod_index_set_path", "vrod_index_set_profiling",
     "vrod_index_last_stats", "vrod_index_shard_stats", "vrod_last_error", "vrod_version", "vrod_synth_rows_device",
@@ -74,6 +75,8 @@ def load() -> C.CDLL:
     L.vrod_index_get_rows.argtypes = [vp, u64, u64, vp]
     L.vrod_index_delete.argtypes = [vp, vp, u64]
     L.vrod_index_live_count.argtypes = [vp, C.POINTER(u64)]
+    L.vrod_index_set_filter.argtypes = [vp, vp, u64]
+    L.vrod_index_filter_count.argtypes = [vp, C.POINTER(u64)]
     L.vrod_search.argtypes = [vp, vp, u32, u32, vp, vp]
     L.vrod_search_device.argtypes = [vp, vp, u32, u32, vp, vp, vp]
     L.vrod_search_synthetic_device.argtypes = [vp, u64, u64, u32, u32, vp, vp, vp]

@@ -178,18 +178,29 @@ __device__ __forceinline__ float sub_rn_s(float s, float b) {
     return r;
 }
 
-template <typename T, int METRIC, int NQ>
+//
+// LIST (the gather path of a filtered search, rescore_list): the same chains over the rows a list names -- column c is
+// row list[c], c < nrows -- for a whole block of `nq_list` consecutive queries of `q`.  Block b takes query group
+// b % n_qgroups (NQ queries; a short last group repeats its last query and writes only its own) and list tile
+// b / n_qgroups, so that the blocks in flight together share their 64 rows through L2.
+template <typename T, int METRIC, int NQ, bool LIST>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void rescore_all_kernel(const T* __restrict__ corpus, uint32_t dim, uint32_t ld,
                                                          const float* __restrict__ q, RescoreQuerySet qs,
-                                                         uint64_t nrows, float* __restrict__ out, uint64_t out_ld) {
+                                                         uint64_t nrows, float* __restrict__ out, uint64_t out_ld,
+                                                         const uint32_t* __restrict__ list, uint32_t nq_list, uint32_t n_qgroups) {
     constexpr int EPU = 16 / (int)sizeof(T);
     constexpr int LPC = 64 / EPU;
     constexpr int RPI = 64 / LPC;
     constexpr int NI = 64 / RPI;
     __shared__ __attribute__((aligned(16))) float tile[64 * kTileStride];
     const int lane = threadIdx.x;
-    const uint64_t row0 = (uint64_t)blockIdx.x * 64;
+    const uint32_t qg = LIST ? blockIdx.x % n_qgroups : 0u;
+    const uint64_t row0 = (uint64_t)(LIST ? blockIdx.x / n_qgroups : blockIdx.x) * 64;
     const uint64_t slot = row0 + lane;
+    if constexpr (LIST) {
+#pragma unroll
+        for (int n = 0; n < NQ; ++n) qs.qi[n] = qg * NQ + n < nq_list ? qg * NQ + n : nq_list - 1;
+    }
     const bool valid = slot < nrows;
     const int nvalid = nrows - row0 < 64 ? (int)(nrows - row0) : 64;   // rows are a prefix of the wave
     const int ni_used = (nvalid + RPI - 1) / RPI;
@@ -210,6 +221,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
             if (it < ni_used) {
                 uint64_t row = row0 + it * RPI + sub;
                 if (row >= nrows) row = row0;
+                if constexpr (LIST) row = list[row];
                 if (e0 < ld) vs[it] = *reinterpret_cast<const u32x4*>(corpus + row * ld + e0);
             }
         }
@@ -278,7 +290,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
     }
     if (valid) {
 #pragma unroll
-        for (int n = 0; n < NQ; ++n) out[(uint64_t)n * out_ld + slot] = acc[n];
+        for (int n = 0; n < NQ; ++n) {
+            if constexpr (LIST) {
+                if (qg * NQ + n < nq_list) out[(uint64_t)(qg * NQ + n) * out_ld + slot] = acc[n];
+            } else {
+                out[(uint64_t)n * out_ld + slot] = acc[n];
+            }
+        }
     }
 }
 
@@ -309,7 +327,7 @@ void launch_rescore_all(const void* d_corpus, int dtype, int metric, uint32_t di
     RescoreQuerySet qs;
     for (int i = 0; i < 8; ++i) qs.qi[i] = query_index[i < nq ? i : nq - 1];
     const unsigned grid = (unsigned)((nrows + 63) / 64);
-#define VROD_RA(TT, MM, NN) rescore_all_kernel<TT, MM, NN><<<grid, 64, 0, s>>>((const TT*)d_corpus, dim, ld, d_q, qs, nrows, d_out, out_ld)
+#define VROD_RA(TT, MM, NN) rescore_all_kernel<TT, MM, NN, false><<<grid, 64, 0, s>>>((const TT*)d_corpus, dim, ld, d_q, qs, nrows, d_out, out_ld, nullptr, 0u, 1u)
 #define VROD_RA_N(TT, MM)                                                                           \
     switch (nq) {                                                                                   \
         case 1: VROD_RA(TT, MM, 1); break;                                                          \
@@ -321,6 +339,27 @@ void launch_rescore_all(const void* d_corpus, int dtype, int metric, uint32_t di
     else { if (metric == M_COSINE) { VROD_RA_N(float, M_COSINE) } else { VROD_RA_N(float, M_L2) } }
 #undef VROD_RA_N
 #undef VROD_RA
+}
+
+void launch_rescore_list(const void* d_corpus, int dtype, int metric, uint32_t dim, uint32_t ld, const float* d_q, uint32_t nq,
+                         const uint32_t* d_list, uint64_t m, float* d_out, uint64_t out_ld, hipStream_t s) {
+    if (!m || !nq) return;
+    RescoreQuerySet qs{};
+    const int nqb = nq >= 8 ? 8 : nq >= 4 ? 4 : nq >= 2 ? 2 : 1;   // queries per lane: 8 once the batch has them
+    const uint32_t n_qgroups = (nq + nqb - 1) / nqb;
+    const unsigned grid = (unsigned)(((m + 63) / 64) * n_qgroups);
+#define VROD_RL(TT, MM, NN) rescore_all_kernel<TT, MM, NN, true><<<grid, 64, 0, s>>>((const TT*)d_corpus, dim, ld, d_q, qs, m, d_out, out_ld, d_list, nq, n_qgroups)
+#define VROD_RL_N(TT, MM)                                                                           \
+    switch (nqb) {                                                                                  \
+        case 1: VROD_RL(TT, MM, 1); break;                                                          \
+        case 2: VROD_RL(TT, MM, 2); break;                                                          \
+        case 4: VROD_RL(TT, MM, 4); break;                                                          \
+        default: VROD_RL(TT, MM, 8); break;                                                         \
+    }
+    if (dtype == DT_BF16) { if (metric == M_COSINE) { VROD_RL_N(bf16_t, M_COSINE) } else { VROD_RL_N(bf16_t, M_L2) } }
+    else { if (metric == M_COSINE) { VROD_RL_N(float, M_COSINE) } else { VROD_RL_N(float, M_L2) } }
+#undef VROD_RL_N
+#undef VROD_RL
 }
 
 }  // namespace vrod

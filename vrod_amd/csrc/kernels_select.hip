@@ -705,6 +705,33 @@ void launch_keys_to_output(const uint64_t* d_keys, uint64_t n, int metric, uint3
     keys_to_output_kernel<<<1, kSortThreads, sort_lds_bytes(n), s>>>(d_keys, (uint32_t)n, metric, k, idmap, d_out_ids, d_out_scores);
 }
 
+// Gather path: keys of nq queries (query q's n <= kSelectChunk keys at keys + q * key_ld) whose rows are COLUMNS of the
+// listed rows: column c is row list[c].  The list is ascending, so the column order is the row order and the keys'
+// tie-break by smaller column is the tie-break by smaller id.  One block per query, outputs [nq][k].
+__global__ __launch_bounds__(kSortThreads) void list_keys_to_output_kernel(
+    const uint64_t* __restrict__ keys, uint64_t key_ld, uint32_t n, int metric, uint32_t k, const uint32_t* __restrict__ list,
+    IdMap idmap, uint64_t* __restrict__ out_ids, float* __restrict__ out_scores) {
+    extern __shared__ __attribute__((aligned(16))) uint64_t skeys[];
+    const uint32_t q = blockIdx.x;
+    const uint32_t np2 = pow2_ceil(n < 2 ? 2 : n);
+    for (uint32_t i = threadIdx.x; i < np2; i += kSortThreads) skeys[i] = i < n ? keys[(uint64_t)q * key_ld + i] : 0ull;
+    __syncthreads();
+    bitonic_sort_desc(skeys, np2);
+    for (uint32_t i = threadIdx.x; i < k; i += kSortThreads) {
+        const uint64_t key = i < np2 ? skeys[i] : 0ull;
+        out_ids[(uint64_t)q * k + i] = key ? idmap(list[key_row(key)]) : UINT64_MAX;
+        out_scores[(uint64_t)q * k + i] = key ? key_to_score_rt(key_skey(key), metric) : __uint_as_float(kScoreNoneBits);
+    }
+}
+
+void launch_list_keys_to_output(const uint64_t* d_keys, uint64_t key_ld, uint64_t n, int nq, int metric, uint32_t k,
+                                const uint32_t* d_list, const IdMap& idmap, uint64_t* d_out_ids, float* d_out_scores,
+                                hipStream_t s) {
+    if (nq <= 0) return;
+    list_keys_to_output_kernel<<<nq, kSortThreads, sort_lds_bytes(n), s>>>(d_keys, key_ld, (uint32_t)n, metric, k, d_list, idmap,
+                                                                            d_out_ids, d_out_scores);
+}
+
 // ------------------------------------------------------------------ shard merge (after the all-gather)
 // Each of the n_lists inputs is sorted best-first with unique ids, so an element's output
 // position is its own index plus, for every other list, the number of that list's

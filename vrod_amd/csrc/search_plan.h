@@ -59,6 +59,50 @@ inline bool graph_route(int forced, uint32_t nq) {
     return forced == VROD_PATH_STREAM || (forced == VROD_PATH_AUTO && nq <= 4);
 }
 
+// ------------------------------------------------------------------ filtered searches: dense scan or gather
+// A handle with an allow-list filter (vrod_index_set_filter) has m eligible rows of its N.  The dense paths scan all N
+// rows and drop the rest; the gather path (VROD_PATH_GATHER) computes the canonical score of the m eligible rows only
+// (kernels_rescore.hip, the list form of rescore_all_kernel) -- no fast pass, no certificate, exact by construction.
+// Both estimates are linear in the batch:
+//   dense  = N * (row_bytes * kDenseNsPerByte + nq * dim * (kDenseNsPerStep[dtype] + kDenseNsPerMaskedStep * log10(N / m)))
+//   gather = m * (row_bytes * kGatherNsPerByte + nq * dim * kGatherNsPerStep)
+// The log term is what a narrow filter costs the batched scan: its thresholds are the k'-th best ELIGIBLE scores, which
+// rows the filter drops beat too, and a dropped row's hit is dumped from the tile before the hit-log pass masks it.  The choice is
+// monotone: gather at m = 0, dense at m = N, and a filter that is dense at (m, nq) stays dense for every larger m or nq
+// (gather / dense grows with nq while kGatherNsPerStep * kDenseNsPerByte / kGatherNsPerByte exceeds the dense per-step
+// cost, 1.0e-4 against at most 3e-6 + 3e-7 * log10(2^32)).
+// Constants: MI355X, 10M x 768 bf16 cosine, k = 10, median ms per batch (scripts/probes/filter_probe.py,
+// profiles/filter/README.md):
+//   eligible            100 %   50 %    10 %    1 %     0.1 %   0.01 %
+//   batch 1024 dense    11.54   11.71   12.51   16.41   26.05   36.63    (MFMA)
+//   batch 1024 gather   -       623.9   121.6   12.28   1.436   0.241
+//   batch 4 dense       2.885   2.922   2.912   2.691   2.526   2.484    (stream)
+//   batch 4 gather      8.168   4.195   0.968   0.234   0.213   0.156
+// dense: 2.9 ms per 15.4 GB pass -> 2.0e-4 ns per corpus byte; 11.5 - 2.9 ms over 10M x 1024 x 768 -> ~1.0e-6 ns per
+// step on bf16 rows (an fp32 corpus: 3x, the split pass's three products); +4.9 / +14.5 / +25 ms at 1 / 0.1 / 0.01 %
+// -> ~3e-7 ns per step and decade of N / m.  gather: 6.4e12 chain steps per second at batch 1024 -> 1.56e-4 ns per step;
+// batch 4 at 10 % (0.97 ms, 1M rows) -> ~3.0e-4 ns per gathered row byte.
+struct FilterCost { double dense_ns, gather_ns; };
+constexpr double kDenseNsPerByte = 2.0e-4, kGatherNsPerByte = 3.0e-4;
+constexpr double kDenseNsPerStepBf16 = 1.0e-6, kDenseNsPerStepF32 = 3.0e-6, kDenseNsPerMaskedStep = 3.0e-7;
+constexpr double kGatherNsPerStep = 1.56e-4;
+inline FilterCost filter_cost(int dtype, uint64_t N, uint64_t m, uint32_t nq, uint32_t dim) {
+    const double row_bytes = (double)dim * (dtype == VROD_DTYPE_BF16 ? 2.0 : 4.0);
+    const double steps = (double)nq * dim;
+    const double masked = m > 0 && m < N ? std::log10((double)N / (double)m) : 0.0;
+    const double dense_step = (dtype == VROD_DTYPE_BF16 ? kDenseNsPerStepBf16 : kDenseNsPerStepF32) + kDenseNsPerMaskedStep * masked;
+    return {(double)N * (row_bytes * kDenseNsPerByte + steps * dense_step), (double)m * (row_bytes * kGatherNsPerByte + steps * kGatherNsPerStep)};
+}
+// Whether a search over m eligible rows of N takes the gather path.  `forced`: the handle's path -- GATHER always
+// gathers, a forced dense path never does, AUTO compares the two estimates.
+inline bool filter_route(int forced, int dtype, uint64_t N, uint64_t m, uint32_t nq, uint32_t dim) {
+    if (forced == VROD_PATH_GATHER) return true;
+    if (forced != VROD_PATH_AUTO) return false;
+    if (m == 0) return true;
+    const FilterCost c = filter_cost(dtype, N, m, nq, dim);
+    return c.gather_ns < c.dense_ns;
+}
+
 // ------------------------------------------------------------------ k'
 // Candidates per query the fast pass hands to the canonical re-score.  `kp_boost` is the handle's margin multiplier
 // (KpBoost), `kp_margin` VROD_DEBUG_KP_MARGIN (0: the default 8).

@@ -181,8 +181,19 @@ struct vrod_index {
     std::vector<uint32_t> del_bits;    // [capacity / 32]
     uint32_t* del_dev = nullptr;       // [capacity / 32] on the device, or null
     uint64_t n_deleted = 0;
-    uint64_t del_gen = 0;              // bumped by every delete that changes the bitmap
+    uint64_t mask_gen = 0;             // bumped by every change of the row mask's contents (delete, set_filter)
     struct SampleWindow { uint64_t S = 0, N = 0, gen = 0, first = 0; bool valid = false; } sample_win;
+
+    // allow-list filter (vrod_index_set_filter): the allowed rows (bit set = allowed) and the EFFECTIVE mask the kernels
+    // get while a filter is set, deleted | ~allowed -- host mirrors over the capacity plus a device copy.  Rows past the
+    // filter's n_rows (rows added later included) are not allowed: the effective mask grows with ones.
+    bool filter_on = false;
+    std::vector<uint32_t> allow_bits, eff_bits;   // [capacity / 32] while filter_on
+    uint32_t* eff_dev = nullptr;                  // [capacity / 32] on the device while filter_on
+    uint64_t n_eligible = 0;                      // rows < count that are live and allowed
+    // gather path: ascending local indices of the eligible rows, built for mask generation list_gen
+    DevBuf list_dev;
+    uint64_t list_gen = UINT64_MAX, list_n = 0;
 
     // workspaces
     DevBuf raw_stage, nrm_ws, out_ids, out_scores;
@@ -233,8 +244,13 @@ struct vrod_index {
 
     size_t row_bytes() const { return (size_t)ld * esize; }
     uint64_t live() const { return count - n_deleted; }
-    // what the kernels get as their row mask: null while nothing is deleted
-    const uint32_t* row_mask() const { return n_deleted ? del_dev : nullptr; }
+    // rows a search may return: live, and allowed while a filter is set
+    uint64_t eligible() const { return filter_on ? n_eligible : live(); }
+    // what the kernels get as their row mask: the effective mask while a filter is set, else the deleted rows, and null
+    // while nothing is deleted
+    const uint32_t* row_mask() const { return filter_on ? eff_dev : n_deleted ? del_dev : nullptr; }
+    // its host mirror (meaningful while row_mask() is non-null)
+    const std::vector<uint32_t>& mask_bits() const { return filter_on ? eff_bits : del_bits; }
 };
 
 static int set_device(const vrod_index* idx) {
@@ -291,11 +307,34 @@ static int index_reserve(vrod_index* idx, uint64_t n_rows) {
             return fail(VROD_ERR_HIP, "growing the deleted-row bitmap failed: %s", hipGetErrorString(de));
         }
     }
+    uint32_t* ne = nullptr;   // the effective mask of a filter: the new rows are not allowed (ones)
+    std::vector<uint32_t> eff_grown;
+    if (idx->filter_on) {
+        eff_grown = idx->eff_bits;
+        eff_grown.resize(want / 32, ~0u);
+        hipError_t fe = hipMalloc((void**)&ne, want / 32 * 4);
+        if (fe == hipSuccess) fe = hipMemcpyAsync(ne, eff_grown.data(), eff_grown.size() * 4, hipMemcpyHostToDevice, idx->stream);
+        if (fe == hipSuccess) fe = hipStreamSynchronize(idx->stream);
+        if (fe != hipSuccess) {
+            (void)hipStreamSynchronize(idx->stream);
+            if (ne) (void)hipFree(ne);
+            if (nd) (void)hipFree(nd);
+            (void)hipFree(nc);
+            (void)hipFree(nx);
+            return fail(VROD_ERR_HIP, "growing the filter's row mask failed: %s", hipGetErrorString(fe));
+        }
+    }
     if (idx->corpus) (void)hipFree(idx->corpus);
     if (idx->xnorm2) (void)hipFree(idx->xnorm2);
     if (idx->planes) { (void)hipFree(idx->planes); idx->planes = nullptr; idx->planes_cap = idx->planes_rows = 0; }   // rebuilt lazily
     if (idx->del_dev) { (void)hipFree(idx->del_dev); idx->del_dev = nd; }
     idx->del_bits.resize(want / 32, 0u);
+    if (idx->filter_on) {
+        if (idx->eff_dev) (void)hipFree(idx->eff_dev);
+        idx->eff_dev = ne;
+        idx->eff_bits.swap(eff_grown);
+        idx->allow_bits.resize(want / 32, 0u);
+    }
     idx->corpus = nc;
     idx->xnorm2 = nx;
     idx->capacity = want;
@@ -465,13 +504,14 @@ struct Timer {
 // select chain over fast (or canonical) scores of `nq` queries -> keys of <= kSelectChunk per query
 // returns pointer/ld/n of the final key set through out params.
 // (the handle's deleted rows are left out at the first level: they never reach the keys)
+// `mask`: the row mask of the columns (the handle's row_mask() when column = row; null for the gather path's columns)
 static int select_chain(vrod_index* idx, Pending& P, const float* d_scores, uint64_t score_ld, uint64_t n, int nq,
-                        uint32_t kp, const uint64_t** out_keys, uint64_t* out_ld, uint64_t* out_n) {
+                        uint32_t kp, const uint32_t* mask, const uint64_t** out_keys, uint64_t* out_ld, uint64_t* out_n) {
     const uint64_t nch0 = (n + kSelectChunk - 1) / kSelectChunk;
     const uint64_t ld_a = nch0 * kp;
     VROD_TRY(P.keys_a.ensure((size_t)nq * ld_a * 8));
     uint64_t cur_n = launch_select_from_scores(d_scores, score_ld, n, nq, score_form(idx->metric), kp, P.keys_a.as<uint64_t>(), ld_a,
-                                               idx->row_mask(), P.stream);
+                                               mask, P.stream);
     const uint64_t* cur = P.keys_a.as<uint64_t>();
     uint64_t cur_ld = ld_a;
     bool a_is_cur = true;
@@ -646,20 +686,26 @@ static int stream_pass(vrod_index* idx, Pending& P, Timer& tm, bool in_graph) {
     return VROD_OK;
 }
 
-// First row of the sample pass's S rows on a handle with deleted rows.  Any window gives a valid threshold (its deleted
-// rows are masked to the worst score, and every window row is scanned again by the filtered stages), but one made of
-// deleted rows gives none: the first stage would then append every row, overflow its lists and send every query to the
-// exact path.  The window stays at row 0 while at least 7/8 of it is live; else it moves to the tile-aligned window
-// with the most live rows (first of equals).  Cached until the bitmap or the stage plan changes.
+// First row of the sample pass's S rows on a handle with a row mask (deleted rows, or a filter: the window's rows that a
+// search may not return).  Any window gives a valid threshold (its masked rows are masked to the worst score, and every
+// window row is scanned again by the filtered stages), but one made of masked rows gives none: the first stage would
+// then append every row, overflow its lists and send every query to the exact path.  The window stays at row 0 while
+// at least 7/8 of it is eligible; else it moves to the tile-aligned window with the most eligible rows (first of
+// equals).  Cached until the mask or the stage plan changes.
+// (The rank j is taken among the window's eligible rows without rescaling: the first stage's rows are as sparse in
+// eligible rows as the window's, so its expected hits per query stay ~j * (stage rows) / S whatever the filter's
+// density -- only a window with fewer than j eligible rows loosens the threshold to the worst score, and then the
+// first stage has about as few eligible rows to append.)
 static uint64_t sample_window(vrod_index* idx, uint64_t S, uint64_t N) {
-    if (!idx->n_deleted || S >= N) return 0;
+    if (!idx->row_mask() || S >= N) return 0;
     vrod_index::SampleWindow& W = idx->sample_win;
-    if (W.valid && W.S == S && W.N == N && W.gen == idx->del_gen) return W.first;
+    if (W.valid && W.S == S && W.N == N && W.gen == idx->mask_gen) return W.first;
     const uint64_t tiles = N / kRowTile, wt = S / kRowTile;   // S < N is a whole number of tiles (plan_stages)
+    const std::vector<uint32_t>& mb = idx->mask_bits();
     std::vector<uint32_t> live(tiles);
     for (uint64_t t = 0; t < tiles; ++t) {
         uint32_t dead = 0;
-        for (uint32_t w = 0; w < kRowTile / 32; ++w) dead += (uint32_t)__builtin_popcount(idx->del_bits[t * (kRowTile / 32) + w]);
+        for (uint32_t w = 0; w < kRowTile / 32; ++w) dead += (uint32_t)__builtin_popcount(mb[t * (kRowTile / 32) + w]);
         live[t] = kRowTile - dead;
     }
     uint64_t cur = 0;
@@ -672,8 +718,77 @@ static uint64_t sample_window(vrod_index* idx, uint64_t S, uint64_t N) {
             if (cur > best) { best = cur; first = t * kRowTile; }
         }
     }
-    W = {S, N, idx->del_gen, first, true};
+    W = {S, N, idx->mask_gen, first, true};
     return first;
+}
+
+// -------- gather path (VROD_PATH_GATHER): the canonical score of the eligible rows only, for every query of the batch,
+// and an exact select by (score, id).  No fast pass, no certificate: exact by construction.
+// The row list -- ascending local indices of the eligible rows -- is built on the host from the mask's mirror and
+// uploaded once per mask generation.  The generation only changes while the handle is idle (delete and set_filter
+// require it), and a completed search's launches are behind its done event: no launch still reads the old list.
+static int gather_list(vrod_index* idx) {
+    if (idx->list_gen == idx->mask_gen && idx->list_n == idx->eligible()) return VROD_OK;
+    const uint32_t* mask = idx->row_mask() ? idx->mask_bits().data() : nullptr;
+    std::vector<uint32_t> rows;
+    rows.reserve(idx->eligible());
+    for (uint64_t w = 0; w * 32 < idx->count; ++w) {
+        uint32_t keep = mask ? ~mask[w] : ~0u;
+        if (idx->count - w * 32 < 32) keep &= (1u << (idx->count - w * 32)) - 1u;
+        while (keep) {
+            rows.push_back((uint32_t)(w * 32 + (uint32_t)__builtin_ctz(keep)));
+            keep &= keep - 1u;
+        }
+    }
+    if (!rows.empty()) {
+        VROD_TRY(idx->list_dev.ensure(rows.size() * 4));
+        HIP_TRY(hipMemcpy(idx->list_dev.p, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
+    }
+    idx->list_n = rows.size();
+    idx->list_gen = idx->mask_gen;
+    return VROD_OK;
+}
+
+static int gather_pass(vrod_index* idx, Pending& P, Timer& tm) {
+    VROD_TRY(gather_list(idx));
+    const uint64_t m = idx->list_n;
+    const uint32_t nq = P.nq, k = P.k;
+    const int form = score_form(idx->metric);
+    vrod_search_stats& st = P.st;
+    hipStream_t s = P.stream;
+    const uint32_t* list = idx->list_dev.as<uint32_t>();
+    // queries per launch: the whole batch while its score block [g][m] stays under 1 GiB (as the exact path's)
+    const uint64_t score_ld = round_up(m, 64);
+    uint64_t g = std::max<uint64_t>(1, (1ull << 30) / (score_ld * 4));
+    if (g >= nq) g = nq;
+    else if (g > 8) g = g / 8 * 8;
+    const uint32_t kx = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(k, m), kSelectChunk / 2);   // (the rest: unfilled)
+    VROD_TRY(P.scores.ensure((size_t)g * score_ld * 4));
+    for (uint32_t q0 = 0; q0 < nq; q0 += (uint32_t)g) {
+        const uint32_t gc = (uint32_t)std::min<uint64_t>(g, nq - q0);
+        size_t a = 0, b = 0;
+        if (idx->profiling) {   // (no launch-attached events here: markers around the launch)
+            tm.arm(a, b);
+            g_launch_events = LaunchEvents{};
+            if (b) HIP_TRY(hipEventRecord(P.ev[a], s));
+        }
+        launch_rescore_list(idx->corpus, idx->dtype, form, idx->dim, idx->ld, P.q_f32.as<float>() + (size_t)q0 * idx->ld, gc, list, m,
+                            P.scores.as<float>(), score_ld, s);
+        if (idx->profiling && b) {
+            HIP_TRY(hipEventRecord(P.ev[b], s));
+            P.scan_pairs.push_back({a, b});
+        }
+        st.scan_launches++;
+        const uint64_t* keys; uint64_t kld, kn;
+        VROD_TRY(select_chain(idx, P, P.scores.as<float>(), score_ld, m, (int)gc, kx, nullptr, &keys, &kld, &kn));
+        launch_list_keys_to_output(keys, kld, kn, (int)gc, form, k, list, idmap_of(idx), P.out_ids + (size_t)q0 * k,
+                                   P.out_scores + (size_t)q0 * k, s);
+    }
+    VROD_TRY(record_scans_done(P, s));
+    st.scan_bytes = (double)m * idx->ld * idx->esize;
+    st.scan_flops = 2.0 * nq * (double)m * idx->dim;
+    HIP_TRY(hipGetLastError());
+    return VROD_OK;
 }
 
 // -------- fast pass B: batched MFMA scan.  (1) dense sample pass over the first S rows, (2) exact j-th best per query =
@@ -729,8 +844,8 @@ static int mfma_pass(vrod_index* idx, Pending& P, Timer& tm, const void* q_lp) {
         // Grouped form where the kernel has it: the threshold is the j-th best of the per-group bests (groups of 32
         // rows: valid -- at least j rows are that good -- and exact unless two of the j best share a group), 1/32 of
         // the dense block to write and to select from.  Only while the groups outnumber j by 8x (else: every score).
-        // A handle with deleted rows takes every score: a group's best may be a deleted row, and at 10 % deleted rows
-        // nearly every group holds one.
+        // A handle with deleted rows (or a filter) takes every score: a group's best may be a masked row, and at 10 %
+        // masked rows nearly every group holds one.
         const bool group_env = debug_env().sample_grouped && !idx->row_mask();
         const uint32_t grows = group_env ? mfma_dense_group_rows(d, scan_dtype) : 0u;
         const uint32_t n_groups = grows ? (uint32_t)(round_up(sp.S, kRowTile) / grows) : 0u;
@@ -789,16 +904,19 @@ static int search_enqueue_body(vrod_index* idx, Pending& P, const float* d_queri
     // ---- plan (search_plan.h)
     const uint64_t N = idx->count;
     const int form = score_form(idx->metric);
-    Route r = route(idx->path, idx->dtype, idx->split_enabled, mfma_skinny_max_queries(true, 2u * idx->ldp * 2u), N, nq, k);
+    // the gather path: forced, or AUTO over a filter narrow enough (search_plan.h filter_route)
+    const bool gather = idx->path == VROD_PATH_GATHER || (idx->filter_on && filter_route(idx->path, idx->dtype, N, idx->eligible(), nq, idx->dim));
+    Route r = gather ? Route{VROD_PATH_GATHER, false}
+                     : route(idx->path, idx->dtype, idx->split_enabled, mfma_skinny_max_queries(true, 2u * idx->ldp * 2u), N, nq, k);
     if (r.split && !planes_ready(idx)) r.split = false;
     P.plan = make_plan(r.path, r.split, form, idx->dim, N, nq, k, idx->kp_boost.boost, debug_env().kp_margin);
     const SearchPlan& plan = P.plan;
     P.kp_boost_used = idx->kp_boost.boost;
-    st.kprime = plan.kp;
+    st.kprime = gather ? 0u : plan.kp;   // (the gather path re-scores every eligible row: no candidates)
     st.path = plan.path;
     st.split_pass = plan.split ? 1u : 0u;
 
-    if (N == 0 || idx->live() == 0) {  // empty corpus, or every row deleted: every slot unfilled
+    if (N == 0 || idx->eligible() == 0) {  // empty corpus, or no row deleted and allowed: every slot unfilled
         std::vector<uint64_t> hi((size_t)nq * k, UINT64_MAX);
         std::vector<uint32_t> hs((size_t)nq * k, kScoreNoneBits);
         HIP_TRY(hipMemcpyAsync(d_out_ids, hi.data(), hi.size() * 8, hipMemcpyHostToDevice, s));
@@ -862,8 +980,9 @@ static int search_enqueue_body(vrod_index* idx, Pending& P, const float* d_queri
     VROD_TRY(P.cand_canon.ensure((size_t)nq * plan.kp * 4));
     if (plan.path == VROD_PATH_STREAM) VROD_TRY(stream_pass(idx, P, tm, in_graph));
     else if (mfma) VROD_TRY(mfma_pass(idx, P, tm, q_lp));
+    else if (gather) VROD_TRY(gather_pass(idx, P, tm));
 
-    if (plan.path != VROD_PATH_EXACT) {
+    if (plan.path != VROD_PATH_EXACT && !gather) {
         // -------- canonical re-score + final ordering + certificate
         launch_rescore_candidates(idx->corpus, idx->dtype, form, idx->dim, idx->ld, P.q_f32.as<float>(), (int)nq,
                                   P.cand_rows.as<uint32_t>(), plan.kp, P.cand_canon.as<float>(), s);
@@ -892,8 +1011,10 @@ static int search_enqueue(vrod_index* idx, Pending& P, const float* d_queries_ra
     // (measured at 10k x 128, one query: a replay costs the HOST less -- 50 vs 65 us per search with two
     // in flight -- but is no faster end to end than plain launches, 91 vs 82 us synchronous: only
     // searches begun while another one is pending, i.e. host-bound pipelines, take it)
-    const bool graphable = graphs_on && !P.graph_off && idx->profiling == 0 && nq >= 1 && nq <= 8 && idx->live() > 0 && idx->n_pending() >= 1 &&
-                           graph_route(idx->path, nq) && (double)N * idx->ld * idx->esize <= 64.0 * 1048576.0;
+    // (a gather search is never replayed: the filter route decides before graph_route)
+    const bool gather = idx->path == VROD_PATH_GATHER || (idx->filter_on && filter_route(idx->path, idx->dtype, N, idx->eligible(), nq, idx->dim));
+    const bool graphable = graphs_on && !P.graph_off && idx->profiling == 0 && nq >= 1 && nq <= 8 && idx->eligible() > 0 && idx->n_pending() >= 1 &&
+                           !gather && graph_route(idx->path, nq) && (double)N * idx->ld * idx->esize <= 64.0 * 1048576.0;
     Pending::GraphKey key{};
     if (graphable) {
         key.q = d_queries_raw; key.oi = d_out_ids; key.os = d_out_scores; key.corpus = idx->corpus; key.xn = idx->xnorm2;
@@ -1009,7 +1130,7 @@ static int band_pass(vrod_index* idx, Pending& P, std::vector<uint32_t>& failed,
     HIP_TRY(hipMemcpyAsync(hcnt.data(), L.counts, (size_t)nf * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(hok.data(), b_ok, (size_t)nf * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    const uint32_t need = (uint32_t)std::min<uint64_t>(k, idx->live());
+    const uint32_t need = (uint32_t)std::min<uint64_t>(k, idx->eligible());
     uint32_t maxc = 0, n_res = 0;
     std::vector<uint32_t> hres(nf_pad, 0u);
     for (uint32_t f = 0; f < nf; ++f) {
@@ -1099,7 +1220,7 @@ static int search_complete(vrod_index* idx, Pending& P) {
         const uint64_t score_ld = round_up(N, 64);
         int gmax = rescore_all_max_queries(idx->ld);
         while (gmax > 1 && (uint64_t)gmax * score_ld * 4 > (1ull << 30)) gmax >>= 1;
-        const uint32_t kx = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(k, idx->live()), kSelectChunk / 2);   // (the rest: unfilled)
+        const uint32_t kx = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(k, idx->eligible()), kSelectChunk / 2);   // (the rest: unfilled)
         for (size_t f0 = 0; f0 < failed.size();) {
             int g = gmax;
             while ((size_t)g > failed.size() - f0) g >>= 1;
@@ -1107,7 +1228,7 @@ static int search_complete(vrod_index* idx, Pending& P) {
             launch_rescore_all(idx->corpus, idx->dtype, score_form(idx->metric), idx->dim, idx->ld, P.q_f32.as<float>(), &failed[f0], g, N,
                                P.scores.as<float>(), score_ld, s);
             const uint64_t* keys; uint64_t kld, kn;
-            VROD_TRY(select_chain(idx, P, P.scores.as<float>(), score_ld, N, g, kx, &keys, &kld, &kn));
+            VROD_TRY(select_chain(idx, P, P.scores.as<float>(), score_ld, N, g, kx, idx->row_mask(), &keys, &kld, &kn));
             for (int i = 0; i < g; ++i) {
                 const uint32_t qi = failed[f0 + i];
                 launch_keys_to_output(keys + (size_t)i * kld, kn, score_form(idx->metric), k, idmap_of(idx), P.out_ids + (size_t)qi * k,
@@ -1249,8 +1370,18 @@ static int composite_add(vrod_index* idx, const float* rows, uint64_t n, bool sy
     return VROD_OK;
 }
 
+// A change of the row mask's contents: the sample window and the gather list follow the generation, and a graph captured
+// before holds the old mask (or the same pointer with other contents, or none): both slots drop theirs.
+static void mask_changed(vrod_index* idx) {
+    idx->mask_gen++;
+    for (Pending& P : idx->slot) {
+        if (P.gexec) { (void)hipGraphExecDestroy(P.gexec); P.gexec = nullptr; }
+        P.gkey_valid = false;
+    }
+}
+
 // Mark local rows (each < count) deleted: the host mirror, then the changed words on the device (allocated for the whole
-// capacity at the first delete).  A graph captured before holds the old row mask, or none: both slots drop theirs.
+// capacity at the first delete); under a filter the effective mask as well.
 static int index_delete_rows(vrod_index* idx, const std::vector<uint64_t>& rows) {
     std::vector<uint64_t> fresh;   // rows this call deletes (repeats and rows deleted before are no-ops)
     uint64_t wlo = UINT64_MAX, whi = 0;
@@ -1274,17 +1405,106 @@ static int index_delete_rows(vrod_index* idx, const std::vector<uint64_t>& rows)
     }
     if (rc == VROD_OK && e == hipSuccess)
         e = hipMemcpyAsync(idx->del_dev + wlo, idx->del_bits.data() + wlo, (whi - wlo + 1) * 4, hipMemcpyHostToDevice, idx->stream);
+    // under a filter: the rows this call deletes that were eligible leave the effective mask's zeros
+    std::vector<uint32_t> eff_old;
+    uint64_t lost = 0;
+    if (idx->filter_on && rc == VROD_OK && e == hipSuccess) {
+        eff_old.assign(idx->eff_bits.begin() + wlo, idx->eff_bits.begin() + whi + 1);
+        for (uint64_t r : fresh) {
+            uint32_t& w = idx->eff_bits[r / 32];
+            const uint32_t bit = 1u << (r % 32);
+            if (!(w & bit)) { w |= bit; ++lost; }
+        }
+        e = hipMemcpyAsync(idx->eff_dev + wlo, idx->eff_bits.data() + wlo, (whi - wlo + 1) * 4, hipMemcpyHostToDevice, idx->stream);
+    }
     if (rc == VROD_OK && e == hipSuccess) e = hipStreamSynchronize(idx->stream);
-    if (rc != VROD_OK || e != hipSuccess) {   // nothing changes: the mirror forgets this call's rows
+    if (rc != VROD_OK || e != hipSuccess) {   // nothing changes: the mirrors forget this call's rows
+        (void)hipStreamSynchronize(idx->stream);
         for (uint64_t r : fresh) idx->del_bits[r / 32] &= ~(1u << (r % 32));
+        if (!eff_old.empty()) std::copy(eff_old.begin(), eff_old.end(), idx->eff_bits.begin() + wlo);
         if (first && idx->del_dev) { (void)hipFree(idx->del_dev); idx->del_dev = nullptr; }
+        else if (idx->del_dev) (void)hipMemcpy(idx->del_dev + wlo, idx->del_bits.data() + wlo, (whi - wlo + 1) * 4, hipMemcpyHostToDevice);
+        if (!eff_old.empty()) (void)hipMemcpy(idx->eff_dev + wlo, idx->eff_bits.data() + wlo, (whi - wlo + 1) * 4, hipMemcpyHostToDevice);
         return rc != VROD_OK ? rc : fail(e == hipErrorOutOfMemory ? VROD_ERR_OUT_OF_MEMORY : VROD_ERR_HIP, "uploading the deleted rows: %s", hipGetErrorString(e));
     }
     idx->n_deleted += fresh.size();
-    idx->del_gen++;
-    for (Pending& P : idx->slot) {
-        if (P.gexec) { (void)hipGraphExecDestroy(P.gexec); P.gexec = nullptr; }
-        P.gkey_valid = false;
+    idx->n_eligible -= lost;
+    mask_changed(idx);
+    return VROD_OK;
+}
+
+// Set (allow != null) or clear the filter of a single-device handle (or shard).  `allow`: n_rows bits (n_rows <= count),
+// bit i set = local row i allowed.  Rows from n_rows on are not allowed.
+static int index_set_filter(vrod_index* idx, const uint32_t* allow, uint64_t n_rows) {
+    VROD_TRY(set_device(idx));
+    if (!allow) {
+        if (!idx->filter_on) return VROD_OK;
+        if (idx->eff_dev) (void)hipFree(idx->eff_dev);
+        idx->eff_dev = nullptr;
+        idx->filter_on = false;
+        std::vector<uint32_t>().swap(idx->allow_bits);
+        std::vector<uint32_t>().swap(idx->eff_bits);
+        idx->n_eligible = 0;
+        mask_changed(idx);
+        return VROD_OK;
+    }
+    const size_t words = idx->del_bits.size();   // capacity / 32
+    std::vector<uint32_t> al(words, 0u), eff(words, ~0u);
+    const uint64_t full = n_rows / 32;
+    for (uint64_t w = 0; w < full; ++w) al[w] = allow[w];
+    if (n_rows % 32) al[full] = allow[full] & ((1u << (n_rows % 32)) - 1u);
+    uint64_t n_el = 0;
+    for (size_t w = 0; w < words; ++w) {
+        eff[w] = idx->del_bits[w] | ~al[w];
+        n_el += (uint64_t)__builtin_popcount(~eff[w]);   // (rows >= count are never allowed: n_rows <= count)
+    }
+    uint32_t* dev = idx->eff_dev;
+    if (words && !dev) HIP_TRY(hipMalloc((void**)&dev, words * 4));
+    if (words) {
+        const hipError_t e = hipMemcpy(dev, eff.data(), words * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            if (dev != idx->eff_dev) (void)hipFree(dev);
+            return fail(VROD_ERR_HIP, "uploading the filter: %s", hipGetErrorString(e));
+        }
+    }
+    idx->eff_dev = dev;
+    idx->allow_bits.swap(al);
+    idx->eff_bits.swap(eff);
+    idx->n_eligible = n_el;
+    idx->filter_on = true;
+    mask_changed(idx);
+    return VROD_OK;
+}
+
+// A composite handle's filter: the bits name global ids; each shard gets the bits of its own local rows.  The global
+// rows dealt to a shard are whole 65536-row blocks, so the bits move a 32-bit word at a time.
+static int composite_set_filter(vrod_index* idx, const uint32_t* allow, uint64_t n_rows) {
+    const size_t G = idx->shards.size();
+    if (!allow) {
+        for (vrod_index* sh : idx->shards) VROD_TRY(index_set_filter(sh, nullptr, 0));
+        return VROD_OK;
+    }
+    std::vector<std::vector<uint32_t>> local(G);
+    std::vector<uint64_t> local_n(G, 0);
+    for (size_t g = 0; g < G; ++g) local[g].assign((idx->shards[g]->count + 31) / 32 + 1, 0u);
+    (void)for_each_piece(idx, 0, n_rows, [&](size_t g, uint64_t r, uint64_t m) {
+        const uint64_t lr = local_row_of(idx, r);   // r and lr are multiples of 32 (block starts), m is unless it is the last piece
+        for (uint64_t i = 0; i < m; i += 32) {
+            uint32_t w = allow[(r + i) / 32];
+            if (m - i < 32) w &= (1u << (m - i)) - 1u;
+            local[g][(lr + i) / 32] = w;
+        }
+        local_n[g] = lr + m;
+        return (int)VROD_OK;
+    });
+    for (size_t g = 0; g < G; ++g) {
+        const int rc = index_set_filter(idx->shards[g], local[g].data(), local_n[g]);
+        if (rc != VROD_OK) {   // all or nothing: no shard keeps a filter
+            const std::string why = g_last_error;
+            for (vrod_index* sh : idx->shards) (void)index_set_filter(sh, nullptr, 0);
+            g_last_error = why;
+            return rc;
+        }
     }
     return VROD_OK;
 }
@@ -1727,6 +1947,8 @@ int vrod_index_destroy(vrod_index* idx) {
     if (idx->planes) (void)hipFree(idx->planes);
     if (idx->xnorm2) (void)hipFree(idx->xnorm2);
     if (idx->del_dev) (void)hipFree(idx->del_dev);
+    if (idx->eff_dev) (void)hipFree(idx->eff_dev);
+    idx->list_dev.release();
     if (idx->flags) (void)hipFree(idx->flags);
     if (idx->stream) (void)hipStreamDestroy(idx->stream);
     delete idx;
@@ -1785,6 +2007,27 @@ int vrod_index_live_count(const vrod_index* idx, uint64_t* out) {
     uint64_t dead = idx->n_deleted;
     for (const vrod_index* sh : idx->shards) dead += sh->n_deleted;
     *out = idx->count - dead;
+    return VROD_OK;
+}
+
+int vrod_index_set_filter(vrod_index* idx, const uint32_t* allow_words, uint64_t n_rows) {
+    if (!idx || (!allow_words && n_rows)) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    VROD_TRY(require_idle(idx, "vrod_index_set_filter"));
+    if (n_rows > idx->count)
+        return fail(VROD_ERR_INVALID_ARG, "a filter of %llu rows on a handle of %llu", (unsigned long long)n_rows, (unsigned long long)idx->count);
+    static const uint32_t kNone = 0u;   // (p, 0): a filter that allows nothing
+    const uint32_t* allow = allow_words ? allow_words : nullptr;
+    if (allow_words && !n_rows) allow = &kNone;
+    if (idx->composite()) return composite_set_filter(idx, allow, n_rows);
+    return index_set_filter(idx, allow, n_rows);
+}
+
+int vrod_index_filter_count(const vrod_index* idx, uint64_t* out) {
+    if (!idx || !out) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    if (!idx->composite()) { *out = idx->eligible(); return VROD_OK; }
+    uint64_t n = 0;
+    for (const vrod_index* sh : idx->shards) n += sh->eligible();
+    *out = n;
     return VROD_OK;
 }
 
@@ -1927,7 +2170,7 @@ int vrod_merge_topk_packed_device(int device, int metric, const void* d_packed, 
 }
 
 int vrod_index_set_path(vrod_index* idx, int path) {
-    if (!idx || path < VROD_PATH_AUTO || path > VROD_PATH_EXACT) return fail(VROD_ERR_INVALID_ARG, "bad path");
+    if (!idx || path < VROD_PATH_AUTO || path > VROD_PATH_GATHER) return fail(VROD_ERR_INVALID_ARG, "bad path");
     if (!idx->composite()) VROD_TRY(require_idle(idx, "vrod_index_set_path"));
     idx->path = path;
     return VROD_OK;

@@ -143,6 +143,11 @@ void launch_scatter_results(const uint64_t* d_ids, const float* d_scores, const 
 void launch_keys_to_output(const uint64_t* d_keys, uint64_t n, int metric, uint32_t k,
                            const IdMap& idmap, uint64_t* d_out_ids, float* d_out_scores,
                            hipStream_t s);
+// Gather path output: the keys of nq queries (n per query, row stride key_ld) name columns of the ascending row list
+// d_list; column c -> row d_list[c] -> idmap.  One launch for all nq queries, outputs [nq][k].
+void launch_list_keys_to_output(const uint64_t* d_keys, uint64_t key_ld, uint64_t n, int nq, int metric, uint32_t k,
+                                const uint32_t* d_list, const IdMap& idmap, uint64_t* d_out_ids, float* d_out_scores,
+                                hipStream_t s);
 
 // Fill a result block with "no result" (ids = UINT64_MAX, scores = NaN): the empty list slots of
 // the multi-device exchange.
@@ -165,6 +170,11 @@ int rescore_all_max_queries(uint32_t ld);
 void launch_rescore_all(const void* d_corpus, int dtype, int metric, uint32_t dim, uint32_t ld,
                         const float* d_q, const uint32_t* query_index, int nq, uint64_t nrows,
                         float* d_out, uint64_t out_ld, hipStream_t s);
+// Gather path of a filtered search: canonical scores (the rescore_all chain) of the m rows d_list names (ascending local
+// row indices) for nq consecutive prepared queries d_q [nq][ld]: d_out[q * out_ld + c] = score of row d_list[c].
+// One launch serves any nq (queries in groups of 8 per lane, rows in tiles of 64 per wave).
+void launch_rescore_list(const void* d_corpus, int dtype, int metric, uint32_t dim, uint32_t ld, const float* d_q, uint32_t nq,
+                         const uint32_t* d_list, uint64_t m, float* d_out, uint64_t out_ld, hipStream_t s);
 
 // ---- kernels_mfma.hip : batched Q.K^T scan with fused threshold filter
 // Timing of the dominant scan launches without marker packets: the launcher of the next scan

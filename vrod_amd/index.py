@@ -15,7 +15,7 @@ from ._lib import SearchStats, VrodError, check
 
 DTYPE_F32, DTYPE_BF16 = 0, 1
 METRIC_COSINE, METRIC_L2, METRIC_IP = 0, 1, 2
-PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT = 0, 1, 2, 3
+PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT, PATH_GATHER = 0, 1, 2, 3, 4
 ID_NONE = np.uint64(0xFFFFFFFFFFFFFFFF)
 MAX_K = 3584
 
@@ -103,6 +103,30 @@ class Index:
         """Rows added minus rows deleted."""
         out = C.c_uint64()
         check(self._L.vrod_index_live_count(self._h, C.byref(out)))
+        return out.value
+
+    def set_filter(self, allow):
+        """Allow-list filter (vrod_index_set_filter): a bool array-like of length <= count() -- entry i True = id
+        offset + i may be returned -- or None to clear.  Every later search returns only rows that are live and allowed;
+        rows past the array (rows added later included) are not allowed."""
+        if allow is None:
+            check(self._L.vrod_index_set_filter(self._h, None, 0))
+            return
+        a = np.asarray(allow)
+        if a.dtype != np.bool_:
+            raise TypeError(f"allow must be a bool array, got {a.dtype}")
+        a = a.reshape(-1)
+        n = a.size
+        buf = np.zeros(max(1, (n + 31) // 32) * 4, np.uint8)   # bit i % 32 of word i / 32 (a little-endian host)
+        packed = np.packbits(a, bitorder="little")
+        buf[:packed.size] = packed
+        words = buf.view(np.uint32)
+        check(self._L.vrod_index_set_filter(self._h, words.ctypes.data_as(C.c_void_p), n))
+
+    def filter_count(self) -> int:
+        """Rows the next search may return: live and allowed (= live_count() without a filter)."""
+        out = C.c_uint64()
+        check(self._L.vrod_index_filter_count(self._h, C.byref(out)))
         return out.value
 
     def set_id_offset(self, off: int):
