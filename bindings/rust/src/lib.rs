@@ -26,6 +26,8 @@ pub const VROD_PATH_MFMA: c_int = 2;
 pub const VROD_PATH_EXACT: c_int = 3;
 /// Filtered searches: canonical scores of the eligible rows only.
 pub const VROD_PATH_GATHER: c_int = 4;
+/// `vrod_range_search`: the result does not fit the caller's buffers (`out_lims` is valid).
+pub const VROD_ERR_CAPACITY: c_int = 8;
 
 #[repr(C)]
 #[derive(Debug, Default, Clone, Copy)]
@@ -92,6 +94,11 @@ extern "C" {
     pub fn vrod_version() -> *const c_char;
     pub fn vrod_synth_rows_device(device: c_int, seed: u64, first_row: u64, n: u64, dim: u32,
                                   d_out: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn vrod_range_search(idx: *mut vrod_index, queries: *const f32, nq: u32, thresholds: *const f32,
+                             capacity: u64, out_lims: *mut u64, out_ids: *mut u64, out_scores: *mut f32) -> c_int;
+    pub fn vrod_range_search_device(idx: *mut vrod_index, d_queries: *const f32, nq: u32, d_thresholds: *const f32,
+                                    capacity: u64, d_out_lims: *mut u64, d_out_ids: *mut u64,
+                                    d_out_scores: *mut f32, stream: *mut c_void) -> c_int;
 }
 
 /// Joins the reference's `thiserror` enums (`src/main.rs:36-40`, `src/command/builder.rs:10-15`).
@@ -206,6 +213,38 @@ impl Collection {
             vrod_search(self.idx, flat.as_ptr(), queries.len() as u32, k as u32, ids.as_mut_ptr(), scores.as_mut_ptr())
         })?;
         Ok((ids, scores))
+    }
+}
+
+impl Collection {
+    /// Every row at least as good as `thresholds[q]` (`>=` for cosine / inner product, `<=` for L2), best first:
+    /// `(lims, ids, scores)` with query `q`'s rows at `lims[q]..lims[q + 1]`.  A count-only call sizes the buffers.
+    pub fn range_search(&self, queries: &[Vec<f32>], thresholds: &[f32]) -> Result<(Vec<u64>, Vec<u64>, Vec<f32>), ScanError> {
+        for q in queries {
+            if q.len() != self.dim {
+                return Err(ScanError::Dim { got: q.len(), want: self.dim });
+            }
+        }
+        if thresholds.len() != queries.len() {
+            return Err(ScanError::Dim { got: thresholds.len(), want: queries.len() });
+        }
+        let flat: Vec<f32> = queries.iter().flatten().copied().collect();
+        let nq = queries.len() as u32;
+        let mut lims = vec![0u64; queries.len() + 1];
+        let rc = unsafe {
+            vrod_range_search(self.idx, flat.as_ptr(), nq, thresholds.as_ptr(), 0, lims.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut())
+        };
+        if rc != VROD_ERR_CAPACITY {
+            check(rc)?;
+            return Ok((lims, Vec::new(), Vec::new()));
+        }
+        let n = lims[queries.len()] as usize;
+        let mut ids = vec![0u64; n];
+        let mut scores = vec![0f32; n];
+        check(unsafe {
+            vrod_range_search(self.idx, flat.as_ptr(), nq, thresholds.as_ptr(), n as u64, lims.as_mut_ptr(), ids.as_mut_ptr(), scores.as_mut_ptr())
+        })?;
+        Ok((lims, ids, scores))
     }
 }
 

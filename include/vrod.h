@@ -63,7 +63,8 @@ typedef enum {
     VROD_ERR_OUT_OF_MEMORY = 4,
     VROD_ERR_HIP = 5,           /* a HIP call failed; vrod_last_error() has the text */
     VROD_ERR_UNSUPPORTED = 6,
-    VROD_ERR_INTERNAL = 7
+    VROD_ERR_INTERNAL = 7,
+    VROD_ERR_CAPACITY = 8       /* vrod_range_search: the result does not fit the caller's buffers (out_lims is valid) */
 } vrod_status;
 
 enum { VROD_DTYPE_F32 = 0, VROD_DTYPE_BF16 = 1 };  /* storage + fast-pass type */
@@ -188,6 +189,31 @@ int vrod_search_begin_synthetic_device(vrod_index *idx, uint64_t seed, uint64_t 
                                        float *d_out_scores, void *stream);
 int vrod_search_end(vrod_index *idx);
 int vrod_search_pending(const vrod_index *idx, uint32_t *out_pending);
+
+/* Range search: EVERY eligible row (live, and allowed while a filter is set) whose canonical score s is at least as
+ * good as the query's threshold -- s >= thresholds[q] (COSINE, IP), s <= thresholds[q] (L2), compared as fp32 values:
+ * the boundary is inclusive, -0.0 == +0.0, a NaN score never qualifies.  Exact, like a search: ids and score bits are
+ * the CPU oracle's.  There is no k and VROD_MAX_K does not apply: one query may return every row.
+ *   thresholds  nq floats in the units of the handle's scores; NaN -> VROD_ERR_INVALID_VALUE, +-inf allowed.
+ *               Queries are prepared exactly as vrod_search prepares them.
+ *   out_lims    nq + 1 entries: out_lims[0] = 0, out_lims[q + 1] - out_lims[q] = qualifying rows of query q.  Always
+ *               exact and always written once the call gets as far as scanning, whatever `capacity` is.
+ *   capacity    entries out_ids / out_scores hold.  out_lims[nq] <= capacity: VROD_OK, entries [out_lims[q],
+ *               out_lims[q + 1]) are query q's rows, best first, ties by smaller id (id_offset applied); entries past
+ *               out_lims[nq] are not touched.  out_lims[nq] > capacity: VROD_ERR_CAPACITY, out_ids / out_scores are
+ *               unspecified, out_lims is valid -- a second call with capacity >= out_lims[nq] succeeds.  capacity = 0
+ *               with null out_ids / out_scores is the count-only form.
+ * nq = 0: VROD_OK with out_lims[0] = 0; an empty handle: all-zero out_lims.  Fails with VROD_ERR_INVALID_ARG while a
+ * search is pending; there is no pipelined form and no graph replay (the output size depends on the data).
+ * vrod_index_set_path is honoured (EXACT: canonical scores of every row; GATHER: of the eligible rows; STREAM has no
+ * threshold form and is treated as AUTO).  vrod_index_last_stats afterwards: path = the route taken, k = 0, kprime =
+ * the largest per-query candidate count of the fast pass, fallback_queries = queries answered by the canonical route.
+ * The _device form takes device pointers on the handle's first device and returns after the results are complete. */
+int vrod_range_search(vrod_index *idx, const float *queries, uint32_t nq, const float *thresholds,
+                      uint64_t capacity, uint64_t *out_lims, uint64_t *out_ids, float *out_scores);
+int vrod_range_search_device(vrod_index *idx, const float *d_queries, uint32_t nq, const float *d_thresholds,
+                             uint64_t capacity, uint64_t *d_out_lims, uint64_t *d_out_ids, float *d_out_scores,
+                             void *stream);
 
 /* Merge n_lists per-shard results (device, each nq x k, list-major: [list][q][k]) into
  * one nq x k on `device` -- the step after the RCCL all-gather. */

@@ -21,7 +21,10 @@ SYMBOLS = [
     "vrod_search_begin_device", "vrod_search_begin_synthetic_device", "vrod_search_end", "vrod_search_pending",
     "vrod_merge_topk_device", "vrod_merge_topk_packed_device", "vrod_index_set_path", "vrod_index_set_profiling",
     "vrod_index_last_stats", "vrod_index_shard_stats", "vrod_last_error", "vrod_version", "vrod_synth_rows_device",
+    "vrod_range_search", "vrod_range_search_device",
 ]
+
+ERR_CAPACITY = 8   # VROD_ERR_CAPACITY: a range search's result does not fit the caller's buffers (out_lims is valid)
 
 
 class VrodError(RuntimeError):
@@ -91,6 +94,8 @@ def load() -> C.CDLL:
     L.vrod_index_last_stats.argtypes = [vp, C.POINTER(SearchStats)]
     L.vrod_index_shard_stats.argtypes = [vp, u32, C.POINTER(i32), C.POINTER(SearchStats)]
     L.vrod_synth_rows_device.argtypes = [i32, u64, u64, u64, u32, vp, vp]
+    L.vrod_range_search.argtypes = [vp, vp, u32, vp, u64, vp, vp, vp]
+    L.vrod_range_search_device.argtypes = [vp, vp, u32, vp, u64, vp, vp, vp, vp]
     for name in SYMBOLS:
         getattr(L, name).restype = i32
     L.vrod_last_error.restype = C.c_char_p

@@ -266,4 +266,78 @@ inline bool band_eligible(const SearchPlan& p, int dtype, uint32_t n_failed, uin
     return p.path == VROD_PATH_MFMA && p.eps_mode != 1 && n_failed >= min_q && p.N >= k && p.nq_pad != 0;
 }
 
+// ------------------------------------------------------------------ range searches
+// A range search (vrod_range_search) returns every eligible row whose canonical score is at least as good as the
+// caller's threshold.  Its fast pass is ONE filtered MFMA launch per row range at a threshold widened by the error
+// bound; the canonical re-score of what it collected decides membership.  Nothing is estimated: no sample pass, no
+// stages, no k', no certificate.
+#if defined(__HIPCC__)
+#define VROD_PLAN_HD __host__ __device__
+#else
+#define VROD_PLAN_HD
+#endif
+// The next float on the WORSE side of t (form M_COSINE: below, M_L2: above); t finite.
+VROD_PLAN_HD inline float range_step_worse(float t, int form) {
+    union { float f; uint32_t u; } v;
+    v.f = t;
+    const bool down = form == M_COSINE;
+    if ((v.u & 0x7FFFFFFFu) == 0u) v.u = (down ? 0x80000000u : 0u) | 1u;       // +-0 -> the smallest denormal of that side
+    else if (((v.u >> 31) != 0u) == down) v.u += 1u;                            // away from zero
+    else v.u -= 1u;                                                             // towards zero
+    return v.f;
+}
+// The fast-pass threshold of one query.  The scan appends rows whose fast score is STRICTLY better than it; with
+// |fast - canonical| <= eps every row whose canonical score is at least as good as `threshold` has a fast score at
+// least as good as threshold -/+ eps, and the rounded difference moved one float further is strictly worse than
+// that: the lists are a superset of the answer, equality included.  eps is eps_bound()'s expression for the batch's
+// largest |q|^2 and the corpus's largest |x|^2.  An infinite threshold stays as it is: on the permissive side every
+// finite fast score passes, on the other nothing does.  *canonical is set when no finite bound exists (a NaN or
+// overflowing norm product -- the IP and overflowing-L2 cases -- or the relative mode 1, which has no absolute form):
+// that query must take the canonical route, and its fast threshold lets nothing pass.
+VROD_PLAN_HD inline float range_fast_threshold(float threshold, int form, int eps_mode, float eps_c, float qn2, float xn2, bool* canonical) {
+    const float kMax = 3.4028234663852886e38f, kInf = __builtin_huge_valf();
+    const float never = form == M_COSINE ? kInf : -kInf;
+    const float qn = __builtin_sqrtf(qn2), xn = __builtin_sqrtf(xn2);
+    const float span = eps_mode == 0 ? qn * xn : (qn + xn) * (qn + xn);
+    const float eps = eps_c * span + eps_c * 2.3509887e-38f;
+    *canonical = eps_mode == 1 || !(span <= kMax) || !(span + eps <= kMax);
+    if (*canonical) return never;
+    if (threshold == kInf || threshold == -kInf) return threshold;
+    const float t = form == M_COSINE ? threshold - eps : threshold + eps;
+    if (!(__builtin_fabsf(t) <= kMax)) return t;   // overflowed to the permissive infinity (a threshold within eps of FLT_MAX)
+    return range_step_worse(t, form);
+}
+
+// Split policy of the filtered launches.  A launch over rows [lo, hi) found max_count hits for its fullest query
+// against a list capacity of cap: more than cap means the range is redone in pieces.  The pieces are whole 256-row
+// tiles (the last one ends at hi), cover [lo, hi) exactly once, and number ceil(max_count / (cap / 2)) -- at least 2,
+// at most the range's tiles -- so that a piece expects half a list.  A range of one tile is never split: a tile
+// appends at most 256 rows per query.  Returns the pieces' bounds: piece i is [b[i], b[i + 1]).
+inline std::vector<uint64_t> range_split(uint64_t lo, uint64_t hi, uint64_t max_count, uint32_t cap) {
+    const uint64_t t0 = lo / kRowTile, t1 = (hi + kRowTile - 1) / kRowTile;
+    const uint64_t tiles = t1 > t0 ? t1 - t0 : 0;
+    std::vector<uint64_t> b{lo};
+    if (tiles > 1 && max_count > cap) {
+        const uint64_t half = std::max<uint64_t>(cap / 2, 1);
+        const uint64_t pieces = std::min<uint64_t>(tiles, std::max<uint64_t>(2, (max_count + half - 1) / half));
+        for (uint64_t i = 1; i < pieces; ++i) b.push_back((t0 + tiles * i / pieces) * kRowTile);
+    }
+    b.push_back(hi);
+    return b;
+}
+// The fast pass a range search runs: always the batched scan (it is the one with a threshold form); over the bf16
+// planes on an fp32 handle that has them.
+inline SearchPlan make_range_plan(bool split, int form, uint32_t dim, uint64_t N, uint32_t nq) {
+    SearchPlan p;
+    p.path = VROD_PATH_MFMA;
+    p.split = split;
+    p.kp = 0;
+    const FastBound fb = fast_bound(VROD_PATH_MFMA, split, form, dim);
+    p.eps_mode = fb.mode;
+    p.eps_c = fb.c;
+    p.nq_pad = (uint32_t)round_up(nq, 256);
+    p.N = N;
+    return p;
+}
+
 }  // namespace vrod

@@ -30,6 +30,7 @@
 #include "../../include/vrod.h"
 #include "vrod_common.h"
 #include "vrod_kernels.h"
+#include "kernels_range.h"
 #include "search_plan.h"
 
 using namespace vrod;
@@ -197,6 +198,9 @@ struct vrod_index {
 
     // workspaces
     DevBuf raw_stage, nrm_ws, out_ids, out_scores;
+    // range searches (vrod_range_search): the pool of qualifying rows and its sort partner, and the small block
+    // [total (u64) | the caller's thresholds [nq] | per-query counters [nq]]
+    DevBuf range_pool, range_pool_b, range_small;
     uint32_t* flags = nullptr;  // [0] bad-value flag of the insert path; [8] max squared row norm
     Pending slot[2];
     // start / stop of the last filtered scan launch of the four most recent searches (Timer::arm_tail): the next search's
@@ -1814,6 +1818,337 @@ static int composite_search(vrod_index* idx, const float* queries, bool from_hos
     return composite_end(idx, from_host ? out_ids : nullptr, from_host ? out_scores : nullptr);
 }
 
+// ------------------------------------------------------------------ range search
+// Every eligible row whose canonical score is at least as good as the caller's per-query threshold (DESIGN.md scan
+// spec rule 10).  A range search is synchronous: it runs in the slot the next search would take, on a handle with
+// nothing pending, and leaves the slot as it found it (no candidate margin, split-pass or graph state is touched).
+//
+//   fast route       thresholds widened by the error bound (range_prepare_kernel), ONE filtered MFMA launch over the
+//                    whole corpus into the slot's list block, counters read back; a list that overflowed means the
+//                    row range is redone in pieces (search_plan.h range_split); every completed range is re-scored
+//                    canonically and cut at the caller's threshold (range_rescore_cut_kernel)
+//   canonical route  the queries without a finite bound, VROD_PATH_EXACT, and the gather route of a narrow filter:
+//                    canonical scores of all (eligible) rows through the exact path's kernels, cut the same way
+// Both append to the shard's pool and count per query; ordering and output are the caller's (range_emit).
+struct RangeShardResult {
+    std::vector<uint64_t> counts;   // qualifying rows per query
+    uint64_t total = 0, stored = 0; // their sum; entries in the shard's pool (unsorted), min(total, pool capacity)
+};
+
+static int range_collect(vrod_index* idx, const float* d_queries_raw, uint32_t nq, const float* h_thresholds, uint64_t capacity,
+                         RangeShardResult& R) {
+    VROD_TRY(set_device(idx));
+    Pending& P = next_slot(idx);
+    hipStream_t s = P.stream;
+    vrod_search_stats& st = P.st;
+    st = vrod_search_stats{};
+    st.nq = nq;
+    R.counts.assign(nq, 0);
+    R.total = R.stored = 0;
+    P.ev_used = 0; P.t0 = P.t1 = 0; P.scan_pairs.clear(); P.sample_pair = -1; P.tail_pair = -1;
+    P.gkey_valid = false;   // the slot's workspaces may move: a search seen before is seen afresh
+    const uint64_t N = idx->count;
+    const int form = score_form(idx->metric);
+    // the route: STREAM has no threshold form (treated as AUTO); the filter route decides as it does for a search
+    const int forced = idx->path == VROD_PATH_STREAM ? VROD_PATH_AUTO : idx->path;
+    const bool gather = forced == VROD_PATH_GATHER || (idx->filter_on && filter_route(forced, idx->dtype, N, idx->eligible(), nq, idx->dim));
+    const bool exact = !gather && forced == VROD_PATH_EXACT;
+    const bool fast = !gather && !exact;
+    st.path = gather ? VROD_PATH_GATHER : exact ? VROD_PATH_EXACT : VROD_PATH_MFMA;
+    if (N == 0 || idx->eligible() == 0) { idx->stats = st; return VROD_OK; }
+    const bool split = fast && idx->dtype == VROD_DTYPE_F32 && idx->split_enabled && planes_ready(idx);
+    P.plan = make_range_plan(split, form, idx->dim, N, nq);
+    P.plan.path = (int)st.path;
+    const SearchPlan& plan = P.plan;
+    st.split_pass = split ? 1u : 0u;
+    Timer tm(idx, P);
+    P.t0 = tm.mark();
+
+    // ---- workspaces; the caller's thresholds and zeroed counters on the device
+    const uint32_t nq_pad = plan.nq_pad, cap = kSelectChunk;
+    VROD_TRY(P.q_f32.ensure((size_t)nq_pad * idx->ld * 4));
+    void* q_lp = nullptr;
+    if (idx->dtype == VROD_DTYPE_BF16) {
+        VROD_TRY(P.q_lp.ensure((size_t)nq_pad * idx->ld * 2));
+        q_lp = P.q_lp.p;
+    }
+    VROD_TRY(P.small.ensure(small_bytes(nq_pad)));
+    if (fast) VROD_TRY(P.lists.ensure(list_bytes(nq_pad)));
+    VROD_TRY(idx->range_small.ensure(8 + (size_t)nq * 8));
+    const uint64_t pool_cap = std::min<uint64_t>(capacity, (uint64_t)nq * idx->eligible());
+    if (pool_cap) VROD_TRY(idx->range_pool.ensure((size_t)pool_cap * sizeof(RangeHit)));
+    RangePool pool{idx->range_pool.as<RangeHit>(), pool_cap, idx->range_small.as<unsigned long long>(), nullptr};
+    float* d_thr = (float*)((char*)idx->range_small.p + 8);
+    pool.per_query = (uint32_t*)(d_thr + nq);
+    HIP_TRY(hipMemsetAsync(idx->range_small.p, 0, 8 + (size_t)nq * 8, s));
+    HIP_TRY(hipMemcpyAsync(d_thr, h_thresholds, (size_t)nq * 4, hipMemcpyHostToDevice, s));
+
+    // ---- prepare the queries exactly as a search does (the same launch resets the list counters and pacing regions)
+    const SmallBlock B = small_block(P);
+    QueryInit qi{};
+    qi.status = B.status;
+    qi.counts = fast ? list_block(P).counts : nullptr;
+    qi.thr = fast ? B.thr : nullptr;
+    qi.thr_live_bits = qi.thr_pad_bits = form == M_COSINE ? 0x7F800000u : 0xFF800000u;   // nothing passes until range_prepare
+    qi.zero_words2 = fast ? pace_region(P, 0) : nullptr;
+    qi.n_zero_words2 = kPaceRegions * (kPaceWords + kClaimWords);
+    launch_prep_queries(d_queries_raw, nq, nq_pad, idx->dim, idx->ld, prep_form(idx->metric), idx->dtype, P.q_f32.as<float>(), q_lp, B.qn2,
+                        &P.flags[0], &P.flags[1], qi, s);
+    if (fast)
+        launch_range_prepare(d_thr, nq, nq_pad, form, plan.eps_mode, plan.eps_c, &P.flags[1], idx->max_xn2_bits, B.thr, B.status, s);
+    HIP_TRY(hipGetLastError());
+
+    // whatever happens from here on, the slot's per-search scalars (bad-value flag, max |q|^2, max error) end up consumed
+    struct FlagReset {
+        Pending& P;
+        ~FlagReset() { (void)hipMemsetAsync(&P.flags[0], 0, 12, P.stream); (void)hipStreamSynchronize(P.stream); }
+    } flag_reset{P};
+
+    std::vector<uint32_t> canon_q;   // queries of the canonical (dense) route
+    std::vector<uint32_t> hcnt(nq), hcanon(nq, 0u);
+    uint32_t hflags[2] = {0u, 0u};
+    auto check_queries = [&]() -> int {
+        if (hflags[0]) { idx->stats = st; return fail(VROD_ERR_INVALID_VALUE, "queries contain NaN or Inf"); }
+        return VROD_OK;
+    };
+    if (fast) {
+        MfmaScanArgs a;
+        VROD_TRY(mfma_args(idx, P, a, idx->dtype == VROD_DTYPE_BF16 ? q_lp : P.q_f32.p, B.qn2, B.thr, nq, nq_pad));
+        if (split) {
+            if (idx->planes_rows < N) {   // planes of the rows added since the last batched search (as mfma_pass)
+                launch_split_rows((const float*)idx->corpus + idx->planes_rows * idx->ld, N - idx->planes_rows, idx->ld, idx->ldp,
+                                  (char*)idx->planes + idx->planes_rows * 2ull * idx->ldp * 2ull, false, s);
+                if (round_up(N, kRowTile) > N)
+                    HIP_TRY(hipMemsetAsync((char*)idx->planes + N * 2ull * idx->ldp * 2ull, 0, (round_up(N, kRowTile) - N) * 2ull * idx->ldp * 2ull, s));
+                idx->planes_rows = N;
+            }
+            VROD_TRY(use_split_planes(idx, a, P.q_f32.as<float>(), nq_pad, P.q_planes, s));
+        }
+        const int scan_dtype = split ? VROD_DTYPE_BF16 : idx->dtype;
+        const ListBlock L = list_block(P);
+        P.pace_launches = 0;
+        // row ranges still to scan, in row order: the whole corpus first; a range whose fullest list overflowed is
+        // replaced by its pieces.  A one-tile range appends at most 256 rows per query: the loop terminates.
+        std::vector<std::pair<uint64_t, uint64_t>> todo{{0, N}};
+        bool first = true;
+        while (!todo.empty()) {
+            const std::pair<uint64_t, uint64_t> rg = todo.back();
+            todo.pop_back();
+            if (!first) HIP_TRY(hipMemsetAsync(L.counts, 0, (size_t)nq_pad * 4, s));
+            launch_filtered(idx, P, tm, a, scan_dtype, rg.first, rg.second, true, false);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(hcnt.data(), L.counts, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+            if (first) {
+                HIP_TRY(hipMemcpyAsync(hcanon.data(), B.status, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipMemcpyAsync(hflags, &P.flags[0], 8, hipMemcpyDeviceToHost, s));
+            }
+            HIP_TRY(hipStreamSynchronize(s));
+            if (first) VROD_TRY(check_queries());
+            first = false;
+            uint32_t maxc = 0;
+            for (uint32_t c : hcnt) maxc = std::max(maxc, c);
+            if (maxc > cap) {
+                const std::vector<uint64_t> b = range_split(rg.first, rg.second, maxc, cap);
+                if (b.size() < 3) { idx->stats = st; return fail(VROD_ERR_INTERNAL, "a hit list of one tile overflowed (%u entries)", maxc); }
+                for (size_t i = b.size() - 1; i > 0; --i) todo.push_back({b[i - 1], b[i]});
+                continue;
+            }
+            st.kprime = std::max(st.kprime, maxc);
+            launch_range_rescore_cut(idx->corpus, idx->dtype, form, idx->dim, idx->ld, P.q_f32.as<float>(), nq, L.lists, L.counts, cap, maxc, d_thr,
+                                     idmap_of(idx), pool, &P.flags[2], s);
+            HIP_TRY(hipGetLastError());
+        }
+        for (uint32_t q = 0; q < nq; ++q)
+            if (hcanon[q]) canon_q.push_back(q);
+        st.fallback_queries = (uint32_t)canon_q.size();
+    } else {
+        HIP_TRY(hipMemcpyAsync(hflags, &P.flags[0], 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        VROD_TRY(check_queries());
+        if (exact) {
+            for (uint32_t q = 0; q < nq; ++q) canon_q.push_back(q);
+            st.fallback_queries = nq;
+        }
+    }
+
+    // ---- canonical route, dense form: up to 8 queries share one pass over the corpus (the exact path's kernel)
+    if (!canon_q.empty()) {
+        const uint64_t score_ld = round_up(N, 64);
+        int gmax = rescore_all_max_queries(idx->ld);
+        while (gmax > 1 && (uint64_t)gmax * score_ld * 4 > (1ull << 30)) gmax >>= 1;
+        for (size_t f0 = 0; f0 < canon_q.size();) {
+            int g = gmax;
+            while ((size_t)g > canon_q.size() - f0) g >>= 1;
+            VROD_TRY(P.scores.ensure((size_t)g * score_ld * 4));
+            launch_rescore_all(idx->corpus, idx->dtype, form, idx->dim, idx->ld, P.q_f32.as<float>(), &canon_q[f0], g, N, P.scores.as<float>(), score_ld, s);
+            launch_range_cut_scores(P.scores.as<float>(), score_ld, N, (uint32_t)g, &canon_q[f0], 0, form, d_thr, idx->row_mask(), nullptr, idmap_of(idx), pool, s);
+            HIP_TRY(hipGetLastError());
+            if (!fast) { st.scan_launches++; st.scan_bytes += (double)N * idx->ld * idx->esize; st.scan_flops += 2.0 * g * (double)N * idx->dim; }
+            f0 += g;
+        }
+    }
+    // ---- canonical route, list form: the eligible rows only (the gather path's kernel)
+    if (gather) {
+        VROD_TRY(gather_list(idx));
+        const uint64_t m = idx->list_n;
+        const uint64_t score_ld = round_up(m, 64);
+        uint64_t g = std::max<uint64_t>(1, (1ull << 30) / (score_ld * 4));
+        if (g >= nq) g = nq;
+        else if (g > 8) g = g / 8 * 8;
+        VROD_TRY(P.scores.ensure((size_t)g * score_ld * 4));
+        for (uint32_t q0 = 0; q0 < nq; q0 += (uint32_t)g) {
+            const uint32_t gc = (uint32_t)std::min<uint64_t>(g, nq - q0);
+            launch_rescore_list(idx->corpus, idx->dtype, form, idx->dim, idx->ld, P.q_f32.as<float>() + (size_t)q0 * idx->ld, gc, idx->list_dev.as<uint32_t>(), m,
+                                P.scores.as<float>(), score_ld, s);
+            launch_range_cut_scores(P.scores.as<float>(), score_ld, m, gc, nullptr, q0, form, d_thr, nullptr, idx->list_dev.as<uint32_t>(), idmap_of(idx), pool, s);
+            HIP_TRY(hipGetLastError());
+            st.scan_launches++;
+        }
+        st.scan_bytes = (double)m * idx->ld * idx->esize;
+        st.scan_flops = 2.0 * nq * (double)m * idx->dim;
+    }
+
+    // ---- counters back
+    std::vector<uint32_t> hq(nq);
+    unsigned long long htotal = 0;
+    uint32_t herr = 0, hmaxx = 0;
+    HIP_TRY(hipMemcpyAsync(hq.data(), pool.per_query, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&htotal, pool.n_total, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&herr, &P.flags[2], 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&hmaxx, idx->max_xn2_bits, 4, hipMemcpyDeviceToHost, s));
+    P.t1 = tm.mark();
+    HIP_TRY(hipStreamSynchronize(s));
+    for (uint32_t q = 0; q < nq; ++q) R.counts[q] = hq[q];
+    R.total = htotal;
+    R.stored = std::min<uint64_t>(htotal, pool_cap);
+    if (fast && canon_q.size() < nq) {   // a fast pass ran for some query
+        memcpy(&st.max_fast_err, &herr, 4);
+        float qn2, xn2;
+        memcpy(&qn2, &hflags[1], 4);
+        memcpy(&xn2, &hmaxx, 4);
+        st.eps_bound = eps_bound(plan.eps_mode, plan.eps_c, qn2, xn2);
+    }
+    if (idx->profiling) {
+        for (size_t i = 0; i < P.scan_pairs.size(); ++i) st.scan_ms += tm.pair_ms(i);
+        if (idx->profiling >= 2) st.total_ms = tm.ms(P.t0, P.t1);
+    }
+    idx->stats = st;
+    return VROD_OK;
+}
+
+// Order `n` pool entries (device memory of the current device, d_pool; d_tmp its sort partner) and write them to the
+// caller's arrays: device pointers, or host pointers through the handle's staging buffers.
+static int range_emit(vrod_index* idx, RangeHit* d_pool, RangeHit* d_tmp, uint64_t n, uint64_t* out_ids, float* out_scores, bool to_host, hipStream_t s) {
+    if (!n) return VROD_OK;
+    const RangeHit* sorted = launch_range_sort(d_pool, d_tmp, n, s);
+    uint64_t* oi = out_ids;
+    float* os = out_scores;
+    if (to_host) {
+        VROD_TRY(idx->out_ids.ensure((size_t)n * 8));
+        VROD_TRY(idx->out_scores.ensure((size_t)n * 4));
+        oi = idx->out_ids.as<uint64_t>();
+        os = idx->out_scores.as<float>();
+    }
+    launch_range_emit(sorted, n, score_form(idx->metric), oi, os, s);
+    HIP_TRY(hipGetLastError());
+    if (to_host) {
+        HIP_TRY(hipMemcpyAsync(out_ids, oi, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out_scores, os, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    return VROD_OK;
+}
+
+// The whole call.  `queries` / outputs: host pointers (to_host) or device pointers on the handle's first device; the
+// thresholds are on the host by now (validated).  h_lims [nq + 1] is always filled once the scan ran.
+static int range_search(vrod_index* idx, const float* queries, bool from_host, uint32_t nq, const float* h_thresholds, uint64_t capacity,
+                        uint64_t* h_lims, uint64_t* out_ids, float* out_scores) {
+    const size_t qbytes = (size_t)nq * idx->dim * 4;
+    std::vector<uint64_t> counts(nq, 0);
+    uint64_t total = 0;
+    std::vector<RangeShardResult> res(idx->composite() ? idx->shards.size() : 1);
+    if (!idx->composite()) {
+        VROD_TRY(set_device(idx));
+        Pending& P = next_slot(idx);
+        const float* dq = queries;
+        if (from_host) {
+            VROD_TRY(P.q_raw.ensure(qbytes));
+            HIP_TRY(hipMemcpyAsync(P.q_raw.p, queries, qbytes, hipMemcpyHostToDevice, P.stream));
+            dq = P.q_raw.as<float>();
+        }
+        VROD_TRY(range_collect(idx, dq, nq, h_thresholds, capacity, res[0]));
+        counts = res[0].counts;
+        total = res[0].total;
+    } else {
+        // every shard answers the same thresholds over its own rows (one after the other); counts add up
+        const size_t G = idx->shards.size();
+        vrod_search_stats agg{};
+        agg.nq = nq;
+        for (size_t g = 0; g < G; ++g) {
+            vrod_index* sh = idx->shards[g];
+            VROD_TRY(set_device(sh));
+            sh->path = idx->path;
+            sh->profiling = idx->profiling;
+            sh->deal = IdMap{idx->id_offset, (uint32_t)kShardBlock, (uint32_t)g, (uint32_t)G};
+            Pending& P = next_slot(sh);
+            VROD_TRY(P.q_raw.ensure(qbytes));
+            HIP_TRY(hipMemcpyAsync(P.q_raw.p, queries, qbytes, from_host ? hipMemcpyHostToDevice : hipMemcpyDefault, P.stream));
+            VROD_TRY(range_collect(sh, P.q_raw.as<float>(), nq, h_thresholds, capacity, res[g]));
+            for (uint32_t q = 0; q < nq; ++q) counts[q] += res[g].counts[q];
+            total += res[g].total;
+            const vrod_search_stats& st = sh->stats;
+            agg.path = st.path;
+            agg.kprime = std::max(agg.kprime, st.kprime);
+            agg.scan_launches += st.scan_launches;
+            agg.fallback_queries = std::max(agg.fallback_queries, st.fallback_queries);   // (the same queries on every shard)
+            agg.split_pass |= st.split_pass;
+            agg.scan_ms = std::max(agg.scan_ms, st.scan_ms);
+            agg.total_ms += st.total_ms;
+            agg.scan_bytes += st.scan_bytes; agg.scan_flops += st.scan_flops;
+            agg.max_fast_err = std::max(agg.max_fast_err, st.max_fast_err);
+            agg.eps_bound = std::max(agg.eps_bound, st.eps_bound);
+        }
+        agg.exchange = 2u;   // peer copies
+        idx->stats = agg;
+    }
+    h_lims[0] = 0;
+    for (uint32_t q = 0; q < nq; ++q) h_lims[q + 1] = h_lims[q] + counts[q];
+    if (total > capacity)
+        return fail(VROD_ERR_CAPACITY, "%llu rows qualify, the buffers hold %llu", (unsigned long long)total, (unsigned long long)capacity);
+    if (!total) return VROD_OK;
+    if (!idx->composite()) {
+        VROD_TRY(idx->range_pool_b.ensure((size_t)total * sizeof(RangeHit)));
+        return range_emit(idx, idx->range_pool.as<RangeHit>(), idx->range_pool_b.as<RangeHit>(), total, out_ids, out_scores, from_host, next_slot(idx).stream);
+    }
+    // the shards' pools gathered on the first device (peer copies) and ordered there as one: (query, score, GLOBAL id)
+    vrod_index::DevGroup& D0 = idx->groups[0];
+    HIP_TRY(hipSetDevice(D0.device));
+    VROD_TRY(idx->range_pool.ensure((size_t)total * sizeof(RangeHit)));
+    VROD_TRY(idx->range_pool_b.ensure((size_t)total * sizeof(RangeHit)));
+    uint64_t at = 0;
+    for (size_t g = 0; g < idx->shards.size(); ++g) {
+        if (!res[g].stored) continue;
+        HIP_TRY(hipMemcpyPeerAsync(idx->range_pool.as<RangeHit>() + at, D0.device, idx->shards[g]->range_pool.p, idx->shards[g]->device,
+                                   (size_t)res[g].stored * sizeof(RangeHit), D0.xstream));
+        at += res[g].stored;
+    }
+    return range_emit(idx, idx->range_pool.as<RangeHit>(), idx->range_pool_b.as<RangeHit>(), total, out_ids, out_scores, from_host, D0.xstream);
+}
+
+static int check_range_args(vrod_index* idx, const void* q, uint32_t nq, const void* thr, uint64_t capacity, const void* lims, const void* oi, const void* os) {
+    if (!idx) return fail(VROD_ERR_INVALID_ARG, "idx is null");
+    if (!lims) return fail(VROD_ERR_INVALID_ARG, "out_lims is null");
+    if (nq && (!q || !thr)) return fail(VROD_ERR_INVALID_ARG, "null buffer");
+    if (capacity && (!oi || !os)) return fail(VROD_ERR_INVALID_ARG, "capacity %llu with a null output buffer", (unsigned long long)capacity);
+    if (idx->n_pending()) return fail(VROD_ERR_INVALID_ARG, "vrod_range_search while a search is pending: call vrod_search_end first");
+    return VROD_OK;
+}
+static int check_thresholds(const float* h_thr, uint32_t nq) {
+    for (uint32_t q = 0; q < nq; ++q)
+        if (h_thr[q] != h_thr[q]) return fail(VROD_ERR_INVALID_VALUE, "threshold %u is NaN", q);
+    return VROD_OK;
+}
+
 // ------------------------------------------------------------------ C ABI
 extern "C" {
 
@@ -1916,6 +2251,7 @@ int vrod_index_destroy(vrod_index* idx) {
         if (idx->caller_ev) (void)hipEventDestroy(idx->caller_ev);
         for (auto& CP : idx->cslot) if (CP.caller_ev) (void)hipEventDestroy(CP.caller_ev);
         idx->out_ids.release(); idx->out_scores.release(); idx->raw_stage.release();
+        idx->range_pool.release(); idx->range_pool_b.release(); idx->range_small.release();
         for (vrod_index* sh : idx->shards) vrod_index_destroy(sh);
         delete idx;
         return VROD_OK;
@@ -1924,7 +2260,7 @@ int vrod_index_destroy(vrod_index* idx) {
     if (idx->stream) (void)hipStreamSynchronize(idx->stream);
     for (Pending& P : idx->slot)
         if (P.stream) (void)hipStreamSynchronize(P.stream);
-    for (DevBuf* b : {&idx->raw_stage, &idx->nrm_ws, &idx->out_ids, &idx->out_scores}) b->release();
+    for (DevBuf* b : {&idx->raw_stage, &idx->nrm_ws, &idx->out_ids, &idx->out_scores, &idx->range_pool, &idx->range_pool_b, &idx->range_small}) b->release();
     for (Pending& P : idx->slot) {
         for (DevBuf* b : {&P.q_raw, &P.q_lp, &P.scores, &P.keys_a, &P.keys_b, &P.lists, &P.small, &P.hist, &P.cand_rows, &P.cand_fast, &P.cand_canon})
             b->release();
@@ -2138,6 +2474,38 @@ int vrod_search(vrod_index* idx, const float* queries, uint32_t nq, uint32_t k, 
     HIP_TRY(hipMemcpyAsync(out_scores, idx->out_scores.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, idx->stream));
     HIP_TRY(hipStreamSynchronize(idx->stream));
     return VROD_OK;
+}
+
+int vrod_range_search(vrod_index* idx, const float* queries, uint32_t nq, const float* thresholds, uint64_t capacity,
+                      uint64_t* out_lims, uint64_t* out_ids, float* out_scores) {
+    VROD_TRY(check_range_args(idx, queries, nq, thresholds, capacity, out_lims, out_ids, out_scores));
+    out_lims[0] = 0;
+    if (!nq) return VROD_OK;
+    VROD_TRY(check_thresholds(thresholds, nq));
+    return range_search(idx, queries, true, nq, thresholds, capacity, out_lims, out_ids, out_scores);
+}
+
+int vrod_range_search_device(vrod_index* idx, const float* d_queries, uint32_t nq, const float* d_thresholds, uint64_t capacity,
+                             uint64_t* d_out_lims, uint64_t* d_out_ids, float* d_out_scores, void* stream) {
+    VROD_TRY(check_range_args(idx, d_queries, nq, d_thresholds, capacity, d_out_lims, d_out_ids, d_out_scores));
+    // pointers on the handle's (first) device.  The call is synchronous: whatever the caller's stream holds -- the
+    // producers of the inputs, the last readers of the outputs -- is complete before the library's streams start.
+    HIP_TRY(hipSetDevice(idx->device));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    std::vector<uint64_t> lims((size_t)nq + 1, 0);
+    std::vector<float> thr(nq);
+    int rc = VROD_OK;
+    if (nq) {
+        HIP_TRY(hipMemcpy(thr.data(), d_thresholds, (size_t)nq * 4, hipMemcpyDeviceToHost));
+        VROD_TRY(check_thresholds(thr.data(), nq));
+        rc = range_search(idx, d_queries, false, nq, thr.data(), capacity, lims.data(), d_out_ids, d_out_scores);
+        if (rc != VROD_OK && rc != VROD_ERR_CAPACITY) return rc;
+    }
+    const std::string why = g_last_error;
+    HIP_TRY(hipSetDevice(idx->device));
+    HIP_TRY(hipMemcpy(d_out_lims, lims.data(), lims.size() * 8, hipMemcpyHostToDevice));
+    g_last_error = why;
+    return rc;
 }
 
 int vrod_merge_topk_device(int device, int metric, const uint64_t* d_ids, const float* d_scores,

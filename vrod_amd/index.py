@@ -196,6 +196,78 @@ class Index:
                                                    out_ids.data_ptr(), out_scores.data_ptr(), C.c_void_p(stream)))
         return out_ids, out_scores
 
+    # -- range search: every row at least as good as a per-query threshold
+    def _range_args(self, nq: int, threshold):
+        thr = np.ascontiguousarray(np.broadcast_to(np.asarray(threshold, dtype=np.float32), (nq,)) if np.ndim(threshold) == 0
+                                   else np.asarray(threshold, dtype=np.float32).reshape(-1))
+        if thr.size != nq:
+            raise ValueError(f"threshold must be a scalar or {nq} values, got {thr.size}")
+        if np.isnan(thr).any():
+            raise ValueError("threshold is NaN")
+        return thr
+
+    def range_search(self, queries: np.ndarray, threshold, capacity=None):
+        """numpy [nq, dim] fp32 and a threshold (a scalar or nq values, in the units of the handle's scores) ->
+        (lims uint64 [nq + 1], ids uint64 [lims[-1]], scores float32 [lims[-1]]): query q's rows are entries
+        lims[q]:lims[q + 1], best first, every row whose score is >= (cosine, ip) / <= (l2) the threshold.
+        capacity=None: a count-only call sizes the buffers; else a result larger than `capacity` raises VrodError with
+        code ERR_CAPACITY (and .lims holds the exact counts)."""
+        queries = np.ascontiguousarray(queries, dtype=np.float32)
+        if queries.ndim == 1:
+            queries = queries[None, :]
+        if queries.ndim != 2 or queries.shape[1] != self.dim:
+            raise ValueError(f"queries must be [nq, {self.dim}]")
+        nq = queries.shape[0]
+        thr = self._range_args(nq, threshold)
+        lims = np.zeros(nq + 1, dtype=np.uint64)
+
+        def call(cap, ids, sc):
+            return self._L.vrod_range_search(self._h, queries.ctypes.data_as(C.c_void_p), nq, thr.ctypes.data_as(C.c_void_p), cap,
+                                             lims.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p) if ids is not None else None,
+                                             sc.ctypes.data_as(C.c_void_p) if sc is not None else None)
+        if capacity is None:
+            rc = call(0, None, None)
+            if rc not in (0, _lib.ERR_CAPACITY):
+                check(rc)
+            capacity = int(lims[-1])
+            if rc == 0:
+                return lims, np.empty(0, np.uint64), np.empty(0, np.float32)
+        capacity = int(capacity)
+        ids = np.empty(max(capacity, 1), dtype=np.uint64)
+        sc = np.empty(max(capacity, 1), dtype=np.float32)
+        rc = call(capacity, ids if capacity else None, sc if capacity else None)
+        if rc == _lib.ERR_CAPACITY:
+            e = VrodError(rc, self._L.vrod_last_error().decode("utf-8", "replace"))
+            e.lims = lims
+            raise e
+        check(rc)
+        n = int(lims[-1])
+        return lims, ids[:n], sc[:n]
+
+    def range_search_device(self, d_queries, d_thresholds, capacity: int, out_lims=None, out_ids=None, out_scores=None):
+        """torch CUDA tensors: queries [nq, dim] fp32, thresholds [nq] fp32 -> (rc, lims int64 [nq + 1], ids int64-viewed
+        uint64 [capacity], scores [capacity]) on the device.  No retry: rc is 0 or ERR_CAPACITY (lims valid either way)."""
+        import torch
+        assert d_queries.is_cuda and d_queries.dtype == torch.float32 and d_queries.is_contiguous()
+        assert d_thresholds.is_cuda and d_thresholds.dtype == torch.float32 and d_thresholds.is_contiguous()
+        nq = d_queries.shape[0]
+        if d_thresholds.numel() != nq:
+            raise ValueError(f"thresholds must hold {nq} values, got {d_thresholds.numel()}")
+        dev = d_queries.device
+        if out_lims is None:
+            out_lims = torch.empty(nq + 1, dtype=torch.int64, device=dev)
+        if out_ids is None:
+            out_ids = torch.empty(max(int(capacity), 1), dtype=torch.int64, device=dev)
+        if out_scores is None:
+            out_scores = torch.empty(max(int(capacity), 1), dtype=torch.float32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = self._L.vrod_range_search_device(self._h, d_queries.data_ptr(), nq, d_thresholds.data_ptr(), int(capacity), out_lims.data_ptr(),
+                                              out_ids.data_ptr() if capacity else None, out_scores.data_ptr() if capacity else None,
+                                              C.c_void_p(stream))
+        if rc not in (0, _lib.ERR_CAPACITY):
+            check(rc)
+        return rc, out_lims, out_ids, out_scores
+
     # -- pipelined search: begin(s+1) before end(s) keeps the device busy between batches
     def search_begin_device(self, d_queries, k: int, out_ids, out_scores):
         import torch
