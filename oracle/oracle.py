@@ -56,6 +56,14 @@ def lib() -> C.CDLL:
         L.orc_scan_topk.argtypes = [f32p, u64, u32, f32p, u32, u32, i32, u64, u64p, f32p, i32]
         L.orc_merge_topk.restype = i32
         L.orc_merge_topk.argtypes = [u64p, f32p, u32, u32, u32, i32, u64p, f32p]
+        L.orc_scan_range.restype = i32
+        L.orc_scan_range.argtypes = [f32p, u64, u32, f32p, u32, f32p, i32, C.POINTER(C.c_uint8), u64, i32, C.POINTER(C.c_void_p)]
+        L.orc_range_lims.restype = u64p
+        L.orc_range_lims.argtypes = [C.c_void_p]
+        L.orc_range_copy.restype = None
+        L.orc_range_copy.argtypes = [C.c_void_p, u64p, f32p]
+        L.orc_range_free.restype = None
+        L.orc_range_free.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -106,6 +114,91 @@ def search(raw_corpus: np.ndarray, raw_queries: np.ndarray, k: int, dtype: int, 
     """End to end: prepare both sides, then scan."""
     return scan_topk(prepare(raw_corpus, dtype, metric, threads), prepare(raw_queries, dtype, metric, threads),
                      k, metric, id_offset, threads)
+
+
+def scan_range(corpus: np.ndarray, queries: np.ndarray, thresholds, metric: int, mask=None,
+               id_offset: int = 0, threads: int = 1):
+    """corpus/queries are PREPARED fp32 arrays; thresholds: a scalar or nq values; metric: the score form
+    (METRIC_COSINE also serves the inner product); mask: None or n bools, row r is eligible iff mask[r].
+    Every eligible row whose canonical score is >= (cosine form) / <= (l2) the query's threshold -- inclusive, a NaN
+    score never qualifies -- per query best first, then id.  Returns (lims u64 [nq + 1], ids u64, scores f32)."""
+    corpus = np.ascontiguousarray(corpus, dtype=np.float32)
+    queries = np.ascontiguousarray(queries, dtype=np.float32)
+    if queries.ndim != 2 or (corpus.ndim == 2 and corpus.shape[1] != queries.shape[1]):
+        raise ValueError(f"corpus {corpus.shape} and queries {queries.shape} must be [n, dim] and [nq, dim]")
+    n, dim = corpus.shape if corpus.ndim == 2 else (0, queries.shape[1])
+    nq = queries.shape[0]
+    thr = np.asarray(thresholds, dtype=np.float32).reshape(-1)
+    if thr.size not in (1, nq):
+        raise ValueError(f"thresholds must be a scalar or {nq} values, got {thr.size}")
+    thr = np.full(nq, thr[0], np.float32) if thr.size == 1 else np.ascontiguousarray(thr)
+    mp = None
+    if mask is not None:
+        mask = np.ascontiguousarray(np.asarray(mask, dtype=bool).reshape(-1)).view(np.uint8)
+        if mask.size != n:
+            raise ValueError(f"mask must hold {n} entries, got {mask.size}")
+        mp = mask.ctypes.data_as(C.POINTER(C.c_uint8))
+    res = C.c_void_p()
+    rc = lib().orc_scan_range(_f32p(corpus), n, dim, _f32p(queries), nq, _f32p(thr), metric, mp, id_offset, threads,
+                              C.byref(res))
+    if rc != 0:
+        raise RuntimeError(f"orc_scan_range rc={rc}")
+    try:
+        lims = np.ctypeslib.as_array(lib().orc_range_lims(res), shape=(nq + 1,)).copy()
+        total = int(lims[-1])
+        ids = np.empty(total, dtype=np.uint64)
+        sc = np.empty(total, dtype=np.float32)
+        if total:
+            lib().orc_range_copy(res, _u64p(ids), _f32p(sc))
+    finally:
+        lib().orc_range_free(res)
+    return lims, ids, sc
+
+
+def range_search(raw_corpus: np.ndarray, raw_queries: np.ndarray, thresholds, dtype: int, prep: int, form: int,
+                 mask=None, id_offset: int = 0, threads: int = 1):
+    """End to end: prepare both sides (prep: METRIC_COSINE normalises, METRIC_L2 takes the vectors as given -- the
+    inner product's preparation too), then scan_range in score form `form`."""
+    return scan_range(prepare(raw_corpus, dtype, prep, threads), prepare(raw_queries, dtype, prep, threads),
+                      thresholds, form, mask, id_offset, threads)
+
+
+def merge_range(parts, form: int):
+    """The union of range answers over disjoint row blocks (each (lims, ids, scores) of the SAME queries): a range
+    answer is decomposable over rows; per query the blocks' entries are ordered by (score best first, id)."""
+    nq = parts[0][0].size - 1
+    lims, oi, osc = [0], [], []
+    for q in range(nq):
+        i = np.concatenate([p[1][int(p[0][q]):int(p[0][q + 1])] for p in parts])
+        s = np.concatenate([p[2][int(p[0][q]):int(p[0][q + 1])] for p in parts])
+        key = -s.astype(np.float64) if form == METRIC_COSINE else s.astype(np.float64)
+        order = np.lexsort((i, key))
+        oi.append(i[order])
+        osc.append(s[order])
+        lims.append(lims[-1] + i.size)
+    return (np.array(lims, np.uint64), np.concatenate(oi) if oi else np.zeros(0, np.uint64),
+            np.concatenate(osc) if osc else np.zeros(0, np.float32))
+
+
+def numpy_range_from_scores(scores: np.ndarray, thresholds, metric: int, mask=None, id_offset: int = 0):
+    """Range answer from a [nq, n] score matrix, restated with numpy (comparison + lexsort)."""
+    nq, n = scores.shape
+    thr = np.broadcast_to(np.asarray(thresholds, dtype=np.float32), (nq,))
+    lims, oi, osc = [0], [], []
+    with np.errstate(invalid="ignore"):
+        for qi in range(nq):
+            s = scores[qi]
+            ok = (s >= thr[qi]) if metric == METRIC_COSINE else (s <= thr[qi])     # a NaN score: False
+            if mask is not None:
+                ok &= np.asarray(mask, dtype=bool)
+            rows = np.flatnonzero(ok)
+            key = -s[rows].astype(np.float64) if metric == METRIC_COSINE else s[rows].astype(np.float64)
+            order = rows[np.lexsort((rows, key))]
+            oi.append(order.astype(np.uint64) + np.uint64(id_offset))
+            osc.append(s[order])
+            lims.append(lims[-1] + order.size)
+    return (np.array(lims, np.uint64), np.concatenate(oi) if oi else np.zeros(0, np.uint64),
+            np.concatenate(osc).astype(np.float32) if osc else np.zeros(0, np.float32))
 
 
 def merge_topk(ids: np.ndarray, scores: np.ndarray, metric: int):

@@ -320,3 +320,212 @@ int orc_scan_topk(const float *corpus, uint64_t n, uint32_t dim, const float *qu
     free(jobs);
     return 0;
 }
+
+/* ------------------------------------------------------------------ range scan */
+
+/* Whether score s is at least as good as threshold t: inclusive; a NaN score never is. */
+static int range_qualifies(int metric, float s, float t) {
+    return metric == ORC_METRIC_COSINE ? (s >= t) : (s <= t);
+}
+
+typedef struct {
+    uint64_t id;
+    float score;
+} range_hit;
+
+/* qsort has no context argument: one comparator per metric */
+static int range_cmp_cosine(const void *a, const void *b) {
+    const range_hit *x = (const range_hit *)a, *y = (const range_hit *)b;
+    if (ranks_before(ORC_METRIC_COSINE, x->score, x->id, y->score, y->id)) return -1;
+    if (ranks_before(ORC_METRIC_COSINE, y->score, y->id, x->score, x->id)) return 1;
+    return 0;
+}
+
+static int range_cmp_l2(const void *a, const void *b) {
+    const range_hit *x = (const range_hit *)a, *y = (const range_hit *)b;
+    if (ranks_before(ORC_METRIC_L2, x->score, x->id, y->score, y->id)) return -1;
+    if (ranks_before(ORC_METRIC_L2, y->score, y->id, x->score, x->id)) return 1;
+    return 0;
+}
+
+typedef struct {
+    range_hit *v;
+    uint64_t n, cap;
+} range_vec;
+
+static int range_vec_push(range_vec *l, uint64_t id, float s) {
+    if (l->n == l->cap) {
+        uint64_t cap = l->cap ? l->cap * 2 : 64;
+        range_hit *v = (range_hit *)realloc(l->v, sizeof(range_hit) * (size_t)cap);
+        if (!v) return 2;
+        l->v = v;
+        l->cap = cap;
+    }
+    l->v[l->n].id = id;
+    l->v[l->n].score = s;
+    l->n++;
+    return 0;
+}
+
+struct orc_range_result {
+    uint32_t nq;
+    uint64_t *lims;  /* nq + 1 */
+    range_hit *hits; /* lims[nq], query by query, best first, then id */
+};
+
+typedef struct {
+    const float *corpus, *queries, *thresholds;
+    const uint8_t *mask;
+    uint64_t r0, r1, id_offset;
+    uint32_t dim, nq;
+    int metric, rc;
+    range_vec *lists; /* nq of them: this worker's rows, in row order */
+} range_job;
+
+static void *range_worker(void *p) {
+    range_job *j = (range_job *)p;
+    for (uint32_t qi = 0; qi < j->nq && !j->rc; ++qi) {
+        const float *q = j->queries + (uint64_t)qi * j->dim;
+        const float t = j->thresholds[qi];
+        for (uint64_t r = j->r0; r < j->r1; ++r) {
+            if (j->mask && !j->mask[r]) continue;
+            const float *x = j->corpus + r * (uint64_t)j->dim;
+            float s = j->metric == ORC_METRIC_COSINE ? orc_dot_canonical(q, x, j->dim)
+                                                     : orc_l2_canonical(q, x, j->dim);
+            if (range_qualifies(j->metric, s, t) && range_vec_push(&j->lists[qi], r + j->id_offset, s)) {
+                j->rc = 2;
+                break;
+            }
+        }
+    }
+    return NULL;
+}
+
+typedef struct {
+    orc_range_result *res;
+    const range_vec *lists; /* collectors x nq */
+    int collectors, metric;
+    uint32_t q0, step;
+} range_sort_job;
+
+static void *range_sort_worker(void *p) {
+    range_sort_job *j = (range_sort_job *)p;
+    const uint32_t nq = j->res->nq;
+    for (uint32_t q = j->q0; q < nq; q += j->step) {
+        range_hit *seg = j->res->hits + j->res->lims[q], *dst = seg;
+        for (int t = 0; t < j->collectors; ++t) {
+            const range_vec *l = &j->lists[(size_t)t * nq + q];
+            if (l->n) memcpy(dst, l->v, sizeof(range_hit) * (size_t)l->n);
+            dst += l->n;
+        }
+        qsort(seg, (size_t)(dst - seg), sizeof(range_hit), j->metric == ORC_METRIC_COSINE ? range_cmp_cosine : range_cmp_l2);
+    }
+    return NULL;
+}
+
+void orc_range_free(orc_range_result *r) {
+    if (!r) return;
+    free(r->lims);
+    free(r->hits);
+    free(r);
+}
+
+int orc_scan_range(const float *corpus, uint64_t n, uint32_t dim, const float *queries,
+                   uint32_t nq, const float *thresholds, int metric, const uint8_t *mask,
+                   uint64_t id_offset, int threads, orc_range_result **out) {
+    *out = NULL;
+    if (metric != ORC_METRIC_COSINE && metric != ORC_METRIC_L2) return 1;
+    for (uint32_t q = 0; q < nq; ++q)
+        if (thresholds[q] != thresholds[q]) return 1; /* a NaN threshold has no meaning */
+    if (threads < 1) threads = 1;
+    if ((uint64_t)threads > n) threads = n ? (int)n : 1;
+    orc_range_result *res = (orc_range_result *)calloc(1, sizeof(orc_range_result));
+    range_vec *lists = (range_vec *)calloc((size_t)threads * (nq ? nq : 1), sizeof(range_vec));
+    pthread_t *th = (pthread_t *)malloc(sizeof(pthread_t) * (size_t)threads);
+    range_job *jobs = (range_job *)malloc(sizeof(range_job) * (size_t)threads);
+    int rc = (!res || !lists || !th || !jobs) ? 2 : 0;
+    if (!rc) {
+        /* collect: row ranges on pthreads, every worker keeps its own per-query lists */
+        for (int t = 0; t < threads; ++t) {
+            range_job *j = &jobs[t];
+            j->corpus = corpus;
+            j->queries = queries;
+            j->thresholds = thresholds;
+            j->mask = mask;
+            j->r0 = n * (uint64_t)t / (uint64_t)threads;
+            j->r1 = n * (uint64_t)(t + 1) / (uint64_t)threads;
+            j->id_offset = id_offset;
+            j->dim = dim;
+            j->nq = nq;
+            j->metric = metric;
+            j->rc = 0;
+            j->lists = lists + (size_t)t * nq;
+            if (t + 1 < threads) pthread_create(&th[t], NULL, range_worker, j);
+        }
+        range_worker(&jobs[threads - 1]);
+        for (int t = 0; t + 1 < threads; ++t) pthread_join(th[t], NULL);
+        for (int t = 0; t < threads; ++t)
+            if (jobs[t].rc) rc = jobs[t].rc;
+    }
+    if (!rc) {
+        res->nq = nq;
+        res->lims = (uint64_t *)malloc(sizeof(uint64_t) * ((size_t)nq + 1));
+        if (!res->lims) rc = 2;
+    }
+    if (!rc) {
+        res->lims[0] = 0;
+        for (uint32_t q = 0; q < nq; ++q) {
+            uint64_t c = 0;
+            for (int t = 0; t < threads; ++t) c += lists[(size_t)t * nq + q].n;
+            res->lims[q + 1] = res->lims[q] + c;
+        }
+        const uint64_t total = res->lims[nq];
+        res->hits = (range_hit *)malloc(sizeof(range_hit) * (size_t)(total ? total : 1));
+        if (!res->hits) rc = 2;
+    }
+    if (!rc) {
+        /* sort: each query's rows gathered in row order, then ordered best first, then id (a total order: the
+         * result does not depend on how the rows were dealt to threads); queries are dealt to the threads */
+        int st = threads < 1 ? 1 : threads;
+        if ((uint32_t)st > nq) st = nq ? (int)nq : 1;
+        range_sort_job *sj = (range_sort_job *)malloc(sizeof(range_sort_job) * (size_t)st);
+        pthread_t *sth = (pthread_t *)malloc(sizeof(pthread_t) * (size_t)st);
+        if (!sj || !sth) rc = 2;
+        else {
+            for (int t = 0; t < st; ++t) {
+                sj[t].res = res;
+                sj[t].lists = lists;
+                sj[t].collectors = threads;
+                sj[t].q0 = (uint32_t)t;
+                sj[t].step = (uint32_t)st;
+                sj[t].metric = metric;
+                if (t + 1 < st) pthread_create(&sth[t], NULL, range_sort_worker, &sj[t]);
+            }
+            range_sort_worker(&sj[st - 1]);
+            for (int t = 0; t + 1 < st; ++t) pthread_join(sth[t], NULL);
+        }
+        free(sj);
+        free(sth);
+    }
+    if (lists)
+        for (size_t i = 0; i < (size_t)threads * nq; ++i) free(lists[i].v);
+    free(lists);
+    free(th);
+    free(jobs);
+    if (rc) {
+        orc_range_free(res);
+        return rc;
+    }
+    *out = res;
+    return 0;
+}
+
+const uint64_t *orc_range_lims(const orc_range_result *r) { return r->lims; }
+
+void orc_range_copy(const orc_range_result *r, uint64_t *out_ids, float *out_scores) {
+    const uint64_t total = r->lims[r->nq];
+    for (uint64_t i = 0; i < total; ++i) {
+        out_ids[i] = r->hits[i].id;
+        out_scores[i] = r->hits[i].score;
+    }
+}

@@ -67,6 +67,20 @@ int orc_scan_topk(const float *corpus, uint64_t n, uint32_t dim, const float *qu
 int orc_merge_topk(const uint64_t *ids, const float *scores, uint32_t n_lists, uint32_t nq,
                    uint32_t k, int metric, uint64_t *out_ids, float *out_scores);
 
+/* --- the range scan: every row of the prepared corpus whose canonical score is at least as good as the query's
+ * threshold -- s >= t (COSINE form, which is also the inner product's) / s <= t (L2), the boundary inclusive; a NaN
+ * score never qualifies; a NaN threshold is refused (rc 1).  mask: NULL, or n bytes, row r is eligible iff
+ * mask[r] != 0.  id = row index + id_offset.  Per query: best first, ties -> smaller id.  Collect, then sort: the
+ * cost is n * dim per query plus the size of the answer.  threads > 1: row ranges on pthreads, same result.
+ * The result is held by the library: read lims (nq + 1 entries), copy the lims[nq] entries out, free. */
+typedef struct orc_range_result orc_range_result;
+int orc_scan_range(const float *corpus, uint64_t n, uint32_t dim, const float *queries,
+                   uint32_t nq, const float *thresholds, int metric, const uint8_t *mask,
+                   uint64_t id_offset, int threads, orc_range_result **out);
+const uint64_t *orc_range_lims(const orc_range_result *r);
+void orc_range_copy(const orc_range_result *r, uint64_t *out_ids, float *out_scores);
+void orc_range_free(orc_range_result *r);
+
 #ifdef __cplusplus
 }
 #endif

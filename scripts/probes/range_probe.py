@@ -10,7 +10,10 @@ total_ms from the library's stats, and the median wall time of the synchronous c
 VROD_HIP_LIB points the same script at another build of the library (a parent build has no range search: only the
 baseline lines are printed).
 
-    python scripts/probes/range_probe.py [--rows 10000000] [--batches 10] [--warmup 2]
+--check compares every range result (lims, ids, score bits) with oracle.range_search over the same synthetic rows,
+in blocks of a million rows on the host: meant for --rows of a few million at most.
+
+    python scripts/probes/range_probe.py [--rows 10000000] [--batches 10] [--warmup 2] [--check]
 """
 import argparse
 import json
@@ -26,6 +29,21 @@ import torch  # noqa: E402
 import vrod_amd as va  # noqa: E402
 
 CORPUS_SEED, QUERY_SEED = 1, 2
+
+
+def oracle_check(a, dq, thr, lims, ids, sc):
+    """The device result against oracle.range_search (bf16, cosine), the corpus scanned in row blocks and merged."""
+    from oracle import oracle as O
+    threads = max(1, min(16, len(os.sched_getaffinity(0))))
+    rq = O.synth_rows(QUERY_SEED, 0, a.nq, a.dim, threads=threads)
+    assert np.array_equal(rq.view(np.uint32), dq.cpu().numpy().view(np.uint32))
+    h_thr = thr.cpu().numpy()
+    parts = [O.range_search(O.synth_rows(CORPUS_SEED, lo, min(10 ** 6, a.rows - lo), a.dim, threads=threads), rq, h_thr, O.DTYPE_BF16,
+                            O.METRIC_COSINE, O.METRIC_COSINE, id_offset=lo, threads=threads) for lo in range(0, a.rows, 10 ** 6)]
+    ol, oi, osc = O.merge_range(parts, O.METRIC_COSINE)
+    total = int(ol[-1])
+    return bool(np.array_equal(lims.cpu().numpy().view(np.uint64), ol) and np.array_equal(ids.cpu().numpy().view(np.uint64)[:total], oi)
+                and np.array_equal(sc.cpu().numpy()[:total].view(np.uint32), osc.view(np.uint32)))
 
 
 def timed(fn, batches, warmup):
@@ -48,6 +66,7 @@ def main():
     ap.add_argument("--nq", type=int, default=1024)
     ap.add_argument("--batches", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--check", action="store_true", help="compare every range result with oracle.range_search")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     has_range = hasattr(va.load(), "vrod_range_search_device")
@@ -88,7 +107,8 @@ def main():
             med, best = timed(run, max(3, a.batches // (1 if total < 10 ** 6 else 3)), a.warmup)
             st = ix.last_stats()
             per = torch.diff(lims).cpu().numpy()
-            print(json.dumps({"run": name, "rc": state["rc"], "rows_total": total, "rows_per_query_min": int(per.min()), "rows_per_query_max": int(per.max()),
+            extra = {"oracle_equal": oracle_check(a, dq, thr, lims, ids, sc)} if a.check else {}
+            print(json.dumps({**extra, "run": name, "rc": state["rc"], "rows_total": total, "rows_per_query_min": int(per.min()), "rows_per_query_max": int(per.max()),
                               "median_ms": med, "min_ms": best, "scan_ms": st["scan_ms"], "total_ms": st["total_ms"], "scan_launches": st["scan_launches"],
                               "kprime": st["kprime"], "fallback_queries": st["fallback_queries"], "max_fast_err": st["max_fast_err"],
                               "eps_bound": st["eps_bound"], "vs_topk10": med / min(base)}), flush=True)

@@ -15,24 +15,7 @@ pytestmark = pytest.mark.gpu
 DT = {"f32": 0, "bf16": 1}
 ME = {"cosine": 0, "l2": 1}
 
-# Which kernel a batch reaches, by the dispatcher's rule (search_plan.h route -- checked on the CPU by
-# test_search_plan.py --, kernels_mfma.hip launch_scan_mfma, kernels_mfma_skinny.hip mfma_skinny_max_queries):
-#   stream       path STREAM forced, <= 4 queries: kernels_stream.hip, one pass per 8 queries
-#   skinny       bf16 rows, path MFMA, 5..64 queries, the queries fit in LDS (64-query form at d = 768; not at d = 3072)
-#   w4           bf16 rows, path MFMA, > 64 queries: the 4-wave kernel
-#   w4-split     fp32 rows, VROD_F32_SPLIT=1, > 32 queries: the 4-wave kernel's SPLIT form over the [hi | lo] planes
-#   skinny-split fp32 rows, VROD_F32_SPLIT=1, <= 32 queries whose [hi | lo] fit in LDS (d = 768; not at d = 3072)
-#   phased       fp32 rows, VROD_F32_SPLIT=0, path MFMA: the 8-wave fp32 matrix-core kernel
-KERNELS = {
-    # name: (dtype, path, queries, VROD_F32_SPLIT, split_pass, dims)
-    "stream-f32": ("f32", 1, 4, "0", 0, (768, 3072)),
-    "stream-bf16": ("bf16", 1, 4, None, 0, (768, 3072)),
-    "skinny": ("bf16", 2, 33, None, 0, (768,)),
-    "w4": ("bf16", 2, 100, None, 0, (768, 3072)),
-    "w4-split": ("f32", 2, 100, "1", 1, (768, 3072)),
-    "skinny-split": ("f32", 2, 20, "1", 1, (768,)),
-    "phased": ("f32", 2, 100, "0", 0, (768, 3072)),
-}
+KERNELS = F.KERNELS     # which kernel a batch reaches: certificate_fixtures.py
 N_ALL = 2048     # <= VROD_MAX_K, and k' = N fits the split pass's k + max(32, k / 2) <= 4096
 
 
