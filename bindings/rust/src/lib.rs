@@ -64,6 +64,8 @@ extern "C" {
     pub fn vrod_index_get_rows(idx: *mut vrod_index, first: u64, n: u64, out_rows: *mut f32) -> c_int;
     pub fn vrod_index_delete(idx: *mut vrod_index, ids: *const u64, n: u64) -> c_int;
     pub fn vrod_index_live_count(idx: *const vrod_index, out: *mut u64) -> c_int;
+    pub fn vrod_index_update(idx: *mut vrod_index, ids: *const u64, rows: *const f32, n: u64) -> c_int;
+    pub fn vrod_index_compact(idx: *mut vrod_index, out_new_ids: *mut u64, map_len: u64) -> c_int;
     pub fn vrod_index_set_filter(idx: *mut vrod_index, allow_words: *const u32, n_rows: u64) -> c_int;
     pub fn vrod_index_filter_count(idx: *const vrod_index, out: *mut u64) -> c_int;
     pub fn vrod_search(idx: *mut vrod_index, queries: *const f32, nq: u32, k: u32,
@@ -162,9 +164,35 @@ impl Collection {
     }
 
     /// Deletes rows by the ids `search` reports (`DeleteCommand::execute`).  An id that is not a row fails the whole
-    /// call and deletes nothing; deleting a row twice is fine.  Ids are never reused: `len()` still counts them.
+    /// call and deletes nothing; deleting a row twice is fine.  Ids are never reused until `compact` renumbers them:
+    /// `len()` still counts them.
     pub fn delete(&mut self, ids: &[u64]) -> Result<(), ScanError> {
         check(unsafe { vrod_index_delete(self.idx, ids.as_ptr(), ids.len() as u64) })
+    }
+
+    /// Gives row `ids[i]` the vector `embeddings[i]` in place (`UpdateCommand::execute`): the row keeps its id and
+    /// the vector is prepared as `add` prepares it.  An id that is not a current row (a deleted one included) or a
+    /// NaN / Inf fails the whole call and changes nothing; an id named twice takes the last vector.
+    pub fn update(&mut self, ids: &[u64], embeddings: &[Vec<f32>]) -> Result<(), ScanError> {
+        if embeddings.len() != ids.len() {
+            return Err(ScanError::Dim { got: embeddings.len(), want: ids.len() });
+        }
+        let mut flat = Vec::with_capacity(embeddings.len() * self.dim);
+        for e in embeddings {
+            if e.len() != self.dim {
+                return Err(ScanError::Dim { got: e.len(), want: self.dim });
+            }
+            flat.extend_from_slice(e);
+        }
+        check(unsafe { vrod_index_update(self.idx, ids.as_ptr(), flat.as_ptr(), ids.len() as u64) })
+    }
+
+    /// Physically removes the deleted rows (`ReindexCommand::execute`) and renumbers the survivors densely, in order.
+    /// Returns the new id of every old row (`u64::MAX` for a deleted one); afterwards `len() == live_len()`.
+    pub fn compact(&mut self) -> Result<Vec<u64>, ScanError> {
+        let mut map = vec![0u64; self.len() as usize];
+        check(unsafe { vrod_index_compact(self.idx, map.as_mut_ptr(), map.len() as u64) })?;
+        Ok(map)
     }
 
     /// Rows added minus rows deleted.

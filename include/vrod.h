@@ -10,6 +10,8 @@
  *                                     (src/command/types.rs:56-80), rows are the
  *                                     Vec<Vec<f32>> of src/utils/embeddings.rs:29
  *   vrod_index_delete              <- the DELETE command CommandBuilder names (src/command/types.rs, builder.rs)
+ *   vrod_index_update              <- the UPDATE command (src/command/types.rs:82, builder.rs:53)
+ *   vrod_index_compact             <- the REINDEX command (src/command/types.rs:134, builder.rs:73)
  *   vrod_search                    <- SearchSimilarCommand::execute
  *                                     (src/command/types.rs:121-132), built by
  *                                     CommandBuilder::build "SEARCHSIMILAR"
@@ -141,9 +143,35 @@ int vrod_index_set_id_offset(vrod_index *idx, uint64_t offset);
  * over the live rows alone (ties still broken by smaller id; slots beyond the live rows are (VROD_ID_NONE, NaN)).
  * Deleting a row again, or naming it twice in one call, is fine.  An id that is not a current row (below the offset,
  * or id - offset >= count) fails the whole call with VROD_ERR_INVALID_ARG and deletes nothing; n == 0 does nothing.
- * Ids are never reused: vrod_index_count still counts every row ever added (and is the next id), vrod_index_get_rows
- * still reads deleted rows back, and vrod_search_stats scan_bytes / scan_flops still count every stored row. */
+ * Ids are never reused until vrod_index_compact renumbers them: vrod_index_count still counts every row ever added
+ * (and is the next id), vrod_index_get_rows still reads deleted rows back, and vrod_search_stats scan_bytes /
+ * scan_flops still count every stored row. */
 int vrod_index_delete(vrod_index *idx, const uint64_t *ids, uint64_t n);
+/* Update rows in place (<- vRod's UPDATE, src/command/types.rs:82, builder.rs:53): row ids[i] (host memory, ids as
+ * searches report them, id_offset applied) gets the vector rows[i] (n x dim fp32, host memory), prepared exactly as
+ * vrod_index_add prepares it (normalised for COSINE, bf16-rounded on BF16 handles), and keeps its id.  Afterwards
+ * every search -- any entry point, path, dtype or metric, pipelined, replayed, multi-device, range, band or exact,
+ * with a filter and deletions in place -- and vrod_index_get_rows give bit for bit what they give on a fresh handle
+ * built from the rows given to vrod_index_add with rows[i] put in place of row ids[i], in order: an id named twice
+ * takes the last vector.  An id that is not a current row (below the offset, id - offset >= count, or a deleted row)
+ * fails the whole call with VROD_ERR_INVALID_ARG, a NaN or Inf anywhere in `rows` with VROD_ERR_INVALID_VALUE; a
+ * failed call changes nothing.  n == 0 does nothing.  Counts, deletions and the filter are unchanged.  The
+ * certificate's bound (vrod_search_stats eps_bound) may stay wider than a fresh handle's -- it follows the largest
+ * row norm the handle has ever held -- the results do not differ.  While a search is pending: VROD_ERR_INVALID_ARG. */
+int vrod_index_update(vrod_index *idx, const uint64_t *ids, const float *rows, uint64_t n);
+/* Compact (<- vRod's REINDEX, src/command/types.rs:134, builder.rs:73): physically remove every deleted row, in
+ * place.  The surviving rows keep their order and are renumbered densely: the survivor with the j-th smallest id gets
+ * id offset + j.  Afterwards the handle is indistinguishable from a fresh handle with the same id_offset to which
+ * only the surviving rows were added, in order: vrod_index_count = vrod_index_live_count = the old live count,
+ * vrod_index_get_rows, every search and range search (ids and score bits), and their scan_bytes / scan_flops --
+ * deleted rows stop costing scan time.  A filter that is set follows its rows (vrod_index_filter_count is unchanged).
+ * out_new_ids (host memory, may be NULL): map_len must equal vrod_index_count before the call (else
+ * VROD_ERR_INVALID_ARG, nothing changes); entry i receives the new id of old id offset + i, or VROD_ID_NONE if that
+ * row was deleted.  With nothing deleted nothing moves and the map is the identity.  The allocation is kept: the freed
+ * rows serve later adds.  Multi-device handles: VROD_ERR_UNSUPPORTED, nothing changes.  While a search is pending:
+ * VROD_ERR_INVALID_ARG.  Every check and allocation comes before the first row moves; a VROD_ERR_HIP after that
+ * leaves the handle unusable (vrod_last_error says so): destroy it. */
+int vrod_index_compact(vrod_index *idx, uint64_t *out_new_ids, uint64_t map_len);
 /* Rows added minus rows deleted. */
 int vrod_index_live_count(const vrod_index *idx, uint64_t *out);
 /* Allow-list filter (one per handle): every search after this call -- any entry point, path, dtype or metric,

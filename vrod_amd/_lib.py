@@ -21,7 +21,7 @@ SYMBOLS = [
     "vrod_search_begin_device", "vrod_search_begin_synthetic_device", "vrod_search_end", "vrod_search_pending",
     "vrod_merge_topk_device", "vrod_merge_topk_packed_device", "vrod_index_set_path", "vrod_index_set_profiling",
     "vrod_index_last_stats", "vrod_index_shard_stats", "vrod_last_error", "vrod_version", "vrod_synth_rows_device",
-    "vrod_range_search", "vrod_range_search_device",
+    "vrod_range_search", "vrod_range_search_device", "vrod_index_update", "vrod_index_compact",
 ]
 
 ERR_CAPACITY = 8   # VROD_ERR_CAPACITY: a range search's result does not fit the caller's buffers (out_lims is valid)
@@ -78,6 +78,8 @@ def load() -> C.CDLL:
     L.vrod_index_get_rows.argtypes = [vp, u64, u64, vp]
     L.vrod_index_delete.argtypes = [vp, vp, u64]
     L.vrod_index_live_count.argtypes = [vp, C.POINTER(u64)]
+    L.vrod_index_update.argtypes = [vp, vp, vp, u64]
+    L.vrod_index_compact.argtypes = [vp, vp, u64]
     L.vrod_index_set_filter.argtypes = [vp, vp, u64]
     L.vrod_index_filter_count.argtypes = [vp, C.POINTER(u64)]
     L.vrod_search.argtypes = [vp, vp, u32, u32, vp, vp]

@@ -101,30 +101,16 @@ template <typename T>
 __global__ __launch_bounds__(256) void row_fastnorm_kernel(const T* __restrict__ rows, uint64_t n,
                                                            uint32_t ld, float* __restrict__ xn2,
                                                            uint32_t* __restrict__ max_bits) {
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     const int lane = threadIdx.x & 63;
     const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
     const uint32_t units = ld * (uint32_t)sizeof(T) / 16;
     float wave_max = 0.0f;   // one atomic per wave, not per row (every row hits the same address)
     for (uint64_t r = wave; r < n; r += nwaves) {
-        const u32x4* x = reinterpret_cast<const u32x4*>(rows + r * (uint64_t)ld);
+        const u32x4_t* x = reinterpret_cast<const u32x4_t*>(rows + r * (uint64_t)ld);
         float s = 0.0f;
-        for (uint32_t j = lane; j < units; j += 64) {
-            const u32x4 v = x[j];
-            if constexpr (sizeof(T) == 2) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float lo = __uint_as_float(v[e] << 16), hi = __uint_as_float(v[e] & 0xFFFF0000u);
-                    s = __builtin_fmaf(lo, lo, s);
-                    s = __builtin_fmaf(hi, hi, s);
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { const float f = __uint_as_float(v[e]); s = __builtin_fmaf(f, f, s); }
-            }
-        }
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        for (uint32_t j = lane; j < units; j += 64) s = fastnorm_fold<T>(x[j], s);
+        s = fastnorm_wave_sum(s);
         if (lane == 0) xn2[r] = s;
         wave_max = __builtin_fmaxf(wave_max, s);
     }

@@ -37,6 +37,31 @@ __device__ inline bf16_t f32_to_bf16_rne(float x) {
     return (bf16_t)(u >> 16);
 }
 
+// ---- fast squared norm of a stored row, one wave per row (kernels_prep.hip row_fastnorm_kernel, kernels_mutate.hip
+// scatter_rows_kernel): lane l folds the 16-B units l, l + 64, ... of the row in ascending order, element by element,
+// then the wave adds its 64 partial sums by xor shuffles.  Both kernels go through these two functions, so a row
+// written by an update gets the xnorm2 bits the same row gets when it is appended.
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+template <typename T>
+__device__ inline float fastnorm_fold(u32x4_t v, float s) {
+    if constexpr (sizeof(T) == 2) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float lo = __uint_as_float(v[e] << 16), hi = __uint_as_float(v[e] & 0xFFFF0000u);
+            s = __builtin_fmaf(lo, lo, s);
+            s = __builtin_fmaf(hi, hi, s);
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { const float f = __uint_as_float(v[e]); s = __builtin_fmaf(f, f, s); }
+    }
+    return s;
+}
+__device__ inline float fastnorm_wave_sum(float s) {
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    return s;
+}
+
 // ---- order-preserving keys: LARGER key == BETTER result ----
 // COSINE (higher score better): monotone map of the float.  L2 (lower better): its
 // complement.  NaN ranks worst (key 0).  Ties on the score are broken by smaller id:

@@ -32,6 +32,7 @@
 #include "vrod_kernels.h"
 #include "kernels_range.h"
 #include "search_plan.h"
+#include "compact_plan.h"
 
 using namespace vrod;
 
@@ -198,6 +199,9 @@ struct vrod_index {
 
     // workspaces
     DevBuf raw_stage, nrm_ws, out_ids, out_scores;
+    // vrod_index_update: a chunk's prepared rows and their destination rows; vrod_index_compact: live rows below each
+    // 32-row word (compact_plan.h compact_word_bases)
+    DevBuf upd_stage, upd_dst, compact_ws;
     // range searches (vrod_range_search): the pool of qualifying rows and its sort partner, and the small block
     // [total (u64) | the caller's thresholds [nq] | per-query counters [nq]]
     DevBuf range_pool, range_pool_b, range_small;
@@ -370,6 +374,10 @@ static int check_bad_flag(vrod_index* idx, const char* what) {
 }
 
 static const uint64_t kStageRows = 1u << 16;
+// rows per staged chunk of an add or update of n rows: 256 MiB of raw rows at most
+static uint64_t stage_chunk_rows(const vrod_index* idx, uint64_t n) {
+    return std::min<uint64_t>(n, std::max<uint64_t>(1024, std::min<uint64_t>(kStageRows, (256ull << 20) / (idx->dim * 4ull))));
+}
 
 static int index_add(vrod_index* idx, const float* rows, uint64_t n, bool synthetic, uint64_t seed,
                      uint64_t first_row) {
@@ -385,7 +393,7 @@ static int index_add(vrod_index* idx, const float* rows, uint64_t n, bool synthe
     // rejected: keep the value it had, so that a rejected add cannot widen (or, with an Inf row,
     // void) the certificate bound of every later search
     HIP_TRY(hipMemcpyAsync(&idx->flags[9], idx->max_xn2_bits, 4, hipMemcpyDeviceToDevice, idx->stream));
-    const uint64_t chunk = std::min<uint64_t>(n, std::max<uint64_t>(1024, std::min<uint64_t>(kStageRows, (256ull << 20) / (idx->dim * 4ull))));
+    const uint64_t chunk = stage_chunk_rows(idx, n);
     VROD_TRY(idx->raw_stage.ensure(chunk * idx->dim * sizeof(float)));
     for (uint64_t done = 0; done < n; done += chunk) {
         const uint64_t m = std::min(chunk, n - done);
@@ -408,6 +416,123 @@ static int index_add(vrod_index* idx, const float* rows, uint64_t n, bool synthe
         (void)hipStreamSynchronize(idx->stream);
         return rc;
     }
+    return VROD_OK;
+}
+
+// ------------------------------------------------------------------ update in place (vrod_index_update)
+// One pass over the n rows of an update, staged in chunks as index_add stages them: upload, prepare into upd_stage.
+//   dst == null: prepare only.  The NaN / Inf check of a call that needs more than one chunk, and of every shard of a
+//                composite handle: every row is checked before any row is written.  Returns what the flag says.
+//   dst != null: row i goes to corpus row dst[i] (kScatterSkip: nowhere), with its xnorm2 entry, the running maximum
+//                and its bf16 planes where they exist (kernels_mutate.hip).  check_first: the call fits one chunk and
+//                has not been checked: the flag is read between the prepare and the scatter.
+// Nothing but the scatter writes to the corpus, xnorm2 or max_xn2_bits, so a rejected update changes none of them.
+static int index_update_pass(vrod_index* idx, const uint32_t* dst, const float* rows, uint64_t n, bool check_first) {
+    VROD_TRY(set_device(idx));
+    const uint64_t chunk = stage_chunk_rows(idx, n);
+    VROD_TRY(idx->raw_stage.ensure(chunk * idx->dim * sizeof(float)));
+    VROD_TRY(idx->upd_stage.ensure(chunk * idx->row_bytes()));
+    VROD_TRY(idx->nrm_ws.ensure(chunk * sizeof(double)));
+    if (dst) VROD_TRY(idx->upd_dst.ensure(chunk * 4));
+    for (uint64_t done = 0; done < n; done += chunk) {
+        const uint64_t m = std::min(chunk, n - done);
+        HIP_TRY(hipMemcpyAsync(idx->raw_stage.p, rows + done * idx->dim, m * idx->dim * sizeof(float), hipMemcpyHostToDevice, idx->stream));
+        launch_prepare_rows(idx->raw_stage.as<float>(), m, idx->dim, idx->ld, prep_form(idx->metric), idx->dtype, idx->nrm_ws.as<double>(),
+                            &idx->flags[0], idx->dtype == VROD_DTYPE_F32 ? idx->upd_stage.as<float>() : nullptr,
+                            idx->dtype == VROD_DTYPE_BF16 ? idx->upd_stage.p : nullptr, idx->stream);
+        HIP_TRY(hipGetLastError());
+        if (!dst) continue;
+        if (check_first) VROD_TRY(check_bad_flag(idx, "rows"));
+        HIP_TRY(hipMemcpyAsync(idx->upd_dst.p, dst + done, m * 4, hipMemcpyHostToDevice, idx->stream));
+        launch_scatter_rows(idx->upd_stage.p, idx->upd_dst.as<uint32_t>(), m, idx->dtype, idx->ld, idx->corpus, idx->xnorm2, idx->max_xn2_bits,
+                            idx->dtype == VROD_DTYPE_F32 ? idx->planes : nullptr, idx->planes_rows, idx->ldp, idx->stream);
+        HIP_TRY(hipGetLastError());
+    }
+    if (!dst) return check_bad_flag(idx, "rows");
+    HIP_TRY(hipStreamSynchronize(idx->stream));
+    return VROD_OK;
+}
+
+// dst: per row of the call its local row, or kScatterSkip for an id that the call names again later
+static int index_update(vrod_index* idx, const std::vector<uint32_t>& dst, const float* rows, uint64_t n) {
+    if (n <= stage_chunk_rows(idx, n)) return index_update_pass(idx, dst.data(), rows, n, true);
+    VROD_TRY(index_update_pass(idx, nullptr, rows, n, false));
+    return index_update_pass(idx, dst.data(), rows, n, false);
+}
+
+static void mask_changed(vrod_index* idx);
+
+// ------------------------------------------------------------------ compaction (vrod_index_compact)
+// The live rows move down in place, chunk by chunk on the handle's stream (compact_plan.h says why that is safe), with
+// their xnorm2 entries; the vacated tail is zeroed again (the scan kernels rely on zero rows past the count), the maximum
+// squared norm is taken afresh over the survivors (= a fresh handle's), the tombstones are cleared and a filter's allowed
+// bits follow their rows.  The bf16 planes of an fp32 handle are not moved: planes_rows = 0 has the next batched search
+// split the compacted rows again, which gives the bits a fresh handle's planes hold.
+// Everything that can fail comes before the first row moves; a HIP error after that leaves the handle unusable.
+static int index_compact(vrod_index* idx, uint64_t* out_new_ids) {
+    const uint64_t count = idx->count;
+    if (!idx->n_deleted) {
+        if (out_new_ids) compact_new_ids(idx->del_bits.data(), count, idx->id_offset, out_new_ids);   // the identity
+        return VROD_OK;
+    }
+    VROD_TRY(set_device(idx));
+    const uint32_t* del = idx->del_bits.data();
+    const size_t words = (size_t)((count + 31) / 32), cap_words = idx->del_bits.size();
+    const size_t rb = idx->row_bytes();
+    const uint64_t chunk_rows = std::max<uint64_t>(32, std::min<uint64_t>(kCompactChunkRows, (256ull << 20) / rb) / 32 * 32);
+    const CompactPlan plan = plan_compact(del, count, chunk_rows);
+    std::vector<uint32_t> base(words);
+    compact_word_bases(del, count, base.data());
+    std::vector<uint32_t> new_allow, new_eff;
+    if (idx->filter_on) {
+        new_allow.resize(cap_words);
+        new_eff.resize(cap_words);
+        compact_bits(del, idx->allow_bits.data(), count, new_allow.data(), cap_words);
+        for (size_t w = 0; w < cap_words; ++w) new_eff[w] = ~new_allow[w];   // nothing is deleted afterwards
+    }
+    uint64_t stage_rows = 0;
+    for (const CompactChunk& c : plan.chunks) if (c.staged) stage_rows = std::max(stage_rows, c.L);
+    if (stage_rows) {
+        VROD_TRY(idx->raw_stage.ensure(stage_rows * rb));
+        VROD_TRY(idx->nrm_ws.ensure(stage_rows * sizeof(float)));
+    }
+    VROD_TRY(idx->compact_ws.ensure(words * 4));
+    HIP_TRY(hipMemcpyAsync(idx->compact_ws.p, base.data(), words * 4, hipMemcpyHostToDevice, idx->stream));
+    HIP_TRY(hipStreamSynchronize(idx->stream));
+
+    // ---- from here on rows move
+    hipStream_t s = idx->stream;
+    char* corpus = (char*)idx->corpus;
+    hipError_t e = hipSuccess;
+    for (const CompactChunk& c : plan.chunks) {
+        if (c.staged) {
+            launch_compact_rows(corpus, idx->xnorm2, idx->del_dev, idx->compact_ws.as<uint32_t>(), c.r0, c.r1, rb, idx->raw_stage.p,
+                                idx->nrm_ws.as<float>(), c.w0, s);
+            e = hipMemcpyAsync(corpus + c.w0 * rb, idx->raw_stage.p, c.L * rb, hipMemcpyDeviceToDevice, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(idx->xnorm2 + c.w0, idx->nrm_ws.p, c.L * sizeof(float), hipMemcpyDeviceToDevice, s);
+        } else {
+            launch_compact_rows(corpus, idx->xnorm2, idx->del_dev, idx->compact_ws.as<uint32_t>(), c.r0, c.r1, rb, corpus, idx->xnorm2, 0, s);
+        }
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e != hipSuccess) break;
+    }
+    if (e == hipSuccess) e = hipMemsetAsync(corpus + plan.live * rb, 0, (count - plan.live) * rb, s);
+    if (e == hipSuccess) e = hipMemsetAsync(idx->xnorm2 + plan.live, 0, (count - plan.live) * sizeof(float), s);
+    if (e == hipSuccess) e = hipMemsetAsync(idx->max_xn2_bits, 0, 4, s);
+    if (e == hipSuccess) { launch_xn2_max(idx->xnorm2, plan.live, idx->max_xn2_bits, s); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemsetAsync(idx->del_dev, 0, cap_words * 4, s);
+    if (e == hipSuccess && idx->filter_on) e = hipMemcpyAsync(idx->eff_dev, new_eff.data(), cap_words * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess)
+        return fail(VROD_ERR_HIP, "vrod_index_compact: %s while rows were moving: the handle is unusable, destroy it", hipGetErrorString(e));
+
+    if (out_new_ids) compact_new_ids(del, count, idx->id_offset, out_new_ids);
+    std::fill(idx->del_bits.begin(), idx->del_bits.end(), 0u);
+    idx->n_deleted = 0;
+    idx->count = plan.live;
+    if (idx->filter_on) { idx->allow_bits.swap(new_allow); idx->eff_bits.swap(new_eff); }   // n_eligible: the same rows
+    idx->planes_rows = 0;
+    mask_changed(idx);
     return VROD_OK;
 }
 
@@ -1525,6 +1650,26 @@ static int composite_delete(vrod_index* idx, const uint64_t* ids, uint64_t n) {
     return VROD_OK;
 }
 
+// An update of a composite handle: each row goes to the shard that holds its id.  Every shard checks its rows (NaN /
+// Inf) before any shard writes one, so a rejected call changes nothing on the handle as a whole.
+// rows_of: per row of the call its global row, skip[i]: the call names that id again later.
+static int composite_update(vrod_index* idx, const std::vector<uint64_t>& rows_of, const std::vector<bool>& skip, const float* rows) {
+    const size_t G = idx->shards.size();
+    std::vector<std::vector<uint32_t>> dst(G);
+    std::vector<std::vector<float>> buf(G);
+    for (size_t i = 0; i < rows_of.size(); ++i) {
+        const uint64_t r = rows_of[i];
+        const size_t g = (size_t)((r / kShardBlock) % G);
+        dst[g].push_back(skip[i] ? kScatterSkip : (uint32_t)local_row_of(idx, r));
+        buf[g].insert(buf[g].end(), rows + i * idx->dim, rows + (i + 1) * idx->dim);
+    }
+    for (size_t g = 0; g < G; ++g)
+        if (!dst[g].empty()) VROD_TRY(index_update_pass(idx->shards[g], nullptr, buf[g].data(), dst[g].size(), false));
+    for (size_t g = 0; g < G; ++g)
+        if (!dst[g].empty()) VROD_TRY(index_update_pass(idx->shards[g], dst[g].data(), buf[g].data(), dst[g].size(), false));
+    return VROD_OK;
+}
+
 static int composite_get_rows(vrod_index* idx, uint64_t first, uint64_t n, float* out_rows) {
     return for_each_piece(idx, first, n, [&](size_t g, uint64_t r, uint64_t m) {
         return vrod_index_get_rows(idx->shards[g], local_row_of(idx, r), m, out_rows + (r - first) * idx->dim);
@@ -2260,7 +2405,8 @@ int vrod_index_destroy(vrod_index* idx) {
     if (idx->stream) (void)hipStreamSynchronize(idx->stream);
     for (Pending& P : idx->slot)
         if (P.stream) (void)hipStreamSynchronize(P.stream);
-    for (DevBuf* b : {&idx->raw_stage, &idx->nrm_ws, &idx->out_ids, &idx->out_scores, &idx->range_pool, &idx->range_pool_b, &idx->range_small}) b->release();
+    for (DevBuf* b : {&idx->raw_stage, &idx->nrm_ws, &idx->out_ids, &idx->out_scores, &idx->range_pool, &idx->range_pool_b, &idx->range_small,
+                      &idx->upd_stage, &idx->upd_dst, &idx->compact_ws}) b->release();
     for (Pending& P : idx->slot) {
         for (DevBuf* b : {&P.q_raw, &P.q_lp, &P.scores, &P.keys_a, &P.keys_b, &P.lists, &P.small, &P.hist, &P.cand_rows, &P.cand_fast, &P.cand_canon})
             b->release();
@@ -2336,6 +2482,46 @@ int vrod_index_delete(vrod_index* idx, const uint64_t* ids, uint64_t n) {
     std::vector<uint64_t> rows(ids, ids + n);
     for (uint64_t& r : rows) r -= idx->id_offset;
     return index_delete_rows(idx, rows);
+}
+
+int vrod_index_update(vrod_index* idx, const uint64_t* ids, const float* rows, uint64_t n) {
+    if (!idx || ((!ids || !rows) && n)) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    VROD_TRY(require_idle(idx, "vrod_index_update"));
+    const size_t G = idx->shards.size();
+    std::vector<uint64_t> rows_of(n);
+    for (uint64_t i = 0; i < n; ++i) {   // the whole call or nothing
+        const uint64_t r = ids[i] - idx->id_offset;
+        bool current = ids[i] >= idx->id_offset && r < idx->count;
+        if (current) {
+            const vrod_index* sh = G ? idx->shards[(size_t)((r / kShardBlock) % G)] : idx;
+            current = !bit_of(sh->del_bits.data(), G ? local_row_of(idx, r) : r);
+        }
+        if (!current)
+            return fail(VROD_ERR_INVALID_ARG, "id %llu is not a current row of this handle (ids %llu..%llu, deleted rows excluded)",
+                        (unsigned long long)ids[i], (unsigned long long)idx->id_offset, (unsigned long long)(idx->id_offset + idx->count));
+        rows_of[i] = r;
+    }
+    if (!n) return VROD_OK;
+    // an id named twice: the last occurrence wins, the earlier ones are prepared and checked but written nowhere
+    std::vector<bool> seen(idx->count, false), skip(n, false);
+    for (uint64_t i = n; i-- > 0;) {
+        if (seen[rows_of[i]]) skip[i] = true;
+        seen[rows_of[i]] = true;
+    }
+    if (G) return composite_update(idx, rows_of, skip, rows);
+    std::vector<uint32_t> dst(n);
+    for (uint64_t i = 0; i < n; ++i) dst[i] = skip[i] ? kScatterSkip : (uint32_t)rows_of[i];
+    return index_update(idx, dst, rows, n);
+}
+
+int vrod_index_compact(vrod_index* idx, uint64_t* out_new_ids, uint64_t map_len) {
+    if (!idx) return fail(VROD_ERR_INVALID_ARG, "idx is null");
+    VROD_TRY(require_idle(idx, "vrod_index_compact"));
+    if (idx->composite())
+        return fail(VROD_ERR_UNSUPPORTED, "vrod_index_compact on a multi-device handle: renumbering would re-deal the rows across the devices");
+    if (out_new_ids && map_len != idx->count)
+        return fail(VROD_ERR_INVALID_ARG, "an id map of %llu entries for a handle of %llu rows", (unsigned long long)map_len, (unsigned long long)idx->count);
+    return index_compact(idx, out_new_ids);
 }
 
 int vrod_index_live_count(const vrod_index* idx, uint64_t* out) {

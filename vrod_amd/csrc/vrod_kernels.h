@@ -58,6 +58,19 @@ void launch_row_fastnorm(const void* d_rows, int dtype, uint64_t n, uint32_t ld,
 void launch_rows_get(const void* d_rows, int dtype, uint64_t n, uint32_t dim, uint32_t ld,
                      float* d_out, hipStream_t s);
 
+// ---- kernels_mutate.hip : vrod_index_update / vrod_index_compact
+// Update: prepared row i of d_staged becomes corpus row d_dst[i] (kScatterSkip: left out), with its xnorm2 entry, the
+// running maximum and -- fp32 handles, rows below planes_rows of non-null d_planes -- its bf16 [hi | lo] planes.
+constexpr uint32_t kScatterSkip = 0xFFFFFFFFu;
+void launch_scatter_rows(const void* d_staged, const uint32_t* d_dst, uint64_t n, int dtype, uint32_t ld, void* d_corpus,
+                         float* d_xn2, uint32_t* d_max_bits, void* d_planes, uint64_t planes_rows, uint32_t ldp, hipStream_t s);
+// Compact: the live rows of [r0, r1) (r0 % 32 == 0; d_del: the deleted-row bitmap; d_word_base: compact_plan.h
+// compact_word_bases) move to d_out_rows / d_out_xn2 at their destination minus out_base.
+void launch_compact_rows(const void* d_rows, const float* d_xn2, const uint32_t* d_del, const uint32_t* d_word_base, uint64_t r0,
+                         uint64_t r1, size_t row_bytes, void* d_out_rows, float* d_out_xn2, uint64_t out_base, hipStream_t s);
+// *d_max_bits (cleared by the caller) = max of d_xn2[0, n) as float bits
+void launch_xn2_max(const float* d_xn2, uint64_t n, uint32_t* d_max_bits, hipStream_t s);
+
 // ---- kernels_stream.hip : Q <= 8 HBM-bound scan, writes fast scores [nq_pad][score_ld]
 // nq_pad in {1,2,4,8}; d_q is [nq_pad][ld] prepared fp32 (zero rows for padding).
 // Also accumulates, per query, a histogram of the top stream_hist_bits(nq_pad) bits of the

@@ -86,8 +86,9 @@ class Index:
         check(self._L.vrod_index_count(self._h, C.byref(out)))
         return out.value
 
-    def delete(self, ids):
-        """Delete rows by the ids searches report (vrod_index_delete): any integer array-like, all or nothing."""
+    @staticmethod
+    def _ids(ids) -> np.ndarray:
+        """Any integer array-like -> a contiguous uint64 vector."""
         a = np.asarray(ids)
         if a.size and a.dtype.kind not in "iu" and not isinstance(ids, np.ndarray):
             # a sequence of Python ints that numpy could not give one integer dtype (e.g. 1 and 2**63 together)
@@ -96,8 +97,31 @@ class Index:
                 a = np.array([int(x) for x in flat], dtype=np.uint64)
         if a.size and a.dtype.kind not in "iu":
             raise TypeError(f"ids must be integers, got {a.dtype}")
-        a = np.ascontiguousarray(a.astype(np.uint64, copy=False).reshape(-1))
+        return np.ascontiguousarray(a.astype(np.uint64, copy=False).reshape(-1))
+
+    def delete(self, ids):
+        """Delete rows by the ids searches report (vrod_index_delete): any integer array-like, all or nothing."""
+        a = self._ids(ids)
         check(self._L.vrod_index_delete(self._h, a.ctypes.data_as(C.c_void_p), a.size))
+
+    def update(self, ids, rows: np.ndarray):
+        """Give row ids[i] the vector rows[i] in place (vrod_index_update): the row keeps its id, the vector is prepared
+        as add() prepares it.  All or nothing; an id named twice takes the last vector."""
+        a = self._ids(ids)
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        if rows.ndim == 1 and a.size == 1:
+            rows = rows[None, :]
+        if rows.ndim != 2 or rows.shape[1] != self.dim or rows.shape[0] != a.size:
+            raise ValueError(f"rows must be [{a.size}, {self.dim}]")
+        check(self._L.vrod_index_update(self._h, a.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p), a.size))
+
+    def compact(self) -> np.ndarray:
+        """Physically remove the deleted rows and renumber the survivors densely (vrod_index_compact).  Returns the
+        new-id map, a uint64 array over the old rows: entry i is the new id of old id offset + i, or ID_NONE."""
+        n = self.count
+        new_ids = np.empty(n, dtype=np.uint64)
+        check(self._L.vrod_index_compact(self._h, new_ids.ctypes.data_as(C.c_void_p), n))
+        return new_ids
 
     def live_count(self) -> int:
         """Rows added minus rows deleted."""
