@@ -101,6 +101,13 @@ extern "C" {
     pub fn vrod_range_search_device(idx: *mut vrod_index, d_queries: *const f32, nq: u32, d_thresholds: *const f32,
                                     capacity: u64, d_out_lims: *mut u64, d_out_ids: *mut u64,
                                     d_out_scores: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn vrod_index_set_labels(idx: *mut vrod_index, first_id: u64, labels: *const u32, n: u64) -> c_int;
+    pub fn vrod_index_get_labels(idx: *mut vrod_index, first_id: u64, n: u64, out_labels: *mut u32) -> c_int;
+    pub fn vrod_search_labeled(idx: *mut vrod_index, queries: *const f32, nq: u32, k: u32, query_labels: *const u32,
+                               out_ids: *mut u64, out_scores: *mut f32) -> c_int;
+    pub fn vrod_search_labeled_device(idx: *mut vrod_index, d_queries: *const f32, nq: u32, k: u32,
+                                      d_query_labels: *const u32, d_out_ids: *mut u64, d_out_scores: *mut f32,
+                                      stream: *mut c_void) -> c_int;
 }
 
 /// Joins the reference's `thiserror` enums (`src/main.rs:36-40`, `src/command/builder.rs:10-15`).
@@ -239,6 +246,38 @@ impl Collection {
         let mut scores = vec![0f32; queries.len() * k];
         check(unsafe {
             vrod_search(self.idx, flat.as_ptr(), queries.len() as u32, k as u32, ids.as_mut_ptr(), scores.as_mut_ptr())
+        })?;
+        Ok((ids, scores))
+    }
+}
+
+impl Collection {
+    /// Give the rows with ids `first_id..first_id + labels.len()` their labels (every row carries 0 until set).
+    pub fn set_labels(&mut self, first_id: u64, labels: &[u32]) -> Result<(), ScanError> {
+        check(unsafe { vrod_index_set_labels(self.idx, first_id, labels.as_ptr(), labels.len() as u64) })
+    }
+
+    pub fn labels(&self, first_id: u64, n: usize) -> Result<Vec<u32>, ScanError> {
+        let mut out = vec![0u32; n];
+        check(unsafe { vrod_index_get_labels(self.idx, first_id, n as u64, out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+
+    /// `search` with a label per query: query `q` sees only the live, allowed rows labelled `labels[q]`.
+    pub fn search_labeled(&self, queries: &[Vec<f32>], k: usize, labels: &[u32]) -> Result<(Vec<u64>, Vec<f32>), ScanError> {
+        for q in queries {
+            if q.len() != self.dim {
+                return Err(ScanError::Dim { got: q.len(), want: self.dim });
+            }
+        }
+        if labels.len() != queries.len() {
+            return Err(ScanError::Dim { got: labels.len(), want: queries.len() });
+        }
+        let flat: Vec<f32> = queries.iter().flatten().copied().collect();
+        let mut ids = vec![0u64; queries.len() * k];
+        let mut scores = vec![0f32; queries.len() * k];
+        check(unsafe {
+            vrod_search_labeled(self.idx, flat.as_ptr(), queries.len() as u32, k as u32, labels.as_ptr(), ids.as_mut_ptr(), scores.as_mut_ptr())
         })?;
         Ok((ids, scores))
     }

@@ -185,6 +185,17 @@ int vrod_index_live_count(const vrod_index *idx, uint64_t *out);
 int vrod_index_set_filter(vrod_index *idx, const uint32_t *allow_words, uint64_t n_rows);
 /* Rows the next search may return: live and allowed (= vrod_index_live_count without a filter). */
 int vrod_index_filter_count(const vrod_index *idx, uint64_t *out);
+/* Row labels: every row carries one uint32_t label -- 0 until set, and 0 for rows added later -- that only
+ * vrod_search_labeled reads (vrod_search, vrod_range_search and the pipelined forms ignore labels entirely).  set_labels
+ * gives the rows with ids [first_id, first_id + n) (ids as searches report them, id_offset applied; deleted rows may be
+ * named) the labels labels[0 .. n) (host memory); a range that is not wholly within the current rows fails with
+ * VROD_ERR_INVALID_ARG and changes nothing; n == 0 does nothing.  vrod_index_update keeps a row's label,
+ * vrod_index_delete leaves labels alone, vrod_index_compact moves them with their rows.  get_labels reads them back
+ * (host memory).  Labels cost nothing until first set: the device array is allocated by the first set_labels.  While a
+ * search is pending: VROD_ERR_INVALID_ARG.  Multi-device handles: set_labels returns VROD_ERR_UNSUPPORTED and changes
+ * nothing (get_labels reports the zeros every row carries). */
+int vrod_index_set_labels(vrod_index *idx, uint64_t first_id, const uint32_t *labels, uint64_t n);
+int vrod_index_get_labels(vrod_index *idx, uint64_t first_id, uint64_t n, uint32_t *out_labels);
 /* Copy prepared rows [first, first+n) back as fp32 (bf16 widened): n x dim. */
 int vrod_index_get_rows(vrod_index *idx, uint64_t first, uint64_t n, float *out_rows);
 
@@ -242,6 +253,27 @@ int vrod_range_search(vrod_index *idx, const float *queries, uint32_t nq, const 
 int vrod_range_search_device(vrod_index *idx, const float *d_queries, uint32_t nq, const float *d_thresholds,
                              uint64_t capacity, uint64_t *d_out_lims, uint64_t *d_out_ids, float *d_out_scores,
                              void *stream);
+
+/* Labelled search -- one batch, a label per query (mixed-tenant batches): query q sees the rows that are live, allowed
+ * by the handle's filter if one is set, and labelled query_labels[q] (nq words, host memory; the _device form: device
+ * memory).  Its result row is bit for bit (ids and score bits, a NaN matching any NaN) what vrod_search returns for that
+ * query on a fresh handle that holds only those rows, in order, with the ids mapped back: ties break by smaller id, slots
+ * beyond the matching rows are (VROD_ID_NONE, NaN), a label no row carries gives a row of those.  A handle whose labels
+ * were never set holds label 0 in every row.  k, null pointers and NaN / Inf in the queries are handled as vrod_search
+ * handles them.  Synchronous, like a range search: no _begin_ form, no graph replay; VROD_ERR_INVALID_ARG while a search
+ * is pending; the _device form returns after the results are complete in device memory.  The rows are grouped by the
+ * batch's labels on the device, in one pass over the label array; a label with few rows has the canonical scores of its
+ * own rows computed (all such labels of the batch in one launch), a label with a large share of the rows takes the
+ * ordinary scan with the other labels masked (vrod_index_set_path: GATHER sends every label the first way, STREAM /
+ * MFMA / EXACT the second).  vrod_index_last_stats afterwards: path = VROD_PATH_GATHER if no label took a scan, else the
+ * path of the last scan; kprime, max_fast_err, eps_bound = maxima over the scans (0 without one); scan_launches,
+ * fallback_queries, band_queries = sums; scan_bytes / scan_flops = the rows (x the queries) of each label scored on its
+ * own, plus every stored row per scan.  Multi-device handles: VROD_ERR_UNSUPPORTED. */
+int vrod_search_labeled(vrod_index *idx, const float *queries, uint32_t nq, uint32_t k,
+                        const uint32_t *query_labels, uint64_t *out_ids, float *out_scores);
+int vrod_search_labeled_device(vrod_index *idx, const float *d_queries, uint32_t nq, uint32_t k,
+                               const uint32_t *d_query_labels, uint64_t *d_out_ids, float *d_out_scores,
+                               void *stream);
 
 /* Merge n_lists per-shard results (device, each nq x k, list-major: [list][q][k]) into
  * one nq x k on `device` -- the step after the RCCL all-gather. */

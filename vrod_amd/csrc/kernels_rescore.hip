@@ -73,28 +73,19 @@ __device__ __forceinline__ float sub_rn_s(float s, float b) {
 }
 
 //
-// LIST (the gather path of a filtered search, rescore_list): the same chains over the rows a list names -- column c is
-// row list[c], c < nrows -- for a whole block of `nq_list` consecutive queries of `q`.  Block b takes query group
-// b % n_qgroups (NQ queries; a short last group repeats its last query and writes only its own) and list tile
-// b / n_qgroups, so that the blocks in flight together share their 64 rows through L2.
+// One body serves three kernels.  The block's 64 rows are rows [row0, row0 + 64) of `nrows` -- of the corpus, or
+// (LIST) of the ascending row list `list` -- and its NQ chains are the queries qs.qi[0..NQ) of `q`; chain n < n_write
+// goes to out[n * out_ld + row0 + lane].  `tile` is the block's [64][kTileStride] LDS staging tile.
 template <typename T, int METRIC, int NQ, bool LIST>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void rescore_all_kernel(const T* __restrict__ corpus, uint32_t dim, uint32_t ld,
-                                                         const float* __restrict__ q, RescoreQuerySet qs,
-                                                         uint64_t nrows, float* __restrict__ out, uint64_t out_ld,
-                                                         const uint32_t* __restrict__ list, uint32_t nq_list, uint32_t n_qgroups) {
+__device__ __forceinline__ void rescore_all_body(const T* __restrict__ corpus, uint32_t dim, uint32_t ld, const float* __restrict__ q,
+                                                 const RescoreQuerySet& qs, uint64_t nrows, uint64_t row0, float* __restrict__ out,
+                                                 uint64_t out_ld, const uint32_t* __restrict__ list, int n_write, float* tile) {
     constexpr int EPU = 16 / (int)sizeof(T);
     constexpr int LPC = 64 / EPU;
     constexpr int RPI = 64 / LPC;
     constexpr int NI = 64 / RPI;
-    __shared__ __attribute__((aligned(16))) float tile[64 * kTileStride];
     const int lane = threadIdx.x;
-    const uint32_t qg = LIST ? blockIdx.x % n_qgroups : 0u;
-    const uint64_t row0 = (uint64_t)(LIST ? blockIdx.x / n_qgroups : blockIdx.x) * 64;
     const uint64_t slot = row0 + lane;
-    if constexpr (LIST) {
-#pragma unroll
-        for (int n = 0; n < NQ; ++n) qs.qi[n] = qg * NQ + n < nq_list ? qg * NQ + n : nq_list - 1;
-    }
     const bool valid = slot < nrows;
     const int nvalid = nrows - row0 < 64 ? (int)(nrows - row0) : 64;   // rows are a prefix of the wave
     const int ni_used = (nvalid + RPI - 1) / RPI;
@@ -184,13 +175,62 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
     }
     if (valid) {
 #pragma unroll
-        for (int n = 0; n < NQ; ++n) {
-            if constexpr (LIST) {
-                if (qg * NQ + n < nq_list) out[(uint64_t)(qg * NQ + n) * out_ld + slot] = acc[n];
-            } else {
-                out[(uint64_t)n * out_ld + slot] = acc[n];
-            }
-        }
+        for (int n = 0; n < NQ; ++n)
+            if (n < n_write) out[(uint64_t)n * out_ld + slot] = acc[n];
+    }
+}
+
+// Exact path (LIST false): block b takes corpus rows [64 b, 64 b + 64) and the NQ queries of `qs`.
+// LIST (the gather path of a filtered search, rescore_list): the same chains over the rows a list names -- column c is
+// row list[c], c < nrows -- for a whole block of `nq_list` consecutive queries of `q`.  Block b takes query group
+// b % n_qgroups (NQ queries; a short last group repeats its last query and writes only its own) and list tile
+// b / n_qgroups, so that the blocks in flight together share their 64 rows through L2.
+template <typename T, int METRIC, int NQ, bool LIST>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void rescore_all_kernel(const T* __restrict__ corpus, uint32_t dim, uint32_t ld,
+                                                         const float* __restrict__ q, RescoreQuerySet qs,
+                                                         uint64_t nrows, float* __restrict__ out, uint64_t out_ld,
+                                                         const uint32_t* __restrict__ list, uint32_t nq_list, uint32_t n_qgroups) {
+    __shared__ __attribute__((aligned(16))) float tile[64 * kTileStride];
+    const uint32_t qg = LIST ? blockIdx.x % n_qgroups : 0u;
+    const uint64_t row0 = (uint64_t)(LIST ? blockIdx.x / n_qgroups : blockIdx.x) * 64;
+    int n_write = NQ;
+    if constexpr (LIST) {
+#pragma unroll
+        for (int n = 0; n < NQ; ++n) qs.qi[n] = qg * NQ + n < nq_list ? qg * NQ + n : nq_list - 1;
+        n_write = (int)(nq_list - qg * NQ < (uint32_t)NQ ? nq_list - qg * NQ : (uint32_t)NQ);
+        out += (uint64_t)qg * NQ * out_ld;
+    }
+    rescore_all_body<T, METRIC, NQ, LIST>(corpus, dim, ld, q, qs, nrows, row0, out, out_ld, list, n_write, tile);
+}
+
+// SEGMENTED (a labelled search, label_plan.h): one launch scores many (label, queries) groups, each over its own
+// segment of one row-list buffer.  Block b finds its entry of the work table (seg_lookup: a binary search over the
+// entries' first blocks, uniform across the wave), then takes one subgroup of the entry's queries -- `nqc` of them per
+// lane, the entry's class -- and one 64-row tile of its segment; consecutive blocks are the subgroups of one tile, so the
+// blocks in flight together share its rows through L2.  Query n of a subgroup is prepared row slot_q[slot] of `q`; a
+// short last subgroup repeats its last query and writes only its own.  out[(slot - slot_first) * out_ld + column].
+template <typename T, int METRIC>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void rescore_segments_kernel(
+    const T* __restrict__ corpus, uint32_t dim, uint32_t ld, const float* __restrict__ q, const SegEntry* __restrict__ entries,
+    uint32_t n_entries, const uint32_t* __restrict__ slot_q, uint32_t slot_first, const uint32_t* __restrict__ lists,
+    float* __restrict__ out, uint64_t out_ld) {
+    __shared__ __attribute__((aligned(16))) float tile[64 * kTileStride];
+    const SegBlock w = seg_lookup(entries, n_entries, blockIdx.x);
+    const SegEntry e = entries[w.entry];
+    const uint32_t s0 = e.slot0 + w.sub * e.nqc;               // first slot of the subgroup
+    const uint32_t left = e.nq - w.sub * e.nqc;                 // its queries (>= 1), capped by the class below
+    RescoreQuerySet qs;
+#pragma unroll
+    for (uint32_t n = 0; n < 8; ++n) qs.qi[n] = slot_q[s0 + (n < left ? n : left - 1)];
+    const uint32_t* list = lists + e.list_base;
+    float* o = out + (uint64_t)(s0 - slot_first) * out_ld;
+    const uint64_t row0 = (uint64_t)w.tile * 64;
+    const int n_write = (int)(left < e.nqc ? left : e.nqc);
+    switch (e.nqc) {
+        case 1: rescore_all_body<T, METRIC, 1, true>(corpus, dim, ld, q, qs, e.m, row0, o, out_ld, list, n_write, tile); break;
+        case 2: rescore_all_body<T, METRIC, 2, true>(corpus, dim, ld, q, qs, e.m, row0, o, out_ld, list, n_write, tile); break;
+        case 4: rescore_all_body<T, METRIC, 4, true>(corpus, dim, ld, q, qs, e.m, row0, o, out_ld, list, n_write, tile); break;
+        default: rescore_all_body<T, METRIC, 8, true>(corpus, dim, ld, q, qs, e.m, row0, o, out_ld, list, n_write, tile); break;
     }
 }
 
@@ -254,6 +294,16 @@ void launch_rescore_list(const void* d_corpus, int dtype, int metric, uint32_t d
     else { if (metric == M_COSINE) { VROD_RL_N(float, M_COSINE) } else { VROD_RL_N(float, M_L2) } }
 #undef VROD_RL_N
 #undef VROD_RL
+}
+
+void launch_rescore_segments(const void* d_corpus, int dtype, int metric, uint32_t dim, uint32_t ld, const float* d_q,
+                             const SegEntry* d_entries, uint32_t n_entries, uint32_t n_blocks, const uint32_t* d_slot_q, uint32_t slot_first,
+                             const uint32_t* d_lists, float* d_out, uint64_t out_ld, hipStream_t s) {
+    if (!n_entries || !n_blocks) return;
+#define VROD_RG(TT, MM) rescore_segments_kernel<TT, MM><<<n_blocks, 64, 0, s>>>((const TT*)d_corpus, dim, ld, d_q, d_entries, n_entries, d_slot_q, slot_first, d_lists, d_out, out_ld)
+    if (dtype == DT_BF16) { if (metric == M_COSINE) VROD_RG(bf16_t, M_COSINE); else VROD_RG(bf16_t, M_L2); }
+    else { if (metric == M_COSINE) VROD_RG(float, M_COSINE); else VROD_RG(float, M_L2); }
+#undef VROD_RG
 }
 
 }  // namespace vrod

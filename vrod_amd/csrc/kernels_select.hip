@@ -94,13 +94,17 @@ __device__ __forceinline__ uint32_t pow2_ceil(uint32_t n) {
 // FROM_SCORES: element i is (score[q][i], row i).  Else: element i is key[q][i].
 // Writes the chunk's best `kp` keys (descending, zero-padded) to out[q][c*kp ...].
 // FROM_SCORES with row_mask: a row whose bit is set is absent (key 0, the padding key).
+// FROM_SCORES with len (a labelled search's segments): query q has len[q] <= n elements, the columns beyond are padding
+// and never become keys.
 template <int METRIC, bool FROM_SCORES>
 __global__ __launch_bounds__(kSortThreads) void select_chunk_kernel(
     const float* __restrict__ scores, const uint64_t* __restrict__ keys_in, uint64_t in_ld,
-    uint64_t n, uint32_t kp, uint64_t* __restrict__ out, uint64_t out_ld, const uint32_t* __restrict__ row_mask) {
+    uint64_t n, uint32_t kp, uint64_t* __restrict__ out, uint64_t out_ld, const uint32_t* __restrict__ row_mask,
+    const uint32_t* __restrict__ len) {
     extern __shared__ __attribute__((aligned(16))) uint64_t skeys[];
     const uint32_t q = blockIdx.y;
     const uint64_t c0 = (uint64_t)blockIdx.x * kSelectChunk;
+    if (FROM_SCORES && len) n = len[q] > c0 ? len[q] : c0;   // (a chunk beyond the query's own length: no element)
     const uint32_t cnt = (uint32_t)(n - c0 < kSelectChunk ? n - c0 : kSelectChunk);
     const uint32_t np2 = pow2_ceil(cnt < 2 ? 2 : cnt);
     for (uint32_t i = threadIdx.x; i < np2; i += kSortThreads) {
@@ -130,14 +134,14 @@ static inline size_t sort_lds_bytes(uint64_t n) {
 
 uint64_t launch_select_from_scores(const float* d_scores, uint64_t score_ld, uint64_t n, int nq,
                                    int metric, uint32_t kp, uint64_t* d_out, uint64_t out_ld,
-                                   const uint32_t* d_row_mask, hipStream_t s) {
+                                   const uint32_t* d_row_mask, hipStream_t s, const uint32_t* d_len) {
     const uint64_t nchunks = (n + kSelectChunk - 1) / kSelectChunk;
     dim3 grid((unsigned)nchunks, nq);
     const size_t lds = sort_lds_bytes(n);
     if (metric == M_COSINE)
-        select_chunk_kernel<M_COSINE, true><<<grid, kSortThreads, lds, s>>>(d_scores, nullptr, score_ld, n, kp, d_out, out_ld, d_row_mask);
+        select_chunk_kernel<M_COSINE, true><<<grid, kSortThreads, lds, s>>>(d_scores, nullptr, score_ld, n, kp, d_out, out_ld, d_row_mask, d_len);
     else
-        select_chunk_kernel<M_L2, true><<<grid, kSortThreads, lds, s>>>(d_scores, nullptr, score_ld, n, kp, d_out, out_ld, d_row_mask);
+        select_chunk_kernel<M_L2, true><<<grid, kSortThreads, lds, s>>>(d_scores, nullptr, score_ld, n, kp, d_out, out_ld, d_row_mask, d_len);
     return nchunks * kp;
 }
 
@@ -145,7 +149,7 @@ uint64_t launch_select_from_keys(const uint64_t* d_in, uint64_t in_ld, uint64_t 
                                  uint32_t kp, uint64_t* d_out, uint64_t out_ld, hipStream_t s) {
     const uint64_t nchunks = (n + kSelectChunk - 1) / kSelectChunk;
     dim3 grid((unsigned)nchunks, nq);
-    select_chunk_kernel<M_COSINE, false><<<grid, kSortThreads, sort_lds_bytes(n), s>>>(nullptr, d_in, in_ld, n, kp, d_out, out_ld, nullptr);
+    select_chunk_kernel<M_COSINE, false><<<grid, kSortThreads, sort_lds_bytes(n), s>>>(nullptr, d_in, in_ld, n, kp, d_out, out_ld, nullptr, nullptr);
     return nchunks * kp;
 }
 
@@ -730,6 +734,35 @@ void launch_list_keys_to_output(const uint64_t* d_keys, uint64_t key_ld, uint64_
     if (nq <= 0) return;
     list_keys_to_output_kernel<<<nq, kSortThreads, sort_lds_bytes(n), s>>>(d_keys, key_ld, (uint32_t)n, metric, k, d_list, idmap,
                                                                             d_out_ids, d_out_scores);
+}
+
+// Labelled search: the keys of the queries in score slots [0, ns) name columns of each slot's OWN segment of the list
+// buffer: column c of slot s is row lists[seg_base[s] + c], and the slot's output row is query slot_q[s] of the batch.
+__global__ __launch_bounds__(kSortThreads) void seg_keys_to_output_kernel(
+    const uint64_t* __restrict__ keys, uint64_t key_ld, uint32_t n, int metric, uint32_t k, const uint32_t* __restrict__ lists,
+    const uint32_t* __restrict__ seg_base, const uint32_t* __restrict__ slot_q, IdMap idmap, uint64_t* __restrict__ out_ids,
+    float* __restrict__ out_scores) {
+    extern __shared__ __attribute__((aligned(16))) uint64_t skeys[];
+    const uint32_t sl = blockIdx.x;
+    const uint32_t np2 = pow2_ceil(n < 2 ? 2 : n);
+    for (uint32_t i = threadIdx.x; i < np2; i += kSortThreads) skeys[i] = i < n ? keys[(uint64_t)sl * key_ld + i] : 0ull;
+    __syncthreads();
+    bitonic_sort_desc(skeys, np2);
+    const uint32_t* list = lists + seg_base[sl];
+    const uint64_t q = slot_q[sl];
+    for (uint32_t i = threadIdx.x; i < k; i += kSortThreads) {
+        const uint64_t key = i < np2 ? skeys[i] : 0ull;
+        out_ids[q * k + i] = key ? idmap(list[key_row(key)]) : UINT64_MAX;
+        out_scores[q * k + i] = key ? key_to_score_rt(key_skey(key), metric) : __uint_as_float(kScoreNoneBits);
+    }
+}
+
+void launch_seg_keys_to_output(const uint64_t* d_keys, uint64_t key_ld, uint64_t n, int ns, int metric, uint32_t k,
+                               const uint32_t* d_lists, const uint32_t* d_seg_base, const uint32_t* d_slot_q, const IdMap& idmap,
+                               uint64_t* d_out_ids, float* d_out_scores, hipStream_t s) {
+    if (ns <= 0) return;
+    seg_keys_to_output_kernel<<<ns, kSortThreads, sort_lds_bytes(n), s>>>(d_keys, key_ld, (uint32_t)n, metric, k, d_lists, d_seg_base,
+                                                                           d_slot_q, idmap, d_out_ids, d_out_scores);
 }
 
 // ------------------------------------------------------------------ shard merge (after the all-gather)

@@ -1,0 +1,115 @@
+// label_plan.h -- the host decisions of a labelled search (vrod_search_labeled): the batch's queries grouped by their
+// label, and the work table of the segmented score launch.  Plain arithmetic, no HIP headers (search_plan.h,
+// compact_plan.h): vrod_index.hip enqueues what these functions decide, tests/test_label_plan.py compiles this header as
+// host C++.  seg_lookup is the one function the score kernel shares with the host (kernels_rescore.hip).
+#pragma once
+#include <stdint.h>
+
+#include <algorithm>
+#include <vector>
+
+#if defined(__HIPCC__)
+#define VROD_LABEL_HD __host__ __device__
+#else
+#define VROD_LABEL_HD
+#endif
+
+namespace vrod {
+
+// Distinct labels one grouping pass serves (kernels_label.hip keeps the sorted table and one counter per label in LDS);
+// a batch with more is served in passes of this many groups.
+constexpr uint32_t kLabelGroupsPerPass = 4096;
+// A group's entry in the offsets the scatter pass gets: this group needs no row list (it takes the dense route).
+constexpr uint32_t kNoSegment = 0xFFFFFFFFu;
+
+// ------------------------------------------------------------------ grouping
+// The batch's distinct labels in ascending order, and per label its queries in ascending order: group g is
+// q_order[q_off[g] .. q_off[g + 1]).
+struct LabelGroups {
+    std::vector<uint32_t> labels;    // [G]
+    std::vector<uint32_t> q_off;     // [G + 1]
+    std::vector<uint32_t> q_order;   // [nq]
+    uint32_t size() const { return (uint32_t)labels.size(); }
+    uint32_t nq_of(uint32_t g) const { return q_off[g + 1] - q_off[g]; }
+};
+inline LabelGroups label_groups(const uint32_t* query_labels, uint32_t nq) {
+    LabelGroups G;
+    G.q_order.resize(nq);
+    for (uint32_t i = 0; i < nq; ++i) G.q_order[i] = i;
+    std::stable_sort(G.q_order.begin(), G.q_order.end(), [&](uint32_t a, uint32_t b) { return query_labels[a] < query_labels[b]; });
+    for (uint32_t i = 0; i < nq; ++i) {
+        const uint32_t l = query_labels[G.q_order[i]];
+        if (G.labels.empty() || G.labels.back() != l) { G.labels.push_back(l); G.q_off.push_back(i); }
+    }
+    G.q_off.push_back(nq);
+    return G;
+}
+
+// Rows per block of the grouping pass over N rows: whole 64-row waves, about 2048 blocks on a large corpus (each block's
+// per-group counts are one row of the [blocks][groups] matrix the prefix pass walks).
+inline uint32_t label_rows_per_block(uint64_t N) {
+    return (uint32_t)std::max<uint64_t>(256, ((N + 2047) / 2048 + 63) / 64 * 64);
+}
+
+// ------------------------------------------------------------------ the segmented score launch
+// A segmented group: `nq` queries, in score slots [slot0, slot0 + nq), over the `m` rows of its segment of the list
+// buffer.  Slots number the queries of the segmented groups only, group after group.
+struct SegGroup { uint32_t list_base, m, slot0, nq; };
+// Queries per lane a group's blocks take (the NQ of rescore_all_body): 8 once the group has 5, so that a group's last
+// subgroup never needs a second kernel form.
+VROD_LABEL_HD inline uint32_t seg_query_class(uint32_t nq) { return nq >= 5 ? 8u : nq >= 3 ? 4u : nq; }
+// One entry of the device work table: blocks [block0, block0 + tiles * subgroups) of the launch, block0 + t * subgroups
+// + s = (tile t, subgroup s) -- the subgroups of one tile are neighbours.  Entries have m > 0 and ascending block0.
+struct SegEntry { uint32_t block0, list_base, m, slot0, nq, nqc; };
+VROD_LABEL_HD inline uint32_t seg_subgroups(const SegEntry& e) { return (e.nq + e.nqc - 1) / e.nqc; }
+VROD_LABEL_HD inline uint32_t seg_tiles(const SegEntry& e) { return (e.m + 63) / 64; }
+struct SegBlock { uint32_t entry, sub, tile; };
+VROD_LABEL_HD inline SegBlock seg_lookup(const SegEntry* e, uint32_t n, uint32_t b) {
+    uint32_t lo = 0, hi = n;   // the last entry with block0 <= b
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) / 2;
+        if (e[mid].block0 <= b) lo = mid; else hi = mid;
+    }
+    const uint32_t local = b - e[lo].block0, ns = seg_subgroups(e[lo]);
+    return {lo, local % ns, local / ns};
+}
+// One launch: entries [e0, e1) of the table (block0 relative to the launch), the slots [slot0, slot0 + n_slots) whose
+// scores it writes, as [n_slots][out_ld] with out_ld = the longest segment rounded up to 64 columns.
+struct SegChunk { uint32_t e0, e1, slot0, n_slots, n_blocks, max_m; };
+struct SegPlan {
+    std::vector<SegEntry> entries;
+    std::vector<SegChunk> chunks;
+};
+// Chunks of whole entries whose score block stays under `max_bytes` (the 1 GiB rule of the gather and exact paths); a
+// group whose own block would not fit is cut into entries of a multiple of 8 queries (8 at the least).  Every slot
+// belongs to exactly one chunk, groups with m == 0 included: they have no entry and no block, their queries' rows of
+// the score block are never read (the select's per-query length is 0).
+inline SegPlan plan_segments(const std::vector<SegGroup>& groups, uint64_t max_bytes = 1ull << 30) {
+    SegPlan P;
+    SegChunk c{0, 0, 0, 0, 0, 0};
+    auto bytes = [](uint64_t slots, uint64_t m) { return slots * ((std::max<uint64_t>(m, 1) + 63) / 64 * 64) * 4; };
+    auto close = [&] {
+        c.e1 = (uint32_t)P.entries.size();
+        if (c.n_slots) P.chunks.push_back(c);
+        c = SegChunk{c.e1, c.e1, c.slot0 + c.n_slots, 0, 0, 0};
+    };
+    for (const SegGroup& g : groups) {
+        const uint64_t fit = max_bytes / bytes(1, g.m);
+        const uint32_t piece = (uint32_t)std::min<uint64_t>(g.nq, std::max<uint64_t>(8, fit / 8 * 8));
+        for (uint32_t q0 = 0; q0 < g.nq; q0 += piece) {
+            const uint32_t nq = std::min(piece, g.nq - q0);
+            if (c.n_slots && bytes(c.n_slots + nq, std::max(c.max_m, g.m)) > max_bytes) close();
+            if (g.m) {
+                SegEntry e{c.n_blocks, g.list_base, g.m, g.slot0 + q0, nq, seg_query_class(nq)};
+                c.n_blocks += seg_tiles(e) * seg_subgroups(e);
+                P.entries.push_back(e);
+            }
+            c.n_slots += nq;
+            c.max_m = std::max(c.max_m, g.m);
+        }
+    }
+    close();
+    return P;
+}
+
+}  // namespace vrod

@@ -33,6 +33,7 @@
 #include "kernels_range.h"
 #include "search_plan.h"
 #include "compact_plan.h"
+#include "label_plan.h"
 
 using namespace vrod;
 
@@ -197,6 +198,21 @@ struct vrod_index {
     DevBuf list_dev;
     uint64_t list_gen = UINT64_MAX, list_n = 0;
 
+    // row labels (vrod_index_set_labels): one word per row of the capacity, 0 until set and for rows at or beyond the
+    // count.  Host mirror and device copy are both allocated at the first set_labels: a handle that never set a label
+    // has neither, and a labelled search on it treats every row as label 0.  No other search reads them.
+    std::vector<uint32_t> lab_bits;    // [capacity] once labels exist
+    uint32_t* lab_dev = nullptr;       // [capacity] on the device, or null
+    // A labelled search's dense groups run the ordinary search flow over ONE label's rows: while mask_ovr is set it
+    // stands for row_mask() and elig_ovr for eligible().  Null outside vrod_search_labeled, so no other call path
+    // changes what it launches.  The override has no host mirror and no generation: what is cached per mask_gen (sample
+    // window, gather list, graphs) is bypassed under it, never refreshed.
+    const uint32_t* mask_ovr = nullptr;
+    uint64_t elig_ovr = 0;
+    // labelled search workspaces: [table | totals | segment offsets], the per-block counts, the row lists, the per-slot
+    // arrays, the work table, a dense group's mask / raw queries / results, the host form's raw queries
+    DevBuf lab_tab, lab_cnt, lab_lists, lab_slots, lab_entries, lab_mask, lab_q, lab_ids, lab_scores, lab_qraw;
+
     // workspaces
     DevBuf raw_stage, nrm_ws, out_ids, out_scores;
     // vrod_index_update: a chunk's prepared rows and their destination rows; vrod_index_compact: live rows below each
@@ -253,10 +269,10 @@ struct vrod_index {
     size_t row_bytes() const { return (size_t)ld * esize; }
     uint64_t live() const { return count - n_deleted; }
     // rows a search may return: live, and allowed while a filter is set
-    uint64_t eligible() const { return filter_on ? n_eligible : live(); }
+    uint64_t eligible() const { return mask_ovr ? elig_ovr : filter_on ? n_eligible : live(); }
     // what the kernels get as their row mask: the effective mask while a filter is set, else the deleted rows, and null
     // while nothing is deleted
-    const uint32_t* row_mask() const { return filter_on ? eff_dev : n_deleted ? del_dev : nullptr; }
+    const uint32_t* row_mask() const { return mask_ovr ? mask_ovr : filter_on ? eff_dev : n_deleted ? del_dev : nullptr; }
     // its host mirror (meaningful while row_mask() is non-null)
     const std::vector<uint32_t>& mask_bits() const { return filter_on ? eff_bits : del_bits; }
 };
@@ -332,9 +348,26 @@ static int index_reserve(vrod_index* idx, uint64_t n_rows) {
             return fail(VROD_ERR_HIP, "growing the filter's row mask failed: %s", hipGetErrorString(fe));
         }
     }
+    uint32_t* nl = nullptr;   // the labels follow the capacity (once they exist): the new rows carry 0
+    if (idx->lab_dev) {
+        hipError_t le = hipMalloc((void**)&nl, want * 4);
+        if (le == hipSuccess) le = hipMemsetAsync(nl, 0, want * 4, idx->stream);
+        if (le == hipSuccess) le = hipMemcpyAsync(nl, idx->lab_bits.data(), idx->count * 4, hipMemcpyHostToDevice, idx->stream);
+        if (le == hipSuccess) le = hipStreamSynchronize(idx->stream);
+        if (le != hipSuccess) {
+            (void)hipStreamSynchronize(idx->stream);
+            if (nl) (void)hipFree(nl);
+            if (ne) (void)hipFree(ne);
+            if (nd) (void)hipFree(nd);
+            (void)hipFree(nc);
+            (void)hipFree(nx);
+            return fail(VROD_ERR_HIP, "growing the row labels failed: %s", hipGetErrorString(le));
+        }
+    }
     if (idx->corpus) (void)hipFree(idx->corpus);
     if (idx->xnorm2) (void)hipFree(idx->xnorm2);
     if (idx->planes) { (void)hipFree(idx->planes); idx->planes = nullptr; idx->planes_cap = idx->planes_rows = 0; }   // rebuilt lazily
+    if (idx->lab_dev) { (void)hipFree(idx->lab_dev); idx->lab_dev = nl; idx->lab_bits.resize(want, 0u); }
     if (idx->del_dev) { (void)hipFree(idx->del_dev); idx->del_dev = nd; }
     idx->del_bits.resize(want / 32, 0u);
     if (idx->filter_on) {
@@ -490,6 +523,13 @@ static int index_compact(vrod_index* idx, uint64_t* out_new_ids) {
         compact_bits(del, idx->allow_bits.data(), count, new_allow.data(), cap_words);
         for (size_t w = 0; w < cap_words; ++w) new_eff[w] = ~new_allow[w];   // nothing is deleted afterwards
     }
+    std::vector<uint32_t> new_lab;   // the labels move with their rows; the vacated tail carries 0 again
+    if (idx->lab_dev) {
+        new_lab.assign(count, 0u);
+        uint64_t j = 0;
+        for (uint64_t r = 0; r < count; ++r)
+            if (!bit_of(del, r)) new_lab[j++] = idx->lab_bits[r];
+    }
     uint64_t stage_rows = 0;
     for (const CompactChunk& c : plan.chunks) if (c.staged) stage_rows = std::max(stage_rows, c.L);
     if (stage_rows) {
@@ -522,6 +562,7 @@ static int index_compact(vrod_index* idx, uint64_t* out_new_ids) {
     if (e == hipSuccess) { launch_xn2_max(idx->xnorm2, plan.live, idx->max_xn2_bits, s); e = hipGetLastError(); }
     if (e == hipSuccess) e = hipMemsetAsync(idx->del_dev, 0, cap_words * 4, s);
     if (e == hipSuccess && idx->filter_on) e = hipMemcpyAsync(idx->eff_dev, new_eff.data(), cap_words * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && idx->lab_dev) e = hipMemcpyAsync(idx->lab_dev, new_lab.data(), count * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess)
         return fail(VROD_ERR_HIP, "vrod_index_compact: %s while rows were moving: the handle is unusable, destroy it", hipGetErrorString(e));
@@ -531,6 +572,7 @@ static int index_compact(vrod_index* idx, uint64_t* out_new_ids) {
     idx->n_deleted = 0;
     idx->count = plan.live;
     if (idx->filter_on) { idx->allow_bits.swap(new_allow); idx->eff_bits.swap(new_eff); }   // n_eligible: the same rows
+    if (idx->lab_dev) std::copy(new_lab.begin(), new_lab.end(), idx->lab_bits.begin());
     idx->planes_rows = 0;
     mask_changed(idx);
     return VROD_OK;
@@ -634,13 +676,15 @@ struct Timer {
 // returns pointer/ld/n of the final key set through out params.
 // (the handle's deleted rows are left out at the first level: they never reach the keys)
 // `mask`: the row mask of the columns (the handle's row_mask() when column = row; null for the gather path's columns)
+// `len` (a labelled search's segments): per query the number of its columns, n the largest of them
 static int select_chain(vrod_index* idx, Pending& P, const float* d_scores, uint64_t score_ld, uint64_t n, int nq,
-                        uint32_t kp, const uint32_t* mask, const uint64_t** out_keys, uint64_t* out_ld, uint64_t* out_n) {
+                        uint32_t kp, const uint32_t* mask, const uint64_t** out_keys, uint64_t* out_ld, uint64_t* out_n,
+                        const uint32_t* len = nullptr) {
     const uint64_t nch0 = (n + kSelectChunk - 1) / kSelectChunk;
     const uint64_t ld_a = nch0 * kp;
     VROD_TRY(P.keys_a.ensure((size_t)nq * ld_a * 8));
     uint64_t cur_n = launch_select_from_scores(d_scores, score_ld, n, nq, score_form(idx->metric), kp, P.keys_a.as<uint64_t>(), ld_a,
-                                               mask, P.stream);
+                                               mask, P.stream, len);
     const uint64_t* cur = P.keys_a.as<uint64_t>();
     uint64_t cur_ld = ld_a;
     bool a_is_cur = true;
@@ -827,6 +871,7 @@ static int stream_pass(vrod_index* idx, Pending& P, Timer& tm, bool in_graph) {
 // first stage has about as few eligible rows to append.)
 static uint64_t sample_window(vrod_index* idx, uint64_t S, uint64_t N) {
     if (!idx->row_mask() || S >= N) return 0;
+    if (idx->mask_ovr) return 0;   // one label's mask (a labelled search): no host mirror to weigh windows by, nothing cached
     vrod_index::SampleWindow& W = idx->sample_win;
     if (W.valid && W.S == S && W.N == N && W.gen == idx->mask_gen) return W.first;
     const uint64_t tiles = N / kRowTile, wt = S / kRowTile;   // S < N is a whole number of tiles (plan_stages)
@@ -1034,7 +1079,7 @@ static int search_enqueue_body(vrod_index* idx, Pending& P, const float* d_queri
     const uint64_t N = idx->count;
     const int form = score_form(idx->metric);
     // the gather path: forced, or AUTO over a filter narrow enough (search_plan.h filter_route)
-    const bool gather = idx->path == VROD_PATH_GATHER || (idx->filter_on && filter_route(idx->path, idx->dtype, N, idx->eligible(), nq, idx->dim));
+    const bool gather = !idx->mask_ovr && (idx->path == VROD_PATH_GATHER || (idx->filter_on && filter_route(idx->path, idx->dtype, N, idx->eligible(), nq, idx->dim)));
     Route r = gather ? Route{VROD_PATH_GATHER, false}
                      : route(idx->path, idx->dtype, idx->split_enabled, mfma_skinny_max_queries(true, 2u * idx->ldp * 2u), N, nq, k);
     if (r.split && !planes_ready(idx)) r.split = false;
@@ -1141,7 +1186,7 @@ static int search_enqueue(vrod_index* idx, Pending& P, const float* d_queries_ra
     // in flight -- but is no faster end to end than plain launches, 91 vs 82 us synchronous: only
     // searches begun while another one is pending, i.e. host-bound pipelines, take it)
     // (a gather search is never replayed: the filter route decides before graph_route)
-    const bool gather = idx->path == VROD_PATH_GATHER || (idx->filter_on && filter_route(idx->path, idx->dtype, N, idx->eligible(), nq, idx->dim));
+    const bool gather = !idx->mask_ovr && (idx->path == VROD_PATH_GATHER || (idx->filter_on && filter_route(idx->path, idx->dtype, N, idx->eligible(), nq, idx->dim)));
     const bool graphable = graphs_on && !P.graph_off && idx->profiling == 0 && nq >= 1 && nq <= 8 && idx->eligible() > 0 && idx->n_pending() >= 1 &&
                            !gather && graph_route(idx->path, nq) && (double)N * idx->ld * idx->esize <= 64.0 * 1048576.0;
     Pending::GraphKey key{};
@@ -2294,6 +2339,200 @@ static int check_thresholds(const float* h_thr, uint32_t nq) {
     return VROD_OK;
 }
 
+// ------------------------------------------------------------------ labelled search (vrod_search_labeled)
+// Query q sees the eligible rows (live, allowed) that carry query_labels[q].  The batch's queries are grouped by label
+// (label_plan.h); ONE device pass over the label array (kernels_label.hip) counts every group's eligible rows and
+// writes the row lists of the groups that want one; filter_route -- the rule of a filtered search, with the group's
+// rows and queries -- sends a group to
+//   the segmented route: the canonical scores of its own rows, all such groups of the batch in one launch per score
+//     chunk (kernels_rescore.hip rescore_segments_kernel), the select chain with a length per query, exact by
+//     construction as the gather path is; or
+//   the dense route: the ordinary search flow (fast pass, certificate, band, exact) over the whole corpus with the
+//     group's mask -- handle mask | (label != L) -- in place of row_mask(): broad groups are few, one search each.
+// Synchronous: the handle is idle before and after.  d_queries_raw / d_out_*: device memory, h_labels: host.
+static void fold_stats(vrod_search_stats& st, const vrod_search_stats& d) {
+    st.path = d.path;
+    st.kprime = std::max(st.kprime, d.kprime);
+    st.scan_launches += d.scan_launches;
+    st.fallback_queries += d.fallback_queries;
+    st.band_queries += d.band_queries;
+    st.max_fast_err = std::max(st.max_fast_err, d.max_fast_err);
+    st.eps_bound = std::max(st.eps_bound, d.eps_bound);
+    st.scan_ms += d.scan_ms;
+    st.sample_ms += d.sample_ms;
+    st.total_ms += d.total_ms;
+    st.split_pass |= d.split_pass;
+}
+
+static int labeled_search(vrod_index* idx, const float* d_queries_raw, uint32_t nq, uint32_t k, const uint32_t* h_labels,
+                          uint64_t* d_out_ids, float* d_out_scores) {
+    vrod_search_stats st{};
+    st.nq = nq; st.k = k; st.path = VROD_PATH_GATHER;
+    const uint64_t N = idx->count;
+    const int form = score_form(idx->metric);
+    Pending& P = next_slot(idx);
+    hipStream_t s = P.stream;
+    if (N == 0) {   // an empty handle: every slot unfilled, as vrod_search
+        launch_fill_none(d_out_ids, d_out_scores, (uint64_t)nq * k, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(s));
+        idx->stats = st;
+        return VROD_OK;
+    }
+    // ---- prepare the queries as a search does; NaN / Inf fails the call before anything is scored
+    P.plan = SearchPlan{};
+    P.plan.nq_pad = nq;
+    VROD_TRY(P.q_f32.ensure((size_t)nq * idx->ld * 4));
+    VROD_TRY(P.small.ensure(small_bytes(nq)));
+    const SmallBlock B = small_block(P);
+    QueryInit qi{};
+    qi.status = B.status;
+    launch_prep_queries(d_queries_raw, nq, nq, idx->dim, idx->ld, prep_form(idx->metric), idx->dtype, P.q_f32.as<float>(), nullptr, B.qn2,
+                        &P.flags[0], &P.flags[1], qi, s);
+    launch_gather_readback(B.status, nq, P.flags, idx->max_xn2_bits, B.readback, s);   // (consumes the slot's scalars)
+    HIP_TRY(hipGetLastError());
+    uint32_t bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, B.readback + nq, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (bad) return fail(VROD_ERR_INVALID_VALUE, "queries contain NaN or Inf");
+
+    // ---- groups, and the per-slot arrays of the segmented route (filled as the passes route their groups)
+    const LabelGroups G = label_groups(h_labels, nq);
+    const uint32_t* base_mask = idx->row_mask();
+    const uint32_t rpb = label_rows_per_block(N);
+    const uint32_t n_blocks = (uint32_t)((N + rpb - 1) / rpb);
+    const double row_bytes = (double)idx->ld * idx->esize;
+    struct Dense { uint32_t g; uint64_t m; };
+    std::vector<Dense> dense;
+    // device copy of q_order (a dense group's queries, and the scatter of its results) followed by as many ones
+    VROD_TRY(idx->lab_slots.ensure((size_t)nq * 4 * 5));
+    uint32_t* d_qorder = idx->lab_slots.as<uint32_t>();
+    uint32_t* d_ones = d_qorder + nq;
+    uint32_t* d_slot_q = d_ones + nq;
+    uint32_t* d_slot_len = d_slot_q + nq;
+    uint32_t* d_slot_base = d_slot_len + nq;
+    {
+        std::vector<uint32_t> up(G.q_order);
+        up.resize((size_t)nq * 2, 1u);
+        HIP_TRY(hipMemcpyAsync(d_qorder, up.data(), up.size() * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    Timer tm(idx, P);
+    P.ev_used = 0; P.scan_pairs.clear(); P.sample_pair = -1; P.tail_pair = -1;
+    for (uint32_t g0 = 0; g0 < G.size(); g0 += kLabelGroupsPerPass) {
+        const uint32_t Gp = std::min<uint32_t>(kLabelGroupsPerPass, G.size() - g0);
+        // ---- pass 1: every group's eligible rows, counted per block of the label array
+        VROD_TRY(idx->lab_tab.ensure((size_t)Gp * 4 * 3));
+        VROD_TRY(idx->lab_cnt.ensure((size_t)n_blocks * Gp * 4));
+        uint32_t* d_table = idx->lab_tab.as<uint32_t>();
+        uint32_t* d_total = d_table + Gp;
+        uint32_t* d_seg_off = d_total + Gp;
+        HIP_TRY(hipMemcpyAsync(d_table, G.labels.data() + g0, (size_t)Gp * 4, hipMemcpyHostToDevice, s));
+        launch_label_group_count(idx->lab_dev, base_mask, N, rpb, d_table, Gp, idx->lab_cnt.as<uint32_t>(), d_total, s);
+        HIP_TRY(hipGetLastError());
+        std::vector<uint32_t> m(Gp);
+        HIP_TRY(hipMemcpyAsync(m.data(), d_total, (size_t)Gp * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        // ---- route
+        std::vector<uint32_t> seg_off(Gp, kNoSegment);
+        std::vector<SegGroup> segs;
+        std::vector<uint32_t> slot_q, slot_len, slot_base;
+        uint64_t list_n = 0;
+        for (uint32_t i = 0; i < Gp; ++i) {
+            const uint32_t g = g0 + i, nqg = G.nq_of(g);
+            if (!filter_route(idx->path, idx->dtype, N, m[i], nqg, idx->dim)) { dense.push_back({g, m[i]}); continue; }
+            seg_off[i] = (uint32_t)list_n;
+            segs.push_back({(uint32_t)list_n, m[i], (uint32_t)slot_q.size(), nqg});
+            for (uint32_t j = 0; j < nqg; ++j) {
+                slot_q.push_back(G.q_order[G.q_off[g] + j]);
+                slot_len.push_back(m[i]);
+                slot_base.push_back((uint32_t)list_n);
+            }
+            list_n += m[i];   // (the groups' rows are disjoint: at most N in all)
+            st.scan_bytes += (double)m[i] * row_bytes;
+            st.scan_flops += 2.0 * nqg * (double)m[i] * idx->dim;
+        }
+        if (segs.empty()) continue;
+        // ---- pass 2: the segmented groups' row lists, ascending
+        const uint32_t ns = (uint32_t)slot_q.size();
+        const SegPlan plan = plan_segments(segs);
+        VROD_TRY(idx->lab_lists.ensure(std::max<uint64_t>(list_n, 1) * 4));
+        VROD_TRY(idx->lab_entries.ensure(std::max<size_t>(plan.entries.size(), 1) * sizeof(SegEntry)));
+        HIP_TRY(hipMemcpyAsync(d_seg_off, seg_off.data(), (size_t)Gp * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_slot_q, slot_q.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_slot_len, slot_len.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_slot_base, slot_base.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s));
+        if (!plan.entries.empty())
+            HIP_TRY(hipMemcpyAsync(idx->lab_entries.p, plan.entries.data(), plan.entries.size() * sizeof(SegEntry), hipMemcpyHostToDevice, s));
+        if (list_n)
+            launch_label_group_scatter(idx->lab_dev, base_mask, N, rpb, d_table, Gp, idx->lab_cnt.as<uint32_t>(), d_seg_off,
+                                       idx->lab_lists.as<uint32_t>(), s);
+        HIP_TRY(hipGetLastError());
+        // ---- score + select, one launch of each kind per chunk of the score block
+        for (const SegChunk& c : plan.chunks) {
+            const uint64_t n_sel = std::max<uint32_t>(c.max_m, 1);
+            const uint64_t out_ld = round_up(n_sel, 64);
+            VROD_TRY(P.scores.ensure((size_t)c.n_slots * out_ld * 4));
+            if (c.n_blocks) {
+                size_t a = 0, b = 0;
+                if (idx->profiling) {   // (markers around the launch, as the gather path)
+                    tm.arm(a, b);
+                    g_launch_events = LaunchEvents{};
+                    if (b) HIP_TRY(hipEventRecord(P.ev[a], s));
+                }
+                launch_rescore_segments(idx->corpus, idx->dtype, form, idx->dim, idx->ld, P.q_f32.as<float>(),
+                                        idx->lab_entries.as<SegEntry>() + c.e0, c.e1 - c.e0, c.n_blocks, d_slot_q, c.slot0,
+                                        idx->lab_lists.as<uint32_t>(), P.scores.as<float>(), out_ld, s);
+                if (idx->profiling && b) { HIP_TRY(hipEventRecord(P.ev[b], s)); P.scan_pairs.push_back({a, b}); }
+                st.scan_launches++;
+            }
+            const uint32_t kx = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(k, n_sel), kSelectChunk / 2);   // (the rest: unfilled)
+            const uint64_t* keys; uint64_t kld, kn;
+            VROD_TRY(select_chain(idx, P, P.scores.as<float>(), out_ld, n_sel, (int)c.n_slots, kx, nullptr, &keys, &kld, &kn, d_slot_len + c.slot0));
+            launch_seg_keys_to_output(keys, kld, kn, (int)c.n_slots, form, k, idx->lab_lists.as<uint32_t>(), d_slot_base + c.slot0,
+                                      d_slot_q + c.slot0, idmap_of(idx), d_out_ids, d_out_scores, s);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipStreamSynchronize(s));   // the next pass reuses the tables
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    if (idx->profiling)
+        for (size_t i = 0; i < P.scan_pairs.size(); ++i) st.scan_ms += tm.ms(P.scan_pairs[i].first, P.scan_pairs[i].second);
+
+    // ---- dense groups: one ordinary search each, over the group's mask
+    if (!dense.empty()) {
+        const uint64_t words = idx->del_bits.size();   // capacity / 32
+        uint32_t max_nq = 0;
+        for (const Dense& d : dense) max_nq = std::max(max_nq, G.nq_of(d.g));
+        VROD_TRY(idx->lab_mask.ensure(words * 4));
+        VROD_TRY(idx->lab_q.ensure((size_t)max_nq * idx->dim * 4));
+        VROD_TRY(idx->lab_ids.ensure((size_t)max_nq * k * 8));
+        VROD_TRY(idx->lab_scores.ensure((size_t)max_nq * k * 4));
+        for (const Dense& d : dense) {
+            const uint32_t nqg = G.nq_of(d.g);
+            const uint32_t* d_qidx = d_qorder + G.q_off[d.g];
+            launch_label_group_mask(idx->lab_dev, base_mask, N, words, G.labels[d.g], idx->lab_mask.as<uint32_t>(), s);
+            launch_gather_rows(d_queries_raw, d_qidx, nqg, idx->dim, idx->lab_q.as<float>(), s);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(s));
+            idx->mask_ovr = idx->lab_mask.as<uint32_t>();
+            idx->elig_ovr = d.m;
+            const int rc = run_search(idx, idx->lab_q.as<float>(), nqg, k, idx->lab_ids.as<uint64_t>(), idx->lab_scores.as<float>());
+            idx->mask_ovr = nullptr;
+            idx->elig_ovr = 0;
+            if (rc != VROD_OK) return rc;
+            fold_stats(st, idx->stats);
+            st.scan_bytes += (double)N * row_bytes;
+            st.scan_flops += 2.0 * nqg * (double)N * idx->dim;
+            launch_scatter_results(idx->lab_ids.as<uint64_t>(), idx->lab_scores.as<float>(), d_qidx, d_ones, nqg, k, d_out_ids, d_out_scores, s);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+    }
+    idx->stats = st;
+    return VROD_OK;
+}
+
 // ------------------------------------------------------------------ C ABI
 extern "C" {
 
@@ -2431,6 +2670,9 @@ int vrod_index_destroy(vrod_index* idx) {
     if (idx->del_dev) (void)hipFree(idx->del_dev);
     if (idx->eff_dev) (void)hipFree(idx->eff_dev);
     idx->list_dev.release();
+    if (idx->lab_dev) (void)hipFree(idx->lab_dev);
+    for (DevBuf* b : {&idx->lab_tab, &idx->lab_cnt, &idx->lab_lists, &idx->lab_slots, &idx->lab_entries, &idx->lab_mask, &idx->lab_q, &idx->lab_ids,
+                      &idx->lab_scores, &idx->lab_qraw}) b->release();
     if (idx->flags) (void)hipFree(idx->flags);
     if (idx->stream) (void)hipStreamDestroy(idx->stream);
     delete idx;
@@ -2660,6 +2902,76 @@ int vrod_search(vrod_index* idx, const float* queries, uint32_t nq, uint32_t k, 
     HIP_TRY(hipMemcpyAsync(out_scores, idx->out_scores.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, idx->stream));
     HIP_TRY(hipStreamSynchronize(idx->stream));
     return VROD_OK;
+}
+
+
+int vrod_index_set_labels(vrod_index* idx, uint64_t first_id, const uint32_t* labels, uint64_t n) {
+    if (!idx || (!labels && n)) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "vrod_index_set_labels on a multi-device handle: labels are not routed to the shards");
+    VROD_TRY(require_idle(idx, "vrod_index_set_labels"));
+    if (first_id < idx->id_offset || first_id - idx->id_offset > idx->count || n > idx->count - (first_id - idx->id_offset))
+        return fail(VROD_ERR_INVALID_ARG, "ids [%llu, %llu) are not all rows of this handle (ids %llu..%llu)", (unsigned long long)first_id,
+                    (unsigned long long)(first_id + n), (unsigned long long)idx->id_offset, (unsigned long long)(idx->id_offset + idx->count));
+    if (!n) return VROD_OK;
+    VROD_TRY(set_device(idx));
+    const uint64_t r0 = first_id - idx->id_offset;
+    if (!idx->lab_dev) {   // the first labels of the handle: every row carries 0 so far
+        uint32_t* d = nullptr;
+        HIP_TRY(hipMalloc((void**)&d, idx->capacity * 4));
+        const hipError_t e = hipMemset(d, 0, idx->capacity * 4);
+        if (e != hipSuccess) { (void)hipFree(d); return fail(VROD_ERR_HIP, "clearing the row labels: %s", hipGetErrorString(e)); }
+        idx->lab_dev = d;
+        idx->lab_bits.assign(idx->capacity, 0u);
+    }
+    HIP_TRY(hipMemcpy(idx->lab_dev + r0, labels, n * 4, hipMemcpyHostToDevice));
+    std::copy(labels, labels + n, idx->lab_bits.begin() + r0);
+    return VROD_OK;
+}
+
+int vrod_index_get_labels(vrod_index* idx, uint64_t first_id, uint64_t n, uint32_t* out_labels) {
+    if (!idx || (!out_labels && n)) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    if (first_id < idx->id_offset || first_id - idx->id_offset > idx->count || n > idx->count - (first_id - idx->id_offset))
+        return fail(VROD_ERR_INVALID_ARG, "ids [%llu, %llu) are not all rows of this handle (ids %llu..%llu)", (unsigned long long)first_id,
+                    (unsigned long long)(first_id + n), (unsigned long long)idx->id_offset, (unsigned long long)(idx->id_offset + idx->count));
+    const uint64_t r0 = first_id - idx->id_offset;
+    for (uint64_t i = 0; i < n; ++i) out_labels[i] = idx->lab_bits.empty() ? 0u : idx->lab_bits[r0 + i];   // (the host mirror is the truth)
+    return VROD_OK;
+}
+
+static int check_labeled_args(vrod_index* idx, const void* q, uint32_t nq, uint32_t k, const void* labels, const void* oi, const void* os) {
+    VROD_TRY(check_search_args(idx, q, nq, k, oi, os));
+    if (nq && !labels) return fail(VROD_ERR_INVALID_ARG, "null buffer");
+    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "vrod_search_labeled on a multi-device handle: labels are not routed to the shards");
+    return VROD_OK;
+}
+
+int vrod_search_labeled(vrod_index* idx, const float* queries, uint32_t nq, uint32_t k, const uint32_t* query_labels,
+                        uint64_t* out_ids, float* out_scores) {
+    VROD_TRY(check_labeled_args(idx, queries, nq, k, query_labels, out_ids, out_scores));
+    if (!nq) return VROD_OK;
+    VROD_TRY(require_idle(idx, "vrod_search_labeled"));
+    VROD_TRY(set_device(idx));
+    VROD_TRY(idx->lab_qraw.ensure((size_t)nq * idx->dim * 4));
+    VROD_TRY(idx->out_ids.ensure((size_t)nq * k * 8));
+    VROD_TRY(idx->out_scores.ensure((size_t)nq * k * 4));
+    HIP_TRY(hipMemcpy(idx->lab_qraw.p, queries, (size_t)nq * idx->dim * 4, hipMemcpyHostToDevice));
+    VROD_TRY(labeled_search(idx, idx->lab_qraw.as<float>(), nq, k, query_labels, idx->out_ids.as<uint64_t>(), idx->out_scores.as<float>()));
+    HIP_TRY(hipMemcpy(out_ids, idx->out_ids.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_scores, idx->out_scores.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    return VROD_OK;
+}
+
+int vrod_search_labeled_device(vrod_index* idx, const float* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_query_labels,
+                               uint64_t* d_out_ids, float* d_out_scores, void* stream) {
+    VROD_TRY(check_labeled_args(idx, d_queries, nq, k, d_query_labels, d_out_ids, d_out_scores));
+    if (!nq) return VROD_OK;
+    VROD_TRY(require_idle(idx, "vrod_search_labeled_device"));
+    VROD_TRY(set_device(idx));
+    // synchronous, as a range search: whatever the caller's stream holds is complete before the library's streams start
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    std::vector<uint32_t> labels(nq);
+    HIP_TRY(hipMemcpy(labels.data(), d_query_labels, (size_t)nq * 4, hipMemcpyDeviceToHost));
+    return labeled_search(idx, d_queries, nq, k, labels.data(), d_out_ids, d_out_scores);
 }
 
 int vrod_range_search(vrod_index* idx, const float* queries, uint32_t nq, const float* thresholds, uint64_t capacity,

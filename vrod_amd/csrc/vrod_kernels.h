@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "search_plan.h"   // kSelectChunk
+#include "label_plan.h"    // SegEntry
 
 namespace vrod {
 
@@ -95,12 +96,13 @@ void launch_hist_compact(const float* d_scores, uint64_t score_ld, uint64_t n, i
 // ---- kernels_select.hip
 // Level 0: fast scores (implicit ids = column index) -> per-chunk top-kp composite keys.
 // Later levels: keys -> keys.  Returns the number of keys per query written to d_out.
-// chunk capacity is kSelectChunk (search_plan.h); kp <= kSelectChunk/2.  Level 0 leaves the rows set in d_row_mask
+// chunk capacity is kSelectChunk (search_plan.h); kp <= kSelectChunk/2.  d_len (may be null; a labelled search): query q
+// has only d_len[q] <= n columns, the rest of its score row is padding and never a key.  Level 0 leaves the rows set in d_row_mask
 // (may be null) out: they become the empty key 0, which ranks below every row (a NaN score included) and is emitted as
 // an unfilled slot.
 uint64_t launch_select_from_scores(const float* d_scores, uint64_t score_ld, uint64_t n, int nq,
                                    int metric, uint32_t kp, uint64_t* d_out, uint64_t out_ld,
-                                   const uint32_t* d_row_mask, hipStream_t s);
+                                   const uint32_t* d_row_mask, hipStream_t s, const uint32_t* d_len = nullptr);
 uint64_t launch_select_from_keys(const uint64_t* d_in, uint64_t in_ld, uint64_t n, int nq,
                                  uint32_t kp, uint64_t* d_out, uint64_t out_ld, hipStream_t s);
 // Final step of a select chain: keys (n <= kSelectChunk per query, sorted or not) ->
@@ -162,6 +164,12 @@ void launch_list_keys_to_output(const uint64_t* d_keys, uint64_t key_ld, uint64_
                                 const uint32_t* d_list, const IdMap& idmap, uint64_t* d_out_ids, float* d_out_scores,
                                 hipStream_t s);
 
+// Labelled search output: as launch_list_keys_to_output, with a list segment (d_lists + d_seg_base[s]) and an output row
+// (d_slot_q[s]) of its own per score slot s < ns.
+void launch_seg_keys_to_output(const uint64_t* d_keys, uint64_t key_ld, uint64_t n, int ns, int metric, uint32_t k,
+                               const uint32_t* d_lists, const uint32_t* d_seg_base, const uint32_t* d_slot_q, const IdMap& idmap,
+                               uint64_t* d_out_ids, float* d_out_scores, hipStream_t s);
+
 // Fill a result block with "no result" (ids = UINT64_MAX, scores = NaN): the empty list slots of
 // the multi-device exchange.
 void launch_fill_none(uint64_t* d_ids, float* d_scores, uint64_t n, hipStream_t s);
@@ -188,6 +196,29 @@ void launch_rescore_all(const void* d_corpus, int dtype, int metric, uint32_t di
 // One launch serves any nq (queries in groups of 8 per lane, rows in tiles of 64 per wave).
 void launch_rescore_list(const void* d_corpus, int dtype, int metric, uint32_t dim, uint32_t ld, const float* d_q, uint32_t nq,
                          const uint32_t* d_list, uint64_t m, float* d_out, uint64_t out_ld, hipStream_t s);
+
+// Segmented form (a labelled search, label_plan.h): ONE launch of n_blocks blocks scores every entry of the work table
+// d_entries -- per entry a group of queries (score slots; slot s is prepared row d_slot_q[s] of d_q) over its own
+// segment of the row lists d_lists: d_out[(s - slot_first) * out_ld + c] = score of row d_lists[list_base + c].
+void launch_rescore_segments(const void* d_corpus, int dtype, int metric, uint32_t dim, uint32_t ld, const float* d_q,
+                             const SegEntry* d_entries, uint32_t n_entries, uint32_t n_blocks, const uint32_t* d_slot_q, uint32_t slot_first,
+                             const uint32_t* d_lists, float* d_out, uint64_t out_ld, hipStream_t s);
+
+// ---- kernels_label.hip : rows grouped by the labels of a batch, one label's dense-scan mask
+// Pass 1 + prefix: d_cnt [blocks][G] (blocks = ceil(count / rows_per_block)) becomes each block's first position within
+// every group, d_total[g] the eligible rows (not set in d_mask, which may be null) that carry d_table[g] (sorted
+// distinct labels, G <= kLabelGroupsPerPass).  d_labels == null: every row carries label 0.
+void launch_label_group_count(const uint32_t* d_labels, const uint32_t* d_mask, uint64_t count, uint32_t rows_per_block,
+                              const uint32_t* d_table, uint32_t G, uint32_t* d_cnt, uint32_t* d_total, hipStream_t s);
+// Pass 2: group g's rows, ascending, into d_lists[d_seg_off[g] ...] (kNoSegment: the group gets no list).
+void launch_label_group_scatter(const uint32_t* d_labels, const uint32_t* d_mask, uint64_t count, uint32_t rows_per_block,
+                                const uint32_t* d_table, uint32_t G, uint32_t* d_cnt, const uint32_t* d_seg_off, uint32_t* d_lists,
+                                hipStream_t s);
+// d_out [n_words]: bit r set = row r is set in d_mask (may be null), carries another label than `label`, or r >= count.
+void launch_label_group_mask(const uint32_t* d_labels, const uint32_t* d_mask, uint64_t count, uint64_t n_words, uint32_t label,
+                             uint32_t* d_out, hipStream_t s);
+// d_dst row i = d_src row d_idx[i] (rows of dim floats)
+void launch_gather_rows(const float* d_src, const uint32_t* d_idx, uint32_t n, uint32_t dim, float* d_dst, hipStream_t s);
 
 // ---- kernels_mfma.hip : batched Q.K^T scan with fused threshold filter
 // Timing of the dominant scan launches without marker packets: the launcher of the next scan

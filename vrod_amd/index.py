@@ -153,6 +153,30 @@ class Index:
         check(self._L.vrod_index_filter_count(self._h, C.byref(out)))
         return out.value
 
+    @staticmethod
+    def _labels(labels, n=None) -> np.ndarray:
+        """An integer array-like of labels (each in 0 .. 2**32 - 1; `n` of them when given) -> a contiguous uint32 vector."""
+        a = np.asarray(labels)
+        if a.dtype.kind not in "iu" and (a.size or isinstance(labels, np.ndarray)):   # (an empty list has no dtype of its own)
+            raise TypeError(f"labels must be an integer array, got {a.dtype}")
+        a = a.reshape(-1)
+        if n is not None and a.size != n:
+            raise ValueError(f"labels must hold {n} values, got {a.size}")
+        if a.size and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+            raise ValueError("labels must fit 32 unsigned bits")
+        return np.ascontiguousarray(a.astype(np.uint32, copy=False))
+
+    def set_labels(self, first_id: int, labels):
+        """Give the rows with ids first_id, first_id + 1, ... the labels of an integer array-like (vrod_index_set_labels).
+        Every row carries label 0 until it is given one; only search_labeled reads labels."""
+        a = self._labels(labels)
+        check(self._L.vrod_index_set_labels(self._h, int(first_id), a.ctypes.data_as(C.c_void_p), a.size))
+
+    def get_labels(self, first_id: int, n: int) -> np.ndarray:
+        out = np.empty(int(n), dtype=np.uint32)
+        check(self._L.vrod_index_get_labels(self._h, int(first_id), int(n), out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def set_id_offset(self, off: int):
         check(self._L.vrod_index_set_id_offset(self._h, int(off)))
 
@@ -197,6 +221,42 @@ class Index:
         check(self._L.vrod_search(self._h, queries.ctypes.data_as(C.c_void_p), nq, int(k),
                                   ids.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p)))
         return ids, sc
+
+    def search_labeled(self, queries: np.ndarray, k: int, labels):
+        """search() with a label per query (vrod_search_labeled): query q sees only the eligible rows that carry labels[q].
+        numpy [nq, dim] fp32, nq integer labels -> (ids uint64 [nq, k], scores float32 [nq, k])."""
+        queries = np.ascontiguousarray(queries, dtype=np.float32)
+        if queries.ndim == 1:
+            queries = queries[None, :]
+        if queries.ndim != 2 or queries.shape[1] != self.dim:
+            raise ValueError(f"queries must be [nq, {self.dim}]")
+        nq = queries.shape[0]
+        lab = self._labels(labels, nq)
+        ids = np.empty((nq, k), dtype=np.uint64)
+        sc = np.empty((nq, k), dtype=np.float32)
+        check(self._L.vrod_search_labeled(self._h, queries.ctypes.data_as(C.c_void_p), nq, int(k), lab.ctypes.data_as(C.c_void_p),
+                                          ids.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p)))
+        return ids, sc
+
+    def search_labeled_device(self, d_queries, k: int, d_labels, out_ids=None, out_scores=None):
+        """torch CUDA tensors: queries [nq, dim] fp32, labels [nq] int32 (the bits of uint32) -> (ids int64-viewed-uint64
+        [nq, k], scores [nq, k]) on the device, complete on return."""
+        import torch
+        assert d_queries.is_cuda and d_queries.dtype == torch.float32 and d_queries.is_contiguous()
+        if d_labels.dtype != torch.int32:
+            raise TypeError(f"labels must be an int32 tensor, got {d_labels.dtype}")
+        nq = d_queries.shape[0]
+        if d_labels.numel() != nq:
+            raise ValueError(f"labels must hold {nq} values, got {d_labels.numel()}")
+        assert d_labels.is_cuda and d_labels.is_contiguous()
+        if out_ids is None:
+            out_ids = torch.empty((nq, k), dtype=torch.int64, device=d_queries.device)
+        if out_scores is None:
+            out_scores = torch.empty((nq, k), dtype=torch.float32, device=d_queries.device)
+        stream = torch.cuda.current_stream(d_queries.device).cuda_stream
+        check(self._L.vrod_search_labeled_device(self._h, d_queries.data_ptr(), nq, int(k), d_labels.data_ptr(), out_ids.data_ptr(),
+                                                 out_scores.data_ptr(), C.c_void_p(stream)))
+        return out_ids, out_scores
 
     def search_device(self, d_queries, k: int, out_ids=None, out_scores=None):
         """torch CUDA tensor [nq, dim] fp32 -> (ids int64-viewed-uint64 [nq,k], scores [nq,k]) on device."""
