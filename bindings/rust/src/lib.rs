@@ -108,6 +108,10 @@ extern "C" {
     pub fn vrod_search_labeled_device(idx: *mut vrod_index, d_queries: *const f32, nq: u32, k: u32,
                                       d_query_labels: *const u32, d_out_ids: *mut u64, d_out_scores: *mut f32,
                                       stream: *mut c_void) -> c_int;
+    pub fn vrod_search_grouped(idx: *mut vrod_index, queries: *const f32, nq: u32, k: u32, out_ids: *mut u64,
+                               out_scores: *mut f32, out_labels: *mut u32) -> c_int;
+    pub fn vrod_search_grouped_device(idx: *mut vrod_index, d_queries: *const f32, nq: u32, k: u32, d_out_ids: *mut u64,
+                                      d_out_scores: *mut f32, d_out_labels: *mut u32, stream: *mut c_void) -> c_int;
 }
 
 /// Joins the reference's `thiserror` enums (`src/main.rs:36-40`, `src/command/builder.rs:10-15`).

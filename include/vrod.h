@@ -186,8 +186,8 @@ int vrod_index_set_filter(vrod_index *idx, const uint32_t *allow_words, uint64_t
 /* Rows the next search may return: live and allowed (= vrod_index_live_count without a filter). */
 int vrod_index_filter_count(const vrod_index *idx, uint64_t *out);
 /* Row labels: every row carries one uint32_t label -- 0 until set, and 0 for rows added later -- that only
- * vrod_search_labeled reads (vrod_search, vrod_range_search and the pipelined forms ignore labels entirely).  set_labels
- * gives the rows with ids [first_id, first_id + n) (ids as searches report them, id_offset applied; deleted rows may be
+ * vrod_search_labeled and vrod_search_grouped read (vrod_search, vrod_range_search and the pipelined forms ignore
+ * labels entirely).  set_labels gives the rows with ids [first_id, first_id + n) (ids as searches report them, id_offset applied; deleted rows may be
  * named) the labels labels[0 .. n) (host memory); a range that is not wholly within the current rows fails with
  * VROD_ERR_INVALID_ARG and changes nothing; n == 0 does nothing.  vrod_index_update keeps a row's label,
  * vrod_index_delete leaves labels alone, vrod_index_compact moves them with their rows.  get_labels reads them back
@@ -274,6 +274,32 @@ int vrod_search_labeled(vrod_index *idx, const float *queries, uint32_t nq, uint
 int vrod_search_labeled_device(vrod_index *idx, const float *d_queries, uint32_t nq, uint32_t k,
                                const uint32_t *d_query_labels, uint64_t *d_out_ids, float *d_out_scores,
                                void *stream);
+
+/* Grouped search -- the best row of each label, the k best labels per query (a document stored as many chunk rows that
+ * share a label: the k best documents, not k chunks of one).  The ELIGIBLE rows of a query are the rows that are live
+ * and, while a filter is set, allowed by the handle's filter.  Every label carried by at least one eligible row has one
+ * REPRESENTATIVE, its best eligible row: the best canonical score, ties broken by the smaller id, a NaN score last, as in
+ * vrod_search.  Query q's result row is the k best representatives, best first, ties by smaller id, id_offset applied;
+ * out_ids / out_scores are nq x k, out_labels (nq x k, may be NULL) holds the label of each result; slots beyond the
+ * number of distinct labels are (VROD_ID_NONE, NaN) with label 0.  Scores are the CPU oracle's bits: the row is what the
+ * oracle's top-1 over each label's eligible rows, sorted, gives.  A handle whose labels were never set holds label 0 in
+ * every row: each query gets exactly one result.  k, null pointers and NaN / Inf in the queries are handled as
+ * vrod_search handles them.  Synchronous, like the labelled and range searches: no _begin_ form, no graph replay;
+ * VROD_ERR_INVALID_ARG while a search is pending; the _device form takes device pointers and returns after the results
+ * are complete in device memory.  Exact for any group size: the ordinary search runs with more results per query (4 k,
+ * at least k + 32, at most VROD_MAX_K or the eligible rows) and its lists are de-duplicated by label on the device; a
+ * query whose list ends before k labels are found -- a few labels own all of it -- is finished from the canonical scores
+ * of every row, with the rows of the labels already taken masked, in as many rounds as it needs (at most k).
+ * vrod_index_set_path is honoured by the first search; EXACT sends every query straight to the canonical scores.
+ * An empty handle, or one without an eligible row, gives all-unfilled rows without looking at the queries, as
+ * vrod_search does.  vrod_index_last_stats afterwards: path = the first search's, or VROD_PATH_EXACT when every query took the canonical
+ * scores; k as given; kprime = the first search's; fallback_queries = the first search's + the queries that took the
+ * canonical scores; scan_bytes / scan_flops = the first search's + every stored row (x the queries) per pass over the
+ * corpus (one per 8 such queries), each such pass one more of scan_launches and part of scan_ms.  Multi-device handles: VROD_ERR_UNSUPPORTED, the outputs are not touched. */
+int vrod_search_grouped(vrod_index *idx, const float *queries, uint32_t nq, uint32_t k,
+                        uint64_t *out_ids, float *out_scores, uint32_t *out_labels);
+int vrod_search_grouped_device(vrod_index *idx, const float *d_queries, uint32_t nq, uint32_t k,
+                               uint64_t *d_out_ids, float *d_out_scores, uint32_t *d_out_labels, void *stream);
 
 /* Merge n_lists per-shard results (device, each nq x k, list-major: [list][q][k]) into
  * one nq x k on `device` -- the step after the RCCL all-gather. */

@@ -23,6 +23,7 @@ SYMBOLS = [
     "vrod_index_last_stats", "vrod_index_shard_stats", "vrod_last_error", "vrod_version", "vrod_synth_rows_device",
     "vrod_range_search", "vrod_range_search_device", "vrod_index_update", "vrod_index_compact",
     "vrod_index_set_labels", "vrod_index_get_labels", "vrod_search_labeled", "vrod_search_labeled_device",
+    "vrod_search_grouped", "vrod_search_grouped_device",
 ]
 
 ERR_CAPACITY = 8   # VROD_ERR_CAPACITY: a range search's result does not fit the caller's buffers (out_lims is valid)
@@ -103,6 +104,8 @@ def load() -> C.CDLL:
     L.vrod_index_get_labels.argtypes = [vp, u64, u64, vp]
     L.vrod_search_labeled.argtypes = [vp, vp, u32, u32, vp, vp, vp]
     L.vrod_search_labeled_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
+    L.vrod_search_grouped.argtypes = [vp, vp, u32, u32, vp, vp, vp]
+    L.vrod_search_grouped_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
     for name in SYMBOLS:
         getattr(L, name).restype = i32
     L.vrod_last_error.restype = C.c_char_p

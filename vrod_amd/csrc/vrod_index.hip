@@ -34,8 +34,11 @@
 #include "search_plan.h"
 #include "compact_plan.h"
 #include "label_plan.h"
+#include "group_plan.h"
 
 using namespace vrod;
+
+static_assert(kGroupMaxK == VROD_MAX_K, "group_plan.h restates the largest k of the ABI");
 
 // ------------------------------------------------------------------ errors
 static thread_local std::string g_last_error;
@@ -212,6 +215,10 @@ struct vrod_index {
     // labelled search workspaces: [table | totals | segment offsets], the per-block counts, the row lists, the per-slot
     // arrays, the work table, a dense group's mask / raw queries / results, the host form's raw queries
     DevBuf lab_tab, lab_cnt, lab_lists, lab_slots, lab_entries, lab_mask, lab_q, lab_ids, lab_scores, lab_qraw;
+    // grouped search workspaces (vrod_search_grouped): the candidate lists [lists][k1], the per-query words [found | valid |
+    // the lists' queries], the dense stage's masks [<= 8][capacity / 32], the labels of the results when the caller
+    // wants none, the host form's raw queries
+    DevBuf grp_ids, grp_scores, grp_small, grp_mask, grp_labels, grp_qraw;
 
     // workspaces
     DevBuf raw_stage, nrm_ws, out_ids, out_scores;
@@ -2533,6 +2540,152 @@ static int labeled_search(vrod_index* idx, const float* d_queries_raw, uint32_t 
     return VROD_OK;
 }
 
+// ------------------------------------------------------------------ grouped search (vrod_search_grouped)
+// The best eligible row of each label (its representative), the k best representatives per query.  A search's list is
+// sorted by (score, id), so the representatives, in their own order, are a sub-sequence of it: the first k distinct
+// labels of an exact top-k1 are the k best representatives whenever the list has that many, or holds every eligible row.
+//   candidate stage: the ordinary search flow with k1 = group_first_k results per query (group_plan.h), then
+//     group_dedupe_kernel keeps the first entry of each label (kernels_group.hip);
+//   dense stage, for the queries that stage leaves unresolved (a few labels own their whole list) and for every query
+//     under VROD_PATH_EXACT: the canonical scores of all rows, once per group of up to 8 queries, then rounds of
+//     [mask per query: the handle's mask | rows of a label already taken -> select the next k1 -> de-duplicate] until the
+//     query is resolved.  A round that does not resolve its query returns k1 unmasked rows, so it takes at least one new
+//     label and masks all of that label's rows: at most k rounds.
+// Synchronous: the handle is idle before and after.  Every pointer is device memory; d_out_labels is never null here.
+static int grouped_search(vrod_index* idx, const float* d_queries_raw, uint32_t nq, uint32_t k, uint64_t* d_out_ids, float* d_out_scores,
+                          uint32_t* d_out_labels) {
+    vrod_search_stats st{};
+    st.nq = nq; st.k = k; st.path = (uint32_t)idx->path;
+    const uint64_t N = idx->count, elig = idx->eligible();
+    const int form = score_form(idx->metric);
+    const IdMap idmap = idmap_of(idx);
+    hipStream_t s = next_slot(idx).stream;
+    VROD_TRY(idx->grp_small.ensure((size_t)nq * 4 * 3));
+    uint32_t* d_found = idx->grp_small.as<uint32_t>();
+    uint32_t* d_valid = d_found + nq;
+    uint32_t* d_qidx = d_valid + nq;
+    launch_fill_none(d_out_ids, d_out_scores, (uint64_t)nq * k, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(d_out_labels, 0, (size_t)nq * k * 4, s));
+    HIP_TRY(hipMemsetAsync(d_found, 0, (size_t)nq * 4 * 2, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (N == 0 || elig == 0) {   // no eligible row: every slot unfilled, as vrod_search
+        idx->stats = st;
+        return VROD_OK;
+    }
+    // a handle without labels holds one label: its representative is the best row, and no list can add a second
+    const bool one_label = !idx->lab_dev;
+    const uint32_t k1 = one_label ? 1u : group_first_k(k, elig);
+    std::vector<uint32_t> hfv((size_t)nq * 2), todo;
+    auto read_state = [&](hipStream_t on) -> int {
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(hfv.data(), d_found, (size_t)nq * 8, hipMemcpyDeviceToHost, on));
+        HIP_TRY(hipStreamSynchronize(on));
+        return VROD_OK;
+    };
+    auto resolved = [&](uint32_t q) { return one_label || group_resolved(hfv[q], k, hfv[nq + q], k1, elig); };
+
+    // ---- candidate stage
+    if (idx->path != VROD_PATH_EXACT) {
+        VROD_TRY(idx->grp_ids.ensure((size_t)nq * k1 * 8));
+        VROD_TRY(idx->grp_scores.ensure((size_t)nq * k1 * 4));
+        VROD_TRY(run_search(idx, d_queries_raw, nq, k1, idx->grp_ids.as<uint64_t>(), idx->grp_scores.as<float>()));
+        st = idx->stats;
+        st.k = k;
+        s = next_slot(idx).stream;
+        launch_group_dedupe(idx->grp_ids.as<uint64_t>(), idx->grp_scores.as<float>(), k1, nq, idx->lab_dev, idmap.offset, nullptr, k,
+                            d_out_ids, d_out_scores, d_out_labels, d_found, d_valid, s);
+        VROD_TRY(read_state(s));
+        for (uint32_t q = 0; q < nq; ++q)
+            if (!resolved(q)) todo.push_back(q);
+    } else {
+        for (uint32_t q = 0; q < nq; ++q) todo.push_back(q);
+    }
+    if (todo.empty()) {
+        idx->stats = st;
+        return VROD_OK;
+    }
+
+    // ---- dense stage: the queries prepared as a search prepares them (NaN / Inf fails the call: under EXACT nothing
+    // has looked at them yet)
+    Pending& P = next_slot(idx);
+    P.plan = SearchPlan{};
+    P.plan.nq_pad = nq;
+    VROD_TRY(P.q_f32.ensure((size_t)nq * idx->ld * 4));
+    VROD_TRY(P.small.ensure(small_bytes(nq)));
+    const SmallBlock B = small_block(P);
+    QueryInit qi{};
+    qi.status = B.status;
+    launch_prep_queries(d_queries_raw, nq, nq, idx->dim, idx->ld, prep_form(idx->metric), idx->dtype, P.q_f32.as<float>(), nullptr, B.qn2,
+                        &P.flags[0], &P.flags[1], qi, s);
+    launch_gather_readback(B.status, nq, P.flags, idx->max_xn2_bits, B.readback, s);   // (consumes the slot's scalars)
+    HIP_TRY(hipGetLastError());
+    uint32_t bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, B.readback + nq, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (bad) return fail(VROD_ERR_INVALID_VALUE, "queries contain NaN or Inf");
+
+    const uint64_t score_ld = round_up(N, 64), words = idx->del_bits.size();   // capacity / 32
+    const double row_bytes = (double)idx->ld * idx->esize;
+    int gmax = rescore_all_max_queries(idx->ld);
+    while (gmax > 1 && (uint64_t)gmax * score_ld * 4 > (1ull << 30)) gmax >>= 1;
+    VROD_TRY(idx->grp_ids.ensure((size_t)gmax * k1 * 8));
+    VROD_TRY(idx->grp_scores.ensure((size_t)gmax * k1 * 4));
+    VROD_TRY(idx->grp_mask.ensure((size_t)gmax * words * 4));
+    Timer tm(idx, P);
+    P.ev_used = 0; P.scan_pairs.clear(); P.sample_pair = -1; P.tail_pair = -1;
+    for (size_t f0 = 0; f0 < todo.size();) {
+        int g = gmax;
+        while ((size_t)g > todo.size() - f0) g >>= 1;
+        VROD_TRY(P.scores.ensure((size_t)g * score_ld * 4));
+        size_t ea = 0, eb = 0;
+        if (idx->profiling) {   // (markers around the launch, as the gather path)
+            tm.arm(ea, eb);
+            g_launch_events = LaunchEvents{};
+            if (eb) HIP_TRY(hipEventRecord(P.ev[ea], s));
+        }
+        launch_rescore_all(idx->corpus, idx->dtype, form, idx->dim, idx->ld, P.q_f32.as<float>(), &todo[f0], g, N, P.scores.as<float>(),
+                           score_ld, s);
+        if (idx->profiling && eb) { HIP_TRY(hipEventRecord(P.ev[eb], s)); P.scan_pairs.push_back({ea, eb}); }
+        HIP_TRY(hipGetLastError());
+        st.scan_launches++;
+        st.scan_bytes += (double)N * row_bytes;
+        st.scan_flops += 2.0 * g * (double)N * idx->dim;
+        struct Active { uint32_t q, score_row; };
+        std::vector<Active> act;
+        for (int i = 0; i < g; ++i) act.push_back({todo[f0 + i], (uint32_t)i});
+        for (uint32_t round = 0; !act.empty(); ++round) {
+            if (round > k) return fail(VROD_ERR_INTERNAL, "grouped search: a dense round took no label");
+            const uint32_t na = (uint32_t)act.size();
+            std::vector<uint32_t> hq(na);
+            for (uint32_t a = 0; a < na; ++a) hq[a] = act[a].q;
+            HIP_TRY(hipMemcpyAsync(d_qidx, hq.data(), (size_t)na * 4, hipMemcpyHostToDevice, s));
+            launch_group_mask(idx->lab_dev, idx->row_mask(), N, words, d_qidx, na, d_out_labels, d_found, k, idx->grp_mask.as<uint32_t>(), s);
+            for (uint32_t a = 0; a < na; ++a) {   // a mask per query: a select chain per query
+                const uint64_t* keys; uint64_t kld, kn;
+                VROD_TRY(select_chain(idx, P, P.scores.as<float>() + (size_t)act[a].score_row * score_ld, score_ld, N, 1, k1,
+                                      idx->grp_mask.as<uint32_t>() + (size_t)a * words, &keys, &kld, &kn));
+                launch_keys_to_output(keys, kn, form, k1, idmap, idx->grp_ids.as<uint64_t>() + (size_t)a * k1,
+                                      idx->grp_scores.as<float>() + (size_t)a * k1, s);
+            }
+            launch_group_dedupe(idx->grp_ids.as<uint64_t>(), idx->grp_scores.as<float>(), k1, na, idx->lab_dev, idmap.offset, d_qidx, k,
+                                d_out_ids, d_out_scores, d_out_labels, d_found, d_valid, s);
+            VROD_TRY(read_state(s));   // (also orders the next round's upload of d_qidx behind this round's readers)
+            std::vector<Active> next;
+            for (const Active& a : act)
+                if (!resolved(a.q)) next.push_back(a);
+            act.swap(next);
+        }
+        f0 += g;
+    }
+    if (idx->profiling)   // (every round ended with a synchronisation: the events are complete)
+        for (size_t i = 0; i < P.scan_pairs.size(); ++i) st.scan_ms += tm.ms(P.scan_pairs[i].first, P.scan_pairs[i].second);
+    st.fallback_queries += (uint32_t)todo.size();
+    if (todo.size() == nq) st.path = VROD_PATH_EXACT;
+    idx->stats = st;
+    return VROD_OK;
+}
+
 // ------------------------------------------------------------------ C ABI
 extern "C" {
 
@@ -2672,7 +2825,8 @@ int vrod_index_destroy(vrod_index* idx) {
     idx->list_dev.release();
     if (idx->lab_dev) (void)hipFree(idx->lab_dev);
     for (DevBuf* b : {&idx->lab_tab, &idx->lab_cnt, &idx->lab_lists, &idx->lab_slots, &idx->lab_entries, &idx->lab_mask, &idx->lab_q, &idx->lab_ids,
-                      &idx->lab_scores, &idx->lab_qraw}) b->release();
+                      &idx->lab_scores, &idx->lab_qraw, &idx->grp_ids, &idx->grp_scores, &idx->grp_small, &idx->grp_mask, &idx->grp_labels,
+                      &idx->grp_qraw}) b->release();
     if (idx->flags) (void)hipFree(idx->flags);
     if (idx->stream) (void)hipStreamDestroy(idx->stream);
     delete idx;
@@ -2972,6 +3126,46 @@ int vrod_search_labeled_device(vrod_index* idx, const float* d_queries, uint32_t
     std::vector<uint32_t> labels(nq);
     HIP_TRY(hipMemcpy(labels.data(), d_query_labels, (size_t)nq * 4, hipMemcpyDeviceToHost));
     return labeled_search(idx, d_queries, nq, k, labels.data(), d_out_ids, d_out_scores);
+}
+
+static int check_grouped_args(vrod_index* idx, const void* q, uint32_t nq, uint32_t k, const void* oi, const void* os) {
+    VROD_TRY(check_search_args(idx, q, nq, k, oi, os));
+    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "vrod_search_grouped on a multi-device handle: labels are not routed to the shards");
+    return VROD_OK;
+}
+
+int vrod_search_grouped(vrod_index* idx, const float* queries, uint32_t nq, uint32_t k, uint64_t* out_ids, float* out_scores,
+                        uint32_t* out_labels) {
+    VROD_TRY(check_grouped_args(idx, queries, nq, k, out_ids, out_scores));
+    if (!nq) return VROD_OK;
+    VROD_TRY(require_idle(idx, "vrod_search_grouped"));
+    VROD_TRY(set_device(idx));
+    VROD_TRY(idx->grp_qraw.ensure((size_t)nq * idx->dim * 4));
+    VROD_TRY(idx->out_ids.ensure((size_t)nq * k * 8));
+    VROD_TRY(idx->out_scores.ensure((size_t)nq * k * 4));
+    VROD_TRY(idx->grp_labels.ensure((size_t)nq * k * 4));
+    HIP_TRY(hipMemcpy(idx->grp_qraw.p, queries, (size_t)nq * idx->dim * 4, hipMemcpyHostToDevice));
+    VROD_TRY(grouped_search(idx, idx->grp_qraw.as<float>(), nq, k, idx->out_ids.as<uint64_t>(), idx->out_scores.as<float>(),
+                            idx->grp_labels.as<uint32_t>()));
+    HIP_TRY(hipMemcpy(out_ids, idx->out_ids.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_scores, idx->out_scores.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    if (out_labels) HIP_TRY(hipMemcpy(out_labels, idx->grp_labels.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    return VROD_OK;
+}
+
+int vrod_search_grouped_device(vrod_index* idx, const float* d_queries, uint32_t nq, uint32_t k, uint64_t* d_out_ids, float* d_out_scores,
+                               uint32_t* d_out_labels, void* stream) {
+    VROD_TRY(check_grouped_args(idx, d_queries, nq, k, d_out_ids, d_out_scores));
+    if (!nq) return VROD_OK;
+    VROD_TRY(require_idle(idx, "vrod_search_grouped_device"));
+    VROD_TRY(set_device(idx));
+    // synchronous, as a range search: whatever the caller's stream holds is complete before the library's streams start
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    if (!d_out_labels) {   // the de-duplication keeps each query's taken labels there
+        VROD_TRY(idx->grp_labels.ensure((size_t)nq * k * 4));
+        d_out_labels = idx->grp_labels.as<uint32_t>();
+    }
+    return grouped_search(idx, d_queries, nq, k, d_out_ids, d_out_scores, d_out_labels);
 }
 
 int vrod_range_search(vrod_index* idx, const float* queries, uint32_t nq, const float* thresholds, uint64_t capacity,

@@ -220,6 +220,20 @@ void launch_label_group_mask(const uint32_t* d_labels, const uint32_t* d_mask, u
 // d_dst row i = d_src row d_idx[i] (rows of dim floats)
 void launch_gather_rows(const float* d_src, const uint32_t* d_idx, uint32_t n, uint32_t dim, float* d_dst, hipStream_t s);
 
+// ---- kernels_group.hip : a grouped search's de-duplication by label and the dense stage's per-query masks
+// List b (d_cand_ids / d_cand_scores + b * k1: a search's result row, ids with id_offset applied) of query d_qidx[b] (b
+// itself when d_qidx is null): the first entry of every label that is not among the d_found[q] < k results already in
+// the query's row of d_out_* [..][k] is appended to them, in list order, while the row has room; d_found[q] = the new
+// count, d_valid[q] = the list's real entries.  d_labels == null: every row carries label 0.  k1 <= kGroupMaxK.
+void launch_group_dedupe(const uint64_t* d_cand_ids, const float* d_cand_scores, uint32_t k1, uint32_t n_lists, const uint32_t* d_labels,
+                         uint64_t id_offset, const uint32_t* d_qidx, uint32_t k, uint64_t* d_out_ids, float* d_out_scores,
+                         uint32_t* d_out_labels, uint32_t* d_found, uint32_t* d_valid, hipStream_t s);
+// d_out [n_queries][n_words]: bit r of row a set = row r is set in d_base_mask (may be null), carries one of the
+// d_found[q] labels in d_out_labels [..][k] of q = d_qidx[a], or r >= count.  Written for the rows below count rounded up
+// to 256, which must lie within n_words * 32 and within the label array.
+void launch_group_mask(const uint32_t* d_labels, const uint32_t* d_base_mask, uint64_t count, uint64_t n_words, const uint32_t* d_qidx,
+                       uint32_t n_queries, const uint32_t* d_out_labels, const uint32_t* d_found, uint32_t k, uint32_t* d_out, hipStream_t s);
+
 // ---- kernels_mfma.hip : batched Q.K^T scan with fused threshold filter
 // Timing of the dominant scan launches without marker packets: the launcher of the next scan
 // kernel attaches these events to the dispatch itself (hipExtLaunchKernelGGL), then clears them.

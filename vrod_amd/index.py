@@ -168,7 +168,7 @@ class Index:
 
     def set_labels(self, first_id: int, labels):
         """Give the rows with ids first_id, first_id + 1, ... the labels of an integer array-like (vrod_index_set_labels).
-        Every row carries label 0 until it is given one; only search_labeled reads labels."""
+        Every row carries label 0 until it is given one; only search_labeled and search_grouped read labels."""
         a = self._labels(labels)
         check(self._L.vrod_index_set_labels(self._h, int(first_id), a.ctypes.data_as(C.c_void_p), a.size))
 
@@ -257,6 +257,40 @@ class Index:
         check(self._L.vrod_search_labeled_device(self._h, d_queries.data_ptr(), nq, int(k), d_labels.data_ptr(), out_ids.data_ptr(),
                                                  out_scores.data_ptr(), C.c_void_p(stream)))
         return out_ids, out_scores
+
+    def search_grouped(self, queries: np.ndarray, k: int):
+        """The best row of each label, the k best labels per query (vrod_search_grouped): numpy [nq, dim] fp32 ->
+        (ids uint64 [nq, k], scores float32 [nq, k], labels uint32 [nq, k]); slots beyond the distinct labels of the
+        eligible rows are (ID_NONE, NaN, 0)."""
+        queries = np.ascontiguousarray(queries, dtype=np.float32)
+        if queries.ndim == 1:
+            queries = queries[None, :]
+        if queries.ndim != 2 or queries.shape[1] != self.dim:
+            raise ValueError(f"queries must be [nq, {self.dim}]")
+        nq = queries.shape[0]
+        ids = np.empty((nq, k), dtype=np.uint64)
+        sc = np.empty((nq, k), dtype=np.float32)
+        lab = np.empty((nq, k), dtype=np.uint32)
+        check(self._L.vrod_search_grouped(self._h, queries.ctypes.data_as(C.c_void_p), nq, int(k), ids.ctypes.data_as(C.c_void_p),
+                                          sc.ctypes.data_as(C.c_void_p), lab.ctypes.data_as(C.c_void_p)))
+        return ids, sc, lab
+
+    def search_grouped_device(self, d_queries, k: int, out_ids=None, out_scores=None, out_labels=None, want_labels=True):
+        """torch CUDA tensor [nq, dim] fp32 -> (ids int64-viewed-uint64 [nq, k], scores [nq, k], labels int32-viewed-uint32
+        [nq, k]) on the device, complete on return.  want_labels=False passes no label buffer (labels is None)."""
+        import torch
+        assert d_queries.is_cuda and d_queries.dtype == torch.float32 and d_queries.is_contiguous()
+        nq = d_queries.shape[0]
+        if out_ids is None:
+            out_ids = torch.empty((nq, k), dtype=torch.int64, device=d_queries.device)
+        if out_scores is None:
+            out_scores = torch.empty((nq, k), dtype=torch.float32, device=d_queries.device)
+        if out_labels is None and want_labels:
+            out_labels = torch.empty((nq, k), dtype=torch.int32, device=d_queries.device)
+        stream = torch.cuda.current_stream(d_queries.device).cuda_stream
+        check(self._L.vrod_search_grouped_device(self._h, d_queries.data_ptr(), nq, int(k), out_ids.data_ptr(), out_scores.data_ptr(),
+                                                 out_labels.data_ptr() if out_labels is not None else None, C.c_void_p(stream)))
+        return out_ids, out_scores, out_labels
 
     def search_device(self, d_queries, k: int, out_ids=None, out_scores=None):
         """torch CUDA tensor [nq, dim] fp32 -> (ids int64-viewed-uint64 [nq,k], scores [nq,k]) on device."""
