@@ -112,6 +112,13 @@ extern "C" {
                                out_scores: *mut f32, out_labels: *mut u32) -> c_int;
     pub fn vrod_search_grouped_device(idx: *mut vrod_index, d_queries: *const f32, nq: u32, k: u32, d_out_ids: *mut u64,
                                       d_out_scores: *mut f32, d_out_labels: *mut u32, stream: *mut c_void) -> c_int;
+    /// `flags`: 0, or 1 (`VROD_BYID_EXCLUDE_SELF`): the row itself is no candidate of its own query.
+    pub fn vrod_search_by_ids(idx: *mut vrod_index, ids: *const u64, nq: u32, k: u32, flags: u32, out_ids: *mut u64,
+                              out_scores: *mut f32) -> c_int;
+    pub fn vrod_search_by_ids_device(idx: *mut vrod_index, d_ids: *const u64, nq: u32, k: u32, flags: u32,
+                                     d_out_ids: *mut u64, d_out_scores: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn vrod_knn_graph(idx: *mut vrod_index, first_id: u64, n: u64, k: u32, out_ids: *mut u64,
+                          out_scores: *mut f32) -> c_int;
 }
 
 /// Joins the reference's `thiserror` enums (`src/main.rs:36-40`, `src/command/builder.rs:10-15`).

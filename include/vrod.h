@@ -301,6 +301,43 @@ int vrod_search_grouped(vrod_index *idx, const float *queries, uint32_t nq, uint
 int vrod_search_grouped_device(vrod_index *idx, const float *d_queries, uint32_t nq, uint32_t k,
                                uint64_t *d_out_ids, float *d_out_scores, uint32_t *d_out_labels, void *stream);
 
+/* Search by stored row id ("more like this") -- query q is the PREPARED stored row ids[q] (nq ids as searches report
+ * them, id_offset applied; host memory, the _device form: device memory), used as stored: it is not normalised again and
+ * not rounded again, so the scores are scores between stored rows and an L2 row is at distance +0.0 from itself.  The
+ * result row is bit for bit (ids and score bits, a NaN matching any NaN) the CPU oracle's canonical scan of that prepared
+ * row over the ELIGIBLE rows (live, and allowed while a filter is set): best first, ties by smaller id, slots beyond the
+ * eligible rows (VROD_ID_NONE, NaN).  Labels are ignored, as in vrod_search.  flags: 0, or VROD_BYID_EXCLUDE_SELF: row
+ * ids[q] is not a candidate of query q -- the result is the top k of the eligible rows other than itself.  The drop is by
+ * id, not by position: an exact duplicate with a smaller id ranks before the row itself, under IP the row need not be its
+ * own best match, under a filter it may not be eligible at all.  With the flag k may be at most VROD_MAX_K - 1 (the
+ * search runs with k + 1 results); a larger k, and unknown flag bits: VROD_ERR_INVALID_ARG.  An id may repeat.  An id that
+ * is not a current row, or names a deleted row, fails the whole call with VROD_ERR_INVALID_ARG and the outputs are not
+ * touched (the _device form: the launch that gathers the rows checks every id and raises one flag, read before anything
+ * else runs -- no host copy of the ids).  nq == 0: VROD_OK.  Synchronous: no _begin_ form, no graph replay;
+ * VROD_ERR_INVALID_ARG while a search is pending; the _device form takes device pointers and returns after the results are
+ * complete in device memory.  vrod_index_set_path is honoured as by vrod_search.  vrod_index_last_stats afterwards: what
+ * the underlying search reported, k = the caller's k.  Multi-device handles: VROD_ERR_UNSUPPORTED, the outputs are not
+ * touched. */
+enum { VROD_BYID_EXCLUDE_SELF = 1u };
+int vrod_search_by_ids(vrod_index *idx, const uint64_t *ids, uint32_t nq, uint32_t k, uint32_t flags,
+                       uint64_t *out_ids, float *out_scores);
+int vrod_search_by_ids_device(vrod_index *idx, const uint64_t *d_ids, uint32_t nq, uint32_t k, uint32_t flags,
+                              uint64_t *d_out_ids, float *d_out_scores, void *stream);
+/* The exact k-NN graph of the corpus: for every row with id in [first_id, first_id + n), result row i (out_ids /
+ * out_scores: host memory, n x k) holds the k nearest OTHER eligible rows of id first_id + i -- exactly what
+ * vrod_search_by_ids(.., VROD_BYID_EXCLUDE_SELF) returns for that id.  A DELETED row in the range gets an all-unfilled
+ * result row ((VROD_ID_NONE, NaN) in every slot) and is never scanned for: the range form stays usable between a delete
+ * and a compact.  A filter that is set restricts the neighbours, not the queries.  A range that is not wholly within the
+ * current rows: VROD_ERR_INVALID_ARG; k at most VROD_MAX_K - 1; n == 0: VROD_OK.  The library cuts the range into batches
+ * of its own choosing and keeps two in flight: batch s + 1's gather and scan are
+ * enqueued before batch s's lists lose self and are copied out; the results do not depend on the batch size.
+ * vrod_index_last_stats afterwards: nq = the live rows of the range, k as given, scan_launches / scan_bytes / scan_flops /
+ * scan_ms / fallback_queries / band_queries = sums over the batches, kprime / max_fast_err / eps_bound = maxima, path =
+ * the last batch's.  VROD_ERR_INVALID_ARG while a search is pending; multi-device handles: VROD_ERR_UNSUPPORTED, the
+ * outputs are not touched. */
+int vrod_knn_graph(vrod_index *idx, uint64_t first_id, uint64_t n, uint32_t k,
+                   uint64_t *out_ids, float *out_scores);
+
 /* Merge n_lists per-shard results (device, each nq x k, list-major: [list][q][k]) into
  * one nq x k on `device` -- the step after the RCCL all-gather. */
 int vrod_merge_topk_device(int device, int metric, const uint64_t *d_ids,

@@ -24,6 +24,7 @@ SYMBOLS = [
     "vrod_range_search", "vrod_range_search_device", "vrod_index_update", "vrod_index_compact",
     "vrod_index_set_labels", "vrod_index_get_labels", "vrod_search_labeled", "vrod_search_labeled_device",
     "vrod_search_grouped", "vrod_search_grouped_device",
+    "vrod_search_by_ids", "vrod_search_by_ids_device", "vrod_knn_graph",
 ]
 
 ERR_CAPACITY = 8   # VROD_ERR_CAPACITY: a range search's result does not fit the caller's buffers (out_lims is valid)
@@ -106,6 +107,9 @@ def load() -> C.CDLL:
     L.vrod_search_labeled_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
     L.vrod_search_grouped.argtypes = [vp, vp, u32, u32, vp, vp, vp]
     L.vrod_search_grouped_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
+    L.vrod_search_by_ids.argtypes = [vp, vp, u32, u32, u32, vp, vp]
+    L.vrod_search_by_ids_device.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp]
+    L.vrod_knn_graph.argtypes = [vp, u64, u64, u32, vp, vp]
     for name in SYMBOLS:
         getattr(L, name).restype = i32
     L.vrod_last_error.restype = C.c_char_p

@@ -35,10 +35,12 @@
 #include "compact_plan.h"
 #include "label_plan.h"
 #include "group_plan.h"
+#include "byid_plan.h"
 
 using namespace vrod;
 
 static_assert(kGroupMaxK == VROD_MAX_K, "group_plan.h restates the largest k of the ABI");
+static_assert(kByidMaxK == VROD_MAX_K, "byid_plan.h restates the largest k of the ABI");
 
 // ------------------------------------------------------------------ errors
 static thread_local std::string g_last_error;
@@ -219,6 +221,16 @@ struct vrod_index {
     // the lists' queries], the dense stage's masks [<= 8][capacity / 32], the labels of the results when the caller
     // wants none, the host form's raw queries
     DevBuf grp_ids, grp_scores, grp_small, grp_mask, grp_labels, grp_qraw;
+    // Searches whose queries are stored rows (vrod_search_by_ids, vrod_knn_graph) hand the search flow rows that are
+    // prepared already: while prep_ovr is not negative it stands for prep_form(metric) in the launch that prepares a
+    // search's queries -- M_L2, the take-as-given form of L2 and IP handles: nothing is normalised, and rounding a bf16
+    // value to bf16 is the identity.  Everything else that launch sets up is unchanged.  Negative outside those two entry
+    // points; a search under it is never captured into a graph nor matched with a captured one.
+    int prep_ovr = -1;
+    // their workspaces, one set per batch in flight (byid_plan.h: a graph's batch s uses set s & 1, a search by ids set
+    // 0): the search's lists [nq][k or k + 1], the lists without self [nq][k], a graph batch's [live rows | place of
+    // every row among them]; and the host form's ids on the device
+    DevBuf byid_ids[2], byid_scores[2], byid_out_ids[2], byid_out_scores[2], byid_map[2], byid_user_ids;
 
     // workspaces
     DevBuf raw_stage, nrm_ws, out_ids, out_scores;
@@ -1151,8 +1163,8 @@ static int search_enqueue_body(vrod_index* idx, Pending& P, const float* d_queri
         qi.zero_words2 = P.hist.as<uint32_t>();
         qi.n_zero_words2 = (uint32_t)kHistWords;
     }
-    launch_prep_queries(d_queries_raw, nq, nq_pad, idx->dim, idx->ld, prep_form(idx->metric), idx->dtype, P.q_f32.as<float>(),
-                        q_lp, B.qn2, &P.flags[0], &P.flags[1], qi, s);
+    launch_prep_queries(d_queries_raw, nq, nq_pad, idx->dim, idx->ld, idx->prep_ovr >= 0 ? idx->prep_ovr : prep_form(idx->metric), idx->dtype,
+                        P.q_f32.as<float>(), q_lp, B.qn2, &P.flags[0], &P.flags[1], qi, s);
     HIP_TRY(hipGetLastError());
 
     // ---- fast pass: k' candidates per query + T
@@ -1194,7 +1206,8 @@ static int search_enqueue(vrod_index* idx, Pending& P, const float* d_queries_ra
     // searches begun while another one is pending, i.e. host-bound pipelines, take it)
     // (a gather search is never replayed: the filter route decides before graph_route)
     const bool gather = !idx->mask_ovr && (idx->path == VROD_PATH_GATHER || (idx->filter_on && filter_route(idx->path, idx->dtype, N, idx->eligible(), nq, idx->dim)));
-    const bool graphable = graphs_on && !P.graph_off && idx->profiling == 0 && nq >= 1 && nq <= 8 && idx->eligible() > 0 && idx->n_pending() >= 1 &&
+    // (nor a search whose queries are stored rows: the captured launch prepares its queries, theirs are prepared)
+    const bool graphable = graphs_on && idx->prep_ovr < 0 && !P.graph_off && idx->profiling == 0 && nq >= 1 && nq <= 8 && idx->eligible() > 0 && idx->n_pending() >= 1 &&
                            !gather && graph_route(idx->path, nq) && (double)N * idx->ld * idx->esize <= 64.0 * 1048576.0;
     Pending::GraphKey key{};
     if (graphable) {
@@ -2686,6 +2699,157 @@ static int grouped_search(vrod_index* idx, const float* d_queries_raw, uint32_t 
     return VROD_OK;
 }
 
+// ------------------------------------------------------------------ searches by stored row (vrod_search_by_ids, vrod_knn_graph)
+// The queries are rows the handle already holds: byid_gather_kernel copies them out of the corpus as fp32 (kernels_byid.hip)
+// and the ordinary search flow takes them as given (prep_ovr) -- the stored row is the query bit for bit, so the scores
+// are scores between stored rows and an L2 row is at distance +0.0 from itself.  With the self drop the search returns
+// k + 1 results into the library's own lists and byid_drop_self_kernel writes the caller's k: the top k of S \ {self} is
+// the top (k + 1) of S with self removed, whatever position self took (an exact duplicate with a smaller id ranks
+// before it; under IP, or under a filter that leaves it out, it may not be in the list at all).
+constexpr uint32_t kByidFlag = 16;   // word of idx->flags the gather raises for an id that is no live row
+
+static int byid_search_begin(vrod_index* idx, const float* d_rows_f32, uint32_t nq, uint32_t k1, uint64_t* d_ids, float* d_scores) {
+    idx->prep_ovr = M_L2;   // set for exactly the enqueue: nothing else prepares queries
+    const int rc = search_begin(idx, d_rows_f32, nq, k1, d_ids, d_scores);
+    idx->prep_ovr = -1;
+    return rc;
+}
+
+// d_ids, d_out_*: device memory.  checked: the host has validated the ids already (the host form); else the gather does,
+// and its flag is read before the search is begun: a failed call leaves the handle and the outputs as they were.
+static int byid_search(vrod_index* idx, const uint64_t* d_ids, bool checked, uint32_t nq, uint32_t k, bool exclude_self,
+                       uint64_t* d_out_ids, float* d_out_scores) {
+    Pending& P = next_slot(idx);
+    hipStream_t s = P.stream;
+    const uint32_t k1 = byid_search_k(k, exclude_self);
+    const bool staged = exclude_self;   // the search writes the library's lists, the drop launch the caller's rows
+    uint64_t* l_ids = d_out_ids;
+    float* l_scores = d_out_scores;
+    if (staged) {
+        VROD_TRY(idx->byid_ids[0].ensure((size_t)nq * k1 * 8));
+        VROD_TRY(idx->byid_scores[0].ensure((size_t)nq * k1 * 4));
+        l_ids = idx->byid_ids[0].as<uint64_t>();
+        l_scores = idx->byid_scores[0].as<float>();
+    }
+    VROD_TRY(P.q_raw.ensure((size_t)nq * idx->dim * 4));
+    launch_byid_gather(idx->corpus, idx->dtype, idx->ld, idx->dim, idx->count, idx->id_offset, idx->n_deleted ? idx->del_dev : nullptr, d_ids,
+                       nullptr, 0, nq, P.q_raw.as<float>(), checked ? nullptr : &idx->flags[kByidFlag], s);
+    HIP_TRY(hipGetLastError());
+    if (!checked) {   // (the search is begun only behind this read-back: a bad id leaves the caller's buffers untouched)
+        uint32_t bad = 0;
+        HIP_TRY(hipMemcpyAsync(&bad, &idx->flags[kByidFlag], 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (bad) {
+            HIP_TRY(hipMemsetAsync(&idx->flags[kByidFlag], 0, 4, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            return fail(VROD_ERR_INVALID_ARG, "an id is not a live row of this handle (ids %llu..%llu, deleted rows excluded)",
+                        (unsigned long long)idx->id_offset, (unsigned long long)(idx->id_offset + idx->count));
+        }
+    }
+    VROD_TRY(byid_search_begin(idx, P.q_raw.as<float>(), nq, k1, l_ids, l_scores));
+    VROD_TRY(search_end(idx));
+    idx->stats.k = k;
+    if (staged) {   // (the search is complete: any stream may follow it)
+        launch_byid_drop_self(l_ids, l_scores, k1, nullptr, d_ids, 0, nq, k, d_out_ids, d_out_scores, idx->stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(idx->stream));
+    }
+    return VROD_OK;
+}
+
+// The graph of rows [row0, row0 + n): batches of byid_plan.h, two in flight -- batch s + 1's gather and search are
+// enqueued (search_begin) before batch s is completed (search_end), its lists lose self and its rows are copied out, so
+// the device scans batch s + 1 while the host and the copy engine finish batch s.  The deleted rows of a batch never
+// reach the scan: byid_live_kernel compacts the batch's live rows (their number comes from the host mirror), and the
+// drop launch writes the deleted rows' result rows unfilled.  out_*: host memory.
+static int knn_graph(vrod_index* idx, uint64_t row0, uint64_t n, uint32_t k, uint64_t* out_ids, float* out_scores) {
+    const uint32_t k1 = byid_search_k(k, true);
+    const uint32_t batch = byid_batch_rows(idx->dtype == VROD_DTYPE_BF16, n);
+    const uint64_t nb = byid_n_batches(n, batch);
+    vrod_search_stats tot{};
+    tot.k = k; tot.path = (uint32_t)idx->path;
+    struct Flight { ByidBatch b; uint32_t live; bool holes; hipStream_t stream; };
+    auto map_of = [&](const Flight& F) { return idx->byid_map[F.b.slot].as<uint32_t>(); };   // [live rows | place of every row]
+    auto begin = [&](uint64_t s, Flight& F) -> int {
+        F.b = byid_batch(n, batch, s);
+        const uint64_t r0 = row0 + F.b.first;
+        const uint32_t m = F.b.rows, c = F.b.slot;
+        uint32_t dead = 0;
+        if (idx->n_deleted) {   // the tombstones of [r0, r0 + m), a word of the host mirror at a time
+            const uint32_t* bits = idx->del_bits.data();
+            for (uint64_t w = r0 / 32; w * 32 < r0 + m; ++w) {
+                uint32_t v = bits[w];
+                if (w * 32 < r0) v &= ~0u << (r0 - w * 32);
+                if ((w + 1) * 32 > r0 + m) v &= ~0u >> ((w + 1) * 32 - (r0 + m));
+                dead += (uint32_t)__builtin_popcount(v);
+            }
+        }
+        F.live = m - dead;
+        F.holes = dead != 0;
+        F.stream = idx->stream;
+        if (!F.live) return VROD_OK;   // nothing to search: the batch's rows are written unfilled
+        Pending& P = next_slot(idx);
+        F.stream = P.stream;
+        VROD_TRY(idx->byid_ids[c].ensure((size_t)F.live * k1 * 8));
+        VROD_TRY(idx->byid_scores[c].ensure((size_t)F.live * k1 * 4));
+        VROD_TRY(P.q_raw.ensure((size_t)F.live * idx->dim * 4));
+        const uint32_t* d_rows = nullptr;
+        if (F.holes) {
+            VROD_TRY(idx->byid_map[c].ensure((size_t)m * 4 * 2));
+            launch_byid_live(idx->del_dev, r0, m, map_of(F), map_of(F) + m, P.stream);
+            d_rows = map_of(F);
+        }
+        launch_byid_gather(idx->corpus, idx->dtype, idx->ld, idx->dim, idx->count, idx->id_offset, nullptr, nullptr, d_rows, r0, F.live,
+                           P.q_raw.as<float>(), nullptr, P.stream);   // (the range and the tombstones were checked on the host)
+        HIP_TRY(hipGetLastError());
+        return byid_search_begin(idx, P.q_raw.as<float>(), F.live, k1, idx->byid_ids[c].as<uint64_t>(), idx->byid_scores[c].as<float>());
+    };
+    auto finish = [&](const Flight& F) -> int {
+        const uint32_t m = F.b.rows, c = F.b.slot;
+        if (F.live) {
+            VROD_TRY(search_end(idx));
+            const vrod_search_stats& d = idx->stats;
+            fold_stats(tot, d);
+            tot.nq += d.nq;
+            tot.scan_bytes += d.scan_bytes;
+            tot.scan_flops += d.scan_flops;
+            tot.overlap_ms += d.overlap_ms;
+        }
+        VROD_TRY(idx->byid_out_ids[c].ensure((size_t)m * k * 8));
+        VROD_TRY(idx->byid_out_scores[c].ensure((size_t)m * k * 4));
+        uint64_t* d_oi = idx->byid_out_ids[c].as<uint64_t>();
+        float* d_os = idx->byid_out_scores[c].as<float>();
+        // on the stream of the search just completed (the other slot's is scanning the next batch); a batch without a
+        // search has no slot: the handle's own stream
+        if (F.live)
+            launch_byid_drop_self(idx->byid_ids[c].as<uint64_t>(), idx->byid_scores[c].as<float>(), k1, F.holes ? map_of(F) + m : nullptr, nullptr,
+                                  idx->id_offset + row0 + F.b.first, m, k, d_oi, d_os, F.stream);
+        else
+            launch_fill_none(d_oi, d_os, (uint64_t)m * k, F.stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(out_ids + F.b.first * k, d_oi, (size_t)m * k * 8, hipMemcpyDeviceToHost, F.stream));
+        HIP_TRY(hipMemcpyAsync(out_scores + F.b.first * k, d_os, (size_t)m * k * 4, hipMemcpyDeviceToHost, F.stream));
+        HIP_TRY(hipStreamSynchronize(F.stream));
+        return VROD_OK;
+    };
+    Flight cur{}, nxt{};
+    int rc = begin(0, cur);
+    for (uint64_t s = 0; rc == VROD_OK && s < nb; ++s) {
+        const bool more = s + 1 < nb;
+        if (more) rc = begin(s + 1, nxt);
+        if (rc == VROD_OK) rc = finish(cur);
+        cur = nxt;
+    }
+    if (rc != VROD_OK) {   // leave the handle idle: whatever is still pending is ended, the first error is the call's
+        const std::string why = g_last_error;
+        while (idx->n_pending()) (void)search_end(idx);
+        g_last_error = why;
+        return rc;
+    }
+    idx->stats = tot;
+    return VROD_OK;
+}
+
 // ------------------------------------------------------------------ C ABI
 extern "C" {
 
@@ -2826,7 +2990,9 @@ int vrod_index_destroy(vrod_index* idx) {
     if (idx->lab_dev) (void)hipFree(idx->lab_dev);
     for (DevBuf* b : {&idx->lab_tab, &idx->lab_cnt, &idx->lab_lists, &idx->lab_slots, &idx->lab_entries, &idx->lab_mask, &idx->lab_q, &idx->lab_ids,
                       &idx->lab_scores, &idx->lab_qraw, &idx->grp_ids, &idx->grp_scores, &idx->grp_small, &idx->grp_mask, &idx->grp_labels,
-                      &idx->grp_qraw}) b->release();
+                      &idx->grp_qraw, &idx->byid_user_ids}) b->release();
+    for (int c = 0; c < 2; ++c)
+        for (DevBuf* b : {&idx->byid_ids[c], &idx->byid_scores[c], &idx->byid_out_ids[c], &idx->byid_out_scores[c], &idx->byid_map[c]}) b->release();
     if (idx->flags) (void)hipFree(idx->flags);
     if (idx->stream) (void)hipStreamDestroy(idx->stream);
     delete idx;
@@ -3166,6 +3332,62 @@ int vrod_search_grouped_device(vrod_index* idx, const float* d_queries, uint32_t
         d_out_labels = idx->grp_labels.as<uint32_t>();
     }
     return grouped_search(idx, d_queries, nq, k, d_out_ids, d_out_scores, d_out_labels);
+}
+
+static int check_byid_args(vrod_index* idx, const void* ids, uint32_t nq, uint32_t k, uint32_t flags, const void* oi, const void* os,
+                           const char* what) {
+    // (what the arguments alone decide comes first: it is checked, and tested, without a handle)
+    if (flags & ~(uint32_t)VROD_BYID_EXCLUDE_SELF) return fail(VROD_ERR_INVALID_ARG, "unknown flag bits 0x%x", flags);
+    if (!byid_k_ok(k, flags & VROD_BYID_EXCLUDE_SELF))
+        return fail(VROD_ERR_INVALID_ARG, "k must be in 1..%u (1..%u with the self drop)", VROD_MAX_K, VROD_MAX_K - 1);
+    if (!idx) return fail(VROD_ERR_INVALID_ARG, "idx is null");
+    if (nq && (!ids || !oi || !os)) return fail(VROD_ERR_INVALID_ARG, "null buffer");
+    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "%s on a multi-device handle: stored rows are not gathered across the shards", what);
+    return VROD_OK;
+}
+
+int vrod_search_by_ids(vrod_index* idx, const uint64_t* ids, uint32_t nq, uint32_t k, uint32_t flags, uint64_t* out_ids, float* out_scores) {
+    VROD_TRY(check_byid_args(idx, ids, nq, k, flags, out_ids, out_scores, "vrod_search_by_ids"));
+    if (!nq) return VROD_OK;
+    VROD_TRY(require_idle(idx, "vrod_search_by_ids"));
+    for (uint32_t q = 0; q < nq; ++q) {   // the host mirror of the tombstones is the truth: nothing is launched for a bad id
+        const uint64_t id = ids[q];
+        if (id < idx->id_offset || id - idx->id_offset >= idx->count || bit_of(idx->del_bits.data(), id - idx->id_offset))
+            return fail(VROD_ERR_INVALID_ARG, "id %llu is not a live row of this handle (ids %llu..%llu, deleted rows excluded)", (unsigned long long)id,
+                        (unsigned long long)idx->id_offset, (unsigned long long)(idx->id_offset + idx->count));
+    }
+    VROD_TRY(set_device(idx));
+    VROD_TRY(idx->byid_user_ids.ensure((size_t)nq * 8));
+    VROD_TRY(idx->out_ids.ensure((size_t)nq * k * 8));
+    VROD_TRY(idx->out_scores.ensure((size_t)nq * k * 4));
+    HIP_TRY(hipMemcpy(idx->byid_user_ids.p, ids, (size_t)nq * 8, hipMemcpyHostToDevice));
+    VROD_TRY(byid_search(idx, idx->byid_user_ids.as<uint64_t>(), true, nq, k, flags & VROD_BYID_EXCLUDE_SELF, idx->out_ids.as<uint64_t>(),
+                         idx->out_scores.as<float>()));
+    HIP_TRY(hipMemcpy(out_ids, idx->out_ids.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_scores, idx->out_scores.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    return VROD_OK;
+}
+
+int vrod_search_by_ids_device(vrod_index* idx, const uint64_t* d_ids, uint32_t nq, uint32_t k, uint32_t flags, uint64_t* d_out_ids,
+                              float* d_out_scores, void* stream) {
+    VROD_TRY(check_byid_args(idx, d_ids, nq, k, flags, d_out_ids, d_out_scores, "vrod_search_by_ids_device"));
+    if (!nq) return VROD_OK;
+    VROD_TRY(require_idle(idx, "vrod_search_by_ids_device"));
+    VROD_TRY(set_device(idx));
+    // synchronous, as a range search: whatever the caller's stream holds is complete before the library's streams start
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return byid_search(idx, d_ids, false, nq, k, flags & VROD_BYID_EXCLUDE_SELF, d_out_ids, d_out_scores);
+}
+
+int vrod_knn_graph(vrod_index* idx, uint64_t first_id, uint64_t n, uint32_t k, uint64_t* out_ids, float* out_scores) {
+    VROD_TRY(check_byid_args(idx, (void*)1, n ? 1u : 0u, k, VROD_BYID_EXCLUDE_SELF, out_ids, out_scores, "vrod_knn_graph"));
+    if (first_id < idx->id_offset || first_id - idx->id_offset > idx->count || n > idx->count - (first_id - idx->id_offset))
+        return fail(VROD_ERR_INVALID_ARG, "ids [%llu, %llu) are not all rows of this handle (ids %llu..%llu)", (unsigned long long)first_id,
+                    (unsigned long long)(first_id + n), (unsigned long long)idx->id_offset, (unsigned long long)(idx->id_offset + idx->count));
+    if (!n) return VROD_OK;
+    VROD_TRY(require_idle(idx, "vrod_knn_graph"));
+    VROD_TRY(set_device(idx));
+    return knn_graph(idx, first_id - idx->id_offset, n, k, out_ids, out_scores);
 }
 
 int vrod_range_search(vrod_index* idx, const float* queries, uint32_t nq, const float* thresholds, uint64_t capacity,

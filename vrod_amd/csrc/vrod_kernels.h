@@ -234,6 +234,23 @@ void launch_group_dedupe(const uint64_t* d_cand_ids, const float* d_cand_scores,
 void launch_group_mask(const uint32_t* d_labels, const uint32_t* d_base_mask, uint64_t count, uint64_t n_words, const uint32_t* d_qidx,
                        uint32_t n_queries, const uint32_t* d_out_labels, const uint32_t* d_found, uint32_t k, uint32_t* d_out, hipStream_t s);
 
+// ---- kernels_byid.hip : queries taken from stored rows (vrod_search_by_ids, vrod_knn_graph)
+// Rows [row0, row0 + m) against the deleted-row bitmap d_del (not null): d_live[j] = the j-th live row, ascending;
+// d_src[i] = j for the live row row0 + i, ~0u for a deleted one.  One work-group: m is a batch.
+void launch_byid_live(const uint32_t* d_del, uint64_t row0, uint32_t m, uint32_t* d_live, uint32_t* d_src, hipStream_t s);
+// d_out [nq][dim] fp32 = the prepared rows as stored (bf16 widened), read with the handle's row stride ld.  Query q is
+//   d_ids != null: row d_ids[q] - id_offset; an id that is no current row, or is set in d_del (may be null), raises
+//                  *d_bad_flag and gives a zero row;
+//   else d_rows != null: row d_rows[q];  else: row base_row + q  (a row >= count raises the flag as well).
+// d_bad_flag may be null when the host has checked the rows already.
+void launch_byid_gather(const void* d_corpus, int dtype, uint32_t ld, uint32_t dim, uint64_t count, uint64_t id_offset,
+                        const uint32_t* d_del, const uint64_t* d_ids, const uint32_t* d_rows, uint64_t base_row, uint32_t nq, float* d_out,
+                        uint32_t* d_bad_flag, hipStream_t s);
+// Output row i < n_out [k] = result list d_src[i] (i when d_src is null; ~0u: an unfilled row) of d_list_* [..][k1], k1 >
+// k, without the entry whose id is d_self[i] (base_id + i when d_self is null), cut to k.
+void launch_byid_drop_self(const uint64_t* d_list_ids, const float* d_list_scores, uint32_t k1, const uint32_t* d_src, const uint64_t* d_self,
+                           uint64_t base_id, uint32_t n_out, uint32_t k, uint64_t* d_out_ids, float* d_out_scores, hipStream_t s);
+
 // ---- kernels_mfma.hip : batched Q.K^T scan with fused threshold filter
 // Timing of the dominant scan launches without marker packets: the launcher of the next scan
 // kernel attaches these events to the dispatch itself (hipExtLaunchKernelGGL), then clears them.

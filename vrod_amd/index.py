@@ -18,6 +18,9 @@ METRIC_COSINE, METRIC_L2, METRIC_IP = 0, 1, 2
 PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT, PATH_GATHER = 0, 1, 2, 3, 4
 ID_NONE = np.uint64(0xFFFFFFFFFFFFFFFF)
 MAX_K = 3584
+BYID_EXCLUDE_SELF = 1   # VROD_BYID_EXCLUDE_SELF
+# rows per batch of knn_graph() by storage type (byid_plan.h: kByidBatchF32, kByidBatchBf16)
+KNN_BATCH = {0: 256, 1: 1024}
 
 _DTYPES = {"f32": DTYPE_F32, "fp32": DTYPE_F32, "float32": DTYPE_F32, "bf16": DTYPE_BF16, "bfloat16": DTYPE_BF16}
 _METRICS = {"cosine": METRIC_COSINE, "cos": METRIC_COSINE, "l2": METRIC_L2, "euclidean": METRIC_L2,
@@ -179,6 +182,7 @@ class Index:
 
     def set_id_offset(self, off: int):
         check(self._L.vrod_index_set_id_offset(self._h, int(off)))
+        self._id_offset = int(off)
 
     def get_rows(self, first: int, n: int) -> np.ndarray:
         out = np.empty((n, self.dim), dtype=np.float32)
@@ -291,6 +295,72 @@ class Index:
         check(self._L.vrod_search_grouped_device(self._h, d_queries.data_ptr(), nq, int(k), out_ids.data_ptr(), out_scores.data_ptr(),
                                                  out_labels.data_ptr() if out_labels is not None else None, C.c_void_p(stream)))
         return out_ids, out_scores, out_labels
+
+    # -- search by stored row: the queries are rows the handle already holds, used as stored
+    @classmethod
+    def _query_ids(cls, ids) -> np.ndarray:
+        """Ids as searches report them: any integer array-like without a negative value -> a contiguous uint64 vector."""
+        a = np.asarray(ids)
+        if a.size and a.dtype.kind == "i" and int(a.min()) < 0:
+            raise ValueError("ids must not be negative")
+        if a.dtype.kind == "b":
+            raise TypeError("ids must be integers, got bool")
+        return cls._ids(ids)
+
+    def search_by_ids(self, ids, k: int, exclude_self: bool = False):
+        """Each stored row's nearest neighbours (vrod_search_by_ids): integer ids [nq] -> (ids uint64 [nq, k], scores
+        float32 [nq, k]).  The query is the prepared row as stored.  exclude_self=True: the row itself is no candidate
+        (k <= MAX_K - 1).  An id that is no live row raises VrodError (code 1)."""
+        a = self._query_ids(ids)
+        nq = a.size
+        out_ids = np.empty((nq, k), dtype=np.uint64)
+        sc = np.empty((nq, k), dtype=np.float32)
+        check(self._L.vrod_search_by_ids(self._h, a.ctypes.data_as(C.c_void_p), nq, int(k), BYID_EXCLUDE_SELF if exclude_self else 0,
+                                         out_ids.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p)))
+        return out_ids, sc
+
+    def search_by_ids_device(self, d_ids, k: int, exclude_self: bool = False, out_ids=None, out_scores=None):
+        """torch CUDA tensor of ids [nq] int64 (the bits of uint64) -> (ids int64-viewed-uint64 [nq, k], scores [nq, k]) on
+        the device, complete on return."""
+        import torch
+        if d_ids.dtype != torch.int64:
+            raise TypeError(f"ids must be an int64 tensor, got {d_ids.dtype}")
+        assert d_ids.is_cuda and d_ids.is_contiguous()
+        nq = d_ids.numel()
+        if out_ids is None:
+            out_ids = torch.empty((nq, k), dtype=torch.int64, device=d_ids.device)
+        if out_scores is None:
+            out_scores = torch.empty((nq, k), dtype=torch.float32, device=d_ids.device)
+        stream = torch.cuda.current_stream(d_ids.device).cuda_stream
+        check(self._L.vrod_search_by_ids_device(self._h, d_ids.data_ptr(), nq, int(k), BYID_EXCLUDE_SELF if exclude_self else 0,
+                                                out_ids.data_ptr(), out_scores.data_ptr(), C.c_void_p(stream)))
+        return out_ids, out_scores
+
+    def knn_graph(self, k: int, first_id=None, n=None):
+        """The exact k-NN graph (vrod_knn_graph): for the rows with ids first_id .. first_id + n - 1 (default: every row,
+        from the smallest id a search on this handle reports) the k nearest other eligible rows -> (ids uint64 [n, k],
+        scores float32 [n, k]); a deleted row's result row is all (ID_NONE, NaN).  The default range starts at the offset
+        given to set_id_offset() of THIS object (0 if it was never called): the C ABI has no getter, so a handle whose
+        offset was set any other way must pass first_id and n."""
+        if first_id is None:
+            if n is not None:
+                raise ValueError("n needs first_id")
+            first_id = self._first_id()
+        first_id = int(first_id)
+        if first_id < 0:
+            raise ValueError("first_id must not be negative")
+        if n is None:
+            n = self._first_id() + self.count - first_id
+        n = int(n)
+        if n < 0:
+            raise ValueError("n must not be negative")
+        out_ids = np.empty((n, k), dtype=np.uint64)
+        sc = np.empty((n, k), dtype=np.float32)
+        check(self._L.vrod_knn_graph(self._h, first_id, n, int(k), out_ids.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p)))
+        return out_ids, sc
+
+    def _first_id(self) -> int:
+        return getattr(self, "_id_offset", 0)
 
     def search_device(self, d_queries, k: int, out_ids=None, out_scores=None):
         """torch CUDA tensor [nq, dim] fp32 -> (ids int64-viewed-uint64 [nq,k], scores [nq,k]) on device."""
