@@ -9,7 +9,7 @@ import numpy as np
 
 from conftest import f32_split
 from index_model import ID_NONE, ModelError, ModelIndex, bits
-from sequence_plans import PIPE_K, PIPE_NQ, Op, apply_mutation, every_form, expected, is_check
+from sequence_plans import PATH_AUTO, PIPE_K, PIPE_NQ, Op, _Maker, apply_mutation, every_form, expected, is_check
 
 SENT_ID, SENT_SC = np.uint64(0x5A5A5A5A5A5A5A5A), np.float32(-12345.5)
 ERR_UNSUPPORTED = 6
@@ -47,6 +47,7 @@ class Pair:
         self.labelled = False
         self.step = -1
         self.evens = 0
+        self.gen = _Maker(seed + 2000, cfg, self.model)         # the plans' own row and query generator, over this pair's model
 
     def __enter__(self):
         return self
@@ -164,6 +165,39 @@ class Pair:
         else:
             same_lists(got, want, what)
         return got
+
+    def routed(self, op, path, tag="", force=None):
+        """A check op that must take the route `path`, under the handle's path as it stands or under the forced path
+        `force` (the handle is back on AUTO afterwards) -> the counters of that search."""
+        if force is not None:
+            self.ix.set_path(force)
+        try:
+            self.check(op, tag)
+            st = self.ix.last_stats()
+        finally:
+            if force is not None:
+                self.ix.set_path(PATH_AUTO)
+        assert st["path"] == path, f"{self.where(op)} {tag}: took path {st['path']}, not {path}: {st}"
+        return st
+
+    def read_back(self, local_rows, what):
+        """Whole rows read back, live or deleted: the bits of the model's prepared rows."""
+        pc = self.model.prepared()
+        rows = np.unique(np.asarray(local_rows, np.int64))
+        for run in np.split(rows, np.flatnonzero(np.diff(rows) > 1) + 1):       # a call per stretch of neighbouring rows
+            lo, n = int(run[0]), int(run.size)
+            got, want = bits(self.ix.get_rows(lo, n)), bits(pc[lo:lo + n])
+            assert np.array_equal(got, want), f"{what}: rows {(lo + np.flatnonzero((got != want).any(axis=1)))[:8].tolist()} read back differently"
+
+    def fresh_rows(self, n):
+        return self.gen.rows(n)
+
+    def queries(self, nq):
+        return self.gen.queries(nq)
+
+    def rank_thresholds(self, rq, rank):
+        """Per query the model's rank-th best score over the eligible rows: a range search at it returns that row too."""
+        return self.model.search(rq, rank)[1][:, rank - 1].copy()
 
     def check_every_form(self, tag, nqs=(3, 40), k=10, forms=None):
         self.evens += 1

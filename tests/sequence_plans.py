@@ -24,7 +24,7 @@ form behind every kind of mutation.
 Where the plans leave the issue's figures, and why.  The issue asks for totals of 1 500 .. 8 000 rows, a labelling with
 about 40 labels of about 20 rows beside a label on more than half of the rows (so at least 1 800 rows), two capacity growths
 under tombstones, filter and labels, and a model-against-numpy check on plans of at most 2 000 rows: two growths from 1 800
-rows end above 3 400.  So COMMITTED holds eight full-size plans that meet all of it and run on the GPU, and MODEL_CHECK two
+rows end above 3 400.  So COMMITTED holds eight full-size plans that meet all of it and run on the GPU, and MODEL_CHECK three
 `small` plans of the same backbone at 337 .. 1 300 rows (about 7 small labels) that exist for the CPU check of the model
 alone.  An f32 handle with VROD_F32_SPLIT=0 never has planes, so counter (d) is asked of the other f32 plans only.
 
@@ -84,10 +84,12 @@ COMMITTED = (
     (17, Config("f32-l2-72-split1", 72, "f32", "l2", split="1")),
     (18, Config("f32-cosine-64-default", 64, "f32", "cosine", split=None)),
 )
-# Two plans of at most 2 000 rows for the CPU check of the model against numpy (test_sequence_plans.py); not run on a GPU.
+# Three plans of at most 2 000 rows for the CPU check of the model against numpy (test_sequence_plans.py); not run on a
+# GPU.  The third is at an odd width: test_gpu_widths.py compares handles of odd and very long rows with the model.
 MODEL_CHECK = (
     (18, Config("bf16-cosine-100-small", 100, "bf16", "cosine", small=True)),
     (19, Config("f32-ip-64-default-small", 64, "f32", "ip", split=None, small=True)),
+    (20, Config("bf16-l2-33-small", 33, "bf16", "l2", small=True)),
 )
 
 

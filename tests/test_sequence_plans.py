@@ -2,7 +2,7 @@
 
 1. Every committed (seed, config) reaches the orderings the plans exist for.  These are conditions, not measurements: a
    change of the generator after which a plan no longer reaches one of them fails here instead of thinning out quietly.
-2. The model is right: for the two small plans every check op's expected values are compared with an independent numpy
+2. The model is right: for the three small plans (one of them at the odd width 33) every check op's expected values are compared with an independent numpy
    restatement -- oracle.numpy_prepare, numpy_scores_canonical over the FULL row set, a mask instead of a gathered subset,
    numpy_topk_from_scores / numpy_range_from_scores -- in ids and score bits.  To keep the CPU suite quick two kinds of
    check op are sampled, not compared whole: of a pipelined op's 8 searches (all of them model.search, which the plain
@@ -46,7 +46,7 @@ def test_every_committed_plan_reaches_the_orderings(oracle, seed, cfg):
     assert cov["k_above"] >= 1, "a k above the eligible rows"
     assert cov["knn"] <= S.KNN_PER_PLAN
     assert 30 <= cov["steps"] <= 41, cov["steps"]
-    if cfg.small:                                       # (sequence_plans' docstring: why these two are smaller than the issue's sizes)
+    if cfg.small:                                       # (sequence_plans' docstring: why these are smaller than the issue's sizes)
         assert cov["max_rows"] <= 2000
     else:
         assert 1500 <= cov["final_rows"] and cov["max_rows"] <= S.MAX_ROWS
@@ -132,7 +132,7 @@ SMALL = list(S.MODEL_CHECK)
 
 @pytest.mark.parametrize("seed,cfg", SMALL, ids=[f"{seed}-{cfg.name}" for seed, cfg in SMALL])
 def test_the_model_agrees_with_a_numpy_restatement(oracle, seed, cfg):
-    assert len(SMALL) == 2
+    assert len(SMALL) == 3 and 33 in {c.dim for _, c in SMALL}
     m = ModelIndex(cfg.dim, cfg.dtype, cfg.metric, cfg.id_offset)
     rng = np.random.default_rng(seed)
     checked = {}
