@@ -52,6 +52,16 @@ pub struct vrod_search_stats {
     pub overlap_ms: f32,
 }
 
+/// One query's predicate over the 64 tag bits of a row (`vrod_search_tagged`): a row with tags `t` matches iff
+/// `(any == 0 || t & any != 0) && t & all == all && t & none == 0`.
+#[repr(C)]
+#[derive(Debug, Default, Clone, Copy, PartialEq, Eq)]
+pub struct vrod_tag_pred {
+    pub any: u64,
+    pub all: u64,
+    pub none: u64,
+}
+
 extern "C" {
     pub fn vrod_index_create(out: *mut *mut vrod_index, dim: u32, dtype: c_int, metric: c_int,
                              device_ids: *const c_int, n_devices: c_int) -> c_int;
@@ -112,6 +122,13 @@ extern "C" {
                                out_scores: *mut f32, out_labels: *mut u32) -> c_int;
     pub fn vrod_search_grouped_device(idx: *mut vrod_index, d_queries: *const f32, nq: u32, k: u32, d_out_ids: *mut u64,
                                       d_out_scores: *mut f32, d_out_labels: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn vrod_index_set_tags(idx: *mut vrod_index, first_id: u64, tags: *const u64, n: u64) -> c_int;
+    pub fn vrod_index_get_tags(idx: *mut vrod_index, first_id: u64, n: u64, out_tags: *mut u64) -> c_int;
+    pub fn vrod_search_tagged(idx: *mut vrod_index, queries: *const f32, nq: u32, k: u32, preds: *const vrod_tag_pred,
+                              out_ids: *mut u64, out_scores: *mut f32) -> c_int;
+    pub fn vrod_search_tagged_device(idx: *mut vrod_index, d_queries: *const f32, nq: u32, k: u32,
+                                     d_preds: *const vrod_tag_pred, d_out_ids: *mut u64, d_out_scores: *mut f32,
+                                     stream: *mut c_void) -> c_int;
     /// `flags`: 0, or 1 (`VROD_BYID_EXCLUDE_SELF`): the row itself is no candidate of its own query.
     pub fn vrod_search_by_ids(idx: *mut vrod_index, ids: *const u64, nq: u32, k: u32, flags: u32, out_ids: *mut u64,
                               out_scores: *mut f32) -> c_int;
@@ -289,6 +306,38 @@ impl Collection {
         let mut scores = vec![0f32; queries.len() * k];
         check(unsafe {
             vrod_search_labeled(self.idx, flat.as_ptr(), queries.len() as u32, k as u32, labels.as_ptr(), ids.as_mut_ptr(), scores.as_mut_ptr())
+        })?;
+        Ok((ids, scores))
+    }
+}
+
+impl Collection {
+    /// Give the rows with ids `first_id..first_id + tags.len()` their 64-bit tag masks (every row carries 0 until set).
+    pub fn set_tags(&mut self, first_id: u64, tags: &[u64]) -> Result<(), ScanError> {
+        check(unsafe { vrod_index_set_tags(self.idx, first_id, tags.as_ptr(), tags.len() as u64) })
+    }
+
+    pub fn tags(&self, first_id: u64, n: usize) -> Result<Vec<u64>, ScanError> {
+        let mut out = vec![0u64; n];
+        check(unsafe { vrod_index_get_tags(self.idx, first_id, n as u64, out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+
+    /// `search` with a tag predicate per query: query `q` sees only the live, allowed rows whose tags match `preds[q]`.
+    pub fn search_tagged(&self, queries: &[Vec<f32>], k: usize, preds: &[vrod_tag_pred]) -> Result<(Vec<u64>, Vec<f32>), ScanError> {
+        for q in queries {
+            if q.len() != self.dim {
+                return Err(ScanError::Dim { got: q.len(), want: self.dim });
+            }
+        }
+        if preds.len() != queries.len() {
+            return Err(ScanError::Dim { got: preds.len(), want: queries.len() });
+        }
+        let flat: Vec<f32> = queries.iter().flatten().copied().collect();
+        let mut ids = vec![0u64; queries.len() * k];
+        let mut scores = vec![0f32; queries.len() * k];
+        check(unsafe {
+            vrod_search_tagged(self.idx, flat.as_ptr(), queries.len() as u32, k as u32, preds.as_ptr(), ids.as_mut_ptr(), scores.as_mut_ptr())
         })?;
         Ok((ids, scores))
     }

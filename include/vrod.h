@@ -196,6 +196,17 @@ int vrod_index_filter_count(const vrod_index *idx, uint64_t *out);
  * nothing (get_labels reports the zeros every row carries). */
 int vrod_index_set_labels(vrod_index *idx, uint64_t first_id, const uint32_t *labels, uint64_t n);
 int vrod_index_get_labels(vrod_index *idx, uint64_t first_id, uint64_t n, uint32_t *out_labels);
+/* Row tags: every row carries one uint64_t tag mask -- 0 until set, and 0 for rows added later -- that only
+ * vrod_search_tagged reads (every other search ignores tags entirely; tags and labels are independent).  set_tags gives
+ * the rows with ids [first_id, first_id + n) (ids as searches report them, id_offset applied; deleted rows may be
+ * named) the masks tags[0 .. n) (host memory); a range that is not wholly within the current rows fails with
+ * VROD_ERR_INVALID_ARG and changes nothing; n == 0 does nothing.  vrod_index_update keeps a row's tags,
+ * vrod_index_delete leaves tags alone, vrod_index_compact moves them with their rows.  get_tags reads them back (host
+ * memory).  Tags cost nothing until first set: the device array is allocated by the first set_tags.  While a search is
+ * pending: VROD_ERR_INVALID_ARG.  Multi-device handles: set_tags returns VROD_ERR_UNSUPPORTED and changes nothing
+ * (get_tags reports the zeros every row carries). */
+int vrod_index_set_tags(vrod_index *idx, uint64_t first_id, const uint64_t *tags, uint64_t n);
+int vrod_index_get_tags(vrod_index *idx, uint64_t first_id, uint64_t n, uint64_t *out_tags);
 /* Copy prepared rows [first, first+n) back as fp32 (bf16 widened): n x dim. */
 int vrod_index_get_rows(vrod_index *idx, uint64_t first, uint64_t n, float *out_rows);
 
@@ -274,6 +285,34 @@ int vrod_search_labeled(vrod_index *idx, const float *queries, uint32_t nq, uint
 int vrod_search_labeled_device(vrod_index *idx, const float *d_queries, uint32_t nq, uint32_t k,
                                const uint32_t *d_query_labels, uint64_t *d_out_ids, float *d_out_scores,
                                void *stream);
+
+/* Tagged search -- one batch, a predicate over the row tags per query (attributes, access groups).  A row with tags t
+ * matches the predicate p iff
+ *     (p.any == 0 || (t & p.any) != 0)  &&  (t & p.all) == p.all  &&  (t & p.none) == 0,
+ * and query q sees the rows that are live, allowed by the handle's filter if one is set, and matching preds[q] (nq
+ * structs, host memory; the _device form: device memory, copied to the host to be grouped).  Labels are ignored.  Its
+ * result row is bit for bit (ids and score bits, a NaN matching any NaN) what vrod_search returns for that query on a
+ * fresh handle that holds only those rows, in order, with the ids mapped back: ties break by smaller id, slots beyond the
+ * matching rows are (VROD_ID_NONE, NaN).  A predicate with all & none != 0 can match nothing: an all-unfilled row, without
+ * a pass over the corpus.  {0, 0, 0} matches every row: the bits of vrod_search under the same filter and deletions.  A
+ * handle whose tags were never set holds 0 in every row.  k, null pointers and NaN / Inf in the queries are handled as
+ * vrod_search handles them; an empty handle gives all-unfilled rows without looking at the queries.  Synchronous, like
+ * the labelled search: no _begin_ form, no graph replay; VROD_ERR_INVALID_ARG while a search is pending; the _device form
+ * returns after the results are complete in device memory.  Queries with identical predicates form one group; every
+ * group's matching rows are counted on the device in one pass over the tag array per 2048 distinct predicates; a
+ * predicate with few rows has the canonical scores of its own rows computed (all such predicates of a pass in one
+ * launch; a row is scored once for every such predicate it matches), a predicate with a large share of the rows takes
+ * the ordinary scan with the other rows masked -- one scan per distinct wide predicate (vrod_index_set_path: GATHER
+ * sends every predicate the first way, STREAM / MFMA / EXACT the second).  vrod_index_last_stats afterwards: as after
+ * vrod_search_labeled, with "predicate" for "label".  Multi-device handles: VROD_ERR_UNSUPPORTED, outputs untouched. */
+typedef struct {
+    uint64_t any, all, none;
+} vrod_tag_pred; /* 24 bytes, no padding */
+int vrod_search_tagged(vrod_index *idx, const float *queries, uint32_t nq, uint32_t k,
+                       const vrod_tag_pred *preds, uint64_t *out_ids, float *out_scores);
+int vrod_search_tagged_device(vrod_index *idx, const float *d_queries, uint32_t nq, uint32_t k,
+                              const vrod_tag_pred *d_preds, uint64_t *d_out_ids, float *d_out_scores,
+                              void *stream);
 
 /* Grouped search -- the best row of each label, the k best labels per query (a document stored as many chunk rows that
  * share a label: the k best documents, not k chunks of one).  The ELIGIBLE rows of a query are the rows that are live

@@ -25,6 +25,7 @@ SYMBOLS = [
     "vrod_index_set_labels", "vrod_index_get_labels", "vrod_search_labeled", "vrod_search_labeled_device",
     "vrod_search_grouped", "vrod_search_grouped_device",
     "vrod_search_by_ids", "vrod_search_by_ids_device", "vrod_knn_graph",
+    "vrod_index_set_tags", "vrod_index_get_tags", "vrod_search_tagged", "vrod_search_tagged_device",
 ]
 
 ERR_CAPACITY = 8   # VROD_ERR_CAPACITY: a range search's result does not fit the caller's buffers (out_lims is valid)
@@ -105,6 +106,10 @@ def load() -> C.CDLL:
     L.vrod_index_get_labels.argtypes = [vp, u64, u64, vp]
     L.vrod_search_labeled.argtypes = [vp, vp, u32, u32, vp, vp, vp]
     L.vrod_search_labeled_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
+    L.vrod_index_set_tags.argtypes = [vp, u64, vp, u64]
+    L.vrod_index_get_tags.argtypes = [vp, u64, u64, vp]
+    L.vrod_search_tagged.argtypes = [vp, vp, u32, u32, vp, vp, vp]
+    L.vrod_search_tagged_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
     L.vrod_search_grouped.argtypes = [vp, vp, u32, u32, vp, vp, vp]
     L.vrod_search_grouped_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
     L.vrod_search_by_ids.argtypes = [vp, vp, u32, u32, u32, vp, vp]

@@ -132,6 +132,11 @@ void launch_label_group_count(const uint32_t* d_labels, const uint32_t* d_mask, 
     label_prefix_kernel<<<(G + 63) / 64, dim3(64, 16), 0, s>>>(d_cnt, n_blocks, G, d_total);
 }
 
+void launch_group_prefix(uint32_t* d_cnt, uint32_t n_blocks, uint32_t G, uint32_t* d_total, hipStream_t s) {
+    if (!G || !n_blocks) return;
+    label_prefix_kernel<<<(G + 63) / 64, dim3(64, 16), 0, s>>>(d_cnt, n_blocks, G, d_total);
+}
+
 void launch_label_group_scatter(const uint32_t* d_labels, const uint32_t* d_mask, uint64_t count, uint32_t rows_per_block,
                                 const uint32_t* d_table, uint32_t G, uint32_t* d_cnt, const uint32_t* d_seg_off, uint32_t* d_lists,
                                 hipStream_t s) {

@@ -34,6 +34,7 @@
 #include "search_plan.h"
 #include "compact_plan.h"
 #include "label_plan.h"
+#include "tag_plan.h"
 #include "group_plan.h"
 #include "byid_plan.h"
 
@@ -214,8 +215,14 @@ struct vrod_index {
     // window, gather list, graphs) is bypassed under it, never refreshed.
     const uint32_t* mask_ovr = nullptr;
     uint64_t elig_ovr = 0;
+    // row tags (vrod_index_set_tags): one 64-bit mask per row of the capacity, kept exactly as the labels are -- host
+    // mirror and device copy allocated at the first set_tags, 0 for rows at or beyond the count.  Only
+    // vrod_search_tagged reads them; a handle that never set one treats every row as 0.
+    std::vector<uint64_t> tag_bits;    // [capacity] once tags exist
+    uint64_t* tag_dev = nullptr;       // [capacity] on the device, or null
     // labelled search workspaces: [table | totals | segment offsets], the per-block counts, the row lists, the per-slot
-    // arrays, the work table, a dense group's mask / raw queries / results, the host form's raw queries
+    // arrays, the work table, a dense group's mask / raw queries / results, the host form's raw queries.  A tagged
+    // search, which is synchronous too, uses the same buffers for the same things (its table holds predicates).
     DevBuf lab_tab, lab_cnt, lab_lists, lab_slots, lab_entries, lab_mask, lab_q, lab_ids, lab_scores, lab_qraw;
     // grouped search workspaces (vrod_search_grouped): the candidate lists [lists][k1], the per-query words [found | valid |
     // the lists' queries], the dense stage's masks [<= 8][capacity / 32], the labels of the results when the caller
@@ -383,9 +390,27 @@ static int index_reserve(vrod_index* idx, uint64_t n_rows) {
             return fail(VROD_ERR_HIP, "growing the row labels failed: %s", hipGetErrorString(le));
         }
     }
+    uint64_t* nt = nullptr;   // so do the tags
+    if (idx->tag_dev) {
+        hipError_t te = hipMalloc((void**)&nt, want * 8);
+        if (te == hipSuccess) te = hipMemsetAsync(nt, 0, want * 8, idx->stream);
+        if (te == hipSuccess) te = hipMemcpyAsync(nt, idx->tag_bits.data(), idx->count * 8, hipMemcpyHostToDevice, idx->stream);
+        if (te == hipSuccess) te = hipStreamSynchronize(idx->stream);
+        if (te != hipSuccess) {
+            (void)hipStreamSynchronize(idx->stream);
+            if (nt) (void)hipFree(nt);
+            if (nl) (void)hipFree(nl);
+            if (ne) (void)hipFree(ne);
+            if (nd) (void)hipFree(nd);
+            (void)hipFree(nc);
+            (void)hipFree(nx);
+            return fail(VROD_ERR_HIP, "growing the row tags failed: %s", hipGetErrorString(te));
+        }
+    }
     if (idx->corpus) (void)hipFree(idx->corpus);
     if (idx->xnorm2) (void)hipFree(idx->xnorm2);
     if (idx->planes) { (void)hipFree(idx->planes); idx->planes = nullptr; idx->planes_cap = idx->planes_rows = 0; }   // rebuilt lazily
+    if (idx->tag_dev) { (void)hipFree(idx->tag_dev); idx->tag_dev = nt; idx->tag_bits.resize(want, 0ull); }
     if (idx->lab_dev) { (void)hipFree(idx->lab_dev); idx->lab_dev = nl; idx->lab_bits.resize(want, 0u); }
     if (idx->del_dev) { (void)hipFree(idx->del_dev); idx->del_dev = nd; }
     idx->del_bits.resize(want / 32, 0u);
@@ -549,6 +574,13 @@ static int index_compact(vrod_index* idx, uint64_t* out_new_ids) {
         for (uint64_t r = 0; r < count; ++r)
             if (!bit_of(del, r)) new_lab[j++] = idx->lab_bits[r];
     }
+    std::vector<uint64_t> new_tag;   // and so do the tags
+    if (idx->tag_dev) {
+        new_tag.assign(count, 0ull);
+        uint64_t j = 0;
+        for (uint64_t r = 0; r < count; ++r)
+            if (!bit_of(del, r)) new_tag[j++] = idx->tag_bits[r];
+    }
     uint64_t stage_rows = 0;
     for (const CompactChunk& c : plan.chunks) if (c.staged) stage_rows = std::max(stage_rows, c.L);
     if (stage_rows) {
@@ -582,6 +614,7 @@ static int index_compact(vrod_index* idx, uint64_t* out_new_ids) {
     if (e == hipSuccess) e = hipMemsetAsync(idx->del_dev, 0, cap_words * 4, s);
     if (e == hipSuccess && idx->filter_on) e = hipMemcpyAsync(idx->eff_dev, new_eff.data(), cap_words * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && idx->lab_dev) e = hipMemcpyAsync(idx->lab_dev, new_lab.data(), count * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && idx->tag_dev) e = hipMemcpyAsync(idx->tag_dev, new_tag.data(), count * 8, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess)
         return fail(VROD_ERR_HIP, "vrod_index_compact: %s while rows were moving: the handle is unusable, destroy it", hipGetErrorString(e));
@@ -592,6 +625,7 @@ static int index_compact(vrod_index* idx, uint64_t* out_new_ids) {
     idx->count = plan.live;
     if (idx->filter_on) { idx->allow_bits.swap(new_allow); idx->eff_bits.swap(new_eff); }   // n_eligible: the same rows
     if (idx->lab_dev) std::copy(new_lab.begin(), new_lab.end(), idx->lab_bits.begin());
+    if (idx->tag_dev) std::copy(new_tag.begin(), new_tag.end(), idx->tag_bits.begin());
     idx->planes_rows = 0;
     mask_changed(idx);
     return VROD_OK;
@@ -2384,22 +2418,10 @@ static void fold_stats(vrod_search_stats& st, const vrod_search_stats& d) {
     st.split_pass |= d.split_pass;
 }
 
-static int labeled_search(vrod_index* idx, const float* d_queries_raw, uint32_t nq, uint32_t k, const uint32_t* h_labels,
-                          uint64_t* d_out_ids, float* d_out_scores) {
-    vrod_search_stats st{};
-    st.nq = nq; st.k = k; st.path = VROD_PATH_GATHER;
-    const uint64_t N = idx->count;
-    const int form = score_form(idx->metric);
-    Pending& P = next_slot(idx);
+// The three steps a labelled and a tagged search share (the second groups by predicate, not by label).
+// Prepare the batch's queries into P.q_f32 as a search does; NaN / Inf fails the call before anything is scored.
+static int prep_group_queries(vrod_index* idx, Pending& P, const float* d_queries_raw, uint32_t nq) {
     hipStream_t s = P.stream;
-    if (N == 0) {   // an empty handle: every slot unfilled, as vrod_search
-        launch_fill_none(d_out_ids, d_out_scores, (uint64_t)nq * k, s);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(s));
-        idx->stats = st;
-        return VROD_OK;
-    }
-    // ---- prepare the queries as a search does; NaN / Inf fails the call before anything is scored
     P.plan = SearchPlan{};
     P.plan.nq_pad = nq;
     VROD_TRY(P.q_f32.ensure((size_t)nq * idx->ld * 4));
@@ -2415,6 +2437,94 @@ static int labeled_search(vrod_index* idx, const float* d_queries_raw, uint32_t 
     HIP_TRY(hipMemcpyAsync(&bad, B.readback + nq, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (bad) return fail(VROD_ERR_INVALID_VALUE, "queries contain NaN or Inf");
+    return VROD_OK;
+}
+
+// The segmented route of one pass: `segs` over the row lists in idx->lab_lists (enqueued on the slot's stream already),
+// slot s = query slot_q[s] over slot_len[s] rows from slot_base[s] on; d_slot: 3 * nq words of device memory.  Score +
+// select, one launch of each kind per chunk of the score block.  Returns with the stream drained.
+static int score_segments(vrod_index* idx, Pending& P, Timer& tm, vrod_search_stats& st, const std::vector<SegGroup>& segs,
+                          const std::vector<uint32_t>& slot_q, const std::vector<uint32_t>& slot_len, const std::vector<uint32_t>& slot_base,
+                          uint32_t* d_slot, uint32_t nq, uint32_t k, uint64_t* d_out_ids, float* d_out_scores) {
+    hipStream_t s = P.stream;
+    const int form = score_form(idx->metric);
+    uint32_t* d_slot_q = d_slot;
+    uint32_t* d_slot_len = d_slot_q + nq;
+    uint32_t* d_slot_base = d_slot_len + nq;
+    const uint32_t ns = (uint32_t)slot_q.size();
+    const SegPlan plan = plan_segments(segs);
+    VROD_TRY(idx->lab_entries.ensure(std::max<size_t>(plan.entries.size(), 1) * sizeof(SegEntry)));
+    HIP_TRY(hipMemcpyAsync(d_slot_q, slot_q.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_slot_len, slot_len.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_slot_base, slot_base.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s));
+    if (!plan.entries.empty())
+        HIP_TRY(hipMemcpyAsync(idx->lab_entries.p, plan.entries.data(), plan.entries.size() * sizeof(SegEntry), hipMemcpyHostToDevice, s));
+    for (const SegChunk& c : plan.chunks) {
+        const uint64_t n_sel = std::max<uint32_t>(c.max_m, 1);
+        const uint64_t out_ld = round_up(n_sel, 64);
+        VROD_TRY(P.scores.ensure((size_t)c.n_slots * out_ld * 4));
+        if (c.n_blocks) {
+            size_t a = 0, b = 0;
+            if (idx->profiling) {   // (markers around the launch, as the gather path)
+                tm.arm(a, b);
+                g_launch_events = LaunchEvents{};
+                if (b) HIP_TRY(hipEventRecord(P.ev[a], s));
+            }
+            launch_rescore_segments(idx->corpus, idx->dtype, form, idx->dim, idx->ld, P.q_f32.as<float>(),
+                                    idx->lab_entries.as<SegEntry>() + c.e0, c.e1 - c.e0, c.n_blocks, d_slot_q, c.slot0,
+                                    idx->lab_lists.as<uint32_t>(), P.scores.as<float>(), out_ld, s);
+            if (idx->profiling && b) { HIP_TRY(hipEventRecord(P.ev[b], s)); P.scan_pairs.push_back({a, b}); }
+            st.scan_launches++;
+        }
+        const uint32_t kx = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(k, n_sel), kSelectChunk / 2);   // (the rest: unfilled)
+        const uint64_t* keys; uint64_t kld, kn;
+        VROD_TRY(select_chain(idx, P, P.scores.as<float>(), out_ld, n_sel, (int)c.n_slots, kx, nullptr, &keys, &kld, &kn, d_slot_len + c.slot0));
+        launch_seg_keys_to_output(keys, kld, kn, (int)c.n_slots, form, k, idx->lab_lists.as<uint32_t>(), d_slot_base + c.slot0,
+                                  d_slot_q + c.slot0, idmap_of(idx), d_out_ids, d_out_scores, s);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(s));   // the next pass reuses the tables
+    return VROD_OK;
+}
+
+// The dense route of one group: the ordinary search flow over the batch's queries d_qidx[0 .. nqg) with the group's mask
+// (idx->lab_mask, enqueued on `s` already; m rows are clear in it) in place of row_mask(), the results scattered to the
+// queries' rows.  lab_q / lab_ids / lab_scores hold nqg queries.
+static int dense_group_search(vrod_index* idx, hipStream_t s, vrod_search_stats& st, const float* d_queries_raw, const uint32_t* d_qidx,
+                              const uint32_t* d_ones, uint32_t nqg, uint64_t m, uint32_t k, uint64_t* d_out_ids, float* d_out_scores) {
+    launch_gather_rows(d_queries_raw, d_qidx, nqg, idx->dim, idx->lab_q.as<float>(), s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    idx->mask_ovr = idx->lab_mask.as<uint32_t>();
+    idx->elig_ovr = m;
+    const int rc = run_search(idx, idx->lab_q.as<float>(), nqg, k, idx->lab_ids.as<uint64_t>(), idx->lab_scores.as<float>());
+    idx->mask_ovr = nullptr;
+    idx->elig_ovr = 0;
+    if (rc != VROD_OK) return rc;
+    fold_stats(st, idx->stats);
+    st.scan_bytes += (double)idx->count * idx->ld * idx->esize;
+    st.scan_flops += 2.0 * nqg * (double)idx->count * idx->dim;
+    launch_scatter_results(idx->lab_ids.as<uint64_t>(), idx->lab_scores.as<float>(), d_qidx, d_ones, nqg, k, d_out_ids, d_out_scores, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    return VROD_OK;
+}
+
+static int labeled_search(vrod_index* idx, const float* d_queries_raw, uint32_t nq, uint32_t k, const uint32_t* h_labels,
+                          uint64_t* d_out_ids, float* d_out_scores) {
+    vrod_search_stats st{};
+    st.nq = nq; st.k = k; st.path = VROD_PATH_GATHER;
+    const uint64_t N = idx->count;
+    Pending& P = next_slot(idx);
+    hipStream_t s = P.stream;
+    if (N == 0) {   // an empty handle: every slot unfilled, as vrod_search
+        launch_fill_none(d_out_ids, d_out_scores, (uint64_t)nq * k, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(s));
+        idx->stats = st;
+        return VROD_OK;
+    }
+    VROD_TRY(prep_group_queries(idx, P, d_queries_raw, nq));
 
     // ---- groups, and the per-slot arrays of the segmented route (filled as the passes route their groups)
     const LabelGroups G = label_groups(h_labels, nq);
@@ -2428,9 +2538,7 @@ static int labeled_search(vrod_index* idx, const float* d_queries_raw, uint32_t 
     VROD_TRY(idx->lab_slots.ensure((size_t)nq * 4 * 5));
     uint32_t* d_qorder = idx->lab_slots.as<uint32_t>();
     uint32_t* d_ones = d_qorder + nq;
-    uint32_t* d_slot_q = d_ones + nq;
-    uint32_t* d_slot_len = d_slot_q + nq;
-    uint32_t* d_slot_base = d_slot_len + nq;
+    uint32_t* d_slot_q = d_ones + nq;   // [slot_q | slot_len | slot_base] of score_segments
     {
         std::vector<uint32_t> up(G.q_order);
         up.resize((size_t)nq * 2, 1u);
@@ -2474,46 +2582,13 @@ static int labeled_search(vrod_index* idx, const float* d_queries_raw, uint32_t 
         }
         if (segs.empty()) continue;
         // ---- pass 2: the segmented groups' row lists, ascending
-        const uint32_t ns = (uint32_t)slot_q.size();
-        const SegPlan plan = plan_segments(segs);
         VROD_TRY(idx->lab_lists.ensure(std::max<uint64_t>(list_n, 1) * 4));
-        VROD_TRY(idx->lab_entries.ensure(std::max<size_t>(plan.entries.size(), 1) * sizeof(SegEntry)));
         HIP_TRY(hipMemcpyAsync(d_seg_off, seg_off.data(), (size_t)Gp * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_slot_q, slot_q.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_slot_len, slot_len.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_slot_base, slot_base.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s));
-        if (!plan.entries.empty())
-            HIP_TRY(hipMemcpyAsync(idx->lab_entries.p, plan.entries.data(), plan.entries.size() * sizeof(SegEntry), hipMemcpyHostToDevice, s));
         if (list_n)
             launch_label_group_scatter(idx->lab_dev, base_mask, N, rpb, d_table, Gp, idx->lab_cnt.as<uint32_t>(), d_seg_off,
                                        idx->lab_lists.as<uint32_t>(), s);
         HIP_TRY(hipGetLastError());
-        // ---- score + select, one launch of each kind per chunk of the score block
-        for (const SegChunk& c : plan.chunks) {
-            const uint64_t n_sel = std::max<uint32_t>(c.max_m, 1);
-            const uint64_t out_ld = round_up(n_sel, 64);
-            VROD_TRY(P.scores.ensure((size_t)c.n_slots * out_ld * 4));
-            if (c.n_blocks) {
-                size_t a = 0, b = 0;
-                if (idx->profiling) {   // (markers around the launch, as the gather path)
-                    tm.arm(a, b);
-                    g_launch_events = LaunchEvents{};
-                    if (b) HIP_TRY(hipEventRecord(P.ev[a], s));
-                }
-                launch_rescore_segments(idx->corpus, idx->dtype, form, idx->dim, idx->ld, P.q_f32.as<float>(),
-                                        idx->lab_entries.as<SegEntry>() + c.e0, c.e1 - c.e0, c.n_blocks, d_slot_q, c.slot0,
-                                        idx->lab_lists.as<uint32_t>(), P.scores.as<float>(), out_ld, s);
-                if (idx->profiling && b) { HIP_TRY(hipEventRecord(P.ev[b], s)); P.scan_pairs.push_back({a, b}); }
-                st.scan_launches++;
-            }
-            const uint32_t kx = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(k, n_sel), kSelectChunk / 2);   // (the rest: unfilled)
-            const uint64_t* keys; uint64_t kld, kn;
-            VROD_TRY(select_chain(idx, P, P.scores.as<float>(), out_ld, n_sel, (int)c.n_slots, kx, nullptr, &keys, &kld, &kn, d_slot_len + c.slot0));
-            launch_seg_keys_to_output(keys, kld, kn, (int)c.n_slots, form, k, idx->lab_lists.as<uint32_t>(), d_slot_base + c.slot0,
-                                      d_slot_q + c.slot0, idmap_of(idx), d_out_ids, d_out_scores, s);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipStreamSynchronize(s));   // the next pass reuses the tables
+        VROD_TRY(score_segments(idx, P, tm, st, segs, slot_q, slot_len, slot_base, d_slot_q, nq, k, d_out_ids, d_out_scores));
     }
     HIP_TRY(hipStreamSynchronize(s));
     if (idx->profiling)
@@ -2532,21 +2607,133 @@ static int labeled_search(vrod_index* idx, const float* d_queries_raw, uint32_t 
             const uint32_t nqg = G.nq_of(d.g);
             const uint32_t* d_qidx = d_qorder + G.q_off[d.g];
             launch_label_group_mask(idx->lab_dev, base_mask, N, words, G.labels[d.g], idx->lab_mask.as<uint32_t>(), s);
-            launch_gather_rows(d_queries_raw, d_qidx, nqg, idx->dim, idx->lab_q.as<float>(), s);
+            VROD_TRY(dense_group_search(idx, s, st, d_queries_raw, d_qidx, d_ones, nqg, d.m, k, d_out_ids, d_out_scores));
+        }
+    }
+    idx->stats = st;
+    return VROD_OK;
+}
+
+// ------------------------------------------------------------------ tagged search (vrod_search_tagged)
+// Query q sees the eligible rows (live, allowed) whose tags match h_preds[q].  The labelled search with two differences
+// (tag_plan.h, kernels_tag.hip): a group is a distinct predicate, and a row belongs to every group it matches.  So every
+// chunk of kTagGroupsPerPass groups is counted first -- one pass over the tag array, into a [blocks][groups] matrix --
+// and its groups routed by filter_route on their counts; then the chunk's narrow groups' row lists are written and
+// scored in passes whose lists stay under the 1 GiB rule (their sum is not bounded by the corpus), each pass one
+// segmented score launch per score chunk; after the last chunk the wide groups take one masked ordinary search each.  Queries whose predicate no row can match
+// (all & none != 0) are in no group: their result rows are filled as unfilled and nothing else looks at them.
+// Synchronous: the handle is idle before and after.  d_queries_raw / d_out_*: device memory, h_preds: host.
+static int tagged_search(vrod_index* idx, const float* d_queries_raw, uint32_t nq, uint32_t k, const TagPred* h_preds, uint64_t* d_out_ids,
+                         float* d_out_scores) {
+    vrod_search_stats st{};
+    st.nq = nq; st.k = k; st.path = VROD_PATH_GATHER;
+    const uint64_t N = idx->count;
+    Pending& P = next_slot(idx);
+    hipStream_t s = P.stream;
+    if (N == 0) {   // an empty handle: every slot unfilled, as vrod_search
+        launch_fill_none(d_out_ids, d_out_scores, (uint64_t)nq * k, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(s));
+        idx->stats = st;
+        return VROD_OK;
+    }
+    VROD_TRY(prep_group_queries(idx, P, d_queries_raw, nq));
+
+    const TagGroups G = tag_groups(h_preds, nq);
+    const uint32_t Gn = G.size();
+    if (G.n_unsatisfiable()) {   // (the groups' queries overwrite their own rows below)
+        launch_fill_none(d_out_ids, d_out_scores, (uint64_t)nq * k, s);
+        HIP_TRY(hipGetLastError());
+    }
+    if (!Gn) {
+        HIP_TRY(hipStreamSynchronize(s));
+        idx->stats = st;
+        return VROD_OK;
+    }
+    const uint32_t* base_mask = idx->row_mask();
+    const uint32_t rpb = label_rows_per_block(N);
+    const uint32_t n_blocks = (uint32_t)((N + rpb - 1) / rpb);
+    const double row_bytes = (double)idx->ld * idx->esize;
+    // device copy of q_order (a dense group's queries, and the scatter of its results) followed by as many ones, then the
+    // per-slot arrays of the segmented route
+    VROD_TRY(idx->lab_slots.ensure((size_t)nq * 4 * 5));
+    uint32_t* d_qorder = idx->lab_slots.as<uint32_t>();
+    uint32_t* d_ones = d_qorder + nq;
+    uint32_t* d_slot = d_ones + nq;
+    // [predicates | totals | a pass's segment offsets] and the count matrix [blocks][groups] of ONE chunk of
+    // kTagGroupsPerPass groups: the workspace does not grow with the batch's distinct predicates
+    const uint32_t Gc = std::min(Gn, kTagGroupsPerPass);
+    VROD_TRY(idx->lab_tab.ensure((size_t)Gc * (sizeof(TagPred) + 8)));
+    VROD_TRY(idx->lab_cnt.ensure((size_t)n_blocks * Gc * 4));
+    TagPred* d_table = idx->lab_tab.as<TagPred>();
+    uint32_t* d_total = (uint32_t*)(d_table + Gc);
+    uint32_t* d_seg_off = d_total + Gc;
+    uint32_t* d_cnt = idx->lab_cnt.as<uint32_t>();
+    std::vector<uint32_t> m(Gn);
+    std::vector<uint8_t> narrow(Gn);
+    {
+        std::vector<uint32_t> up(G.q_order);
+        up.resize((size_t)nq * 2, 1u);
+        HIP_TRY(hipMemcpyAsync(d_qorder, up.data(), up.size() * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    Timer tm(idx, P);
+    P.ev_used = 0; P.scan_pairs.clear(); P.sample_pair = -1; P.tail_pair = -1;
+    for (uint32_t c0 = 0; c0 < Gn; c0 += kTagGroupsPerPass) {
+        const uint32_t Gp = std::min(kTagGroupsPerPass, Gn - c0);
+        // ---- pass 1: the chunk's groups' eligible matching rows, counted per block of the tag array
+        HIP_TRY(hipMemcpyAsync(d_table, G.preds.data() + c0, (size_t)Gp * sizeof(TagPred), hipMemcpyHostToDevice, s));
+        launch_tag_group_count(idx->tag_dev, base_mask, N, rpb, d_table, Gp, d_cnt, Gp, s);
+        launch_group_prefix(d_cnt, n_blocks, Gp, d_total, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(m.data() + c0, d_total, (size_t)Gp * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        // ---- route
+        for (uint32_t g = c0; g < c0 + Gp; ++g) narrow[g] = filter_route(idx->path, idx->dtype, N, m[g], G.nq_of(g), idx->dim);
+        const std::vector<uint32_t> mc(m.begin() + c0, m.begin() + c0 + Gp);
+        const std::vector<uint8_t> nc(narrow.begin() + c0, narrow.begin() + c0 + Gp);
+        // ---- pass 2 per scatter pass: the narrow groups' row lists, ascending, then score + select
+        for (const TagPass& tp : plan_tag_passes(mc, nc)) {
+            std::vector<SegGroup> segs;
+            std::vector<uint32_t> slot_q, slot_len, slot_base;
+            for (uint32_t i = tp.g0; i < tp.g1; ++i) {
+                const uint32_t g = c0 + i, base = tp.seg_off[i - tp.g0], nqg = G.nq_of(g);
+                if (base == kNoSegment) continue;
+                segs.push_back({base, m[g], (uint32_t)slot_q.size(), nqg});
+                for (uint32_t j = 0; j < nqg; ++j) {
+                    slot_q.push_back(G.q_order[G.q_off[g] + j]);
+                    slot_len.push_back(m[g]);
+                    slot_base.push_back(base);
+                }
+                st.scan_bytes += (double)m[g] * row_bytes;
+                st.scan_flops += 2.0 * nqg * (double)m[g] * idx->dim;
+            }
+            VROD_TRY(idx->lab_lists.ensure(std::max<uint64_t>(tp.list_n, 1) * 4));
+            HIP_TRY(hipMemcpyAsync(d_seg_off, tp.seg_off.data(), (size_t)(tp.g1 - tp.g0) * 4, hipMemcpyHostToDevice, s));
+            if (tp.list_n)
+                launch_tag_group_scatter(idx->tag_dev, base_mask, N, rpb, d_table + tp.g0, tp.g1 - tp.g0, d_cnt + tp.g0, Gp, d_seg_off,
+                                         idx->lab_lists.as<uint32_t>(), s);
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipStreamSynchronize(s));
-            idx->mask_ovr = idx->lab_mask.as<uint32_t>();
-            idx->elig_ovr = d.m;
-            const int rc = run_search(idx, idx->lab_q.as<float>(), nqg, k, idx->lab_ids.as<uint64_t>(), idx->lab_scores.as<float>());
-            idx->mask_ovr = nullptr;
-            idx->elig_ovr = 0;
-            if (rc != VROD_OK) return rc;
-            fold_stats(st, idx->stats);
-            st.scan_bytes += (double)N * row_bytes;
-            st.scan_flops += 2.0 * nqg * (double)N * idx->dim;
-            launch_scatter_results(idx->lab_ids.as<uint64_t>(), idx->lab_scores.as<float>(), d_qidx, d_ones, nqg, k, d_out_ids, d_out_scores, s);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipStreamSynchronize(s));
+            VROD_TRY(score_segments(idx, P, tm, st, segs, slot_q, slot_len, slot_base, d_slot, nq, k, d_out_ids, d_out_scores));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    if (idx->profiling)
+        for (size_t i = 0; i < P.scan_pairs.size(); ++i) st.scan_ms += tm.ms(P.scan_pairs[i].first, P.scan_pairs[i].second);
+
+    // ---- wide groups: one ordinary search each, over the predicate's mask
+    uint32_t max_nq = 0;
+    for (uint32_t g = 0; g < Gn; ++g) if (!narrow[g]) max_nq = std::max(max_nq, G.nq_of(g));
+    if (max_nq) {
+        const uint64_t words = idx->del_bits.size();   // capacity / 32
+        VROD_TRY(idx->lab_mask.ensure(words * 4));
+        VROD_TRY(idx->lab_q.ensure((size_t)max_nq * idx->dim * 4));
+        VROD_TRY(idx->lab_ids.ensure((size_t)max_nq * k * 8));
+        VROD_TRY(idx->lab_scores.ensure((size_t)max_nq * k * 4));
+        for (uint32_t g = 0; g < Gn; ++g) {
+            if (narrow[g]) continue;
+            launch_tag_group_mask(idx->tag_dev, base_mask, N, words, G.preds[g], idx->lab_mask.as<uint32_t>(), s);
+            VROD_TRY(dense_group_search(idx, s, st, d_queries_raw, d_qorder + G.q_off[g], d_ones, G.nq_of(g), m[g], k, d_out_ids, d_out_scores));
         }
     }
     idx->stats = st;
@@ -2988,6 +3175,7 @@ int vrod_index_destroy(vrod_index* idx) {
     if (idx->eff_dev) (void)hipFree(idx->eff_dev);
     idx->list_dev.release();
     if (idx->lab_dev) (void)hipFree(idx->lab_dev);
+    if (idx->tag_dev) (void)hipFree(idx->tag_dev);
     for (DevBuf* b : {&idx->lab_tab, &idx->lab_cnt, &idx->lab_lists, &idx->lab_slots, &idx->lab_entries, &idx->lab_mask, &idx->lab_q, &idx->lab_ids,
                       &idx->lab_scores, &idx->lab_qraw, &idx->grp_ids, &idx->grp_scores, &idx->grp_small, &idx->grp_mask, &idx->grp_labels,
                       &idx->grp_qraw, &idx->byid_user_ids}) b->release();
@@ -3292,6 +3480,78 @@ int vrod_search_labeled_device(vrod_index* idx, const float* d_queries, uint32_t
     std::vector<uint32_t> labels(nq);
     HIP_TRY(hipMemcpy(labels.data(), d_query_labels, (size_t)nq * 4, hipMemcpyDeviceToHost));
     return labeled_search(idx, d_queries, nq, k, labels.data(), d_out_ids, d_out_scores);
+}
+
+int vrod_index_set_tags(vrod_index* idx, uint64_t first_id, const uint64_t* tags, uint64_t n) {
+    if (!idx || (!tags && n)) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "vrod_index_set_tags on a multi-device handle: tags are not routed to the shards");
+    VROD_TRY(require_idle(idx, "vrod_index_set_tags"));
+    if (first_id < idx->id_offset || first_id - idx->id_offset > idx->count || n > idx->count - (first_id - idx->id_offset))
+        return fail(VROD_ERR_INVALID_ARG, "ids [%llu, %llu) are not all rows of this handle (ids %llu..%llu)", (unsigned long long)first_id,
+                    (unsigned long long)(first_id + n), (unsigned long long)idx->id_offset, (unsigned long long)(idx->id_offset + idx->count));
+    if (!n) return VROD_OK;
+    VROD_TRY(set_device(idx));
+    const uint64_t r0 = first_id - idx->id_offset;
+    if (!idx->tag_dev) {   // the first tags of the handle: every row carries 0 so far
+        uint64_t* d = nullptr;
+        HIP_TRY(hipMalloc((void**)&d, idx->capacity * 8));
+        const hipError_t e = hipMemset(d, 0, idx->capacity * 8);
+        if (e != hipSuccess) { (void)hipFree(d); return fail(VROD_ERR_HIP, "clearing the row tags: %s", hipGetErrorString(e)); }
+        idx->tag_dev = d;
+        idx->tag_bits.assign(idx->capacity, 0ull);
+    }
+    HIP_TRY(hipMemcpy(idx->tag_dev + r0, tags, n * 8, hipMemcpyHostToDevice));
+    std::copy(tags, tags + n, idx->tag_bits.begin() + r0);
+    return VROD_OK;
+}
+
+int vrod_index_get_tags(vrod_index* idx, uint64_t first_id, uint64_t n, uint64_t* out_tags) {
+    if (!idx || (!out_tags && n)) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    if (first_id < idx->id_offset || first_id - idx->id_offset > idx->count || n > idx->count - (first_id - idx->id_offset))
+        return fail(VROD_ERR_INVALID_ARG, "ids [%llu, %llu) are not all rows of this handle (ids %llu..%llu)", (unsigned long long)first_id,
+                    (unsigned long long)(first_id + n), (unsigned long long)idx->id_offset, (unsigned long long)(idx->id_offset + idx->count));
+    const uint64_t r0 = first_id - idx->id_offset;
+    for (uint64_t i = 0; i < n; ++i) out_tags[i] = idx->tag_bits.empty() ? 0ull : idx->tag_bits[r0 + i];   // (the host mirror is the truth)
+    return VROD_OK;
+}
+
+static_assert(sizeof(vrod_tag_pred) == 24 && sizeof(TagPred) == 24, "vrod_tag_pred is three packed 64-bit words");
+
+static int check_tagged_args(vrod_index* idx, const void* q, uint32_t nq, uint32_t k, const void* preds, const void* oi, const void* os) {
+    VROD_TRY(check_search_args(idx, q, nq, k, oi, os));
+    if (nq && !preds) return fail(VROD_ERR_INVALID_ARG, "null buffer");
+    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "vrod_search_tagged on a multi-device handle: tags are not routed to the shards");
+    return VROD_OK;
+}
+
+int vrod_search_tagged(vrod_index* idx, const float* queries, uint32_t nq, uint32_t k, const vrod_tag_pred* preds, uint64_t* out_ids,
+                       float* out_scores) {
+    VROD_TRY(check_tagged_args(idx, queries, nq, k, preds, out_ids, out_scores));
+    if (!nq) return VROD_OK;
+    VROD_TRY(require_idle(idx, "vrod_search_tagged"));
+    VROD_TRY(set_device(idx));
+    VROD_TRY(idx->lab_qraw.ensure((size_t)nq * idx->dim * 4));
+    VROD_TRY(idx->out_ids.ensure((size_t)nq * k * 8));
+    VROD_TRY(idx->out_scores.ensure((size_t)nq * k * 4));
+    if (idx->count) HIP_TRY(hipMemcpy(idx->lab_qraw.p, queries, (size_t)nq * idx->dim * 4, hipMemcpyHostToDevice));
+    VROD_TRY(tagged_search(idx, idx->lab_qraw.as<float>(), nq, k, reinterpret_cast<const TagPred*>(preds), idx->out_ids.as<uint64_t>(),
+                           idx->out_scores.as<float>()));
+    HIP_TRY(hipMemcpy(out_ids, idx->out_ids.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_scores, idx->out_scores.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    return VROD_OK;
+}
+
+int vrod_search_tagged_device(vrod_index* idx, const float* d_queries, uint32_t nq, uint32_t k, const vrod_tag_pred* d_preds,
+                              uint64_t* d_out_ids, float* d_out_scores, void* stream) {
+    VROD_TRY(check_tagged_args(idx, d_queries, nq, k, d_preds, d_out_ids, d_out_scores));
+    if (!nq) return VROD_OK;
+    VROD_TRY(require_idle(idx, "vrod_search_tagged_device"));
+    VROD_TRY(set_device(idx));
+    // synchronous, as a labelled search: whatever the caller's stream holds is complete before the library's streams start
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    std::vector<TagPred> preds(nq);
+    HIP_TRY(hipMemcpy(preds.data(), d_preds, (size_t)nq * sizeof(TagPred), hipMemcpyDeviceToHost));
+    return tagged_search(idx, d_queries, nq, k, preds.data(), d_out_ids, d_out_scores);
 }
 
 static int check_grouped_args(vrod_index* idx, const void* q, uint32_t nq, uint32_t k, const void* oi, const void* os) {

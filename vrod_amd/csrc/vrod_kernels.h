@@ -6,6 +6,7 @@
 
 #include "search_plan.h"   // kSelectChunk
 #include "label_plan.h"    // SegEntry
+#include "tag_plan.h"      // TagPred
 
 namespace vrod {
 
@@ -219,6 +220,22 @@ void launch_label_group_mask(const uint32_t* d_labels, const uint32_t* d_mask, u
                              uint32_t* d_out, hipStream_t s);
 // d_dst row i = d_src row d_idx[i] (rows of dim floats)
 void launch_gather_rows(const float* d_src, const uint32_t* d_idx, uint32_t n, uint32_t dim, float* d_dst, hipStream_t s);
+
+// The prefix pass on its own: d_cnt [n_blocks][G] -> exclusive prefix over the blocks per group, d_total[g] = the sum.
+void launch_group_prefix(uint32_t* d_cnt, uint32_t n_blocks, uint32_t G, uint32_t* d_total, hipStream_t s);
+
+// ---- kernels_tag.hip : rows grouped by the tag predicates of a batch, one predicate's dense-scan mask
+// Pass 1: d_cnt[b * cnt_ld + g] (b < ceil(count / rows_per_block)) = the eligible rows (not set in d_mask, which may be
+// null) of block b whose tags match d_table[g], g < G <= kTagGroupsPerPass.  A row counts towards every group it
+// matches.  d_tags == null: every row carries 0.  launch_group_prefix over the whole matrix follows.
+void launch_tag_group_count(const uint64_t* d_tags, const uint32_t* d_mask, uint64_t count, uint32_t rows_per_block, const TagPred* d_table,
+                            uint32_t G, uint32_t* d_cnt, uint32_t cnt_ld, hipStream_t s);
+// Pass 2, over the prefixed counts: group g's rows, ascending, into d_lists[d_seg_off[g] ...] (kNoSegment: no list).
+void launch_tag_group_scatter(const uint64_t* d_tags, const uint32_t* d_mask, uint64_t count, uint32_t rows_per_block, const TagPred* d_table,
+                              uint32_t G, const uint32_t* d_cnt, uint32_t cnt_ld, const uint32_t* d_seg_off, uint32_t* d_lists, hipStream_t s);
+// d_out [n_words]: bit r set = row r is set in d_mask (may be null), does not match p, or r >= count.
+void launch_tag_group_mask(const uint64_t* d_tags, const uint32_t* d_mask, uint64_t count, uint64_t n_words, const TagPred& p, uint32_t* d_out,
+                           hipStream_t s);
 
 // ---- kernels_group.hip : a grouped search's de-duplication by label and the dense stage's per-query masks
 // List b (d_cand_ids / d_cand_scores + b * k1: a search's result row, ids with id_offset applied) of query d_qidx[b] (b

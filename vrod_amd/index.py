@@ -180,6 +180,33 @@ class Index:
         check(self._L.vrod_index_get_labels(self._h, int(first_id), int(n), out.ctypes.data_as(C.c_void_p)))
         return out
 
+    @staticmethod
+    def _u64(values, what, shape) -> np.ndarray:
+        """An integer array-like of 64-bit masks -> a contiguous uint64 array of `shape` (-1: any length)."""
+        a = np.asarray(values)
+        if a.dtype.kind not in "iu" and (a.size or isinstance(values, np.ndarray)):   # (an empty list has no dtype of its own)
+            raise TypeError(f"{what} must be an integer array, got {a.dtype}")
+        if a.dtype != np.uint64:
+            if a.size and int(a.min()) < 0:
+                raise ValueError(f"{what} must fit 64 unsigned bits")
+            a = a.astype(np.uint64)
+        try:
+            a = a.reshape(shape)
+        except ValueError:
+            raise ValueError(f"{what} must have shape {shape}, got {a.shape}") from None
+        return np.ascontiguousarray(a)
+
+    def set_tags(self, first_id: int, tags):
+        """Give the rows with ids first_id, first_id + 1, ... the 64-bit tag masks of an integer array-like
+        (vrod_index_set_tags).  Every row carries 0 until it is given tags; only search_tagged reads them."""
+        a = self._u64(tags, "tags", (-1,))
+        check(self._L.vrod_index_set_tags(self._h, int(first_id), a.ctypes.data_as(C.c_void_p), a.size))
+
+    def get_tags(self, first_id: int, n: int) -> np.ndarray:
+        out = np.empty(int(n), dtype=np.uint64)
+        check(self._L.vrod_index_get_tags(self._h, int(first_id), int(n), out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def set_id_offset(self, off: int):
         check(self._L.vrod_index_set_id_offset(self._h, int(off)))
         self._id_offset = int(off)
@@ -260,6 +287,43 @@ class Index:
         stream = torch.cuda.current_stream(d_queries.device).cuda_stream
         check(self._L.vrod_search_labeled_device(self._h, d_queries.data_ptr(), nq, int(k), d_labels.data_ptr(), out_ids.data_ptr(),
                                                  out_scores.data_ptr(), C.c_void_p(stream)))
+        return out_ids, out_scores
+
+    def search_tagged(self, queries: np.ndarray, k: int, preds):
+        """search() with a tag predicate per query (vrod_search_tagged): preds is [nq, 3] uint64, the columns any, all,
+        none; query q sees only the eligible rows whose tags t satisfy (any == 0 or t & any) and t & all == all and not
+        t & none.  numpy [nq, dim] fp32 -> (ids uint64 [nq, k], scores float32 [nq, k])."""
+        queries = np.ascontiguousarray(queries, dtype=np.float32)
+        if queries.ndim == 1:
+            queries = queries[None, :]
+        if queries.ndim != 2 or queries.shape[1] != self.dim:
+            raise ValueError(f"queries must be [nq, {self.dim}]")
+        nq = queries.shape[0]
+        p = self._u64(preds, "preds", (nq, 3))
+        ids = np.empty((nq, k), dtype=np.uint64)
+        sc = np.empty((nq, k), dtype=np.float32)
+        check(self._L.vrod_search_tagged(self._h, queries.ctypes.data_as(C.c_void_p), nq, int(k), p.ctypes.data_as(C.c_void_p),
+                                         ids.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p)))
+        return ids, sc
+
+    def search_tagged_device(self, d_queries, k: int, d_preds, out_ids=None, out_scores=None):
+        """torch CUDA tensors: queries [nq, dim] fp32, preds [nq, 3] int64 (the bits of uint64: any, all, none) -> (ids
+        int64-viewed-uint64 [nq, k], scores [nq, k]) on the device, complete on return."""
+        import torch
+        assert d_queries.is_cuda and d_queries.dtype == torch.float32 and d_queries.is_contiguous()
+        if d_preds.dtype != torch.int64:
+            raise TypeError(f"preds must be an int64 tensor, got {d_preds.dtype}")
+        nq = d_queries.shape[0]
+        if tuple(d_preds.shape) != (nq, 3):
+            raise ValueError(f"preds must be [{nq}, 3], got {tuple(d_preds.shape)}")
+        assert d_preds.is_cuda and d_preds.is_contiguous()
+        if out_ids is None:
+            out_ids = torch.empty((nq, k), dtype=torch.int64, device=d_queries.device)
+        if out_scores is None:
+            out_scores = torch.empty((nq, k), dtype=torch.float32, device=d_queries.device)
+        stream = torch.cuda.current_stream(d_queries.device).cuda_stream
+        check(self._L.vrod_search_tagged_device(self._h, d_queries.data_ptr(), nq, int(k), d_preds.data_ptr(), out_ids.data_ptr(),
+                                                out_scores.data_ptr(), C.c_void_p(stream)))
         return out_ids, out_scores
 
     def search_grouped(self, queries: np.ndarray, k: int):
