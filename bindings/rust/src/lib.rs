@@ -62,6 +62,23 @@ pub struct vrod_tag_pred {
     pub none: u64,
 }
 
+/// The most vectors one query of `vrod_search_multivec` may hold.
+pub const VROD_MAX_QUERY_VECTORS: u32 = 256;
+
+/// What the last `vrod_search_multivec` call did (`vrod_index_last_multivec`): `certified_queries` were answered by the
+/// candidate route, `dense_queries` by the dense route; `k1` is 0 when no first-stage search ran.
+#[repr(C)]
+#[derive(Debug, Default, Clone, Copy, PartialEq, Eq)]
+pub struct vrod_multivec_stats {
+    pub nq: u32,
+    pub vectors: u32,
+    pub k1: u32,
+    pub certified_queries: u32,
+    pub dense_queries: u32,
+    pub candidate_labels: u64,
+    pub candidate_rows: u64,
+}
+
 extern "C" {
     pub fn vrod_index_create(out: *mut *mut vrod_index, dim: u32, dtype: c_int, metric: c_int,
                              device_ids: *const c_int, n_devices: c_int) -> c_int;
@@ -136,6 +153,13 @@ extern "C" {
                                      d_out_ids: *mut u64, d_out_scores: *mut f32, stream: *mut c_void) -> c_int;
     pub fn vrod_knn_graph(idx: *mut vrod_index, first_id: u64, n: u64, k: u32, out_ids: *mut u64,
                           out_scores: *mut f32) -> c_int;
+    /// Query q owns vectors `query_lims[q] .. query_lims[q + 1]`; `out_found` may be null.
+    pub fn vrod_search_multivec(idx: *mut vrod_index, vectors: *const f32, query_lims: *const u32, nq: u32, k: u32,
+                                out_labels: *mut u32, out_scores: *mut f32, out_found: *mut u32) -> c_int;
+    pub fn vrod_search_multivec_device(idx: *mut vrod_index, d_vectors: *const f32, d_query_lims: *const u32, nq: u32,
+                                       k: u32, d_out_labels: *mut u32, d_out_scores: *mut f32, d_out_found: *mut u32,
+                                       stream: *mut c_void) -> c_int;
+    pub fn vrod_index_last_multivec(idx: *const vrod_index, out: *mut vrod_multivec_stats) -> c_int;
 }
 
 /// Joins the reference's `thiserror` enums (`src/main.rs:36-40`, `src/command/builder.rs:10-15`).

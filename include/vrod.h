@@ -340,6 +340,57 @@ int vrod_search_grouped(vrod_index *idx, const float *queries, uint32_t nq, uint
 int vrod_search_grouped_device(vrod_index *idx, const float *d_queries, uint32_t nq, uint32_t k,
                                uint64_t *d_out_ids, float *d_out_scores, uint32_t *d_out_labels, void *stream);
 
+/* Multi-vector search -- a query is a SET of vectors (several phrasings, query tokens, a late-interaction encoder's
+ * output), a document the rows that share a label, and each document is scored by MaxSim:
+ *     S(q, L) = sum over the query's vectors t, first to last, of M(t, L),
+ *     M(t, L) = the best canonical score of vector t over the ELIGIBLE rows of label L (live, and allowed while a filter is
+ *               set): the maximum for COSINE and IP, the minimum for L2; a NaN row score loses to any number, M is NaN only
+ *               if every eligible row of L scores NaN.
+ * S is an fp32 sum taken left to right from +0.0f, one rounding per add; under IP overflow it may be +-inf or NaN.
+ *   vectors     query_lims[nq] x dim fp32; every vector is prepared exactly as vrod_search prepares a query (normalised for
+ *               COSINE, bf16-rounded on BF16 handles); NaN or Inf anywhere: VROD_ERR_INVALID_VALUE.
+ *   query_lims  nq + 1 words: query q owns vectors [query_lims[q], query_lims[q + 1]).  query_lims[0] != 0, a decreasing
+ *               entry, a query with 0 or with more than VROD_MAX_QUERY_VECTORS vectors: VROD_ERR_INVALID_ARG.
+ *   result      row q of out_labels / out_scores (nq x k) holds the k best labels among those with at least one eligible
+ *               row -- the highest S for COSINE and IP, the lowest for L2, a NaN S last, ties by the smaller label -- and
+ *               their S; out_found[q] (out_found may be NULL) = the filled slots = min(k, labels with an eligible row); the
+ *               slots past it are (label 0, NaN).  Score bits are the CPU oracle's: its top-1 over each label's eligible
+ *               rows per vector, added in fp32 in order (a NaN matches any NaN).
+ * Labels are those of vrod_index_set_labels; a handle whose labels were never set is one document with label 0.  Tags are
+ * ignored.  k and null pointers are handled as vrod_search_grouped handles them; nq == 0: VROD_OK.  Every check comes before
+ * the first write: a refused call leaves the outputs untouched.  An empty handle, or one without an eligible row, gives
+ * all-unfilled rows without looking at the vectors, as vrod_search does.  Synchronous: no _begin_ form, no graph replay;
+ * VROD_ERR_INVALID_ARG while a search is pending; the _device form takes device pointers on the handle's device (query_lims
+ * included) and returns after the results are complete in device memory.  Multi-device handles: VROD_ERR_UNSUPPORTED, the
+ * outputs are not touched.
+ * Exact by one of two routes per query.  Candidate route: the ordinary certified search runs for every vector with k1
+ * results each (the grouped search's rule; a call with more than 2048 vectors is cut between queries); the labels of the
+ * rows in a query's lists are its candidates, the eligible rows of the candidates are scored against the query's vectors
+ * and S is ranked among them.  With theta_t the last score of vector t's full list, a label outside every list has
+ * M(t, L) no better than theta_t, and rounded addition is monotone, so U = the same fp32 sum of the theta_t bounds S of
+ * every other label: the answer stands when the query has k candidates and its k-th S is strictly better than U, or when
+ * one of its lists came back short (then every label is a candidate).  Dense route, for every other query -- a list with
+ * a NaN or infinite score, candidates that own more than a quarter of the rows, a failed certificate -- and for every
+ * query under VROD_PATH_EXACT or on a handle without labels: the canonical scores of every row, folded to the best per
+ * (vector, document) and added per document.  vrod_index_set_path is honoured by the first-stage search.
+ * vrod_index_last_stats afterwards, as after vrod_search_grouped: path = the first search's, or VROD_PATH_EXACT when every
+ * query went dense; nq = the queries (not the vectors); k as given; kprime = the first search's; fallback_queries = the
+ * first search's + the dense queries; scan_bytes / scan_flops = the first search's + the rows (x the vectors) of every
+ * candidate label scored + every stored row (x the query's vectors) per dense pass over the corpus (one per 8 vectors of a
+ * dense query), each such launch one more of scan_launches; scan_ms stays the first search's.
+ * vrod_index_last_multivec: what the last multi-vector call did -- which route answered (certified_queries + dense_queries
+ * = nq), k1 (0 when no first-stage search ran), and the candidate labels and rows scored, summed over the queries. */
+#define VROD_MAX_QUERY_VECTORS 256u
+typedef struct {
+    uint32_t nq, vectors, k1, certified_queries, dense_queries;
+    uint64_t candidate_labels, candidate_rows;
+} vrod_multivec_stats;
+int vrod_search_multivec(vrod_index *idx, const float *vectors, const uint32_t *query_lims, uint32_t nq, uint32_t k,
+                         uint32_t *out_labels, float *out_scores, uint32_t *out_found);
+int vrod_search_multivec_device(vrod_index *idx, const float *d_vectors, const uint32_t *d_query_lims, uint32_t nq, uint32_t k,
+                                uint32_t *d_out_labels, float *d_out_scores, uint32_t *d_out_found, void *stream);
+int vrod_index_last_multivec(const vrod_index *idx, vrod_multivec_stats *out);
+
 /* Search by stored row id ("more like this") -- query q is the PREPARED stored row ids[q] (nq ids as searches report
  * them, id_offset applied; host memory, the _device form: device memory), used as stored: it is not normalised again and
  * not rounded again, so the scores are scores between stored rows and an L2 row is at distance +0.0 from itself.  The

@@ -26,6 +26,7 @@ SYMBOLS = [
     "vrod_search_grouped", "vrod_search_grouped_device",
     "vrod_search_by_ids", "vrod_search_by_ids_device", "vrod_knn_graph",
     "vrod_index_set_tags", "vrod_index_get_tags", "vrod_search_tagged", "vrod_search_tagged_device",
+    "vrod_search_multivec", "vrod_search_multivec_device", "vrod_index_last_multivec",
 ]
 
 ERR_CAPACITY = 8   # VROD_ERR_CAPACITY: a range search's result does not fit the caller's buffers (out_lims is valid)
@@ -46,6 +47,16 @@ class SearchStats(C.Structure):
         ("max_fast_err", C.c_float), ("eps_bound", C.c_float),
         ("split_pass", C.c_uint32), ("band_queries", C.c_uint32), ("sample_ms", C.c_float), ("exchange", C.c_uint32),
         ("overlap_ms", C.c_float),
+    ]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class MultivecStats(C.Structure):
+    _fields_ = [
+        ("nq", C.c_uint32), ("vectors", C.c_uint32), ("k1", C.c_uint32), ("certified_queries", C.c_uint32),
+        ("dense_queries", C.c_uint32), ("candidate_labels", C.c_uint64), ("candidate_rows", C.c_uint64),
     ]
 
     def as_dict(self):
@@ -115,6 +126,9 @@ def load() -> C.CDLL:
     L.vrod_search_by_ids.argtypes = [vp, vp, u32, u32, u32, vp, vp]
     L.vrod_search_by_ids_device.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp]
     L.vrod_knn_graph.argtypes = [vp, u64, u64, u32, vp, vp]
+    L.vrod_search_multivec.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp]
+    L.vrod_search_multivec_device.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, vp]
+    L.vrod_index_last_multivec.argtypes = [vp, C.POINTER(MultivecStats)]
     for name in SYMBOLS:
         getattr(L, name).restype = i32
     L.vrod_last_error.restype = C.c_char_p

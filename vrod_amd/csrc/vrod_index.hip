@@ -36,12 +36,14 @@
 #include "label_plan.h"
 #include "tag_plan.h"
 #include "group_plan.h"
+#include "multivec_plan.h"
 #include "byid_plan.h"
 
 using namespace vrod;
 
 static_assert(kGroupMaxK == VROD_MAX_K, "group_plan.h restates the largest k of the ABI");
 static_assert(kByidMaxK == VROD_MAX_K, "byid_plan.h restates the largest k of the ABI");
+static_assert(kMultivecMaxK == VROD_MAX_K && kMultivecMaxVectors == VROD_MAX_QUERY_VECTORS, "multivec_plan.h restates the ABI's limits");
 
 // ------------------------------------------------------------------ errors
 static thread_local std::string g_last_error;
@@ -228,6 +230,19 @@ struct vrod_index {
     // the lists' queries], the dense stage's masks [<= 8][capacity / 32], the labels of the results when the caller
     // wants none, the host form's raw queries
     DevBuf grp_ids, grp_scores, grp_small, grp_mask, grp_labels, grp_qraw;
+    // multi-vector search (vrod_search_multivec).  The document index: doc_rank[row] = the rank of the row's label among
+    // the handle's distinct labels, ascending (doc_labels [n_docs]), built on the host from lab_bits at the first search
+    // that needs it and kept until set_labels, add or compact change what it was built from (update and delete do not);
+    // a handle without labels is one document, label 0, and has no rank array.  Then the workspaces: the prepared vectors
+    // of the whole call, the first-stage lists [vectors][k1], the de-duplication's entry labels / tables / candidate
+    // labels, the per-query words, the dense route's best [<= 8][n_docs] / S rows / absent bitmap, the candidate route's
+    // M per score slot and its pair arrays, and the host form's raw vectors and results.
+    DevBuf doc_rank, doc_labels;
+    uint64_t n_docs = 0;
+    bool doc_valid = false;
+    DevBuf mv_q, mv_ids, mv_scores, mv_ent, mv_tab, mv_cand, mv_small, mv_best, mv_S, mv_absent, mv_M, mv_pairs, mv_raw, mv_lims, mv_out_labels,
+        mv_out_scores, mv_found;
+    vrod_multivec_stats mv_stats{};
     // Searches whose queries are stored rows (vrod_search_by_ids, vrod_knn_graph) hand the search flow rows that are
     // prepared already: while prep_ovr is not negative it stands for prep_form(metric) in the launch that prepares a
     // search's queries -- M_L2, the take-as-given form of L2 and IP handles: nothing is normalised, and rounding a bf16
@@ -460,6 +475,7 @@ static int index_add(vrod_index* idx, const float* rows, uint64_t n, bool synthe
                      uint64_t first_row) {
     if (!n) return VROD_OK;
     VROD_TRY(set_device(idx));
+    idx->doc_valid = false;   // (the document index of a multi-vector search covers the rows it was built from)
     if (idx->count + n > idx->capacity) {
         uint64_t want = std::max(idx->count + n, idx->capacity + idx->capacity / 2);
         if (synthetic || idx->capacity == 0) want = idx->count + n;
@@ -547,6 +563,7 @@ static void mask_changed(vrod_index* idx);
 // split the compacted rows again, which gives the bits a fresh handle's planes hold.
 // Everything that can fail comes before the first row moves; a HIP error after that leaves the handle unusable.
 static int index_compact(vrod_index* idx, uint64_t* out_new_ids) {
+    idx->doc_valid = false;   // (rows move, labels may vanish: the document index is rebuilt by the next multi-vector search)
     const uint64_t count = idx->count;
     if (!idx->n_deleted) {
         if (out_new_ids) compact_new_ids(idx->del_bits.data(), count, idx->id_offset, out_new_ids);   // the identity
@@ -2886,6 +2903,391 @@ static int grouped_search(vrod_index* idx, const float* d_queries_raw, uint32_t 
     return VROD_OK;
 }
 
+// ------------------------------------------------------------------ multi-vector search (vrod_search_multivec)
+// A query is the vectors [lims[q], lims[q + 1]) of the call, a document the eligible rows of one label, and
+//     S(q, L) = M(first, L) + ... + M(last, L)   (fp32, from +0, left to right),  M(t, L) = the best canonical score of
+// vector t over the document's rows; the k best documents per query, ties by the smaller label.  Two routes:
+//   candidate route (multivec_candidates): the ordinary certified search for every vector of a sub-batch with k1 results
+//     each; a query's candidates are the labels in any of its lists, de-duplicated on the device; their rows are grouped
+//     by label (the labelled search's passes), scored against the vectors of every query that holds the label as a
+//     candidate in the segmented launch, reduced to M per score slot and to S per (query, candidate), and ranked by the
+//     select chain.  The answer stands when multivec_plan.h's certificate holds;
+//   dense route (multivec_dense), for every other query and for all of them under VROD_PATH_EXACT: the canonical scores
+//     of every row against up to 8 vectors at a time, folded into best[vector][document] and added into S[document]
+//     group after group -- so the table never holds more than 8 vectors whatever the query's length -- then the select
+//     chain over the documents, with the documents that have no eligible row masked out.
+// Synchronous: the handle is idle before and after.  d_raw and the outputs are device memory, h_lims host memory.
+static int multivec_doc_index(vrod_index* idx) {
+    if (idx->doc_valid) return VROD_OK;
+    const uint64_t N = idx->count;
+    std::vector<uint32_t> docs(1, 0u);
+    if (idx->lab_dev) {
+        docs.assign(idx->lab_bits.begin(), idx->lab_bits.begin() + N);
+        std::sort(docs.begin(), docs.end());
+        docs.erase(std::unique(docs.begin(), docs.end()), docs.end());
+        std::vector<uint32_t> rank(N);
+        for (uint64_t r = 0; r < N; ++r)
+            rank[r] = (uint32_t)(std::lower_bound(docs.begin(), docs.end(), idx->lab_bits[r]) - docs.begin());
+        VROD_TRY(idx->doc_rank.ensure(N * 4));
+        HIP_TRY(hipMemcpy(idx->doc_rank.p, rank.data(), N * 4, hipMemcpyHostToDevice));
+    }
+    VROD_TRY(idx->doc_labels.ensure(docs.size() * 4));
+    HIP_TRY(hipMemcpy(idx->doc_labels.p, docs.data(), docs.size() * 4, hipMemcpyHostToDevice));
+    idx->n_docs = docs.size();
+    idx->doc_valid = true;
+    return VROD_OK;
+}
+
+// The select chain, then one more pass over its keys: [nq][kp] keys sorted best first, 0 = none.
+static int select_sorted(vrod_index* idx, Pending& P, const float* d_scores, uint64_t score_ld, uint64_t n, int nq, uint32_t kp,
+                         const uint32_t* mask, const uint32_t* len, const uint64_t** out_keys) {
+    const uint64_t* keys; uint64_t kld, kn;
+    VROD_TRY(select_chain(idx, P, d_scores, score_ld, n, nq, kp, mask, &keys, &kld, &kn, len));
+    DevBuf& dst = keys == P.keys_a.as<uint64_t>() ? P.keys_b : P.keys_a;
+    VROD_TRY(dst.ensure((size_t)nq * kp * 8));
+    launch_select_from_keys(keys, kld, kn, nq, kp, dst.as<uint64_t>(), kp, P.stream);
+    *out_keys = dst.as<uint64_t>();
+    return VROD_OK;
+}
+
+// The dense route for the queries `todo` (indices of the call), whose result rows it writes whole.
+static int multivec_dense(vrod_index* idx, vrod_search_stats& st, const uint32_t* lims, const std::vector<uint32_t>& todo, uint32_t k,
+                          uint32_t* d_out_labels, float* d_out_scores, uint32_t* d_found) {
+    if (todo.empty()) return VROD_OK;
+    VROD_TRY(multivec_doc_index(idx));
+    Pending& P = next_slot(idx);
+    hipStream_t s = P.stream;
+    const int form = score_form(idx->metric);
+    const uint64_t N = idx->count, D = idx->n_docs, score_ld = round_up(N, 64), Dld = round_up(D, 64);
+    const double row_bytes = (double)idx->ld * idx->esize;
+    const uint32_t gmax = (uint32_t)rescore_all_max_queries(idx->ld);   // 8
+    const uint32_t qg_max = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(64, (1ull << 30) / (Dld * 4)));
+    const uint32_t kx = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(k, D), kSelectChunk / 2);   // (the rest: unfilled)
+    VROD_TRY(P.scores.ensure((size_t)gmax * score_ld * 4));
+    VROD_TRY(idx->mv_best.ensure((size_t)gmax * D * 4));
+    VROD_TRY(idx->mv_absent.ensure(((size_t)D + 31) / 32 * 4 + 64));
+    VROD_TRY(idx->mv_S.ensure((size_t)std::min<size_t>(qg_max, todo.size()) * Dld * 4));
+    VROD_TRY(idx->mv_pairs.ensure((size_t)qg_max * 4));
+    uint32_t* d_qidx = idx->mv_pairs.as<uint32_t>();
+    const uint32_t* d_rank = idx->lab_dev ? idx->doc_rank.as<uint32_t>() : nullptr;
+    bool have_absent = false;
+    for (size_t f0 = 0; f0 < todo.size(); f0 += qg_max) {
+        const uint32_t qg = (uint32_t)std::min<size_t>(qg_max, todo.size() - f0);
+        for (uint32_t i = 0; i < qg; ++i) {
+            const uint32_t q = todo[f0 + i];
+            for (uint32_t v0 = lims[q]; v0 < lims[q + 1]; v0 += gmax) {
+                const uint32_t g = std::min(gmax, lims[q + 1] - v0);
+                uint32_t gl = 1;   // the launch takes 1, 2, 4 or 8 vectors: the last one repeats up to that
+                while (gl < g) gl <<= 1;
+                uint32_t qi[8];
+                for (uint32_t j = 0; j < gl; ++j) qi[j] = v0 + std::min(j, g - 1);
+                launch_rescore_all(idx->corpus, idx->dtype, form, idx->dim, idx->ld, idx->mv_q.as<float>(), qi, (int)gl, N, P.scores.as<float>(),
+                                   score_ld, s);
+                HIP_TRY(hipMemsetAsync(idx->mv_best.p, 0, (size_t)g * D * 4, s));
+                launch_multivec_fold(P.scores.as<float>(), score_ld, g, N, d_rank, idx->row_mask(), form, idx->mv_best.as<uint32_t>(), D, s);
+                launch_multivec_sum(idx->mv_best.as<uint32_t>(), g, D, form, v0 == lims[q], idx->mv_S.as<float>() + (size_t)i * Dld,
+                                    have_absent ? nullptr : idx->mv_absent.as<uint32_t>(), s);
+                HIP_TRY(hipGetLastError());
+                have_absent = true;   // (the same for every vector and every query: which documents have an eligible row)
+                st.scan_launches++;
+                st.scan_bytes += (double)N * row_bytes;
+                st.scan_flops += 2.0 * g * (double)N * idx->dim;
+            }
+        }
+        const uint64_t* keys;
+        VROD_TRY(select_sorted(idx, P, idx->mv_S.as<float>(), Dld, D, (int)qg, kx, idx->mv_absent.as<uint32_t>(), nullptr, &keys));
+        HIP_TRY(hipMemcpyAsync(d_qidx, &todo[f0], (size_t)qg * 4, hipMemcpyHostToDevice, s));
+        launch_multivec_output(keys, kx, kx, qg, form, k, idx->doc_labels.as<uint32_t>(), nullptr, d_qidx, d_out_labels, d_out_scores, d_found,
+                               nullptr, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(s));   // the next group reuses S and the query indices
+    }
+    return VROD_OK;
+}
+
+// The candidate route for the sub-batch of queries [q0, q1): the result rows of the queries it certifies are final, the
+// others are appended to `dense`.
+static int multivec_candidates(vrod_index* idx, vrod_search_stats& st, bool first_batch, const float* d_raw, const uint32_t* lims, uint32_t q0,
+                               uint32_t q1, uint32_t k, uint32_t k1, uint32_t* d_out_labels, float* d_out_scores, uint32_t* d_found,
+                               std::vector<uint32_t>& dense) {
+    const uint32_t nqs = q1 - q0, vbase = lims[q0], V = lims[q1] - vbase;
+    const uint64_t N = idx->count, elig = idx->eligible();
+    const int form = score_form(idx->metric);
+    const double row_bytes = (double)idx->ld * idx->esize;
+    vrod_multivec_stats& ms = idx->mv_stats;
+    // ---- the certified lists of every vector
+    VROD_TRY(idx->mv_ids.ensure((size_t)V * k1 * 8));
+    VROD_TRY(idx->mv_scores.ensure((size_t)V * k1 * 4));
+    VROD_TRY(run_search(idx, d_raw + (size_t)vbase * idx->dim, V, k1, idx->mv_ids.as<uint64_t>(), idx->mv_scores.as<float>()));
+    if (first_batch) {
+        st = idx->stats;
+    } else {
+        fold_stats(st, idx->stats);
+        st.scan_bytes += idx->stats.scan_bytes;
+        st.scan_flops += idx->stats.scan_flops;
+    }
+    Pending& P = next_slot(idx);
+    hipStream_t s = P.stream;
+
+    // ---- the distinct labels of each query's lists, its flags and U
+    std::vector<MultivecQuery> mq(nqs);
+    uint64_t tab_words = 0;
+    for (uint32_t i = 0; i < nqs; ++i) {
+        const uint32_t m = lims[q0 + i + 1] - lims[q0 + i], slots = multivec_table_slots(m * k1);
+        uint32_t bits = 0;
+        while ((1u << bits) < slots) ++bits;
+        mq[i] = MultivecQuery{lims[q0 + i] - vbase, m, (lims[q0 + i] - vbase) * k1, (uint32_t)tab_words, slots, 32 - bits};
+        tab_words += slots;
+    }
+    const size_t entries = (size_t)V * k1;
+    VROD_TRY(idx->mv_ent.ensure(entries * 4));
+    VROD_TRY(idx->mv_cand.ensure(entries * 4));
+    VROD_TRY(idx->mv_tab.ensure(tab_words * 4));
+    // per query: [MultivecQuery | count | flags | U | kth | table offset | query index | candidates]
+    VROD_TRY(idx->mv_small.ensure((size_t)nqs * (sizeof(MultivecQuery) + 7 * 4)));
+    MultivecQuery* d_mq = idx->mv_small.as<MultivecQuery>();
+    uint32_t* d_count = (uint32_t*)(d_mq + nqs);
+    uint32_t* d_flags = d_count + nqs;
+    float* d_U = (float*)(d_flags + nqs);
+    float* d_kth = d_U + nqs;
+    uint32_t* d_tab_off = (uint32_t*)(d_kth + nqs);
+    uint32_t* d_qidx = d_tab_off + nqs;
+    uint32_t* d_len = d_qidx + nqs;
+    HIP_TRY(hipMemcpyAsync(d_mq, mq.data(), (size_t)nqs * sizeof(MultivecQuery), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(idx->mv_tab.p, 0xFF, tab_words * 4, s));
+    launch_multivec_candidates(idx->mv_ids.as<uint64_t>(), idx->mv_scores.as<float>(), k1, idx->lab_dev, idmap_of(idx).offset, d_mq, nqs,
+                               idx->mv_ent.as<uint32_t>(), idx->mv_tab.as<uint32_t>(), idx->mv_cand.as<uint32_t>(), d_count, d_flags, d_U, s);
+    HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> cf((size_t)nqs * 3), cand(entries);
+    HIP_TRY(hipMemcpyAsync(cf.data(), d_count, (size_t)nqs * 12, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(cand.data(), idx->mv_cand.p, entries * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const uint32_t* h_count = cf.data();
+    const uint32_t* h_flags = h_count + nqs;
+    const float* h_U = (const float*)(h_flags + nqs);
+
+    // ---- the candidates' eligible rows, counted per label (passes of kLabelGroupsPerPass labels)
+    std::vector<uint8_t> alive(nqs, 1);
+    std::vector<uint32_t> labs;
+    for (uint32_t i = 0; i < nqs; ++i) {
+        if (h_flags[i] & 2u) { alive[i] = 0; continue; }   // a NaN or infinite score in a list: the bound says nothing
+        uint32_t* c = cand.data() + mq[i].ent_off;
+        std::sort(c, c + h_count[i]);   // ascending: the select's tie-break by smaller column is by smaller label
+        labs.insert(labs.end(), c, c + h_count[i]);
+    }
+    std::sort(labs.begin(), labs.end());
+    labs.erase(std::unique(labs.begin(), labs.end()), labs.end());
+    const uint32_t* base_mask = idx->row_mask();
+    const uint32_t rpb = label_rows_per_block(N);
+    const uint32_t n_blocks = (uint32_t)((N + rpb - 1) / rpb);
+    const uint32_t Gc = (uint32_t)std::min<size_t>(std::max<size_t>(labs.size(), 1), kLabelGroupsPerPass);
+    VROD_TRY(idx->lab_tab.ensure((size_t)Gc * 4 * 3));
+    VROD_TRY(idx->lab_cnt.ensure((size_t)n_blocks * Gc * 4));
+    uint32_t* d_table = idx->lab_tab.as<uint32_t>();
+    uint32_t* d_total = d_table + Gc;
+    uint32_t* d_seg_off = d_total + Gc;
+    std::vector<uint32_t> rows_of(labs.size());
+    for (size_t g0 = 0; g0 < labs.size(); g0 += kLabelGroupsPerPass) {
+        const uint32_t Gp = (uint32_t)std::min<size_t>(kLabelGroupsPerPass, labs.size() - g0);
+        HIP_TRY(hipMemcpyAsync(d_table, labs.data() + g0, (size_t)Gp * 4, hipMemcpyHostToDevice, s));
+        launch_label_group_count(idx->lab_dev, base_mask, N, rpb, d_table, Gp, idx->lab_cnt.as<uint32_t>(), d_total, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(rows_of.data() + g0, d_total, (size_t)Gp * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    auto lab_index = [&](uint32_t label) { return (size_t)(std::lower_bound(labs.begin(), labs.end(), label) - labs.begin()); };
+
+    // ---- route: a query whose candidates own too many rows, or whose score slots no longer fit, goes dense
+    uint64_t total_slots = 0;
+    std::vector<uint32_t> live;   // sub-batch indices of the queries that stay
+    for (uint32_t i = 0; i < nqs; ++i) {
+        if (!alive[i]) continue;
+        uint64_t cand_rows = 0;
+        const uint32_t* c = cand.data() + mq[i].ent_off;
+        for (uint32_t j = 0; j < h_count[i]; ++j) cand_rows += rows_of[lab_index(c[j])];
+        const uint64_t slots = (uint64_t)h_count[i] * mq[i].m;
+        if (multivec_candidates_too_broad(cand_rows, N) || total_slots + slots > kMultivecMaxSlots) { alive[i] = 0; continue; }
+        total_slots += slots;
+        live.push_back(i);
+        ms.candidate_labels += h_count[i];
+        ms.candidate_rows += cand_rows;
+    }
+    for (uint32_t i = 0; i < nqs; ++i)
+        if (!alive[i]) dense.push_back(q0 + i);
+    if (live.empty()) return VROD_OK;
+
+    // ---- the labels the live queries use, each with its users (query, candidate column)
+    struct User { uint32_t li, col; };
+    std::vector<std::vector<User>> users(labs.size());
+    for (uint32_t li = 0; li < live.size(); ++li) {
+        const uint32_t i = live[li];
+        const uint32_t* c = cand.data() + mq[i].ent_off;
+        for (uint32_t j = 0; j < h_count[i]; ++j) users[lab_index(c[j])].push_back({li, j});
+    }
+    std::vector<uint32_t> used;   // indices into labs, ascending
+    for (size_t g = 0; g < labs.size(); ++g)
+        if (!users[g].empty()) used.push_back((uint32_t)g);
+    std::vector<std::vector<uint32_t>> pair_slot(live.size());
+    for (uint32_t li = 0; li < live.size(); ++li) pair_slot[li].resize(h_count[live[li]]);
+    VROD_TRY(idx->mv_M.ensure(std::max<uint64_t>(total_slots, 1) * 4));
+
+    // ---- per pass: the labels' row lists, the segmented score launch, M per score slot
+    uint32_t slot_base = 0;
+    for (size_t u0 = 0; u0 < used.size(); u0 += kLabelGroupsPerPass) {
+        const uint32_t Gp = (uint32_t)std::min<size_t>(kLabelGroupsPerPass, used.size() - u0);
+        std::vector<uint32_t> table(Gp), seg_off(Gp);
+        std::vector<SegGroup> segs;
+        std::vector<uint32_t> slot_q, slot_len;
+        uint64_t list_n = 0;
+        for (uint32_t g = 0; g < Gp; ++g) {
+            const uint32_t lab_i = used[u0 + g], m_rows = rows_of[lab_i];
+            table[g] = labs[lab_i];
+            seg_off[g] = (uint32_t)list_n;
+            const uint32_t slot0 = (uint32_t)slot_q.size();
+            for (const User& u : users[lab_i]) {
+                const uint32_t q = q0 + live[u.li];
+                pair_slot[u.li][u.col] = slot_base + (uint32_t)slot_q.size();
+                for (uint32_t v = lims[q]; v < lims[q + 1]; ++v) { slot_q.push_back(v); slot_len.push_back(m_rows); }
+            }
+            const uint32_t nsl = (uint32_t)slot_q.size() - slot0;
+            segs.push_back({(uint32_t)list_n, m_rows, slot0, nsl});
+            list_n += m_rows;   // (the labels' rows are disjoint: at most N in all)
+            st.scan_bytes += (double)m_rows * row_bytes;
+            st.scan_flops += 2.0 * nsl * (double)m_rows * idx->dim;
+        }
+        const uint32_t ns = (uint32_t)slot_q.size();
+        HIP_TRY(hipMemcpyAsync(d_table, table.data(), (size_t)Gp * 4, hipMemcpyHostToDevice, s));
+        launch_label_group_count(idx->lab_dev, base_mask, N, rpb, d_table, Gp, idx->lab_cnt.as<uint32_t>(), d_total, s);
+        VROD_TRY(idx->lab_lists.ensure(std::max<uint64_t>(list_n, 1) * 4));
+        HIP_TRY(hipMemcpyAsync(d_seg_off, seg_off.data(), (size_t)Gp * 4, hipMemcpyHostToDevice, s));
+        if (list_n)
+            launch_label_group_scatter(idx->lab_dev, base_mask, N, rpb, d_table, Gp, idx->lab_cnt.as<uint32_t>(), d_seg_off,
+                                       idx->lab_lists.as<uint32_t>(), s);
+        HIP_TRY(hipGetLastError());
+        const SegPlan plan = plan_segments(segs);
+        VROD_TRY(idx->lab_entries.ensure(std::max<size_t>(plan.entries.size(), 1) * sizeof(SegEntry)));
+        VROD_TRY(idx->lab_slots.ensure((size_t)ns * 4 * 2));
+        uint32_t* d_slot_q = idx->lab_slots.as<uint32_t>();
+        uint32_t* d_slot_len = d_slot_q + ns;
+        HIP_TRY(hipMemcpyAsync(d_slot_q, slot_q.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_slot_len, slot_len.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s));
+        if (!plan.entries.empty())
+            HIP_TRY(hipMemcpyAsync(idx->lab_entries.p, plan.entries.data(), plan.entries.size() * sizeof(SegEntry), hipMemcpyHostToDevice, s));
+        for (const SegChunk& c : plan.chunks) {
+            const uint64_t out_ld = round_up(std::max<uint32_t>(c.max_m, 1), 64);
+            VROD_TRY(P.scores.ensure((size_t)c.n_slots * out_ld * 4));
+            if (c.n_blocks) {
+                launch_rescore_segments(idx->corpus, idx->dtype, form, idx->dim, idx->ld, idx->mv_q.as<float>(),
+                                        idx->lab_entries.as<SegEntry>() + c.e0, c.e1 - c.e0, c.n_blocks, d_slot_q, c.slot0,
+                                        idx->lab_lists.as<uint32_t>(), P.scores.as<float>(), out_ld, s);
+                st.scan_launches++;
+            }
+            launch_multivec_slot_best(P.scores.as<float>(), out_ld, c.n_slots, d_slot_len + c.slot0, form,
+                                      idx->mv_M.as<float>() + slot_base + c.slot0, s);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipStreamSynchronize(s));   // the next pass reuses the tables
+        slot_base += ns;
+    }
+
+    // ---- S per (query, candidate), the select chain with a length per query, the outputs, the certificate
+    uint32_t max_c = 1;
+    for (uint32_t i : live) max_c = std::max(max_c, h_count[i]);
+    const uint64_t Sld = round_up(max_c, 64);
+    const uint32_t rows_max = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(live.size(), (1ull << 30) / (Sld * 4)));
+    VROD_TRY(idx->mv_S.ensure((size_t)rows_max * Sld * 4));
+    HIP_TRY(hipMemcpyAsync(idx->mv_cand.p, cand.data(), entries * 4, hipMemcpyHostToDevice, s));   // (sorted per query now)
+    for (size_t l0 = 0; l0 < live.size(); l0 += rows_max) {
+        const uint32_t nr = (uint32_t)std::min<size_t>(rows_max, live.size() - l0);
+        std::vector<uint32_t> p_slot, p_m, tab_off(nr), qidx(nr), len(nr);
+        std::vector<uint64_t> p_dst;
+        for (uint32_t r = 0; r < nr; ++r) {
+            const uint32_t li = (uint32_t)l0 + r, i = live[li];
+            tab_off[r] = mq[i].ent_off; qidx[r] = q0 + i; len[r] = h_count[i];
+            for (uint32_t j = 0; j < h_count[i]; ++j) {
+                p_slot.push_back(pair_slot[li][j]); p_m.push_back(mq[i].m); p_dst.push_back((uint64_t)r * Sld + j);
+            }
+        }
+        const uint32_t np = (uint32_t)p_slot.size();
+        VROD_TRY(idx->mv_pairs.ensure((size_t)np * 16 + 64));
+        uint64_t* d_dst = idx->mv_pairs.as<uint64_t>();
+        uint32_t* d_pslot = (uint32_t*)(d_dst + np);
+        uint32_t* d_pm = d_pslot + np;
+        HIP_TRY(hipMemcpyAsync(d_dst, p_dst.data(), (size_t)np * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_pslot, p_slot.data(), (size_t)np * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_pm, p_m.data(), (size_t)np * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_tab_off, tab_off.data(), (size_t)nr * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_qidx, qidx.data(), (size_t)nr * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_len, len.data(), (size_t)nr * 4, hipMemcpyHostToDevice, s));
+        launch_multivec_pair_sum(idx->mv_M.as<float>(), d_pslot, d_pm, d_dst, np, idx->mv_S.as<float>(), s);
+        const uint32_t kx = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(k, max_c), kSelectChunk / 2);
+        const uint64_t* keys;
+        VROD_TRY(select_sorted(idx, P, idx->mv_S.as<float>(), Sld, max_c, (int)nr, kx, nullptr, d_len, &keys));
+        launch_multivec_output(keys, kx, kx, nr, form, k, idx->mv_cand.as<uint32_t>(), d_tab_off, d_qidx, d_out_labels, d_out_scores, d_found,
+                               d_kth, s);
+        HIP_TRY(hipGetLastError());
+        std::vector<float> kth(nr);
+        HIP_TRY(hipMemcpyAsync(kth.data(), d_kth, (size_t)nr * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        for (uint32_t r = 0; r < nr; ++r) {
+            const uint32_t i = live[l0 + r];
+            const bool complete = multivec_lists_complete(h_flags[i] & 1u, k1, elig);
+            if (multivec_certified(complete, h_count[i], k, kth[r], h_U[i], form == M_COSINE)) ms.certified_queries++;
+            else dense.push_back(q0 + i);   // (its row is written again, whole, by the dense route)
+        }
+    }
+    return VROD_OK;
+}
+
+static int multivec_search(vrod_index* idx, const float* d_raw, const uint32_t* lims, uint32_t nq, uint32_t k, uint32_t* d_out_labels,
+                           float* d_out_scores, uint32_t* d_found) {
+    vrod_search_stats st{};
+    st.nq = nq; st.k = k; st.path = (uint32_t)idx->path;
+    vrod_multivec_stats& ms = idx->mv_stats;
+    ms = vrod_multivec_stats{};
+    ms.nq = nq; ms.vectors = lims[nq];
+    const uint64_t N = idx->count, elig = idx->eligible();
+    hipStream_t s = next_slot(idx).stream;
+    if (N == 0 || elig == 0) {   // no eligible row: every slot unfilled, the vectors are not looked at (as vrod_search)
+        std::vector<uint32_t> nan((size_t)nq * k, kScoreNoneBits);
+        HIP_TRY(hipMemcpyAsync(d_out_scores, nan.data(), nan.size() * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(d_out_labels, 0, (size_t)nq * k * 4, s));
+        HIP_TRY(hipMemsetAsync(d_found, 0, (size_t)nq * 4, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        idx->stats = st;
+        return VROD_OK;
+    }
+    // every vector prepared as a search prepares a query, and checked, before anything is written
+    {
+        Pending& P = next_slot(idx);
+        VROD_TRY(prep_group_queries(idx, P, d_raw, lims[nq]));
+        VROD_TRY(idx->mv_q.ensure((size_t)lims[nq] * idx->ld * 4));
+        HIP_TRY(hipMemcpyAsync(idx->mv_q.p, P.q_f32.p, (size_t)lims[nq] * idx->ld * 4, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    std::vector<uint32_t> dense;
+    // a handle without labels is one document that owns every row: nothing for the candidate route to narrow
+    if (idx->path != VROD_PATH_EXACT && idx->lab_dev) {
+        const uint32_t k1 = multivec_first_k(k, elig);
+        ms.k1 = k1;
+        for (uint32_t q0 = 0; q0 < nq;) {
+            const uint32_t q1 = multivec_cut(lims, nq, q0);
+            VROD_TRY(multivec_candidates(idx, st, q0 == 0, d_raw, lims, q0, q1, k, k1, d_out_labels, d_out_scores, d_found, dense));
+            q0 = q1;
+        }
+        st.nq = nq; st.k = k;
+        std::sort(dense.begin(), dense.end());
+    } else {
+        for (uint32_t q = 0; q < nq; ++q) dense.push_back(q);
+    }
+    VROD_TRY(multivec_dense(idx, st, lims, dense, k, d_out_labels, d_out_scores, d_found));
+    ms.dense_queries = (uint32_t)dense.size();
+    st.fallback_queries += (uint32_t)dense.size();
+    if (dense.size() == nq) st.path = VROD_PATH_EXACT;
+    idx->stats = st;
+    return VROD_OK;
+}
+
 // ------------------------------------------------------------------ searches by stored row (vrod_search_by_ids, vrod_knn_graph)
 // The queries are rows the handle already holds: byid_gather_kernel copies them out of the corpus as fp32 (kernels_byid.hip)
 // and the ordinary search flow takes them as given (prep_ovr) -- the stored row is the query bit for bit, so the scores
@@ -3178,7 +3580,9 @@ int vrod_index_destroy(vrod_index* idx) {
     if (idx->tag_dev) (void)hipFree(idx->tag_dev);
     for (DevBuf* b : {&idx->lab_tab, &idx->lab_cnt, &idx->lab_lists, &idx->lab_slots, &idx->lab_entries, &idx->lab_mask, &idx->lab_q, &idx->lab_ids,
                       &idx->lab_scores, &idx->lab_qraw, &idx->grp_ids, &idx->grp_scores, &idx->grp_small, &idx->grp_mask, &idx->grp_labels,
-                      &idx->grp_qraw, &idx->byid_user_ids}) b->release();
+                      &idx->grp_qraw, &idx->byid_user_ids, &idx->doc_rank, &idx->doc_labels, &idx->mv_q, &idx->mv_ids, &idx->mv_scores, &idx->mv_ent,
+                      &idx->mv_tab, &idx->mv_cand, &idx->mv_small, &idx->mv_best, &idx->mv_S, &idx->mv_absent, &idx->mv_M, &idx->mv_pairs,
+                      &idx->mv_raw, &idx->mv_lims, &idx->mv_out_labels, &idx->mv_out_scores, &idx->mv_found}) b->release();
     for (int c = 0; c < 2; ++c)
         for (DevBuf* b : {&idx->byid_ids[c], &idx->byid_scores[c], &idx->byid_out_ids[c], &idx->byid_out_scores[c], &idx->byid_map[c]}) b->release();
     if (idx->flags) (void)hipFree(idx->flags);
@@ -3431,6 +3835,7 @@ int vrod_index_set_labels(vrod_index* idx, uint64_t first_id, const uint32_t* la
         idx->lab_dev = d;
         idx->lab_bits.assign(idx->capacity, 0u);
     }
+    idx->doc_valid = false;
     HIP_TRY(hipMemcpy(idx->lab_dev + r0, labels, n * 4, hipMemcpyHostToDevice));
     std::copy(labels, labels + n, idx->lab_bits.begin() + r0);
     return VROD_OK;
@@ -3592,6 +3997,68 @@ int vrod_search_grouped_device(vrod_index* idx, const float* d_queries, uint32_t
         d_out_labels = idx->grp_labels.as<uint32_t>();
     }
     return grouped_search(idx, d_queries, nq, k, d_out_ids, d_out_scores, d_out_labels);
+}
+
+static int check_multivec_args(vrod_index* idx, const void* v, const void* lims, uint32_t nq, uint32_t k, const void* ol, const void* os) {
+    VROD_TRY(check_search_args(idx, v, nq, k, ol, os));
+    if (nq && !lims) return fail(VROD_ERR_INVALID_ARG, "null buffer");
+    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "vrod_search_multivec on a multi-device handle: labels are not routed to the shards");
+    return VROD_OK;
+}
+
+static int check_multivec_lims(const uint32_t* lims, uint32_t nq) {
+    switch (multivec_check_lims(lims, nq)) {
+        case 0: return VROD_OK;
+        case 1: return fail(VROD_ERR_INVALID_ARG, "query_lims[0] must be 0");
+        case 2: return fail(VROD_ERR_INVALID_ARG, "query_lims must not decrease");
+        case 3: return fail(VROD_ERR_INVALID_ARG, "a query without a vector");
+        default: return fail(VROD_ERR_INVALID_ARG, "a query with more than %u vectors", VROD_MAX_QUERY_VECTORS);
+    }
+}
+
+int vrod_search_multivec(vrod_index* idx, const float* vectors, const uint32_t* query_lims, uint32_t nq, uint32_t k, uint32_t* out_labels,
+                         float* out_scores, uint32_t* out_found) {
+    VROD_TRY(check_multivec_args(idx, vectors, query_lims, nq, k, out_labels, out_scores));
+    if (!nq) return VROD_OK;
+    VROD_TRY(require_idle(idx, "vrod_search_multivec"));
+    VROD_TRY(check_multivec_lims(query_lims, nq));
+    VROD_TRY(set_device(idx));
+    const size_t nv = query_lims[nq];
+    VROD_TRY(idx->mv_raw.ensure(nv * idx->dim * 4));
+    VROD_TRY(idx->mv_out_labels.ensure((size_t)nq * k * 4));
+    VROD_TRY(idx->mv_out_scores.ensure((size_t)nq * k * 4));
+    VROD_TRY(idx->mv_found.ensure((size_t)nq * 4));
+    HIP_TRY(hipMemcpy(idx->mv_raw.p, vectors, nv * idx->dim * 4, hipMemcpyHostToDevice));
+    VROD_TRY(multivec_search(idx, idx->mv_raw.as<float>(), query_lims, nq, k, idx->mv_out_labels.as<uint32_t>(), idx->mv_out_scores.as<float>(),
+                             idx->mv_found.as<uint32_t>()));
+    HIP_TRY(hipMemcpy(out_labels, idx->mv_out_labels.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_scores, idx->mv_out_scores.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    if (out_found) HIP_TRY(hipMemcpy(out_found, idx->mv_found.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
+    return VROD_OK;
+}
+
+int vrod_search_multivec_device(vrod_index* idx, const float* d_vectors, const uint32_t* d_query_lims, uint32_t nq, uint32_t k,
+                                uint32_t* d_out_labels, float* d_out_scores, uint32_t* d_out_found, void* stream) {
+    VROD_TRY(check_multivec_args(idx, d_vectors, d_query_lims, nq, k, d_out_labels, d_out_scores));
+    if (!nq) return VROD_OK;
+    VROD_TRY(require_idle(idx, "vrod_search_multivec_device"));
+    VROD_TRY(set_device(idx));
+    // synchronous, as a range search: whatever the caller's stream holds is complete before the library's streams start
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    std::vector<uint32_t> lims((size_t)nq + 1);
+    HIP_TRY(hipMemcpy(lims.data(), d_query_lims, lims.size() * 4, hipMemcpyDeviceToHost));
+    VROD_TRY(check_multivec_lims(lims.data(), nq));
+    if (!d_out_found) {
+        VROD_TRY(idx->mv_found.ensure((size_t)nq * 4));
+        d_out_found = idx->mv_found.as<uint32_t>();
+    }
+    return multivec_search(idx, d_vectors, lims.data(), nq, k, d_out_labels, d_out_scores, d_out_found);
+}
+
+int vrod_index_last_multivec(const vrod_index* idx, vrod_multivec_stats* out) {
+    if (!idx || !out) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    *out = idx->mv_stats;
+    return VROD_OK;
 }
 
 static int check_byid_args(vrod_index* idx, const void* ids, uint32_t nq, uint32_t k, uint32_t flags, const void* oi, const void* os,

@@ -7,6 +7,7 @@
 #include "search_plan.h"   // kSelectChunk
 #include "label_plan.h"    // SegEntry
 #include "tag_plan.h"      // TagPred
+#include "multivec_plan.h" // MultivecQuery
 
 namespace vrod {
 
@@ -250,6 +251,33 @@ void launch_group_dedupe(const uint64_t* d_cand_ids, const float* d_cand_scores,
 // to 256, which must lie within n_words * 32 and within the label array.
 void launch_group_mask(const uint32_t* d_labels, const uint32_t* d_base_mask, uint64_t count, uint64_t n_words, const uint32_t* d_qidx,
                        uint32_t n_queries, const uint32_t* d_out_labels, const uint32_t* d_found, uint32_t k, uint32_t* d_out, hipStream_t s);
+
+// ---- kernels_multivec.hip : a multi-vector search's document scores (vrod_search_multivec)
+// Dense route.  Fold: canonical scores d_scores [g][score_ld] of rows [0, n_rows) -> d_best [g][n_docs] (zeroed by the
+// caller), the best score per (vector, document) as an order-preserving key; d_rank[r] = the document of row r (null: one
+// document), rows set in d_mask (may be null) are left out.  Sum: d_S[d] = (first ? +0 : d_S[d]) + M(0, d) + ... in
+// order; d_absent (may be null; ceil(n_docs / 32) words) = the bitmap of the documents without an eligible row.
+void launch_multivec_fold(const float* d_scores, uint64_t score_ld, uint32_t g, uint64_t n_rows, const uint32_t* d_rank, const uint32_t* d_mask,
+                          int metric, uint32_t* d_best, uint64_t n_docs, hipStream_t s);
+void launch_multivec_sum(const uint32_t* d_best, uint32_t g, uint64_t n_docs, int metric, bool first, float* d_S, uint32_t* d_absent,
+                         hipStream_t s);
+// Candidate route.  Per query of d_queries (multivec_plan.h MultivecQuery) over the lists d_ids / d_scores [vectors][k1]:
+// its distinct labels (unordered) at d_cand + ent_off, their number, flags (1: a short list, 2: a non-finite score) and U.
+// d_lab: as many words as list entries; d_table: the queries' tables, all 0xFFFFFFFF.  d_labels == null: label 0.
+void launch_multivec_candidates(const uint64_t* d_ids, const float* d_scores, uint32_t k1, const uint32_t* d_labels, uint64_t id_offset,
+                                const MultivecQuery* d_queries, uint32_t nq, uint32_t* d_lab, uint32_t* d_table, uint32_t* d_cand, uint32_t* d_count,
+                                uint32_t* d_flags, float* d_U, hipStream_t s);
+// d_M[s] = the best of the first d_len[s] scores of slot s < n_slots of a score chunk [n_slots][score_ld] (NaN loses).
+void launch_multivec_slot_best(const float* d_scores, uint64_t score_ld, uint32_t n_slots, const uint32_t* d_len, int metric, float* d_M,
+                               hipStream_t s);
+// d_out[d_dst[p]] = d_M[d_slot[p]] + ... + d_M[d_slot[p] + d_m[p] - 1], from +0, left to right.
+void launch_multivec_pair_sum(const float* d_M, const uint32_t* d_slot, const uint32_t* d_m, const uint64_t* d_dst, uint32_t n_pairs, float* d_out,
+                              hipStream_t s);
+// Sorted keys [n_rows][key_ld] (kp per row, best first, 0 = none) over columns of d_table + d_tab_off[i] -> rows d_qidx[i]
+// (i without d_qidx) of d_out_labels / d_out_scores [..][k], d_found[q] = filled slots, d_kth[i] (may be null) = slot k - 1.
+void launch_multivec_output(const uint64_t* d_keys, uint64_t key_ld, uint32_t kp, uint32_t n_rows, int metric, uint32_t k, const uint32_t* d_table,
+                            const uint32_t* d_tab_off, const uint32_t* d_qidx, uint32_t* d_out_labels, float* d_out_scores, uint32_t* d_found,
+                            float* d_kth, hipStream_t s);
 
 // ---- kernels_byid.hip : queries taken from stored rows (vrod_search_by_ids, vrod_knn_graph)
 // Rows [row0, row0 + m) against the deleted-row bitmap d_del (not null): d_live[j] = the j-th live row, ascending;

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import SearchStats, VrodError, check
+from ._lib import MultivecStats, SearchStats, VrodError, check
 
 DTYPE_F32, DTYPE_BF16 = 0, 1
 METRIC_COSINE, METRIC_L2, METRIC_IP = 0, 1, 2
@@ -19,6 +19,7 @@ PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT, PATH_GATHER = 0, 1, 2, 3, 4
 ID_NONE = np.uint64(0xFFFFFFFFFFFFFFFF)
 MAX_K = 3584
 BYID_EXCLUDE_SELF = 1   # VROD_BYID_EXCLUDE_SELF
+MAX_QUERY_VECTORS = 256   # VROD_MAX_QUERY_VECTORS
 # rows per batch of knn_graph() by storage type (byid_plan.h: kByidBatchF32, kByidBatchBf16)
 KNN_BATCH = {0: 256, 1: 1024}
 
@@ -359,6 +360,75 @@ class Index:
         check(self._L.vrod_search_grouped_device(self._h, d_queries.data_ptr(), nq, int(k), out_ids.data_ptr(), out_scores.data_ptr(),
                                                  out_labels.data_ptr() if out_labels is not None else None, C.c_void_p(stream)))
         return out_ids, out_scores, out_labels
+
+    # -- multi-vector search: a query is a set of vectors, a document the rows of one label, scored by MaxSim
+    def _multivec_args(self, vectors, lims):
+        """A list of [m_i, dim] arrays, or (vectors [n, dim], lims [nq + 1]) -> contiguous fp32 vectors and uint32 lims."""
+        if lims is None:
+            parts = [np.asarray(v, dtype=np.float32) for v in vectors]
+            parts = [v[None, :] if v.ndim == 1 else v for v in parts]
+            for v in parts:
+                if v.ndim != 2 or v.shape[1] != self.dim:
+                    raise ValueError(f"every query must be [m, {self.dim}]")
+            lims = np.cumsum([0] + [v.shape[0] for v in parts])
+            vectors = np.concatenate(parts) if parts else np.zeros((0, self.dim), np.float32)
+        vectors = np.ascontiguousarray(vectors, dtype=np.float32)
+        if vectors.ndim != 2 or vectors.shape[1] != self.dim:
+            raise ValueError(f"vectors must be [n, {self.dim}]")
+        la = np.asarray(lims)
+        if la.ndim != 1 or la.size < 1 or la.dtype.kind not in "iu":
+            raise ValueError("lims must be a vector of nq + 1 integers")
+        if la.size and (int(la.min()) < 0 or int(la.max()) > 0xFFFFFFFF):
+            raise ValueError("lims must fit uint32")
+        la = np.ascontiguousarray(la, dtype=np.uint32)
+        if int(la[-1]) != vectors.shape[0]:
+            raise ValueError(f"lims[-1] = {int(la[-1])} must equal the number of vectors, {vectors.shape[0]}")
+        return vectors, la
+
+    def search_multivec(self, vectors, k: int, lims=None):
+        """The k best documents (labels) per multi-vector query (vrod_search_multivec).  `vectors`: a list of [m_i, dim]
+        arrays, one per query, or -- with lims [nq + 1] -- all vectors as [n, dim], query q owning rows lims[q]:lims[q + 1].
+        -> (labels uint32 [nq, k], scores float32 [nq, k], found uint32 [nq]); slots past found[q] are (0, NaN)."""
+        vectors, la = self._multivec_args(vectors, lims)
+        nq = la.size - 1
+        lab = np.empty((nq, k), dtype=np.uint32)
+        sc = np.empty((nq, k), dtype=np.float32)
+        found = np.empty(nq, dtype=np.uint32)
+        check(self._L.vrod_search_multivec(self._h, vectors.ctypes.data_as(C.c_void_p), la.ctypes.data_as(C.c_void_p), nq, int(k),
+                                           lab.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p), found.ctypes.data_as(C.c_void_p)))
+        return lab, sc, found
+
+    def search_multivec_device(self, d_vectors, d_lims, k: int, out_labels=None, out_scores=None, out_found=None, want_found=True):
+        """torch CUDA tensors: vectors [n, dim] fp32, lims [nq + 1] int32 (the bits of uint32) -> (labels int32-viewed-uint32
+        [nq, k], scores [nq, k], found int32 [nq]) on the device, complete on return.  want_found=False passes no found
+        buffer (found is None)."""
+        import torch
+        assert d_vectors.is_cuda and d_vectors.dtype == torch.float32 and d_vectors.is_contiguous()
+        if d_vectors.dim() != 2 or d_vectors.shape[1] != self.dim:
+            raise ValueError(f"vectors must be [n, {self.dim}]")
+        if d_lims.dtype != torch.int32:
+            raise TypeError(f"lims must be an int32 tensor, got {d_lims.dtype}")
+        if d_lims.dim() != 1 or d_lims.numel() < 1:
+            raise ValueError("lims must be a vector of nq + 1 entries")
+        assert d_lims.is_cuda and d_lims.is_contiguous()
+        nq = d_lims.numel() - 1
+        if out_labels is None:
+            out_labels = torch.empty((nq, k), dtype=torch.int32, device=d_vectors.device)
+        if out_scores is None:
+            out_scores = torch.empty((nq, k), dtype=torch.float32, device=d_vectors.device)
+        if out_found is None and want_found:
+            out_found = torch.empty((nq,), dtype=torch.int32, device=d_vectors.device)
+        stream = torch.cuda.current_stream(d_vectors.device).cuda_stream
+        check(self._L.vrod_search_multivec_device(self._h, d_vectors.data_ptr(), d_lims.data_ptr(), nq, int(k), out_labels.data_ptr(),
+                                                  out_scores.data_ptr(), out_found.data_ptr() if out_found is not None else None,
+                                                  C.c_void_p(stream)))
+        return out_labels, out_scores, out_found
+
+    def last_multivec(self) -> dict:
+        """What the last search_multivec call did (vrod_index_last_multivec): which route answered how many queries."""
+        st = MultivecStats()
+        check(self._L.vrod_index_last_multivec(self._h, C.byref(st)))
+        return st.as_dict()
 
     # -- search by stored row: the queries are rows the handle already holds, used as stored
     @classmethod
