@@ -62,6 +62,9 @@ pub struct vrod_tag_pred {
     pub none: u64,
 }
 
+/// The largest `pool` of `vrod_search_diverse`.
+pub const VROD_MAX_DIVERSE_POOL: u32 = 1024;
+
 /// The most vectors one query of `vrod_search_multivec` may hold.
 pub const VROD_MAX_QUERY_VECTORS: u32 = 256;
 
@@ -160,6 +163,12 @@ extern "C" {
                                        k: u32, d_out_labels: *mut u32, d_out_scores: *mut f32, d_out_found: *mut u32,
                                        stream: *mut c_void) -> c_int;
     pub fn vrod_index_last_multivec(idx: *const vrod_index, out: *mut vrod_multivec_stats) -> c_int;
+    /// Exact greedy MMR over the certified top `pool`; rows come back in selection order; `out_mmr` may be null.
+    pub fn vrod_search_diverse(idx: *mut vrod_index, queries: *const f32, nq: u32, k: u32, pool: u32, lambda: f32,
+                               out_ids: *mut u64, out_scores: *mut f32, out_mmr: *mut f32) -> c_int;
+    pub fn vrod_search_diverse_device(idx: *mut vrod_index, d_queries: *const f32, nq: u32, k: u32, pool: u32, lambda: f32,
+                                      d_out_ids: *mut u64, d_out_scores: *mut f32, d_out_mmr: *mut f32,
+                                      stream: *mut c_void) -> c_int;
 }
 
 /// Joins the reference's `thiserror` enums (`src/main.rs:36-40`, `src/command/builder.rs:10-15`).

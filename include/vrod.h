@@ -391,6 +391,42 @@ int vrod_search_multivec_device(vrod_index *idx, const float *d_vectors, const u
                                 uint32_t *d_out_labels, float *d_out_scores, uint32_t *d_out_found, void *stream);
 int vrod_index_last_multivec(const vrod_index *idx, vrod_multivec_stats *out);
 
+/* Diversified search -- exact greedy Maximal Marginal Relevance over the certified top pool: the answer to "the ten rows
+ * are ten copies of the same thing" when nobody has labelled the copies.  Per query:
+ *   pool       what vrod_search returns for it with k = pool over the eligible rows (live, and allowed while a filter is
+ *              set): positions 0 .. m-1, best first, m = the filled slots (m <= pool), r_i = the canonical score at
+ *              position i.  Labels and tags are ignored.
+ *   pair score g(i, j) = the canonical score between the PREPARED stored rows at positions i and j, used as stored, exactly
+ *              as vrod_search_by_ids scores a stored row against another (the chain is symmetric in its operands for all
+ *              three metrics).
+ *   redundancy pen_i = the best g(i, s) over the rows s selected so far -- the maximum for COSINE and IP, the minimum for
+ *              L2, folded in selection order, an equal g changing nothing; a NaN g loses to any number, pen_i is NaN only
+ *              if every such g is NaN.
+ *   selection  step 0 takes position 0.  Step t >= 1 evaluates every position i not selected yet, with mu = fl(1 - lambda):
+ *                  v_i = fl( fl(lambda * r_i) - fl(mu * pen_i) )
+ *              every operation rounded once to fp32, no fused multiply-add, and takes the largest v for COSINE and IP, the
+ *              smallest for L2; values compare as fp32 (-0.0 == +0.0), a NaN v loses to any number, ties -- an all-NaN step
+ *              included -- go to the smaller pool position.  min(k, m) steps.
+ *   result     row q of out_ids / out_scores / out_mmr (nq x k) lists the selected rows in SELECTION order: the id
+ *              (id_offset applied), r_i -- the oracle's bits -- and v at the moment of selection, slot 0 holding
+ *              fl(lambda * r_0); out_mmr may be NULL.  Slots past min(k, m) are (VROD_ID_NONE, NaN, NaN).
+ * lambda = 1 reproduces vrod_search's first k bit for bit on finite scores; lambda = 0 ranks by redundancy alone.
+ * k = 0, k > pool, pool > VROD_MAX_DIVERSE_POOL, lambda NaN or outside [0, 1], null pointers: VROD_ERR_INVALID_ARG; NaN or
+ * Inf in the queries: VROD_ERR_INVALID_VALUE, as vrod_search; nq == 0: VROD_OK.  Every check comes before the first write: a
+ * refused call leaves the outputs untouched.  An empty handle, or one without an eligible row, gives all-unfilled rows
+ * without looking at the queries.  Synchronous: no _begin_ form, no graph replay; VROD_ERR_INVALID_ARG while a search is
+ * pending; the _device form takes device pointers and returns after the results are complete in device memory.
+ * Multi-device handles: VROD_ERR_UNSUPPORTED, the outputs are not touched.
+ * The first stage is the ordinary certified search with `pool` results (vrod_index_set_path is honoured by it); one more
+ * launch then selects on the device, a work-group per query with its state in LDS, scoring the pool against each newly
+ * selected row with the canonical chain: k * m chains, never the m x m matrix.  vrod_index_last_stats afterwards reports
+ * the first-stage search, with k = the caller's k. */
+#define VROD_MAX_DIVERSE_POOL 1024u
+int vrod_search_diverse(vrod_index *idx, const float *queries, uint32_t nq, uint32_t k, uint32_t pool, float lambda,
+                        uint64_t *out_ids, float *out_scores, float *out_mmr);
+int vrod_search_diverse_device(vrod_index *idx, const float *d_queries, uint32_t nq, uint32_t k, uint32_t pool, float lambda,
+                               uint64_t *d_out_ids, float *d_out_scores, float *d_out_mmr, void *stream);
+
 /* Search by stored row id ("more like this") -- query q is the PREPARED stored row ids[q] (nq ids as searches report
  * them, id_offset applied; host memory, the _device form: device memory), used as stored: it is not normalised again and
  * not rounded again, so the scores are scores between stored rows and an L2 row is at distance +0.0 from itself.  The

@@ -37,6 +37,7 @@
 #include "tag_plan.h"
 #include "group_plan.h"
 #include "multivec_plan.h"
+#include "diverse_plan.h"
 #include "byid_plan.h"
 
 using namespace vrod;
@@ -44,6 +45,8 @@ using namespace vrod;
 static_assert(kGroupMaxK == VROD_MAX_K, "group_plan.h restates the largest k of the ABI");
 static_assert(kByidMaxK == VROD_MAX_K, "byid_plan.h restates the largest k of the ABI");
 static_assert(kMultivecMaxK == VROD_MAX_K && kMultivecMaxVectors == VROD_MAX_QUERY_VECTORS, "multivec_plan.h restates the ABI's limits");
+static_assert(kDiverseMaxPool == VROD_MAX_DIVERSE_POOL && kDiverseMaxPool <= VROD_MAX_K && kDiverseMaxDim == VROD_MAX_DIM,
+              "diverse_plan.h restates the ABI's limits");
 
 // ------------------------------------------------------------------ errors
 static thread_local std::string g_last_error;
@@ -243,6 +246,9 @@ struct vrod_index {
     DevBuf mv_q, mv_ids, mv_scores, mv_ent, mv_tab, mv_cand, mv_small, mv_best, mv_S, mv_absent, mv_M, mv_pairs, mv_raw, mv_lims, mv_out_labels,
         mv_out_scores, mv_found;
     vrod_multivec_stats mv_stats{};
+    // diversified search (vrod_search_diverse): the first-stage lists [nq][pool], and the host form's raw queries and
+    // its selection values
+    DevBuf dv_ids, dv_scores, dv_qraw, dv_mmr;
     // Searches whose queries are stored rows (vrod_search_by_ids, vrod_knn_graph) hand the search flow rows that are
     // prepared already: while prep_ovr is not negative it stands for prep_form(metric) in the launch that prepares a
     // search's queries -- M_L2, the take-as-given form of L2 and IP handles: nothing is normalised, and rounding a bf16
@@ -3288,6 +3294,37 @@ static int multivec_search(vrod_index* idx, const float* d_raw, const uint32_t* 
     return VROD_OK;
 }
 
+// ------------------------------------------------------------------ diversified search (vrod_search_diverse)
+// The ordinary certified search with `pool` results per query into the handle's lists, then ONE launch of the selection
+// kernel (kernels_diverse.hip): a work-group per query picks min(k, filled) rows of its list by exact greedy MMR.  The
+// first stage refuses NaN / Inf queries before anything is written; the outputs are written by the selection alone.
+// Synchronous: the handle is idle before and after.  Every pointer is device memory; d_out_mmr may be null.
+static int diverse_search(vrod_index* idx, const float* d_queries_raw, uint32_t nq, uint32_t k, uint32_t pool, float lambda,
+                          uint64_t* d_out_ids, float* d_out_scores, float* d_out_mmr) {
+    if (idx->count == 0 || idx->eligible() == 0) {   // no eligible row: every slot unfilled, the queries are not looked at
+        vrod_search_stats st{};
+        st.nq = nq; st.k = k; st.path = (uint32_t)idx->path;
+        hipStream_t s = next_slot(idx).stream;
+        launch_fill_none(d_out_ids, d_out_scores, (uint64_t)nq * k, s);
+        HIP_TRY(hipGetLastError());
+        if (d_out_mmr) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)d_out_mmr, (int)kScoreNoneBits, (size_t)nq * k, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        idx->stats = st;
+        return VROD_OK;
+    }
+    if (!diverse_waves(idx->dim, pool)) return fail(VROD_ERR_INTERNAL, "diversified search: no work-group fits dim %u, pool %u", idx->dim, pool);
+    VROD_TRY(idx->dv_ids.ensure((size_t)nq * pool * 8));
+    VROD_TRY(idx->dv_scores.ensure((size_t)nq * pool * 4));
+    VROD_TRY(run_search(idx, d_queries_raw, nq, pool, idx->dv_ids.as<uint64_t>(), idx->dv_scores.as<float>()));
+    idx->stats.k = k;
+    hipStream_t s = next_slot(idx).stream;
+    launch_diverse_select(idx->corpus, idx->dtype, score_form(idx->metric), idx->dim, idx->ld, idx->dv_ids.as<uint64_t>(),
+                          idx->dv_scores.as<float>(), nq, pool, k, lambda, idmap_of(idx).offset, d_out_ids, d_out_scores, d_out_mmr, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    return VROD_OK;
+}
+
 // ------------------------------------------------------------------ searches by stored row (vrod_search_by_ids, vrod_knn_graph)
 // The queries are rows the handle already holds: byid_gather_kernel copies them out of the corpus as fp32 (kernels_byid.hip)
 // and the ordinary search flow takes them as given (prep_ovr) -- the stored row is the query bit for bit, so the scores
@@ -3582,7 +3619,8 @@ int vrod_index_destroy(vrod_index* idx) {
                       &idx->lab_scores, &idx->lab_qraw, &idx->grp_ids, &idx->grp_scores, &idx->grp_small, &idx->grp_mask, &idx->grp_labels,
                       &idx->grp_qraw, &idx->byid_user_ids, &idx->doc_rank, &idx->doc_labels, &idx->mv_q, &idx->mv_ids, &idx->mv_scores, &idx->mv_ent,
                       &idx->mv_tab, &idx->mv_cand, &idx->mv_small, &idx->mv_best, &idx->mv_S, &idx->mv_absent, &idx->mv_M, &idx->mv_pairs,
-                      &idx->mv_raw, &idx->mv_lims, &idx->mv_out_labels, &idx->mv_out_scores, &idx->mv_found}) b->release();
+                      &idx->mv_raw, &idx->mv_lims, &idx->mv_out_labels, &idx->mv_out_scores, &idx->mv_found, &idx->dv_ids, &idx->dv_scores,
+                      &idx->dv_qraw, &idx->dv_mmr}) b->release();
     for (int c = 0; c < 2; ++c)
         for (DevBuf* b : {&idx->byid_ids[c], &idx->byid_scores[c], &idx->byid_out_ids[c], &idx->byid_out_scores[c], &idx->byid_map[c]}) b->release();
     if (idx->flags) (void)hipFree(idx->flags);
@@ -4059,6 +4097,52 @@ int vrod_index_last_multivec(const vrod_index* idx, vrod_multivec_stats* out) {
     if (!idx || !out) return fail(VROD_ERR_INVALID_ARG, "null argument");
     *out = idx->mv_stats;
     return VROD_OK;
+}
+
+static int check_diverse_args(vrod_index* idx, const void* q, uint32_t nq, uint32_t k, uint32_t pool, float lambda, const void* oi,
+                              const void* os) {
+    // (what the arguments alone decide comes first: it is checked, and tested, without a handle)
+    switch (diverse_check_args(k, pool, lambda)) {
+        case 0: break;
+        case 1: return fail(VROD_ERR_INVALID_ARG, "k must be at least 1");
+        case 2: return fail(VROD_ERR_INVALID_ARG, "k = %u is larger than the pool, %u", k, pool);
+        case 3: return fail(VROD_ERR_INVALID_ARG, "pool must be at most %u", VROD_MAX_DIVERSE_POOL);
+        default: return fail(VROD_ERR_INVALID_ARG, "lambda must be in [0, 1]");
+    }
+    if (!idx) return fail(VROD_ERR_INVALID_ARG, "idx is null");
+    if (nq && (!q || !oi || !os)) return fail(VROD_ERR_INVALID_ARG, "null buffer");
+    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "vrod_search_diverse on a multi-device handle: stored rows are not gathered across the shards");
+    return VROD_OK;
+}
+
+int vrod_search_diverse(vrod_index* idx, const float* queries, uint32_t nq, uint32_t k, uint32_t pool, float lambda, uint64_t* out_ids,
+                        float* out_scores, float* out_mmr) {
+    VROD_TRY(check_diverse_args(idx, queries, nq, k, pool, lambda, out_ids, out_scores));
+    if (!nq) return VROD_OK;
+    VROD_TRY(require_idle(idx, "vrod_search_diverse"));
+    VROD_TRY(set_device(idx));
+    VROD_TRY(idx->dv_qraw.ensure((size_t)nq * idx->dim * 4));
+    VROD_TRY(idx->out_ids.ensure((size_t)nq * k * 8));
+    VROD_TRY(idx->out_scores.ensure((size_t)nq * k * 4));
+    VROD_TRY(idx->dv_mmr.ensure((size_t)nq * k * 4));
+    HIP_TRY(hipMemcpy(idx->dv_qraw.p, queries, (size_t)nq * idx->dim * 4, hipMemcpyHostToDevice));
+    VROD_TRY(diverse_search(idx, idx->dv_qraw.as<float>(), nq, k, pool, lambda, idx->out_ids.as<uint64_t>(), idx->out_scores.as<float>(),
+                            idx->dv_mmr.as<float>()));
+    HIP_TRY(hipMemcpy(out_ids, idx->out_ids.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_scores, idx->out_scores.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    if (out_mmr) HIP_TRY(hipMemcpy(out_mmr, idx->dv_mmr.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    return VROD_OK;
+}
+
+int vrod_search_diverse_device(vrod_index* idx, const float* d_queries, uint32_t nq, uint32_t k, uint32_t pool, float lambda,
+                               uint64_t* d_out_ids, float* d_out_scores, float* d_out_mmr, void* stream) {
+    VROD_TRY(check_diverse_args(idx, d_queries, nq, k, pool, lambda, d_out_ids, d_out_scores));
+    if (!nq) return VROD_OK;
+    VROD_TRY(require_idle(idx, "vrod_search_diverse_device"));
+    VROD_TRY(set_device(idx));
+    // synchronous, as a range search: whatever the caller's stream holds is complete before the library's streams start
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return diverse_search(idx, d_queries, nq, k, pool, lambda, d_out_ids, d_out_scores, d_out_mmr);
 }
 
 static int check_byid_args(vrod_index* idx, const void* ids, uint32_t nq, uint32_t k, uint32_t flags, const void* oi, const void* os,

@@ -279,6 +279,15 @@ void launch_multivec_output(const uint64_t* d_keys, uint64_t key_ld, uint32_t kp
                             const uint32_t* d_tab_off, const uint32_t* d_qidx, uint32_t* d_out_labels, float* d_out_scores, uint32_t* d_found,
                             float* d_kth, hipStream_t s);
 
+// ---- kernels_diverse.hip : the greedy selection of a diversified search (vrod_search_diverse)
+// The search's lists d_list_ids / d_list_scores [nq][pool] (filled slots first, ids with id_offset applied) -> per query
+// min(k, filled) rows by exact greedy MMR in selection order: d_out_ids / d_out_scores [nq][k], and v at the moment of
+// selection in d_out_mmr (may be null); the slots no step fills are (~0, NaN, NaN).  mu = fl(1 - lambda) is taken here.
+// One work-group per query; pool <= kDiverseMaxPool, dim <= kDiverseMaxDim (diverse_plan.h sizes the work-group).
+void launch_diverse_select(const void* d_corpus, int dtype, int metric, uint32_t dim, uint32_t ld, const uint64_t* d_list_ids,
+                           const float* d_list_scores, uint32_t nq, uint32_t pool, uint32_t k, float lambda, uint64_t id_offset,
+                           uint64_t* d_out_ids, float* d_out_scores, float* d_out_mmr, hipStream_t s);
+
 // ---- kernels_byid.hip : queries taken from stored rows (vrod_search_by_ids, vrod_knn_graph)
 // Rows [row0, row0 + m) against the deleted-row bitmap d_del (not null): d_live[j] = the j-th live row, ascending;
 // d_src[i] = j for the live row row0 + i, ~0u for a deleted one.  One work-group: m is a batch.

@@ -20,6 +20,7 @@ ID_NONE = np.uint64(0xFFFFFFFFFFFFFFFF)
 MAX_K = 3584
 BYID_EXCLUDE_SELF = 1   # VROD_BYID_EXCLUDE_SELF
 MAX_QUERY_VECTORS = 256   # VROD_MAX_QUERY_VECTORS
+MAX_DIVERSE_POOL = 1024   # VROD_MAX_DIVERSE_POOL
 # rows per batch of knn_graph() by storage type (byid_plan.h: kByidBatchF32, kByidBatchBf16)
 KNN_BATCH = {0: 256, 1: 1024}
 
@@ -429,6 +430,44 @@ class Index:
         st = MultivecStats()
         check(self._L.vrod_index_last_multivec(self._h, C.byref(st)))
         return st.as_dict()
+
+    # -- diversified search: exact greedy MMR over the certified top pool
+    def search_diverse(self, queries: np.ndarray, k: int, pool: int, lam: float):
+        """k rows of the `pool` best per query, picked greedily by lam * relevance - (1 - lam) * similarity to the rows
+        already picked (vrod_search_diverse): numpy [nq, dim] fp32 -> (ids uint64 [nq, k], scores float32 [nq, k], mmr
+        float32 [nq, k]) in selection order; slots past the eligible rows are (ID_NONE, NaN, NaN)."""
+        queries = np.ascontiguousarray(queries, dtype=np.float32)
+        if queries.ndim == 1:
+            queries = queries[None, :]
+        if queries.ndim != 2 or queries.shape[1] != self.dim:
+            raise ValueError(f"queries must be [nq, {self.dim}]")
+        nq = queries.shape[0]
+        ids = np.empty((nq, k), dtype=np.uint64)
+        sc = np.empty((nq, k), dtype=np.float32)
+        mmr = np.empty((nq, k), dtype=np.float32)
+        check(self._L.vrod_search_diverse(self._h, queries.ctypes.data_as(C.c_void_p), nq, int(k), int(pool), float(lam),
+                                          ids.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p), mmr.ctypes.data_as(C.c_void_p)))
+        return ids, sc, mmr
+
+    def search_diverse_device(self, d_queries, k: int, pool: int, lam: float, out_ids=None, out_scores=None, out_mmr=None, want_mmr=True):
+        """torch CUDA tensor [nq, dim] fp32 -> (ids int64-viewed-uint64 [nq, k], scores [nq, k], mmr [nq, k]) on the device,
+        complete on return.  want_mmr=False passes no mmr buffer (mmr is None)."""
+        import torch
+        assert d_queries.is_cuda and d_queries.dtype == torch.float32 and d_queries.is_contiguous()
+        if d_queries.dim() != 2 or d_queries.shape[1] != self.dim:
+            raise ValueError(f"queries must be [nq, {self.dim}]")
+        nq = d_queries.shape[0]
+        if out_ids is None:
+            out_ids = torch.empty((nq, k), dtype=torch.int64, device=d_queries.device)
+        if out_scores is None:
+            out_scores = torch.empty((nq, k), dtype=torch.float32, device=d_queries.device)
+        if out_mmr is None and want_mmr:
+            out_mmr = torch.empty((nq, k), dtype=torch.float32, device=d_queries.device)
+        stream = torch.cuda.current_stream(d_queries.device).cuda_stream
+        check(self._L.vrod_search_diverse_device(self._h, d_queries.data_ptr(), nq, int(k), int(pool), float(lam), out_ids.data_ptr(),
+                                                 out_scores.data_ptr(), out_mmr.data_ptr() if out_mmr is not None else None,
+                                                 C.c_void_p(stream)))
+        return out_ids, out_scores, out_mmr
 
     # -- search by stored row: the queries are rows the handle already holds, used as stored
     @classmethod
