@@ -391,3 +391,31 @@ def test_route_mixed(topical_handle):
     assert mv["certified_queries"] + mv["dense_queries"] == ok.size
     assert mv["certified_queries"] == int(ok.sum()), (mv, ok.tolist())
     assert_same(device_form(ix, vec, lims, k), model.rank(present, S, k), "mixed k=10 device form")
+
+
+# ------------------------------------------------------------------------------------------- more than one label pass
+def test_candidate_route_over_several_label_passes(va):
+    """The candidate route counts, lists and scores its labels in passes of kLabelGroupsPerPass = 4096 (label_plan.h).
+    Every row its own document and 512 single-vector queries: their top-k1 lists name far more labels than one pass
+    holds, so the counting loop and the list / score loop both run more than once."""
+    n, dim, nq, k, per_pass = 16_384, 32, 512, 8, 4096
+    rng = np.random.default_rng(4097)
+    raw = rng.standard_normal((n, dim)).astype(np.float32)
+    vec = rng.standard_normal((nq, dim)).astype(np.float32)
+    labels = rng.permutation(n).astype(np.uint32) * np.uint32(3) + np.uint32(1)      # distinct, scattered, none of them 0
+    lims = lims_of([1] * nq)
+    model = MultivecModel(dim, "f32", "l2")
+    with make_index(va, model, raw, labels) as ix:
+        k1 = first_k(k, n)
+        assert k1 == 40
+        ids, _ = model._topk(np.arange(n), model._queries(vec), k1)                  # the exact lists of the first stage
+        distinct = np.unique(labels[ids.astype(np.int64)]).size
+        print("distinct candidate labels", distinct)
+        assert distinct > per_pass, f"premise: {distinct} distinct labels in the top-{k1} lists"
+        assert_same(ix.search_multivec(vec, k, lims=lims), model.search_multivec(vec, lims, k), "several label passes")
+        mv, st = ix.last_multivec(), ix.last_stats()
+        print(mv, st)
+        assert mv["candidate_labels"] > 0 and mv["certified_queries"] + mv["dense_queries"] == nq and mv["k1"] == k1, mv
+        # no list holds a NaN, 40 candidate rows are not too broad and 512 * 40 score slots fit (multivec_plan.h): every
+        # query stays on the candidate route up to the certificate, so all `distinct` labels are listed and scored
+        assert mv["candidate_labels"] == nq * k1 and mv["candidate_rows"] == nq * k1, mv

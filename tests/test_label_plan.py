@@ -5,7 +5,10 @@ with g++ against the real header.
   - plan_segments + seg_lookup (the function the score kernel calls per block): over all blocks of all chunks, every
     (score slot, 64-row tile) pair of every group is covered exactly once, a block's queries stay inside its entry, a
     short last subgroup covers only its own queries, consecutive blocks of one tile are neighbours, every slot belongs
-    to exactly one chunk and a chunk's score block respects the byte limit (groups of fewer than 8 queries aside)."""
+    to exactly one chunk and a chunk's score block respects the byte limit (groups of fewer than 8 queries aside);
+  - SlotTables::add, which builds those groups and the per-slot arrays of a pass: a group's slot0 is the running slot
+    count, slot_len / slot_base repeat its m / list_base once per query, slot_q lists its queries in the order given,
+    and the groups it built pass the coverage checks above."""
 import itertools
 import os
 import shutil
@@ -45,11 +48,27 @@ int main() {
             scanf("%u %llu", &ng, &limit);
             std::vector<SegGroup> gs(ng);
             uint32_t slot = 0, base = 0;
-            for (unsigned i = 0; i < ng; ++i) {
-                unsigned m, nq;
-                scanf("%u %u", &m, &nq);
-                gs[i] = SegGroup{base, m, slot, nq};
-                slot += nq; base += m;
+            if (what == 'T') {   // the groups through SlotTables::add, each with its queries
+                SlotTables t;
+                for (unsigned i = 0; i < ng; ++i) {
+                    unsigned m, nq;
+                    scanf("%u %u", &m, &nq);
+                    std::vector<uint32_t> q(nq + 1);
+                    for (unsigned j = 0; j < nq; ++j) scanf("%u", &q[j]);
+                    t.add(base, m, q.data(), nq);
+                    base += m;
+                }
+                printf("T %zu %u %zu %zu %zu\n", t.segs.size(), t.size(), t.slot_q.size(), t.slot_len.size(), t.slot_base.size());
+                for (const SegGroup& g : t.segs) printf("g %u %u %u %u\n", g.list_base, g.m, g.slot0, g.nq);
+                for (uint32_t i = 0; i < t.size(); ++i) printf("s %u %u %u\n", t.slot_q[i], t.slot_len[i], t.slot_base[i]);
+                gs = t.segs;
+            } else {
+                for (unsigned i = 0; i < ng; ++i) {
+                    unsigned m, nq;
+                    scanf("%u %u", &m, &nq);
+                    gs[i] = SegGroup{base, m, slot, nq};
+                    slot += nq; base += m;
+                }
             }
             const SegPlan p = limit ? plan_segments(gs, limit) : plan_segments(gs);
             printf("P %zu %zu\n", p.entries.size(), p.chunks.size());
@@ -115,10 +134,8 @@ def test_label_groups(run, labels):
         assert g[1:] == [i for i, l in enumerate(labels) if l == g[0]]      # every query of the label, ascending
 
 
-@pytest.mark.parametrize("case", range(len(seg_cases())))
-def test_work_table_covers_every_query_tile_pair_once(run, case):
-    groups, limit = seg_cases()[case]
-    out = run(f"S {len(groups)} {limit} " + " ".join(f"{m} {nq}" for m, nq in groups) + "\n")
+def check_coverage(out, groups, limit):
+    """`out`: the driver's lines from "P ..." on, for `groups` = [(m, nq)] laid out group after group."""
     n_entries, n_chunks = (int(x) for x in out[0].split()[1:])
     limit_bytes = limit or (1 << 30)
     slot0, base = [], []
@@ -167,3 +184,38 @@ def test_work_table_covers_every_query_tile_pair_once(run, case):
     assert entries_seen == set(range(n_entries))
     want = {(sl, t) for sl, (lb, m) in owner.items() for t in range(-(-m // 64))}
     assert set(seen) == want
+
+
+@pytest.mark.parametrize("case", range(len(seg_cases())))
+def test_work_table_covers_every_query_tile_pair_once(run, case):
+    groups, limit = seg_cases()[case]
+    check_coverage(run(f"S {len(groups)} {limit} " + " ".join(f"{m} {nq}" for m, nq in groups) + "\n"), groups, limit)
+
+
+# (m, the group's queries): nq = 1, m = 0, several groups in a row, queries neither sorted nor distinct across groups
+SLOT_CASES = [
+    [(5, [7])],
+    [(0, [3, 1])],
+    [(65, [4, 0, 9]), (0, [2]), (1, [8]), (130, list(range(30, 10, -1))), (0, [5, 6]), (64, [1, 1, 3])],
+    [(m, list(range(100 * i, 100 * i + nq))) for i, (m, nq) in enumerate(itertools.product(M_SET + [200], NQ_SET + [2, 5, 17]))],
+]
+
+
+@pytest.mark.parametrize("limit", [0, 64 * 4 * 16])
+@pytest.mark.parametrize("case", range(len(SLOT_CASES)))
+def test_slot_tables(run, case, limit):
+    groups = SLOT_CASES[case]
+    out = run(f"T {len(groups)} {limit} " + " ".join(f"{m} {len(qs)} " + " ".join(map(str, qs)) for m, qs in groups) + "\n")
+    n_slots = sum(len(qs) for _, qs in groups)
+    assert [int(x) for x in out[0].split()[1:]] == [len(groups), n_slots, n_slots, n_slots, n_slots]
+    segs = [tuple(int(x) for x in line.split()[1:]) for line in out[1:1 + len(groups)]]
+    slots = [tuple(int(x) for x in line.split()[1:]) for line in out[1 + len(groups):1 + len(groups) + n_slots]]
+    slot0 = base = 0
+    for (m, qs), seg in zip(groups, segs):
+        assert seg == (base, m, slot0, len(qs))                      # slot0: the running slot count
+        mine = slots[slot0:slot0 + len(qs)]
+        assert [s[0] for s in mine] == qs                            # its queries, in the order given
+        assert all(s[1] == m and s[2] == base for s in mine)         # m and list_base, once per query
+        slot0 += len(qs)
+        base += m
+    check_coverage(out[1 + len(groups) + n_slots:], [(m, len(qs)) for m, qs in groups], limit)

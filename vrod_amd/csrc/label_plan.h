@@ -55,6 +55,20 @@ inline uint32_t label_rows_per_block(uint64_t N) {
 // A segmented group: `nq` queries, in score slots [slot0, slot0 + nq), over the `m` rows of its segment of the list
 // buffer.  Slots number the queries of the segmented groups only, group after group.
 struct SegGroup { uint32_t list_base, m, slot0, nq; };
+// The segmented groups of one pass as plan_segments and the score launch take them, group after group: slot s is query
+// slot_q[s] over the slot_len[s] list entries from slot_base[s] on.
+struct SlotTables {
+    std::vector<SegGroup> segs;
+    std::vector<uint32_t> slot_q, slot_len, slot_base;
+    uint32_t size() const { return (uint32_t)slot_q.size(); }
+    // a group of `nq` queries over the `m` rows of the list buffer from `list_base` on: the next `nq` slots
+    void add(uint32_t list_base, uint32_t m, const uint32_t* queries, uint32_t nq) {
+        segs.push_back({list_base, m, size(), nq});
+        slot_q.insert(slot_q.end(), queries, queries + nq);
+        slot_len.insert(slot_len.end(), nq, m);
+        slot_base.insert(slot_base.end(), nq, list_base);
+    }
+};
 // Queries per lane a group's blocks take (the NQ of rescore_all_body): 8 once the group has 5, so that a group's last
 // subgroup never needs a second kernel form.
 VROD_LABEL_HD inline uint32_t seg_query_class(uint32_t nq) { return nq >= 5 ? 8u : nq >= 3 ? 4u : nq; }

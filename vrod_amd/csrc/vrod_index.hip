@@ -141,6 +141,8 @@ struct Pending {
     bool early_sample = false;     // its sample pass was ordered in front of the previous search's last stage
     uint32_t kp_boost_used = 1;    // the candidate-margin multiplier this search was enqueued with
     vrod_search_stats st{};
+    // a synchronous search that times its own launches starts from no event in use
+    void reset_events() { ev_used = 0; scan_pairs.clear(); sample_pair = -1; tail_pair = -1; }
 
     // hipGraph replay of small, launch-bound searches (search_enqueue): the launches of a search
     // whose every pointer and size equals the captured one are replayed as one graph launch
@@ -711,6 +713,25 @@ struct Timer {
         float m = 0.f;
         if (idx->profiling && a < P.ev_used && b < P.ev_used) (void)hipEventElapsedTime(&m, P.ev[a], P.ev[b]);
         return m;
+    }
+    // Markers around ONE launch on the slot's stream, for launches that take no launch-attached events: begin_launch in
+    // front of it, end_launch behind it.  Nothing is created or recorded while profiling is off.
+    int begin_launch(size_t& a, size_t& b) {
+        a = b = 0;
+        if (!idx->profiling) return VROD_OK;
+        arm(a, b);
+        g_launch_events = LaunchEvents{};
+        if (b) HIP_TRY(hipEventRecord(P.ev[a], P.stream));
+        return VROD_OK;
+    }
+    int end_launch(size_t a, size_t b) {
+        if (idx->profiling && b) { HIP_TRY(hipEventRecord(P.ev[b], P.stream)); P.scan_pairs.push_back({a, b}); }
+        return VROD_OK;
+    }
+    // the time between the markers of every launch so far, added to st.scan_ms (the stream is drained)
+    void add_scan_ms(vrod_search_stats& st) {
+        if (idx->profiling)
+            for (size_t i = 0; i < P.scan_pairs.size(); ++i) st.scan_ms += ms(P.scan_pairs[i].first, P.scan_pairs[i].second);
     }
     // The LAST filtered launch of a staged MFMA search is timed by events of the handle's ring instead (tail_ev[seq & 3]):
     // the next search's sample pass may run beside it, and that search wants both intervals when it is completed --
@@ -2441,9 +2462,18 @@ static void fold_stats(vrod_search_stats& st, const vrod_search_stats& d) {
     st.split_pass |= d.split_pass;
 }
 
-// The three steps a labelled and a tagged search share (the second groups by predicate, not by label).
+// The steps the synchronous searches over groups of queries share (labelled, tagged, grouped, multi-vector).
+// No eligible row can answer: every result slot unfilled (as vrod_search), the stream drained, `st` the call's stats.
+static int return_unfilled(vrod_index* idx, hipStream_t s, const vrod_search_stats& st, uint64_t* d_out_ids, float* d_out_scores, uint64_t n) {
+    launch_fill_none(d_out_ids, d_out_scores, n, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    idx->stats = st;
+    return VROD_OK;
+}
+
 // Prepare the batch's queries into P.q_f32 as a search does; NaN / Inf fails the call before anything is scored.
-static int prep_group_queries(vrod_index* idx, Pending& P, const float* d_queries_raw, uint32_t nq) {
+static int prep_queries_checked(vrod_index* idx, Pending& P, const float* d_queries_raw, uint32_t nq) {
     hipStream_t s = P.stream;
     P.plan = SearchPlan{};
     P.plan.nq_pad = nq;
@@ -2463,50 +2493,99 @@ static int prep_group_queries(vrod_index* idx, Pending& P, const float* d_querie
     return VROD_OK;
 }
 
-// The segmented route of one pass: `segs` over the row lists in idx->lab_lists (enqueued on the slot's stream already),
-// slot s = query slot_q[s] over slot_len[s] rows from slot_base[s] on; d_slot: 3 * nq words of device memory.  Score +
-// select, one launch of each kind per chunk of the score block.  Returns with the stream drained.
-static int score_segments(vrod_index* idx, Pending& P, Timer& tm, vrod_search_stats& st, const std::vector<SegGroup>& segs,
-                          const std::vector<uint32_t>& slot_q, const std::vector<uint32_t>& slot_len, const std::vector<uint32_t>& slot_base,
-                          uint32_t* d_slot, uint32_t nq, uint32_t k, uint64_t* d_out_ids, float* d_out_scores) {
+// The two passes over the label array (kernels_label.hip) for up to Gc labels at a time.  Their workspace: lab_tab as
+// [table | totals | segment offsets], Gc words each, and the per-block counts in lab_cnt.
+struct LabelPassWs { uint32_t rpb; uint32_t* table; uint32_t* total; uint32_t* seg_off; uint32_t* cnt; };
+static int label_pass_ws(vrod_index* idx, uint32_t Gc, LabelPassWs& W) {
+    const uint32_t rpb = label_rows_per_block(idx->count);
+    const uint32_t n_blocks = (uint32_t)((idx->count + rpb - 1) / rpb);
+    VROD_TRY(idx->lab_tab.ensure((size_t)Gc * 4 * 3));
+    VROD_TRY(idx->lab_cnt.ensure((size_t)n_blocks * Gc * 4));
+    uint32_t* t = idx->lab_tab.as<uint32_t>();
+    W = LabelPassWs{rpb, t, t + Gc, t + 2 * (size_t)Gc, idx->lab_cnt.as<uint32_t>()};
+    return VROD_OK;
+}
+// Pass 1: the eligible rows of each of the Gp labels h_table, counted per block of the label array and in all.
+// h_total: the totals are read back into it, and the stream is drained; null: the launch is only enqueued.
+static int label_count_pass(vrod_index* idx, hipStream_t s, const LabelPassWs& W, const uint32_t* h_table, uint32_t Gp, uint32_t* h_total) {
+    HIP_TRY(hipMemcpyAsync(W.table, h_table, (size_t)Gp * 4, hipMemcpyHostToDevice, s));
+    launch_label_group_count(idx->lab_dev, idx->row_mask(), idx->count, W.rpb, W.table, Gp, W.cnt, W.total, s);
+    if (!h_total) return VROD_OK;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h_total, W.total, (size_t)Gp * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return VROD_OK;
+}
+// Pass 2, behind pass 1 over the same table: the rows of every label with a segment offset (not kNoSegment) written to
+// idx->lab_lists from that offset on, ascending; list_n rows in all.
+static int label_scatter_pass(vrod_index* idx, hipStream_t s, const LabelPassWs& W, const uint32_t* h_seg_off, uint32_t Gp, uint64_t list_n) {
+    VROD_TRY(idx->lab_lists.ensure(std::max<uint64_t>(list_n, 1) * 4));
+    HIP_TRY(hipMemcpyAsync(W.seg_off, h_seg_off, (size_t)Gp * 4, hipMemcpyHostToDevice, s));
+    if (list_n)
+        launch_label_group_scatter(idx->lab_dev, idx->row_mask(), idx->count, W.rpb, W.table, Gp, W.cnt, W.seg_off, idx->lab_lists.as<uint32_t>(), s);
+    HIP_TRY(hipGetLastError());
+    return VROD_OK;
+}
+
+// Device copies of a pass's slot tables (label_plan.h SlotTables): [slot_q | slot_len | slot_base], n words each.
+struct DevSlots { uint32_t* q; uint32_t* len; uint32_t* base; };
+static DevSlots dev_slots(uint32_t* p, size_t n) { return {p, p + n, p + 2 * n}; }
+
+// The segmented route of one pass: the groups of T over the row lists in idx->lab_lists (enqueued on the slot's stream
+// already), scored against the prepared queries d_q.  The tables go to D (slot_base only where the pass has one), then
+// per chunk of the score block ONE score launch into P.scores -- between markers when `tm` is given -- and
+// step(chunk, out_ld), which enqueues what reads the chunk's scores.  Returns with the stream drained.
+template <typename Step>
+static int run_segments(vrod_index* idx, Pending& P, Timer* tm, vrod_search_stats& st, const float* d_q, const SlotTables& T, const DevSlots& D,
+                        Step&& step) {
     hipStream_t s = P.stream;
-    const int form = score_form(idx->metric);
-    uint32_t* d_slot_q = d_slot;
-    uint32_t* d_slot_len = d_slot_q + nq;
-    uint32_t* d_slot_base = d_slot_len + nq;
-    const uint32_t ns = (uint32_t)slot_q.size();
-    const SegPlan plan = plan_segments(segs);
+    const uint32_t ns = T.size();
+    const SegPlan plan = plan_segments(T.segs);
     VROD_TRY(idx->lab_entries.ensure(std::max<size_t>(plan.entries.size(), 1) * sizeof(SegEntry)));
-    HIP_TRY(hipMemcpyAsync(d_slot_q, slot_q.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_slot_len, slot_len.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_slot_base, slot_base.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(D.q, T.slot_q.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(D.len, T.slot_len.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s));
+    if (!T.slot_base.empty()) HIP_TRY(hipMemcpyAsync(D.base, T.slot_base.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s));
     if (!plan.entries.empty())
         HIP_TRY(hipMemcpyAsync(idx->lab_entries.p, plan.entries.data(), plan.entries.size() * sizeof(SegEntry), hipMemcpyHostToDevice, s));
     for (const SegChunk& c : plan.chunks) {
-        const uint64_t n_sel = std::max<uint32_t>(c.max_m, 1);
-        const uint64_t out_ld = round_up(n_sel, 64);
+        const uint64_t out_ld = round_up(std::max<uint32_t>(c.max_m, 1), 64);
         VROD_TRY(P.scores.ensure((size_t)c.n_slots * out_ld * 4));
         if (c.n_blocks) {
             size_t a = 0, b = 0;
-            if (idx->profiling) {   // (markers around the launch, as the gather path)
-                tm.arm(a, b);
-                g_launch_events = LaunchEvents{};
-                if (b) HIP_TRY(hipEventRecord(P.ev[a], s));
-            }
-            launch_rescore_segments(idx->corpus, idx->dtype, form, idx->dim, idx->ld, P.q_f32.as<float>(),
-                                    idx->lab_entries.as<SegEntry>() + c.e0, c.e1 - c.e0, c.n_blocks, d_slot_q, c.slot0,
-                                    idx->lab_lists.as<uint32_t>(), P.scores.as<float>(), out_ld, s);
-            if (idx->profiling && b) { HIP_TRY(hipEventRecord(P.ev[b], s)); P.scan_pairs.push_back({a, b}); }
+            if (tm) VROD_TRY(tm->begin_launch(a, b));
+            launch_rescore_segments(idx->corpus, idx->dtype, score_form(idx->metric), idx->dim, idx->ld, d_q, idx->lab_entries.as<SegEntry>() + c.e0,
+                                    c.e1 - c.e0, c.n_blocks, D.q, c.slot0, idx->lab_lists.as<uint32_t>(), P.scores.as<float>(), out_ld, s);
+            if (tm) VROD_TRY(tm->end_launch(a, b));
             st.scan_launches++;
         }
-        const uint32_t kx = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(k, n_sel), kSelectChunk / 2);   // (the rest: unfilled)
-        const uint64_t* keys; uint64_t kld, kn;
-        VROD_TRY(select_chain(idx, P, P.scores.as<float>(), out_ld, n_sel, (int)c.n_slots, kx, nullptr, &keys, &kld, &kn, d_slot_len + c.slot0));
-        launch_seg_keys_to_output(keys, kld, kn, (int)c.n_slots, form, k, idx->lab_lists.as<uint32_t>(), d_slot_base + c.slot0,
-                                  d_slot_q + c.slot0, idmap_of(idx), d_out_ids, d_out_scores, s);
+        VROD_TRY(step(c, out_ld));
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipStreamSynchronize(s));   // the next pass reuses the tables
+    return VROD_OK;
+}
+
+// ... of a labelled or tagged search: the select chain with a length per slot, then the k best of every slot to its
+// query's result row.
+static int score_segments(vrod_index* idx, Pending& P, Timer& tm, vrod_search_stats& st, const SlotTables& T, const DevSlots& D, uint32_t k,
+                          uint64_t* d_out_ids, float* d_out_scores) {
+    return run_segments(idx, P, &tm, st, P.q_f32.as<float>(), T, D, [&](const SegChunk& c, uint64_t out_ld) -> int {
+        const uint64_t n_sel = std::max<uint32_t>(c.max_m, 1);
+        const uint32_t kx = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(k, n_sel), kSelectChunk / 2);   // (the rest: unfilled)
+        const uint64_t* keys; uint64_t kld, kn;
+        VROD_TRY(select_chain(idx, P, P.scores.as<float>(), out_ld, n_sel, (int)c.n_slots, kx, nullptr, &keys, &kld, &kn, D.len + c.slot0));
+        launch_seg_keys_to_output(keys, kld, kn, (int)c.n_slots, score_form(idx->metric), k, idx->lab_lists.as<uint32_t>(), D.base + c.slot0,
+                                  D.q + c.slot0, idmap_of(idx), d_out_ids, d_out_scores, P.stream);
+        return VROD_OK;
+    });
+}
+
+// The workspace of the wide groups' searches: a group's mask, and the raw queries and results of up to max_nq queries.
+static int wide_group_ws(vrod_index* idx, uint32_t max_nq, uint32_t k) {
+    VROD_TRY(idx->lab_mask.ensure(idx->del_bits.size() * 4));   // capacity / 32 words
+    VROD_TRY(idx->lab_q.ensure((size_t)max_nq * idx->dim * 4));
+    VROD_TRY(idx->lab_ids.ensure((size_t)max_nq * k * 8));
+    VROD_TRY(idx->lab_scores.ensure((size_t)max_nq * k * 4));
     return VROD_OK;
 }
 
@@ -2540,20 +2619,12 @@ static int labeled_search(vrod_index* idx, const float* d_queries_raw, uint32_t 
     const uint64_t N = idx->count;
     Pending& P = next_slot(idx);
     hipStream_t s = P.stream;
-    if (N == 0) {   // an empty handle: every slot unfilled, as vrod_search
-        launch_fill_none(d_out_ids, d_out_scores, (uint64_t)nq * k, s);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(s));
-        idx->stats = st;
-        return VROD_OK;
-    }
-    VROD_TRY(prep_group_queries(idx, P, d_queries_raw, nq));
+    if (N == 0) return return_unfilled(idx, s, st, d_out_ids, d_out_scores, (uint64_t)nq * k);   // an empty handle
+    VROD_TRY(prep_queries_checked(idx, P, d_queries_raw, nq));
 
     // ---- groups, and the per-slot arrays of the segmented route (filled as the passes route their groups)
     const LabelGroups G = label_groups(h_labels, nq);
     const uint32_t* base_mask = idx->row_mask();
-    const uint32_t rpb = label_rows_per_block(N);
-    const uint32_t n_blocks = (uint32_t)((N + rpb - 1) / rpb);
     const double row_bytes = (double)idx->ld * idx->esize;
     struct Dense { uint32_t g; uint64_t m; };
     std::vector<Dense> dense;
@@ -2561,7 +2632,7 @@ static int labeled_search(vrod_index* idx, const float* d_queries_raw, uint32_t 
     VROD_TRY(idx->lab_slots.ensure((size_t)nq * 4 * 5));
     uint32_t* d_qorder = idx->lab_slots.as<uint32_t>();
     uint32_t* d_ones = d_qorder + nq;
-    uint32_t* d_slot_q = d_ones + nq;   // [slot_q | slot_len | slot_base] of score_segments
+    const DevSlots d_slots = dev_slots(d_ones + nq, nq);
     {
         std::vector<uint32_t> up(G.q_order);
         up.resize((size_t)nq * 2, 1u);
@@ -2569,63 +2640,41 @@ static int labeled_search(vrod_index* idx, const float* d_queries_raw, uint32_t 
         HIP_TRY(hipStreamSynchronize(s));
     }
     Timer tm(idx, P);
-    P.ev_used = 0; P.scan_pairs.clear(); P.sample_pair = -1; P.tail_pair = -1;
+    P.reset_events();
     for (uint32_t g0 = 0; g0 < G.size(); g0 += kLabelGroupsPerPass) {
         const uint32_t Gp = std::min<uint32_t>(kLabelGroupsPerPass, G.size() - g0);
         // ---- pass 1: every group's eligible rows, counted per block of the label array
-        VROD_TRY(idx->lab_tab.ensure((size_t)Gp * 4 * 3));
-        VROD_TRY(idx->lab_cnt.ensure((size_t)n_blocks * Gp * 4));
-        uint32_t* d_table = idx->lab_tab.as<uint32_t>();
-        uint32_t* d_total = d_table + Gp;
-        uint32_t* d_seg_off = d_total + Gp;
-        HIP_TRY(hipMemcpyAsync(d_table, G.labels.data() + g0, (size_t)Gp * 4, hipMemcpyHostToDevice, s));
-        launch_label_group_count(idx->lab_dev, base_mask, N, rpb, d_table, Gp, idx->lab_cnt.as<uint32_t>(), d_total, s);
-        HIP_TRY(hipGetLastError());
+        LabelPassWs W;
+        VROD_TRY(label_pass_ws(idx, Gp, W));
         std::vector<uint32_t> m(Gp);
-        HIP_TRY(hipMemcpyAsync(m.data(), d_total, (size_t)Gp * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
+        VROD_TRY(label_count_pass(idx, s, W, G.labels.data() + g0, Gp, m.data()));
         // ---- route
         std::vector<uint32_t> seg_off(Gp, kNoSegment);
-        std::vector<SegGroup> segs;
-        std::vector<uint32_t> slot_q, slot_len, slot_base;
+        SlotTables T;
         uint64_t list_n = 0;
         for (uint32_t i = 0; i < Gp; ++i) {
             const uint32_t g = g0 + i, nqg = G.nq_of(g);
             if (!filter_route(idx->path, idx->dtype, N, m[i], nqg, idx->dim)) { dense.push_back({g, m[i]}); continue; }
             seg_off[i] = (uint32_t)list_n;
-            segs.push_back({(uint32_t)list_n, m[i], (uint32_t)slot_q.size(), nqg});
-            for (uint32_t j = 0; j < nqg; ++j) {
-                slot_q.push_back(G.q_order[G.q_off[g] + j]);
-                slot_len.push_back(m[i]);
-                slot_base.push_back((uint32_t)list_n);
-            }
+            T.add((uint32_t)list_n, m[i], &G.q_order[G.q_off[g]], nqg);
             list_n += m[i];   // (the groups' rows are disjoint: at most N in all)
             st.scan_bytes += (double)m[i] * row_bytes;
             st.scan_flops += 2.0 * nqg * (double)m[i] * idx->dim;
         }
-        if (segs.empty()) continue;
+        if (T.segs.empty()) continue;
         // ---- pass 2: the segmented groups' row lists, ascending
-        VROD_TRY(idx->lab_lists.ensure(std::max<uint64_t>(list_n, 1) * 4));
-        HIP_TRY(hipMemcpyAsync(d_seg_off, seg_off.data(), (size_t)Gp * 4, hipMemcpyHostToDevice, s));
-        if (list_n)
-            launch_label_group_scatter(idx->lab_dev, base_mask, N, rpb, d_table, Gp, idx->lab_cnt.as<uint32_t>(), d_seg_off,
-                                       idx->lab_lists.as<uint32_t>(), s);
-        HIP_TRY(hipGetLastError());
-        VROD_TRY(score_segments(idx, P, tm, st, segs, slot_q, slot_len, slot_base, d_slot_q, nq, k, d_out_ids, d_out_scores));
+        VROD_TRY(label_scatter_pass(idx, s, W, seg_off.data(), Gp, list_n));
+        VROD_TRY(score_segments(idx, P, tm, st, T, d_slots, k, d_out_ids, d_out_scores));
     }
     HIP_TRY(hipStreamSynchronize(s));
-    if (idx->profiling)
-        for (size_t i = 0; i < P.scan_pairs.size(); ++i) st.scan_ms += tm.ms(P.scan_pairs[i].first, P.scan_pairs[i].second);
+    tm.add_scan_ms(st);
 
     // ---- dense groups: one ordinary search each, over the group's mask
     if (!dense.empty()) {
         const uint64_t words = idx->del_bits.size();   // capacity / 32
         uint32_t max_nq = 0;
         for (const Dense& d : dense) max_nq = std::max(max_nq, G.nq_of(d.g));
-        VROD_TRY(idx->lab_mask.ensure(words * 4));
-        VROD_TRY(idx->lab_q.ensure((size_t)max_nq * idx->dim * 4));
-        VROD_TRY(idx->lab_ids.ensure((size_t)max_nq * k * 8));
-        VROD_TRY(idx->lab_scores.ensure((size_t)max_nq * k * 4));
+        VROD_TRY(wide_group_ws(idx, max_nq, k));
         for (const Dense& d : dense) {
             const uint32_t nqg = G.nq_of(d.g);
             const uint32_t* d_qidx = d_qorder + G.q_off[d.g];
@@ -2653,25 +2702,15 @@ static int tagged_search(vrod_index* idx, const float* d_queries_raw, uint32_t n
     const uint64_t N = idx->count;
     Pending& P = next_slot(idx);
     hipStream_t s = P.stream;
-    if (N == 0) {   // an empty handle: every slot unfilled, as vrod_search
-        launch_fill_none(d_out_ids, d_out_scores, (uint64_t)nq * k, s);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(s));
-        idx->stats = st;
-        return VROD_OK;
-    }
-    VROD_TRY(prep_group_queries(idx, P, d_queries_raw, nq));
+    if (N == 0) return return_unfilled(idx, s, st, d_out_ids, d_out_scores, (uint64_t)nq * k);   // an empty handle
+    VROD_TRY(prep_queries_checked(idx, P, d_queries_raw, nq));
 
     const TagGroups G = tag_groups(h_preds, nq);
     const uint32_t Gn = G.size();
+    if (!Gn) return return_unfilled(idx, s, st, d_out_ids, d_out_scores, (uint64_t)nq * k);   // no predicate can match
     if (G.n_unsatisfiable()) {   // (the groups' queries overwrite their own rows below)
         launch_fill_none(d_out_ids, d_out_scores, (uint64_t)nq * k, s);
         HIP_TRY(hipGetLastError());
-    }
-    if (!Gn) {
-        HIP_TRY(hipStreamSynchronize(s));
-        idx->stats = st;
-        return VROD_OK;
     }
     const uint32_t* base_mask = idx->row_mask();
     const uint32_t rpb = label_rows_per_block(N);
@@ -2682,7 +2721,7 @@ static int tagged_search(vrod_index* idx, const float* d_queries_raw, uint32_t n
     VROD_TRY(idx->lab_slots.ensure((size_t)nq * 4 * 5));
     uint32_t* d_qorder = idx->lab_slots.as<uint32_t>();
     uint32_t* d_ones = d_qorder + nq;
-    uint32_t* d_slot = d_ones + nq;
+    const DevSlots d_slots = dev_slots(d_ones + nq, nq);
     // [predicates | totals | a pass's segment offsets] and the count matrix [blocks][groups] of ONE chunk of
     // kTagGroupsPerPass groups: the workspace does not grow with the batch's distinct predicates
     const uint32_t Gc = std::min(Gn, kTagGroupsPerPass);
@@ -2701,7 +2740,7 @@ static int tagged_search(vrod_index* idx, const float* d_queries_raw, uint32_t n
         HIP_TRY(hipStreamSynchronize(s));
     }
     Timer tm(idx, P);
-    P.ev_used = 0; P.scan_pairs.clear(); P.sample_pair = -1; P.tail_pair = -1;
+    P.reset_events();
     for (uint32_t c0 = 0; c0 < Gn; c0 += kTagGroupsPerPass) {
         const uint32_t Gp = std::min(kTagGroupsPerPass, Gn - c0);
         // ---- pass 1: the chunk's groups' eligible matching rows, counted per block of the tag array
@@ -2717,17 +2756,11 @@ static int tagged_search(vrod_index* idx, const float* d_queries_raw, uint32_t n
         const std::vector<uint8_t> nc(narrow.begin() + c0, narrow.begin() + c0 + Gp);
         // ---- pass 2 per scatter pass: the narrow groups' row lists, ascending, then score + select
         for (const TagPass& tp : plan_tag_passes(mc, nc)) {
-            std::vector<SegGroup> segs;
-            std::vector<uint32_t> slot_q, slot_len, slot_base;
+            SlotTables T;
             for (uint32_t i = tp.g0; i < tp.g1; ++i) {
                 const uint32_t g = c0 + i, base = tp.seg_off[i - tp.g0], nqg = G.nq_of(g);
                 if (base == kNoSegment) continue;
-                segs.push_back({base, m[g], (uint32_t)slot_q.size(), nqg});
-                for (uint32_t j = 0; j < nqg; ++j) {
-                    slot_q.push_back(G.q_order[G.q_off[g] + j]);
-                    slot_len.push_back(m[g]);
-                    slot_base.push_back(base);
-                }
+                T.add(base, m[g], &G.q_order[G.q_off[g]], nqg);
                 st.scan_bytes += (double)m[g] * row_bytes;
                 st.scan_flops += 2.0 * nqg * (double)m[g] * idx->dim;
             }
@@ -2737,22 +2770,18 @@ static int tagged_search(vrod_index* idx, const float* d_queries_raw, uint32_t n
                 launch_tag_group_scatter(idx->tag_dev, base_mask, N, rpb, d_table + tp.g0, tp.g1 - tp.g0, d_cnt + tp.g0, Gp, d_seg_off,
                                          idx->lab_lists.as<uint32_t>(), s);
             HIP_TRY(hipGetLastError());
-            VROD_TRY(score_segments(idx, P, tm, st, segs, slot_q, slot_len, slot_base, d_slot, nq, k, d_out_ids, d_out_scores));
+            VROD_TRY(score_segments(idx, P, tm, st, T, d_slots, k, d_out_ids, d_out_scores));
         }
     }
     HIP_TRY(hipStreamSynchronize(s));
-    if (idx->profiling)
-        for (size_t i = 0; i < P.scan_pairs.size(); ++i) st.scan_ms += tm.ms(P.scan_pairs[i].first, P.scan_pairs[i].second);
+    tm.add_scan_ms(st);
 
     // ---- wide groups: one ordinary search each, over the predicate's mask
     uint32_t max_nq = 0;
     for (uint32_t g = 0; g < Gn; ++g) if (!narrow[g]) max_nq = std::max(max_nq, G.nq_of(g));
     if (max_nq) {
         const uint64_t words = idx->del_bits.size();   // capacity / 32
-        VROD_TRY(idx->lab_mask.ensure(words * 4));
-        VROD_TRY(idx->lab_q.ensure((size_t)max_nq * idx->dim * 4));
-        VROD_TRY(idx->lab_ids.ensure((size_t)max_nq * k * 8));
-        VROD_TRY(idx->lab_scores.ensure((size_t)max_nq * k * 4));
+        VROD_TRY(wide_group_ws(idx, max_nq, k));
         for (uint32_t g = 0; g < Gn; ++g) {
             if (narrow[g]) continue;
             launch_tag_group_mask(idx->tag_dev, base_mask, N, words, G.preds[g], idx->lab_mask.as<uint32_t>(), s);
@@ -2832,21 +2861,7 @@ static int grouped_search(vrod_index* idx, const float* d_queries_raw, uint32_t 
     // ---- dense stage: the queries prepared as a search prepares them (NaN / Inf fails the call: under EXACT nothing
     // has looked at them yet)
     Pending& P = next_slot(idx);
-    P.plan = SearchPlan{};
-    P.plan.nq_pad = nq;
-    VROD_TRY(P.q_f32.ensure((size_t)nq * idx->ld * 4));
-    VROD_TRY(P.small.ensure(small_bytes(nq)));
-    const SmallBlock B = small_block(P);
-    QueryInit qi{};
-    qi.status = B.status;
-    launch_prep_queries(d_queries_raw, nq, nq, idx->dim, idx->ld, prep_form(idx->metric), idx->dtype, P.q_f32.as<float>(), nullptr, B.qn2,
-                        &P.flags[0], &P.flags[1], qi, s);
-    launch_gather_readback(B.status, nq, P.flags, idx->max_xn2_bits, B.readback, s);   // (consumes the slot's scalars)
-    HIP_TRY(hipGetLastError());
-    uint32_t bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, B.readback + nq, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (bad) return fail(VROD_ERR_INVALID_VALUE, "queries contain NaN or Inf");
+    VROD_TRY(prep_queries_checked(idx, P, d_queries_raw, nq));
 
     const uint64_t score_ld = round_up(N, 64), words = idx->del_bits.size();   // capacity / 32
     const double row_bytes = (double)idx->ld * idx->esize;
@@ -2856,20 +2871,16 @@ static int grouped_search(vrod_index* idx, const float* d_queries_raw, uint32_t 
     VROD_TRY(idx->grp_scores.ensure((size_t)gmax * k1 * 4));
     VROD_TRY(idx->grp_mask.ensure((size_t)gmax * words * 4));
     Timer tm(idx, P);
-    P.ev_used = 0; P.scan_pairs.clear(); P.sample_pair = -1; P.tail_pair = -1;
+    P.reset_events();
     for (size_t f0 = 0; f0 < todo.size();) {
         int g = gmax;
         while ((size_t)g > todo.size() - f0) g >>= 1;
         VROD_TRY(P.scores.ensure((size_t)g * score_ld * 4));
         size_t ea = 0, eb = 0;
-        if (idx->profiling) {   // (markers around the launch, as the gather path)
-            tm.arm(ea, eb);
-            g_launch_events = LaunchEvents{};
-            if (eb) HIP_TRY(hipEventRecord(P.ev[ea], s));
-        }
+        VROD_TRY(tm.begin_launch(ea, eb));
         launch_rescore_all(idx->corpus, idx->dtype, form, idx->dim, idx->ld, P.q_f32.as<float>(), &todo[f0], g, N, P.scores.as<float>(),
                            score_ld, s);
-        if (idx->profiling && eb) { HIP_TRY(hipEventRecord(P.ev[eb], s)); P.scan_pairs.push_back({ea, eb}); }
+        VROD_TRY(tm.end_launch(ea, eb));
         HIP_TRY(hipGetLastError());
         st.scan_launches++;
         st.scan_bytes += (double)N * row_bytes;
@@ -2901,8 +2912,7 @@ static int grouped_search(vrod_index* idx, const float* d_queries_raw, uint32_t 
         }
         f0 += g;
     }
-    if (idx->profiling)   // (every round ended with a synchronisation: the events are complete)
-        for (size_t i = 0; i < P.scan_pairs.size(); ++i) st.scan_ms += tm.ms(P.scan_pairs[i].first, P.scan_pairs[i].second);
+    tm.add_scan_ms(st);   // (every round ended with a synchronisation: the events are complete)
     st.fallback_queries += (uint32_t)todo.size();
     if (todo.size() == nq) st.path = VROD_PATH_EXACT;
     idx->stats = st;
@@ -3083,23 +3093,12 @@ static int multivec_candidates(vrod_index* idx, vrod_search_stats& st, bool firs
     }
     std::sort(labs.begin(), labs.end());
     labs.erase(std::unique(labs.begin(), labs.end()), labs.end());
-    const uint32_t* base_mask = idx->row_mask();
-    const uint32_t rpb = label_rows_per_block(N);
-    const uint32_t n_blocks = (uint32_t)((N + rpb - 1) / rpb);
-    const uint32_t Gc = (uint32_t)std::min<size_t>(std::max<size_t>(labs.size(), 1), kLabelGroupsPerPass);
-    VROD_TRY(idx->lab_tab.ensure((size_t)Gc * 4 * 3));
-    VROD_TRY(idx->lab_cnt.ensure((size_t)n_blocks * Gc * 4));
-    uint32_t* d_table = idx->lab_tab.as<uint32_t>();
-    uint32_t* d_total = d_table + Gc;
-    uint32_t* d_seg_off = d_total + Gc;
+    LabelPassWs W;
+    VROD_TRY(label_pass_ws(idx, (uint32_t)std::min<size_t>(std::max<size_t>(labs.size(), 1), kLabelGroupsPerPass), W));
     std::vector<uint32_t> rows_of(labs.size());
     for (size_t g0 = 0; g0 < labs.size(); g0 += kLabelGroupsPerPass) {
         const uint32_t Gp = (uint32_t)std::min<size_t>(kLabelGroupsPerPass, labs.size() - g0);
-        HIP_TRY(hipMemcpyAsync(d_table, labs.data() + g0, (size_t)Gp * 4, hipMemcpyHostToDevice, s));
-        launch_label_group_count(idx->lab_dev, base_mask, N, rpb, d_table, Gp, idx->lab_cnt.as<uint32_t>(), d_total, s);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(rows_of.data() + g0, d_total, (size_t)Gp * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
+        VROD_TRY(label_count_pass(idx, s, W, labs.data() + g0, Gp, rows_of.data() + g0));
     }
     auto lab_index = [&](uint32_t label) { return (size_t)(std::lower_bound(labs.begin(), labs.end(), label) - labs.begin()); };
 
@@ -3142,57 +3141,34 @@ static int multivec_candidates(vrod_index* idx, vrod_search_stats& st, bool firs
     for (size_t u0 = 0; u0 < used.size(); u0 += kLabelGroupsPerPass) {
         const uint32_t Gp = (uint32_t)std::min<size_t>(kLabelGroupsPerPass, used.size() - u0);
         std::vector<uint32_t> table(Gp), seg_off(Gp);
-        std::vector<SegGroup> segs;
-        std::vector<uint32_t> slot_q, slot_len;
+        SlotTables T;   // (a label's slots are every vector of every query that holds it: filled here, no slot_base)
         uint64_t list_n = 0;
         for (uint32_t g = 0; g < Gp; ++g) {
             const uint32_t lab_i = used[u0 + g], m_rows = rows_of[lab_i];
             table[g] = labs[lab_i];
             seg_off[g] = (uint32_t)list_n;
-            const uint32_t slot0 = (uint32_t)slot_q.size();
+            const uint32_t slot0 = T.size();
             for (const User& u : users[lab_i]) {
                 const uint32_t q = q0 + live[u.li];
-                pair_slot[u.li][u.col] = slot_base + (uint32_t)slot_q.size();
-                for (uint32_t v = lims[q]; v < lims[q + 1]; ++v) { slot_q.push_back(v); slot_len.push_back(m_rows); }
+                pair_slot[u.li][u.col] = slot_base + T.size();
+                for (uint32_t v = lims[q]; v < lims[q + 1]; ++v) { T.slot_q.push_back(v); T.slot_len.push_back(m_rows); }
             }
-            const uint32_t nsl = (uint32_t)slot_q.size() - slot0;
-            segs.push_back({(uint32_t)list_n, m_rows, slot0, nsl});
+            const uint32_t nsl = T.size() - slot0;
+            T.segs.push_back({(uint32_t)list_n, m_rows, slot0, nsl});
             list_n += m_rows;   // (the labels' rows are disjoint: at most N in all)
             st.scan_bytes += (double)m_rows * row_bytes;
             st.scan_flops += 2.0 * nsl * (double)m_rows * idx->dim;
         }
-        const uint32_t ns = (uint32_t)slot_q.size();
-        HIP_TRY(hipMemcpyAsync(d_table, table.data(), (size_t)Gp * 4, hipMemcpyHostToDevice, s));
-        launch_label_group_count(idx->lab_dev, base_mask, N, rpb, d_table, Gp, idx->lab_cnt.as<uint32_t>(), d_total, s);
-        VROD_TRY(idx->lab_lists.ensure(std::max<uint64_t>(list_n, 1) * 4));
-        HIP_TRY(hipMemcpyAsync(d_seg_off, seg_off.data(), (size_t)Gp * 4, hipMemcpyHostToDevice, s));
-        if (list_n)
-            launch_label_group_scatter(idx->lab_dev, base_mask, N, rpb, d_table, Gp, idx->lab_cnt.as<uint32_t>(), d_seg_off,
-                                       idx->lab_lists.as<uint32_t>(), s);
-        HIP_TRY(hipGetLastError());
-        const SegPlan plan = plan_segments(segs);
-        VROD_TRY(idx->lab_entries.ensure(std::max<size_t>(plan.entries.size(), 1) * sizeof(SegEntry)));
+        const uint32_t ns = T.size();
+        VROD_TRY(label_count_pass(idx, s, W, table.data(), Gp, nullptr));
+        VROD_TRY(label_scatter_pass(idx, s, W, seg_off.data(), Gp, list_n));
         VROD_TRY(idx->lab_slots.ensure((size_t)ns * 4 * 2));
-        uint32_t* d_slot_q = idx->lab_slots.as<uint32_t>();
-        uint32_t* d_slot_len = d_slot_q + ns;
-        HIP_TRY(hipMemcpyAsync(d_slot_q, slot_q.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_slot_len, slot_len.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s));
-        if (!plan.entries.empty())
-            HIP_TRY(hipMemcpyAsync(idx->lab_entries.p, plan.entries.data(), plan.entries.size() * sizeof(SegEntry), hipMemcpyHostToDevice, s));
-        for (const SegChunk& c : plan.chunks) {
-            const uint64_t out_ld = round_up(std::max<uint32_t>(c.max_m, 1), 64);
-            VROD_TRY(P.scores.ensure((size_t)c.n_slots * out_ld * 4));
-            if (c.n_blocks) {
-                launch_rescore_segments(idx->corpus, idx->dtype, form, idx->dim, idx->ld, idx->mv_q.as<float>(),
-                                        idx->lab_entries.as<SegEntry>() + c.e0, c.e1 - c.e0, c.n_blocks, d_slot_q, c.slot0,
-                                        idx->lab_lists.as<uint32_t>(), P.scores.as<float>(), out_ld, s);
-                st.scan_launches++;
-            }
-            launch_multivec_slot_best(P.scores.as<float>(), out_ld, c.n_slots, d_slot_len + c.slot0, form,
-                                      idx->mv_M.as<float>() + slot_base + c.slot0, s);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipStreamSynchronize(s));   // the next pass reuses the tables
+        const DevSlots D = dev_slots(idx->lab_slots.as<uint32_t>(), ns);
+        // (no markers: this route's launches are not part of scan_ms)
+        VROD_TRY(run_segments(idx, P, nullptr, st, idx->mv_q.as<float>(), T, D, [&](const SegChunk& c, uint64_t out_ld) -> int {
+            launch_multivec_slot_best(P.scores.as<float>(), out_ld, c.n_slots, D.len + c.slot0, form, idx->mv_M.as<float>() + slot_base + c.slot0, s);
+            return VROD_OK;
+        }));
         slot_base += ns;
     }
 
@@ -3266,7 +3242,7 @@ static int multivec_search(vrod_index* idx, const float* d_raw, const uint32_t* 
     // every vector prepared as a search prepares a query, and checked, before anything is written
     {
         Pending& P = next_slot(idx);
-        VROD_TRY(prep_group_queries(idx, P, d_raw, lims[nq]));
+        VROD_TRY(prep_queries_checked(idx, P, d_raw, lims[nq]));
         VROD_TRY(idx->mv_q.ensure((size_t)lims[nq] * idx->ld * 4));
         HIP_TRY(hipMemcpyAsync(idx->mv_q.p, P.q_f32.p, (size_t)lims[nq] * idx->ld * 4, hipMemcpyDeviceToDevice, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -3766,6 +3742,35 @@ int vrod_index_get_rows(vrod_index* idx, uint64_t first, uint64_t n, float* out_
     return VROD_OK;
 }
 
+// [first_id, first_id + n) are ids of this handle's rows (n = 0 at the end of them included)
+static int check_id_range(const vrod_index* idx, uint64_t first_id, uint64_t n) {
+    if (first_id < idx->id_offset || first_id - idx->id_offset > idx->count || n > idx->count - (first_id - idx->id_offset))
+        return fail(VROD_ERR_INVALID_ARG, "ids [%llu, %llu) are not all rows of this handle (ids %llu..%llu)", (unsigned long long)first_id,
+                    (unsigned long long)(first_id + n), (unsigned long long)idx->id_offset, (unsigned long long)(idx->id_offset + idx->count));
+    return VROD_OK;
+}
+
+// The handle's own top-k result rows, which a host form's search writes: grown for nq * k, and copied out to the caller.
+static int grow_topk_out(vrod_index* idx, uint32_t nq, uint32_t k) {
+    VROD_TRY(idx->out_ids.ensure((size_t)nq * k * 8));
+    VROD_TRY(idx->out_scores.ensure((size_t)nq * k * 4));
+    return VROD_OK;
+}
+static int copy_topk_out(vrod_index* idx, uint32_t nq, uint32_t k, uint64_t* out_ids, float* out_scores) {
+    HIP_TRY(hipMemcpy(out_ids, idx->out_ids.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_scores, idx->out_scores.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    return VROD_OK;
+}
+
+// What every synchronous device form starts with: the handle idle, its device current, and -- as a range search --
+// whatever the caller's stream holds complete before the library's streams start.
+static int begin_sync_device(vrod_index* idx, const char* what, void* stream) {
+    VROD_TRY(require_idle(idx, what));
+    VROD_TRY(set_device(idx));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return VROD_OK;
+}
+
 static int check_search_args(vrod_index* idx, const void* q, uint32_t nq, uint32_t k, const void* oi, const void* os) {
     if (!idx) return fail(VROD_ERR_INVALID_ARG, "idx is null");
     if (nq && (!q || !oi || !os)) return fail(VROD_ERR_INVALID_ARG, "null buffer");
@@ -3844,8 +3849,7 @@ int vrod_search(vrod_index* idx, const float* queries, uint32_t nq, uint32_t k, 
     VROD_TRY(set_device(idx));
     Pending& P = next_slot(idx);
     VROD_TRY(P.q_raw.ensure((size_t)nq * idx->dim * 4));
-    VROD_TRY(idx->out_ids.ensure((size_t)nq * k * 8));
-    VROD_TRY(idx->out_scores.ensure((size_t)nq * k * 4));
+    VROD_TRY(grow_topk_out(idx, nq, k));
     HIP_TRY(hipMemcpyAsync(P.q_raw.p, queries, (size_t)nq * idx->dim * 4, hipMemcpyHostToDevice, P.stream));
     VROD_TRY(run_search(idx, P.q_raw.as<float>(), nq, k, idx->out_ids.as<uint64_t>(), idx->out_scores.as<float>()));
     HIP_TRY(hipMemcpyAsync(out_ids, idx->out_ids.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost, idx->stream));
@@ -3859,9 +3863,7 @@ int vrod_index_set_labels(vrod_index* idx, uint64_t first_id, const uint32_t* la
     if (!idx || (!labels && n)) return fail(VROD_ERR_INVALID_ARG, "null argument");
     if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "vrod_index_set_labels on a multi-device handle: labels are not routed to the shards");
     VROD_TRY(require_idle(idx, "vrod_index_set_labels"));
-    if (first_id < idx->id_offset || first_id - idx->id_offset > idx->count || n > idx->count - (first_id - idx->id_offset))
-        return fail(VROD_ERR_INVALID_ARG, "ids [%llu, %llu) are not all rows of this handle (ids %llu..%llu)", (unsigned long long)first_id,
-                    (unsigned long long)(first_id + n), (unsigned long long)idx->id_offset, (unsigned long long)(idx->id_offset + idx->count));
+    VROD_TRY(check_id_range(idx, first_id, n));
     if (!n) return VROD_OK;
     VROD_TRY(set_device(idx));
     const uint64_t r0 = first_id - idx->id_offset;
@@ -3881,9 +3883,7 @@ int vrod_index_set_labels(vrod_index* idx, uint64_t first_id, const uint32_t* la
 
 int vrod_index_get_labels(vrod_index* idx, uint64_t first_id, uint64_t n, uint32_t* out_labels) {
     if (!idx || (!out_labels && n)) return fail(VROD_ERR_INVALID_ARG, "null argument");
-    if (first_id < idx->id_offset || first_id - idx->id_offset > idx->count || n > idx->count - (first_id - idx->id_offset))
-        return fail(VROD_ERR_INVALID_ARG, "ids [%llu, %llu) are not all rows of this handle (ids %llu..%llu)", (unsigned long long)first_id,
-                    (unsigned long long)(first_id + n), (unsigned long long)idx->id_offset, (unsigned long long)(idx->id_offset + idx->count));
+    VROD_TRY(check_id_range(idx, first_id, n));
     const uint64_t r0 = first_id - idx->id_offset;
     for (uint64_t i = 0; i < n; ++i) out_labels[i] = idx->lab_bits.empty() ? 0u : idx->lab_bits[r0 + i];   // (the host mirror is the truth)
     return VROD_OK;
@@ -3903,23 +3903,17 @@ int vrod_search_labeled(vrod_index* idx, const float* queries, uint32_t nq, uint
     VROD_TRY(require_idle(idx, "vrod_search_labeled"));
     VROD_TRY(set_device(idx));
     VROD_TRY(idx->lab_qraw.ensure((size_t)nq * idx->dim * 4));
-    VROD_TRY(idx->out_ids.ensure((size_t)nq * k * 8));
-    VROD_TRY(idx->out_scores.ensure((size_t)nq * k * 4));
+    VROD_TRY(grow_topk_out(idx, nq, k));
     HIP_TRY(hipMemcpy(idx->lab_qraw.p, queries, (size_t)nq * idx->dim * 4, hipMemcpyHostToDevice));
     VROD_TRY(labeled_search(idx, idx->lab_qraw.as<float>(), nq, k, query_labels, idx->out_ids.as<uint64_t>(), idx->out_scores.as<float>()));
-    HIP_TRY(hipMemcpy(out_ids, idx->out_ids.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_scores, idx->out_scores.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
-    return VROD_OK;
+    return copy_topk_out(idx, nq, k, out_ids, out_scores);
 }
 
 int vrod_search_labeled_device(vrod_index* idx, const float* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_query_labels,
                                uint64_t* d_out_ids, float* d_out_scores, void* stream) {
     VROD_TRY(check_labeled_args(idx, d_queries, nq, k, d_query_labels, d_out_ids, d_out_scores));
     if (!nq) return VROD_OK;
-    VROD_TRY(require_idle(idx, "vrod_search_labeled_device"));
-    VROD_TRY(set_device(idx));
-    // synchronous, as a range search: whatever the caller's stream holds is complete before the library's streams start
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    VROD_TRY(begin_sync_device(idx, "vrod_search_labeled_device", stream));
     std::vector<uint32_t> labels(nq);
     HIP_TRY(hipMemcpy(labels.data(), d_query_labels, (size_t)nq * 4, hipMemcpyDeviceToHost));
     return labeled_search(idx, d_queries, nq, k, labels.data(), d_out_ids, d_out_scores);
@@ -3929,9 +3923,7 @@ int vrod_index_set_tags(vrod_index* idx, uint64_t first_id, const uint64_t* tags
     if (!idx || (!tags && n)) return fail(VROD_ERR_INVALID_ARG, "null argument");
     if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "vrod_index_set_tags on a multi-device handle: tags are not routed to the shards");
     VROD_TRY(require_idle(idx, "vrod_index_set_tags"));
-    if (first_id < idx->id_offset || first_id - idx->id_offset > idx->count || n > idx->count - (first_id - idx->id_offset))
-        return fail(VROD_ERR_INVALID_ARG, "ids [%llu, %llu) are not all rows of this handle (ids %llu..%llu)", (unsigned long long)first_id,
-                    (unsigned long long)(first_id + n), (unsigned long long)idx->id_offset, (unsigned long long)(idx->id_offset + idx->count));
+    VROD_TRY(check_id_range(idx, first_id, n));
     if (!n) return VROD_OK;
     VROD_TRY(set_device(idx));
     const uint64_t r0 = first_id - idx->id_offset;
@@ -3950,9 +3942,7 @@ int vrod_index_set_tags(vrod_index* idx, uint64_t first_id, const uint64_t* tags
 
 int vrod_index_get_tags(vrod_index* idx, uint64_t first_id, uint64_t n, uint64_t* out_tags) {
     if (!idx || (!out_tags && n)) return fail(VROD_ERR_INVALID_ARG, "null argument");
-    if (first_id < idx->id_offset || first_id - idx->id_offset > idx->count || n > idx->count - (first_id - idx->id_offset))
-        return fail(VROD_ERR_INVALID_ARG, "ids [%llu, %llu) are not all rows of this handle (ids %llu..%llu)", (unsigned long long)first_id,
-                    (unsigned long long)(first_id + n), (unsigned long long)idx->id_offset, (unsigned long long)(idx->id_offset + idx->count));
+    VROD_TRY(check_id_range(idx, first_id, n));
     const uint64_t r0 = first_id - idx->id_offset;
     for (uint64_t i = 0; i < n; ++i) out_tags[i] = idx->tag_bits.empty() ? 0ull : idx->tag_bits[r0 + i];   // (the host mirror is the truth)
     return VROD_OK;
@@ -3974,24 +3964,18 @@ int vrod_search_tagged(vrod_index* idx, const float* queries, uint32_t nq, uint3
     VROD_TRY(require_idle(idx, "vrod_search_tagged"));
     VROD_TRY(set_device(idx));
     VROD_TRY(idx->lab_qraw.ensure((size_t)nq * idx->dim * 4));
-    VROD_TRY(idx->out_ids.ensure((size_t)nq * k * 8));
-    VROD_TRY(idx->out_scores.ensure((size_t)nq * k * 4));
+    VROD_TRY(grow_topk_out(idx, nq, k));
     if (idx->count) HIP_TRY(hipMemcpy(idx->lab_qraw.p, queries, (size_t)nq * idx->dim * 4, hipMemcpyHostToDevice));
     VROD_TRY(tagged_search(idx, idx->lab_qraw.as<float>(), nq, k, reinterpret_cast<const TagPred*>(preds), idx->out_ids.as<uint64_t>(),
                            idx->out_scores.as<float>()));
-    HIP_TRY(hipMemcpy(out_ids, idx->out_ids.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_scores, idx->out_scores.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
-    return VROD_OK;
+    return copy_topk_out(idx, nq, k, out_ids, out_scores);
 }
 
 int vrod_search_tagged_device(vrod_index* idx, const float* d_queries, uint32_t nq, uint32_t k, const vrod_tag_pred* d_preds,
                               uint64_t* d_out_ids, float* d_out_scores, void* stream) {
     VROD_TRY(check_tagged_args(idx, d_queries, nq, k, d_preds, d_out_ids, d_out_scores));
     if (!nq) return VROD_OK;
-    VROD_TRY(require_idle(idx, "vrod_search_tagged_device"));
-    VROD_TRY(set_device(idx));
-    // synchronous, as a labelled search: whatever the caller's stream holds is complete before the library's streams start
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    VROD_TRY(begin_sync_device(idx, "vrod_search_tagged_device", stream));
     std::vector<TagPred> preds(nq);
     HIP_TRY(hipMemcpy(preds.data(), d_preds, (size_t)nq * sizeof(TagPred), hipMemcpyDeviceToHost));
     return tagged_search(idx, d_queries, nq, k, preds.data(), d_out_ids, d_out_scores);
@@ -4010,14 +3994,12 @@ int vrod_search_grouped(vrod_index* idx, const float* queries, uint32_t nq, uint
     VROD_TRY(require_idle(idx, "vrod_search_grouped"));
     VROD_TRY(set_device(idx));
     VROD_TRY(idx->grp_qraw.ensure((size_t)nq * idx->dim * 4));
-    VROD_TRY(idx->out_ids.ensure((size_t)nq * k * 8));
-    VROD_TRY(idx->out_scores.ensure((size_t)nq * k * 4));
+    VROD_TRY(grow_topk_out(idx, nq, k));
     VROD_TRY(idx->grp_labels.ensure((size_t)nq * k * 4));
     HIP_TRY(hipMemcpy(idx->grp_qraw.p, queries, (size_t)nq * idx->dim * 4, hipMemcpyHostToDevice));
     VROD_TRY(grouped_search(idx, idx->grp_qraw.as<float>(), nq, k, idx->out_ids.as<uint64_t>(), idx->out_scores.as<float>(),
                             idx->grp_labels.as<uint32_t>()));
-    HIP_TRY(hipMemcpy(out_ids, idx->out_ids.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_scores, idx->out_scores.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    VROD_TRY(copy_topk_out(idx, nq, k, out_ids, out_scores));
     if (out_labels) HIP_TRY(hipMemcpy(out_labels, idx->grp_labels.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
     return VROD_OK;
 }
@@ -4026,10 +4008,7 @@ int vrod_search_grouped_device(vrod_index* idx, const float* d_queries, uint32_t
                                uint32_t* d_out_labels, void* stream) {
     VROD_TRY(check_grouped_args(idx, d_queries, nq, k, d_out_ids, d_out_scores));
     if (!nq) return VROD_OK;
-    VROD_TRY(require_idle(idx, "vrod_search_grouped_device"));
-    VROD_TRY(set_device(idx));
-    // synchronous, as a range search: whatever the caller's stream holds is complete before the library's streams start
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    VROD_TRY(begin_sync_device(idx, "vrod_search_grouped_device", stream));
     if (!d_out_labels) {   // the de-duplication keeps each query's taken labels there
         VROD_TRY(idx->grp_labels.ensure((size_t)nq * k * 4));
         d_out_labels = idx->grp_labels.as<uint32_t>();
@@ -4079,10 +4058,7 @@ int vrod_search_multivec_device(vrod_index* idx, const float* d_vectors, const u
                                 uint32_t* d_out_labels, float* d_out_scores, uint32_t* d_out_found, void* stream) {
     VROD_TRY(check_multivec_args(idx, d_vectors, d_query_lims, nq, k, d_out_labels, d_out_scores));
     if (!nq) return VROD_OK;
-    VROD_TRY(require_idle(idx, "vrod_search_multivec_device"));
-    VROD_TRY(set_device(idx));
-    // synchronous, as a range search: whatever the caller's stream holds is complete before the library's streams start
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    VROD_TRY(begin_sync_device(idx, "vrod_search_multivec_device", stream));
     std::vector<uint32_t> lims((size_t)nq + 1);
     HIP_TRY(hipMemcpy(lims.data(), d_query_lims, lims.size() * 4, hipMemcpyDeviceToHost));
     VROD_TRY(check_multivec_lims(lims.data(), nq));
@@ -4122,14 +4098,12 @@ int vrod_search_diverse(vrod_index* idx, const float* queries, uint32_t nq, uint
     VROD_TRY(require_idle(idx, "vrod_search_diverse"));
     VROD_TRY(set_device(idx));
     VROD_TRY(idx->dv_qraw.ensure((size_t)nq * idx->dim * 4));
-    VROD_TRY(idx->out_ids.ensure((size_t)nq * k * 8));
-    VROD_TRY(idx->out_scores.ensure((size_t)nq * k * 4));
+    VROD_TRY(grow_topk_out(idx, nq, k));
     VROD_TRY(idx->dv_mmr.ensure((size_t)nq * k * 4));
     HIP_TRY(hipMemcpy(idx->dv_qraw.p, queries, (size_t)nq * idx->dim * 4, hipMemcpyHostToDevice));
     VROD_TRY(diverse_search(idx, idx->dv_qraw.as<float>(), nq, k, pool, lambda, idx->out_ids.as<uint64_t>(), idx->out_scores.as<float>(),
                             idx->dv_mmr.as<float>()));
-    HIP_TRY(hipMemcpy(out_ids, idx->out_ids.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_scores, idx->out_scores.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    VROD_TRY(copy_topk_out(idx, nq, k, out_ids, out_scores));
     if (out_mmr) HIP_TRY(hipMemcpy(out_mmr, idx->dv_mmr.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
     return VROD_OK;
 }
@@ -4138,10 +4112,7 @@ int vrod_search_diverse_device(vrod_index* idx, const float* d_queries, uint32_t
                                uint64_t* d_out_ids, float* d_out_scores, float* d_out_mmr, void* stream) {
     VROD_TRY(check_diverse_args(idx, d_queries, nq, k, pool, lambda, d_out_ids, d_out_scores));
     if (!nq) return VROD_OK;
-    VROD_TRY(require_idle(idx, "vrod_search_diverse_device"));
-    VROD_TRY(set_device(idx));
-    // synchronous, as a range search: whatever the caller's stream holds is complete before the library's streams start
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    VROD_TRY(begin_sync_device(idx, "vrod_search_diverse_device", stream));
     return diverse_search(idx, d_queries, nq, k, pool, lambda, d_out_ids, d_out_scores, d_out_mmr);
 }
 
@@ -4169,32 +4140,24 @@ int vrod_search_by_ids(vrod_index* idx, const uint64_t* ids, uint32_t nq, uint32
     }
     VROD_TRY(set_device(idx));
     VROD_TRY(idx->byid_user_ids.ensure((size_t)nq * 8));
-    VROD_TRY(idx->out_ids.ensure((size_t)nq * k * 8));
-    VROD_TRY(idx->out_scores.ensure((size_t)nq * k * 4));
+    VROD_TRY(grow_topk_out(idx, nq, k));
     HIP_TRY(hipMemcpy(idx->byid_user_ids.p, ids, (size_t)nq * 8, hipMemcpyHostToDevice));
     VROD_TRY(byid_search(idx, idx->byid_user_ids.as<uint64_t>(), true, nq, k, flags & VROD_BYID_EXCLUDE_SELF, idx->out_ids.as<uint64_t>(),
                          idx->out_scores.as<float>()));
-    HIP_TRY(hipMemcpy(out_ids, idx->out_ids.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_scores, idx->out_scores.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
-    return VROD_OK;
+    return copy_topk_out(idx, nq, k, out_ids, out_scores);
 }
 
 int vrod_search_by_ids_device(vrod_index* idx, const uint64_t* d_ids, uint32_t nq, uint32_t k, uint32_t flags, uint64_t* d_out_ids,
                               float* d_out_scores, void* stream) {
     VROD_TRY(check_byid_args(idx, d_ids, nq, k, flags, d_out_ids, d_out_scores, "vrod_search_by_ids_device"));
     if (!nq) return VROD_OK;
-    VROD_TRY(require_idle(idx, "vrod_search_by_ids_device"));
-    VROD_TRY(set_device(idx));
-    // synchronous, as a range search: whatever the caller's stream holds is complete before the library's streams start
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    VROD_TRY(begin_sync_device(idx, "vrod_search_by_ids_device", stream));
     return byid_search(idx, d_ids, false, nq, k, flags & VROD_BYID_EXCLUDE_SELF, d_out_ids, d_out_scores);
 }
 
 int vrod_knn_graph(vrod_index* idx, uint64_t first_id, uint64_t n, uint32_t k, uint64_t* out_ids, float* out_scores) {
     VROD_TRY(check_byid_args(idx, (void*)1, n ? 1u : 0u, k, VROD_BYID_EXCLUDE_SELF, out_ids, out_scores, "vrod_knn_graph"));
-    if (first_id < idx->id_offset || first_id - idx->id_offset > idx->count || n > idx->count - (first_id - idx->id_offset))
-        return fail(VROD_ERR_INVALID_ARG, "ids [%llu, %llu) are not all rows of this handle (ids %llu..%llu)", (unsigned long long)first_id,
-                    (unsigned long long)(first_id + n), (unsigned long long)idx->id_offset, (unsigned long long)(idx->id_offset + idx->count));
+    VROD_TRY(check_id_range(idx, first_id, n));
     if (!n) return VROD_OK;
     VROD_TRY(require_idle(idx, "vrod_knn_graph"));
     VROD_TRY(set_device(idx));
