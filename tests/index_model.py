@@ -15,39 +15,24 @@ so that sequence_plans.coverage() can count the growths).
 Expected results of EVERY search form come from one primitive: oracle.prepare of the current rows (cached, redone for
 the rows a mutation touched), then oracle.scan_topk / oracle.scan_range over the eligible (live and allowed) rows taken in
 ascending order, positions mapped back to ids + offset.
-"""
-import os
 
+The codes (DT, the metric codes, ID_NONE), THREADS and the helpers bits and drop_self come from support.py, the bottom
+layer of the test helpers; this module defines the model and its status codes only.
+"""
 import numpy as np
 
 from oracle import oracle as O
 
-DT = {"f32": 0, "bf16": 1}
-METRIC_COSINE, METRIC_L2 = 0, 1
-ID_NONE = np.uint64(0xFFFFFFFFFFFFFFFF)
+from support import DT, ID_NONE, METRIC_COSINE, METRIC_L2, THREADS, drop_self
+
 ERR_INVALID_ARG, ERR_INVALID_VALUE, ERR_UNSUPPORTED = 1, 2, 6
 ROW_TILE = 256                                     # index_reserve rounds the capacity up to this
-THREADS = max(1, min(16, len(os.sched_getaffinity(0))))
 
 
 class ModelError(Exception):
     def __init__(self, code, what=""):
         super().__init__(f"status {code}: {what}")
         self.code = code
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def drop_self(ids, sc, self_ids, k):
-    """Each (k + 1)-list without the entry that carries the query's own id, cut to k."""
-    oi = np.empty((ids.shape[0], k), np.uint64)
-    osc = np.empty((ids.shape[0], k), np.float32)
-    for q in range(ids.shape[0]):
-        keep = np.flatnonzero(ids[q] != self_ids[q])[:k]
-        oi[q], osc[q] = ids[q][keep], sc[q][keep]
-    return oi, osc
 
 
 class ModelIndex:

@@ -9,16 +9,14 @@ lists.
 import numpy as np
 
 from index_model import ID_NONE, METRIC_L2, ModelIndex
+from support import MAX_K, first_k    # (both are part of this mirror: test_multivec_plan.py checks them against the header)
 
-MAX_K = 3584
 MAX_QUERY_VECTORS = 256
 BATCH_VECTORS = 2048
 DENSE_SHARE = 4
 
 
 # ---- multivec_plan.h, mirrored
-def first_k(k, eligible):
-    return min(MAX_K, eligible, max(4 * k, k + 32))
 
 
 def cut(lims, q0, max_vectors=BATCH_VECTORS):

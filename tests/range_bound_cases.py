@@ -28,14 +28,11 @@ band_counts() counts, per query, the rows within one bound of the threshold that
 (n_out).  The condition every case must meet on the reference alone: n_in >= 1 and n_out >= 1 for at least three
 quarters of its queries.
 """
-import os
-
 import numpy as np
 
 import certificate_fixtures as F
+from support import DT, THREADS, prep_of, form_of
 
-DT = {"f32": 0, "bf16": 1}
-THREADS = max(1, min(16, len(os.sched_getaffinity(0))))
 # a range search has no stream form
 KERNELS = {name: row for name, row in F.KERNELS.items() if not name.startswith("stream")}
 NEAR_TIES_K = 10            # clusters of 3 k + 8 = 38 rows
@@ -45,14 +42,6 @@ N_LARGE, DIM_LARGE = 300_000, 128
 DIM_SHORT = 16              # split_worst on the split kernels
 LARGE_BEST = 4096           # at N_LARGE: the threshold is a score among the query's best rows
 MIN_QUERY_SHARE = 0.75
-
-
-def prep_of(metric):
-    return 0 if metric == "cosine" else 1          # ip: the vectors as given
-
-
-def form_of(metric):
-    return 1 if metric == "l2" else 0              # ip: the dot form
 
 
 def _families(dtype, metric):

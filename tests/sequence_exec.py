@@ -8,21 +8,16 @@ import ctypes as C
 import numpy as np
 
 from conftest import f32_split
-from index_model import ID_NONE, ModelError, ModelIndex, bits
+from index_model import ID_NONE, ModelError, ModelIndex
 from sequence_plans import PATH_AUTO, PIPE_K, PIPE_NQ, Op, _Maker, apply_mutation, every_form, expected, is_check
+from support import assert_same, bits
 
 SENT_ID, SENT_SC = np.uint64(0x5A5A5A5A5A5A5A5A), np.float32(-12345.5)
 ERR_UNSUPPORTED = 6
 
 
 def same_lists(got, want, what):
-    ids, sc = got[0], got[1]
-    oi, osc = want[0], want[1]
-    assert ids.shape == oi.shape and sc.shape == osc.shape, f"{what}: shapes {ids.shape} {oi.shape}"
-    assert np.array_equal(ids, oi), f"{what}: ids differ at {np.argwhere(ids != oi)[:5].tolist()}"
-    na, nb = np.isnan(sc), np.isnan(osc)
-    assert np.array_equal(na, nb), f"{what}: NaN positions differ at {np.argwhere(na != nb)[:5].tolist()}"
-    assert np.array_equal(bits(sc)[~na], bits(osc)[~nb]), f"{what}: score bits differ at {np.argwhere(bits(sc) != bits(osc))[:5].tolist()}"
+    assert_same(got[0], got[1], want[0], want[1], what)
     if len(want) == 3:
         assert np.array_equal(got[2], want[2]), f"{what}: labels differ at {np.argwhere(got[2] != want[2])[:5].tolist()}"
 

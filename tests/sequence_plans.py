@@ -28,16 +28,17 @@ rows end above 3 400.  So COMMITTED holds eight full-size plans that meet all of
 `small` plans of the same backbone at 337 .. 1 300 rows (about 7 small labels) that exist for the CPU check of the model
 alone.  An f32 handle with VROD_F32_SPLIT=0 never has planes, so counter (d) is asked of the other f32 plans only.
 
-coverage() routes a search the way the library does (route, graph_route and filter_route of search_plan.h, restated
-below): an ordering counts only if the search in it takes the route the ordering is about.
+coverage() routes a search the way the library does (route and graph_route of search_plan.h, restated
+below; filter_route is support.takes_segments): an ordering counts only if the search in it takes the route the ordering is
+about.
 """
 from dataclasses import dataclass, field
 
 import numpy as np
 
 from index_model import ModelError, ModelIndex
+from support import PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT, PATH_GATHER, takes_segments as filter_route
 
-PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT, PATH_GATHER = 0, 1, 2, 3, 4
 MUTATIONS = ("add", "delete", "update", "set_filter", "set_labels", "compact", "set_path")
 FORMS = ("search", "search_labeled", "search_grouped", "range_search", "search_by_ids", "knn_graph", "pipelined")
 ADD_SIZES = (1, 37, 300, 1500)
@@ -97,21 +98,6 @@ MODEL_CHECK = (
 def graph_route(path, nq):
     """The route a search must have to be captured and replayed (search_plan.h graph_route)."""
     return path == PATH_STREAM or (path == PATH_AUTO and nq <= 4)
-
-
-def filter_route(path, dtype, N, m, nq, dim):
-    """Whether a search over m eligible rows of N gathers (search_plan.h filter_route and filter_cost)."""
-    if path == PATH_GATHER:
-        return True
-    if path != PATH_AUTO:
-        return False
-    if m == 0:
-        return True
-    row_bytes = dim * (2.0 if dtype == "bf16" else 4.0)
-    steps = float(nq) * dim
-    masked = np.log10(N / m) if 0 < m < N else 0.0
-    dense = N * (row_bytes * 2.0e-4 + steps * ((1.0e-6 if dtype == "bf16" else 3.0e-6) + 3.0e-7 * masked))
-    return m * (row_bytes * 3.0e-4 + steps * 1.56e-4) < dense
 
 
 def builds_planes(cfg, path, filtered, N, m, nq):

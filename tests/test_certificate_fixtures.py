@@ -5,9 +5,7 @@ import numpy as np
 import pytest
 
 import certificate_fixtures as F
-
-DT = {"f32": 0, "bf16": 1}
-ME = {"cosine": 0, "l2": 1}
+from support import DT, ME
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])

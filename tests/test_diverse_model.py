@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import diverse_model as DM
-from index_model import ID_NONE, bits
+from support import ID_NONE, bits
 
 D = 24
 

@@ -11,48 +11,22 @@ rows scaled by exp(U(-1, 1)) so that a row is often not its own best match.  The
 three batches, both workspaces reused, a partial tail.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
+import support
+from support import (  # noqa: F401
+    DT, METRIC_COSINE, METRIC_L2, PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT, PATH_GATHER, ID_NONE, THREADS, va, O, bits, drop_self)
+
 pytestmark = pytest.mark.gpu
 
-DT = {"f32": 0, "bf16": 1}
-METRIC_COSINE, METRIC_L2 = 0, 1
-PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT, PATH_GATHER = 0, 1, 2, 3, 4
-ID_NONE = np.uint64(0xFFFFFFFFFFFFFFFF)
-THREADS = max(1, min(16, len(os.sched_getaffinity(0))))
 N, K = 3000, 10
 SENT_ID, SENT_SC = np.uint64(0x5A5A5A5A5A5A5A5A), np.float32(-12345.5)
 
 
-@pytest.fixture(scope="module")
-def va():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import vrod_amd
-    vrod_amd.load()
-    return vrod_amd
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
 def assert_same(got, want, what=""):
-    (ids, sc), (oi, osc) = got, want
-    assert ids.shape == oi.shape and sc.shape == osc.shape, what
-    assert np.array_equal(ids, oi), f"{what}: ids differ at {np.argwhere(ids != oi)[:5]}"
-    na, nb = np.isnan(sc), np.isnan(osc)
-    assert np.array_equal(na, nb), f"{what}: NaN positions differ at {np.argwhere(na != nb)[:5]}"
-    assert np.array_equal(bits(sc)[~na], bits(osc)[~nb]), f"{what}: score bits differ"
+    support.assert_same(*got, *want, what)
 
 
 def raw_corpus(n, d, metric, seed):
@@ -80,17 +54,6 @@ def corpus(O, d, dtype, metric, n=N):
         pc.setflags(write=False)
         _CACHE[key] = (raw, pc)
     return _CACHE[key]
-
-
-def drop_self(ids, sc, self_ids, k):
-    """numpy restatement: each (k + 1)-list without the entry whose id is the query's own, cut to k."""
-    oi = np.empty((ids.shape[0], k), np.uint64)
-    osc = np.empty((ids.shape[0], k), np.float32)
-    for q in range(ids.shape[0]):
-        keep = np.flatnonzero(ids[q] != self_ids[q])[:k]
-        assert keep.size == k
-        oi[q], osc[q] = ids[q][keep], sc[q][keep]
-    return oi, osc
 
 
 def expect(O, pc, metric, qrows, k, elig=None, exclude_self=False, id_offset=0):

@@ -10,10 +10,9 @@ import numpy as np
 import pytest
 
 import certificate_fixtures as F
+from support import DT, ME, va, bits  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-DT = {"f32": 0, "bf16": 1}
-ME = {"cosine": 0, "l2": 1}
 
 KERNELS = F.KERNELS     # which kernel a batch reaches: certificate_fixtures.py
 N_ALL = 2048     # <= VROD_MAX_K, and k' = N fits the split pass's k + max(32, k / 2) <= 4096
@@ -36,19 +35,6 @@ def _cases():
                 for fam in _families(dtype, metric):
                     out.append(pytest.param(name, dim, metric, fam, id=f"{name}-{dim}-{metric}-{fam}"))
     return out
-
-
-@pytest.fixture(scope="module")
-def va():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import vrod_amd
-    vrod_amd.load()
-    return vrod_amd
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def _search(va, raw, rq, k, dtype, metric, path, mode):

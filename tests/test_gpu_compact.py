@@ -10,24 +10,13 @@ import os
 import numpy as np
 import pytest
 
+from support import (  # noqa: F401
+    DT, METRIC_L2, PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT, PATH_GATHER, ID_NONE, THREADS, va, bits, assert_same, check_bound, prep_of, form_of, eligible_rows, oracle_over)
+
 pytestmark = pytest.mark.gpu
 
-DT = {"f32": 0, "bf16": 1}
-METRIC_COSINE, METRIC_L2 = 0, 1
-PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT, PATH_GATHER = 0, 1, 2, 3, 4
-ID_NONE = np.uint64(0xFFFFFFFFFFFFFFFF)
-THREADS = max(1, min(16, len(os.sched_getaffinity(0))))
 METRICS = ["cosine", "l2", "ip"]
 CHUNK = 65536          # compact_plan.h kCompactChunkRows: rows per staged chunk (rows of <= 4 KiB)
-
-
-@pytest.fixture(scope="module")
-def va():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import vrod_amd
-    vrod_amd.load()
-    return vrod_amd
 
 
 def test_chunk_constant_is_the_headers():
@@ -37,43 +26,9 @@ def test_chunk_constant_is_the_headers():
     assert int(re.search(r"kCompactChunkRows = 1u << (\d+);", src).group(1)) == 16 and CHUNK == 1 << 16
 
 
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def assert_same(ids, sc, oi, osc, what=""):
-    assert np.array_equal(ids, oi), f"{what}: ids differ at {np.argwhere(ids != oi)[:5]}"
-    na, nb = np.isnan(sc), np.isnan(osc)
-    assert np.array_equal(na, nb), f"{what}: NaN positions differ at {np.argwhere(na != nb)[:5]}"
-    assert np.array_equal(bits(sc)[~na], bits(osc)[~nb]), f"{what}: score bits differ"
-
-
-def check_bound(st, what):
-    if st["path"] != PATH_EXACT and np.isfinite(st["eps_bound"]):
-        assert st["max_fast_err"] <= st["eps_bound"], f"{what}: {st}"
-
-
-def prep_of(metric):
-    return METRIC_COSINE if metric == "cosine" else METRIC_L2
-
-
-def form_of(metric):
-    return METRIC_L2 if metric == "l2" else METRIC_COSINE
-
-
 def oracle_rows(O, rows, rq, k, dtype, metric, id_offset=0, allowed=None):
     """The oracle over `rows` (ids 0.. + id_offset), or over its allowed rows with the ids mapped back."""
-    nq = rq.shape[0]
-    sel = np.arange(rows.shape[0]) if allowed is None else np.flatnonzero(allowed)
-    if sel.size == 0:
-        return np.full((nq, k), ID_NONE, np.uint64), np.full((nq, k), np.nan, np.float32)
-    pc = O.prepare(np.ascontiguousarray(rows[sel]), DT[dtype], prep_of(metric), threads=THREADS)
-    pq = O.prepare(rq, DT[dtype], prep_of(metric), threads=THREADS)
-    i, s = O.scan_topk(pc, pq, k, form_of(metric), threads=THREADS)
-    out = np.full(i.shape, ID_NONE, np.uint64)
-    m = i != ID_NONE
-    out[m] = sel[i[m].astype(np.int64)].astype(np.uint64) + np.uint64(id_offset)
-    return out, s
+    return oracle_over(O, rows, rq, k, dtype, metric, eligible_rows(rows.shape[0], allowed), id_offset)
 
 
 def numpy_map(n, deleted, offset=0):

@@ -6,62 +6,20 @@ every id i != ID_NONE becomes live[i].  live is increasing, so ties still break 
 the live rows are (ID_NONE, NaN).  Wherever the certificate's bound is finite and the path is not EXACT, the observed
 |fast - canonical| must lie inside it.
 """
-import os
-
 import numpy as np
 import pytest
 
+from support import (  # noqa: F401
+    PATH_STREAM, PATH_MFMA, PATH_EXACT, ID_NONE, va, bits, assert_same, check_bound, eligible_rows, oracle_over)
+
 pytestmark = pytest.mark.gpu
 
-DT = {"f32": 0, "bf16": 1}
-METRIC_COSINE, METRIC_L2 = 0, 1
-PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT = 0, 1, 2, 3
-ID_NONE = np.uint64(0xFFFFFFFFFFFFFFFF)
-THREADS = max(1, min(16, len(os.sched_getaffinity(0))))
 METRICS = ["cosine", "l2", "ip"]
-
-
-@pytest.fixture(scope="module")
-def va():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import vrod_amd
-    vrod_amd.load()
-    return vrod_amd
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def assert_same(ids, sc, oi, osc, what=""):
-    assert np.array_equal(ids, oi), f"{what}: ids differ at {np.argwhere(ids != oi)[:5]}"
-    na, nb = np.isnan(sc), np.isnan(osc)
-    assert np.array_equal(na, nb), f"{what}: NaN positions differ at {np.argwhere(na != nb)[:5]}"
-    assert np.array_equal(bits(sc)[~na], bits(osc)[~nb]), f"{what}: score bits differ"
-
-
-def check_bound(st, what):
-    if st["path"] != PATH_EXACT and np.isfinite(st["eps_bound"]):
-        assert st["max_fast_err"] <= st["eps_bound"], f"{what}: {st}"
 
 
 def oracle_live(O, raw, rq, k, dtype, metric, deleted, id_offset=0):
     """The oracle over the live rows of `raw`, ids mapped back (+ id_offset)."""
-    n = raw.shape[0]
-    live = np.setdiff1d(np.arange(n, dtype=np.int64), np.asarray(deleted, dtype=np.int64))
-    nq = rq.shape[0]
-    if live.size == 0:
-        return np.full((nq, k), ID_NONE, np.uint64), np.full((nq, k), np.nan, np.float32)
-    prep = METRIC_COSINE if metric == "cosine" else METRIC_L2
-    scan = METRIC_L2 if metric == "l2" else METRIC_COSINE
-    pc = O.prepare(np.ascontiguousarray(raw[live]), DT[dtype], prep, threads=THREADS)
-    pq = O.prepare(rq, DT[dtype], prep, threads=THREADS)
-    i, s = O.scan_topk(pc, pq, k, scan, threads=THREADS)
-    out = np.full(i.shape, ID_NONE, np.uint64)
-    m = i != ID_NONE
-    out[m] = live[i[m].astype(np.int64)].astype(np.uint64) + np.uint64(id_offset)
-    return out, s
+    return oracle_over(O, raw, rq, k, dtype, metric, eligible_rows(raw.shape[0], deleted=deleted), id_offset)
 
 
 def search_case(va, O, raw, rq, k, dtype, metric, deleted, path, split=None, what=""):

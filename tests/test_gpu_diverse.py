@@ -16,38 +16,18 @@ import numpy as np
 import pytest
 
 from diverse_model import DiverseModel
+import support
+from support import PATH_AUTO, PATH_EXACT, ID_NONE, va, bits, same_f32  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-PATH_AUTO, PATH_EXACT = 0, 3
-ID_NONE = np.uint64(0xFFFFFFFFFFFFFFFF)
 N = 3000
 SENT_ID, SENT_SC, SENT_MM = np.uint64(0x5A5A5A5A5A5A5A5A), np.float32(-12345.5), np.float32(-777.25)
 
 
-@pytest.fixture(scope="module")
-def va():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import vrod_amd
-    vrod_amd.load()
-    return vrod_amd
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def same_f32(a, b):
-    na, nb = np.isnan(a), np.isnan(b)
-    return np.array_equal(na, nb) and np.array_equal(bits(a)[~na], bits(b)[~nb])
-
-
 def assert_same(got, want, what=""):
     (ids, sc, mm), (oi, osc, omm) = got, want
-    assert ids.shape == oi.shape and sc.shape == osc.shape and mm.shape == omm.shape, what
-    assert np.array_equal(ids, oi), f"{what}: ids differ at {np.argwhere(ids != oi)[:5]}"
-    assert same_f32(sc, osc), f"{what}: score bits differ"
+    support.assert_same(ids, sc, oi, osc, what)
     assert same_f32(mm, omm), f"{what}: mmr bits differ at {np.argwhere(bits(mm) != bits(omm))[:5]}"
 
 

@@ -6,39 +6,15 @@ i != ID_NONE becomes eligible[i].  eligible is increasing, so ties still break b
 eligible rows are (ID_NONE, NaN).  Wherever the path is not EXACT or GATHER, the observed |fast - canonical| must lie
 inside the certificate's bound; a GATHER search reports no fast pass at all.
 """
-import os
-
 import numpy as np
 import pytest
 
+from support import (  # noqa: F401
+    PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT, PATH_GATHER, ID_NONE, va, assert_same, eligible_rows, oracle_over, row_bytes)
+
 pytestmark = pytest.mark.gpu
 
-DT = {"f32": 0, "bf16": 1}
-METRIC_COSINE, METRIC_L2 = 0, 1
-PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT, PATH_GATHER = 0, 1, 2, 3, 4
-ID_NONE = np.uint64(0xFFFFFFFFFFFFFFFF)
-THREADS = max(1, min(16, len(os.sched_getaffinity(0))))
 METRICS = ["cosine", "l2", "ip"]
-
-
-@pytest.fixture(scope="module")
-def va():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import vrod_amd
-    vrod_amd.load()
-    return vrod_amd
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def assert_same(ids, sc, oi, osc, what=""):
-    assert np.array_equal(ids, oi), f"{what}: ids differ at {np.argwhere(ids != oi)[:5]}"
-    na, nb = np.isnan(sc), np.isnan(osc)
-    assert np.array_equal(na, nb), f"{what}: NaN positions differ at {np.argwhere(na != nb)[:5]}"
-    assert np.array_equal(bits(sc)[~na], bits(osc)[~nb]), f"{what}: score bits differ"
 
 
 def check_stats(st, what, m=None, row_bytes=None, dim=None):
@@ -50,34 +26,6 @@ def check_stats(st, what, m=None, row_bytes=None, dim=None):
             assert st["scan_flops"] == 2.0 * st["nq"] * m * dim, f"{what}: {st}"
     elif st["path"] != PATH_EXACT and np.isfinite(st["eps_bound"]):
         assert st["max_fast_err"] <= st["eps_bound"], f"{what}: {st}"
-
-
-def eligible_rows(n, allow, deleted=()):
-    """Rows < n that are allowed (allow: bool array, rows past it are not) and not deleted."""
-    a = np.zeros(n, bool)
-    a[:len(allow)] = allow
-    a[np.asarray(deleted, dtype=np.int64)] = False
-    return np.flatnonzero(a)
-
-
-def oracle_eligible(O, raw, rq, k, dtype, metric, eligible, id_offset=0):
-    """The oracle over the rows `eligible` of `raw`, ids mapped back (+ id_offset)."""
-    nq = rq.shape[0]
-    if eligible.size == 0:
-        return np.full((nq, k), ID_NONE, np.uint64), np.full((nq, k), np.nan, np.float32)
-    prep = METRIC_COSINE if metric == "cosine" else METRIC_L2
-    scan = METRIC_L2 if metric == "l2" else METRIC_COSINE
-    pc = O.prepare(np.ascontiguousarray(raw[eligible]), DT[dtype], prep, threads=THREADS)
-    pq = O.prepare(rq, DT[dtype], prep, threads=THREADS)
-    i, s = O.scan_topk(pc, pq, k, scan, threads=THREADS)
-    out = np.full(i.shape, ID_NONE, np.uint64)
-    m = i != ID_NONE
-    out[m] = eligible[i[m].astype(np.int64)].astype(np.uint64) + np.uint64(id_offset)
-    return out, s
-
-
-def row_bytes(dtype, dim):
-    return (-(-dim // 64) * 64 * 2) if dtype == "bf16" else (-(-dim // 32) * 32 * 4)
 
 
 # ---------------------------------------------------------------- every path x dtype x metric x filter kind
@@ -121,7 +69,7 @@ def test_every_path_honours_the_filter(va, oracle, big, metric, dtype):
             ix.set_filter(allow)
             el = eligible_rows(N_BIG, allow)
             assert ix.filter_count() == el.size and ix.live_count() == N_BIG and ix.count == N_BIG
-            oi, osc = oracle_eligible(oracle, raw, queries, k, dtype, metric, el)
+            oi, osc = oracle_over(oracle, raw, queries, k, dtype, metric, el)
             for path, nq in PATHS:
                 what = f"{metric}/{dtype}/{kind}/path={path}/nq={nq}"
                 ix.set_path(path)
@@ -164,7 +112,7 @@ def test_fp32_mfma_forms_under_a_filter(va, oracle, big, split):
             ids, sc = ix.search(queries[:nq], k)
             st = ix.last_stats()
             assert st["split_pass"] == (1 if split == "1" else 0), st
-            oi, osc = oracle_eligible(oracle, raw, queries[:nq], k, "f32", "cosine", eligible_rows(N_BIG, filters[kind]))
+            oi, osc = oracle_over(oracle, raw, queries[:nq], k, "f32", "cosine", eligible_rows(N_BIG, filters[kind]))
             assert_same(ids, sc, oi, osc, f"split={split}/{kind}")
             check_stats(st, f"split={split}/{kind}")
 
@@ -191,7 +139,7 @@ def test_band_pass_with_copies_under_a_filter(va, oracle, big):
         ix.set_filter(allow)
         ids, sc = ix.search(rq, 10)
         st = ix.last_stats()
-    oi, osc = oracle_eligible(oracle, raw, rq, 10, "bf16", "cosine", eligible_rows(N_BIG, allow))
+    oi, osc = oracle_over(oracle, raw, rq, 10, "bf16", "cosine", eligible_rows(N_BIG, allow))
     assert_same(ids, sc, oi, osc, "copies")
     for g in range(nq):
         allowed = np.sort(pos[g][allow[pos[g]]])
@@ -212,7 +160,7 @@ def small():
 
 
 def run_paths(ix, O, raw, queries, k, dtype, metric, el, what, id_offset=0):
-    oi, osc = oracle_eligible(O, raw, queries, k, dtype, metric, el, id_offset)
+    oi, osc = oracle_over(O, raw, queries, k, dtype, metric, el, id_offset)
     for path, nq in SMALL_PATHS:
         ix.set_path(path)
         ids, sc = ix.search(queries[:nq], k)
@@ -346,7 +294,7 @@ def test_filter_while_pending_fails_then_applies(va, oracle, small):
             ix.search_end()
             torch.cuda.synchronize()
             got += [(o[0].cpu().numpy().view(np.uint64).copy(), o[1].cpu().numpy().copy()) for o in outs[1:]]
-    oi, osc = oracle_eligible(oracle, raw, queries[:nq], k, "bf16", "cosine", np.flatnonzero(allow))
+    oi, osc = oracle_over(oracle, raw, queries[:nq], k, "bf16", "cosine", np.flatnonzero(allow))
     for i, (ids, sc) in enumerate(got):
         assert_same(ids, sc, oi, osc, f"pipelined {i}")
 
@@ -394,7 +342,7 @@ def test_graph_replay_sees_every_filter_change(va, oracle):
             else:
                 ix.set_filter(None)
                 allow = np.ones(n, bool)
-            oi, osc = oracle_eligible(oracle, raw, rq, k, "f32", "cosine", eligible_rows(n, allow, gone))
+            oi, osc = oracle_over(oracle, raw, rq, k, "f32", "cosine", eligible_rows(n, allow, gone))
             for step, (ids, sc) in enumerate(pipeline(ix, 8)):
                 assert_same(ids, sc, oi, osc, f"{what}, step {step}")
 
@@ -419,10 +367,10 @@ def test_multi_device_routes_the_filter_to_shards(va, oracle, metric, nq, path):
         el = eligible_rows(n, allow, deleted)
         assert ix.filter_count() == el.size
         ids, sc = ix.search(rq, k)
-        oi, osc = oracle_eligible(oracle, raw, rq, k, "f32", metric, el)
+        oi, osc = oracle_over(oracle, raw, rq, k, "f32", metric, el)
         assert_same(ids, sc, oi, osc, f"multi/{metric}/nq={nq}/path={path}")
         ix.set_filter(None)
         assert ix.filter_count() == n - deleted.size
         ids, sc = ix.search(rq, k)
-        oi, osc = oracle_eligible(oracle, raw, rq, k, "f32", metric, eligible_rows(n, np.ones(n, bool), deleted))
+        oi, osc = oracle_over(oracle, raw, rq, k, "f32", metric, eligible_rows(n, np.ones(n, bool), deleted))
         assert_same(ids, sc, oi, osc, f"multi cleared/{metric}/nq={nq}/path={path}")

@@ -21,22 +21,11 @@ same generator the oracle holds (tests/test_gpu_parity.py::test_synth_stream_mat
 import numpy as np
 import pytest
 
+from support import va, bits  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 CORPUS_SEED, QUERY_SEED = 1, 2
-
-
-@pytest.fixture(scope="module")
-def va():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import vrod_amd
-    vrod_amd.load()
-    return vrod_amd
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def search_syn(ix, seed, first, nq, k, path=0):

@@ -5,16 +5,9 @@ form of this.)"""
 import numpy as np
 import pytest
 
+from support import DT, ME, va  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def va():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import vrod_amd
-    vrod_amd.load()
-    return vrod_amd
 
 
 @pytest.mark.parametrize("dtype,metric,seed", [("bf16", "cosine", 7), ("f32", "l2", 8)])

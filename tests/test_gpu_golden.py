@@ -8,6 +8,8 @@ import os
 import numpy as np
 import pytest
 
+from support import va  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -15,13 +17,6 @@ GOLD = np.load(os.path.join(HERE, "golden", "golden.npz"), allow_pickle=False)
 META = json.load(open(os.path.join(HERE, "golden", "golden_meta.json")))
 DTYPE = {0: "f32", 1: "bf16"}
 METRIC = {0: "cosine", 1: "l2"}
-
-
-@pytest.fixture(scope="module")
-def va():
-    import vrod_amd
-    vrod_amd.load()
-    return vrod_amd
 
 
 def test_device_generator_matches_golden(va):

@@ -7,20 +7,9 @@ and step aside as soon as anything differs.
 import numpy as np
 import pytest
 
+from support import DT, ME, va, bits  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def va():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import vrod_amd
-    vrod_amd.load()
-    return vrod_amd
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 @pytest.mark.parametrize("dtype,metric,nq", [("f32", "cosine", 1), ("f32", "l2", 4), ("bf16", "cosine", 3)])

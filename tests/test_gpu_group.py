@@ -22,19 +22,15 @@ before the library is asked anything:
     210 of its ~ 310 labels -- so at k = 300 and k = 400 light queries take the dense stage too, which the comparison
     with the oracle covers.
 """
-import os
-
 import numpy as np
 import pytest
 
+import support
+from support import (  # noqa: F401
+    DT, METRIC_COSINE, METRIC_L2, PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT, PATH_GATHER, ID_NONE, MAX_K, THREADS, va, O, bits, first_k)
+
 pytestmark = pytest.mark.gpu
 
-DT = {"f32": 0, "bf16": 1}
-METRIC_COSINE, METRIC_L2 = 0, 1
-PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT, PATH_GATHER = 0, 1, 2, 3, 4
-ID_NONE = np.uint64(0xFFFFFFFFFFFFFFFF)
-MAX_K = 3584
-THREADS = max(1, min(16, len(os.sched_getaffinity(0))))
 N, NQ = 20_000, 70
 L_A, L_B, L_BROAD = 3_000_000_000, 70_000, 0xFFFFFFFF
 N_A, N_B, N_BROAD = 5_000, 3_700, 4_500
@@ -44,36 +40,9 @@ HEAVY = (0, 1)
 K_ABOVE = 400                                      # more than the corpus has labels
 
 
-def first_k(k, eligible):
-    """group_plan.h group_first_k, restated."""
-    return min(MAX_K, eligible, max(4 * k, k + 32))
-
-
-@pytest.fixture(scope="module")
-def va():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import vrod_amd
-    vrod_amd.load()
-    return vrod_amd
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
 def assert_same(got, want, what=""):
     (ids, sc, lab), (oi, osc, ol) = got, want
-    assert np.array_equal(ids, oi), f"{what}: ids differ at {np.argwhere(ids != oi)[:5]}"
-    na, nb = np.isnan(sc), np.isnan(osc)
-    assert np.array_equal(na, nb), f"{what}: NaN positions differ at {np.argwhere(na != nb)[:5]}"
-    assert np.array_equal(bits(sc)[~na], bits(osc)[~nb]), f"{what}: score bits differ"
+    support.assert_same(ids, sc, oi, osc, what)
     assert np.array_equal(lab, ol), f"{what}: labels differ at {np.argwhere(lab != ol)[:5]}"
 
 

@@ -13,44 +13,18 @@ import subprocess
 import numpy as np
 import pytest
 
+from support import DT, METRIC_COSINE, METRIC_L2, THREADS, va, bits, assert_same, check_bound  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
-DT = {"f32": 0, "bf16": 1}
-METRIC_COSINE, METRIC_L2 = 0, 1
-THREADS = max(1, min(16, len(os.sched_getaffinity(0))))
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VROD = os.path.join(ROOT, "vrod_amd", "vrod")
-
-
-@pytest.fixture(scope="module")
-def va():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import vrod_amd
-    vrod_amd.load()
-    return vrod_amd
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def assert_same(ids, sc, oi, osc, what=""):
-    assert np.array_equal(ids, oi), f"{what}: ids differ at {np.argwhere(ids != oi)[:5]}"
-    na, nb = np.isnan(sc), np.isnan(osc)
-    assert np.array_equal(na, nb), f"{what}: NaN positions differ at {np.argwhere(na != nb)[:5]}"
-    assert np.array_equal(bits(sc)[~na], bits(osc)[~nb]), f"{what}: score bits differ"
 
 
 def oracle_ip(O, raw, rq, k, dtype, id_offset=0):
     pc = O.prepare(raw, DT[dtype], METRIC_L2, threads=THREADS)
     pq = O.prepare(rq, DT[dtype], METRIC_L2, threads=THREADS)
     return O.scan_topk(pc, pq, k, METRIC_COSINE, id_offset=id_offset, threads=THREADS)
-
-
-def check_bound(st, what):
-    if st["path"] != 3 and np.isfinite(st["eps_bound"]):
-        assert st["max_fast_err"] <= st["eps_bound"], f"{what}: {st}"
 
 
 def run_case(va, O, raw, rq, k, dtype, path, split=None, expect=None):

@@ -8,65 +8,18 @@ One corpus (40 000 rows; d = 64, and d = 100 whose tail chunk has padding that m
 of the rows (AUTO scans it densely), one on a tenth, labels of exactly 1, 63, 64, 65 and 8 193 (= kSelectChunk + 1) rows,
 200 labels of ~20 rows, label 0 on what is left, and two labels no row carries.
 """
-import math
-import os
-
 import numpy as np
 import pytest
 
+from support import (  # noqa: F401
+    PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT, PATH_GATHER, ID_NONE, va, O, assert_same, oracle_over, row_bytes, takes_segments)
+
 pytestmark = pytest.mark.gpu
 
-DT = {"f32": 0, "bf16": 1}
-METRIC_COSINE, METRIC_L2 = 0, 1
-PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT, PATH_GATHER = 0, 1, 2, 3, 4
-ID_NONE = np.uint64(0xFFFFFFFFFFFFFFFF)
-THREADS = max(1, min(16, len(os.sched_getaffinity(0))))
 N = 40_000
 L_HALF, L_TENTH, L_BIG, L_NONE_A, L_NONE_B = 4_000_000_000, 1000, 8193, 5, 77777
 L_EXACT = {1: 1, 63: 63, 64: 64, 65: 65}          # label -> rows
 SMALL0, N_SMALL = 10_000, 200
-
-
-@pytest.fixture(scope="module")
-def va():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import vrod_amd
-    vrod_amd.load()
-    return vrod_amd
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def assert_same(ids, sc, oi, osc, what=""):
-    assert np.array_equal(ids, oi), f"{what}: ids differ at {np.argwhere(ids != oi)[:5]}"
-    na, nb = np.isnan(sc), np.isnan(osc)
-    assert np.array_equal(na, nb), f"{what}: NaN positions differ at {np.argwhere(na != nb)[:5]}"
-    assert np.array_equal(bits(sc)[~na], bits(osc)[~nb]), f"{what}: score bits differ"
-
-
-def oracle_eligible(O, raw, rq, k, dtype, metric, eligible, id_offset=0):
-    """The oracle over the rows `eligible` of `raw`, ids mapped back (+ id_offset)."""
-    nq = rq.shape[0]
-    if eligible.size == 0:
-        return np.full((nq, k), ID_NONE, np.uint64), np.full((nq, k), np.nan, np.float32)
-    prep = METRIC_COSINE if metric == "cosine" else METRIC_L2
-    scan = METRIC_L2 if metric == "l2" else METRIC_COSINE
-    pc = O.prepare(np.ascontiguousarray(raw[eligible]), DT[dtype], prep, threads=THREADS)
-    pq = O.prepare(rq, DT[dtype], prep, threads=THREADS)
-    i, s = O.scan_topk(pc, pq, k, scan, threads=THREADS)
-    out = np.full(i.shape, ID_NONE, np.uint64)
-    m = i != ID_NONE
-    out[m] = eligible[i[m].astype(np.int64)].astype(np.uint64) + np.uint64(id_offset)
-    return out, s
 
 
 def expected(O, raw, rq, qlabels, k, dtype, metric, labels, ok=None, id_offset=0):
@@ -78,27 +31,8 @@ def expected(O, raw, rq, qlabels, k, dtype, metric, labels, ok=None, id_offset=0
     for L in np.unique(qlabels):
         qs = np.flatnonzero(qlabels == L)
         rows = np.flatnonzero((labels == L) & ok)
-        ids[qs], sc[qs] = oracle_eligible(O, raw, np.ascontiguousarray(rq[qs]), k, dtype, metric, rows, id_offset)
+        ids[qs], sc[qs] = oracle_over(O, raw, np.ascontiguousarray(rq[qs]), k, dtype, metric, rows, id_offset)
     return ids, sc
-
-
-def row_bytes(dtype, dim):
-    return (-(-dim // 64) * 64 * 2) if dtype == "bf16" else (-(-dim // 32) * 32 * 4)
-
-
-def takes_segments(path, dtype, n, m, nq, dim):
-    """search_plan.h filter_route, restated: whether a group of nq queries over m of n rows is scored on its own rows."""
-    if path == PATH_GATHER:
-        return True
-    if path != PATH_AUTO:
-        return False
-    if m == 0:
-        return True
-    rb = dim * (2.0 if dtype == "bf16" else 4.0)
-    steps = float(nq) * dim
-    masked = math.log10(n / m) if 0 < m < n else 0.0
-    dense_step = (1.0e-6 if dtype == "bf16" else 3.0e-6) + 3.0e-7 * masked
-    return m * (rb * 3.0e-4 + steps * 1.56e-4) < n * (rb * 2.0e-4 + steps * dense_step)
 
 
 def make_labels(rng):

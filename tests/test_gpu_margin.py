@@ -9,20 +9,9 @@ are the oracle's bits throughout.
 import numpy as np
 import pytest
 
+from support import va, bits  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def va():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import vrod_amd
-    vrod_amd.load()
-    return vrod_amd
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def test_margin_follows_the_certificates(va, oracle):

@@ -19,10 +19,10 @@ import numpy as np
 import pytest
 
 from multivec_model import MultivecModel, first_k
+from support import PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT, va, assert_scores_same  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT = 0, 1, 2, 3
 PATHS = {"auto": PATH_AUTO, "exact": PATH_EXACT, "stream": PATH_STREAM, "mfma": PATH_MFMA}
 N = 7_000
 L_BROAD, N_BROAD = 0xFFFFFFFF, 2_000
@@ -41,26 +41,11 @@ CASES = {
 K_ABOVE = 1_000   # more than the corpus has labels
 
 
-@pytest.fixture(scope="module")
-def va():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import vrod_amd
-    vrod_amd.load()
-    return vrod_amd
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
 def assert_same(got, want, what=""):
     (lab, sc, found), (ol, osc, of) = got, want
     assert np.array_equal(found, of), f"{what}: found differs at {np.argwhere(found != of)[:5]}"
     assert np.array_equal(lab, ol), f"{what}: labels differ at {np.argwhere(lab != ol)[:5]}"
-    na, nb = np.isnan(sc), np.isnan(osc)
-    assert np.array_equal(na, nb), f"{what}: NaN positions differ at {np.argwhere(na != nb)[:5]}"
-    assert np.array_equal(bits(sc)[~na], bits(osc)[~nb]), f"{what}: score bits differ"
+    assert_scores_same(sc, osc, what)
 
 
 def parity_labels(rng, n=N):

@@ -7,28 +7,10 @@ canonical re-score makes even the bf16 path bit-exact, which is stricter than th
 import numpy as np
 import pytest
 
+from support import DT, ME, va, bits  # noqa: F401
+from support import assert_same_all_bits as assert_same    # every score bit: these results hold no (ID_NONE, NaN) filler
+
 pytestmark = pytest.mark.gpu
-
-DT = {"f32": 0, "bf16": 1}
-ME = {"cosine": 0, "l2": 1}
-
-
-@pytest.fixture(scope="module")
-def va():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import vrod_amd
-    vrod_amd.load()  # raises if the HIP library is missing: no fallback
-    return vrod_amd
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def assert_same(ids, sc, oi, osc, what=""):
-    assert np.array_equal(ids, oi), f"{what}: ids differ at {np.argwhere(ids != oi)[:5]}"
-    assert np.array_equal(bits(sc), bits(osc)), f"{what}: score bits differ"
 
 
 def run_case(va, O, raw, rq, k, dtype, metric, path, id_offset=0):
@@ -470,3 +452,45 @@ def test_dim_beyond_the_limit_is_rejected(va):
     with pytest.raises(va.VrodError) as e:
         va.Index(32769, "f32", "cosine")
     assert e.value.code == 1
+
+
+def test_device_forms_refuse_queries_of_another_width(va, oracle):
+    """A device tensor whose rows are not `dim` wide would make the library read past the end of it (or take the wrong
+    rows): every device form that takes query vectors raises ValueError before the library is called, nothing is left
+    pending, and the handle answers a correct search afterwards."""
+    import torch
+    n, dim, nq, k = 200, 16, 4, 5
+    rng = np.random.default_rng(80)
+    raw = rng.standard_normal((n, dim)).astype(np.float32)
+    rq = rng.standard_normal((nq, dim)).astype(np.float32)
+    labels = torch.zeros(nq, dtype=torch.int32, device="cuda")
+    preds = torch.zeros((nq, 3), dtype=torch.int64, device="cuda")
+    thr = torch.zeros(nq, dtype=torch.float32, device="cuda")
+    oi = torch.empty((nq, k), dtype=torch.int64, device="cuda")
+    osc = torch.empty((nq, k), dtype=torch.float32, device="cuda")
+    with va.Index(dim, "f32", "cosine") as ix:
+        ix.add(raw)
+        forms = {
+            "search_device": lambda t: ix.search_device(t, k),
+            "search_labeled_device": lambda t: ix.search_labeled_device(t, k, labels),
+            "search_tagged_device": lambda t: ix.search_tagged_device(t, k, preds),
+            "search_grouped_device": lambda t: ix.search_grouped_device(t, k),
+            "range_search_device": lambda t: ix.range_search_device(t, thr, 64),
+            "search_begin_device": lambda t: ix.search_begin_device(t, k, oi, osc),
+            "search_diverse_device": lambda t: ix.search_diverse_device(t, k, 8, 0.5),
+        }
+        for width in (17, 15):
+            bad = torch.zeros((nq, width), dtype=torch.float32, device="cuda")
+            for name, call in forms.items():
+                with pytest.raises(ValueError, match=f"must be \\[n, {dim}\\]"):
+                    call(bad)
+                assert ix.pending == 0, name
+        with pytest.raises(ValueError, match=f"must be \\[n, {dim}\\]"):
+            ix.search_multivec_device(bad, torch.tensor([0, 2, 4], dtype=torch.int32, device="cuda"), k)
+        with pytest.raises(ValueError, match=f"must be \\[n, {dim}\\]"):
+            ix.search_device(torch.zeros(dim, dtype=torch.float32, device="cuda"), k)     # one query still needs [1, dim]
+        ids, sc = ix.search(rq, k)
+        di, ds = ix.search_device(torch.from_numpy(rq).cuda(), k)
+    want = oracle.search(raw, rq, k, DT["f32"], ME["cosine"])
+    assert_same(ids, sc, *want, "host form after the refusals")
+    assert_same(di.cpu().numpy().view(np.uint64), ds.cpu().numpy(), *want, "device form after the refusals")

@@ -8,23 +8,9 @@ search's prepare launch) and when a batch with NaN queries sits next to a good o
 import numpy as np
 import pytest
 
+from support import DT, ME, va, bits  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-DT = {"f32": 0, "bf16": 1}
-ME = {"cosine": 0, "l2": 1}
-
-
-@pytest.fixture(scope="module")
-def va():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import vrod_amd
-    vrod_amd.load()
-    return vrod_amd
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def pipelined(ix, torch, batches, k):

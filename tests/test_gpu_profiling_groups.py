@@ -14,21 +14,13 @@ nothing a handle learns from one search (the candidate margin) separates the run
 import numpy as np
 import pytest
 
+from support import PATH_MFMA, PATH_EXACT, PATH_GATHER, va  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
-PATH_MFMA, PATH_EXACT, PATH_GATHER = 2, 3, 4
 N, DIM, NQ, K = 4096, 64, 24, 10
 SIZES = [1, 37, 300, 1000]                              # the fifth label owns the rest
 TIMINGS = ("scan_ms", "total_ms", "sample_ms", "overlap_ms")
-
-
-@pytest.fixture(scope="module")
-def va():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import vrod_amd
-    vrod_amd.load()
-    return vrod_amd
 
 
 @pytest.fixture(scope="module")

@@ -5,9 +5,9 @@ oracle.  Seeds are fixed: failures reproduce."""
 import numpy as np
 import pytest
 
+from support import DT, ME, va  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-DT = {"f32": 0, "bf16": 1}
-ME = {"cosine": 0, "l2": 1}
 
 
 def _cases():
@@ -31,13 +31,6 @@ def _cases():
             nq = 64
         out.append((i, n, dim, nq, k, dtype, metric, path, scale, dup))
     return out
-
-
-@pytest.fixture(scope="module")
-def va():
-    import vrod_amd
-    vrod_amd.load()
-    return vrod_amd
 
 
 @pytest.mark.parametrize("case", _cases(), ids=lambda c: f"{c[0]}-n{c[1]}-d{c[2]}-q{c[3]}-k{c[4]}-{c[5]}-{c[6]}-p{c[7]}")

@@ -7,35 +7,19 @@ through elig.  lims, ids and score bits must be the oracle's, and wherever a fas
 must lie inside the bound the search reports.
 """
 import functools
-import os
 
 import numpy as np
 import pytest
 
 from conftest import f32_split
+from support import DT, PATH_STREAM, PATH_MFMA, PATH_EXACT, PATH_GATHER, THREADS, va, bits, assert_same_all_bits, hard_thresholds  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-DT = {"f32": 0, "bf16": 1}
-PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT, PATH_GATHER = 0, 1, 2, 3, 4
 ERR_INVALID_ARG, ERR_CAPACITY = 1, 8
-THREADS = max(1, min(16, len(os.sched_getaffinity(0))))
 METRICS = ["cosine", "l2", "ip"]
 # (handle dtype, VROD_F32_SPLIT): fp32 over the bf16 planes, fp32 on the fp32 matrix pass, bf16
 FORMS = [("f32", "1"), ("f32", "0"), ("bf16", None)]
-
-
-@pytest.fixture(scope="module")
-def va():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import vrod_amd
-    vrod_amd.load()
-    return vrod_amd
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def better(metric):
@@ -72,8 +56,7 @@ def oracle_range(all_ids, all_sc, thr, metric, id_offset=0):
 def assert_range(got, want, what=""):
     (lims, ids, sc), (ol, oi, osc) = got, want
     assert np.array_equal(lims, ol), f"{what}: lims differ at {np.argwhere(lims != ol)[:5].ravel()} got {lims[:8]} want {ol[:8]}"
-    assert np.array_equal(ids, oi), f"{what}: ids differ at {np.argwhere(ids != oi)[:5].ravel()}"
-    assert np.array_equal(bits(sc), bits(osc)), f"{what}: score bits differ"
+    assert_same_all_bits(ids, sc, oi, osc, what)
 
 
 def check_stats(st, what, nq):
@@ -81,22 +64,6 @@ def check_stats(st, what, nq):
     assert st["k"] == 0 and st["nq"] == nq and st["band_queries"] == 0 and st["sample_ms"] == 0, f"{what}: {st}"
     if st["path"] == PATH_MFMA and st["fallback_queries"] < nq:
         assert np.isfinite(st["eps_bound"]) and st["max_fast_err"] <= st["eps_bound"], f"{what}: {st}"
-
-
-def hard_thresholds(all_sc, metric):
-    """Per query, cycling: exactly the score of the r-th result (r = 1, 10, 1000: the inclusive boundary), the midpoint
-    between two neighbouring scores, and better than the best (an empty result among non-empty ones)."""
-    nq, m = all_sc.shape
-    thr = np.empty(nq, np.float32)
-    for q in range(nq):
-        kind = q % 5
-        if kind < 3:
-            thr[q] = all_sc[q, min((0, 9, 999)[kind], m - 1)]
-        elif kind == 3:
-            thr[q] = np.float32((np.float64(all_sc[q, 20]) + np.float64(all_sc[q, 21])) / 2)
-        else:
-            thr[q] = np.nextafter(all_sc[q, 0], np.float32(-np.inf if metric == "l2" else np.inf))
-    return thr
 
 
 # ---------------------------------------------------------------- the matrix: dtype x metric x batch size

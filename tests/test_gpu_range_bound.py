@@ -10,22 +10,9 @@ import numpy as np
 import pytest
 
 import range_bound_cases as R
+from support import PATH_MFMA, va, bits  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-PATH_MFMA = 2
-
-
-@pytest.fixture(scope="module")
-def va():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import vrod_amd
-    vrod_amd.load()
-    return vrod_amd
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 @pytest.mark.parametrize("case", R.cases(), ids=R.case_id)

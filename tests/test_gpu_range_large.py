@@ -15,34 +15,12 @@ import sys
 import numpy as np
 import pytest
 
+from support import DT, PATH_MFMA, THREADS, va, bits, assert_same_all_bits, prep_of, form_of, hard_thresholds  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DT = {"f32": 0, "bf16": 1}
-PATH_MFMA = 2
-THREADS = max(1, min(16, len(os.sched_getaffinity(0))))
 LIST_CAP = 8192                      # entries of a query's hit list (kSelectChunk)
 SORT_CHUNK = 2048                    # kernels_range.hip kRangeSortChunk
-
-
-@pytest.fixture(scope="module")
-def va():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import vrod_amd
-    vrod_amd.load()
-    return vrod_amd
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def prep_of(metric):
-    return 0 if metric == "cosine" else 1
-
-
-def form_of(metric):
-    return 1 if metric == "l2" else 0
 
 
 def worse(metric):
@@ -52,8 +30,7 @@ def worse(metric):
 def assert_range(got, want, what):
     (lims, ids, sc), (ol, oi, osc) = got, want
     assert np.array_equal(lims, ol), f"{what}: counts differ at queries {np.argwhere(np.diff(lims.astype(np.int64)) != np.diff(ol.astype(np.int64)))[:8].ravel()}"
-    assert np.array_equal(ids, oi), f"{what}: ids differ at {np.argwhere(ids != oi)[:5].ravel()}"
-    assert np.array_equal(bits(sc), bits(osc)), f"{what}: score bits differ"
+    assert_same_all_bits(ids, sc, oi, osc, what)
 
 
 def reference(O, raw, rq, thr, dtype, metric, mask=None, block=4_000_000):
@@ -293,22 +270,6 @@ K_DIMS = [(40, "cosine"), (129, "l2"), (300, "ip"), (768, "l2"), (4096, "cosine"
 # long row is 2048 elements, 32 queries at a time (33 would take the 4-wave kernel).
 KERNEL_FORMS = [(k, dt, sp, nq, dim, me) for k, dt, sp, nq in (("w4", "bf16", None, 100), ("w4-split", "f32", "1", 100), ("phased", "f32", "0", 100))
                 for dim, me in K_DIMS] + [("skinny", "bf16", None, 33, dim, me) for dim, me in K_DIMS[:4]] + [("skinny", "bf16", None, 32, 2048, "cosine")]
-
-
-def hard_thresholds(all_sc, metric):
-    """As tests/test_gpu_range.py: per query, cycling: exactly the score of the 1st / 10th / 1000th result, the midpoint
-    between two neighbouring scores, and better than the best."""
-    nq, m = all_sc.shape
-    thr = np.empty(nq, np.float32)
-    for q in range(nq):
-        kind = q % 5
-        if kind < 3:
-            thr[q] = all_sc[q, min((0, 9, 999)[kind], m - 1)]
-        elif kind == 3:
-            thr[q] = np.float32((np.float64(all_sc[q, 20]) + np.float64(all_sc[q, 21])) / 2)
-        else:
-            thr[q] = np.nextafter(all_sc[q, 0], -worse(metric))
-    return thr
 
 
 @pytest.mark.parametrize("kernel, dtype, split, nq, dim, metric", KERNEL_FORMS, ids=[f"{k[0]}-{k[4]}-{k[5]}" for k in KERNEL_FORMS])

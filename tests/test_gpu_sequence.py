@@ -12,10 +12,10 @@ import pytest
 
 import sequence_plans as S
 from sequence_exec import ERR_UNSUPPORTED, SENT_ID, SENT_SC, Pair, same_lists
+from support import PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_GATHER
 
 pytestmark = pytest.mark.gpu
 
-PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT, PATH_GATHER = 0, 1, 2, 3, 4
 D = 72
 L_BIG, L_NOBODY = S.L_BIG, S.L_NOBODY
 

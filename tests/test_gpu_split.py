@@ -8,17 +8,9 @@ import os
 import numpy as np
 import pytest
 
+from support import ME, va, bits  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-ME = {"cosine": 0, "l2": 1}
-
-
-@pytest.fixture(scope="module")
-def va():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import vrod_amd
-    vrod_amd.load()
-    return vrod_amd
 
 
 @pytest.fixture()
@@ -30,10 +22,6 @@ def split_env():
         del os.environ["VROD_F32_SPLIT"]
     else:
         os.environ["VROD_F32_SPLIT"] = old
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 @pytest.mark.parametrize("metric", ["cosine", "l2"])

@@ -16,12 +16,10 @@ import sys
 import numpy as np
 import pytest
 
+from support import bits
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def stage_plan(n, nq, k, metric, num_cus):

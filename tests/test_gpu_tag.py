@@ -13,7 +13,6 @@ d = 64, and d = 100 whose tail chunk has padding that must not be walked).  Its 
   3 rows carry all 64 bits (they alone carry bits 6 and 7) and sit in every list at once; what is left carries 0.
 """
 import itertools
-import math
 import os
 import re
 
@@ -21,11 +20,11 @@ import numpy as np
 import pytest
 
 from tag_model import TagModelIndex, distinct_preds, tag_matches
+from support import (  # noqa: F401
+    PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT, PATH_GATHER, ID_NONE, va, assert_same, row_bytes, takes_segments)
 
 pytestmark = pytest.mark.gpu
 
-PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT, PATH_GATHER = 0, 1, 2, 3, 4
-ID_NONE = np.uint64(0xFFFFFFFFFFFFFFFF)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = 40_003
 ALL_ONES = 0xFFFFFFFFFFFFFFFF
@@ -52,45 +51,6 @@ P_UNSAT2 = (0, ALL_ONES, 1 << 63)
 
 def p_pair(j):
     return (0, B(*PAIRS[j]), 0)                      # all of two bits
-
-
-@pytest.fixture(scope="module")
-def va():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import vrod_amd
-    vrod_amd.load()
-    return vrod_amd
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def assert_same(ids, sc, oi, osc, what=""):
-    assert np.array_equal(ids, oi), f"{what}: ids differ at {np.argwhere(ids != oi)[:5]}"
-    na, nb = np.isnan(sc), np.isnan(osc)
-    assert np.array_equal(na, nb), f"{what}: NaN positions differ at {np.argwhere(na != nb)[:5]}"
-    assert np.array_equal(bits(sc)[~na], bits(osc)[~nb]), f"{what}: score bits differ"
-
-
-def row_bytes(dtype, dim):
-    return (-(-dim // 64) * 64 * 2) if dtype == "bf16" else (-(-dim // 32) * 32 * 4)
-
-
-def takes_segments(path, dtype, n, m, nq, dim):
-    """search_plan.h filter_route, restated: whether a group of nq queries over m of n rows is scored on its own rows."""
-    if path == PATH_GATHER:
-        return True
-    if path != PATH_AUTO:
-        return False
-    if m == 0:
-        return True
-    rb = dim * (2.0 if dtype == "bf16" else 4.0)
-    steps = float(nq) * dim
-    masked = math.log10(n / m) if 0 < m < n else 0.0
-    dense_step = (1.0e-6 if dtype == "bf16" else 3.0e-6) + 3.0e-7 * masked
-    return m * (rb * 3.0e-4 + steps * 1.56e-4) < n * (rb * 2.0e-4 + steps * dense_step)
 
 
 def make_tags(rng):

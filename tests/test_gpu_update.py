@@ -5,74 +5,20 @@ handle built from raw' -- the rows given to add() with raw'[ids[i] - offset] = r
 reference is the oracle over prepare(raw'), with deletions and a filter applied as rules 8 and 9 say.  Wherever the
 certificate's bound is finite and the path is not EXACT, the observed |fast - canonical| must lie inside it.
 """
-import os
-
 import numpy as np
 import pytest
 
+from support import (  # noqa: F401
+    DT, METRIC_COSINE, METRIC_L2, PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT, PATH_GATHER, ID_NONE, THREADS, va, bits, assert_same, check_bound, prep_of, form_of, eligible_rows, oracle_over)
+
 pytestmark = pytest.mark.gpu
 
-DT = {"f32": 0, "bf16": 1}
-METRIC_COSINE, METRIC_L2 = 0, 1
-PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT, PATH_GATHER = 0, 1, 2, 3, 4
-ID_NONE = np.uint64(0xFFFFFFFFFFFFFFFF)
-THREADS = max(1, min(16, len(os.sched_getaffinity(0))))
 METRICS = ["cosine", "l2", "ip"]
-
-
-@pytest.fixture(scope="module")
-def va():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import vrod_amd
-    vrod_amd.load()
-    return vrod_amd
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def assert_same(ids, sc, oi, osc, what=""):
-    assert np.array_equal(ids, oi), f"{what}: ids differ at {np.argwhere(ids != oi)[:5]}"
-    na, nb = np.isnan(sc), np.isnan(osc)
-    assert np.array_equal(na, nb), f"{what}: NaN positions differ at {np.argwhere(na != nb)[:5]}"
-    assert np.array_equal(bits(sc)[~na], bits(osc)[~nb]), f"{what}: score bits differ"
-
-
-def check_bound(st, what):
-    if st["path"] != PATH_EXACT and np.isfinite(st["eps_bound"]):
-        assert st["max_fast_err"] <= st["eps_bound"], f"{what}: {st}"
-
-
-def prep_of(metric):
-    return METRIC_COSINE if metric == "cosine" else METRIC_L2
-
-
-def form_of(metric):
-    return METRIC_L2 if metric == "l2" else METRIC_COSINE
 
 
 def oracle_live(O, raw, rq, k, dtype, metric, deleted=(), id_offset=0, allowed=None):
     """The oracle over the eligible rows of `raw` (not deleted, and allowed if a bool mask is given), ids mapped back."""
-    n = raw.shape[0]
-    keep = np.ones(n, bool)
-    keep[np.asarray(deleted, dtype=np.int64)] = False
-    if allowed is not None:
-        a = np.zeros(n, bool)
-        a[:len(allowed)] = allowed
-        keep &= a
-    live = np.flatnonzero(keep)
-    nq = rq.shape[0]
-    if live.size == 0:
-        return np.full((nq, k), ID_NONE, np.uint64), np.full((nq, k), np.nan, np.float32)
-    pc = O.prepare(np.ascontiguousarray(raw[live]), DT[dtype], prep_of(metric), threads=THREADS)
-    pq = O.prepare(rq, DT[dtype], prep_of(metric), threads=THREADS)
-    i, s = O.scan_topk(pc, pq, k, form_of(metric), threads=THREADS)
-    out = np.full(i.shape, ID_NONE, np.uint64)
-    m = i != ID_NONE
-    out[m] = live[i[m].astype(np.int64)].astype(np.uint64) + np.uint64(id_offset)
-    return out, s
+    return oracle_over(O, raw, rq, k, dtype, metric, eligible_rows(raw.shape[0], allowed, deleted), id_offset)
 
 
 def applied(raw, ids, rows, offset=0):

@@ -31,8 +31,8 @@ import pytest
 
 import sequence_plans as S
 from sequence_exec import Pair
+from support import PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT, PATH_GATHER
 
-PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT, PATH_GATHER = S.PATH_AUTO, S.PATH_STREAM, S.PATH_MFMA, S.PATH_EXACT, S.PATH_GATHER
 WIDTHS = (1, 3, 31, 33, 65, 129, 257, 1100, 4100, 32768)
 ROWS = {1: 5003, 3: 4999, 31: 4001, 33: 3501, 65: 3333, 129: 3001, 257: 3003, 1100: 1500, 4100: 1500, 32768: 600}
 METRICS = ("cosine", "l2", "ip")

@@ -10,13 +10,11 @@ import os
 import numpy as np
 import pytest
 
+from support import bits
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = np.load(os.path.join(HERE, "golden", "golden.npz"), allow_pickle=False)
 META = json.load(open(os.path.join(HERE, "golden", "golden_meta.json")))
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 @pytest.mark.parametrize("name", sorted(META))

@@ -5,27 +5,15 @@ include/vrod.h: inclusive boundary, a NaN score never qualifies, best first then
 import numpy as np
 import pytest
 
-DT = {"f32": 0, "bf16": 1}
+from support import DT, assert_same_all_bits, bits, prep_of, form_of
+
 METRICS = ["cosine", "l2", "ip"]
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def prep_of(metric):
-    return 0 if metric == "cosine" else 1
-
-
-def form_of(metric):
-    return 1 if metric == "l2" else 0
 
 
 def assert_same(got, want, what=""):
     assert np.array_equal(got[0], want[0]), f"{what}: lims {got[0][:8]} != {want[0][:8]}"
     assert got[1].dtype == np.uint64 and got[2].dtype == np.float32
-    assert np.array_equal(got[1], want[1]), f"{what}: ids differ at {np.argwhere(got[1] != want[1])[:5].ravel()}"
-    assert np.array_equal(bits(got[2]), bits(want[2])), f"{what}: score bits differ"
+    assert_same_all_bits(got[1], got[2], want[1], want[2], what)
 
 
 def prefix_composition(O, raw, rq, thr, dtype, metric, elig=None, id_offset=0):

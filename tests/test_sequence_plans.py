@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 
 import sequence_plans as S
-from index_model import ID_NONE, ModelIndex, bits
+from index_model import ID_NONE, ModelIndex
+from support import bits
 from oracle import oracle as O
 
 PLANS = {}

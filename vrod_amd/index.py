@@ -38,6 +38,24 @@ def _enum(v, table, what):
     return int(v)
 
 
+def _ptr(a):
+    """The data pointer of a numpy array; None (a NULL pointer) stays None."""
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _out(nq, k, *dtypes):
+    """One empty [nq, k] numpy result array per dtype."""
+    return tuple(np.empty((nq, k), dtype=d) for d in dtypes)
+
+
+def _device_out(out, shape, dtype, device):
+    """The caller's output tensor, or a new one of `shape`."""
+    if out is None:
+        import torch
+        out = torch.empty(shape, dtype=dtype, device=device)
+    return out
+
+
 class Index:
     """One shard of a brute-force index on one MI355X."""
 
@@ -80,7 +98,7 @@ class Index:
         rows = np.ascontiguousarray(rows, dtype=np.float32)
         if rows.ndim != 2 or rows.shape[1] != self.dim:
             raise ValueError(f"rows must be [n, {self.dim}]")
-        check(self._L.vrod_index_add(self._h, rows.ctypes.data_as(C.c_void_p), rows.shape[0]))
+        check(self._L.vrod_index_add(self._h, _ptr(rows), rows.shape[0]))
 
     def add_synthetic(self, seed: int, first_row: int, n: int):
         check(self._L.vrod_index_add_synthetic(self._h, int(seed), int(first_row), int(n)))
@@ -107,7 +125,7 @@ class Index:
     def delete(self, ids):
         """Delete rows by the ids searches report (vrod_index_delete): any integer array-like, all or nothing."""
         a = self._ids(ids)
-        check(self._L.vrod_index_delete(self._h, a.ctypes.data_as(C.c_void_p), a.size))
+        check(self._L.vrod_index_delete(self._h, _ptr(a), a.size))
 
     def update(self, ids, rows: np.ndarray):
         """Give row ids[i] the vector rows[i] in place (vrod_index_update): the row keeps its id, the vector is prepared
@@ -118,14 +136,14 @@ class Index:
             rows = rows[None, :]
         if rows.ndim != 2 or rows.shape[1] != self.dim or rows.shape[0] != a.size:
             raise ValueError(f"rows must be [{a.size}, {self.dim}]")
-        check(self._L.vrod_index_update(self._h, a.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p), a.size))
+        check(self._L.vrod_index_update(self._h, _ptr(a), _ptr(rows), a.size))
 
     def compact(self) -> np.ndarray:
         """Physically remove the deleted rows and renumber the survivors densely (vrod_index_compact).  Returns the
         new-id map, a uint64 array over the old rows: entry i is the new id of old id offset + i, or ID_NONE."""
         n = self.count
         new_ids = np.empty(n, dtype=np.uint64)
-        check(self._L.vrod_index_compact(self._h, new_ids.ctypes.data_as(C.c_void_p), n))
+        check(self._L.vrod_index_compact(self._h, _ptr(new_ids), n))
         return new_ids
 
     def live_count(self) -> int:
@@ -150,7 +168,7 @@ class Index:
         packed = np.packbits(a, bitorder="little")
         buf[:packed.size] = packed
         words = buf.view(np.uint32)
-        check(self._L.vrod_index_set_filter(self._h, words.ctypes.data_as(C.c_void_p), n))
+        check(self._L.vrod_index_set_filter(self._h, _ptr(words), n))
 
     def filter_count(self) -> int:
         """Rows the next search may return: live and allowed (= live_count() without a filter)."""
@@ -175,11 +193,11 @@ class Index:
         """Give the rows with ids first_id, first_id + 1, ... the labels of an integer array-like (vrod_index_set_labels).
         Every row carries label 0 until it is given one; only search_labeled and search_grouped read labels."""
         a = self._labels(labels)
-        check(self._L.vrod_index_set_labels(self._h, int(first_id), a.ctypes.data_as(C.c_void_p), a.size))
+        check(self._L.vrod_index_set_labels(self._h, int(first_id), _ptr(a), a.size))
 
     def get_labels(self, first_id: int, n: int) -> np.ndarray:
         out = np.empty(int(n), dtype=np.uint32)
-        check(self._L.vrod_index_get_labels(self._h, int(first_id), int(n), out.ctypes.data_as(C.c_void_p)))
+        check(self._L.vrod_index_get_labels(self._h, int(first_id), int(n), _ptr(out)))
         return out
 
     @staticmethod
@@ -202,11 +220,11 @@ class Index:
         """Give the rows with ids first_id, first_id + 1, ... the 64-bit tag masks of an integer array-like
         (vrod_index_set_tags).  Every row carries 0 until it is given tags; only search_tagged reads them."""
         a = self._u64(tags, "tags", (-1,))
-        check(self._L.vrod_index_set_tags(self._h, int(first_id), a.ctypes.data_as(C.c_void_p), a.size))
+        check(self._L.vrod_index_set_tags(self._h, int(first_id), _ptr(a), a.size))
 
     def get_tags(self, first_id: int, n: int) -> np.ndarray:
         out = np.empty(int(n), dtype=np.uint64)
-        check(self._L.vrod_index_get_tags(self._h, int(first_id), int(n), out.ctypes.data_as(C.c_void_p)))
+        check(self._L.vrod_index_get_tags(self._h, int(first_id), int(n), _ptr(out)))
         return out
 
     def set_id_offset(self, off: int):
@@ -215,7 +233,7 @@ class Index:
 
     def get_rows(self, first: int, n: int) -> np.ndarray:
         out = np.empty((n, self.dim), dtype=np.float32)
-        check(self._L.vrod_index_get_rows(self._h, int(first), int(n), out.ctypes.data_as(C.c_void_p)))
+        check(self._L.vrod_index_get_rows(self._h, int(first), int(n), _ptr(out)))
         return out
 
     # -- knobs
@@ -241,125 +259,105 @@ class Index:
         return d
 
     # -- search
-    def search(self, queries: np.ndarray, k: int):
-        """numpy [nq, dim] fp32 -> (ids uint64 [nq, k], scores float32 [nq, k])."""
+    def _queries(self, queries) -> np.ndarray:
+        """Any [nq, dim] (or [dim]) array-like -> a contiguous [nq, dim] fp32 array."""
         queries = np.ascontiguousarray(queries, dtype=np.float32)
         if queries.ndim == 1:
             queries = queries[None, :]
         if queries.ndim != 2 or queries.shape[1] != self.dim:
             raise ValueError(f"queries must be [nq, {self.dim}]")
+        return queries
+
+    def _device_queries(self, t, what="queries"):
+        """Checks a device tensor of queries ([n, dim] fp32, contiguous) -> (n, its device, its device's current stream)."""
+        import torch
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+        if t.dim() != 2 or t.shape[1] != self.dim:
+            raise ValueError(f"{what} must be [n, {self.dim}]")
+        return t.shape[0], t.device, C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+    def search(self, queries: np.ndarray, k: int):
+        """numpy [nq, dim] fp32 -> (ids uint64 [nq, k], scores float32 [nq, k])."""
+        queries = self._queries(queries)
         nq = queries.shape[0]
-        ids = np.empty((nq, k), dtype=np.uint64)
-        sc = np.empty((nq, k), dtype=np.float32)
-        check(self._L.vrod_search(self._h, queries.ctypes.data_as(C.c_void_p), nq, int(k),
-                                  ids.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p)))
+        ids, sc = _out(nq, k, np.uint64, np.float32)
+        check(self._L.vrod_search(self._h, _ptr(queries), nq, int(k), _ptr(ids), _ptr(sc)))
         return ids, sc
 
     def search_labeled(self, queries: np.ndarray, k: int, labels):
         """search() with a label per query (vrod_search_labeled): query q sees only the eligible rows that carry labels[q].
         numpy [nq, dim] fp32, nq integer labels -> (ids uint64 [nq, k], scores float32 [nq, k])."""
-        queries = np.ascontiguousarray(queries, dtype=np.float32)
-        if queries.ndim == 1:
-            queries = queries[None, :]
-        if queries.ndim != 2 or queries.shape[1] != self.dim:
-            raise ValueError(f"queries must be [nq, {self.dim}]")
+        queries = self._queries(queries)
         nq = queries.shape[0]
         lab = self._labels(labels, nq)
-        ids = np.empty((nq, k), dtype=np.uint64)
-        sc = np.empty((nq, k), dtype=np.float32)
-        check(self._L.vrod_search_labeled(self._h, queries.ctypes.data_as(C.c_void_p), nq, int(k), lab.ctypes.data_as(C.c_void_p),
-                                          ids.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p)))
+        ids, sc = _out(nq, k, np.uint64, np.float32)
+        check(self._L.vrod_search_labeled(self._h, _ptr(queries), nq, int(k), _ptr(lab), _ptr(ids), _ptr(sc)))
         return ids, sc
 
     def search_labeled_device(self, d_queries, k: int, d_labels, out_ids=None, out_scores=None):
         """torch CUDA tensors: queries [nq, dim] fp32, labels [nq] int32 (the bits of uint32) -> (ids int64-viewed-uint64
         [nq, k], scores [nq, k]) on the device, complete on return."""
         import torch
-        assert d_queries.is_cuda and d_queries.dtype == torch.float32 and d_queries.is_contiguous()
+        nq, dev, stream = self._device_queries(d_queries)
         if d_labels.dtype != torch.int32:
             raise TypeError(f"labels must be an int32 tensor, got {d_labels.dtype}")
-        nq = d_queries.shape[0]
         if d_labels.numel() != nq:
             raise ValueError(f"labels must hold {nq} values, got {d_labels.numel()}")
         assert d_labels.is_cuda and d_labels.is_contiguous()
-        if out_ids is None:
-            out_ids = torch.empty((nq, k), dtype=torch.int64, device=d_queries.device)
-        if out_scores is None:
-            out_scores = torch.empty((nq, k), dtype=torch.float32, device=d_queries.device)
-        stream = torch.cuda.current_stream(d_queries.device).cuda_stream
+        out_ids = _device_out(out_ids, (nq, k), torch.int64, dev)
+        out_scores = _device_out(out_scores, (nq, k), torch.float32, dev)
         check(self._L.vrod_search_labeled_device(self._h, d_queries.data_ptr(), nq, int(k), d_labels.data_ptr(), out_ids.data_ptr(),
-                                                 out_scores.data_ptr(), C.c_void_p(stream)))
+                                                 out_scores.data_ptr(), stream))
         return out_ids, out_scores
 
     def search_tagged(self, queries: np.ndarray, k: int, preds):
         """search() with a tag predicate per query (vrod_search_tagged): preds is [nq, 3] uint64, the columns any, all,
         none; query q sees only the eligible rows whose tags t satisfy (any == 0 or t & any) and t & all == all and not
         t & none.  numpy [nq, dim] fp32 -> (ids uint64 [nq, k], scores float32 [nq, k])."""
-        queries = np.ascontiguousarray(queries, dtype=np.float32)
-        if queries.ndim == 1:
-            queries = queries[None, :]
-        if queries.ndim != 2 or queries.shape[1] != self.dim:
-            raise ValueError(f"queries must be [nq, {self.dim}]")
+        queries = self._queries(queries)
         nq = queries.shape[0]
         p = self._u64(preds, "preds", (nq, 3))
-        ids = np.empty((nq, k), dtype=np.uint64)
-        sc = np.empty((nq, k), dtype=np.float32)
-        check(self._L.vrod_search_tagged(self._h, queries.ctypes.data_as(C.c_void_p), nq, int(k), p.ctypes.data_as(C.c_void_p),
-                                         ids.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p)))
+        ids, sc = _out(nq, k, np.uint64, np.float32)
+        check(self._L.vrod_search_tagged(self._h, _ptr(queries), nq, int(k), _ptr(p), _ptr(ids), _ptr(sc)))
         return ids, sc
 
     def search_tagged_device(self, d_queries, k: int, d_preds, out_ids=None, out_scores=None):
         """torch CUDA tensors: queries [nq, dim] fp32, preds [nq, 3] int64 (the bits of uint64: any, all, none) -> (ids
         int64-viewed-uint64 [nq, k], scores [nq, k]) on the device, complete on return."""
         import torch
-        assert d_queries.is_cuda and d_queries.dtype == torch.float32 and d_queries.is_contiguous()
+        nq, dev, stream = self._device_queries(d_queries)
         if d_preds.dtype != torch.int64:
             raise TypeError(f"preds must be an int64 tensor, got {d_preds.dtype}")
-        nq = d_queries.shape[0]
         if tuple(d_preds.shape) != (nq, 3):
             raise ValueError(f"preds must be [{nq}, 3], got {tuple(d_preds.shape)}")
         assert d_preds.is_cuda and d_preds.is_contiguous()
-        if out_ids is None:
-            out_ids = torch.empty((nq, k), dtype=torch.int64, device=d_queries.device)
-        if out_scores is None:
-            out_scores = torch.empty((nq, k), dtype=torch.float32, device=d_queries.device)
-        stream = torch.cuda.current_stream(d_queries.device).cuda_stream
+        out_ids = _device_out(out_ids, (nq, k), torch.int64, dev)
+        out_scores = _device_out(out_scores, (nq, k), torch.float32, dev)
         check(self._L.vrod_search_tagged_device(self._h, d_queries.data_ptr(), nq, int(k), d_preds.data_ptr(), out_ids.data_ptr(),
-                                                out_scores.data_ptr(), C.c_void_p(stream)))
+                                                out_scores.data_ptr(), stream))
         return out_ids, out_scores
 
     def search_grouped(self, queries: np.ndarray, k: int):
         """The best row of each label, the k best labels per query (vrod_search_grouped): numpy [nq, dim] fp32 ->
         (ids uint64 [nq, k], scores float32 [nq, k], labels uint32 [nq, k]); slots beyond the distinct labels of the
         eligible rows are (ID_NONE, NaN, 0)."""
-        queries = np.ascontiguousarray(queries, dtype=np.float32)
-        if queries.ndim == 1:
-            queries = queries[None, :]
-        if queries.ndim != 2 or queries.shape[1] != self.dim:
-            raise ValueError(f"queries must be [nq, {self.dim}]")
+        queries = self._queries(queries)
         nq = queries.shape[0]
-        ids = np.empty((nq, k), dtype=np.uint64)
-        sc = np.empty((nq, k), dtype=np.float32)
-        lab = np.empty((nq, k), dtype=np.uint32)
-        check(self._L.vrod_search_grouped(self._h, queries.ctypes.data_as(C.c_void_p), nq, int(k), ids.ctypes.data_as(C.c_void_p),
-                                          sc.ctypes.data_as(C.c_void_p), lab.ctypes.data_as(C.c_void_p)))
+        ids, sc, lab = _out(nq, k, np.uint64, np.float32, np.uint32)
+        check(self._L.vrod_search_grouped(self._h, _ptr(queries), nq, int(k), _ptr(ids), _ptr(sc), _ptr(lab)))
         return ids, sc, lab
 
     def search_grouped_device(self, d_queries, k: int, out_ids=None, out_scores=None, out_labels=None, want_labels=True):
         """torch CUDA tensor [nq, dim] fp32 -> (ids int64-viewed-uint64 [nq, k], scores [nq, k], labels int32-viewed-uint32
         [nq, k]) on the device, complete on return.  want_labels=False passes no label buffer (labels is None)."""
         import torch
-        assert d_queries.is_cuda and d_queries.dtype == torch.float32 and d_queries.is_contiguous()
-        nq = d_queries.shape[0]
-        if out_ids is None:
-            out_ids = torch.empty((nq, k), dtype=torch.int64, device=d_queries.device)
-        if out_scores is None:
-            out_scores = torch.empty((nq, k), dtype=torch.float32, device=d_queries.device)
-        if out_labels is None and want_labels:
-            out_labels = torch.empty((nq, k), dtype=torch.int32, device=d_queries.device)
-        stream = torch.cuda.current_stream(d_queries.device).cuda_stream
+        nq, dev, stream = self._device_queries(d_queries)
+        out_ids = _device_out(out_ids, (nq, k), torch.int64, dev)
+        out_scores = _device_out(out_scores, (nq, k), torch.float32, dev)
+        if want_labels:
+            out_labels = _device_out(out_labels, (nq, k), torch.int32, dev)
         check(self._L.vrod_search_grouped_device(self._h, d_queries.data_ptr(), nq, int(k), out_ids.data_ptr(), out_scores.data_ptr(),
-                                                 out_labels.data_ptr() if out_labels is not None else None, C.c_void_p(stream)))
+                                                 out_labels.data_ptr() if out_labels is not None else None, stream))
         return out_ids, out_scores, out_labels
 
     # -- multi-vector search: a query is a set of vectors, a document the rows of one label, scored by MaxSim
@@ -392,11 +390,9 @@ class Index:
         -> (labels uint32 [nq, k], scores float32 [nq, k], found uint32 [nq]); slots past found[q] are (0, NaN)."""
         vectors, la = self._multivec_args(vectors, lims)
         nq = la.size - 1
-        lab = np.empty((nq, k), dtype=np.uint32)
-        sc = np.empty((nq, k), dtype=np.float32)
+        lab, sc = _out(nq, k, np.uint32, np.float32)
         found = np.empty(nq, dtype=np.uint32)
-        check(self._L.vrod_search_multivec(self._h, vectors.ctypes.data_as(C.c_void_p), la.ctypes.data_as(C.c_void_p), nq, int(k),
-                                           lab.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p), found.ctypes.data_as(C.c_void_p)))
+        check(self._L.vrod_search_multivec(self._h, _ptr(vectors), _ptr(la), nq, int(k), _ptr(lab), _ptr(sc), _ptr(found)))
         return lab, sc, found
 
     def search_multivec_device(self, d_vectors, d_lims, k: int, out_labels=None, out_scores=None, out_found=None, want_found=True):
@@ -404,25 +400,19 @@ class Index:
         [nq, k], scores [nq, k], found int32 [nq]) on the device, complete on return.  want_found=False passes no found
         buffer (found is None)."""
         import torch
-        assert d_vectors.is_cuda and d_vectors.dtype == torch.float32 and d_vectors.is_contiguous()
-        if d_vectors.dim() != 2 or d_vectors.shape[1] != self.dim:
-            raise ValueError(f"vectors must be [n, {self.dim}]")
+        _, dev, stream = self._device_queries(d_vectors, "vectors")
         if d_lims.dtype != torch.int32:
             raise TypeError(f"lims must be an int32 tensor, got {d_lims.dtype}")
         if d_lims.dim() != 1 or d_lims.numel() < 1:
             raise ValueError("lims must be a vector of nq + 1 entries")
         assert d_lims.is_cuda and d_lims.is_contiguous()
         nq = d_lims.numel() - 1
-        if out_labels is None:
-            out_labels = torch.empty((nq, k), dtype=torch.int32, device=d_vectors.device)
-        if out_scores is None:
-            out_scores = torch.empty((nq, k), dtype=torch.float32, device=d_vectors.device)
-        if out_found is None and want_found:
-            out_found = torch.empty((nq,), dtype=torch.int32, device=d_vectors.device)
-        stream = torch.cuda.current_stream(d_vectors.device).cuda_stream
+        out_labels = _device_out(out_labels, (nq, k), torch.int32, dev)
+        out_scores = _device_out(out_scores, (nq, k), torch.float32, dev)
+        if want_found:
+            out_found = _device_out(out_found, (nq,), torch.int32, dev)
         check(self._L.vrod_search_multivec_device(self._h, d_vectors.data_ptr(), d_lims.data_ptr(), nq, int(k), out_labels.data_ptr(),
-                                                  out_scores.data_ptr(), out_found.data_ptr() if out_found is not None else None,
-                                                  C.c_void_p(stream)))
+                                                  out_scores.data_ptr(), out_found.data_ptr() if out_found is not None else None, stream))
         return out_labels, out_scores, out_found
 
     def last_multivec(self) -> dict:
@@ -436,37 +426,23 @@ class Index:
         """k rows of the `pool` best per query, picked greedily by lam * relevance - (1 - lam) * similarity to the rows
         already picked (vrod_search_diverse): numpy [nq, dim] fp32 -> (ids uint64 [nq, k], scores float32 [nq, k], mmr
         float32 [nq, k]) in selection order; slots past the eligible rows are (ID_NONE, NaN, NaN)."""
-        queries = np.ascontiguousarray(queries, dtype=np.float32)
-        if queries.ndim == 1:
-            queries = queries[None, :]
-        if queries.ndim != 2 or queries.shape[1] != self.dim:
-            raise ValueError(f"queries must be [nq, {self.dim}]")
+        queries = self._queries(queries)
         nq = queries.shape[0]
-        ids = np.empty((nq, k), dtype=np.uint64)
-        sc = np.empty((nq, k), dtype=np.float32)
-        mmr = np.empty((nq, k), dtype=np.float32)
-        check(self._L.vrod_search_diverse(self._h, queries.ctypes.data_as(C.c_void_p), nq, int(k), int(pool), float(lam),
-                                          ids.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p), mmr.ctypes.data_as(C.c_void_p)))
+        ids, sc, mmr = _out(nq, k, np.uint64, np.float32, np.float32)
+        check(self._L.vrod_search_diverse(self._h, _ptr(queries), nq, int(k), int(pool), float(lam), _ptr(ids), _ptr(sc), _ptr(mmr)))
         return ids, sc, mmr
 
     def search_diverse_device(self, d_queries, k: int, pool: int, lam: float, out_ids=None, out_scores=None, out_mmr=None, want_mmr=True):
         """torch CUDA tensor [nq, dim] fp32 -> (ids int64-viewed-uint64 [nq, k], scores [nq, k], mmr [nq, k]) on the device,
         complete on return.  want_mmr=False passes no mmr buffer (mmr is None)."""
         import torch
-        assert d_queries.is_cuda and d_queries.dtype == torch.float32 and d_queries.is_contiguous()
-        if d_queries.dim() != 2 or d_queries.shape[1] != self.dim:
-            raise ValueError(f"queries must be [nq, {self.dim}]")
-        nq = d_queries.shape[0]
-        if out_ids is None:
-            out_ids = torch.empty((nq, k), dtype=torch.int64, device=d_queries.device)
-        if out_scores is None:
-            out_scores = torch.empty((nq, k), dtype=torch.float32, device=d_queries.device)
-        if out_mmr is None and want_mmr:
-            out_mmr = torch.empty((nq, k), dtype=torch.float32, device=d_queries.device)
-        stream = torch.cuda.current_stream(d_queries.device).cuda_stream
+        nq, dev, stream = self._device_queries(d_queries)
+        out_ids = _device_out(out_ids, (nq, k), torch.int64, dev)
+        out_scores = _device_out(out_scores, (nq, k), torch.float32, dev)
+        if want_mmr:
+            out_mmr = _device_out(out_mmr, (nq, k), torch.float32, dev)
         check(self._L.vrod_search_diverse_device(self._h, d_queries.data_ptr(), nq, int(k), int(pool), float(lam), out_ids.data_ptr(),
-                                                 out_scores.data_ptr(), out_mmr.data_ptr() if out_mmr is not None else None,
-                                                 C.c_void_p(stream)))
+                                                 out_scores.data_ptr(), out_mmr.data_ptr() if out_mmr is not None else None, stream))
         return out_ids, out_scores, out_mmr
 
     # -- search by stored row: the queries are rows the handle already holds, used as stored
@@ -486,10 +462,9 @@ class Index:
         (k <= MAX_K - 1).  An id that is no live row raises VrodError (code 1)."""
         a = self._query_ids(ids)
         nq = a.size
-        out_ids = np.empty((nq, k), dtype=np.uint64)
-        sc = np.empty((nq, k), dtype=np.float32)
-        check(self._L.vrod_search_by_ids(self._h, a.ctypes.data_as(C.c_void_p), nq, int(k), BYID_EXCLUDE_SELF if exclude_self else 0,
-                                         out_ids.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p)))
+        out_ids, sc = _out(nq, k, np.uint64, np.float32)
+        check(self._L.vrod_search_by_ids(self._h, _ptr(a), nq, int(k), BYID_EXCLUDE_SELF if exclude_self else 0,
+                                         _ptr(out_ids), _ptr(sc)))
         return out_ids, sc
 
     def search_by_ids_device(self, d_ids, k: int, exclude_self: bool = False, out_ids=None, out_scores=None):
@@ -500,10 +475,8 @@ class Index:
             raise TypeError(f"ids must be an int64 tensor, got {d_ids.dtype}")
         assert d_ids.is_cuda and d_ids.is_contiguous()
         nq = d_ids.numel()
-        if out_ids is None:
-            out_ids = torch.empty((nq, k), dtype=torch.int64, device=d_ids.device)
-        if out_scores is None:
-            out_scores = torch.empty((nq, k), dtype=torch.float32, device=d_ids.device)
+        out_ids = _device_out(out_ids, (nq, k), torch.int64, d_ids.device)
+        out_scores = _device_out(out_scores, (nq, k), torch.float32, d_ids.device)
         stream = torch.cuda.current_stream(d_ids.device).cuda_stream
         check(self._L.vrod_search_by_ids_device(self._h, d_ids.data_ptr(), nq, int(k), BYID_EXCLUDE_SELF if exclude_self else 0,
                                                 out_ids.data_ptr(), out_scores.data_ptr(), C.c_void_p(stream)))
@@ -527,9 +500,8 @@ class Index:
         n = int(n)
         if n < 0:
             raise ValueError("n must not be negative")
-        out_ids = np.empty((n, k), dtype=np.uint64)
-        sc = np.empty((n, k), dtype=np.float32)
-        check(self._L.vrod_knn_graph(self._h, first_id, n, int(k), out_ids.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p)))
+        out_ids, sc = _out(n, k, np.uint64, np.float32)
+        check(self._L.vrod_knn_graph(self._h, first_id, n, int(k), _ptr(out_ids), _ptr(sc)))
         return out_ids, sc
 
     def _first_id(self) -> int:
@@ -538,15 +510,10 @@ class Index:
     def search_device(self, d_queries, k: int, out_ids=None, out_scores=None):
         """torch CUDA tensor [nq, dim] fp32 -> (ids int64-viewed-uint64 [nq,k], scores [nq,k]) on device."""
         import torch
-        assert d_queries.is_cuda and d_queries.dtype == torch.float32 and d_queries.is_contiguous()
-        nq = d_queries.shape[0]
-        if out_ids is None:
-            out_ids = torch.empty((nq, k), dtype=torch.int64, device=d_queries.device)
-        if out_scores is None:
-            out_scores = torch.empty((nq, k), dtype=torch.float32, device=d_queries.device)
-        stream = torch.cuda.current_stream(d_queries.device).cuda_stream
-        check(self._L.vrod_search_device(self._h, d_queries.data_ptr(), nq, int(k), out_ids.data_ptr(),
-                                         out_scores.data_ptr(), C.c_void_p(stream)))
+        nq, dev, stream = self._device_queries(d_queries)
+        out_ids = _device_out(out_ids, (nq, k), torch.int64, dev)
+        out_scores = _device_out(out_scores, (nq, k), torch.float32, dev)
+        check(self._L.vrod_search_device(self._h, d_queries.data_ptr(), nq, int(k), out_ids.data_ptr(), out_scores.data_ptr(), stream))
         return out_ids, out_scores
 
     def search_synthetic_device(self, seed: int, first_row: int, nq: int, k: int, out_ids, out_scores):
@@ -573,19 +540,13 @@ class Index:
         lims[q]:lims[q + 1], best first, every row whose score is >= (cosine, ip) / <= (l2) the threshold.
         capacity=None: a count-only call sizes the buffers; else a result larger than `capacity` raises VrodError with
         code ERR_CAPACITY (and .lims holds the exact counts)."""
-        queries = np.ascontiguousarray(queries, dtype=np.float32)
-        if queries.ndim == 1:
-            queries = queries[None, :]
-        if queries.ndim != 2 or queries.shape[1] != self.dim:
-            raise ValueError(f"queries must be [nq, {self.dim}]")
+        queries = self._queries(queries)
         nq = queries.shape[0]
         thr = self._range_args(nq, threshold)
         lims = np.zeros(nq + 1, dtype=np.uint64)
 
         def call(cap, ids, sc):
-            return self._L.vrod_range_search(self._h, queries.ctypes.data_as(C.c_void_p), nq, thr.ctypes.data_as(C.c_void_p), cap,
-                                             lims.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p) if ids is not None else None,
-                                             sc.ctypes.data_as(C.c_void_p) if sc is not None else None)
+            return self._L.vrod_range_search(self._h, _ptr(queries), nq, _ptr(thr), cap, _ptr(lims), _ptr(ids), _ptr(sc))
         if capacity is None:
             rc = call(0, None, None)
             if rc not in (0, _lib.ERR_CAPACITY):
@@ -609,33 +570,23 @@ class Index:
         """torch CUDA tensors: queries [nq, dim] fp32, thresholds [nq] fp32 -> (rc, lims int64 [nq + 1], ids int64-viewed
         uint64 [capacity], scores [capacity]) on the device.  No retry: rc is 0 or ERR_CAPACITY (lims valid either way)."""
         import torch
-        assert d_queries.is_cuda and d_queries.dtype == torch.float32 and d_queries.is_contiguous()
+        nq, dev, stream = self._device_queries(d_queries)
         assert d_thresholds.is_cuda and d_thresholds.dtype == torch.float32 and d_thresholds.is_contiguous()
-        nq = d_queries.shape[0]
         if d_thresholds.numel() != nq:
             raise ValueError(f"thresholds must hold {nq} values, got {d_thresholds.numel()}")
-        dev = d_queries.device
-        if out_lims is None:
-            out_lims = torch.empty(nq + 1, dtype=torch.int64, device=dev)
-        if out_ids is None:
-            out_ids = torch.empty(max(int(capacity), 1), dtype=torch.int64, device=dev)
-        if out_scores is None:
-            out_scores = torch.empty(max(int(capacity), 1), dtype=torch.float32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        out_lims = _device_out(out_lims, nq + 1, torch.int64, dev)
+        out_ids = _device_out(out_ids, max(int(capacity), 1), torch.int64, dev)
+        out_scores = _device_out(out_scores, max(int(capacity), 1), torch.float32, dev)
         rc = self._L.vrod_range_search_device(self._h, d_queries.data_ptr(), nq, d_thresholds.data_ptr(), int(capacity), out_lims.data_ptr(),
-                                              out_ids.data_ptr() if capacity else None, out_scores.data_ptr() if capacity else None,
-                                              C.c_void_p(stream))
+                                              out_ids.data_ptr() if capacity else None, out_scores.data_ptr() if capacity else None, stream)
         if rc not in (0, _lib.ERR_CAPACITY):
             check(rc)
         return rc, out_lims, out_ids, out_scores
 
     # -- pipelined search: begin(s+1) before end(s) keeps the device busy between batches
     def search_begin_device(self, d_queries, k: int, out_ids, out_scores):
-        import torch
-        assert d_queries.is_cuda and d_queries.dtype == torch.float32 and d_queries.is_contiguous()
-        stream = torch.cuda.current_stream(d_queries.device).cuda_stream
-        check(self._L.vrod_search_begin_device(self._h, d_queries.data_ptr(), d_queries.shape[0], int(k),
-                                               out_ids.data_ptr(), out_scores.data_ptr(), C.c_void_p(stream)))
+        nq, _, stream = self._device_queries(d_queries)
+        check(self._L.vrod_search_begin_device(self._h, d_queries.data_ptr(), nq, int(k), out_ids.data_ptr(), out_scores.data_ptr(), stream))
 
     def search_begin_synthetic_device(self, seed: int, first_row: int, nq: int, k: int, out_ids, out_scores):
         import torch
@@ -660,10 +611,8 @@ def merge_topk_device(device: int, metric, ids, scores, out_ids=None, out_scores
     L = _lib.load()
     n_lists, nq, k = ids.shape
     assert ids.is_contiguous() and scores.is_contiguous()
-    if out_ids is None:
-        out_ids = torch.empty((nq, k), dtype=torch.int64, device=ids.device)
-    if out_scores is None:
-        out_scores = torch.empty((nq, k), dtype=torch.float32, device=ids.device)
+    out_ids = _device_out(out_ids, (nq, k), torch.int64, ids.device)
+    out_scores = _device_out(out_scores, (nq, k), torch.float32, ids.device)
     stream = torch.cuda.current_stream(ids.device).cuda_stream
     check(L.vrod_merge_topk_device(int(device), _enum(metric, _METRICS, "metric"), ids.data_ptr(), scores.data_ptr(),
                                    n_lists, nq, k, out_ids.data_ptr(), out_scores.data_ptr(), C.c_void_p(stream)))
