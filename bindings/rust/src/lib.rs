@@ -65,6 +65,12 @@ pub struct vrod_tag_pred {
 /// The largest `pool` of `vrod_search_diverse`.
 pub const VROD_MAX_DIVERSE_POOL: u32 = 1024;
 
+/// `vrod_search_combined`: the most stored-row terms, and the most excluded ids (terms included under the flag), of one query.
+pub const VROD_MAX_COMBINE_TERMS: u32 = 256;
+pub const VROD_MAX_EXCLUDE: u32 = 1024;
+/// `flags` of `vrod_search_combined`: a query's term ids are excluded from its result.
+pub const VROD_COMBINED_EXCLUDE_TERMS: u32 = 1;
+
 /// The most vectors one query of `vrod_search_multivec` may hold.
 pub const VROD_MAX_QUERY_VECTORS: u32 = 256;
 
@@ -169,6 +175,17 @@ extern "C" {
     pub fn vrod_search_diverse_device(idx: *mut vrod_index, d_queries: *const f32, nq: u32, k: u32, pool: u32, lambda: f32,
                                       d_out_ids: *mut u64, d_out_scores: *mut f32, d_out_mmr: *mut f32,
                                       stream: *mut c_void) -> c_int;
+    /// Query q = its prepared vector (if `vectors` is not null) and the stored rows `term_ids[term_lims[q] .. term_lims[q + 1]]`,
+    /// weighted and added in order; its result leaves out `exclude_ids[exclude_lims[q] .. exclude_lims[q + 1]]` (both may be
+    /// null) and, with `VROD_COMBINED_EXCLUDE_TERMS`, the terms.
+    pub fn vrod_search_combined(idx: *mut vrod_index, vectors: *const f32, vector_weights: *const f32, term_lims: *const u32,
+                                term_ids: *const u64, term_weights: *const f32, exclude_lims: *const u32,
+                                exclude_ids: *const u64, nq: u32, k: u32, flags: u32, out_ids: *mut u64,
+                                out_scores: *mut f32) -> c_int;
+    pub fn vrod_search_combined_device(idx: *mut vrod_index, d_vectors: *const f32, d_vector_weights: *const f32,
+                                       d_term_lims: *const u32, d_term_ids: *const u64, d_term_weights: *const f32,
+                                       d_exclude_lims: *const u32, d_exclude_ids: *const u64, nq: u32, k: u32, flags: u32,
+                                       d_out_ids: *mut u64, d_out_scores: *mut f32, stream: *mut c_void) -> c_int;
 }
 
 /// Joins the reference's `thiserror` enums (`src/main.rs:36-40`, `src/command/builder.rs:10-15`).

@@ -464,6 +464,50 @@ int vrod_search_by_ids_device(vrod_index *idx, const uint64_t *d_ids, uint32_t n
 int vrod_knn_graph(vrod_index *idx, uint64_t first_id, uint64_t n, uint32_t k,
                    uint64_t *out_ids, float *out_scores);
 
+/* Search by weighted examples ("more like these, less like those, never what was seen") -- the query is combined on the
+ * device from an optional vector and stored rows, and the result leaves a per-query set of ids out.  Per query q, with
+ * fl() one rounding to fp32 and no fused multiply-add anywhere:
+ *   operands     If `vectors` is given (nq x dim; may be NULL), row q of it is the first operand: prepared first exactly as
+ *                vrod_search prepares a query (normalised for COSINE, bf16-rounded on BF16 handles), with weight
+ *                vector_weights[q], or 1.0f when that pointer is NULL.  The terms term_ids[term_lims[q] .. term_lims[q + 1])
+ *                follow in the order given (term_lims: nq + 1 entries, term_ids / term_weights: term_lims[nq] entries): each
+ *                is the PREPARED stored row as vrod_index_get_rows returns it -- bf16 widened, nothing normalised or rounded
+ *                again -- with weight term_weights[t].  Term ids are ids as searches report them, id_offset applied.
+ *   combination  For each coordinate j: acc = +0.0f, then for each operand in order acc = fl(acc + fl(w * x[j])).  The order
+ *                is part of the contract.
+ *   search       The combined vector is a raw query to vrod_search: prepared again (normalised for COSINE, bf16-rounded on
+ *                BF16) and searched over the eligible rows (live, and allowed while a filter is set).  Labels and tags are
+ *                ignored; vrod_index_set_path is honoured.
+ *   exclusion    The excluded set of q is exclude_ids[exclude_lims[q] .. exclude_lims[q + 1]) (both NULL: none) and, with
+ *                VROD_COMBINED_EXCLUDE_TERMS, q's term ids.  The result is the top k of the eligible rows outside that set:
+ *                best first, ties by smaller id, slots beyond it (VROD_ID_NONE, NaN).  Exclusion is by id; an excluded id
+ *                that is not a current row, names a deleted row, repeats, or equals VROD_ID_NONE is ignored: seen-lists
+ *                outlive deletes.
+ * The result is bit for bit what the CPU oracle gives for the combined vector over those rows.
+ * Every check comes before the first write: a refused call leaves the outputs untouched.  VROD_ERR_INVALID_ARG: null
+ * required pointers; term_lims[0] != 0 or a decreasing entry, the same for exclude_lims; a query with no operand at all (no
+ * vector and zero terms); more than VROD_MAX_COMBINE_TERMS terms in a query; more than VROD_MAX_EXCLUDE excluded entries in
+ * a query (its terms included under the flag, duplicates counted); unknown flag bits; k == 0; k + the batch's largest
+ * excluded count > VROD_MAX_K (the search runs with that many results); a term id that is not a live row (the host form
+ * checks its mirror of the tombstones; the _device form: the launch that combines checks every id and raises one flag, read
+ * before the search is begun); a pending search.  VROD_ERR_INVALID_VALUE: NaN or Inf in `vectors` or in a weight, or a
+ * combined vector that holds a NaN or Inf (overflow).  Multi-device handles: VROD_ERR_UNSUPPORTED.  nq == 0: VROD_OK.  An
+ * empty handle, or one without an eligible row, gives all-unfilled rows, as vrod_search does.
+ * Synchronous: no _begin_ form, no graph replay; the _device form takes device pointers (the two lims arrays are copied
+ * to the host) and returns after the results are complete in device memory.  vrod_index_last_stats afterwards: what the
+ * underlying search reported, k = the caller's k. */
+#define VROD_MAX_COMBINE_TERMS 256u    /* stored-row operands per query */
+#define VROD_MAX_EXCLUDE 1024u         /* excluded ids per query: the terms under the flag + its exclude list */
+enum { VROD_COMBINED_EXCLUDE_TERMS = 1u };
+int vrod_search_combined(vrod_index *idx, const float *vectors, const float *vector_weights,
+                         const uint32_t *term_lims, const uint64_t *term_ids, const float *term_weights,
+                         const uint32_t *exclude_lims, const uint64_t *exclude_ids,
+                         uint32_t nq, uint32_t k, uint32_t flags, uint64_t *out_ids, float *out_scores);
+int vrod_search_combined_device(vrod_index *idx, const float *d_vectors, const float *d_vector_weights,
+                                const uint32_t *d_term_lims, const uint64_t *d_term_ids, const float *d_term_weights,
+                                const uint32_t *d_exclude_lims, const uint64_t *d_exclude_ids,
+                                uint32_t nq, uint32_t k, uint32_t flags, uint64_t *d_out_ids, float *d_out_scores, void *stream);
+
 /* Merge n_lists per-shard results (device, each nq x k, list-major: [list][q][k]) into
  * one nq x k on `device` -- the step after the RCCL all-gather. */
 int vrod_merge_topk_device(int device, int metric, const uint64_t *d_ids,

@@ -39,12 +39,16 @@
 #include "multivec_plan.h"
 #include "diverse_plan.h"
 #include "byid_plan.h"
+#include "combine_plan.h"
 
 using namespace vrod;
 
 static_assert(kGroupMaxK == VROD_MAX_K, "group_plan.h restates the largest k of the ABI");
 static_assert(kByidMaxK == VROD_MAX_K, "byid_plan.h restates the largest k of the ABI");
 static_assert(kMultivecMaxK == VROD_MAX_K && kMultivecMaxVectors == VROD_MAX_QUERY_VECTORS, "multivec_plan.h restates the ABI's limits");
+static_assert(kCombineMaxK == VROD_MAX_K && kCombineMaxTerms == VROD_MAX_COMBINE_TERMS && kCombineMaxExclude == VROD_MAX_EXCLUDE &&
+                  kCombineExcludeTerms == VROD_COMBINED_EXCLUDE_TERMS,
+              "combine_plan.h restates the ABI's limits");
 static_assert(kDiverseMaxPool == VROD_MAX_DIVERSE_POOL && kDiverseMaxPool <= VROD_MAX_K && kDiverseMaxDim == VROD_MAX_DIM,
               "diverse_plan.h restates the ABI's limits");
 
@@ -261,6 +265,10 @@ struct vrod_index {
     // 0): the search's lists [nq][k or k + 1], the lists without self [nq][k], a graph batch's [live rows | place of
     // every row among them]; and the host form's ids on the device
     DevBuf byid_ids[2], byid_scores[2], byid_out_ids[2], byid_out_scores[2], byid_map[2], byid_user_ids;
+    // search by weighted examples (vrod_search_combined): the search's lists [nq][k1] while a query excludes anything, and
+    // the host form's arguments on the device -- its raw vectors, and one block [term ids | excluded ids | term weights |
+    // vector weights | term lims | exclude lims]
+    DevBuf cmb_ids, cmb_scores, cmb_vec, cmb_args;
 
     // workspaces
     DevBuf raw_stage, nrm_ws, out_ids, out_scores;
@@ -3359,6 +3367,71 @@ static int byid_search(vrod_index* idx, const uint64_t* d_ids, bool checked, uin
     return VROD_OK;
 }
 
+// ------------------------------------------------------------------ search by weighted examples (vrod_search_combined)
+// The query is built on the device (combine_queries_kernel, kernels_combine.hip): the caller's vector, prepared as a search
+// prepares a query, then the named stored rows as stored, each times its weight, added in the caller's order with two
+// roundings per step.  The combined vector is an ordinary raw query: the search flow prepares it again (no prep_ovr).  A
+// batch in which some query excludes ids runs the search with k1 = k + the largest excluded count into the library's own
+// lists, and drop_excluded_kernel writes the caller's k; a batch that excludes nothing searches straight into the
+// caller's rows.  Every pointer is device memory except the two lims arrays, which the host has validated (counts).
+// checked: the host has validated the term ids and the weights as well; else the combine launch does.  Its flag word --
+// the overflow check in either case -- is read before the search is begun: a refused call leaves the outputs as they were.
+constexpr uint32_t kCombineFlag = 17;   // word of idx->flags the combine launch raises
+
+struct CombineArgs {
+    const float* d_vectors;        // raw [nq][dim], or null
+    const float* d_vector_weights; // [nq], or null
+    const uint32_t* d_term_lims;
+    const uint64_t* d_term_ids;
+    const float* d_term_weights;
+    const uint32_t* d_excl_lims;   // null: no exclude list
+    const uint64_t* d_excl_ids;
+};
+
+static int combined_search(vrod_index* idx, const CombineArgs& a, const CombineCounts& counts, uint32_t nq, uint32_t k, uint32_t flags,
+                           uint64_t* d_out_ids, float* d_out_scores) {
+    Pending& P = next_slot(idx);
+    hipStream_t s = P.stream;
+    const uint32_t k1 = combine_search_k(k, counts.max_excluded);
+    const bool staged = counts.max_excluded != 0;   // the search writes the library's lists, the drop launch the caller's rows
+    uint64_t* l_ids = d_out_ids;
+    float* l_scores = d_out_scores;
+    if (staged) {
+        VROD_TRY(idx->cmb_ids.ensure((size_t)nq * k1 * 8));
+        VROD_TRY(idx->cmb_scores.ensure((size_t)nq * k1 * 4));
+        l_ids = idx->cmb_ids.as<uint64_t>();
+        l_scores = idx->cmb_scores.as<float>();
+    }
+    if (a.d_vectors) VROD_TRY(prep_queries_checked(idx, P, a.d_vectors, nq));   // -> P.q_f32 [nq][ld]; NaN / Inf fails here
+    VROD_TRY(P.q_raw.ensure((size_t)nq * idx->dim * 4));
+    launch_combine_queries(idx->corpus, idx->dtype, idx->ld, idx->dim, idx->count, idx->id_offset, idx->n_deleted ? idx->del_dev : nullptr,
+                           a.d_vectors ? P.q_f32.as<float>() : nullptr, a.d_vector_weights, a.d_term_lims, a.d_term_ids, a.d_term_weights, nq,
+                           P.q_raw.as<float>(), &idx->flags[kCombineFlag], s);
+    HIP_TRY(hipGetLastError());
+    uint32_t bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, &idx->flags[kCombineFlag], 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (bad) {
+        HIP_TRY(hipMemsetAsync(&idx->flags[kCombineFlag], 0, 4, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (bad & kCombineBadId)
+            return fail(VROD_ERR_INVALID_ARG, "a term id is not a live row of this handle (ids %llu..%llu, deleted rows excluded)",
+                        (unsigned long long)idx->id_offset, (unsigned long long)(idx->id_offset + idx->count));
+        if (bad & kCombineBadWeight) return fail(VROD_ERR_INVALID_VALUE, "a weight is NaN or Inf");
+        return fail(VROD_ERR_INVALID_VALUE, "a combined vector holds NaN or Inf (overflow)");
+    }
+    VROD_TRY(run_search(idx, P.q_raw.as<float>(), nq, k1, l_ids, l_scores));
+    idx->stats.k = k;
+    if (staged) {   // (the search is complete: any stream may follow it)
+        const bool with_terms = flags & VROD_COMBINED_EXCLUDE_TERMS;
+        launch_drop_excluded(l_ids, l_scores, k1, a.d_excl_lims, a.d_excl_ids, with_terms ? a.d_term_lims : nullptr, a.d_term_ids, nq, k, d_out_ids,
+                             d_out_scores, idx->stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(idx->stream));
+    }
+    return VROD_OK;
+}
+
 // The graph of rows [row0, row0 + n): batches of byid_plan.h, two in flight -- batch s + 1's gather and search are
 // enqueued (search_begin) before batch s is completed (search_end), its lists lose self and its rows are copied out, so
 // the device scans batch s + 1 while the host and the copy engine finish batch s.  The deleted rows of a batch never
@@ -3596,7 +3669,7 @@ int vrod_index_destroy(vrod_index* idx) {
                       &idx->grp_qraw, &idx->byid_user_ids, &idx->doc_rank, &idx->doc_labels, &idx->mv_q, &idx->mv_ids, &idx->mv_scores, &idx->mv_ent,
                       &idx->mv_tab, &idx->mv_cand, &idx->mv_small, &idx->mv_best, &idx->mv_S, &idx->mv_absent, &idx->mv_M, &idx->mv_pairs,
                       &idx->mv_raw, &idx->mv_lims, &idx->mv_out_labels, &idx->mv_out_scores, &idx->mv_found, &idx->dv_ids, &idx->dv_scores,
-                      &idx->dv_qraw, &idx->dv_mmr}) b->release();
+                      &idx->dv_qraw, &idx->dv_mmr, &idx->cmb_ids, &idx->cmb_scores, &idx->cmb_vec, &idx->cmb_args}) b->release();
     for (int c = 0; c < 2; ++c)
         for (DevBuf* b : {&idx->byid_ids[c], &idx->byid_scores[c], &idx->byid_out_ids[c], &idx->byid_out_scores[c], &idx->byid_map[c]}) b->release();
     if (idx->flags) (void)hipFree(idx->flags);
@@ -4153,6 +4226,109 @@ int vrod_search_by_ids_device(vrod_index* idx, const uint64_t* d_ids, uint32_t n
     if (!nq) return VROD_OK;
     VROD_TRY(begin_sync_device(idx, "vrod_search_by_ids_device", stream));
     return byid_search(idx, d_ids, false, nq, k, flags & VROD_BYID_EXCLUDE_SELF, d_out_ids, d_out_scores);
+}
+
+// What the arguments alone decide comes first (checked, and tested, without a handle), then the handle and the pointers.
+static int check_combined_args(vrod_index* idx, const void* term_lims, uint32_t nq, uint32_t k, uint32_t flags, const void* oi, const void* os,
+                               const char* what) {
+    switch (combine_check_args(k, flags)) {
+        case 0: break;
+        case 1: return fail(VROD_ERR_INVALID_ARG, "unknown flag bits 0x%x", flags);
+        default: return fail(VROD_ERR_INVALID_ARG, "k must be in 1..%u", VROD_MAX_K);
+    }
+    if (!idx) return fail(VROD_ERR_INVALID_ARG, "idx is null");
+    if (nq && (!term_lims || !oi || !os)) return fail(VROD_ERR_INVALID_ARG, "null buffer");
+    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "%s on a multi-device handle: stored rows are not gathered across the shards", what);
+    return VROD_OK;
+}
+
+// The two lims arrays (host copies; excl_lims may be null) against combine_plan.h, and the pointers their totals require.
+static int check_combined_batch(const uint32_t* term_lims, const void* term_ids, const void* term_weights, const uint32_t* excl_lims,
+                                const void* excl_ids, bool has_vector, uint32_t nq, uint32_t k, uint32_t flags, CombineCounts* counts) {
+    uint32_t q = 0;
+    switch (combine_check_batch(term_lims, excl_lims, nq, has_vector, k, flags, counts, &q)) {
+        case 0: break;
+        case 3: return fail(VROD_ERR_INVALID_ARG, "term_lims must start at 0 and never decrease");
+        case 4: return fail(VROD_ERR_INVALID_ARG, "exclude_lims must start at 0 and never decrease");
+        case 5: return fail(VROD_ERR_INVALID_ARG, "query %u has no operand: no vector and no term", q);
+        case 6: return fail(VROD_ERR_INVALID_ARG, "query %u has more than %u terms", q, VROD_MAX_COMBINE_TERMS);
+        case 7: return fail(VROD_ERR_INVALID_ARG, "query %u excludes more than %u ids (its terms included under the flag)", q, VROD_MAX_EXCLUDE);
+        default: return fail(VROD_ERR_INVALID_ARG, "k + the largest excluded count must be at most %u", VROD_MAX_K);
+    }
+    if (term_lims[nq] && (!term_ids || !term_weights)) return fail(VROD_ERR_INVALID_ARG, "null buffer");
+    if (excl_lims && excl_lims[nq] && !excl_ids) return fail(VROD_ERR_INVALID_ARG, "null buffer");
+    return VROD_OK;
+}
+
+int vrod_search_combined(vrod_index* idx, const float* vectors, const float* vector_weights, const uint32_t* term_lims, const uint64_t* term_ids,
+                         const float* term_weights, const uint32_t* exclude_lims, const uint64_t* exclude_ids, uint32_t nq, uint32_t k,
+                         uint32_t flags, uint64_t* out_ids, float* out_scores) {
+    VROD_TRY(check_combined_args(idx, term_lims, nq, k, flags, out_ids, out_scores, "vrod_search_combined"));
+    if (!nq) return VROD_OK;
+    VROD_TRY(require_idle(idx, "vrod_search_combined"));
+    CombineCounts counts;
+    VROD_TRY(check_combined_batch(term_lims, term_ids, term_weights, exclude_lims, exclude_ids, vectors != nullptr, nq, k, flags, &counts));
+    const uint32_t T = term_lims[nq], X = exclude_lims ? exclude_lims[nq] : 0u;
+    for (uint32_t t = 0; t < T; ++t) {   // the host mirror of the tombstones is the truth: nothing is launched for a bad id
+        const uint64_t id = term_ids[t];
+        if (id < idx->id_offset || id - idx->id_offset >= idx->count || bit_of(idx->del_bits.data(), id - idx->id_offset))
+            return fail(VROD_ERR_INVALID_ARG, "term id %llu is not a live row of this handle (ids %llu..%llu, deleted rows excluded)",
+                        (unsigned long long)id, (unsigned long long)idx->id_offset, (unsigned long long)(idx->id_offset + idx->count));
+        if (!std::isfinite(term_weights[t])) return fail(VROD_ERR_INVALID_VALUE, "term weight %u is NaN or Inf", t);
+    }
+    if (vectors && vector_weights)
+        for (uint32_t q = 0; q < nq; ++q)
+            if (!std::isfinite(vector_weights[q])) return fail(VROD_ERR_INVALID_VALUE, "vector weight %u is NaN or Inf", q);
+    VROD_TRY(set_device(idx));
+    // the arguments on the device: [term ids | excluded ids | term weights | vector weights | term lims | exclude lims]
+    const bool vw = vectors && vector_weights;
+    const size_t o_tid = 0, o_xid = o_tid + (size_t)T * 8, o_tw = o_xid + (size_t)X * 8, o_vw = o_tw + (size_t)T * 4,
+                 o_tl = o_vw + (vw ? (size_t)nq * 4 : 0), o_xl = o_tl + ((size_t)nq + 1) * 4, bytes = o_xl + (exclude_lims ? ((size_t)nq + 1) * 4 : 0);
+    VROD_TRY(idx->cmb_args.ensure(bytes));
+    char* base = idx->cmb_args.as<char>();
+    if (T) {
+        HIP_TRY(hipMemcpy(base + o_tid, term_ids, (size_t)T * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(base + o_tw, term_weights, (size_t)T * 4, hipMemcpyHostToDevice));
+    }
+    if (X) HIP_TRY(hipMemcpy(base + o_xid, exclude_ids, (size_t)X * 8, hipMemcpyHostToDevice));
+    if (vw) HIP_TRY(hipMemcpy(base + o_vw, vector_weights, (size_t)nq * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(base + o_tl, term_lims, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice));
+    if (exclude_lims) HIP_TRY(hipMemcpy(base + o_xl, exclude_lims, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice));
+    if (vectors) {
+        VROD_TRY(idx->cmb_vec.ensure((size_t)nq * idx->dim * 4));
+        HIP_TRY(hipMemcpy(idx->cmb_vec.p, vectors, (size_t)nq * idx->dim * 4, hipMemcpyHostToDevice));
+    }
+    CombineArgs a{};
+    a.d_vectors = vectors ? idx->cmb_vec.as<float>() : nullptr;
+    a.d_vector_weights = vw ? (const float*)(base + o_vw) : nullptr;
+    a.d_term_lims = (const uint32_t*)(base + o_tl);
+    a.d_term_ids = (const uint64_t*)(base + o_tid);
+    a.d_term_weights = (const float*)(base + o_tw);
+    a.d_excl_lims = exclude_lims ? (const uint32_t*)(base + o_xl) : nullptr;
+    a.d_excl_ids = (const uint64_t*)(base + o_xid);
+    VROD_TRY(grow_topk_out(idx, nq, k));
+    VROD_TRY(combined_search(idx, a, counts, nq, k, flags, idx->out_ids.as<uint64_t>(), idx->out_scores.as<float>()));
+    return copy_topk_out(idx, nq, k, out_ids, out_scores);
+}
+
+int vrod_search_combined_device(vrod_index* idx, const float* d_vectors, const float* d_vector_weights, const uint32_t* d_term_lims,
+                                const uint64_t* d_term_ids, const float* d_term_weights, const uint32_t* d_exclude_lims,
+                                const uint64_t* d_exclude_ids, uint32_t nq, uint32_t k, uint32_t flags, uint64_t* d_out_ids, float* d_out_scores,
+                                void* stream) {
+    VROD_TRY(check_combined_args(idx, d_term_lims, nq, k, flags, d_out_ids, d_out_scores, "vrod_search_combined_device"));
+    if (!nq) return VROD_OK;
+    VROD_TRY(begin_sync_device(idx, "vrod_search_combined_device", stream));
+    std::vector<uint32_t> tl((size_t)nq + 1), xl;
+    HIP_TRY(hipMemcpy(tl.data(), d_term_lims, tl.size() * 4, hipMemcpyDeviceToHost));
+    if (d_exclude_lims) {
+        xl.resize((size_t)nq + 1);
+        HIP_TRY(hipMemcpy(xl.data(), d_exclude_lims, xl.size() * 4, hipMemcpyDeviceToHost));
+    }
+    CombineCounts counts;
+    VROD_TRY(check_combined_batch(tl.data(), d_term_ids, d_term_weights, d_exclude_lims ? xl.data() : nullptr, d_exclude_ids, d_vectors != nullptr,
+                                  nq, k, flags, &counts));
+    CombineArgs a{d_vectors, d_vectors ? d_vector_weights : nullptr, d_term_lims, d_term_ids, d_term_weights, d_exclude_lims, d_exclude_ids};
+    return combined_search(idx, a, counts, nq, k, flags, d_out_ids, d_out_scores);
 }
 
 int vrod_knn_graph(vrod_index* idx, uint64_t first_id, uint64_t n, uint32_t k, uint64_t* out_ids, float* out_scores) {

@@ -8,6 +8,7 @@
 #include "label_plan.h"    // SegEntry
 #include "tag_plan.h"      // TagPred
 #include "multivec_plan.h" // MultivecQuery
+#include "combine_plan.h"  // kCombineMaxExclude, combine_lanes_per_query
 
 namespace vrod {
 
@@ -304,6 +305,23 @@ void launch_byid_gather(const void* d_corpus, int dtype, uint32_t ld, uint32_t d
 // k, without the entry whose id is d_self[i] (base_id + i when d_self is null), cut to k.
 void launch_byid_drop_self(const uint64_t* d_list_ids, const float* d_list_scores, uint32_t k1, const uint32_t* d_src, const uint64_t* d_self,
                            uint64_t base_id, uint32_t n_out, uint32_t k, uint64_t* d_out_ids, float* d_out_scores, hipStream_t s);
+
+// ---- kernels_combine.hip : queries combined from stored rows, results minus an id set (vrod_search_combined)
+// d_out [nq][dim] fp32: per coordinate +0, then acc = fl(acc + fl(w * x)) over query q's operands in order -- row q of d_vec
+// ([nq][ld] prepared fp32; null: no vector operand) with weight d_vec_w[q] (null: 1), then the prepared stored rows
+// d_term_ids[d_term_lims[q] .. d_term_lims[q + 1]) - id_offset as stored (bf16 widened) with weights d_term_w.  *d_flag
+// gets kCombineBadId for a term id that is no current row or is set in d_del (may be null), kCombineBadWeight for a NaN /
+// Inf weight, kCombineNonFinite for a NaN / Inf result.
+constexpr uint32_t kCombineBadId = 1u, kCombineBadWeight = 2u, kCombineNonFinite = 4u;
+void launch_combine_queries(const void* d_corpus, int dtype, uint32_t ld, uint32_t dim, uint64_t count, uint64_t id_offset, const uint32_t* d_del,
+                            const float* d_vec, const float* d_vec_w, const uint32_t* d_term_lims, const uint64_t* d_term_ids,
+                            const float* d_term_w, uint32_t nq, float* d_out, uint32_t* d_flag, hipStream_t s);
+// Output row q [k] = row q of d_list_* [nq][k1] without the entries whose id is among d_excl_ids[d_excl_lims[q] ..
+// d_excl_lims[q + 1]) (d_excl_lims null: none) or d_term_ids[d_term_lims[q] .. d_term_lims[q + 1]) (d_term_lims null:
+// none), in order, cut to k and padded unfilled.  At most kCombineMaxExclude ids per query in all.
+void launch_drop_excluded(const uint64_t* d_list_ids, const float* d_list_scores, uint32_t k1, const uint32_t* d_excl_lims,
+                          const uint64_t* d_excl_ids, const uint32_t* d_term_lims, const uint64_t* d_term_ids, uint32_t nq, uint32_t k,
+                          uint64_t* d_out_ids, float* d_out_scores, hipStream_t s);
 
 // ---- kernels_mfma.hip : batched Q.K^T scan with fused threshold filter
 // Timing of the dominant scan launches without marker packets: the launcher of the next scan

@@ -21,6 +21,9 @@ MAX_K = 3584
 BYID_EXCLUDE_SELF = 1   # VROD_BYID_EXCLUDE_SELF
 MAX_QUERY_VECTORS = 256   # VROD_MAX_QUERY_VECTORS
 MAX_DIVERSE_POOL = 1024   # VROD_MAX_DIVERSE_POOL
+MAX_COMBINE_TERMS = 256   # VROD_MAX_COMBINE_TERMS
+MAX_EXCLUDE = 1024        # VROD_MAX_EXCLUDE
+COMBINED_EXCLUDE_TERMS = 1   # VROD_COMBINED_EXCLUDE_TERMS
 # rows per batch of knn_graph() by storage type (byid_plan.h: kByidBatchF32, kByidBatchBf16)
 KNN_BATCH = {0: 256, 1: 1024}
 
@@ -503,6 +506,94 @@ class Index:
         out_ids, sc = _out(n, k, np.uint64, np.float32)
         check(self._L.vrod_knn_graph(self._h, first_id, n, int(k), _ptr(out_ids), _ptr(sc)))
         return out_ids, sc
+
+    # -- search by weighted examples: the query is combined on the device from a vector and stored rows
+    @classmethod
+    def _ragged_ids(cls, ids, lims, what):
+        """A list of per-query id sequences, or -- with lims [nq + 1] -- all ids flat -> (uint64 ids, uint32 lims)."""
+        if lims is None:
+            parts = [cls._query_ids(p) for p in ids]
+            lims = np.cumsum([0] + [p.size for p in parts])
+            flat = np.concatenate(parts) if parts else np.zeros(0, np.uint64)
+        else:
+            flat = cls._query_ids(ids)
+        la = np.asarray(lims)
+        if la.ndim != 1 or la.size < 1 or la.dtype.kind not in "iu":
+            raise ValueError(f"{what} lims must be a vector of nq + 1 integers")
+        if int(la.min()) < 0 or int(la.max()) > 0xFFFFFFFF:
+            raise ValueError(f"{what} lims must fit uint32")
+        la = np.ascontiguousarray(la, dtype=np.uint32)
+        if int(la[-1]) != flat.size:
+            raise ValueError(f"{what} lims[-1] = {int(la[-1])} must equal the number of ids, {flat.size}")
+        return np.ascontiguousarray(flat, dtype=np.uint64), la
+
+    def search_combined(self, k: int, term_ids, term_weights, term_lims=None, vectors=None, vector_weights=None, exclude_ids=None,
+                        exclude_lims=None, exclude_terms: bool = False):
+        """Search by weighted examples (vrod_search_combined).  Query q is fl-summed in order from row q of `vectors` ([nq, dim]
+        fp32 or None; prepared as a query, weight vector_weights[q] or 1) and the stored rows term_ids of q as stored, each
+        times its weight; the result leaves out q's exclude_ids and, with exclude_terms, its terms.  term_ids / term_weights
+        (and exclude_ids): a list of per-query sequences, or flat arrays with term_lims (exclude_lims) [nq + 1].
+        -> (ids uint64 [nq, k], scores float32 [nq, k])."""
+        tid, tl = self._ragged_ids(term_ids, term_lims, "term")
+        nq = tl.size - 1
+        if term_lims is None:
+            tw = np.concatenate([np.asarray(w, dtype=np.float32).reshape(-1) for w in term_weights]) if nq else np.zeros(0, np.float32)
+        else:
+            tw = np.asarray(term_weights, dtype=np.float32).reshape(-1)
+        tw = np.ascontiguousarray(tw, dtype=np.float32)
+        if tw.size != tid.size:
+            raise ValueError(f"term_weights must hold {tid.size} values, got {tw.size}")
+        vec = vw = None
+        if vectors is not None:
+            vec = self._queries(vectors)
+            if vec.shape[0] != nq:
+                raise ValueError(f"vectors must be [{nq}, {self.dim}]")
+            if vector_weights is not None:
+                vw = np.ascontiguousarray(np.asarray(vector_weights, dtype=np.float32).reshape(-1))
+                if vw.size != nq:
+                    raise ValueError(f"vector_weights must hold {nq} values, got {vw.size}")
+        xid = xl = None
+        if exclude_ids is not None:
+            xid, xl = self._ragged_ids(exclude_ids, exclude_lims, "exclude")
+            if xl.size != nq + 1:
+                raise ValueError(f"exclude lists for {xl.size - 1} queries, terms for {nq}")
+        out_ids, sc = _out(nq, k, np.uint64, np.float32)
+        check(self._L.vrod_search_combined(self._h, _ptr(vec), _ptr(vw), _ptr(tl), _ptr(tid), _ptr(tw), _ptr(xl), _ptr(xid), nq, int(k),
+                                           COMBINED_EXCLUDE_TERMS if exclude_terms else 0, _ptr(out_ids), _ptr(sc)))
+        return out_ids, sc
+
+    def search_combined_device(self, k: int, d_term_lims, d_term_ids, d_term_weights, d_vectors=None, d_vector_weights=None,
+                               d_exclude_lims=None, d_exclude_ids=None, exclude_terms: bool = False, out_ids=None, out_scores=None):
+        """torch CUDA tensors: term_lims [nq + 1] int32 (the bits of uint32), term_ids int64 (the bits of uint64), term_weights
+        fp32; optional vectors [nq, dim] fp32, vector_weights [nq] fp32, exclude_lims [nq + 1] int32, exclude_ids int64 ->
+        (ids int64-viewed-uint64 [nq, k], scores [nq, k]) on the device, complete on return."""
+        import torch
+
+        def ptr(t, dtype, what):
+            if t is None:
+                return None
+            if t.dtype != dtype:
+                raise TypeError(f"{what} must be a {dtype} tensor, got {t.dtype}")
+            assert t.is_cuda and t.is_contiguous()
+            return t.data_ptr()
+        if d_term_lims.dim() != 1 or d_term_lims.numel() < 1:
+            raise ValueError("term_lims must be a vector of nq + 1 entries")
+        nq = d_term_lims.numel() - 1
+        dev = d_term_lims.device
+        if d_vectors is not None and self._device_queries(d_vectors, "vectors")[0] != nq:
+            raise ValueError(f"vectors must be [{nq}, {self.dim}]")
+        if d_exclude_lims is not None and d_exclude_lims.numel() != nq + 1:
+            raise ValueError(f"exclude_lims must hold {nq + 1} entries")
+        out_ids = _device_out(out_ids, (nq, k), torch.int64, dev)
+        out_scores = _device_out(out_scores, (nq, k), torch.float32, dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        check(self._L.vrod_search_combined_device(
+            self._h, ptr(d_vectors, torch.float32, "vectors"), ptr(d_vector_weights, torch.float32, "vector_weights"),
+            ptr(d_term_lims, torch.int32, "term_lims"), ptr(d_term_ids, torch.int64, "term_ids"),
+            ptr(d_term_weights, torch.float32, "term_weights"), ptr(d_exclude_lims, torch.int32, "exclude_lims"),
+            ptr(d_exclude_ids, torch.int64, "exclude_ids"), nq, int(k), COMBINED_EXCLUDE_TERMS if exclude_terms else 0,
+            out_ids.data_ptr(), out_scores.data_ptr(), C.c_void_p(stream)))
+        return out_ids, out_scores
 
     def _first_id(self) -> int:
         return getattr(self, "_id_offset", 0)
