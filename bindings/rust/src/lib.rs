@@ -71,6 +71,9 @@ pub const VROD_MAX_EXCLUDE: u32 = 1024;
 /// `flags` of `vrod_search_combined`: a query's term ids are excluded from its result.
 pub const VROD_COMBINED_EXCLUDE_TERMS: u32 = 1;
 
+/// The most list entries one query of `vrod_search_candidates` / `vrod_score_candidates` may hold.
+pub const VROD_MAX_CANDIDATES: u32 = 16384;
+
 /// The most vectors one query of `vrod_search_multivec` may hold.
 pub const VROD_MAX_QUERY_VECTORS: u32 = 256;
 
@@ -186,6 +189,18 @@ extern "C" {
                                        d_term_lims: *const u32, d_term_ids: *const u64, d_term_weights: *const f32,
                                        d_exclude_lims: *const u32, d_exclude_ids: *const u64, nq: u32, k: u32, flags: u32,
                                        d_out_ids: *mut u64, d_out_scores: *mut f32, stream: *mut c_void) -> c_int;
+    /// Query q sees only the rows `cand_ids[cand_lims[q] .. cand_lims[q + 1]]` name (any order; repeats, deleted, disallowed
+    /// and stale ids are ignored): its exact top k among them.
+    pub fn vrod_search_candidates(idx: *mut vrod_index, queries: *const f32, nq: u32, k: u32, cand_lims: *const u32,
+                                  cand_ids: *const u64, out_ids: *mut u64, out_scores: *mut f32) -> c_int;
+    pub fn vrod_search_candidates_device(idx: *mut vrod_index, d_queries: *const f32, nq: u32, k: u32,
+                                         d_cand_lims: *const u32, d_cand_ids: *const u64, d_out_ids: *mut u64,
+                                         d_out_scores: *mut f32, stream: *mut c_void) -> c_int;
+    /// `out_scores[t]` = the canonical score of query q against row `cand_ids[t]`, NaN where the id is ignored.
+    pub fn vrod_score_candidates(idx: *mut vrod_index, queries: *const f32, nq: u32, cand_lims: *const u32,
+                                 cand_ids: *const u64, out_scores: *mut f32) -> c_int;
+    pub fn vrod_score_candidates_device(idx: *mut vrod_index, d_queries: *const f32, nq: u32, d_cand_lims: *const u32,
+                                        d_cand_ids: *const u64, d_out_scores: *mut f32, stream: *mut c_void) -> c_int;
 }
 
 /// Joins the reference's `thiserror` enums (`src/main.rs:36-40`, `src/command/builder.rs:10-15`).

@@ -508,6 +508,49 @@ int vrod_search_combined_device(vrod_index *idx, const float *d_vectors, const f
                                 const uint32_t *d_exclude_lims, const uint64_t *d_exclude_ids,
                                 uint32_t nq, uint32_t k, uint32_t flags, uint64_t *d_out_ids, float *d_out_scores, void *stream);
 
+/* Candidate-list searches -- the second stage of hybrid retrieval: the caller already holds a list of ids per query (from a
+ * keyword index, an SQL pre-filter, an access-control lookup) and wants only those rows scored.
+ *   lists           Query q owns cand_ids[cand_lims[q] .. cand_lims[q + 1]) (cand_lims: nq + 1 entries, cand_ids:
+ *                   cand_lims[nq] entries, in any order).  Ids are ids as searches report them, id_offset applied.
+ *   candidate set   The DISTINCT ids of q's list that are current rows, live, and allowed by the handle's filter while one
+ *                   is set.  An id below the offset, past the count, equal to VROD_ID_NONE, deleted or disallowed is
+ *                   ignored, not an error, and a repeated id counts once: lists kept outside the database outlive deletes
+ *                   (the rule of vrod_search_combined's exclude lists).  Labels and tags are ignored.
+ * vrod_search_candidates: result row q (out_ids / out_scores: nq x k) is bit for bit -- ids and score bits, a NaN matching
+ * any NaN -- what vrod_search returns for that query on a fresh handle that holds only the candidate rows, in ascending id
+ * order, with the ids mapped back: best first, ties by smaller id, NaN last, whatever the order of the caller's list.  Slots
+ * beyond the candidate set are (VROD_ID_NONE, NaN); an empty list, or one with nothing eligible in it, gives an
+ * all-unfilled row.  k ranges over 1 .. VROD_MAX_K.
+ * vrod_score_candidates: out_scores has cand_lims[nq] entries aligned with cand_ids; entry t of query q is the canonical
+ * score of q against row cand_ids[t] -- the bits vrod_search would report for that row -- and NaN where the id is ignored
+ * under the rule above.  A repeated id gets its score at every position.  Under IP a score whose terms overflow to +inf and
+ * -inf is NaN as well: the two cases cannot be told apart here.
+ * Queries are prepared exactly as vrod_search prepares them; NaN / Inf in them: VROD_ERR_INVALID_VALUE.
+ * VROD_ERR_INVALID_ARG: null required pointers; cand_lims[0] != 0 or a decreasing entry; a list of more than
+ * VROD_MAX_CANDIDATES entries (repeats and ignored ids counted); k == 0 or k > VROD_MAX_K; a pending search.  Every check
+ * comes before the first write: a refused call leaves the outputs untouched.  Multi-device handles: VROD_ERR_UNSUPPORTED,
+ * the outputs are not touched.  nq == 0: VROD_OK.  An empty handle, or one without an eligible row, gives all-unfilled rows
+ * (the search form) or all NaN (the score form) without looking at the queries.
+ * Synchronous: no _begin_ form, no graph replay; the _device forms take device pointers (cand_lims included: it is copied
+ * to the host to be checked, the ids never are) and return after the results are complete in device memory.
+ * vrod_index_set_path is ignored: the candidates are always scored on their own rows by the canonical chain, there is no
+ * fast pass and no certificate.  vrod_index_last_stats afterwards: path = VROD_PATH_GATHER, nq, k (0 for the score form),
+ * kprime = the largest candidate set of the batch (the score form: the most entries scored for one query, repeats
+ * counted), scan_launches = the score launches, fallback_queries = band_queries = 0, max_fast_err = eps_bound = 0,
+ * scan_bytes = the rows scored x the stored row bytes and scan_flops = 2 x the rows scored x dim, summed over the queries
+ * (the search form scores a candidate set once, the score form every eligible entry, repeats included). */
+#define VROD_MAX_CANDIDATES 16384u   /* list entries per query, repeats and stale ids counted */
+int vrod_search_candidates(vrod_index *idx, const float *queries, uint32_t nq, uint32_t k,
+                           const uint32_t *cand_lims, const uint64_t *cand_ids,
+                           uint64_t *out_ids, float *out_scores);
+int vrod_search_candidates_device(vrod_index *idx, const float *d_queries, uint32_t nq, uint32_t k,
+                                  const uint32_t *d_cand_lims, const uint64_t *d_cand_ids,
+                                  uint64_t *d_out_ids, float *d_out_scores, void *stream);
+int vrod_score_candidates(vrod_index *idx, const float *queries, uint32_t nq,
+                          const uint32_t *cand_lims, const uint64_t *cand_ids, float *out_scores);
+int vrod_score_candidates_device(vrod_index *idx, const float *d_queries, uint32_t nq,
+                                 const uint32_t *d_cand_lims, const uint64_t *d_cand_ids, float *d_out_scores, void *stream);
+
 /* Merge n_lists per-shard results (device, each nq x k, list-major: [list][q][k]) into
  * one nq x k on `device` -- the step after the RCCL all-gather. */
 int vrod_merge_topk_device(int device, int metric, const uint64_t *d_ids,

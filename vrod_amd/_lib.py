@@ -29,6 +29,7 @@ SYMBOLS = [
     "vrod_search_multivec", "vrod_search_multivec_device", "vrod_index_last_multivec",
     "vrod_search_diverse", "vrod_search_diverse_device",
     "vrod_search_combined", "vrod_search_combined_device",
+    "vrod_search_candidates", "vrod_search_candidates_device", "vrod_score_candidates", "vrod_score_candidates_device",
 ]
 
 ERR_CAPACITY = 8   # VROD_ERR_CAPACITY: a range search's result does not fit the caller's buffers (out_lims is valid)
@@ -135,6 +136,10 @@ def load() -> C.CDLL:
     L.vrod_search_diverse_device.argtypes = [vp, vp, u32, u32, u32, C.c_float, vp, vp, vp, vp]
     L.vrod_search_combined.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp]
     L.vrod_search_combined_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp]
+    L.vrod_search_candidates.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
+    L.vrod_search_candidates_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp, vp]
+    L.vrod_score_candidates.argtypes = [vp, vp, u32, vp, vp, vp]
+    L.vrod_score_candidates_device.argtypes = [vp, vp, u32, vp, vp, vp, vp]
     for name in SYMBOLS:
         getattr(L, name).restype = i32
     L.vrod_last_error.restype = C.c_char_p

@@ -269,6 +269,11 @@ struct vrod_index {
     // the host form's arguments on the device -- its raw vectors, and one block [term ids | excluded ids | term weights |
     // vector weights | term lims | exclude lims]
     DevBuf cmb_ids, cmb_scores, cmb_vec, cmb_args;
+    // candidate-list searches (vrod_search_candidates, vrod_score_candidates): the lists' entries as local rows, the
+    // per-query words [lengths | the queries by sort class, or the score launch's tile offsets], and the host forms'
+    // arguments on the device -- [ids | lims] and the raw queries.  The resolved segments go to lab_lists, the slot
+    // tables to lab_slots: the segmented driver finds them where a labelled search leaves its own.
+    DevBuf cand_rows, cand_small, cand_args, cand_qraw;
 
     // workspaces
     DevBuf raw_stage, nrm_ws, out_ids, out_scores;
@@ -3432,6 +3437,122 @@ static int combined_search(vrod_index* idx, const CombineArgs& a, const CombineC
     return VROD_OK;
 }
 
+// ------------------------------------------------------------------ candidate-list searches (vrod_search_candidates, vrod_score_candidates)
+// Query q sees the rows its own list of ids names: the distinct ids that are current rows, live and allowed.  The lists
+// are resolved on the device (kernels_candidates.hip) -- ids to local rows against row_mask(), the mask every search
+// reads -- so neither form copies an id to the host.
+//   the search form sorts every resolved list ascending and drops repeats (one work-group per query, launches by sort
+//     class: candidates_plan.h), reads the nq lengths back and hands the segmented driver one group of one slot per
+//     query: the canonical scores of its own rows, the select chain with a length per slot, exact by construction as a
+//     labelled search's segmented route is.  There is no fast pass, no certificate and no route to choose;
+//   the score form walks the canonical chain of every entry of the resolved, unsorted lists in ONE launch, one (query,
+//     entry) pair per lane, and writes each score at its entry's position.
+// Synchronous: the handle is idle before and after.  Every pointer is device memory except h_lims, which the host has
+// validated (cand_check_lims); d_lims is its device copy.
+static_assert(kCandMaxList == VROD_MAX_CANDIDATES, "candidates_plan.h restates VROD_MAX_CANDIDATES");
+
+static int candidates_resolve(vrod_index* idx, hipStream_t s, const uint64_t* d_ids, uint32_t n) {
+    VROD_TRY(idx->cand_rows.ensure((size_t)n * 4));
+    launch_cand_resolve(d_ids, n, idx->count, idx->id_offset, idx->row_mask(), idx->cand_rows.as<uint32_t>(), s);
+    HIP_TRY(hipGetLastError());
+    return VROD_OK;
+}
+
+static int candidates_search(vrod_index* idx, const float* d_queries_raw, uint32_t nq, uint32_t k, const uint32_t* h_lims, const uint32_t* d_lims,
+                             const uint64_t* d_ids, uint64_t* d_out_ids, float* d_out_scores) {
+    vrod_search_stats st{};
+    st.nq = nq; st.k = k; st.path = VROD_PATH_GATHER;
+    Pending& P = next_slot(idx);
+    hipStream_t s = P.stream;
+    const uint64_t nk = (uint64_t)nq * k;
+    if (idx->count == 0 || idx->eligible() == 0) return return_unfilled(idx, s, st, d_out_ids, d_out_scores, nk);   // no row can answer
+    VROD_TRY(prep_queries_checked(idx, P, d_queries_raw, nq));
+    const uint32_t n_entries = h_lims[nq];
+    if (!n_entries) return return_unfilled(idx, s, st, d_out_ids, d_out_scores, nk);   // every list is empty
+
+    // ---- ids -> rows, then per query the ascending distinct rows into its segment of lab_lists, and their number
+    VROD_TRY(candidates_resolve(idx, s, d_ids, n_entries));
+    VROD_TRY(idx->lab_lists.ensure((size_t)n_entries * 4));
+    VROD_TRY(idx->cand_small.ensure((size_t)nq * 4 * 2));
+    uint32_t* d_len = idx->cand_small.as<uint32_t>();
+    uint32_t* d_order = d_len + nq;
+    const CandSortPlan sp = cand_sort_plan(h_lims, nq);
+    HIP_TRY(hipMemcpyAsync(d_order, sp.order.data(), (size_t)nq * 4, hipMemcpyHostToDevice, s));
+    for (uint32_t c = 0; c < kCandClasses; ++c)
+        launch_cand_sort_unique(idx->cand_rows.as<uint32_t>(), d_lims, d_order + sp.first[c], sp.first[c + 1] - sp.first[c], c,
+                                idx->lab_lists.as<uint32_t>(), d_len, s);
+    HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> len(nq);
+    HIP_TRY(hipMemcpyAsync(len.data(), d_len, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+
+    // ---- one slot and one segment per query that has a row; the others' result rows are unfilled
+    const CandSlots S = cand_slot_tables(h_lims, len.data(), nq);
+    st.kprime = S.max_len;
+    st.scan_bytes = (double)S.rows * idx->ld * idx->esize;
+    st.scan_flops = 2.0 * (double)S.rows * idx->dim;
+    if (S.n_empty) {   // (the other queries overwrite their own rows below)
+        launch_fill_none(d_out_ids, d_out_scores, nk, s);
+        HIP_TRY(hipGetLastError());
+    }
+    if (S.T.size()) {
+        VROD_TRY(idx->lab_slots.ensure((size_t)S.T.size() * 4 * 3));
+        const DevSlots d_slots = dev_slots(idx->lab_slots.as<uint32_t>(), S.T.size());
+        Timer tm(idx, P);
+        P.reset_events();
+        VROD_TRY(score_segments(idx, P, tm, st, S.T, d_slots, k, d_out_ids, d_out_scores));
+        tm.add_scan_ms(st);
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    idx->stats = st;
+    return VROD_OK;
+}
+
+static int candidates_score(vrod_index* idx, const float* d_queries_raw, uint32_t nq, const uint32_t* h_lims, const uint32_t* d_lims,
+                            const uint64_t* d_ids, float* d_out_scores) {
+    vrod_search_stats st{};
+    st.nq = nq; st.k = 0; st.path = VROD_PATH_GATHER;
+    Pending& P = next_slot(idx);
+    hipStream_t s = P.stream;
+    const uint32_t n_entries = h_lims[nq];
+    if (idx->count == 0 || idx->eligible() == 0) {   // no row can be scored: every entry is ignored
+        if (n_entries) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)d_out_scores, (int)kScoreNoneBits, n_entries, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        idx->stats = st;
+        return VROD_OK;
+    }
+    VROD_TRY(prep_queries_checked(idx, P, d_queries_raw, nq));
+    if (n_entries) {
+        VROD_TRY(candidates_resolve(idx, s, d_ids, n_entries));
+        // [entries scored per query | the tile offsets of the launch]
+        const std::vector<uint32_t> off = cand_tile_offsets(h_lims, nq);
+        VROD_TRY(idx->cand_small.ensure(((size_t)nq * 2 + 1) * 4));
+        uint32_t* d_cnt = idx->cand_small.as<uint32_t>();
+        uint32_t* d_off = d_cnt + nq;
+        HIP_TRY(hipMemsetAsync(d_cnt, 0, (size_t)nq * 4, s));
+        HIP_TRY(hipMemcpyAsync(d_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, s));
+        Timer tm(idx, P);
+        P.reset_events();
+        size_t a = 0, b = 0;
+        VROD_TRY(tm.begin_launch(a, b));
+        launch_cand_score(idx->corpus, idx->dtype, score_form(idx->metric), idx->dim, idx->ld, P.q_f32.as<float>(), d_lims, d_off, nq, off[nq],
+                          idx->cand_rows.as<uint32_t>(), d_out_scores, d_cnt, s);
+        VROD_TRY(tm.end_launch(a, b));
+        HIP_TRY(hipGetLastError());
+        st.scan_launches = 1;
+        std::vector<uint32_t> cnt(nq);
+        HIP_TRY(hipMemcpyAsync(cnt.data(), d_cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        tm.add_scan_ms(st);
+        uint64_t rows = 0;   // entries scored: a repeated id is scored at every position
+        for (uint32_t q = 0; q < nq; ++q) { rows += cnt[q]; st.kprime = std::max(st.kprime, cnt[q]); }
+        st.scan_bytes = (double)rows * idx->ld * idx->esize;
+        st.scan_flops = 2.0 * (double)rows * idx->dim;
+    }
+    idx->stats = st;
+    return VROD_OK;
+}
+
 // The graph of rows [row0, row0 + n): batches of byid_plan.h, two in flight -- batch s + 1's gather and search are
 // enqueued (search_begin) before batch s is completed (search_end), its lists lose self and its rows are copied out, so
 // the device scans batch s + 1 while the host and the copy engine finish batch s.  The deleted rows of a batch never
@@ -3669,7 +3790,8 @@ int vrod_index_destroy(vrod_index* idx) {
                       &idx->grp_qraw, &idx->byid_user_ids, &idx->doc_rank, &idx->doc_labels, &idx->mv_q, &idx->mv_ids, &idx->mv_scores, &idx->mv_ent,
                       &idx->mv_tab, &idx->mv_cand, &idx->mv_small, &idx->mv_best, &idx->mv_S, &idx->mv_absent, &idx->mv_M, &idx->mv_pairs,
                       &idx->mv_raw, &idx->mv_lims, &idx->mv_out_labels, &idx->mv_out_scores, &idx->mv_found, &idx->dv_ids, &idx->dv_scores,
-                      &idx->dv_qraw, &idx->dv_mmr, &idx->cmb_ids, &idx->cmb_scores, &idx->cmb_vec, &idx->cmb_args}) b->release();
+                      &idx->dv_qraw, &idx->dv_mmr, &idx->cmb_ids, &idx->cmb_scores, &idx->cmb_vec, &idx->cmb_args, &idx->cand_rows,
+                      &idx->cand_small, &idx->cand_args, &idx->cand_qraw}) b->release();
     for (int c = 0; c < 2; ++c)
         for (DevBuf* b : {&idx->byid_ids[c], &idx->byid_scores[c], &idx->byid_out_ids[c], &idx->byid_out_scores[c], &idx->byid_map[c]}) b->release();
     if (idx->flags) (void)hipFree(idx->flags);
@@ -4329,6 +4451,98 @@ int vrod_search_combined_device(vrod_index* idx, const float* d_vectors, const f
                                   nq, k, flags, &counts));
     CombineArgs a{d_vectors, d_vectors ? d_vector_weights : nullptr, d_term_lims, d_term_ids, d_term_weights, d_exclude_lims, d_exclude_ids};
     return combined_search(idx, a, counts, nq, k, flags, d_out_ids, d_out_scores);
+}
+
+// k: the search form's (the score form has none: has_k false).  out: the ids of the search form, the scores of the score form.
+static int check_candidates_args(vrod_index* idx, const void* q, uint32_t nq, bool has_k, uint32_t k, const void* lims, const void* out,
+                                 const void* out2, const char* what) {
+    if (!idx) return fail(VROD_ERR_INVALID_ARG, "idx is null");
+    if (has_k && (k == 0 || k > VROD_MAX_K)) return fail(VROD_ERR_INVALID_ARG, "k must be in 1..%u", VROD_MAX_K);
+    if (nq && (!q || !lims || (has_k && (!out || !out2)))) return fail(VROD_ERR_INVALID_ARG, "null buffer");
+    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "%s on a multi-device handle: candidate ids are not routed to the shards", what);
+    return VROD_OK;
+}
+
+// The lims array (a host copy) against candidates_plan.h, and the pointers its total requires.
+static int check_candidates_lists(const uint32_t* lims, uint32_t nq, const void* ids, const void* out_scores) {
+    uint32_t q = 0;
+    switch (cand_check_lims(lims, nq, &q)) {
+        case 0: break;
+        case 1: return fail(VROD_ERR_INVALID_ARG, "cand_lims must start at 0 and never decrease");
+        default: return fail(VROD_ERR_INVALID_ARG, "query %u lists more than %u candidates", q, VROD_MAX_CANDIDATES);
+    }
+    if (lims[nq] && (!ids || !out_scores)) return fail(VROD_ERR_INVALID_ARG, "null buffer");
+    return VROD_OK;
+}
+
+// A host form's lists and raw queries on the device: cand_args as [ids | lims], cand_qraw.
+static int upload_candidates(vrod_index* idx, const float* queries, uint32_t nq, const uint32_t* lims, const uint64_t* ids,
+                             const uint64_t** d_ids, const uint32_t** d_lims) {
+    const size_t n = lims[nq], o_lims = n * 8;
+    VROD_TRY(idx->cand_args.ensure(o_lims + ((size_t)nq + 1) * 4));
+    VROD_TRY(idx->cand_qraw.ensure((size_t)nq * idx->dim * 4));
+    char* base = idx->cand_args.as<char>();
+    if (n) HIP_TRY(hipMemcpy(base, ids, n * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(base + o_lims, lims, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(idx->cand_qraw.p, queries, (size_t)nq * idx->dim * 4, hipMemcpyHostToDevice));
+    *d_ids = (const uint64_t*)base;
+    *d_lims = (const uint32_t*)(base + o_lims);
+    return VROD_OK;
+}
+
+int vrod_search_candidates(vrod_index* idx, const float* queries, uint32_t nq, uint32_t k, const uint32_t* cand_lims, const uint64_t* cand_ids,
+                           uint64_t* out_ids, float* out_scores) {
+    VROD_TRY(check_candidates_args(idx, queries, nq, true, k, cand_lims, out_ids, out_scores, "vrod_search_candidates"));
+    if (!nq) return VROD_OK;
+    VROD_TRY(require_idle(idx, "vrod_search_candidates"));
+    VROD_TRY(check_candidates_lists(cand_lims, nq, cand_ids, out_scores));
+    VROD_TRY(set_device(idx));
+    const uint64_t* d_ids;
+    const uint32_t* d_lims;
+    VROD_TRY(upload_candidates(idx, queries, nq, cand_lims, cand_ids, &d_ids, &d_lims));
+    VROD_TRY(grow_topk_out(idx, nq, k));
+    VROD_TRY(candidates_search(idx, idx->cand_qraw.as<float>(), nq, k, cand_lims, d_lims, d_ids, idx->out_ids.as<uint64_t>(),
+                               idx->out_scores.as<float>()));
+    return copy_topk_out(idx, nq, k, out_ids, out_scores);
+}
+
+int vrod_search_candidates_device(vrod_index* idx, const float* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_cand_lims,
+                                  const uint64_t* d_cand_ids, uint64_t* d_out_ids, float* d_out_scores, void* stream) {
+    VROD_TRY(check_candidates_args(idx, d_queries, nq, true, k, d_cand_lims, d_out_ids, d_out_scores, "vrod_search_candidates_device"));
+    if (!nq) return VROD_OK;
+    VROD_TRY(begin_sync_device(idx, "vrod_search_candidates_device", stream));
+    std::vector<uint32_t> lims((size_t)nq + 1);
+    HIP_TRY(hipMemcpy(lims.data(), d_cand_lims, lims.size() * 4, hipMemcpyDeviceToHost));
+    VROD_TRY(check_candidates_lists(lims.data(), nq, d_cand_ids, d_out_scores));
+    return candidates_search(idx, d_queries, nq, k, lims.data(), d_cand_lims, d_cand_ids, d_out_ids, d_out_scores);
+}
+
+int vrod_score_candidates(vrod_index* idx, const float* queries, uint32_t nq, const uint32_t* cand_lims, const uint64_t* cand_ids,
+                          float* out_scores) {
+    VROD_TRY(check_candidates_args(idx, queries, nq, false, 0, cand_lims, nullptr, nullptr, "vrod_score_candidates"));
+    if (!nq) return VROD_OK;
+    VROD_TRY(require_idle(idx, "vrod_score_candidates"));
+    VROD_TRY(check_candidates_lists(cand_lims, nq, cand_ids, out_scores));
+    VROD_TRY(set_device(idx));
+    const uint64_t* d_ids;
+    const uint32_t* d_lims;
+    VROD_TRY(upload_candidates(idx, queries, nq, cand_lims, cand_ids, &d_ids, &d_lims));
+    const size_t n = cand_lims[nq];
+    VROD_TRY(idx->out_scores.ensure(std::max<size_t>(n, 1) * 4));
+    VROD_TRY(candidates_score(idx, idx->cand_qraw.as<float>(), nq, cand_lims, d_lims, d_ids, idx->out_scores.as<float>()));
+    if (n) HIP_TRY(hipMemcpy(out_scores, idx->out_scores.p, n * 4, hipMemcpyDeviceToHost));
+    return VROD_OK;
+}
+
+int vrod_score_candidates_device(vrod_index* idx, const float* d_queries, uint32_t nq, const uint32_t* d_cand_lims, const uint64_t* d_cand_ids,
+                                 float* d_out_scores, void* stream) {
+    VROD_TRY(check_candidates_args(idx, d_queries, nq, false, 0, d_cand_lims, nullptr, nullptr, "vrod_score_candidates_device"));
+    if (!nq) return VROD_OK;
+    VROD_TRY(begin_sync_device(idx, "vrod_score_candidates_device", stream));
+    std::vector<uint32_t> lims((size_t)nq + 1);
+    HIP_TRY(hipMemcpy(lims.data(), d_cand_lims, lims.size() * 4, hipMemcpyDeviceToHost));
+    VROD_TRY(check_candidates_lists(lims.data(), nq, d_cand_ids, d_out_scores));
+    return candidates_score(idx, d_queries, nq, lims.data(), d_cand_lims, d_cand_ids, d_out_scores);
 }
 
 int vrod_knn_graph(vrod_index* idx, uint64_t first_id, uint64_t n, uint32_t k, uint64_t* out_ids, float* out_scores) {

@@ -9,6 +9,7 @@
 #include "tag_plan.h"      // TagPred
 #include "multivec_plan.h" // MultivecQuery
 #include "combine_plan.h"  // kCombineMaxExclude, combine_lanes_per_query
+#include "candidates_plan.h" // kCandMaxList, the sort classes, cand_tile_query
 
 namespace vrod {
 
@@ -322,6 +323,24 @@ void launch_combine_queries(const void* d_corpus, int dtype, uint32_t ld, uint32
 void launch_drop_excluded(const uint64_t* d_list_ids, const float* d_list_scores, uint32_t k1, const uint32_t* d_excl_lims,
                           const uint64_t* d_excl_ids, const uint32_t* d_term_lims, const uint64_t* d_term_ids, uint32_t nq, uint32_t k,
                           uint64_t* d_out_ids, float* d_out_scores, hipStream_t s);
+
+// ---- kernels_candidates.hip : per-query id lists -> row segments, and their scores in list order (vrod_search_candidates,
+// vrod_score_candidates)
+// d_rows[i] = the local row of d_ids[i] (ids with id_offset applied), or kCandNoRow when the id is VROD_ID_NONE, no
+// current row, or set in d_row_mask (may be null).
+void launch_cand_resolve(const uint64_t* d_ids, uint32_t n, uint64_t count, uint64_t id_offset, const uint32_t* d_row_mask, uint32_t* d_rows,
+                         hipStream_t s);
+// One work-group per query q = d_qidx[b], b < n_queries, all of sort class `sort_class` (candidates_plan.h): the distinct
+// rows of d_rows[d_lims[q] .. d_lims[q + 1]) without kCandNoRow, ascending, into d_lists from d_lims[q] on; d_len[q] =
+// their number.
+void launch_cand_sort_unique(const uint32_t* d_rows, const uint32_t* d_lims, const uint32_t* d_qidx, uint32_t n_queries, uint32_t sort_class,
+                             uint32_t* d_lists, uint32_t* d_len, hipStream_t s);
+// d_out[t] = the canonical score (the chain of rescore_chain.h, as a search reports it) of prepared query q of d_q [nq][ld]
+// against row d_rows[t] for every t in [d_lims[q], d_lims[q + 1]); NaN where d_rows[t] is kCandNoRow.  d_tile_off [nq + 1]:
+// cand_tile_offsets, n_tiles its last entry.  d_n_scored[q] (cleared by the caller) += the entries of q that were scored.
+void launch_cand_score(const void* d_corpus, int dtype, int metric, uint32_t dim, uint32_t ld, const float* d_q, const uint32_t* d_lims,
+                       const uint32_t* d_tile_off, uint32_t nq, uint32_t n_tiles, const uint32_t* d_rows, float* d_out, uint32_t* d_n_scored,
+                       hipStream_t s);
 
 // ---- kernels_mfma.hip : batched Q.K^T scan with fused threshold filter
 // Timing of the dominant scan launches without marker packets: the launcher of the next scan

@@ -24,6 +24,7 @@ MAX_DIVERSE_POOL = 1024   # VROD_MAX_DIVERSE_POOL
 MAX_COMBINE_TERMS = 256   # VROD_MAX_COMBINE_TERMS
 MAX_EXCLUDE = 1024        # VROD_MAX_EXCLUDE
 COMBINED_EXCLUDE_TERMS = 1   # VROD_COMBINED_EXCLUDE_TERMS
+MAX_CANDIDATES = 16384    # VROD_MAX_CANDIDATES
 # rows per batch of knn_graph() by storage type (byid_plan.h: kByidBatchF32, kByidBatchBf16)
 KNN_BATCH = {0: 256, 1: 1024}
 
@@ -594,6 +595,66 @@ class Index:
             ptr(d_exclude_ids, torch.int64, "exclude_ids"), nq, int(k), COMBINED_EXCLUDE_TERMS if exclude_terms else 0,
             out_ids.data_ptr(), out_scores.data_ptr(), C.c_void_p(stream)))
         return out_ids, out_scores
+
+    # -- candidate lists: every query is scored against the rows its own list of ids names
+    def _candidate_args(self, queries, cand_ids, cand_lims):
+        queries = self._queries(queries)
+        cid, cl = self._ragged_ids(cand_ids, cand_lims, "candidate")
+        if cl.size != queries.shape[0] + 1:
+            raise ValueError(f"candidate lists for {cl.size - 1} queries, {queries.shape[0]} queries")
+        return queries, cid, cl
+
+    def search_candidates(self, queries: np.ndarray, k: int, cand_ids, cand_lims=None):
+        """search() over a list of candidate ids per query (vrod_search_candidates): query q sees only the distinct ids of
+        its list that are live, allowed rows, in any order; ids that are not are ignored.  cand_ids: a list of per-query
+        sequences, or flat with cand_lims [nq + 1].  -> (ids uint64 [nq, k], scores float32 [nq, k])."""
+        queries, cid, cl = self._candidate_args(queries, cand_ids, cand_lims)
+        nq = queries.shape[0]
+        ids, sc = _out(nq, k, np.uint64, np.float32)
+        check(self._L.vrod_search_candidates(self._h, _ptr(queries), nq, int(k), _ptr(cl), _ptr(cid), _ptr(ids), _ptr(sc)))
+        return ids, sc
+
+    def score_candidates(self, queries: np.ndarray, cand_ids, cand_lims=None):
+        """The canonical score of every listed id against its query (vrod_score_candidates), in the caller's order: NaN where
+        the id is not a live, allowed row.  cand_ids as for search_candidates.  -> scores float32, flat, aligned with the
+        ids (query q owns [lims[q], lims[q + 1]))."""
+        queries, cid, cl = self._candidate_args(queries, cand_ids, cand_lims)
+        sc = np.empty(cid.size, np.float32)
+        check(self._L.vrod_score_candidates(self._h, _ptr(queries), queries.shape[0], _ptr(cl), _ptr(cid), _ptr(sc)))
+        return sc
+
+    def _device_candidates(self, d_queries, d_cand_lims, d_cand_ids):
+        import torch
+        nq, dev, stream = self._device_queries(d_queries)
+        if d_cand_lims.dtype != torch.int32:
+            raise TypeError(f"cand_lims must be an int32 tensor, got {d_cand_lims.dtype}")
+        if d_cand_ids.dtype != torch.int64:
+            raise TypeError(f"cand_ids must be an int64 tensor, got {d_cand_ids.dtype}")
+        if d_cand_lims.dim() != 1 or d_cand_lims.numel() != nq + 1:
+            raise ValueError(f"cand_lims must hold {nq + 1} entries")
+        assert d_cand_lims.is_cuda and d_cand_lims.is_contiguous() and d_cand_ids.is_cuda and d_cand_ids.is_contiguous()
+        return nq, dev, stream
+
+    def search_candidates_device(self, d_queries, k: int, d_cand_lims, d_cand_ids, out_ids=None, out_scores=None):
+        """torch CUDA tensors: queries [nq, dim] fp32, cand_lims [nq + 1] int32 (the bits of uint32), cand_ids int64 (the bits
+        of uint64) -> (ids int64-viewed-uint64 [nq, k], scores [nq, k]) on the device, complete on return."""
+        import torch
+        nq, dev, stream = self._device_candidates(d_queries, d_cand_lims, d_cand_ids)
+        out_ids = _device_out(out_ids, (nq, k), torch.int64, dev)
+        out_scores = _device_out(out_scores, (nq, k), torch.float32, dev)
+        check(self._L.vrod_search_candidates_device(self._h, d_queries.data_ptr(), nq, int(k), d_cand_lims.data_ptr(), d_cand_ids.data_ptr(),
+                                                    out_ids.data_ptr(), out_scores.data_ptr(), stream))
+        return out_ids, out_scores
+
+    def score_candidates_device(self, d_queries, d_cand_lims, d_cand_ids, out_scores=None):
+        """torch CUDA tensors as for search_candidates_device -> scores fp32, one per entry of cand_ids, on the device,
+        complete on return."""
+        import torch
+        nq, dev, stream = self._device_candidates(d_queries, d_cand_lims, d_cand_ids)
+        out_scores = _device_out(out_scores, (d_cand_ids.numel(),), torch.float32, dev)
+        check(self._L.vrod_score_candidates_device(self._h, d_queries.data_ptr(), nq, d_cand_lims.data_ptr(), d_cand_ids.data_ptr(),
+                                                   out_scores.data_ptr(), stream))
+        return out_scores
 
     def _first_id(self) -> int:
         return getattr(self, "_id_offset", 0)
