@@ -81,9 +81,20 @@ static int fail(int code, const char* fmt, ...) {
     } while (0)
 
 // ------------------------------------------------------------------ device buffer that only grows
+// It owns its memory: whatever holds one (the handle, a Pending, a DevGroup) frees it by going away, under the device
+// that is current then, and cannot be copied.  A buffer on another device than its holder's is released by hand first.
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~DevBuf() { release(); }
     int ensure(size_t bytes) {
         if (bytes <= cap) return VROD_OK;
         if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
@@ -231,49 +242,45 @@ struct vrod_index {
     // vrod_search_tagged reads them; a handle that never set one treats every row as 0.
     std::vector<uint64_t> tag_bits;    // [capacity] once tags exist
     uint64_t* tag_dev = nullptr;       // [capacity] on the device, or null
+    // Workspaces the synchronous searches share, one per role (DESIGN.md "Shared workspaces"): the handle is idle before
+    // and after each of those calls, so no two of them hold one at once.
+    //   host_q, host_args: a host form's raw queries or vectors, and its other arguments, on the device;
+    //   list_ids / list_scores: the first-stage lists a search flow writes and one launch reads.  Two sets: vrod_knn_graph
+    //     keeps two batches in flight and batch s uses set s & 1 (byid_plan.h); every other call takes set 0;
+    //   out_col [nq][k] words (a grouped or multi-vector search's labels, a diversified search's selection values) and
+    //     out_found [nq]: the result columns beside out_ids / out_scores, for a host form or a caller that passes none.
+    DevBuf host_q, host_args, list_ids[2], list_scores[2], out_col, out_found;
     // labelled search workspaces: [table | totals | segment offsets], the per-block counts, the row lists, the per-slot
-    // arrays, the work table, a dense group's mask / raw queries / results, the host form's raw queries.  A tagged
+    // arrays, the work table, a dense group's mask / raw queries (its results go to the shared lists).  A tagged
     // search, which is synchronous too, uses the same buffers for the same things (its table holds predicates).
-    DevBuf lab_tab, lab_cnt, lab_lists, lab_slots, lab_entries, lab_mask, lab_q, lab_ids, lab_scores, lab_qraw;
-    // grouped search workspaces (vrod_search_grouped): the candidate lists [lists][k1], the per-query words [found | valid |
-    // the lists' queries], the dense stage's masks [<= 8][capacity / 32], the labels of the results when the caller
-    // wants none, the host form's raw queries
-    DevBuf grp_ids, grp_scores, grp_small, grp_mask, grp_labels, grp_qraw;
+    DevBuf lab_tab, lab_cnt, lab_lists, lab_slots, lab_entries, lab_mask, lab_q;
+    // grouped search workspaces (vrod_search_grouped): the per-query words [found | valid | the lists' queries] and the
+    // dense stage's masks [<= 8][capacity / 32]
+    DevBuf grp_small, grp_mask;
     // multi-vector search (vrod_search_multivec).  The document index: doc_rank[row] = the rank of the row's label among
     // the handle's distinct labels, ascending (doc_labels [n_docs]), built on the host from lab_bits at the first search
     // that needs it and kept until set_labels, add or compact change what it was built from (update and delete do not);
     // a handle without labels is one document, label 0, and has no rank array.  Then the workspaces: the prepared vectors
-    // of the whole call, the first-stage lists [vectors][k1], the de-duplication's entry labels / tables / candidate
-    // labels, the per-query words, the dense route's best [<= 8][n_docs] / S rows / absent bitmap, the candidate route's
-    // M per score slot and its pair arrays, and the host form's raw vectors and results.
+    // of the whole call, the de-duplication's entry labels / tables / candidate labels, the per-query words, the dense
+    // route's best [<= 8][n_docs] / S rows / absent bitmap, the candidate route's M per score slot and its pair arrays.
     DevBuf doc_rank, doc_labels;
     uint64_t n_docs = 0;
     bool doc_valid = false;
-    DevBuf mv_q, mv_ids, mv_scores, mv_ent, mv_tab, mv_cand, mv_small, mv_best, mv_S, mv_absent, mv_M, mv_pairs, mv_raw, mv_lims, mv_out_labels,
-        mv_out_scores, mv_found;
+    DevBuf mv_q, mv_ent, mv_tab, mv_cand, mv_small, mv_best, mv_S, mv_absent, mv_M, mv_pairs;
     vrod_multivec_stats mv_stats{};
-    // diversified search (vrod_search_diverse): the first-stage lists [nq][pool], and the host form's raw queries and
-    // its selection values
-    DevBuf dv_ids, dv_scores, dv_qraw, dv_mmr;
     // Searches whose queries are stored rows (vrod_search_by_ids, vrod_knn_graph) hand the search flow rows that are
     // prepared already: while prep_ovr is not negative it stands for prep_form(metric) in the launch that prepares a
     // search's queries -- M_L2, the take-as-given form of L2 and IP handles: nothing is normalised, and rounding a bf16
     // value to bf16 is the identity.  Everything else that launch sets up is unchanged.  Negative outside those two entry
     // points; a search under it is never captured into a graph nor matched with a captured one.
     int prep_ovr = -1;
-    // their workspaces, one set per batch in flight (byid_plan.h: a graph's batch s uses set s & 1, a search by ids set
-    // 0): the search's lists [nq][k or k + 1], the lists without self [nq][k], a graph batch's [live rows | place of
-    // every row among them]; and the host form's ids on the device
-    DevBuf byid_ids[2], byid_scores[2], byid_out_ids[2], byid_out_scores[2], byid_map[2], byid_user_ids;
-    // search by weighted examples (vrod_search_combined): the search's lists [nq][k1] while a query excludes anything, and
-    // the host form's arguments on the device -- its raw vectors, and one block [term ids | excluded ids | term weights |
-    // vector weights | term lims | exclude lims]
-    DevBuf cmb_ids, cmb_scores, cmb_vec, cmb_args;
-    // candidate-list searches (vrod_search_candidates, vrod_score_candidates): the lists' entries as local rows, the
-    // per-query words [lengths | the queries by sort class, or the score launch's tile offsets], and the host forms'
-    // arguments on the device -- [ids | lims] and the raw queries.  The resolved segments go to lab_lists, the slot
-    // tables to lab_slots: the segmented driver finds them where a labelled search leaves its own.
-    DevBuf cand_rows, cand_small, cand_args, cand_qraw;
+    // a graph's workspaces, one set per batch in flight as its lists: the lists without self [rows][k], and the batch's
+    // [live rows | place of every row among them]
+    DevBuf byid_out_ids[2], byid_out_scores[2], byid_map[2];
+    // candidate-list searches (vrod_search_candidates, vrod_score_candidates): the lists' entries as local rows and the
+    // per-query words [lengths | the queries by sort class, or the score launch's tile offsets].  The resolved segments go
+    // to lab_lists, the slot tables to lab_slots: the segmented driver finds them where a labelled search leaves its own.
+    DevBuf cand_rows, cand_small;
 
     // workspaces
     DevBuf raw_stage, nrm_ws, out_ids, out_scores;
@@ -341,6 +348,13 @@ struct vrod_index {
 
 static int set_device(const vrod_index* idx) {
     HIP_TRY(hipSetDevice(idx->device));
+    return VROD_OK;
+}
+
+// Set `c` of the shared first-stage lists, grown for n entries.
+static int grow_lists(vrod_index* idx, int c, size_t n) {
+    VROD_TRY(idx->list_ids[c].ensure(n * 8));
+    VROD_TRY(idx->list_scores[c].ensure(n * 4));
     return VROD_OK;
 }
 
@@ -474,15 +488,22 @@ static int append_prepared(vrod_index* idx, const float* d_raw, uint64_t n) {
     return VROD_OK;
 }
 
-static int check_bad_flag(vrod_index* idx, const char* what) {
-    uint32_t bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, &idx->flags[0], 4, hipMemcpyDeviceToHost, idx->stream));
-    HIP_TRY(hipStreamSynchronize(idx->stream));
-    if (bad) {
-        HIP_TRY(hipMemsetAsync(&idx->flags[0], 0, 4, idx->stream));
-        HIP_TRY(hipStreamSynchronize(idx->stream));
-        return fail(VROD_ERR_INVALID_VALUE, "%s contain NaN or Inf", what);
+// Word `w` of idx->flags as the launches on `s` so far leave it; a raised word is cleared for the next call.
+static int take_flag(vrod_index* idx, uint32_t w, hipStream_t s, uint32_t* bad) {
+    *bad = 0;
+    HIP_TRY(hipMemcpyAsync(bad, &idx->flags[w], 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (*bad) {
+        HIP_TRY(hipMemsetAsync(&idx->flags[w], 0, 4, s));
+        HIP_TRY(hipStreamSynchronize(s));
     }
+    return VROD_OK;
+}
+
+static int check_bad_flag(vrod_index* idx, const char* what) {
+    uint32_t bad;
+    VROD_TRY(take_flag(idx, 0, idx->stream, &bad));
+    if (bad) return fail(VROD_ERR_INVALID_VALUE, "%s contain NaN or Inf", what);
     return VROD_OK;
 }
 
@@ -2597,14 +2618,12 @@ static int score_segments(vrod_index* idx, Pending& P, Timer& tm, vrod_search_st
 static int wide_group_ws(vrod_index* idx, uint32_t max_nq, uint32_t k) {
     VROD_TRY(idx->lab_mask.ensure(idx->del_bits.size() * 4));   // capacity / 32 words
     VROD_TRY(idx->lab_q.ensure((size_t)max_nq * idx->dim * 4));
-    VROD_TRY(idx->lab_ids.ensure((size_t)max_nq * k * 8));
-    VROD_TRY(idx->lab_scores.ensure((size_t)max_nq * k * 4));
-    return VROD_OK;
+    return grow_lists(idx, 0, (size_t)max_nq * k);
 }
 
 // The dense route of one group: the ordinary search flow over the batch's queries d_qidx[0 .. nqg) with the group's mask
 // (idx->lab_mask, enqueued on `s` already; m rows are clear in it) in place of row_mask(), the results scattered to the
-// queries' rows.  lab_q / lab_ids / lab_scores hold nqg queries.
+// queries' rows.  lab_q and set 0 of the shared lists hold nqg queries.
 static int dense_group_search(vrod_index* idx, hipStream_t s, vrod_search_stats& st, const float* d_queries_raw, const uint32_t* d_qidx,
                               const uint32_t* d_ones, uint32_t nqg, uint64_t m, uint32_t k, uint64_t* d_out_ids, float* d_out_scores) {
     launch_gather_rows(d_queries_raw, d_qidx, nqg, idx->dim, idx->lab_q.as<float>(), s);
@@ -2612,14 +2631,14 @@ static int dense_group_search(vrod_index* idx, hipStream_t s, vrod_search_stats&
     HIP_TRY(hipStreamSynchronize(s));
     idx->mask_ovr = idx->lab_mask.as<uint32_t>();
     idx->elig_ovr = m;
-    const int rc = run_search(idx, idx->lab_q.as<float>(), nqg, k, idx->lab_ids.as<uint64_t>(), idx->lab_scores.as<float>());
+    const int rc = run_search(idx, idx->lab_q.as<float>(), nqg, k, idx->list_ids[0].as<uint64_t>(), idx->list_scores[0].as<float>());
     idx->mask_ovr = nullptr;
     idx->elig_ovr = 0;
     if (rc != VROD_OK) return rc;
     fold_stats(st, idx->stats);
     st.scan_bytes += (double)idx->count * idx->ld * idx->esize;
     st.scan_flops += 2.0 * nqg * (double)idx->count * idx->dim;
-    launch_scatter_results(idx->lab_ids.as<uint64_t>(), idx->lab_scores.as<float>(), d_qidx, d_ones, nqg, k, d_out_ids, d_out_scores, s);
+    launch_scatter_results(idx->list_ids[0].as<uint64_t>(), idx->list_scores[0].as<float>(), d_qidx, d_ones, nqg, k, d_out_ids, d_out_scores, s);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
     return VROD_OK;
@@ -2852,13 +2871,12 @@ static int grouped_search(vrod_index* idx, const float* d_queries_raw, uint32_t 
 
     // ---- candidate stage
     if (idx->path != VROD_PATH_EXACT) {
-        VROD_TRY(idx->grp_ids.ensure((size_t)nq * k1 * 8));
-        VROD_TRY(idx->grp_scores.ensure((size_t)nq * k1 * 4));
-        VROD_TRY(run_search(idx, d_queries_raw, nq, k1, idx->grp_ids.as<uint64_t>(), idx->grp_scores.as<float>()));
+        VROD_TRY(grow_lists(idx, 0, (size_t)nq * k1));
+        VROD_TRY(run_search(idx, d_queries_raw, nq, k1, idx->list_ids[0].as<uint64_t>(), idx->list_scores[0].as<float>()));
         st = idx->stats;
         st.k = k;
         s = next_slot(idx).stream;
-        launch_group_dedupe(idx->grp_ids.as<uint64_t>(), idx->grp_scores.as<float>(), k1, nq, idx->lab_dev, idmap.offset, nullptr, k,
+        launch_group_dedupe(idx->list_ids[0].as<uint64_t>(), idx->list_scores[0].as<float>(), k1, nq, idx->lab_dev, idmap.offset, nullptr, k,
                             d_out_ids, d_out_scores, d_out_labels, d_found, d_valid, s);
         VROD_TRY(read_state(s));
         for (uint32_t q = 0; q < nq; ++q)
@@ -2880,8 +2898,7 @@ static int grouped_search(vrod_index* idx, const float* d_queries_raw, uint32_t 
     const double row_bytes = (double)idx->ld * idx->esize;
     int gmax = rescore_all_max_queries(idx->ld);
     while (gmax > 1 && (uint64_t)gmax * score_ld * 4 > (1ull << 30)) gmax >>= 1;
-    VROD_TRY(idx->grp_ids.ensure((size_t)gmax * k1 * 8));
-    VROD_TRY(idx->grp_scores.ensure((size_t)gmax * k1 * 4));
+    VROD_TRY(grow_lists(idx, 0, (size_t)gmax * k1));   // (the candidate stage's lists are spent: their reader was drained)
     VROD_TRY(idx->grp_mask.ensure((size_t)gmax * words * 4));
     Timer tm(idx, P);
     P.reset_events();
@@ -2912,10 +2929,10 @@ static int grouped_search(vrod_index* idx, const float* d_queries_raw, uint32_t 
                 const uint64_t* keys; uint64_t kld, kn;
                 VROD_TRY(select_chain(idx, P, P.scores.as<float>() + (size_t)act[a].score_row * score_ld, score_ld, N, 1, k1,
                                       idx->grp_mask.as<uint32_t>() + (size_t)a * words, &keys, &kld, &kn));
-                launch_keys_to_output(keys, kn, form, k1, idmap, idx->grp_ids.as<uint64_t>() + (size_t)a * k1,
-                                      idx->grp_scores.as<float>() + (size_t)a * k1, s);
+                launch_keys_to_output(keys, kn, form, k1, idmap, idx->list_ids[0].as<uint64_t>() + (size_t)a * k1,
+                                      idx->list_scores[0].as<float>() + (size_t)a * k1, s);
             }
-            launch_group_dedupe(idx->grp_ids.as<uint64_t>(), idx->grp_scores.as<float>(), k1, na, idx->lab_dev, idmap.offset, d_qidx, k,
+            launch_group_dedupe(idx->list_ids[0].as<uint64_t>(), idx->list_scores[0].as<float>(), k1, na, idx->lab_dev, idmap.offset, d_qidx, k,
                                 d_out_ids, d_out_scores, d_out_labels, d_found, d_valid, s);
             VROD_TRY(read_state(s));   // (also orders the next round's upload of d_qidx behind this round's readers)
             std::vector<Active> next;
@@ -3045,9 +3062,8 @@ static int multivec_candidates(vrod_index* idx, vrod_search_stats& st, bool firs
     const double row_bytes = (double)idx->ld * idx->esize;
     vrod_multivec_stats& ms = idx->mv_stats;
     // ---- the certified lists of every vector
-    VROD_TRY(idx->mv_ids.ensure((size_t)V * k1 * 8));
-    VROD_TRY(idx->mv_scores.ensure((size_t)V * k1 * 4));
-    VROD_TRY(run_search(idx, d_raw + (size_t)vbase * idx->dim, V, k1, idx->mv_ids.as<uint64_t>(), idx->mv_scores.as<float>()));
+    VROD_TRY(grow_lists(idx, 0, (size_t)V * k1));
+    VROD_TRY(run_search(idx, d_raw + (size_t)vbase * idx->dim, V, k1, idx->list_ids[0].as<uint64_t>(), idx->list_scores[0].as<float>()));
     if (first_batch) {
         st = idx->stats;
     } else {
@@ -3084,7 +3100,7 @@ static int multivec_candidates(vrod_index* idx, vrod_search_stats& st, bool firs
     uint32_t* d_len = d_qidx + nqs;
     HIP_TRY(hipMemcpyAsync(d_mq, mq.data(), (size_t)nqs * sizeof(MultivecQuery), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(idx->mv_tab.p, 0xFF, tab_words * 4, s));
-    launch_multivec_candidates(idx->mv_ids.as<uint64_t>(), idx->mv_scores.as<float>(), k1, idx->lab_dev, idmap_of(idx).offset, d_mq, nqs,
+    launch_multivec_candidates(idx->list_ids[0].as<uint64_t>(), idx->list_scores[0].as<float>(), k1, idx->lab_dev, idmap_of(idx).offset, d_mq, nqs,
                                idx->mv_ent.as<uint32_t>(), idx->mv_tab.as<uint32_t>(), idx->mv_cand.as<uint32_t>(), d_count, d_flags, d_U, s);
     HIP_TRY(hipGetLastError());
     std::vector<uint32_t> cf((size_t)nqs * 3), cand(entries);
@@ -3294,21 +3310,16 @@ static int diverse_search(vrod_index* idx, const float* d_queries_raw, uint32_t 
         vrod_search_stats st{};
         st.nq = nq; st.k = k; st.path = (uint32_t)idx->path;
         hipStream_t s = next_slot(idx).stream;
-        launch_fill_none(d_out_ids, d_out_scores, (uint64_t)nq * k, s);
-        HIP_TRY(hipGetLastError());
         if (d_out_mmr) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)d_out_mmr, (int)kScoreNoneBits, (size_t)nq * k, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        idx->stats = st;
-        return VROD_OK;
+        return return_unfilled(idx, s, st, d_out_ids, d_out_scores, (uint64_t)nq * k);
     }
     if (!diverse_waves(idx->dim, pool)) return fail(VROD_ERR_INTERNAL, "diversified search: no work-group fits dim %u, pool %u", idx->dim, pool);
-    VROD_TRY(idx->dv_ids.ensure((size_t)nq * pool * 8));
-    VROD_TRY(idx->dv_scores.ensure((size_t)nq * pool * 4));
-    VROD_TRY(run_search(idx, d_queries_raw, nq, pool, idx->dv_ids.as<uint64_t>(), idx->dv_scores.as<float>()));
+    VROD_TRY(grow_lists(idx, 0, (size_t)nq * pool));
+    VROD_TRY(run_search(idx, d_queries_raw, nq, pool, idx->list_ids[0].as<uint64_t>(), idx->list_scores[0].as<float>()));
     idx->stats.k = k;
     hipStream_t s = next_slot(idx).stream;
-    launch_diverse_select(idx->corpus, idx->dtype, score_form(idx->metric), idx->dim, idx->ld, idx->dv_ids.as<uint64_t>(),
-                          idx->dv_scores.as<float>(), nq, pool, k, lambda, idmap_of(idx).offset, d_out_ids, d_out_scores, d_out_mmr, s);
+    launch_diverse_select(idx->corpus, idx->dtype, score_form(idx->metric), idx->dim, idx->ld, idx->list_ids[0].as<uint64_t>(),
+                          idx->list_scores[0].as<float>(), nq, pool, k, lambda, idmap_of(idx).offset, d_out_ids, d_out_scores, d_out_mmr, s);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
     return VROD_OK;
@@ -3341,25 +3352,20 @@ static int byid_search(vrod_index* idx, const uint64_t* d_ids, bool checked, uin
     uint64_t* l_ids = d_out_ids;
     float* l_scores = d_out_scores;
     if (staged) {
-        VROD_TRY(idx->byid_ids[0].ensure((size_t)nq * k1 * 8));
-        VROD_TRY(idx->byid_scores[0].ensure((size_t)nq * k1 * 4));
-        l_ids = idx->byid_ids[0].as<uint64_t>();
-        l_scores = idx->byid_scores[0].as<float>();
+        VROD_TRY(grow_lists(idx, 0, (size_t)nq * k1));
+        l_ids = idx->list_ids[0].as<uint64_t>();
+        l_scores = idx->list_scores[0].as<float>();
     }
     VROD_TRY(P.q_raw.ensure((size_t)nq * idx->dim * 4));
     launch_byid_gather(idx->corpus, idx->dtype, idx->ld, idx->dim, idx->count, idx->id_offset, idx->n_deleted ? idx->del_dev : nullptr, d_ids,
                        nullptr, 0, nq, P.q_raw.as<float>(), checked ? nullptr : &idx->flags[kByidFlag], s);
     HIP_TRY(hipGetLastError());
     if (!checked) {   // (the search is begun only behind this read-back: a bad id leaves the caller's buffers untouched)
-        uint32_t bad = 0;
-        HIP_TRY(hipMemcpyAsync(&bad, &idx->flags[kByidFlag], 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (bad) {
-            HIP_TRY(hipMemsetAsync(&idx->flags[kByidFlag], 0, 4, s));
-            HIP_TRY(hipStreamSynchronize(s));
+        uint32_t bad;
+        VROD_TRY(take_flag(idx, kByidFlag, s, &bad));
+        if (bad)
             return fail(VROD_ERR_INVALID_ARG, "an id is not a live row of this handle (ids %llu..%llu, deleted rows excluded)",
                         (unsigned long long)idx->id_offset, (unsigned long long)(idx->id_offset + idx->count));
-        }
     }
     VROD_TRY(byid_search_begin(idx, P.q_raw.as<float>(), nq, k1, l_ids, l_scores));
     VROD_TRY(search_end(idx));
@@ -3402,10 +3408,9 @@ static int combined_search(vrod_index* idx, const CombineArgs& a, const CombineC
     uint64_t* l_ids = d_out_ids;
     float* l_scores = d_out_scores;
     if (staged) {
-        VROD_TRY(idx->cmb_ids.ensure((size_t)nq * k1 * 8));
-        VROD_TRY(idx->cmb_scores.ensure((size_t)nq * k1 * 4));
-        l_ids = idx->cmb_ids.as<uint64_t>();
-        l_scores = idx->cmb_scores.as<float>();
+        VROD_TRY(grow_lists(idx, 0, (size_t)nq * k1));
+        l_ids = idx->list_ids[0].as<uint64_t>();
+        l_scores = idx->list_scores[0].as<float>();
     }
     if (a.d_vectors) VROD_TRY(prep_queries_checked(idx, P, a.d_vectors, nq));   // -> P.q_f32 [nq][ld]; NaN / Inf fails here
     VROD_TRY(P.q_raw.ensure((size_t)nq * idx->dim * 4));
@@ -3413,12 +3418,9 @@ static int combined_search(vrod_index* idx, const CombineArgs& a, const CombineC
                            a.d_vectors ? P.q_f32.as<float>() : nullptr, a.d_vector_weights, a.d_term_lims, a.d_term_ids, a.d_term_weights, nq,
                            P.q_raw.as<float>(), &idx->flags[kCombineFlag], s);
     HIP_TRY(hipGetLastError());
-    uint32_t bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, &idx->flags[kCombineFlag], 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    uint32_t bad;
+    VROD_TRY(take_flag(idx, kCombineFlag, s, &bad));
     if (bad) {
-        HIP_TRY(hipMemsetAsync(&idx->flags[kCombineFlag], 0, 4, s));
-        HIP_TRY(hipStreamSynchronize(s));
         if (bad & kCombineBadId)
             return fail(VROD_ERR_INVALID_ARG, "a term id is not a live row of this handle (ids %llu..%llu, deleted rows excluded)",
                         (unsigned long long)idx->id_offset, (unsigned long long)(idx->id_offset + idx->count));
@@ -3586,8 +3588,7 @@ static int knn_graph(vrod_index* idx, uint64_t row0, uint64_t n, uint32_t k, uin
         if (!F.live) return VROD_OK;   // nothing to search: the batch's rows are written unfilled
         Pending& P = next_slot(idx);
         F.stream = P.stream;
-        VROD_TRY(idx->byid_ids[c].ensure((size_t)F.live * k1 * 8));
-        VROD_TRY(idx->byid_scores[c].ensure((size_t)F.live * k1 * 4));
+        VROD_TRY(grow_lists(idx, (int)c, (size_t)F.live * k1));
         VROD_TRY(P.q_raw.ensure((size_t)F.live * idx->dim * 4));
         const uint32_t* d_rows = nullptr;
         if (F.holes) {
@@ -3598,7 +3599,7 @@ static int knn_graph(vrod_index* idx, uint64_t row0, uint64_t n, uint32_t k, uin
         launch_byid_gather(idx->corpus, idx->dtype, idx->ld, idx->dim, idx->count, idx->id_offset, nullptr, nullptr, d_rows, r0, F.live,
                            P.q_raw.as<float>(), nullptr, P.stream);   // (the range and the tombstones were checked on the host)
         HIP_TRY(hipGetLastError());
-        return byid_search_begin(idx, P.q_raw.as<float>(), F.live, k1, idx->byid_ids[c].as<uint64_t>(), idx->byid_scores[c].as<float>());
+        return byid_search_begin(idx, P.q_raw.as<float>(), F.live, k1, idx->list_ids[c].as<uint64_t>(), idx->list_scores[c].as<float>());
     };
     auto finish = [&](const Flight& F) -> int {
         const uint32_t m = F.b.rows, c = F.b.slot;
@@ -3618,7 +3619,7 @@ static int knn_graph(vrod_index* idx, uint64_t row0, uint64_t n, uint32_t k, uin
         // on the stream of the search just completed (the other slot's is scanning the next batch); a batch without a
         // search has no slot: the handle's own stream
         if (F.live)
-            launch_byid_drop_self(idx->byid_ids[c].as<uint64_t>(), idx->byid_scores[c].as<float>(), k1, F.holes ? map_of(F) + m : nullptr, nullptr,
+            launch_byid_drop_self(idx->list_ids[c].as<uint64_t>(), idx->list_scores[c].as<float>(), k1, F.holes ? map_of(F) + m : nullptr, nullptr,
                                   idx->id_offset + row0 + F.b.first, m, k, d_oi, d_os, F.stream);
         else
             launch_fill_none(d_oi, d_os, (uint64_t)m * k, F.stream);
@@ -3728,11 +3729,12 @@ int vrod_index_create(vrod_index** out, uint32_t dim, int dtype, int metric, con
     return VROD_OK;
 }
 
+// Orders the teardown; the handle's buffers free themselves when it is deleted, under the device set just before.
 int vrod_index_destroy(vrod_index* idx) {
     if (!idx) return VROD_OK;
     if (idx->composite()) {
         while (idx->n_pending()) (void)composite_end(idx, nullptr, nullptr);   // a begun search is ended before its buffers go
-        for (size_t g = 0; g < idx->shards.size(); ++g) {
+        for (size_t g = 0; g < idx->shards.size(); ++g) {   // (buffers on the shards' devices: released under them)
             (void)hipSetDevice(idx->shards[g]->device);
             for (int c = 0; c < 2; ++c)
                 if (g < idx->sh_q[c].size()) idx->sh_q[c][g].release();
@@ -3744,12 +3746,10 @@ int vrod_index_destroy(vrod_index* idx) {
             for (int c = 0; c < 2; ++c) { D.send[c].release(); D.recv[c].release(); }
             if (D.xstream) (void)hipStreamDestroy(D.xstream);
         }
+        for (vrod_index* sh : idx->shards) vrod_index_destroy(sh);
         (void)hipSetDevice(idx->device);
         if (idx->caller_ev) (void)hipEventDestroy(idx->caller_ev);
         for (auto& CP : idx->cslot) if (CP.caller_ev) (void)hipEventDestroy(CP.caller_ev);
-        idx->out_ids.release(); idx->out_scores.release(); idx->raw_stage.release();
-        idx->range_pool.release(); idx->range_pool_b.release(); idx->range_small.release();
-        for (vrod_index* sh : idx->shards) vrod_index_destroy(sh);
         delete idx;
         return VROD_OK;
     }
@@ -3757,43 +3757,25 @@ int vrod_index_destroy(vrod_index* idx) {
     if (idx->stream) (void)hipStreamSynchronize(idx->stream);
     for (Pending& P : idx->slot)
         if (P.stream) (void)hipStreamSynchronize(P.stream);
-    for (DevBuf* b : {&idx->raw_stage, &idx->nrm_ws, &idx->out_ids, &idx->out_scores, &idx->range_pool, &idx->range_pool_b, &idx->range_small,
-                      &idx->upd_stage, &idx->upd_dst, &idx->compact_ws}) b->release();
     for (Pending& P : idx->slot) {
-        for (DevBuf* b : {&P.q_raw, &P.q_lp, &P.scores, &P.keys_a, &P.keys_b, &P.lists, &P.small, &P.hist, &P.cand_rows, &P.cand_fast, &P.cand_canon})
-            b->release();
         if (P.flags) (void)hipFree(P.flags);
         if (P.stream) (void)hipStreamDestroy(P.stream);
-        P.q_f32.release();
-        P.q_planes.release();
-        P.dump.release();
-        for (DevBuf* b : {&P.band_idx, &P.band_q, &P.band_q_lp, &P.band_planes, &P.band_small, &P.band_ids, &P.band_scores}) b->release();
         if (P.gexec) (void)hipGraphExecDestroy(P.gexec);
         for (hipEvent_t e : P.ev) (void)hipEventDestroy(e);
-        for (auto& T : idx->tail_ev) { if (T.start) (void)hipEventDestroy(T.start); if (T.stop) (void)hipEventDestroy(T.stop); T = {}; }
         if (P.done) (void)hipEventDestroy(P.done);
         if (P.scans_done) (void)hipEventDestroy(P.scans_done);
         if (P.mid_done) (void)hipEventDestroy(P.mid_done);
         if (P.h_readback) (void)hipHostFree(P.h_readback);
     }
+    for (auto& T : idx->tail_ev) { if (T.start) (void)hipEventDestroy(T.start); if (T.stop) (void)hipEventDestroy(T.stop); }
     if (idx->caller_ev) (void)hipEventDestroy(idx->caller_ev);
     if (idx->corpus) (void)hipFree(idx->corpus);
     if (idx->planes) (void)hipFree(idx->planes);
     if (idx->xnorm2) (void)hipFree(idx->xnorm2);
     if (idx->del_dev) (void)hipFree(idx->del_dev);
     if (idx->eff_dev) (void)hipFree(idx->eff_dev);
-    idx->list_dev.release();
     if (idx->lab_dev) (void)hipFree(idx->lab_dev);
     if (idx->tag_dev) (void)hipFree(idx->tag_dev);
-    for (DevBuf* b : {&idx->lab_tab, &idx->lab_cnt, &idx->lab_lists, &idx->lab_slots, &idx->lab_entries, &idx->lab_mask, &idx->lab_q, &idx->lab_ids,
-                      &idx->lab_scores, &idx->lab_qraw, &idx->grp_ids, &idx->grp_scores, &idx->grp_small, &idx->grp_mask, &idx->grp_labels,
-                      &idx->grp_qraw, &idx->byid_user_ids, &idx->doc_rank, &idx->doc_labels, &idx->mv_q, &idx->mv_ids, &idx->mv_scores, &idx->mv_ent,
-                      &idx->mv_tab, &idx->mv_cand, &idx->mv_small, &idx->mv_best, &idx->mv_S, &idx->mv_absent, &idx->mv_M, &idx->mv_pairs,
-                      &idx->mv_raw, &idx->mv_lims, &idx->mv_out_labels, &idx->mv_out_scores, &idx->mv_found, &idx->dv_ids, &idx->dv_scores,
-                      &idx->dv_qraw, &idx->dv_mmr, &idx->cmb_ids, &idx->cmb_scores, &idx->cmb_vec, &idx->cmb_args, &idx->cand_rows,
-                      &idx->cand_small, &idx->cand_args, &idx->cand_qraw}) b->release();
-    for (int c = 0; c < 2; ++c)
-        for (DevBuf* b : {&idx->byid_ids[c], &idx->byid_scores[c], &idx->byid_out_ids[c], &idx->byid_out_scores[c], &idx->byid_map[c]}) b->release();
     if (idx->flags) (void)hipFree(idx->flags);
     if (idx->stream) (void)hipStreamDestroy(idx->stream);
     delete idx;
@@ -3973,6 +3955,52 @@ static int check_search_args(vrod_index* idx, const void* q, uint32_t nq, uint32
     return VROD_OK;
 }
 
+// The arguments of a derived search, refused in this order: a null handle; a null pointer of `first` (all are needed once
+// nq is not zero); k, where the call has one that is checked here; a null pointer of `then`; a composite handle, as
+// "<what> on a multi-device handle: <why_not>".
+static const char kLabelsNotRouted[] = "labels are not routed to the shards", kTagsNotRouted[] = "tags are not routed to the shards",
+                  kRowsNotGathered[] = "stored rows are not gathered across the shards",
+                  kCandidatesNotRouted[] = "candidate ids are not routed to the shards";
+static int check_derived_args(vrod_index* idx, const char* what, const char* why_not, uint32_t nq, std::initializer_list<const void*> first,
+                              bool has_k, uint32_t k, std::initializer_list<const void*> then = {}) {
+    if (!idx) return fail(VROD_ERR_INVALID_ARG, "idx is null");
+    for (const void* p : first)
+        if (nq && !p) return fail(VROD_ERR_INVALID_ARG, "null buffer");
+    if (has_k && (k == 0 || k > VROD_MAX_K)) return fail(VROD_ERR_INVALID_ARG, "k must be in 1..%u", VROD_MAX_K);
+    for (const void* p : then)
+        if (nq && !p) return fail(VROD_ERR_INVALID_ARG, "null buffer");
+    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "%s on a multi-device handle: %s", what, why_not);
+    return VROD_OK;
+}
+
+// What the host form of a derived search starts with: the handle idle, its device current, the caller's n raw vectors
+// in host_q (vecs null: room for them, nothing copied) and the handle's top-k result rows grown (k = 0: the call has
+// none); copy_topk_out ends it.  A form that validates host arrays behind the idle check makes that check itself first.
+static int begin_host_form(vrod_index* idx, const char* what, const float* vecs, size_t n, uint32_t nq, uint32_t k) {
+    VROD_TRY(require_idle(idx, what));
+    VROD_TRY(set_device(idx));
+    VROD_TRY(idx->host_q.ensure(n * idx->dim * 4));
+    if (k) VROD_TRY(grow_topk_out(idx, nq, k));
+    if (vecs && n) HIP_TRY(hipMemcpy(idx->host_q.p, vecs, n * idx->dim * 4, hipMemcpyHostToDevice));
+    return VROD_OK;
+}
+
+// A device form's lims array [nq + 1], read to the host.
+static int read_lims(const uint32_t* d_lims, uint32_t nq, std::vector<uint32_t>& lims) {
+    lims.resize((size_t)nq + 1);
+    HIP_TRY(hipMemcpy(lims.data(), d_lims, lims.size() * 4, hipMemcpyDeviceToHost));
+    return VROD_OK;
+}
+
+// `id` names a live row of this handle (kind: what the message calls it).  The host mirror of the tombstones is the
+// truth: a host form launches nothing for a bad id.
+static int check_live_id(const vrod_index* idx, uint64_t id, const char* kind) {
+    if (id < idx->id_offset || id - idx->id_offset >= idx->count || bit_of(idx->del_bits.data(), id - idx->id_offset))
+        return fail(VROD_ERR_INVALID_ARG, "%s %llu is not a live row of this handle (ids %llu..%llu, deleted rows excluded)", kind,
+                    (unsigned long long)id, (unsigned long long)idx->id_offset, (unsigned long long)(idx->id_offset + idx->count));
+    return VROD_OK;
+}
+
 int vrod_search_device(vrod_index* idx, const float* d_queries, uint32_t nq, uint32_t k,
                        uint64_t* d_out_ids, float* d_out_scores, void* stream) {
     VROD_TRY(check_search_args(idx, d_queries, nq, k, d_out_ids, d_out_scores));
@@ -4085,22 +4113,15 @@ int vrod_index_get_labels(vrod_index* idx, uint64_t first_id, uint64_t n, uint32
 }
 
 static int check_labeled_args(vrod_index* idx, const void* q, uint32_t nq, uint32_t k, const void* labels, const void* oi, const void* os) {
-    VROD_TRY(check_search_args(idx, q, nq, k, oi, os));
-    if (nq && !labels) return fail(VROD_ERR_INVALID_ARG, "null buffer");
-    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "vrod_search_labeled on a multi-device handle: labels are not routed to the shards");
-    return VROD_OK;
+    return check_derived_args(idx, "vrod_search_labeled", kLabelsNotRouted, nq, {q, oi, os}, true, k, {labels});
 }
 
 int vrod_search_labeled(vrod_index* idx, const float* queries, uint32_t nq, uint32_t k, const uint32_t* query_labels,
                         uint64_t* out_ids, float* out_scores) {
     VROD_TRY(check_labeled_args(idx, queries, nq, k, query_labels, out_ids, out_scores));
     if (!nq) return VROD_OK;
-    VROD_TRY(require_idle(idx, "vrod_search_labeled"));
-    VROD_TRY(set_device(idx));
-    VROD_TRY(idx->lab_qraw.ensure((size_t)nq * idx->dim * 4));
-    VROD_TRY(grow_topk_out(idx, nq, k));
-    HIP_TRY(hipMemcpy(idx->lab_qraw.p, queries, (size_t)nq * idx->dim * 4, hipMemcpyHostToDevice));
-    VROD_TRY(labeled_search(idx, idx->lab_qraw.as<float>(), nq, k, query_labels, idx->out_ids.as<uint64_t>(), idx->out_scores.as<float>()));
+    VROD_TRY(begin_host_form(idx, "vrod_search_labeled", queries, nq, nq, k));
+    VROD_TRY(labeled_search(idx, idx->host_q.as<float>(), nq, k, query_labels, idx->out_ids.as<uint64_t>(), idx->out_scores.as<float>()));
     return copy_topk_out(idx, nq, k, out_ids, out_scores);
 }
 
@@ -4146,22 +4167,15 @@ int vrod_index_get_tags(vrod_index* idx, uint64_t first_id, uint64_t n, uint64_t
 static_assert(sizeof(vrod_tag_pred) == 24 && sizeof(TagPred) == 24, "vrod_tag_pred is three packed 64-bit words");
 
 static int check_tagged_args(vrod_index* idx, const void* q, uint32_t nq, uint32_t k, const void* preds, const void* oi, const void* os) {
-    VROD_TRY(check_search_args(idx, q, nq, k, oi, os));
-    if (nq && !preds) return fail(VROD_ERR_INVALID_ARG, "null buffer");
-    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "vrod_search_tagged on a multi-device handle: tags are not routed to the shards");
-    return VROD_OK;
+    return check_derived_args(idx, "vrod_search_tagged", kTagsNotRouted, nq, {q, oi, os}, true, k, {preds});
 }
 
 int vrod_search_tagged(vrod_index* idx, const float* queries, uint32_t nq, uint32_t k, const vrod_tag_pred* preds, uint64_t* out_ids,
                        float* out_scores) {
     VROD_TRY(check_tagged_args(idx, queries, nq, k, preds, out_ids, out_scores));
     if (!nq) return VROD_OK;
-    VROD_TRY(require_idle(idx, "vrod_search_tagged"));
-    VROD_TRY(set_device(idx));
-    VROD_TRY(idx->lab_qraw.ensure((size_t)nq * idx->dim * 4));
-    VROD_TRY(grow_topk_out(idx, nq, k));
-    if (idx->count) HIP_TRY(hipMemcpy(idx->lab_qraw.p, queries, (size_t)nq * idx->dim * 4, hipMemcpyHostToDevice));
-    VROD_TRY(tagged_search(idx, idx->lab_qraw.as<float>(), nq, k, reinterpret_cast<const TagPred*>(preds), idx->out_ids.as<uint64_t>(),
+    VROD_TRY(begin_host_form(idx, "vrod_search_tagged", idx->count ? queries : nullptr, nq, nq, k));   // (an empty handle reads none)
+    VROD_TRY(tagged_search(idx, idx->host_q.as<float>(), nq, k, reinterpret_cast<const TagPred*>(preds), idx->out_ids.as<uint64_t>(),
                            idx->out_scores.as<float>()));
     return copy_topk_out(idx, nq, k, out_ids, out_scores);
 }
@@ -4177,25 +4191,19 @@ int vrod_search_tagged_device(vrod_index* idx, const float* d_queries, uint32_t 
 }
 
 static int check_grouped_args(vrod_index* idx, const void* q, uint32_t nq, uint32_t k, const void* oi, const void* os) {
-    VROD_TRY(check_search_args(idx, q, nq, k, oi, os));
-    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "vrod_search_grouped on a multi-device handle: labels are not routed to the shards");
-    return VROD_OK;
+    return check_derived_args(idx, "vrod_search_grouped", kLabelsNotRouted, nq, {q, oi, os}, true, k);
 }
 
 int vrod_search_grouped(vrod_index* idx, const float* queries, uint32_t nq, uint32_t k, uint64_t* out_ids, float* out_scores,
                         uint32_t* out_labels) {
     VROD_TRY(check_grouped_args(idx, queries, nq, k, out_ids, out_scores));
     if (!nq) return VROD_OK;
-    VROD_TRY(require_idle(idx, "vrod_search_grouped"));
-    VROD_TRY(set_device(idx));
-    VROD_TRY(idx->grp_qraw.ensure((size_t)nq * idx->dim * 4));
-    VROD_TRY(grow_topk_out(idx, nq, k));
-    VROD_TRY(idx->grp_labels.ensure((size_t)nq * k * 4));
-    HIP_TRY(hipMemcpy(idx->grp_qraw.p, queries, (size_t)nq * idx->dim * 4, hipMemcpyHostToDevice));
-    VROD_TRY(grouped_search(idx, idx->grp_qraw.as<float>(), nq, k, idx->out_ids.as<uint64_t>(), idx->out_scores.as<float>(),
-                            idx->grp_labels.as<uint32_t>()));
+    VROD_TRY(begin_host_form(idx, "vrod_search_grouped", queries, nq, nq, k));
+    VROD_TRY(idx->out_col.ensure((size_t)nq * k * 4));
+    VROD_TRY(grouped_search(idx, idx->host_q.as<float>(), nq, k, idx->out_ids.as<uint64_t>(), idx->out_scores.as<float>(),
+                            idx->out_col.as<uint32_t>()));
     VROD_TRY(copy_topk_out(idx, nq, k, out_ids, out_scores));
-    if (out_labels) HIP_TRY(hipMemcpy(out_labels, idx->grp_labels.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    if (out_labels) HIP_TRY(hipMemcpy(out_labels, idx->out_col.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
     return VROD_OK;
 }
 
@@ -4205,17 +4213,14 @@ int vrod_search_grouped_device(vrod_index* idx, const float* d_queries, uint32_t
     if (!nq) return VROD_OK;
     VROD_TRY(begin_sync_device(idx, "vrod_search_grouped_device", stream));
     if (!d_out_labels) {   // the de-duplication keeps each query's taken labels there
-        VROD_TRY(idx->grp_labels.ensure((size_t)nq * k * 4));
-        d_out_labels = idx->grp_labels.as<uint32_t>();
+        VROD_TRY(idx->out_col.ensure((size_t)nq * k * 4));
+        d_out_labels = idx->out_col.as<uint32_t>();
     }
     return grouped_search(idx, d_queries, nq, k, d_out_ids, d_out_scores, d_out_labels);
 }
 
 static int check_multivec_args(vrod_index* idx, const void* v, const void* lims, uint32_t nq, uint32_t k, const void* ol, const void* os) {
-    VROD_TRY(check_search_args(idx, v, nq, k, ol, os));
-    if (nq && !lims) return fail(VROD_ERR_INVALID_ARG, "null buffer");
-    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "vrod_search_multivec on a multi-device handle: labels are not routed to the shards");
-    return VROD_OK;
+    return check_derived_args(idx, "vrod_search_multivec", kLabelsNotRouted, nq, {v, ol, os}, true, k, {lims});
 }
 
 static int check_multivec_lims(const uint32_t* lims, uint32_t nq) {
@@ -4234,18 +4239,14 @@ int vrod_search_multivec(vrod_index* idx, const float* vectors, const uint32_t* 
     if (!nq) return VROD_OK;
     VROD_TRY(require_idle(idx, "vrod_search_multivec"));
     VROD_TRY(check_multivec_lims(query_lims, nq));
-    VROD_TRY(set_device(idx));
-    const size_t nv = query_lims[nq];
-    VROD_TRY(idx->mv_raw.ensure(nv * idx->dim * 4));
-    VROD_TRY(idx->mv_out_labels.ensure((size_t)nq * k * 4));
-    VROD_TRY(idx->mv_out_scores.ensure((size_t)nq * k * 4));
-    VROD_TRY(idx->mv_found.ensure((size_t)nq * 4));
-    HIP_TRY(hipMemcpy(idx->mv_raw.p, vectors, nv * idx->dim * 4, hipMemcpyHostToDevice));
-    VROD_TRY(multivec_search(idx, idx->mv_raw.as<float>(), query_lims, nq, k, idx->mv_out_labels.as<uint32_t>(), idx->mv_out_scores.as<float>(),
-                             idx->mv_found.as<uint32_t>()));
-    HIP_TRY(hipMemcpy(out_labels, idx->mv_out_labels.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_scores, idx->mv_out_scores.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
-    if (out_found) HIP_TRY(hipMemcpy(out_found, idx->mv_found.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
+    VROD_TRY(begin_host_form(idx, "vrod_search_multivec", vectors, query_lims[nq], nq, k));
+    VROD_TRY(idx->out_col.ensure((size_t)nq * k * 4));
+    VROD_TRY(idx->out_found.ensure((size_t)nq * 4));
+    VROD_TRY(multivec_search(idx, idx->host_q.as<float>(), query_lims, nq, k, idx->out_col.as<uint32_t>(), idx->out_scores.as<float>(),
+                             idx->out_found.as<uint32_t>()));
+    HIP_TRY(hipMemcpy(out_labels, idx->out_col.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_scores, idx->out_scores.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    if (out_found) HIP_TRY(hipMemcpy(out_found, idx->out_found.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
     return VROD_OK;
 }
 
@@ -4254,12 +4255,12 @@ int vrod_search_multivec_device(vrod_index* idx, const float* d_vectors, const u
     VROD_TRY(check_multivec_args(idx, d_vectors, d_query_lims, nq, k, d_out_labels, d_out_scores));
     if (!nq) return VROD_OK;
     VROD_TRY(begin_sync_device(idx, "vrod_search_multivec_device", stream));
-    std::vector<uint32_t> lims((size_t)nq + 1);
-    HIP_TRY(hipMemcpy(lims.data(), d_query_lims, lims.size() * 4, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> lims;
+    VROD_TRY(read_lims(d_query_lims, nq, lims));
     VROD_TRY(check_multivec_lims(lims.data(), nq));
     if (!d_out_found) {
-        VROD_TRY(idx->mv_found.ensure((size_t)nq * 4));
-        d_out_found = idx->mv_found.as<uint32_t>();
+        VROD_TRY(idx->out_found.ensure((size_t)nq * 4));
+        d_out_found = idx->out_found.as<uint32_t>();
     }
     return multivec_search(idx, d_vectors, lims.data(), nq, k, d_out_labels, d_out_scores, d_out_found);
 }
@@ -4280,26 +4281,19 @@ static int check_diverse_args(vrod_index* idx, const void* q, uint32_t nq, uint3
         case 3: return fail(VROD_ERR_INVALID_ARG, "pool must be at most %u", VROD_MAX_DIVERSE_POOL);
         default: return fail(VROD_ERR_INVALID_ARG, "lambda must be in [0, 1]");
     }
-    if (!idx) return fail(VROD_ERR_INVALID_ARG, "idx is null");
-    if (nq && (!q || !oi || !os)) return fail(VROD_ERR_INVALID_ARG, "null buffer");
-    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "vrod_search_diverse on a multi-device handle: stored rows are not gathered across the shards");
-    return VROD_OK;
+    return check_derived_args(idx, "vrod_search_diverse", kRowsNotGathered, nq, {q, oi, os}, false, 0);
 }
 
 int vrod_search_diverse(vrod_index* idx, const float* queries, uint32_t nq, uint32_t k, uint32_t pool, float lambda, uint64_t* out_ids,
                         float* out_scores, float* out_mmr) {
     VROD_TRY(check_diverse_args(idx, queries, nq, k, pool, lambda, out_ids, out_scores));
     if (!nq) return VROD_OK;
-    VROD_TRY(require_idle(idx, "vrod_search_diverse"));
-    VROD_TRY(set_device(idx));
-    VROD_TRY(idx->dv_qraw.ensure((size_t)nq * idx->dim * 4));
-    VROD_TRY(grow_topk_out(idx, nq, k));
-    VROD_TRY(idx->dv_mmr.ensure((size_t)nq * k * 4));
-    HIP_TRY(hipMemcpy(idx->dv_qraw.p, queries, (size_t)nq * idx->dim * 4, hipMemcpyHostToDevice));
-    VROD_TRY(diverse_search(idx, idx->dv_qraw.as<float>(), nq, k, pool, lambda, idx->out_ids.as<uint64_t>(), idx->out_scores.as<float>(),
-                            idx->dv_mmr.as<float>()));
+    VROD_TRY(begin_host_form(idx, "vrod_search_diverse", queries, nq, nq, k));
+    VROD_TRY(idx->out_col.ensure((size_t)nq * k * 4));
+    VROD_TRY(diverse_search(idx, idx->host_q.as<float>(), nq, k, pool, lambda, idx->out_ids.as<uint64_t>(), idx->out_scores.as<float>(),
+                            idx->out_col.as<float>()));
     VROD_TRY(copy_topk_out(idx, nq, k, out_ids, out_scores));
-    if (out_mmr) HIP_TRY(hipMemcpy(out_mmr, idx->dv_mmr.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    if (out_mmr) HIP_TRY(hipMemcpy(out_mmr, idx->out_col.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
     return VROD_OK;
 }
 
@@ -4317,27 +4311,18 @@ static int check_byid_args(vrod_index* idx, const void* ids, uint32_t nq, uint32
     if (flags & ~(uint32_t)VROD_BYID_EXCLUDE_SELF) return fail(VROD_ERR_INVALID_ARG, "unknown flag bits 0x%x", flags);
     if (!byid_k_ok(k, flags & VROD_BYID_EXCLUDE_SELF))
         return fail(VROD_ERR_INVALID_ARG, "k must be in 1..%u (1..%u with the self drop)", VROD_MAX_K, VROD_MAX_K - 1);
-    if (!idx) return fail(VROD_ERR_INVALID_ARG, "idx is null");
-    if (nq && (!ids || !oi || !os)) return fail(VROD_ERR_INVALID_ARG, "null buffer");
-    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "%s on a multi-device handle: stored rows are not gathered across the shards", what);
-    return VROD_OK;
+    return check_derived_args(idx, what, kRowsNotGathered, nq, {ids, oi, os}, false, 0);
 }
 
 int vrod_search_by_ids(vrod_index* idx, const uint64_t* ids, uint32_t nq, uint32_t k, uint32_t flags, uint64_t* out_ids, float* out_scores) {
     VROD_TRY(check_byid_args(idx, ids, nq, k, flags, out_ids, out_scores, "vrod_search_by_ids"));
     if (!nq) return VROD_OK;
     VROD_TRY(require_idle(idx, "vrod_search_by_ids"));
-    for (uint32_t q = 0; q < nq; ++q) {   // the host mirror of the tombstones is the truth: nothing is launched for a bad id
-        const uint64_t id = ids[q];
-        if (id < idx->id_offset || id - idx->id_offset >= idx->count || bit_of(idx->del_bits.data(), id - idx->id_offset))
-            return fail(VROD_ERR_INVALID_ARG, "id %llu is not a live row of this handle (ids %llu..%llu, deleted rows excluded)", (unsigned long long)id,
-                        (unsigned long long)idx->id_offset, (unsigned long long)(idx->id_offset + idx->count));
-    }
-    VROD_TRY(set_device(idx));
-    VROD_TRY(idx->byid_user_ids.ensure((size_t)nq * 8));
-    VROD_TRY(grow_topk_out(idx, nq, k));
-    HIP_TRY(hipMemcpy(idx->byid_user_ids.p, ids, (size_t)nq * 8, hipMemcpyHostToDevice));
-    VROD_TRY(byid_search(idx, idx->byid_user_ids.as<uint64_t>(), true, nq, k, flags & VROD_BYID_EXCLUDE_SELF, idx->out_ids.as<uint64_t>(),
+    for (uint32_t q = 0; q < nq; ++q) VROD_TRY(check_live_id(idx, ids[q], "id"));
+    VROD_TRY(begin_host_form(idx, "vrod_search_by_ids", nullptr, 0, nq, k));
+    VROD_TRY(idx->host_args.ensure((size_t)nq * 8));
+    HIP_TRY(hipMemcpy(idx->host_args.p, ids, (size_t)nq * 8, hipMemcpyHostToDevice));
+    VROD_TRY(byid_search(idx, idx->host_args.as<uint64_t>(), true, nq, k, flags & VROD_BYID_EXCLUDE_SELF, idx->out_ids.as<uint64_t>(),
                          idx->out_scores.as<float>()));
     return copy_topk_out(idx, nq, k, out_ids, out_scores);
 }
@@ -4358,10 +4343,7 @@ static int check_combined_args(vrod_index* idx, const void* term_lims, uint32_t 
         case 1: return fail(VROD_ERR_INVALID_ARG, "unknown flag bits 0x%x", flags);
         default: return fail(VROD_ERR_INVALID_ARG, "k must be in 1..%u", VROD_MAX_K);
     }
-    if (!idx) return fail(VROD_ERR_INVALID_ARG, "idx is null");
-    if (nq && (!term_lims || !oi || !os)) return fail(VROD_ERR_INVALID_ARG, "null buffer");
-    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "%s on a multi-device handle: stored rows are not gathered across the shards", what);
-    return VROD_OK;
+    return check_derived_args(idx, what, kRowsNotGathered, nq, {term_lims, oi, os}, false, 0);
 }
 
 // The two lims arrays (host copies; excl_lims may be null) against combine_plan.h, and the pointers their totals require.
@@ -4391,23 +4373,20 @@ int vrod_search_combined(vrod_index* idx, const float* vectors, const float* vec
     CombineCounts counts;
     VROD_TRY(check_combined_batch(term_lims, term_ids, term_weights, exclude_lims, exclude_ids, vectors != nullptr, nq, k, flags, &counts));
     const uint32_t T = term_lims[nq], X = exclude_lims ? exclude_lims[nq] : 0u;
-    for (uint32_t t = 0; t < T; ++t) {   // the host mirror of the tombstones is the truth: nothing is launched for a bad id
-        const uint64_t id = term_ids[t];
-        if (id < idx->id_offset || id - idx->id_offset >= idx->count || bit_of(idx->del_bits.data(), id - idx->id_offset))
-            return fail(VROD_ERR_INVALID_ARG, "term id %llu is not a live row of this handle (ids %llu..%llu, deleted rows excluded)",
-                        (unsigned long long)id, (unsigned long long)idx->id_offset, (unsigned long long)(idx->id_offset + idx->count));
+    for (uint32_t t = 0; t < T; ++t) {
+        VROD_TRY(check_live_id(idx, term_ids[t], "term id"));
         if (!std::isfinite(term_weights[t])) return fail(VROD_ERR_INVALID_VALUE, "term weight %u is NaN or Inf", t);
     }
     if (vectors && vector_weights)
         for (uint32_t q = 0; q < nq; ++q)
             if (!std::isfinite(vector_weights[q])) return fail(VROD_ERR_INVALID_VALUE, "vector weight %u is NaN or Inf", q);
-    VROD_TRY(set_device(idx));
+    VROD_TRY(begin_host_form(idx, "vrod_search_combined", vectors, vectors ? nq : 0, nq, k));
     // the arguments on the device: [term ids | excluded ids | term weights | vector weights | term lims | exclude lims]
     const bool vw = vectors && vector_weights;
     const size_t o_tid = 0, o_xid = o_tid + (size_t)T * 8, o_tw = o_xid + (size_t)X * 8, o_vw = o_tw + (size_t)T * 4,
                  o_tl = o_vw + (vw ? (size_t)nq * 4 : 0), o_xl = o_tl + ((size_t)nq + 1) * 4, bytes = o_xl + (exclude_lims ? ((size_t)nq + 1) * 4 : 0);
-    VROD_TRY(idx->cmb_args.ensure(bytes));
-    char* base = idx->cmb_args.as<char>();
+    VROD_TRY(idx->host_args.ensure(bytes));
+    char* base = idx->host_args.as<char>();
     if (T) {
         HIP_TRY(hipMemcpy(base + o_tid, term_ids, (size_t)T * 8, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(base + o_tw, term_weights, (size_t)T * 4, hipMemcpyHostToDevice));
@@ -4416,19 +4395,14 @@ int vrod_search_combined(vrod_index* idx, const float* vectors, const float* vec
     if (vw) HIP_TRY(hipMemcpy(base + o_vw, vector_weights, (size_t)nq * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(base + o_tl, term_lims, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice));
     if (exclude_lims) HIP_TRY(hipMemcpy(base + o_xl, exclude_lims, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice));
-    if (vectors) {
-        VROD_TRY(idx->cmb_vec.ensure((size_t)nq * idx->dim * 4));
-        HIP_TRY(hipMemcpy(idx->cmb_vec.p, vectors, (size_t)nq * idx->dim * 4, hipMemcpyHostToDevice));
-    }
     CombineArgs a{};
-    a.d_vectors = vectors ? idx->cmb_vec.as<float>() : nullptr;
+    a.d_vectors = vectors ? idx->host_q.as<float>() : nullptr;
     a.d_vector_weights = vw ? (const float*)(base + o_vw) : nullptr;
     a.d_term_lims = (const uint32_t*)(base + o_tl);
     a.d_term_ids = (const uint64_t*)(base + o_tid);
     a.d_term_weights = (const float*)(base + o_tw);
     a.d_excl_lims = exclude_lims ? (const uint32_t*)(base + o_xl) : nullptr;
     a.d_excl_ids = (const uint64_t*)(base + o_xid);
-    VROD_TRY(grow_topk_out(idx, nq, k));
     VROD_TRY(combined_search(idx, a, counts, nq, k, flags, idx->out_ids.as<uint64_t>(), idx->out_scores.as<float>()));
     return copy_topk_out(idx, nq, k, out_ids, out_scores);
 }
@@ -4440,27 +4414,14 @@ int vrod_search_combined_device(vrod_index* idx, const float* d_vectors, const f
     VROD_TRY(check_combined_args(idx, d_term_lims, nq, k, flags, d_out_ids, d_out_scores, "vrod_search_combined_device"));
     if (!nq) return VROD_OK;
     VROD_TRY(begin_sync_device(idx, "vrod_search_combined_device", stream));
-    std::vector<uint32_t> tl((size_t)nq + 1), xl;
-    HIP_TRY(hipMemcpy(tl.data(), d_term_lims, tl.size() * 4, hipMemcpyDeviceToHost));
-    if (d_exclude_lims) {
-        xl.resize((size_t)nq + 1);
-        HIP_TRY(hipMemcpy(xl.data(), d_exclude_lims, xl.size() * 4, hipMemcpyDeviceToHost));
-    }
+    std::vector<uint32_t> tl, xl;
+    VROD_TRY(read_lims(d_term_lims, nq, tl));
+    if (d_exclude_lims) VROD_TRY(read_lims(d_exclude_lims, nq, xl));
     CombineCounts counts;
     VROD_TRY(check_combined_batch(tl.data(), d_term_ids, d_term_weights, d_exclude_lims ? xl.data() : nullptr, d_exclude_ids, d_vectors != nullptr,
                                   nq, k, flags, &counts));
     CombineArgs a{d_vectors, d_vectors ? d_vector_weights : nullptr, d_term_lims, d_term_ids, d_term_weights, d_exclude_lims, d_exclude_ids};
     return combined_search(idx, a, counts, nq, k, flags, d_out_ids, d_out_scores);
-}
-
-// k: the search form's (the score form has none: has_k false).  out: the ids of the search form, the scores of the score form.
-static int check_candidates_args(vrod_index* idx, const void* q, uint32_t nq, bool has_k, uint32_t k, const void* lims, const void* out,
-                                 const void* out2, const char* what) {
-    if (!idx) return fail(VROD_ERR_INVALID_ARG, "idx is null");
-    if (has_k && (k == 0 || k > VROD_MAX_K)) return fail(VROD_ERR_INVALID_ARG, "k must be in 1..%u", VROD_MAX_K);
-    if (nq && (!q || !lims || (has_k && (!out || !out2)))) return fail(VROD_ERR_INVALID_ARG, "null buffer");
-    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "%s on a multi-device handle: candidate ids are not routed to the shards", what);
-    return VROD_OK;
 }
 
 // The lims array (a host copy) against candidates_plan.h, and the pointers its total requires.
@@ -4475,16 +4436,14 @@ static int check_candidates_lists(const uint32_t* lims, uint32_t nq, const void*
     return VROD_OK;
 }
 
-// A host form's lists and raw queries on the device: cand_args as [ids | lims], cand_qraw.
-static int upload_candidates(vrod_index* idx, const float* queries, uint32_t nq, const uint32_t* lims, const uint64_t* ids,
-                             const uint64_t** d_ids, const uint32_t** d_lims) {
+// A host form's lists on the device: host_args as [ids | lims].
+static int upload_candidates(vrod_index* idx, uint32_t nq, const uint32_t* lims, const uint64_t* ids, const uint64_t** d_ids,
+                             const uint32_t** d_lims) {
     const size_t n = lims[nq], o_lims = n * 8;
-    VROD_TRY(idx->cand_args.ensure(o_lims + ((size_t)nq + 1) * 4));
-    VROD_TRY(idx->cand_qraw.ensure((size_t)nq * idx->dim * 4));
-    char* base = idx->cand_args.as<char>();
+    VROD_TRY(idx->host_args.ensure(o_lims + ((size_t)nq + 1) * 4));
+    char* base = idx->host_args.as<char>();
     if (n) HIP_TRY(hipMemcpy(base, ids, n * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(base + o_lims, lims, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(idx->cand_qraw.p, queries, (size_t)nq * idx->dim * 4, hipMemcpyHostToDevice));
     *d_ids = (const uint64_t*)base;
     *d_lims = (const uint32_t*)(base + o_lims);
     return VROD_OK;
@@ -4492,55 +4451,55 @@ static int upload_candidates(vrod_index* idx, const float* queries, uint32_t nq,
 
 int vrod_search_candidates(vrod_index* idx, const float* queries, uint32_t nq, uint32_t k, const uint32_t* cand_lims, const uint64_t* cand_ids,
                            uint64_t* out_ids, float* out_scores) {
-    VROD_TRY(check_candidates_args(idx, queries, nq, true, k, cand_lims, out_ids, out_scores, "vrod_search_candidates"));
+    VROD_TRY(check_derived_args(idx, "vrod_search_candidates", kCandidatesNotRouted, nq, {}, true, k, {queries, cand_lims, out_ids, out_scores}));
     if (!nq) return VROD_OK;
     VROD_TRY(require_idle(idx, "vrod_search_candidates"));
     VROD_TRY(check_candidates_lists(cand_lims, nq, cand_ids, out_scores));
-    VROD_TRY(set_device(idx));
+    VROD_TRY(begin_host_form(idx, "vrod_search_candidates", queries, nq, nq, k));
     const uint64_t* d_ids;
     const uint32_t* d_lims;
-    VROD_TRY(upload_candidates(idx, queries, nq, cand_lims, cand_ids, &d_ids, &d_lims));
-    VROD_TRY(grow_topk_out(idx, nq, k));
-    VROD_TRY(candidates_search(idx, idx->cand_qraw.as<float>(), nq, k, cand_lims, d_lims, d_ids, idx->out_ids.as<uint64_t>(),
+    VROD_TRY(upload_candidates(idx, nq, cand_lims, cand_ids, &d_ids, &d_lims));
+    VROD_TRY(candidates_search(idx, idx->host_q.as<float>(), nq, k, cand_lims, d_lims, d_ids, idx->out_ids.as<uint64_t>(),
                                idx->out_scores.as<float>()));
     return copy_topk_out(idx, nq, k, out_ids, out_scores);
 }
 
 int vrod_search_candidates_device(vrod_index* idx, const float* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_cand_lims,
                                   const uint64_t* d_cand_ids, uint64_t* d_out_ids, float* d_out_scores, void* stream) {
-    VROD_TRY(check_candidates_args(idx, d_queries, nq, true, k, d_cand_lims, d_out_ids, d_out_scores, "vrod_search_candidates_device"));
+    VROD_TRY(check_derived_args(idx, "vrod_search_candidates_device", kCandidatesNotRouted, nq, {}, true, k,
+                                {d_queries, d_cand_lims, d_out_ids, d_out_scores}));
     if (!nq) return VROD_OK;
     VROD_TRY(begin_sync_device(idx, "vrod_search_candidates_device", stream));
-    std::vector<uint32_t> lims((size_t)nq + 1);
-    HIP_TRY(hipMemcpy(lims.data(), d_cand_lims, lims.size() * 4, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> lims;
+    VROD_TRY(read_lims(d_cand_lims, nq, lims));
     VROD_TRY(check_candidates_lists(lims.data(), nq, d_cand_ids, d_out_scores));
     return candidates_search(idx, d_queries, nq, k, lims.data(), d_cand_lims, d_cand_ids, d_out_ids, d_out_scores);
 }
 
 int vrod_score_candidates(vrod_index* idx, const float* queries, uint32_t nq, const uint32_t* cand_lims, const uint64_t* cand_ids,
                           float* out_scores) {
-    VROD_TRY(check_candidates_args(idx, queries, nq, false, 0, cand_lims, nullptr, nullptr, "vrod_score_candidates"));
+    VROD_TRY(check_derived_args(idx, "vrod_score_candidates", kCandidatesNotRouted, nq, {}, false, 0, {queries, cand_lims}));
     if (!nq) return VROD_OK;
     VROD_TRY(require_idle(idx, "vrod_score_candidates"));
     VROD_TRY(check_candidates_lists(cand_lims, nq, cand_ids, out_scores));
-    VROD_TRY(set_device(idx));
+    VROD_TRY(begin_host_form(idx, "vrod_score_candidates", queries, nq, nq, 0));
     const uint64_t* d_ids;
     const uint32_t* d_lims;
-    VROD_TRY(upload_candidates(idx, queries, nq, cand_lims, cand_ids, &d_ids, &d_lims));
+    VROD_TRY(upload_candidates(idx, nq, cand_lims, cand_ids, &d_ids, &d_lims));
     const size_t n = cand_lims[nq];
     VROD_TRY(idx->out_scores.ensure(std::max<size_t>(n, 1) * 4));
-    VROD_TRY(candidates_score(idx, idx->cand_qraw.as<float>(), nq, cand_lims, d_lims, d_ids, idx->out_scores.as<float>()));
+    VROD_TRY(candidates_score(idx, idx->host_q.as<float>(), nq, cand_lims, d_lims, d_ids, idx->out_scores.as<float>()));
     if (n) HIP_TRY(hipMemcpy(out_scores, idx->out_scores.p, n * 4, hipMemcpyDeviceToHost));
     return VROD_OK;
 }
 
 int vrod_score_candidates_device(vrod_index* idx, const float* d_queries, uint32_t nq, const uint32_t* d_cand_lims, const uint64_t* d_cand_ids,
                                  float* d_out_scores, void* stream) {
-    VROD_TRY(check_candidates_args(idx, d_queries, nq, false, 0, d_cand_lims, nullptr, nullptr, "vrod_score_candidates_device"));
+    VROD_TRY(check_derived_args(idx, "vrod_score_candidates_device", kCandidatesNotRouted, nq, {}, false, 0, {d_queries, d_cand_lims}));
     if (!nq) return VROD_OK;
     VROD_TRY(begin_sync_device(idx, "vrod_score_candidates_device", stream));
-    std::vector<uint32_t> lims((size_t)nq + 1);
-    HIP_TRY(hipMemcpy(lims.data(), d_cand_lims, lims.size() * 4, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> lims;
+    VROD_TRY(read_lims(d_cand_lims, nq, lims));
     VROD_TRY(check_candidates_lists(lims.data(), nq, d_cand_ids, d_out_scores));
     return candidates_score(idx, d_queries, nq, lims.data(), d_cand_lims, d_cand_ids, d_out_scores);
 }
