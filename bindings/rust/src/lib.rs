@@ -62,6 +62,18 @@ pub struct vrod_tag_pred {
     pub none: u64,
 }
 
+/// One query's predicate of `vrod_search_where`: the tag clauses of `vrod_tag_pred` and `lo <= v && v <= hi` on the row's
+/// signed 64-bit value `v`, both ends inclusive.
+#[repr(C)]
+#[derive(Debug, Clone, Copy, PartialEq, Eq)]
+pub struct vrod_where {
+    pub any: u64,
+    pub all: u64,
+    pub none: u64,
+    pub lo: i64,
+    pub hi: i64,
+}
+
 /// The largest `pool` of `vrod_search_diverse`.
 pub const VROD_MAX_DIVERSE_POOL: u32 = 1024;
 
@@ -158,6 +170,13 @@ extern "C" {
     pub fn vrod_search_tagged_device(idx: *mut vrod_index, d_queries: *const f32, nq: u32, k: u32,
                                      d_preds: *const vrod_tag_pred, d_out_ids: *mut u64, d_out_scores: *mut f32,
                                      stream: *mut c_void) -> c_int;
+    pub fn vrod_index_set_values(idx: *mut vrod_index, first_id: u64, values: *const i64, n: u64) -> c_int;
+    pub fn vrod_index_get_values(idx: *mut vrod_index, first_id: u64, n: u64, out_values: *mut i64) -> c_int;
+    pub fn vrod_search_where(idx: *mut vrod_index, queries: *const f32, nq: u32, k: u32, preds: *const vrod_where,
+                             out_ids: *mut u64, out_scores: *mut f32) -> c_int;
+    pub fn vrod_search_where_device(idx: *mut vrod_index, d_queries: *const f32, nq: u32, k: u32,
+                                    d_preds: *const vrod_where, d_out_ids: *mut u64, d_out_scores: *mut f32,
+                                    stream: *mut c_void) -> c_int;
     /// `flags`: 0, or 1 (`VROD_BYID_EXCLUDE_SELF`): the row itself is no candidate of its own query.
     pub fn vrod_search_by_ids(idx: *mut vrod_index, ids: *const u64, nq: u32, k: u32, flags: u32, out_ids: *mut u64,
                               out_scores: *mut f32) -> c_int;
@@ -403,6 +422,37 @@ impl Collection {
         let mut scores = vec![0f32; queries.len() * k];
         check(unsafe {
             vrod_search_tagged(self.idx, flat.as_ptr(), queries.len() as u32, k as u32, preds.as_ptr(), ids.as_mut_ptr(), scores.as_mut_ptr())
+        })?;
+        Ok((ids, scores))
+    }
+
+    /// Give the rows with ids `first_id..first_id + values.len()` their signed 64-bit values (every row carries 0 until set).
+    pub fn set_values(&mut self, first_id: u64, values: &[i64]) -> Result<(), ScanError> {
+        check(unsafe { vrod_index_set_values(self.idx, first_id, values.as_ptr(), values.len() as u64) })
+    }
+
+    pub fn values(&self, first_id: u64, n: usize) -> Result<Vec<i64>, ScanError> {
+        let mut out = vec![0i64; n];
+        check(unsafe { vrod_index_get_values(self.idx, first_id, n as u64, out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+
+    /// `search` with a tags + value-interval predicate per query: query `q` sees only the live, allowed rows whose tags
+    /// and value match `preds[q]`.
+    pub fn search_where(&self, queries: &[Vec<f32>], k: usize, preds: &[vrod_where]) -> Result<(Vec<u64>, Vec<f32>), ScanError> {
+        for q in queries {
+            if q.len() != self.dim {
+                return Err(ScanError::Dim { got: q.len(), want: self.dim });
+            }
+        }
+        if preds.len() != queries.len() {
+            return Err(ScanError::Dim { got: preds.len(), want: queries.len() });
+        }
+        let flat: Vec<f32> = queries.iter().flatten().copied().collect();
+        let mut ids = vec![0u64; queries.len() * k];
+        let mut scores = vec![0f32; queries.len() * k];
+        check(unsafe {
+            vrod_search_where(self.idx, flat.as_ptr(), queries.len() as u32, k as u32, preds.as_ptr(), ids.as_mut_ptr(), scores.as_mut_ptr())
         })?;
         Ok((ids, scores))
     }

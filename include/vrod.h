@@ -207,6 +207,17 @@ int vrod_index_get_labels(vrod_index *idx, uint64_t first_id, uint64_t n, uint32
  * (get_tags reports the zeros every row carries). */
 int vrod_index_set_tags(vrod_index *idx, uint64_t first_id, const uint64_t *tags, uint64_t n);
 int vrod_index_get_tags(vrod_index *idx, uint64_t first_id, uint64_t n, uint64_t *out_tags);
+/* Row values: every row carries one signed 64-bit value -- 0 until set, and 0 for rows added later -- that only
+ * vrod_search_where reads (every other search ignores values entirely; values, tags and labels are independent): a
+ * timestamp, a price, a version.  The rules are those of the tags: set_values gives the rows with ids [first_id,
+ * first_id + n) (ids as searches report them, id_offset applied; deleted rows may be named) the values values[0 .. n)
+ * (host memory); a range that is not wholly within the current rows fails with VROD_ERR_INVALID_ARG and changes nothing;
+ * n == 0 does nothing.  vrod_index_update keeps a row's value, vrod_index_delete leaves values alone, vrod_index_compact
+ * moves them with their rows.  get_values reads them back (host memory).  Values cost nothing until first set: the device
+ * array is allocated by the first set_values.  While a search is pending: VROD_ERR_INVALID_ARG.  Multi-device handles:
+ * set_values returns VROD_ERR_UNSUPPORTED and changes nothing (get_values reports the zeros every row carries). */
+int vrod_index_set_values(vrod_index *idx, uint64_t first_id, const int64_t *values, uint64_t n);
+int vrod_index_get_values(vrod_index *idx, uint64_t first_id, uint64_t n, int64_t *out_values);
 /* Copy prepared rows [first, first+n) back as fp32 (bf16 widened): n x dim. */
 int vrod_index_get_rows(vrod_index *idx, uint64_t first, uint64_t n, float *out_rows);
 
@@ -313,6 +324,29 @@ int vrod_search_tagged(vrod_index *idx, const float *queries, uint32_t nq, uint3
 int vrod_search_tagged_device(vrod_index *idx, const float *d_queries, uint32_t nq, uint32_t k,
                               const vrod_tag_pred *d_preds, uint64_t *d_out_ids, float *d_out_scores,
                               void *stream);
+
+/* Search with a tags + value-interval predicate per query ("only rows newer than t", "price between a and b", usually
+ * joined with a tenant or access group).  A row with tags t and value v matches the predicate p iff
+ *     (p.any == 0 || (t & p.any) != 0)  &&  (t & p.all) == p.all  &&  (t & p.none) == 0  &&  p.lo <= v  &&  v <= p.hi,
+ * the interval compared as signed values, both ends inclusive.  lo > hi, or all & none != 0, can match nothing: an
+ * all-unfilled row, without a pass over the corpus.  {0, 0, 0, INT64_MIN, INT64_MAX} matches every row: the bits of
+ * vrod_search under the same filter and deletions.  A handle whose tags (values) were never set holds 0 in every row.
+ * Everything else is the contract of vrod_search_tagged: query q sees the live, allowed, matching rows and gets, bit for
+ * bit, the top k over those rows in ascending id order (ties by smaller id, NaN last, unfilled slots (VROD_ID_NONE,
+ * NaN)); k, null pointers, NaN / Inf in the queries, an empty handle and a pending search are handled the same way;
+ * synchronous, no _begin_ form, no graph replay; vrod_index_set_path is honoured (GATHER: every predicate scored on its
+ * own rows; STREAM / MFMA / EXACT: every predicate by a masked scan); vrod_index_last_stats reads as after a tagged
+ * search; the _device form copies the predicates to the host to group them.  One pass over the tag and value arrays
+ * serves 1024 distinct predicates.  Multi-device handles: VROD_ERR_UNSUPPORTED, outputs untouched. */
+typedef struct {
+    uint64_t any, all, none;
+    int64_t lo, hi;
+} vrod_where; /* 40 bytes, no padding */
+int vrod_search_where(vrod_index *idx, const float *queries, uint32_t nq, uint32_t k,
+                      const vrod_where *preds, uint64_t *out_ids, float *out_scores);
+int vrod_search_where_device(vrod_index *idx, const float *d_queries, uint32_t nq, uint32_t k,
+                             const vrod_where *d_preds, uint64_t *d_out_ids, float *d_out_scores,
+                             void *stream);
 
 /* Grouped search -- the best row of each label, the k best labels per query (a document stored as many chunk rows that
  * share a label: the k best documents, not k chunks of one).  The ELIGIBLE rows of a query are the rows that are live

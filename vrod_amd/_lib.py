@@ -26,6 +26,7 @@ SYMBOLS = [
     "vrod_search_grouped", "vrod_search_grouped_device",
     "vrod_search_by_ids", "vrod_search_by_ids_device", "vrod_knn_graph",
     "vrod_index_set_tags", "vrod_index_get_tags", "vrod_search_tagged", "vrod_search_tagged_device",
+    "vrod_index_set_values", "vrod_index_get_values", "vrod_search_where", "vrod_search_where_device",
     "vrod_search_multivec", "vrod_search_multivec_device", "vrod_index_last_multivec",
     "vrod_search_diverse", "vrod_search_diverse_device",
     "vrod_search_combined", "vrod_search_combined_device",
@@ -124,6 +125,10 @@ def load() -> C.CDLL:
     L.vrod_index_get_tags.argtypes = [vp, u64, u64, vp]
     L.vrod_search_tagged.argtypes = [vp, vp, u32, u32, vp, vp, vp]
     L.vrod_search_tagged_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
+    L.vrod_index_set_values.argtypes = [vp, u64, vp, u64]
+    L.vrod_index_get_values.argtypes = [vp, u64, u64, vp]
+    L.vrod_search_where.argtypes = [vp, vp, u32, u32, vp, vp, vp]
+    L.vrod_search_where_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
     L.vrod_search_grouped.argtypes = [vp, vp, u32, u32, vp, vp, vp]
     L.vrod_search_grouped_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
     L.vrod_search_by_ids.argtypes = [vp, vp, u32, u32, u32, vp, vp]

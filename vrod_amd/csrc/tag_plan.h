@@ -37,34 +37,36 @@ constexpr uint32_t kTagGroupsPerPass = 2048;
 constexpr uint32_t kTagLdsPerGroup = 28;
 
 // ------------------------------------------------------------------ grouping
-// The batch's distinct satisfiable predicates ordered by (any, all, none), and per predicate its queries in ascending
-// order: group g is q_order[q_off[g] .. q_off[g + 1]).  The queries of unsatisfiable predicates come last in q_order,
-// from q_off[size()] on, ascending: they belong to no group and no pass, their result rows are all unfilled.
-struct TagGroups {
-    std::vector<TagPred> preds;      // [G]
+// The batch's distinct satisfiable predicates in ascending order, and per predicate its queries in ascending order:
+// group g is q_order[q_off[g] .. q_off[g + 1]).  The queries of unsatisfiable predicates come last in q_order, from
+// q_off[size()] on, ascending: they belong to no group and no pass, their result rows are all unfilled.
+// (A template over the predicate: where_plan.h groups its wider predicates with the same code.)
+template <typename Pred>
+struct PredGroups {
+    std::vector<Pred> preds;         // [G]
     std::vector<uint32_t> q_off;     // [G + 1]
     std::vector<uint32_t> q_order;   // [nq]
     uint32_t size() const { return (uint32_t)preds.size(); }
     uint32_t nq_of(uint32_t g) const { return q_off[g + 1] - q_off[g]; }
     uint32_t n_unsatisfiable() const { return (uint32_t)q_order.size() - q_off.back(); }
 };
-inline TagGroups tag_groups(const TagPred* p, uint32_t nq) {
-    TagGroups G;
+// unsat(p): no row can match p; before(a, b): the strict order of the groups.
+template <typename Pred, typename Unsat, typename Before>
+inline PredGroups<Pred> group_preds(const Pred* p, uint32_t nq, Unsat unsat, Before before) {
+    PredGroups<Pred> G;
     G.q_order.resize(nq);
     for (uint32_t i = 0; i < nq; ++i) G.q_order[i] = i;
     auto less = [&](uint32_t a, uint32_t b) {
-        const bool ua = tag_unsatisfiable(p[a]), ub = tag_unsatisfiable(p[b]);
+        const bool ua = unsat(p[a]), ub = unsat(p[b]);
         if (ua != ub) return ub;
         if (ua) return false;
-        if (p[a].any != p[b].any) return p[a].any < p[b].any;
-        if (p[a].all != p[b].all) return p[a].all < p[b].all;
-        return p[a].none < p[b].none;
+        return before(p[a], p[b]);
     };
     std::stable_sort(G.q_order.begin(), G.q_order.end(), less);
     uint32_t i = 0;
-    for (; i < nq && !tag_unsatisfiable(p[G.q_order[i]]); ++i) {
-        const TagPred& t = p[G.q_order[i]];
-        if (G.preds.empty() || G.preds.back().any != t.any || G.preds.back().all != t.all || G.preds.back().none != t.none) {
+    for (; i < nq && !unsat(p[G.q_order[i]]); ++i) {
+        const Pred& t = p[G.q_order[i]];
+        if (G.preds.empty() || before(G.preds.back(), t)) {
             G.preds.push_back(t);
             G.q_off.push_back(i);
         }
@@ -72,6 +74,14 @@ inline TagGroups tag_groups(const TagPred* p, uint32_t nq) {
     G.q_off.push_back(i);
     return G;
 }
+// Tag predicates: ordered by (any, all, none).
+using TagGroups = PredGroups<TagPred>;
+inline bool tag_before(const TagPred& a, const TagPred& b) {
+    if (a.any != b.any) return a.any < b.any;
+    if (a.all != b.all) return a.all < b.all;
+    return a.none < b.none;
+}
+inline TagGroups tag_groups(const TagPred* p, uint32_t nq) { return group_preds(p, nq, tag_unsatisfiable, tag_before); }
 
 // ------------------------------------------------------------------ scatter passes
 // One pass over the tag array writes the row lists of the narrow groups among [g0, g1): group g's list starts at

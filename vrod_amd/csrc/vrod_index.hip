@@ -35,6 +35,7 @@
 #include "compact_plan.h"
 #include "label_plan.h"
 #include "tag_plan.h"
+#include "where_plan.h"
 #include "group_plan.h"
 #include "multivec_plan.h"
 #include "diverse_plan.h"
@@ -242,6 +243,10 @@ struct vrod_index {
     // vrod_search_tagged reads them; a handle that never set one treats every row as 0.
     std::vector<uint64_t> tag_bits;    // [capacity] once tags exist
     uint64_t* tag_dev = nullptr;       // [capacity] on the device, or null
+    // row values (vrod_index_set_values): one signed 64-bit value per row of the capacity, kept exactly as the tags are.
+    // Only vrod_search_where reads them; a handle that never set one treats every row as 0.
+    std::vector<int64_t> val_bits;     // [capacity] once values exist
+    int64_t* val_dev = nullptr;        // [capacity] on the device, or null
     // Workspaces the synchronous searches share, one per role (DESIGN.md "Shared workspaces"): the handle is idle before
     // and after each of those calls, so no two of them hold one at once.
     //   host_q, host_args: a host form's raw queries or vectors, and its other arguments, on the device;
@@ -457,9 +462,28 @@ static int index_reserve(vrod_index* idx, uint64_t n_rows) {
             return fail(VROD_ERR_HIP, "growing the row tags failed: %s", hipGetErrorString(te));
         }
     }
+    int64_t* nv = nullptr;   // and the values
+    if (idx->val_dev) {
+        hipError_t ve = hipMalloc((void**)&nv, want * 8);
+        if (ve == hipSuccess) ve = hipMemsetAsync(nv, 0, want * 8, idx->stream);
+        if (ve == hipSuccess) ve = hipMemcpyAsync(nv, idx->val_bits.data(), idx->count * 8, hipMemcpyHostToDevice, idx->stream);
+        if (ve == hipSuccess) ve = hipStreamSynchronize(idx->stream);
+        if (ve != hipSuccess) {
+            (void)hipStreamSynchronize(idx->stream);
+            if (nv) (void)hipFree(nv);
+            if (nt) (void)hipFree(nt);
+            if (nl) (void)hipFree(nl);
+            if (ne) (void)hipFree(ne);
+            if (nd) (void)hipFree(nd);
+            (void)hipFree(nc);
+            (void)hipFree(nx);
+            return fail(VROD_ERR_HIP, "growing the row values failed: %s", hipGetErrorString(ve));
+        }
+    }
     if (idx->corpus) (void)hipFree(idx->corpus);
     if (idx->xnorm2) (void)hipFree(idx->xnorm2);
     if (idx->planes) { (void)hipFree(idx->planes); idx->planes = nullptr; idx->planes_cap = idx->planes_rows = 0; }   // rebuilt lazily
+    if (idx->val_dev) { (void)hipFree(idx->val_dev); idx->val_dev = nv; idx->val_bits.resize(want, 0ll); }
     if (idx->tag_dev) { (void)hipFree(idx->tag_dev); idx->tag_dev = nt; idx->tag_bits.resize(want, 0ull); }
     if (idx->lab_dev) { (void)hipFree(idx->lab_dev); idx->lab_dev = nl; idx->lab_bits.resize(want, 0u); }
     if (idx->del_dev) { (void)hipFree(idx->del_dev); idx->del_dev = nd; }
@@ -640,6 +664,13 @@ static int index_compact(vrod_index* idx, uint64_t* out_new_ids) {
         for (uint64_t r = 0; r < count; ++r)
             if (!bit_of(del, r)) new_tag[j++] = idx->tag_bits[r];
     }
+    std::vector<int64_t> new_val;    // and the values
+    if (idx->val_dev) {
+        new_val.assign(count, 0ll);
+        uint64_t j = 0;
+        for (uint64_t r = 0; r < count; ++r)
+            if (!bit_of(del, r)) new_val[j++] = idx->val_bits[r];
+    }
     uint64_t stage_rows = 0;
     for (const CompactChunk& c : plan.chunks) if (c.staged) stage_rows = std::max(stage_rows, c.L);
     if (stage_rows) {
@@ -674,6 +705,7 @@ static int index_compact(vrod_index* idx, uint64_t* out_new_ids) {
     if (e == hipSuccess && idx->filter_on) e = hipMemcpyAsync(idx->eff_dev, new_eff.data(), cap_words * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && idx->lab_dev) e = hipMemcpyAsync(idx->lab_dev, new_lab.data(), count * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && idx->tag_dev) e = hipMemcpyAsync(idx->tag_dev, new_tag.data(), count * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && idx->val_dev) e = hipMemcpyAsync(idx->val_dev, new_val.data(), count * 8, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess)
         return fail(VROD_ERR_HIP, "vrod_index_compact: %s while rows were moving: the handle is unusable, destroy it", hipGetErrorString(e));
@@ -685,6 +717,7 @@ static int index_compact(vrod_index* idx, uint64_t* out_new_ids) {
     if (idx->filter_on) { idx->allow_bits.swap(new_allow); idx->eff_bits.swap(new_eff); }   // n_eligible: the same rows
     if (idx->lab_dev) std::copy(new_lab.begin(), new_lab.end(), idx->lab_bits.begin());
     if (idx->tag_dev) std::copy(new_tag.begin(), new_tag.end(), idx->tag_bits.begin());
+    if (idx->val_dev) std::copy(new_val.begin(), new_val.end(), idx->val_bits.begin());
     idx->planes_rows = 0;
     mask_changed(idx);
     return VROD_OK;
@@ -2718,17 +2751,56 @@ static int labeled_search(vrod_index* idx, const float* d_queries_raw, uint32_t 
     return VROD_OK;
 }
 
-// ------------------------------------------------------------------ tagged search (vrod_search_tagged)
-// Query q sees the eligible rows (live, allowed) whose tags match h_preds[q].  The labelled search with two differences
-// (tag_plan.h, kernels_tag.hip): a group is a distinct predicate, and a row belongs to every group it matches.  So every
-// chunk of kTagGroupsPerPass groups is counted first -- one pass over the tag array, into a [blocks][groups] matrix --
-// and its groups routed by filter_route on their counts; then the chunk's narrow groups' row lists are written and
-// scored in passes whose lists stay under the 1 GiB rule (their sum is not bounded by the corpus), each pass one
-// segmented score launch per score chunk; after the last chunk the wide groups take one masked ordinary search each.  Queries whose predicate no row can match
-// (all & none != 0) are in no group: their result rows are filled as unfilled and nothing else looks at them.
+// ------------------------------------------------------------------ predicate searches (vrod_search_tagged, vrod_search_where)
+// What the flow below needs of a predicate type: its grouping, the groups one pass serves, and the three launches over
+// the handle's side arrays -- count and scatter over a pass's table, and one predicate's effective mask.
+struct TagSearch {
+    using Pred = TagPred;
+    static constexpr uint32_t kGroupsPerPass = kTagGroupsPerPass;
+    static TagGroups groups(const TagPred* p, uint32_t nq) { return tag_groups(p, nq); }
+    static void count(const vrod_index* idx, const uint32_t* mask, uint32_t rpb, const TagPred* table, uint32_t G, uint32_t* cnt, uint32_t cnt_ld,
+                      hipStream_t s) {
+        launch_tag_group_count(idx->tag_dev, mask, idx->count, rpb, table, G, cnt, cnt_ld, s);
+    }
+    static void scatter(const vrod_index* idx, const uint32_t* mask, uint32_t rpb, const TagPred* table, uint32_t G, const uint32_t* cnt,
+                        uint32_t cnt_ld, const uint32_t* seg_off, uint32_t* lists, hipStream_t s) {
+        launch_tag_group_scatter(idx->tag_dev, mask, idx->count, rpb, table, G, cnt, cnt_ld, seg_off, lists, s);
+    }
+    static void mask_of(const vrod_index* idx, const uint32_t* mask, uint64_t words, const TagPred& p, uint32_t* out, hipStream_t s) {
+        launch_tag_group_mask(idx->tag_dev, mask, idx->count, words, p, out, s);
+    }
+};
+struct WhereSearch {
+    using Pred = WherePred;
+    static constexpr uint32_t kGroupsPerPass = kWhereGroupsPerPass;
+    static WhereGroups groups(const WherePred* p, uint32_t nq) { return where_groups(p, nq); }
+    static void count(const vrod_index* idx, const uint32_t* mask, uint32_t rpb, const WherePred* table, uint32_t G, uint32_t* cnt,
+                      uint32_t cnt_ld, hipStream_t s) {
+        launch_where_group_count(idx->tag_dev, idx->val_dev, mask, idx->count, rpb, table, G, cnt, cnt_ld, s);
+    }
+    static void scatter(const vrod_index* idx, const uint32_t* mask, uint32_t rpb, const WherePred* table, uint32_t G, const uint32_t* cnt,
+                        uint32_t cnt_ld, const uint32_t* seg_off, uint32_t* lists, hipStream_t s) {
+        launch_where_group_scatter(idx->tag_dev, idx->val_dev, mask, idx->count, rpb, table, G, cnt, cnt_ld, seg_off, lists, s);
+    }
+    static void mask_of(const vrod_index* idx, const uint32_t* mask, uint64_t words, const WherePred& p, uint32_t* out, hipStream_t s) {
+        launch_where_group_mask(idx->tag_dev, idx->val_dev, mask, idx->count, words, p, out, s);
+    }
+};
+
+// Query q sees the eligible rows (live, allowed) that match h_preds[q].  The labelled search with two differences
+// (tag_plan.h, kernels_tag.hip; where_plan.h, kernels_where.hip): a group is a distinct predicate, and a row belongs to
+// every group it matches.  So every chunk of S::kGroupsPerPass groups is counted first -- one pass over the side arrays,
+// into a [blocks][groups] matrix -- and its groups routed by filter_route on their counts; then the chunk's narrow
+// groups' row lists are written and scored in passes whose lists stay under the 1 GiB rule (their sum is not bounded by
+// the corpus), each pass one segmented score launch per score chunk; after the last chunk the wide groups take one
+// masked ordinary search each.  Queries whose predicate no row can match (all & none != 0, an empty interval) are in no
+// group: their result rows are filled as unfilled and nothing else looks at them.
 // Synchronous: the handle is idle before and after.  d_queries_raw / d_out_*: device memory, h_preds: host.
-static int tagged_search(vrod_index* idx, const float* d_queries_raw, uint32_t nq, uint32_t k, const TagPred* h_preds, uint64_t* d_out_ids,
-                         float* d_out_scores) {
+template <typename S>
+static int pred_search(vrod_index* idx, const float* d_queries_raw, uint32_t nq, uint32_t k, const typename S::Pred* h_preds,
+                       uint64_t* d_out_ids, float* d_out_scores) {
+    using Pred = typename S::Pred;
+    constexpr uint32_t kPerPass = S::kGroupsPerPass;
     vrod_search_stats st{};
     st.nq = nq; st.k = k; st.path = VROD_PATH_GATHER;
     const uint64_t N = idx->count;
@@ -2737,7 +2809,7 @@ static int tagged_search(vrod_index* idx, const float* d_queries_raw, uint32_t n
     if (N == 0) return return_unfilled(idx, s, st, d_out_ids, d_out_scores, (uint64_t)nq * k);   // an empty handle
     VROD_TRY(prep_queries_checked(idx, P, d_queries_raw, nq));
 
-    const TagGroups G = tag_groups(h_preds, nq);
+    const PredGroups<Pred> G = S::groups(h_preds, nq);
     const uint32_t Gn = G.size();
     if (!Gn) return return_unfilled(idx, s, st, d_out_ids, d_out_scores, (uint64_t)nq * k);   // no predicate can match
     if (G.n_unsatisfiable()) {   // (the groups' queries overwrite their own rows below)
@@ -2755,11 +2827,11 @@ static int tagged_search(vrod_index* idx, const float* d_queries_raw, uint32_t n
     uint32_t* d_ones = d_qorder + nq;
     const DevSlots d_slots = dev_slots(d_ones + nq, nq);
     // [predicates | totals | a pass's segment offsets] and the count matrix [blocks][groups] of ONE chunk of
-    // kTagGroupsPerPass groups: the workspace does not grow with the batch's distinct predicates
-    const uint32_t Gc = std::min(Gn, kTagGroupsPerPass);
-    VROD_TRY(idx->lab_tab.ensure((size_t)Gc * (sizeof(TagPred) + 8)));
+    // kPerPass groups: the workspace does not grow with the batch's distinct predicates
+    const uint32_t Gc = std::min(Gn, kPerPass);
+    VROD_TRY(idx->lab_tab.ensure((size_t)Gc * (sizeof(Pred) + 8)));
     VROD_TRY(idx->lab_cnt.ensure((size_t)n_blocks * Gc * 4));
-    TagPred* d_table = idx->lab_tab.as<TagPred>();
+    Pred* d_table = idx->lab_tab.template as<Pred>();
     uint32_t* d_total = (uint32_t*)(d_table + Gc);
     uint32_t* d_seg_off = d_total + Gc;
     uint32_t* d_cnt = idx->lab_cnt.as<uint32_t>();
@@ -2773,11 +2845,11 @@ static int tagged_search(vrod_index* idx, const float* d_queries_raw, uint32_t n
     }
     Timer tm(idx, P);
     P.reset_events();
-    for (uint32_t c0 = 0; c0 < Gn; c0 += kTagGroupsPerPass) {
-        const uint32_t Gp = std::min(kTagGroupsPerPass, Gn - c0);
-        // ---- pass 1: the chunk's groups' eligible matching rows, counted per block of the tag array
-        HIP_TRY(hipMemcpyAsync(d_table, G.preds.data() + c0, (size_t)Gp * sizeof(TagPred), hipMemcpyHostToDevice, s));
-        launch_tag_group_count(idx->tag_dev, base_mask, N, rpb, d_table, Gp, d_cnt, Gp, s);
+    for (uint32_t c0 = 0; c0 < Gn; c0 += kPerPass) {
+        const uint32_t Gp = std::min(kPerPass, Gn - c0);
+        // ---- pass 1: the chunk's groups' eligible matching rows, counted per block of the side arrays
+        HIP_TRY(hipMemcpyAsync(d_table, G.preds.data() + c0, (size_t)Gp * sizeof(Pred), hipMemcpyHostToDevice, s));
+        S::count(idx, base_mask, rpb, d_table, Gp, d_cnt, Gp, s);
         launch_group_prefix(d_cnt, n_blocks, Gp, d_total, s);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(m.data() + c0, d_total, (size_t)Gp * 4, hipMemcpyDeviceToHost, s));
@@ -2787,7 +2859,7 @@ static int tagged_search(vrod_index* idx, const float* d_queries_raw, uint32_t n
         const std::vector<uint32_t> mc(m.begin() + c0, m.begin() + c0 + Gp);
         const std::vector<uint8_t> nc(narrow.begin() + c0, narrow.begin() + c0 + Gp);
         // ---- pass 2 per scatter pass: the narrow groups' row lists, ascending, then score + select
-        for (const TagPass& tp : plan_tag_passes(mc, nc)) {
+        for (const TagPass& tp : plan_tag_passes(mc, nc, 1ull << 30, kPerPass)) {
             SlotTables T;
             for (uint32_t i = tp.g0; i < tp.g1; ++i) {
                 const uint32_t g = c0 + i, base = tp.seg_off[i - tp.g0], nqg = G.nq_of(g);
@@ -2799,8 +2871,7 @@ static int tagged_search(vrod_index* idx, const float* d_queries_raw, uint32_t n
             VROD_TRY(idx->lab_lists.ensure(std::max<uint64_t>(tp.list_n, 1) * 4));
             HIP_TRY(hipMemcpyAsync(d_seg_off, tp.seg_off.data(), (size_t)(tp.g1 - tp.g0) * 4, hipMemcpyHostToDevice, s));
             if (tp.list_n)
-                launch_tag_group_scatter(idx->tag_dev, base_mask, N, rpb, d_table + tp.g0, tp.g1 - tp.g0, d_cnt + tp.g0, Gp, d_seg_off,
-                                         idx->lab_lists.as<uint32_t>(), s);
+                S::scatter(idx, base_mask, rpb, d_table + tp.g0, tp.g1 - tp.g0, d_cnt + tp.g0, Gp, d_seg_off, idx->lab_lists.template as<uint32_t>(), s);
             HIP_TRY(hipGetLastError());
             VROD_TRY(score_segments(idx, P, tm, st, T, d_slots, k, d_out_ids, d_out_scores));
         }
@@ -2816,7 +2887,7 @@ static int tagged_search(vrod_index* idx, const float* d_queries_raw, uint32_t n
         VROD_TRY(wide_group_ws(idx, max_nq, k));
         for (uint32_t g = 0; g < Gn; ++g) {
             if (narrow[g]) continue;
-            launch_tag_group_mask(idx->tag_dev, base_mask, N, words, G.preds[g], idx->lab_mask.as<uint32_t>(), s);
+            S::mask_of(idx, base_mask, words, G.preds[g], idx->lab_mask.template as<uint32_t>(), s);
             VROD_TRY(dense_group_search(idx, s, st, d_queries_raw, d_qorder + G.q_off[g], d_ones, G.nq_of(g), m[g], k, d_out_ids, d_out_scores));
         }
     }
@@ -3776,6 +3847,7 @@ int vrod_index_destroy(vrod_index* idx) {
     if (idx->eff_dev) (void)hipFree(idx->eff_dev);
     if (idx->lab_dev) (void)hipFree(idx->lab_dev);
     if (idx->tag_dev) (void)hipFree(idx->tag_dev);
+    if (idx->val_dev) (void)hipFree(idx->val_dev);
     if (idx->flags) (void)hipFree(idx->flags);
     if (idx->stream) (void)hipStreamDestroy(idx->stream);
     delete idx;
@@ -4135,59 +4207,110 @@ int vrod_search_labeled_device(vrod_index* idx, const float* d_queries, uint32_t
     return labeled_search(idx, d_queries, nq, k, labels.data(), d_out_ids, d_out_scores);
 }
 
-int vrod_index_set_tags(vrod_index* idx, uint64_t first_id, const uint64_t* tags, uint64_t n) {
-    if (!idx || (!tags && n)) return fail(VROD_ERR_INVALID_ARG, "null argument");
-    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "vrod_index_set_tags on a multi-device handle: tags are not routed to the shards");
-    VROD_TRY(require_idle(idx, "vrod_index_set_tags"));
+extern "C++" {   // (templates, inside the C entry points' block)
+// A per-row side array of 64-bit words (tags, values): host mirror and device copy allocated at the first set, 0 until
+// then.  set: the rows with ids [first_id, first_id + n) take src[0 .. n); get: the host mirror is the truth.
+template <typename T>
+static int side_array_set(vrod_index* idx, const char* what, const char* noun, uint64_t first_id, const T* src, uint64_t n, std::vector<T>& host,
+                          T*& dev) {
+    static_assert(sizeof(T) == 8, "tags and values are 64-bit words");
+    if (!src && n) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "%s on a multi-device handle: %s are not routed to the shards", what, noun);
+    VROD_TRY(require_idle(idx, what));
     VROD_TRY(check_id_range(idx, first_id, n));
     if (!n) return VROD_OK;
     VROD_TRY(set_device(idx));
     const uint64_t r0 = first_id - idx->id_offset;
-    if (!idx->tag_dev) {   // the first tags of the handle: every row carries 0 so far
-        uint64_t* d = nullptr;
+    if (!dev) {   // the first of the handle: every row carries 0 so far
+        T* d = nullptr;
         HIP_TRY(hipMalloc((void**)&d, idx->capacity * 8));
         const hipError_t e = hipMemset(d, 0, idx->capacity * 8);
-        if (e != hipSuccess) { (void)hipFree(d); return fail(VROD_ERR_HIP, "clearing the row tags: %s", hipGetErrorString(e)); }
-        idx->tag_dev = d;
-        idx->tag_bits.assign(idx->capacity, 0ull);
+        if (e != hipSuccess) { (void)hipFree(d); return fail(VROD_ERR_HIP, "clearing the row %s: %s", noun, hipGetErrorString(e)); }
+        dev = d;
+        host.assign(idx->capacity, T(0));
     }
-    HIP_TRY(hipMemcpy(idx->tag_dev + r0, tags, n * 8, hipMemcpyHostToDevice));
-    std::copy(tags, tags + n, idx->tag_bits.begin() + r0);
+    HIP_TRY(hipMemcpy(dev + r0, src, n * 8, hipMemcpyHostToDevice));
+    std::copy(src, src + n, host.begin() + r0);
     return VROD_OK;
+}
+template <typename T>
+static int side_array_get(vrod_index* idx, uint64_t first_id, uint64_t n, const std::vector<T>& host, T* out) {
+    if (!out && n) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    VROD_TRY(check_id_range(idx, first_id, n));
+    const uint64_t r0 = first_id - idx->id_offset;
+    for (uint64_t i = 0; i < n; ++i) out[i] = host.empty() ? T(0) : host[r0 + i];
+    return VROD_OK;
+}
+}  // extern "C++"
+
+int vrod_index_set_tags(vrod_index* idx, uint64_t first_id, const uint64_t* tags, uint64_t n) {
+    if (!idx) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    return side_array_set(idx, "vrod_index_set_tags", "tags", first_id, tags, n, idx->tag_bits, idx->tag_dev);
 }
 
 int vrod_index_get_tags(vrod_index* idx, uint64_t first_id, uint64_t n, uint64_t* out_tags) {
-    if (!idx || (!out_tags && n)) return fail(VROD_ERR_INVALID_ARG, "null argument");
-    VROD_TRY(check_id_range(idx, first_id, n));
-    const uint64_t r0 = first_id - idx->id_offset;
-    for (uint64_t i = 0; i < n; ++i) out_tags[i] = idx->tag_bits.empty() ? 0ull : idx->tag_bits[r0 + i];   // (the host mirror is the truth)
-    return VROD_OK;
+    if (!idx) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    return side_array_get(idx, first_id, n, idx->tag_bits, out_tags);
+}
+
+int vrod_index_set_values(vrod_index* idx, uint64_t first_id, const int64_t* values, uint64_t n) {
+    if (!idx) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    return side_array_set(idx, "vrod_index_set_values", "values", first_id, values, n, idx->val_bits, idx->val_dev);
+}
+
+int vrod_index_get_values(vrod_index* idx, uint64_t first_id, uint64_t n, int64_t* out_values) {
+    if (!idx) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    return side_array_get(idx, first_id, n, idx->val_bits, out_values);
 }
 
 static_assert(sizeof(vrod_tag_pred) == 24 && sizeof(TagPred) == 24, "vrod_tag_pred is three packed 64-bit words");
+static_assert(sizeof(vrod_where) == 40 && sizeof(WherePred) == 40, "vrod_where is five packed 64-bit words");
 
-static int check_tagged_args(vrod_index* idx, const void* q, uint32_t nq, uint32_t k, const void* preds, const void* oi, const void* os) {
-    return check_derived_args(idx, "vrod_search_tagged", kTagsNotRouted, nq, {q, oi, os}, true, k, {preds});
+// The two forms of a predicate search (S: TagSearch, WhereSearch; ApiPred: the header's struct of S::Pred's layout).
+static const char kValuesNotRouted[] = "tags and values are not routed to the shards";
+extern "C++" {
+template <typename S, typename ApiPred>
+static int pred_search_host(vrod_index* idx, const char* what, const char* why_not, const float* queries, uint32_t nq, uint32_t k,
+                            const ApiPred* preds, uint64_t* out_ids, float* out_scores) {
+    VROD_TRY(check_derived_args(idx, what, why_not, nq, {queries, out_ids, out_scores}, true, k, {preds}));
+    if (!nq) return VROD_OK;
+    VROD_TRY(begin_host_form(idx, what, idx->count ? queries : nullptr, nq, nq, k));   // (an empty handle reads none)
+    VROD_TRY(pred_search<S>(idx, idx->host_q.as<float>(), nq, k, reinterpret_cast<const typename S::Pred*>(preds), idx->out_ids.as<uint64_t>(),
+                            idx->out_scores.as<float>()));
+    return copy_topk_out(idx, nq, k, out_ids, out_scores);
 }
+template <typename S, typename ApiPred>
+static int pred_search_device(vrod_index* idx, const char* what, const char* what_device, const char* why_not, const float* d_queries, uint32_t nq,
+                              uint32_t k, const ApiPred* d_preds, uint64_t* d_out_ids, float* d_out_scores, void* stream) {
+    VROD_TRY(check_derived_args(idx, what, why_not, nq, {d_queries, d_out_ids, d_out_scores}, true, k, {d_preds}));
+    if (!nq) return VROD_OK;
+    VROD_TRY(begin_sync_device(idx, what_device, stream));
+    std::vector<typename S::Pred> preds(nq);
+    HIP_TRY(hipMemcpy(preds.data(), d_preds, (size_t)nq * sizeof(typename S::Pred), hipMemcpyDeviceToHost));
+    return pred_search<S>(idx, d_queries, nq, k, preds.data(), d_out_ids, d_out_scores);
+}
+}  // extern "C++"
 
 int vrod_search_tagged(vrod_index* idx, const float* queries, uint32_t nq, uint32_t k, const vrod_tag_pred* preds, uint64_t* out_ids,
                        float* out_scores) {
-    VROD_TRY(check_tagged_args(idx, queries, nq, k, preds, out_ids, out_scores));
-    if (!nq) return VROD_OK;
-    VROD_TRY(begin_host_form(idx, "vrod_search_tagged", idx->count ? queries : nullptr, nq, nq, k));   // (an empty handle reads none)
-    VROD_TRY(tagged_search(idx, idx->host_q.as<float>(), nq, k, reinterpret_cast<const TagPred*>(preds), idx->out_ids.as<uint64_t>(),
-                           idx->out_scores.as<float>()));
-    return copy_topk_out(idx, nq, k, out_ids, out_scores);
+    return pred_search_host<TagSearch>(idx, "vrod_search_tagged", kTagsNotRouted, queries, nq, k, preds, out_ids, out_scores);
 }
 
 int vrod_search_tagged_device(vrod_index* idx, const float* d_queries, uint32_t nq, uint32_t k, const vrod_tag_pred* d_preds,
                               uint64_t* d_out_ids, float* d_out_scores, void* stream) {
-    VROD_TRY(check_tagged_args(idx, d_queries, nq, k, d_preds, d_out_ids, d_out_scores));
-    if (!nq) return VROD_OK;
-    VROD_TRY(begin_sync_device(idx, "vrod_search_tagged_device", stream));
-    std::vector<TagPred> preds(nq);
-    HIP_TRY(hipMemcpy(preds.data(), d_preds, (size_t)nq * sizeof(TagPred), hipMemcpyDeviceToHost));
-    return tagged_search(idx, d_queries, nq, k, preds.data(), d_out_ids, d_out_scores);
+    return pred_search_device<TagSearch>(idx, "vrod_search_tagged", "vrod_search_tagged_device", kTagsNotRouted, d_queries, nq, k, d_preds,
+                                         d_out_ids, d_out_scores, stream);
+}
+
+int vrod_search_where(vrod_index* idx, const float* queries, uint32_t nq, uint32_t k, const vrod_where* preds, uint64_t* out_ids,
+                      float* out_scores) {
+    return pred_search_host<WhereSearch>(idx, "vrod_search_where", kValuesNotRouted, queries, nq, k, preds, out_ids, out_scores);
+}
+
+int vrod_search_where_device(vrod_index* idx, const float* d_queries, uint32_t nq, uint32_t k, const vrod_where* d_preds, uint64_t* d_out_ids,
+                             float* d_out_scores, void* stream) {
+    return pred_search_device<WhereSearch>(idx, "vrod_search_where", "vrod_search_where_device", kValuesNotRouted, d_queries, nq, k, d_preds,
+                                           d_out_ids, d_out_scores, stream);
 }
 
 static int check_grouped_args(vrod_index* idx, const void* q, uint32_t nq, uint32_t k, const void* oi, const void* os) {

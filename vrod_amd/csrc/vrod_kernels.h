@@ -7,6 +7,7 @@
 #include "search_plan.h"   // kSelectChunk
 #include "label_plan.h"    // SegEntry
 #include "tag_plan.h"      // TagPred
+#include "where_plan.h"    // WherePred
 #include "multivec_plan.h" // MultivecQuery
 #include "combine_plan.h"  // kCombineMaxExclude, combine_lanes_per_query
 #include "candidates_plan.h" // kCandMaxList, the sort classes, cand_tile_query
@@ -239,6 +240,17 @@ void launch_tag_group_scatter(const uint64_t* d_tags, const uint32_t* d_mask, ui
 // d_out [n_words]: bit r set = row r is set in d_mask (may be null), does not match p, or r >= count.
 void launch_tag_group_mask(const uint64_t* d_tags, const uint32_t* d_mask, uint64_t count, uint64_t n_words, const TagPred& p, uint32_t* d_out,
                            hipStream_t s);
+
+// ---- kernels_where.hip : rows grouped by the tags + value-interval predicates of a batch, one predicate's dense-scan mask
+// The three launches of kernels_tag.hip with a row's value (d_vals, null: every row carries 0) beside its tags and
+// WherePred for TagPred: G <= kWhereGroupsPerPass.
+void launch_where_group_count(const uint64_t* d_tags, const int64_t* d_vals, const uint32_t* d_mask, uint64_t count, uint32_t rows_per_block,
+                              const WherePred* d_table, uint32_t G, uint32_t* d_cnt, uint32_t cnt_ld, hipStream_t s);
+void launch_where_group_scatter(const uint64_t* d_tags, const int64_t* d_vals, const uint32_t* d_mask, uint64_t count, uint32_t rows_per_block,
+                                const WherePred* d_table, uint32_t G, const uint32_t* d_cnt, uint32_t cnt_ld, const uint32_t* d_seg_off,
+                                uint32_t* d_lists, hipStream_t s);
+void launch_where_group_mask(const uint64_t* d_tags, const int64_t* d_vals, const uint32_t* d_mask, uint64_t count, uint64_t n_words,
+                             const WherePred& p, uint32_t* d_out, hipStream_t s);
 
 // ---- kernels_group.hip : a grouped search's de-duplication by label and the dense stage's per-query masks
 // List b (d_cand_ids / d_cand_scores + b * k1: a search's result row, ids with id_offset applied) of query d_qidx[b] (b

@@ -25,6 +25,8 @@ MAX_COMBINE_TERMS = 256   # VROD_MAX_COMBINE_TERMS
 MAX_EXCLUDE = 1024        # VROD_MAX_EXCLUDE
 COMBINED_EXCLUDE_TERMS = 1   # VROD_COMBINED_EXCLUDE_TERMS
 MAX_CANDIDATES = 16384    # VROD_MAX_CANDIDATES
+# vrod_where: one query's predicate of search_where, 40 bytes
+WHERE_DTYPE = np.dtype([("any", np.uint64), ("all", np.uint64), ("none", np.uint64), ("lo", np.int64), ("hi", np.int64)])
 # rows per batch of knn_graph() by storage type (byid_plan.h: kByidBatchF32, kByidBatchBf16)
 KNN_BATCH = {0: 256, 1: 1024}
 
@@ -231,6 +233,61 @@ class Index:
         check(self._L.vrod_index_get_tags(self._h, int(first_id), int(n), _ptr(out)))
         return out
 
+    @staticmethod
+    def _i64(values, what) -> np.ndarray:
+        """An integer array-like of signed 64-bit values -> a contiguous int64 vector."""
+        a = np.asarray(values)
+        if a.dtype.kind not in "iu" and (a.size or isinstance(values, np.ndarray)):   # (an empty list has no dtype of its own)
+            raise TypeError(f"{what} must be an integer array, got {a.dtype}")
+        if a.dtype.kind == "u" and a.size and int(a.max()) > 0x7FFFFFFFFFFFFFFF:
+            raise ValueError(f"{what} must fit 64 signed bits")
+        return np.ascontiguousarray(a.reshape(-1).astype(np.int64, copy=False))
+
+    def set_values(self, first_id: int, values):
+        """Give the rows with ids first_id, first_id + 1, ... the signed 64-bit values of an integer array-like
+        (vrod_index_set_values).  Every row carries 0 until it is given a value; only search_where reads them."""
+        a = self._i64(values, "values")
+        check(self._L.vrod_index_set_values(self._h, int(first_id), _ptr(a), a.size))
+
+    def get_values(self, first_id: int, n: int) -> np.ndarray:
+        out = np.empty(int(n), dtype=np.int64)
+        check(self._L.vrod_index_get_values(self._h, int(first_id), int(n), _ptr(out)))
+        return out
+
+    @classmethod
+    def _where(cls, preds, nq) -> np.ndarray:
+        """The predicates of search_where -> a contiguous [nq] array of WHERE_DTYPE (the layout of vrod_where).  preds is
+        such a structured array, or an integer [nq, 5] array-like with the columns any, all, none (64 unsigned bits) and
+        lo, hi (64 signed bits); Python ints keep both ranges, an int64 array's masks must not be negative, a uint64
+        array's ends must fit 63 bits."""
+        if isinstance(preds, np.ndarray) and preds.dtype.names:
+            if preds.dtype != WHERE_DTYPE:
+                raise TypeError(f"preds must have dtype {WHERE_DTYPE}, got {preds.dtype}")
+            p = np.ascontiguousarray(preds.reshape(-1))
+        else:
+            a = preds if isinstance(preds, np.ndarray) else np.array(preds, dtype=object)   # (a list keeps its Python ints)
+            if a.dtype == object and a.size:
+                if not all(isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_)) for x in a.reshape(-1)):
+                    raise TypeError("preds must hold integers")
+            elif a.dtype.kind not in "iu" and (a.size or isinstance(preds, np.ndarray)):
+                raise TypeError(f"preds must be an integer array, got {a.dtype}")
+            if a.size == 0:
+                a = np.zeros((0, 5), np.int64)
+            if a.ndim != 2 or a.shape[1] != 5:
+                raise ValueError(f"preds must have shape ({nq}, 5), got {a.shape}")
+            p = np.empty(a.shape[0], WHERE_DTYPE)
+            for j, name in enumerate(WHERE_DTYPE.names):
+                col = a[:, j]
+                if col.dtype == object:   # Python ints: the column's own range decides
+                    try:
+                        col = col.astype(np.uint64 if j < 3 else np.int64)
+                    except OverflowError:
+                        raise ValueError(f"preds column {name} does not fit 64 {'unsigned' if j < 3 else 'signed'} bits") from None
+                p[name] = cls._u64(col, f"preds column {name}", (-1,)) if j < 3 else cls._i64(col, f"preds column {name}")
+        if p.size != nq:
+            raise ValueError(f"preds must hold {nq} predicates, got {p.size}")
+        return p
+
     def set_id_offset(self, off: int):
         check(self._L.vrod_index_set_id_offset(self._h, int(off)))
         self._id_offset = int(off)
@@ -339,6 +396,34 @@ class Index:
         out_scores = _device_out(out_scores, (nq, k), torch.float32, dev)
         check(self._L.vrod_search_tagged_device(self._h, d_queries.data_ptr(), nq, int(k), d_preds.data_ptr(), out_ids.data_ptr(),
                                                 out_scores.data_ptr(), stream))
+        return out_ids, out_scores
+
+    def search_where(self, queries: np.ndarray, k: int, preds):
+        """search() with a tags + value-interval predicate per query (vrod_search_where): preds is a structured array of
+        WHERE_DTYPE or [nq, 5] integers, the columns any, all, none, lo, hi; query q sees only the eligible rows whose tags
+        satisfy (any, all, none) as in search_tagged and whose value v satisfies lo <= v <= hi (signed, inclusive).
+        numpy [nq, dim] fp32 -> (ids uint64 [nq, k], scores float32 [nq, k])."""
+        queries = self._queries(queries)
+        nq = queries.shape[0]
+        p = self._where(preds, nq)
+        ids, sc = _out(nq, k, np.uint64, np.float32)
+        check(self._L.vrod_search_where(self._h, _ptr(queries), nq, int(k), _ptr(p), _ptr(ids), _ptr(sc)))
+        return ids, sc
+
+    def search_where_device(self, d_queries, k: int, d_preds, out_ids=None, out_scores=None):
+        """torch CUDA tensors: queries [nq, dim] fp32, preds [nq, 5] int64 (any, all, none as the bits of uint64; lo, hi)
+        -> (ids int64-viewed-uint64 [nq, k], scores [nq, k]) on the device, complete on return."""
+        import torch
+        nq, dev, stream = self._device_queries(d_queries)
+        if d_preds.dtype != torch.int64:
+            raise TypeError(f"preds must be an int64 tensor, got {d_preds.dtype}")
+        if tuple(d_preds.shape) != (nq, 5):
+            raise ValueError(f"preds must be [{nq}, 5], got {tuple(d_preds.shape)}")
+        assert d_preds.is_cuda and d_preds.is_contiguous()
+        out_ids = _device_out(out_ids, (nq, k), torch.int64, dev)
+        out_scores = _device_out(out_scores, (nq, k), torch.float32, dev)
+        check(self._L.vrod_search_where_device(self._h, d_queries.data_ptr(), nq, int(k), d_preds.data_ptr(), out_ids.data_ptr(),
+                                               out_scores.data_ptr(), stream))
         return out_ids, out_scores
 
     def search_grouped(self, queries: np.ndarray, k: int):
