@@ -28,6 +28,28 @@ pub const VROD_PATH_EXACT: c_int = 3;
 pub const VROD_PATH_GATHER: c_int = 4;
 /// `vrod_range_search`: the result does not fit the caller's buffers (`out_lims` is valid).
 pub const VROD_ERR_CAPACITY: c_int = 8;
+/// Snapshots: open / read / write / rename / fsync failed.
+pub const VROD_ERR_IO: c_int = 9;
+/// Snapshots: not a snapshot, a truncated file, sizes that disagree, a checksum mismatch.
+pub const VROD_ERR_CORRUPT: c_int = 10;
+
+/// What a snapshot's header says (`vrod_snapshot_info`; a struct tag in C, the function has the same name).
+#[repr(C)]
+#[derive(Debug, Default, Clone, Copy, PartialEq, Eq)]
+pub struct vrod_snapshot_info {
+    pub version: u32,
+    pub dim: u32,
+    pub dtype: u32,
+    pub metric: u32,
+    pub count: u64,
+    pub live_count: u64,
+    pub id_offset: u64,
+    pub file_bytes: u64,
+    pub has_filter: u32,
+    pub has_labels: u32,
+    pub has_tags: u32,
+    pub has_values: u32,
+}
 
 #[repr(C)]
 #[derive(Debug, Default, Clone, Copy)]
@@ -220,6 +242,14 @@ extern "C" {
                                  cand_ids: *const u64, out_scores: *mut f32) -> c_int;
     pub fn vrod_score_candidates_device(idx: *mut vrod_index, d_queries: *const f32, nq: u32, d_cand_lims: *const u32,
                                         d_cand_ids: *const u64, d_out_scores: *mut f32, stream: *mut c_void) -> c_int;
+    /// Snapshots: the whole observable state of a single-device handle in one file, and back (`Database::load`).
+    pub fn vrod_index_save(idx: *mut vrod_index, path: *const c_char) -> c_int;
+    pub fn vrod_index_load(out: *mut *mut vrod_index, path: *const c_char, device_ids: *const c_int, n_devices: c_int) -> c_int;
+    pub fn vrod_snapshot_info(path: *const c_char, out: *mut vrod_snapshot_info) -> c_int;
+    pub fn vrod_snapshot_verify(path: *const c_char) -> c_int;
+    pub fn vrod_snapshot_checksum(bytes: *const c_void, n_bytes: u64, first_word: u64, out: *mut u64) -> c_int;
+    pub fn vrod_snapshot_checksum_device(device: c_int, d_bytes: *const c_void, n_bytes: u64, first_word: u64, out: *mut u64,
+                                         stream: *mut c_void) -> c_int;
 }
 
 /// Joins the reference's `thiserror` enums (`src/main.rs:36-40`, `src/command/builder.rs:10-15`).

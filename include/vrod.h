@@ -66,7 +66,9 @@ typedef enum {
     VROD_ERR_HIP = 5,           /* a HIP call failed; vrod_last_error() has the text */
     VROD_ERR_UNSUPPORTED = 6,
     VROD_ERR_INTERNAL = 7,
-    VROD_ERR_CAPACITY = 8       /* vrod_range_search: the result does not fit the caller's buffers (out_lims is valid) */
+    VROD_ERR_CAPACITY = 8,      /* vrod_range_search: the result does not fit the caller's buffers (out_lims is valid) */
+    VROD_ERR_IO = 9,            /* snapshots: open / read / write / rename / fsync failed; vrod_last_error() carries errno's text */
+    VROD_ERR_CORRUPT = 10       /* snapshots: not a snapshot, a truncated file, sizes that disagree, a checksum mismatch */
 } vrod_status;
 
 enum { VROD_DTYPE_F32 = 0, VROD_DTYPE_BF16 = 1 };  /* storage + fast-pass type */
@@ -220,6 +222,59 @@ int vrod_index_set_values(vrod_index *idx, uint64_t first_id, const int64_t *val
 int vrod_index_get_values(vrod_index *idx, uint64_t first_id, uint64_t n, int64_t *out_values);
 /* Copy prepared rows [first, first+n) back as fp32 (bf16 widened): n x dim. */
 int vrod_index_get_rows(vrod_index *idx, uint64_t first, uint64_t n, float *out_rows);
+
+/* --- snapshots ------------------------------------------------------------- */
+/* A snapshot is one file that holds the whole observable state of a single-device handle; a handle loaded from it is
+ * indistinguishable from the one that was saved, to the bit (<- the reference's Database::load, src/database/mod.rs,
+ * which is todo!()).  The format (version 1, little-endian; DESIGN.md "Snapshots") is a 4096-byte header -- magic
+ * "VRODSNAP", version, the scalars of vrod_snapshot_info, a table of sections (kind, offset, payload bytes, checksum) and
+ * its own checksum -- and the sections, each on a 4096-byte boundary, zero-padded; all offsets and lengths are 64-bit.
+ *   saved       dim, dtype, metric, count, id_offset; the prepared rows as stored (bf16 or fp32, never rounded again),
+ *               DENSE: [count][dim] elements, the row pitch is not part of the format; the per-row squared norms; the
+ *               largest squared norm the handle has ever held (it keeps vrod_search_stats eps_bound the same); the
+ *               deleted-row bits; the allowed bits of a filter, if one is set; labels, tags and values, each only if it
+ *               was ever set -- "never set" survives the round trip, those arrays still cost nothing until first set.
+ *   not saved   vrod_index_set_path, the profiling level, the last stats (vrod_index_last_stats, _last_multivec), the
+ *               bf16 [hi | lo] planes of an F32 handle (rebuilt at the next batched search), the self-tuned candidate
+ *               margin (kprime starts over) and spare capacity (vrod_index_reserve).
+ * vrod_index_save writes to "<path>.tmp", fsyncs and renames it over `path`: a failure of any kind removes the temporary
+ * file and leaves an older file at `path` as it was.  The handle is left exactly as it was found: every search after the
+ * call gives what it gave before it, captured graphs included.  The bytes depend on the state alone (no timestamps, zero
+ * padding): saving twice gives identical files, and so does save, load, save.  Null arguments, or a search pending:
+ * VROD_ERR_INVALID_ARG; a multi-device handle: VROD_ERR_UNSUPPORTED, nothing is written; the file system refusing:
+ * VROD_ERR_IO.
+ * vrod_index_load creates a handle (as vrod_index_create does: VROD_F32_SPLIT applies, n_devices <= 1, device_ids[0] or
+ * device 0) that matches the saved one in every observable of this header: vrod_index_count, _live_count, _filter_count,
+ * _get_rows, _get_labels, _get_tags, _get_values, every search entry point (ids and score bits, a NaN matching any NaN),
+ * eps_bound, scan_bytes and scan_flops; later mutations behave as they would have on the original.  Everything that can
+ * be checked without a device is checked before the first device call -- the header, the version, the section table
+ * against the file's real length, and the checksum of every section of at most 1 MiB -- so a bad file fails the same way
+ * on a machine without a GPU.  Every section's checksum is verified: the rows and the larger arrays by the device, over
+ * the bytes as they arrived in its memory (the host never makes a pass over them).  Not a snapshot, truncated, sizes that
+ * disagree, a checksum mismatch: VROD_ERR_CORRUPT; another version, or section kinds this build does not know:
+ * VROD_ERR_UNSUPPORTED; n_devices > 1: VROD_ERR_UNSUPPORTED; open or read failing: VROD_ERR_IO.  On any failure *out is
+ * NULL and nothing is kept.  A snapshot loads onto the dtype and metric it was saved with, nothing else.
+ * Rows move between the device and the file in chunks (a multiple of 32 rows, 32 MiB by default) through two pinned host
+ * buffers on the handle's stream: the pack / unpack kernel and the copy of one chunk run beside the file I/O of its
+ * neighbour.  VROD_DEBUG_SNAPSHOT_CHUNK_ROWS (read at every call) sets the rows per chunk.
+ * vrod_snapshot_info reads the header alone; vrod_snapshot_verify checks the whole file on the host.  Neither needs a device.
+ * The section checksum: with w_i the payload's little-endian u32 words (the last one zero-filled) and i = first_word +
+ * the word's position, z = w_i + (i + 1) * 0x9E3779B97F4A7C15, z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9,
+ * z = (z ^ z >> 27) * 0x94D049BB133111EB, z ^= z >> 31, all mod 2^64; the checksum is the sum of the z mod 2^64, so any
+ * chunking or order gives the same value.  vrod_snapshot_checksum computes it on the host, _checksum_device over device
+ * memory (d_bytes 4-byte aligned; `out` is host memory, written when the call returns). */
+struct vrod_snapshot_info {   /* (a struct tag, not a typedef: the function below has the same name, as stat(2) does) */
+    uint32_t version, dim, dtype, metric;
+    uint64_t count, live_count, id_offset, file_bytes;
+    uint32_t has_filter, has_labels, has_tags, has_values;
+};
+int vrod_index_save(vrod_index *idx, const char *path);
+int vrod_index_load(vrod_index **out, const char *path, const int *device_ids, int n_devices);
+int vrod_snapshot_info(const char *path, struct vrod_snapshot_info *out);
+int vrod_snapshot_verify(const char *path);
+int vrod_snapshot_checksum(const void *bytes, uint64_t n_bytes, uint64_t first_word, uint64_t *out);
+int vrod_snapshot_checksum_device(int device, const void *d_bytes, uint64_t n_bytes, uint64_t first_word,
+                                  uint64_t *out, void *stream);
 
 /* --- search ---------------------------------------------------------------- */
 /* queries: nq x dim fp32 host; out_ids: nq x k; out_scores: nq x k. */

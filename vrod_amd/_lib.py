@@ -31,9 +31,13 @@ SYMBOLS = [
     "vrod_search_diverse", "vrod_search_diverse_device",
     "vrod_search_combined", "vrod_search_combined_device",
     "vrod_search_candidates", "vrod_search_candidates_device", "vrod_score_candidates", "vrod_score_candidates_device",
+    "vrod_index_save", "vrod_index_load", "vrod_snapshot_info", "vrod_snapshot_verify",
+    "vrod_snapshot_checksum", "vrod_snapshot_checksum_device",
 ]
 
 ERR_CAPACITY = 8   # VROD_ERR_CAPACITY: a range search's result does not fit the caller's buffers (out_lims is valid)
+ERR_IO = 9         # VROD_ERR_IO: a snapshot's file could not be opened, read, written or renamed
+ERR_CORRUPT = 10   # VROD_ERR_CORRUPT: not a snapshot, truncated, sizes that disagree, a checksum mismatch
 
 
 class VrodError(RuntimeError):
@@ -61,6 +65,18 @@ class MultivecStats(C.Structure):
     _fields_ = [
         ("nq", C.c_uint32), ("vectors", C.c_uint32), ("k1", C.c_uint32), ("certified_queries", C.c_uint32),
         ("dense_queries", C.c_uint32), ("candidate_labels", C.c_uint64), ("candidate_rows", C.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class SnapshotInfo(C.Structure):
+    """struct vrod_snapshot_info: what a snapshot's header says."""
+    _fields_ = [
+        ("version", C.c_uint32), ("dim", C.c_uint32), ("dtype", C.c_uint32), ("metric", C.c_uint32),
+        ("count", C.c_uint64), ("live_count", C.c_uint64), ("id_offset", C.c_uint64), ("file_bytes", C.c_uint64),
+        ("has_filter", C.c_uint32), ("has_labels", C.c_uint32), ("has_tags", C.c_uint32), ("has_values", C.c_uint32),
     ]
 
     def as_dict(self):
@@ -145,6 +161,12 @@ def load() -> C.CDLL:
     L.vrod_search_candidates_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp, vp]
     L.vrod_score_candidates.argtypes = [vp, vp, u32, vp, vp, vp]
     L.vrod_score_candidates_device.argtypes = [vp, vp, u32, vp, vp, vp, vp]
+    L.vrod_index_save.argtypes = [vp, C.c_char_p]
+    L.vrod_index_load.argtypes = [C.POINTER(vp), C.c_char_p, C.POINTER(i32), i32]
+    L.vrod_snapshot_info.argtypes = [C.c_char_p, C.POINTER(SnapshotInfo)]
+    L.vrod_snapshot_verify.argtypes = [C.c_char_p]
+    L.vrod_snapshot_checksum.argtypes = [vp, u64, u64, C.POINTER(u64)]
+    L.vrod_snapshot_checksum_device.argtypes = [i32, vp, u64, u64, C.POINTER(u64), vp]
     for name in SYMBOLS:
         getattr(L, name).restype = i32
     L.vrod_last_error.restype = C.c_char_p

@@ -15,10 +15,13 @@
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <fcntl.h>
+#include <sys/stat.h>
 #include <unistd.h>
 #include <rccl/rccl.h>   // types and prototypes only: librccl is dlopen'ed when a multi-device handle is created
 
 #include <algorithm>
+#include <cerrno>
+#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -41,6 +44,7 @@
 #include "diverse_plan.h"
 #include "byid_plan.h"
 #include "combine_plan.h"
+#include "snapshot_plan.h"
 
 using namespace vrod;
 
@@ -289,6 +293,9 @@ struct vrod_index {
 
     // workspaces
     DevBuf raw_stage, nrm_ws, out_ids, out_scores;
+    // vrod_index_save: the two dense chunks the pack kernel writes and the copies to the host read (a handle made by
+    // vrod_index_load used it the other way round)
+    DevBuf snap_stage;
     // vrod_index_update: a chunk's prepared rows and their destination rows; vrod_index_compact: live rows below each
     // 32-row word (compact_plan.h compact_word_bases)
     DevBuf upd_stage, upd_dst, compact_ws;
@@ -3718,6 +3725,398 @@ static int knn_graph(vrod_index* idx, uint64_t row0, uint64_t n, uint32_t k, uin
     return VROD_OK;
 }
 
+// ------------------------------------------------------------------ snapshots (vrod_index_save, vrod_index_load)
+// The file format, its validation and the chunk arithmetic are snapshot_plan.h's, the kernels kernels_snapshot.hip's.
+// Here: the file I/O and the two-buffer pipeline between the device and the file.
+//   save   chunk c: pack kernel (rows -> dense staging, checksum) and the copy to pinned buffer c & 1 are enqueued on the
+//          handle's stream; the host then writes chunk c - 1 from the other buffer while they run.
+//   load   chunk c is read from the file into pinned buffer c & 1 while the copy to the device and the unpack kernel
+//          (dense staging -> rows, checksum) of chunk c - 1 run.
+// The side arrays take the same pipeline with a plain copy in place of the kernel and one checksum launch over the
+// device array.  The checksums are taken on the device, over device memory, on both sides: HBM -> file -> HBM is covered
+// end to end and the host makes no pass over the rows.  The bitmaps are the host mirrors' (the truth for both), checked
+// on the host: a 32nd of a byte per row.
+constexpr uint32_t kSnapSumWord = 32;   // idx->flags[32 .. 48): one 64-bit device sum per section kind (SNAP_KIND_END = 8)
+
+static int snap_status(SnapStatus st, const char* path, const char* why) {
+    if (st == SNAP_OK) return VROD_OK;
+    return fail(st == SNAP_UNSUPPORTED ? VROD_ERR_UNSUPPORTED : VROD_ERR_CORRUPT, "%s: %s", path, why);
+}
+
+struct SnapFd {
+    int fd = -1;
+    ~SnapFd() { if (fd >= 0) (void)close(fd); }
+};
+
+static int snap_pwrite(int fd, const void* p, uint64_t n, uint64_t off) {
+    const char* b = (const char*)p;
+    while (n) {
+        const ssize_t w = pwrite(fd, b, (size_t)n, (off_t)off);
+        if (w < 0 && errno == EINTR) continue;
+        if (w <= 0) return fail(VROD_ERR_IO, "writing the snapshot: %s", strerror(w < 0 ? errno : EIO));
+        b += w; off += (uint64_t)w; n -= (uint64_t)w;
+    }
+    return VROD_OK;
+}
+
+// (the file's length was checked against its header: a short read means it shrank since)
+static int snap_pread(int fd, void* p, uint64_t n, uint64_t off) {
+    char* b = (char*)p;
+    while (n) {
+        const ssize_t r = pread(fd, b, (size_t)n, (off_t)off);
+        if (r < 0 && errno == EINTR) continue;
+        if (r < 0) return fail(VROD_ERR_IO, "reading the snapshot: %s", strerror(errno));
+        if (r == 0) return fail(VROD_ERR_CORRUPT, "the snapshot ends before its header says (truncated)");
+        b += r; off += (uint64_t)r; n -= (uint64_t)r;
+    }
+    return VROD_OK;
+}
+
+// Opens `path`, reads and validates its header block against the file's real length.  No device call.
+static int snap_open(const char* path, SnapFd& f, SnapHeader& h) {
+    f.fd = open(path, O_RDONLY | O_CLOEXEC);
+    if (f.fd < 0) return fail(VROD_ERR_IO, "open %s: %s", path, strerror(errno));
+    struct stat st;
+    if (fstat(f.fd, &st) != 0) return fail(VROD_ERR_IO, "stat %s: %s", path, strerror(errno));
+    if (!S_ISREG(st.st_mode)) return fail(VROD_ERR_IO, "%s is not a regular file", path);
+    unsigned char block[kSnapBlock];
+    uint64_t have = 0;
+    while (have < kSnapBlock) {
+        const ssize_t r = pread(f.fd, block + have, kSnapBlock - have, (off_t)have);
+        if (r < 0 && errno == EINTR) continue;
+        if (r < 0) return fail(VROD_ERR_IO, "read %s: %s", path, strerror(errno));
+        if (r == 0) break;
+        have += (uint64_t)r;
+    }
+    const char* why = "";
+    return snap_status(snap_parse_header(block, have, (uint64_t)st.st_size, h, &why), path, why);
+}
+
+// The checksum of every section of at most max_bytes, on the host, 4 MiB at a time.
+static int snap_verify_sections(int fd, const char* path, const SnapHeader& h, uint64_t max_bytes) {
+    std::vector<unsigned char> buf;
+    for (uint32_t i = 0; i < h.n_sections; ++i) {
+        const SnapSection& sec = h.sections[i];
+        if (sec.bytes > max_bytes) continue;
+        const uint64_t piece = 4ull << 20;
+        buf.resize((size_t)std::min(piece, sec.bytes));
+        uint64_t sum = 0;
+        for (uint64_t off = 0; off < sec.bytes; off += piece) {
+            const uint64_t n = std::min(piece, sec.bytes - off);
+            VROD_TRY(snap_pread(fd, buf.data(), n, sec.offset + off));
+            sum += snap_checksum(buf.data(), n, off / 4);
+        }
+        if (sum != sec.checksum) return fail(VROD_ERR_CORRUPT, "%s: checksum mismatch in section %u", path, sec.kind);
+    }
+    return VROD_OK;
+}
+
+// The deleted-row bits (a 32nd of a byte per row) name count - live_count rows.
+static int snap_check_live(int fd, const char* path, const SnapHeader& h) {
+    std::vector<uint32_t> del((size_t)((h.count + 31) / 32));
+    VROD_TRY(snap_pread(fd, del.data(), del.size() * 4, h.find(SNAP_DELETED)->offset));
+    if (h.count - snap_count_bits(del.data(), h.count) != h.live_count)
+        return fail(VROD_ERR_CORRUPT, "%s: the deleted-row bits disagree with the live count", path);
+    return VROD_OK;
+}
+
+// Two pinned host buffers and the events behind the device work that reads or writes each.  VROD_DEBUG_SNAPSHOT_TIMING=1:
+// where a call's time went, one line on stderr -- the kernels and the copies by HIP events, the file I/O and the waits
+// for the device by the host's clock.
+struct SnapPipe {
+    hipStream_t stream = nullptr;
+    void* host[2] = {nullptr, nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    hipEvent_t tm[2][3] = {};   // timing: [buffer][before the first step | between the two | behind the second]
+    bool timing = false, used[2] = {false, false}, timed[2] = {false, false};
+    size_t bytes = 0;
+    double first_ms = 0, second_ms = 0, file_ms = 0, wait_ms = 0;
+    std::chrono::steady_clock::time_point t_open;
+    static double since(std::chrono::steady_clock::time_point t) {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+    }
+    int open(hipStream_t s, size_t n) {
+        stream = s;
+        bytes = n;
+        const char* e = getenv("VROD_DEBUG_SNAPSHOT_TIMING");
+        timing = e && e[0] == '1';
+        t_open = std::chrono::steady_clock::now();
+        for (int b = 0; b < 2; ++b) {
+            HIP_TRY(hipHostMalloc(&host[b], n, hipHostMallocDefault));
+            HIP_TRY(hipEventCreateWithFlags(&ev[b], hipEventDisableTiming));
+            if (timing) for (hipEvent_t& t : tm[b]) HIP_TRY(hipEventCreate(&t));
+        }
+        return VROD_OK;
+    }
+    int mark(int b, int i) {
+        if (timing) { HIP_TRY(hipEventRecord(tm[b][i], stream)); if (i == 2) timed[b] = true; }
+        return VROD_OK;
+    }
+    // the device is done with buffer b
+    int wait(int b) {
+        if (!used[b]) return VROD_OK;
+        const auto t = std::chrono::steady_clock::now();
+        HIP_TRY(hipEventSynchronize(ev[b]));
+        wait_ms += since(t);
+        used[b] = false;
+        if (timed[b]) {
+            float a = 0, c = 0;
+            HIP_TRY(hipEventElapsedTime(&a, tm[b][0], tm[b][1]));
+            HIP_TRY(hipEventElapsedTime(&c, tm[b][1], tm[b][2]));
+            first_ms += a; second_ms += c;
+            timed[b] = false;
+        }
+        return VROD_OK;
+    }
+    int submitted(int b) {
+        HIP_TRY(hipEventRecord(ev[b], stream));
+        used[b] = true;
+        return VROD_OK;
+    }
+    void report(const char* what, const char* first, const char* second, uint64_t file_bytes) const {
+        if (timing)
+            fprintf(stderr, "{\"vrod_snapshot\": \"%s\", \"file_bytes\": %llu, \"total_ms\": %.3f, \"%s_ms\": %.3f, \"%s_ms\": %.3f, "
+                    "\"file_ms\": %.3f, \"device_wait_ms\": %.3f}\n", what, (unsigned long long)file_bytes, since(t_open), first, first_ms,
+                    second, second_ms, file_ms, wait_ms);
+    }
+    ~SnapPipe() {
+        if (stream) (void)hipStreamSynchronize(stream);   // (a copy may still be aimed at a buffer)
+        for (int b = 0; b < 2; ++b) {
+            if (host[b]) (void)hipHostFree(host[b]);
+            if (ev[b]) (void)hipEventDestroy(ev[b]);
+            for (hipEvent_t t : tm[b]) if (t) (void)hipEventDestroy(t);
+        }
+    }
+};
+
+// `total` bytes in pieces of `piece` leave for the file at file_off: produce(off, n, b) enqueues whatever ends with bytes
+// [off, off + n) in pinned buffer b; piece c + 1 is enqueued before the host waits for piece c and writes it.
+template <typename F>
+static int snap_stream_out(SnapPipe& P, int fd, uint64_t file_off, uint64_t total, uint64_t piece, F&& produce) {
+    if (!total) return VROD_OK;
+    const uint64_t n_pieces = (total + piece - 1) / piece;
+    auto enqueue = [&](uint64_t c) -> int {
+        const int b = (int)(c & 1);
+        VROD_TRY(produce(c * piece, std::min(piece, total - c * piece), b));
+        return P.submitted(b);
+    };
+    VROD_TRY(enqueue(0));
+    for (uint64_t c = 0; c < n_pieces; ++c) {
+        if (c + 1 < n_pieces) VROD_TRY(enqueue(c + 1));
+        VROD_TRY(P.wait((int)(c & 1)));
+        const auto t = std::chrono::steady_clock::now();
+        VROD_TRY(snap_pwrite(fd, P.host[c & 1], std::min(piece, total - c * piece), file_off + c * piece));
+        P.file_ms += SnapPipe::since(t);
+    }
+    return VROD_OK;
+}
+
+// The inverse: piece c is read into pinned buffer c & 1 (once the device is done with what it held), then consume(off, n,
+// b) enqueues its way to the device; the read of piece c + 1 runs beside it.
+template <typename F>
+static int snap_stream_in(SnapPipe& P, int fd, uint64_t file_off, uint64_t total, uint64_t piece, F&& consume) {
+    for (uint64_t c = 0; c * piece < total; ++c) {
+        const int b = (int)(c & 1);
+        const uint64_t n = std::min(piece, total - c * piece);
+        VROD_TRY(P.wait(b));
+        const auto t = std::chrono::steady_clock::now();
+        VROD_TRY(snap_pread(fd, P.host[b], n, file_off + c * piece));
+        P.file_ms += SnapPipe::since(t);
+        VROD_TRY(consume(c * piece, n, b));
+        VROD_TRY(P.submitted(b));
+    }
+    return VROD_OK;
+}
+
+// rows per chunk of a save or load of `count` rows (a small handle gets small buffers)
+static uint64_t snap_chunk_rows_now(const vrod_index* idx, uint64_t count) {
+    const char* e = getenv("VROD_DEBUG_SNAPSHOT_CHUNK_ROWS");   // read at every call: tests reach the chunk seams at small sizes
+    return std::min(snap_chunk_rows(idx->dim, (uint32_t)idx->dtype, e ? strtoull(e, nullptr, 10) : 0), round_up(std::max<uint64_t>(count, 1), 32));
+}
+// bytes of one dense chunk in the staging buffers (whole words, whole 16-byte units)
+static size_t snap_stage_bytes(const vrod_index* idx, uint64_t chunk_rows) { return (size_t)round_up(chunk_rows * idx->dim * idx->esize, 16); }
+
+// the first ceil(count / 32) words of a host bitmap, the bits at and above `count` cleared
+static std::vector<uint32_t> snap_bitmap(const std::vector<uint32_t>& bits, uint64_t count) {
+    std::vector<uint32_t> w(bits.begin(), bits.begin() + (count + 31) / 32);
+    if (count % 32) w.back() &= (1u << (count % 32)) - 1u;
+    return w;
+}
+
+static int snap_save_body(vrod_index* idx, int fd) {
+    VROD_TRY(set_device(idx));
+    hipStream_t s = idx->stream;
+    const uint64_t count = idx->count, es = idx->esize;
+    SnapHeader h;
+    h.dim = idx->dim; h.dtype = (uint32_t)idx->dtype; h.metric = (uint32_t)idx->metric;
+    h.count = count; h.live_count = idx->live(); h.id_offset = idx->id_offset;
+    auto add = [&](uint32_t kind) { h.sections[h.n_sections].kind = kind; h.sections[h.n_sections++].bytes = snap_section_bytes(kind, count, h.dim, h.dtype); };
+    add(SNAP_ROWS); add(SNAP_NORMS); add(SNAP_DELETED);
+    if (idx->filter_on) add(SNAP_FILTER);
+    if (idx->lab_dev) add(SNAP_LABELS);
+    if (idx->tag_dev) add(SNAP_TAGS);
+    if (idx->val_dev) add(SNAP_VALUES);
+    snap_layout(h);
+    if (ftruncate(fd, (off_t)h.file_bytes) != 0) return fail(VROD_ERR_IO, "sizing the snapshot: %s", strerror(errno));   // (the padding: zeros)
+
+    const uint64_t chunk = snap_chunk_rows_now(idx, count);
+    const size_t stage = snap_stage_bytes(idx, chunk);
+    uint64_t* d_sum = (uint64_t*)(idx->flags + kSnapSumWord);
+    uint64_t h_sum[SNAP_KIND_END] = {};
+    {
+        SnapPipe P;
+        VROD_TRY(P.open(s, stage));
+        VROD_TRY(idx->snap_stage.ensure(2 * stage));
+        HIP_TRY(hipMemsetAsync(d_sum, 0, sizeof h_sum, s));
+        HIP_TRY(hipMemcpyAsync(&h.max_xn2_bits, idx->max_xn2_bits, 4, hipMemcpyDeviceToHost, s));
+        for (uint32_t i = 0; i < h.n_sections; ++i) {
+            const SnapSection& sec = h.sections[i];
+            if (sec.kind == SNAP_ROWS) {
+                VROD_TRY(snap_stream_out(P, fd, sec.offset, sec.bytes, chunk * idx->dim * es, [&](uint64_t off, uint64_t n, int b) -> int {
+                    const uint64_t r0 = off / (idx->dim * es), m = n / (idx->dim * es);
+                    char* dense = idx->snap_stage.as<char>() + (size_t)b * stage;
+                    VROD_TRY(P.mark(b, 0));
+                    launch_snapshot_pack((const char*)idx->corpus + r0 * idx->row_bytes(), m, idx->dim, idx->ld, idx->dtype, dense, off / 4,
+                                         d_sum + SNAP_ROWS, s);
+                    HIP_TRY(hipGetLastError());
+                    VROD_TRY(P.mark(b, 1));
+                    HIP_TRY(hipMemcpyAsync(P.host[b], dense, round_up(n, 4), hipMemcpyDeviceToHost, s));
+                    return P.mark(b, 2);
+                }));
+                continue;
+            }
+            const void* d_arr = sec.kind == SNAP_NORMS ? (const void*)idx->xnorm2 : sec.kind == SNAP_LABELS ? (const void*)idx->lab_dev
+                              : sec.kind == SNAP_TAGS ? (const void*)idx->tag_dev : sec.kind == SNAP_VALUES ? (const void*)idx->val_dev : nullptr;
+            if (!d_arr) continue;   // the bitmaps: below
+            launch_snapshot_checksum(d_arr, sec.bytes, 0, d_sum + sec.kind, s);
+            HIP_TRY(hipGetLastError());
+            VROD_TRY(snap_stream_out(P, fd, sec.offset, sec.bytes, stage, [&](uint64_t off, uint64_t n, int b) -> int {
+                HIP_TRY(hipMemcpyAsync(P.host[b], (const char*)d_arr + off, n, hipMemcpyDeviceToHost, s));
+                return VROD_OK;
+            }));
+        }
+        HIP_TRY(hipMemcpyAsync(h_sum, d_sum, sizeof h_sum, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        P.report("save", "pack_kernel", "copy_d2h", h.file_bytes);
+    }
+    for (uint32_t i = 0; i < h.n_sections; ++i) {
+        SnapSection& sec = h.sections[i];
+        if (sec.kind == SNAP_DELETED || sec.kind == SNAP_FILTER) {
+            const std::vector<uint32_t> w = snap_bitmap(sec.kind == SNAP_DELETED ? idx->del_bits : idx->allow_bits, count);
+            sec.checksum = snap_checksum(w.data(), sec.bytes, 0);
+            VROD_TRY(snap_pwrite(fd, w.data(), sec.bytes, sec.offset));
+        } else {
+            sec.checksum = h_sum[sec.kind];
+        }
+    }
+    unsigned char block[kSnapBlock];
+    snap_encode_header(h, block);
+    VROD_TRY(snap_pwrite(fd, block, kSnapBlock, 0));
+    if (fsync(fd) != 0) return fail(VROD_ERR_IO, "fsync of the snapshot: %s", strerror(errno));
+    return VROD_OK;
+}
+
+// a side array of a loaded handle: device copy and host mirror over the capacity, rows [0, count) from the file
+template <typename T>
+static int snap_load_side(vrod_index* idx, SnapPipe& P, int fd, const SnapSection& sec, std::vector<T>& host, T*& dev, uint64_t* d_sum) {
+    hipStream_t s = idx->stream;
+    T* d = nullptr;
+    HIP_TRY(hipMalloc((void**)&d, idx->capacity * sizeof(T)));
+    dev = d;   // (the handle owns it from here: a failure below is followed by vrod_index_destroy)
+    HIP_TRY(hipMemsetAsync(d, 0, idx->capacity * sizeof(T), s));
+    host.assign(idx->capacity, T(0));
+    VROD_TRY(snap_stream_in(P, fd, sec.offset, sec.bytes, P.bytes / 8 * 8, [&](uint64_t off, uint64_t n, int b) -> int {
+        memcpy((char*)host.data() + off, P.host[b], n);
+        HIP_TRY(hipMemcpyAsync((char*)d + off, P.host[b], n, hipMemcpyHostToDevice, s));
+        return VROD_OK;
+    }));
+    launch_snapshot_checksum(d, sec.bytes, 0, d_sum + sec.kind, s);
+    HIP_TRY(hipGetLastError());
+    return VROD_OK;
+}
+
+// Fills a freshly created handle from an open, validated snapshot.
+static int snap_load_body(vrod_index* idx, int fd, const char* path, const SnapHeader& h) {
+    VROD_TRY(set_device(idx));
+    hipStream_t s = idx->stream;
+    const uint64_t count = h.count, es = idx->esize;
+    idx->id_offset = h.id_offset;
+    VROD_TRY(index_reserve(idx, count));   // every byte of the new allocations is zero: row padding, rows past the count
+
+    // the bitmaps first, on the host
+    const SnapSection* sec_del = h.find(SNAP_DELETED);
+    VROD_TRY(snap_pread(fd, idx->del_bits.data(), sec_del->bytes, sec_del->offset));
+    if (snap_checksum(idx->del_bits.data(), sec_del->bytes, 0) != sec_del->checksum)
+        return fail(VROD_ERR_CORRUPT, "%s: checksum mismatch in section %u", path, (unsigned)SNAP_DELETED);
+    if (count % 32) idx->del_bits[count / 32] &= (1u << (count % 32)) - 1u;
+    const uint64_t n_deleted = snap_count_bits(idx->del_bits.data(), count);   // (checked against the live count before the device was opened)
+    std::vector<uint32_t> allow;
+    if (const SnapSection* sec = h.find(SNAP_FILTER)) {
+        allow.resize((size_t)(sec->bytes / 4));
+        VROD_TRY(snap_pread(fd, allow.data(), sec->bytes, sec->offset));
+        if (snap_checksum(allow.data(), sec->bytes, 0) != sec->checksum)
+            return fail(VROD_ERR_CORRUPT, "%s: checksum mismatch in section %u", path, (unsigned)SNAP_FILTER);
+    }
+
+    const uint64_t chunk = snap_chunk_rows_now(idx, count);
+    const size_t stage = snap_stage_bytes(idx, chunk);
+    uint64_t* d_sum = (uint64_t*)(idx->flags + kSnapSumWord);
+    uint64_t h_sum[SNAP_KIND_END] = {};
+    {
+        SnapPipe P;
+        VROD_TRY(P.open(s, stage));
+        VROD_TRY(idx->snap_stage.ensure(2 * stage));
+        HIP_TRY(hipMemsetAsync(d_sum, 0, sizeof h_sum, s));
+        const SnapSection* rows = h.find(SNAP_ROWS);
+        VROD_TRY(snap_stream_in(P, fd, rows->offset, rows->bytes, chunk * idx->dim * es, [&](uint64_t off, uint64_t n, int b) -> int {
+            const uint64_t r0 = off / (idx->dim * es), m = n / (idx->dim * es);
+            char* dense = idx->snap_stage.as<char>() + (size_t)b * stage;
+            if (n % 4) memset((char*)P.host[b] + n, 0, 4 - n % 4);   // the zero fill of the payload's last word
+            VROD_TRY(P.mark(b, 0));
+            HIP_TRY(hipMemcpyAsync(dense, P.host[b], round_up(n, 4), hipMemcpyHostToDevice, s));
+            VROD_TRY(P.mark(b, 1));
+            launch_snapshot_unpack(dense, m, idx->dim, idx->ld, idx->dtype, (char*)idx->corpus + r0 * idx->row_bytes(), off / 4,
+                                   d_sum + SNAP_ROWS, s);
+            HIP_TRY(hipGetLastError());
+            return P.mark(b, 2);
+        }));
+        const SnapSection* norms = h.find(SNAP_NORMS);
+        VROD_TRY(snap_stream_in(P, fd, norms->offset, norms->bytes, stage / 4 * 4, [&](uint64_t off, uint64_t n, int b) -> int {
+            HIP_TRY(hipMemcpyAsync((char*)idx->xnorm2 + off, P.host[b], n, hipMemcpyHostToDevice, s));
+            return VROD_OK;
+        }));
+        launch_snapshot_checksum(idx->xnorm2, norms->bytes, 0, d_sum + SNAP_NORMS, s);
+        HIP_TRY(hipGetLastError());
+        if (const SnapSection* sec = h.find(SNAP_LABELS)) VROD_TRY(snap_load_side(idx, P, fd, *sec, idx->lab_bits, idx->lab_dev, d_sum));
+        if (const SnapSection* sec = h.find(SNAP_TAGS)) VROD_TRY(snap_load_side(idx, P, fd, *sec, idx->tag_bits, idx->tag_dev, d_sum));
+        if (const SnapSection* sec = h.find(SNAP_VALUES)) VROD_TRY(snap_load_side(idx, P, fd, *sec, idx->val_bits, idx->val_dev, d_sum));
+        HIP_TRY(hipMemcpyAsync(idx->max_xn2_bits, &h.max_xn2_bits, 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(h_sum, d_sum, sizeof h_sum, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        P.report("load", "copy_h2d", "unpack_kernel", h.file_bytes);
+    }
+    for (uint32_t i = 0; i < h.n_sections; ++i) {
+        const SnapSection& sec = h.sections[i];
+        if (sec.kind == SNAP_DELETED || sec.kind == SNAP_FILTER) continue;
+        if (h_sum[sec.kind] != sec.checksum)
+            return fail(VROD_ERR_CORRUPT, "%s: checksum mismatch in section %u (as it arrived in device memory)", path, sec.kind);
+    }
+    idx->count = count;
+    if (n_deleted) {
+        HIP_TRY(hipMalloc((void**)&idx->del_dev, idx->del_bits.size() * 4));
+        HIP_TRY(hipMemcpy(idx->del_dev, idx->del_bits.data(), idx->del_bits.size() * 4, hipMemcpyHostToDevice));
+        idx->n_deleted = n_deleted;
+        mask_changed(idx);
+    }
+    // rows the filter does not name are not allowed, so the file's ceil(count / 32) words over `count` rows give the
+    // effective mask and the eligible count the saved handle had, whatever n_rows its filter was set with
+    if (h.find(SNAP_FILTER)) {
+        static const uint32_t kNone = 0u;
+        VROD_TRY(index_set_filter(idx, count ? allow.data() : &kNone, count));
+    }
+    return VROD_OK;
+}
+
 // ------------------------------------------------------------------ C ABI
 extern "C" {
 
@@ -4693,6 +5092,89 @@ int vrod_merge_topk_packed_device(int device, int metric, const void* d_packed, 
     const float* scores = (const float*)((const char*)d_packed + (uint64_t)nq * k * 8);
     launch_merge_topk(score_form(metric), ids, scores, block_bytes / 8, block_bytes / 4, n_lists, nq, k, d_out_ids, d_out_scores, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return VROD_OK;
+}
+
+int vrod_index_save(vrod_index* idx, const char* path) {
+    if (!idx || !path || !path[0]) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "vrod_index_save on a multi-device handle: a snapshot holds one device's rows");
+    VROD_TRY(require_idle(idx, "vrod_index_save"));
+    const std::string tmp = std::string(path) + ".tmp";
+    SnapFd f;
+    f.fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
+    if (f.fd < 0) return fail(VROD_ERR_IO, "open %s: %s", tmp.c_str(), strerror(errno));
+    int rc = snap_save_body(idx, f.fd);
+    if (close(f.fd) != 0 && rc == VROD_OK) rc = fail(VROD_ERR_IO, "close %s: %s", tmp.c_str(), strerror(errno));
+    f.fd = -1;
+    if (rc == VROD_OK && rename(tmp.c_str(), path) != 0) rc = fail(VROD_ERR_IO, "rename %s -> %s: %s", tmp.c_str(), path, strerror(errno));
+    if (rc != VROD_OK) (void)unlink(tmp.c_str());   // whatever is at `path` stays as it was
+    return rc;
+}
+
+int vrod_index_load(vrod_index** out, const char* path, const int* device_ids, int n_devices) {
+    if (!out) return fail(VROD_ERR_INVALID_ARG, "out is null");
+    *out = nullptr;
+    if (!path || !path[0] || n_devices < 0 || (n_devices > 0 && !device_ids)) return fail(VROD_ERR_INVALID_ARG, "null argument or bad device list");
+    if (n_devices > 1) return fail(VROD_ERR_UNSUPPORTED, "vrod_index_load onto a multi-device handle: a snapshot holds one device's rows");
+    // everything that needs no device, before the first device call
+    SnapFd f;
+    SnapHeader h;
+    VROD_TRY(snap_open(path, f, h));
+    VROD_TRY(snap_verify_sections(f.fd, path, h, kSnapHostVerifyBytes));
+    VROD_TRY(snap_check_live(f.fd, path, h));
+    vrod_index* idx = nullptr;
+    VROD_TRY(vrod_index_create(&idx, h.dim, (int)h.dtype, (int)h.metric, device_ids, n_devices));
+    const int rc = snap_load_body(idx, f.fd, path, h);
+    if (rc != VROD_OK) {
+        const std::string why = g_last_error;
+        vrod_index_destroy(idx);
+        g_last_error = why;
+        return rc;
+    }
+    *out = idx;
+    return VROD_OK;
+}
+
+int vrod_snapshot_info(const char* path, struct vrod_snapshot_info* out) {
+    if (!path || !out) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    SnapFd f;
+    SnapHeader h;
+    VROD_TRY(snap_open(path, f, h));
+    out->version = h.version; out->dim = h.dim; out->dtype = h.dtype; out->metric = h.metric;
+    out->count = h.count; out->live_count = h.live_count; out->id_offset = h.id_offset; out->file_bytes = h.file_bytes;
+    out->has_filter = h.find(SNAP_FILTER) != nullptr;
+    out->has_labels = h.find(SNAP_LABELS) != nullptr;
+    out->has_tags = h.find(SNAP_TAGS) != nullptr;
+    out->has_values = h.find(SNAP_VALUES) != nullptr;
+    return VROD_OK;
+}
+
+int vrod_snapshot_verify(const char* path) {
+    if (!path) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    SnapFd f;
+    SnapHeader h;
+    VROD_TRY(snap_open(path, f, h));
+    VROD_TRY(snap_verify_sections(f.fd, path, h, UINT64_MAX));
+    return snap_check_live(f.fd, path, h);
+}
+
+int vrod_snapshot_checksum(const void* bytes, uint64_t n_bytes, uint64_t first_word, uint64_t* out) {
+    if (!out || (!bytes && n_bytes)) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    *out = snap_checksum(bytes, n_bytes, first_word);
+    return VROD_OK;
+}
+
+int vrod_snapshot_checksum_device(int device, const void* d_bytes, uint64_t n_bytes, uint64_t first_word, uint64_t* out, void* stream) {
+    if (!out || (!d_bytes && n_bytes)) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    if ((uintptr_t)d_bytes % 4) return fail(VROD_ERR_INVALID_ARG, "d_bytes must be 4-byte aligned");
+    HIP_TRY(hipSetDevice(device));
+    DevBuf sum;
+    VROD_TRY(sum.ensure(8));
+    HIP_TRY(hipMemsetAsync(sum.p, 0, 8, (hipStream_t)stream));
+    launch_snapshot_checksum(d_bytes, n_bytes, first_word, sum.as<uint64_t>(), (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, sum.p, 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return VROD_OK;
 }

@@ -77,6 +77,17 @@ void launch_compact_rows(const void* d_rows, const float* d_xn2, const uint32_t*
 // *d_max_bits (cleared by the caller) = max of d_xn2[0, n) as float bits
 void launch_xn2_max(const float* d_xn2, uint64_t n, uint32_t* d_max_bits, hipStream_t s);
 
+// ---- kernels_snapshot.hip : vrod_index_save / vrod_index_load
+// Pack: n_rows stored rows (pitch ld) -> d_dense, [n_rows][dim] elements; unpack: the inverse (only the rows' elements are
+// written).  Both add the checksum terms (snapshot_plan.h) of the dense words, the first of which has the section-wide
+// index first_word, to *d_sum.  n_rows * dim * element size <= kSnapChunkBytesMax; d_dense holds that rounded up to 4.
+void launch_snapshot_pack(const void* d_rows, uint64_t n_rows, uint32_t dim, uint32_t ld, int dtype, void* d_dense, uint64_t first_word,
+                          uint64_t* d_sum, hipStream_t s);
+void launch_snapshot_unpack(const void* d_dense, uint64_t n_rows, uint32_t dim, uint32_t ld, int dtype, void* d_rows, uint64_t first_word,
+                            uint64_t* d_sum, hipStream_t s);
+// *d_sum += the checksum terms of n_bytes at d_bytes (4-byte aligned)
+void launch_snapshot_checksum(const void* d_bytes, uint64_t n_bytes, uint64_t first_word, uint64_t* d_sum, hipStream_t s);
+
 // ---- kernels_stream.hip : Q <= 8 HBM-bound scan, writes fast scores [nq_pad][score_ld]
 // nq_pad in {1,2,4,8}; d_q is [nq_pad][ld] prepared fp32 (zero rows for padding).
 // Also accumulates, per query, a histogram of the top stream_hist_bits(nq_pad) bits of the

@@ -7,11 +7,12 @@ here: device buffers, streams and torch.distributed for the RCCL all-gather).
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 
 from . import _lib
-from ._lib import MultivecStats, SearchStats, VrodError, check
+from ._lib import MultivecStats, SearchStats, SnapshotInfo, VrodError, check
 
 DTYPE_F32, DTYPE_BF16 = 0, 1
 METRIC_COSINE, METRIC_L2, METRIC_IP = 0, 1, 2
@@ -77,6 +78,25 @@ class Index:
         self.device = ids[0]
         dev = (C.c_int * len(ids))(*ids)
         check(self._L.vrod_index_create(C.byref(self._h), self.dim, self.dtype, self.metric, dev, len(ids)))
+
+    # -- snapshots
+    def save(self, path):
+        """Write the handle's whole observable state to `path` (vrod_index_save): atomic, deterministic bytes."""
+        check(self._L.vrod_index_save(self._h, os.fsencode(path)))
+
+    @classmethod
+    def load(cls, path, device: int = 0):
+        """A new handle from a snapshot (vrod_index_load): it answers every call as the saved one did, to the bit."""
+        self = cls.__new__(cls)
+        self._L = _lib.load()
+        self._h = C.c_void_p()
+        self.device = int(device)
+        dev = (C.c_int * 1)(self.device)
+        check(self._L.vrod_index_load(C.byref(self._h), os.fsencode(path), dev, 1))
+        info = snapshot_info(path)
+        self.dim, self.dtype, self.metric = info["dim"], info["dtype"], info["metric"]
+        self._id_offset = info["id_offset"]
+        return self
 
     # -- lifecycle
     def close(self):
@@ -840,6 +860,18 @@ class Index:
         out = C.c_uint32()
         check(self._L.vrod_search_pending(self._h, C.byref(out)))
         return out.value
+
+
+def snapshot_info(path) -> dict:
+    """What a snapshot's header says (vrod_snapshot_info): host only, the header block alone is read."""
+    out = SnapshotInfo()
+    check(_lib.load().vrod_snapshot_info(os.fsencode(path), C.byref(out)))
+    return out.as_dict()
+
+
+def snapshot_verify(path) -> None:
+    """Check a whole snapshot file on the host (vrod_snapshot_verify): raises VrodError if it is not sound."""
+    check(_lib.load().vrod_snapshot_verify(os.fsencode(path)))
 
 
 def merge_topk_device(device: int, metric, ids, scores, out_ids=None, out_scores=None):
