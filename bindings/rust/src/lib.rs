@@ -125,6 +125,17 @@ pub struct vrod_multivec_stats {
     pub candidate_rows: u64,
 }
 
+/// `vrod_key_stats`: the state of a handle's key table.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct vrod_key_stats {
+    pub keyed_live: u64,
+    pub slots: u64,
+    pub occupied: u64,
+    pub rebuilds: u64,
+    pub max_probe: u64,
+}
+
 extern "C" {
     pub fn vrod_index_create(out: *mut *mut vrod_index, dim: u32, dtype: c_int, metric: c_int,
                              device_ids: *const c_int, n_devices: c_int) -> c_int;
@@ -250,6 +261,16 @@ extern "C" {
     pub fn vrod_snapshot_checksum(bytes: *const c_void, n_bytes: u64, first_word: u64, out: *mut u64) -> c_int;
     pub fn vrod_snapshot_checksum_device(device: c_int, d_bytes: *const c_void, n_bytes: u64, first_word: u64, out: *mut u64,
                                          stream: *mut c_void) -> c_int;
+    /// Row keys: caller-chosen 64-bit names that survive `vrod_index_compact`, unique among the live rows.
+    pub fn vrod_index_set_keys(idx: *mut vrod_index, first_id: u64, keys: *const u64, n: u64) -> c_int;
+    pub fn vrod_index_get_keys(idx: *mut vrod_index, first_id: u64, n: u64, out_keys: *mut u64) -> c_int;
+    pub fn vrod_index_find_keys(idx: *mut vrod_index, keys: *const u64, n: u64, out_ids: *mut u64) -> c_int;
+    pub fn vrod_index_find_keys_device(idx: *mut vrod_index, d_keys: *const u64, n: u64, d_out_ids: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn vrod_index_ids_to_keys(idx: *mut vrod_index, ids: *const u64, n: u64, out_keys: *mut u64) -> c_int;
+    pub fn vrod_index_ids_to_keys_device(idx: *mut vrod_index, d_ids: *const u64, n: u64, d_out_keys: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn vrod_index_delete_keys(idx: *mut vrod_index, keys: *const u64, n: u64, out_deleted: *mut u64) -> c_int;
+    pub fn vrod_index_upsert(idx: *mut vrod_index, keys: *const u64, rows: *const f32, n: u64, out_ids: *mut u64) -> c_int;
+    pub fn vrod_index_key_stats(idx: *const vrod_index, out: *mut vrod_key_stats) -> c_int;
 }
 
 /// Joins the reference's `thiserror` enums (`src/main.rs:36-40`, `src/command/builder.rs:10-15`).
@@ -485,6 +506,63 @@ impl Collection {
             vrod_search_where(self.idx, flat.as_ptr(), queries.len() as u32, k as u32, preds.as_ptr(), ids.as_mut_ptr(), scores.as_mut_ptr())
         })?;
         Ok((ids, scores))
+    }
+}
+
+impl Collection {
+    /// Give the rows with ids `first_id..first_id + keys.len()` the caller's keys (`u64::MAX`: no key).  No two live rows
+    /// may hold the same key; a host that keys its payloads by them renumbers nothing after `compact`.
+    pub fn set_keys(&mut self, first_id: u64, keys: &[u64]) -> Result<(), ScanError> {
+        check(unsafe { vrod_index_set_keys(self.idx, first_id, keys.as_ptr(), keys.len() as u64) })
+    }
+
+    pub fn keys(&self, first_id: u64, n: usize) -> Result<Vec<u64>, ScanError> {
+        let mut out = vec![u64::MAX; n];
+        check(unsafe { vrod_index_get_keys(self.idx, first_id, n as u64, out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+
+    /// The id of the live row that holds each key, `u64::MAX` where none does.
+    pub fn find_keys(&self, keys: &[u64]) -> Result<Vec<u64>, ScanError> {
+        let mut out = vec![u64::MAX; keys.len()];
+        check(unsafe { vrod_index_find_keys(self.idx, keys.as_ptr(), keys.len() as u64, out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+
+    /// The key each id's row stores (a search's ids -> the caller's names), `u64::MAX` where there is none.
+    pub fn ids_to_keys(&self, ids: &[u64]) -> Result<Vec<u64>, ScanError> {
+        let mut out = vec![u64::MAX; ids.len()];
+        check(unsafe { vrod_index_ids_to_keys(self.idx, ids.as_ptr(), ids.len() as u64, out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+
+    /// Delete the live row of each key; unknown keys are ignored.  Returns the number of rows that died.
+    pub fn delete_keys(&mut self, keys: &[u64]) -> Result<u64, ScanError> {
+        let mut died = 0u64;
+        check(unsafe { vrod_index_delete_keys(self.idx, keys.as_ptr(), keys.len() as u64, &mut died) })?;
+        Ok(died)
+    }
+
+    /// Update the row of each key in place, or append it and give it the key.  Returns each key's id.
+    pub fn upsert(&mut self, keys: &[u64], embeddings: &[Vec<f32>]) -> Result<Vec<u64>, ScanError> {
+        if embeddings.len() != keys.len() {
+            return Err(ScanError::Dim { got: embeddings.len(), want: keys.len() });
+        }
+        for e in embeddings {
+            if e.len() != self.dim {
+                return Err(ScanError::Dim { got: e.len(), want: self.dim });
+            }
+        }
+        let flat: Vec<f32> = embeddings.iter().flatten().copied().collect();
+        let mut ids = vec![u64::MAX; keys.len()];
+        check(unsafe { vrod_index_upsert(self.idx, keys.as_ptr(), flat.as_ptr(), keys.len() as u64, ids.as_mut_ptr()) })?;
+        Ok(ids)
+    }
+
+    pub fn key_stats(&self) -> Result<vrod_key_stats, ScanError> {
+        let mut st = vrod_key_stats::default();
+        check(unsafe { vrod_index_key_stats(self.idx, &mut st) })?;
+        Ok(st)
     }
 }
 

@@ -220,6 +220,65 @@ int vrod_index_get_tags(vrod_index *idx, uint64_t first_id, uint64_t n, uint64_t
  * set_values returns VROD_ERR_UNSUPPORTED and changes nothing (get_values reports the zeros every row carries). */
 int vrod_index_set_values(vrod_index *idx, uint64_t first_id, const int64_t *values, uint64_t n);
 int vrod_index_get_values(vrod_index *idx, uint64_t first_id, uint64_t n, int64_t *out_values);
+/* Row keys: every row carries one uint64_t key chosen by the caller -- VROD_ID_NONE ("no key") until set, and for rows
+ * added later -- that names the row across vrod_index_compact, which renumbers ids.  No search reads keys; ids stay
+ * insertion indices and every other entry point returns what it returns on a handle without keys.
+ * set_keys / get_keys follow the rules of the values: the rows with ids [first_id, first_id + n) (ids as searches report
+ * them, id_offset applied; deleted rows may be named) take keys[0 .. n) (host memory); a range that is not wholly within
+ * the current rows fails with VROD_ERR_INVALID_ARG and changes nothing; n == 0 does nothing; the device arrays are
+ * allocated by the first set_keys; while a search is pending: VROD_ERR_INVALID_ARG; multi-device handles:
+ * VROD_ERR_UNSUPPORTED (get_keys reports VROD_ID_NONE for every row).  And one rule of their own:
+ *   uniqueness  after a successful call no two LIVE rows hold the same key; VROD_ID_NONE may repeat, and setting it clears
+ *               a row's key.  A call in which two live rows of the range would get the same key, or which gives a live
+ *               row a key that a live row outside the range holds, fails with VROD_ERR_INVALID_ARG and changes nothing.
+ *               Re-keying is fine: a permutation of the range's keys, the same keys again; a row's old key is free once
+ *               the call succeeds.  Keys given to deleted rows are stored and read back by get_keys, are never found and
+ *               take no part in uniqueness.
+ * vrod_index_update keeps a row's key, vrod_index_delete frees it (the key is no longer found and may be given to another
+ * row), vrod_index_compact moves keys with their rows, a snapshot holds them once they were set (a file in which two live
+ * rows share a key: VROD_ERR_CORRUPT at load; builds older than the section answer VROD_ERR_UNSUPPORTED to such a file).
+ * The keys are found through an open-addressing table in device memory (linear probing, a power of two of slots, at
+ * least 1024; DESIGN.md "Row keys").  The home slot of a key is part of this contract: z = key + 0x9E3779B97F4A7C15,
+ * z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9, z = (z ^ z >> 27) * 0x94D049BB133111EB, z ^= z >> 31, home = z & (slots - 1),
+ * all mod 2^64 (the mixer of the snapshot checksum).  Slots of deleted or re-keyed rows stay behind; the occupied slots,
+ * those included, never exceed slots / 2: before an insert could cross that, the table is rebuilt from the live keyed
+ * rows, doubled until they and the incoming keys fit in a quarter of it.  It is also rebuilt by vrod_index_compact and
+ * built by vrod_index_load.  Every walk is bounded by the slot count: one that runs out is VROD_ERR_INTERNAL, not a hang.
+ *   find_keys     out_ids[i] = the id (id_offset applied) of the live row that holds keys[i]; VROD_ID_NONE for a key no
+ *                 live row holds and for VROD_ID_NONE itself.  Keys may repeat.  The filter is not consulted: a key names
+ *                 a row whether or not the next search may return it.  Keys never set: every answer is VROD_ID_NONE.
+ *   ids_to_keys   out_keys[i] = the key row ids[i] stores -- a deleted row's too -- or VROD_ID_NONE for VROD_ID_NONE (an
+ *                 unfilled result slot), an id that is not a current row, or a row without a key: it turns any search's
+ *                 nq x k ids into the caller's names.
+ *   The _device forms take device pointers and a stream (the caller's work on it is complete before the library starts)
+ *   and return after the results are complete in device memory.  All four: VROD_ERR_INVALID_ARG while a search is pending,
+ *   VROD_ERR_UNSUPPORTED on multi-device handles, outputs untouched.
+ *   delete_keys   deletes the live row of each key as vrod_index_delete would; a key no live row holds is ignored (lists
+ *                 kept outside outlive deletes), repeats are fine; *out_deleted (may be NULL) = rows that died.
+ *   upsert        rows: n x dim fp32, host memory.  If a live row holds keys[i] it is updated in place exactly as
+ *                 vrod_index_update would (it keeps its id, label, tags and value); otherwise rows[i] is appended exactly
+ *                 as vrod_index_add would and gets the key; appended rows take the next ids in the order of the call.
+ *                 out_ids (may be NULL) receives each key's id.  VROD_ID_NONE as a key or a key twice in one call:
+ *                 VROD_ERR_INVALID_ARG; NaN or Inf anywhere in rows: VROD_ERR_INVALID_VALUE; every check comes before
+ *                 the first row is written, a refused call changes nothing.  Afterwards every search gives bit for bit
+ *                 what it gives on a handle that had the same update and add calls made on it.
+ * vrod_index_key_stats: all zero before the first set_keys. */
+typedef struct {
+    uint64_t keyed_live;   /* live rows with a key */
+    uint64_t slots;
+    uint64_t occupied;     /* slots in use, stale ones included */
+    uint64_t rebuilds;     /* since the handle was created or loaded */
+    uint64_t max_probe;    /* the longest walk an insert or rebuild has made since the last rebuild, in slots */
+} vrod_key_stats;
+int vrod_index_set_keys(vrod_index *idx, uint64_t first_id, const uint64_t *keys, uint64_t n);
+int vrod_index_get_keys(vrod_index *idx, uint64_t first_id, uint64_t n, uint64_t *out_keys);
+int vrod_index_find_keys(vrod_index *idx, const uint64_t *keys, uint64_t n, uint64_t *out_ids);
+int vrod_index_find_keys_device(vrod_index *idx, const uint64_t *d_keys, uint64_t n, uint64_t *d_out_ids, void *stream);
+int vrod_index_ids_to_keys(vrod_index *idx, const uint64_t *ids, uint64_t n, uint64_t *out_keys);
+int vrod_index_ids_to_keys_device(vrod_index *idx, const uint64_t *d_ids, uint64_t n, uint64_t *d_out_keys, void *stream);
+int vrod_index_delete_keys(vrod_index *idx, const uint64_t *keys, uint64_t n, uint64_t *out_deleted);
+int vrod_index_upsert(vrod_index *idx, const uint64_t *keys, const float *rows, uint64_t n, uint64_t *out_ids);
+int vrod_index_key_stats(const vrod_index *idx, vrod_key_stats *out);
 /* Copy prepared rows [first, first+n) back as fp32 (bf16 widened): n x dim. */
 int vrod_index_get_rows(vrod_index *idx, uint64_t first, uint64_t n, float *out_rows);
 

@@ -33,6 +33,9 @@ SYMBOLS = [
     "vrod_search_candidates", "vrod_search_candidates_device", "vrod_score_candidates", "vrod_score_candidates_device",
     "vrod_index_save", "vrod_index_load", "vrod_snapshot_info", "vrod_snapshot_verify",
     "vrod_snapshot_checksum", "vrod_snapshot_checksum_device",
+    "vrod_index_set_keys", "vrod_index_get_keys", "vrod_index_find_keys", "vrod_index_find_keys_device",
+    "vrod_index_ids_to_keys", "vrod_index_ids_to_keys_device", "vrod_index_delete_keys", "vrod_index_upsert",
+    "vrod_index_key_stats",
 ]
 
 ERR_CAPACITY = 8   # VROD_ERR_CAPACITY: a range search's result does not fit the caller's buffers (out_lims is valid)
@@ -78,6 +81,15 @@ class SnapshotInfo(C.Structure):
         ("count", C.c_uint64), ("live_count", C.c_uint64), ("id_offset", C.c_uint64), ("file_bytes", C.c_uint64),
         ("has_filter", C.c_uint32), ("has_labels", C.c_uint32), ("has_tags", C.c_uint32), ("has_values", C.c_uint32),
     ]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class KeyStats(C.Structure):
+    """vrod_key_stats: the state of a handle's key table."""
+    _fields_ = [("keyed_live", C.c_uint64), ("slots", C.c_uint64), ("occupied", C.c_uint64), ("rebuilds", C.c_uint64),
+                ("max_probe", C.c_uint64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -167,6 +179,15 @@ def load() -> C.CDLL:
     L.vrod_snapshot_verify.argtypes = [C.c_char_p]
     L.vrod_snapshot_checksum.argtypes = [vp, u64, u64, C.POINTER(u64)]
     L.vrod_snapshot_checksum_device.argtypes = [i32, vp, u64, u64, C.POINTER(u64), vp]
+    L.vrod_index_set_keys.argtypes = [vp, u64, vp, u64]
+    L.vrod_index_get_keys.argtypes = [vp, u64, u64, vp]
+    L.vrod_index_find_keys.argtypes = [vp, vp, u64, vp]
+    L.vrod_index_find_keys_device.argtypes = [vp, vp, u64, vp, vp]
+    L.vrod_index_ids_to_keys.argtypes = [vp, vp, u64, vp]
+    L.vrod_index_ids_to_keys_device.argtypes = [vp, vp, u64, vp, vp]
+    L.vrod_index_delete_keys.argtypes = [vp, vp, u64, C.POINTER(u64)]
+    L.vrod_index_upsert.argtypes = [vp, vp, vp, u64, vp]
+    L.vrod_index_key_stats.argtypes = [vp, C.POINTER(KeyStats)]
     for name in SYMBOLS:
         getattr(L, name).restype = i32
     L.vrod_last_error.restype = C.c_char_p

@@ -36,7 +36,9 @@ enum SnapKind : uint32_t {
     SNAP_LABELS = 5,    // [count] u32; present once labels were set
     SNAP_TAGS = 6,      // [count] u64; present once tags were set
     SNAP_VALUES = 7,    // [count] i64; present once values were set
-    SNAP_KIND_END = 8
+    SNAP_KEYS = 8,      // [count] u64; present once keys were set (the key table is not saved: a load rebuilds it).
+                        // Builds older than the kind answer VROD_ERR_UNSUPPORTED to a file that has it.
+    SNAP_KIND_END = 9
 };
 
 // a save or load moves the rows in chunks of this many dense bytes (a multiple of 32 rows, at least 32) through two
@@ -76,7 +78,7 @@ inline uint64_t snap_section_bytes(uint32_t kind, uint64_t count, uint32_t dim, 
         case SNAP_NORMS: return count * 4;
         case SNAP_DELETED: case SNAP_FILTER: return (count + 31) / 32 * 4;
         case SNAP_LABELS: return count * 4;
-        case SNAP_TAGS: case SNAP_VALUES: return count * 8;
+        case SNAP_TAGS: case SNAP_VALUES: case SNAP_KEYS: return count * 8;
         default: return 0;
     }
 }

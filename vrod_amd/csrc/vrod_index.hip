@@ -45,6 +45,7 @@
 #include "byid_plan.h"
 #include "combine_plan.h"
 #include "snapshot_plan.h"
+#include "keys_plan.h"
 
 using namespace vrod;
 
@@ -54,6 +55,7 @@ static_assert(kMultivecMaxK == VROD_MAX_K && kMultivecMaxVectors == VROD_MAX_QUE
 static_assert(kCombineMaxK == VROD_MAX_K && kCombineMaxTerms == VROD_MAX_COMBINE_TERMS && kCombineMaxExclude == VROD_MAX_EXCLUDE &&
                   kCombineExcludeTerms == VROD_COMBINED_EXCLUDE_TERMS,
               "combine_plan.h restates the ABI's limits");
+static_assert(kKeyNone == VROD_ID_NONE, "keys_plan.h restates the ABI's \"no key\"");
 static_assert(kDiverseMaxPool == VROD_MAX_DIVERSE_POOL && kDiverseMaxPool <= VROD_MAX_K && kDiverseMaxDim == VROD_MAX_DIM,
               "diverse_plan.h restates the ABI's limits");
 
@@ -251,6 +253,15 @@ struct vrod_index {
     // Only vrod_search_where reads them; a handle that never set one treats every row as 0.
     std::vector<int64_t> val_bits;     // [capacity] once values exist
     int64_t* val_dev = nullptr;        // [capacity] on the device, or null
+    // row keys (vrod_index_set_keys): one caller-chosen 64-bit key per row of the capacity, VROD_ID_NONE until set, kept
+    // as the values are, and unique among the live rows.  The device table (keys_plan.h, kernels_keys.hip) finds a key's
+    // row; it exists from the first set_keys on.  No search reads either: a handle that never set a key has neither.
+    std::vector<uint64_t> key_bits;    // [capacity] once keys exist
+    uint64_t* key_dev = nullptr;       // [capacity] on the device, or null
+    KeyTable ktab{};                   // the table's two device arrays
+    uint64_t key_occupied = 0;         // slots in use, stale ones included: at most ktab.slots / 2
+    uint64_t keyed_live = 0;           // live rows whose key is not VROD_ID_NONE
+    uint64_t key_rebuilds = 0, key_max_probe = 0;   // vrod_index_key_stats
     // Workspaces the synchronous searches share, one per role (DESIGN.md "Shared workspaces"): the handle is idle before
     // and after each of those calls, so no two of them hold one at once.
     //   host_q, host_args: a host form's raw queries or vectors, and its other arguments, on the device;
@@ -487,8 +498,28 @@ static int index_reserve(vrod_index* idx, uint64_t n_rows) {
             return fail(VROD_ERR_HIP, "growing the row values failed: %s", hipGetErrorString(ve));
         }
     }
+    uint64_t* nk = nullptr;   // and the keys: the new rows carry none (every byte 0xFF)
+    if (idx->key_dev) {
+        hipError_t ke = hipMalloc((void**)&nk, want * 8);
+        if (ke == hipSuccess) ke = hipMemsetAsync(nk, 0xFF, want * 8, idx->stream);
+        if (ke == hipSuccess) ke = hipMemcpyAsync(nk, idx->key_bits.data(), idx->count * 8, hipMemcpyHostToDevice, idx->stream);
+        if (ke == hipSuccess) ke = hipStreamSynchronize(idx->stream);
+        if (ke != hipSuccess) {
+            (void)hipStreamSynchronize(idx->stream);
+            if (nk) (void)hipFree(nk);
+            if (nv) (void)hipFree(nv);
+            if (nt) (void)hipFree(nt);
+            if (nl) (void)hipFree(nl);
+            if (ne) (void)hipFree(ne);
+            if (nd) (void)hipFree(nd);
+            (void)hipFree(nc);
+            (void)hipFree(nx);
+            return fail(VROD_ERR_HIP, "growing the row keys failed: %s", hipGetErrorString(ke));
+        }
+    }
     if (idx->corpus) (void)hipFree(idx->corpus);
     if (idx->xnorm2) (void)hipFree(idx->xnorm2);
+    if (idx->key_dev) { (void)hipFree(idx->key_dev); idx->key_dev = nk; idx->key_bits.resize(want, kKeyNone); }
     if (idx->planes) { (void)hipFree(idx->planes); idx->planes = nullptr; idx->planes_cap = idx->planes_rows = 0; }   // rebuilt lazily
     if (idx->val_dev) { (void)hipFree(idx->val_dev); idx->val_dev = nv; idx->val_bits.resize(want, 0ll); }
     if (idx->tag_dev) { (void)hipFree(idx->tag_dev); idx->tag_dev = nt; idx->tag_bits.resize(want, 0ull); }
@@ -628,6 +659,73 @@ static int index_update(vrod_index* idx, const std::vector<uint32_t>& dst, const
 
 static void mask_changed(vrod_index* idx);
 
+// ------------------------------------------------------------------ the key table (keys_plan.h, kernels_keys.hip)
+constexpr uint32_t kKeyCtrWord = 64;   // idx->flags[64 .. 70): the table's device counters (KeyCounters)
+static KeyCounters* key_ctr(const vrod_index* idx) { return (KeyCounters*)(idx->flags + kKeyCtrWord); }
+
+// What the launches on the handle's stream left in the counters (the stream is drained).  `what` names the caller.
+static int keys_take_counters(vrod_index* idx, const char* what, KeyCounters& c) {
+    HIP_TRY(hipMemcpyAsync(&c, key_ctr(idx), sizeof c, hipMemcpyDeviceToHost, idx->stream));
+    HIP_TRY(hipStreamSynchronize(idx->stream));
+    if (c.err & kKeyErrFull)
+        return fail(VROD_ERR_INTERNAL, "%s: a walk of the key table met no empty slot in %llu (%llu occupied)", what,
+                    (unsigned long long)idx->ktab.slots, (unsigned long long)idx->key_occupied);
+    return VROD_OK;
+}
+
+// An empty table sized for n keys (key_table_slots: it grows, never shrinks).  The old arrays go only when the new
+// ones exist, so a caller that runs this before it writes anything has every allocation of a rebuild behind it.
+static int keys_table_clear(vrod_index* idx, uint64_t n) {
+    VROD_TRY(set_device(idx));
+    const uint64_t slots = key_table_slots(n, idx->ktab.slots);
+    if (slots != idx->ktab.slots) {
+        uint64_t* nk = nullptr;
+        uint32_t* nr = nullptr;
+        HIP_TRY(hipMalloc((void**)&nk, slots * 8));
+        const hipError_t e = hipMalloc((void**)&nr, slots * 4);
+        if (e != hipSuccess) { (void)hipFree(nk); return fail(VROD_ERR_OUT_OF_MEMORY, "hipMalloc of the key table: %s", hipGetErrorString(e)); }
+        if (idx->ktab.slot_key) (void)hipFree(idx->ktab.slot_key);
+        if (idx->ktab.slot_row) (void)hipFree(idx->ktab.slot_row);
+        idx->ktab.slot_key = nk; idx->ktab.slot_row = nr; idx->ktab.slots = slots;
+    }
+    HIP_TRY(hipMemsetAsync(idx->ktab.slot_key, 0xFF, slots * 8, idx->stream));
+    HIP_TRY(hipMemsetAsync(idx->ktab.slot_row, 0, slots * 4, idx->stream));
+    idx->key_occupied = 0;
+    idx->key_max_probe = 0;
+    return VROD_OK;
+}
+// The table anew from the live keyed rows of the key column as it stands, sized for n keys.  counted: it is a rebuild
+// of vrod_key_stats (the first table of a handle, and a loaded handle's, are not).  *dup (may be null): two live rows
+// hold one key -- with a null dup that is an internal error.
+static int keys_rebuild(vrod_index* idx, uint64_t n, bool counted, const char* what, bool* dup = nullptr) {
+    VROD_TRY(keys_table_clear(idx, n));
+    hipStream_t s = idx->stream;
+    HIP_TRY(hipMemsetAsync(key_ctr(idx), 0, sizeof(KeyCounters), s));
+    launch_keys_insert(idx->ktab, idx->key_dev, idx->del_dev, 0, idx->count, true, key_ctr(idx), s);
+    HIP_TRY(hipGetLastError());
+    KeyCounters c{};
+    VROD_TRY(keys_take_counters(idx, what, c));
+    idx->key_occupied = c.claimed;
+    idx->key_max_probe = c.max_probe;
+    if (counted) idx->key_rebuilds++;
+    if (dup) *dup = (c.err & kKeyErrHeld) != 0;
+    else if (c.err & kKeyErrHeld) return fail(VROD_ERR_INTERNAL, "%s: two live rows hold one key", what);
+    return VROD_OK;
+}
+
+// The keys that rows [r0, r0 + n) of the key column hold go into the table (the load rule was seen to before).
+static int keys_insert(vrod_index* idx, uint64_t r0, uint64_t n, const char* what) {
+    hipStream_t s = idx->stream;
+    HIP_TRY(hipMemsetAsync(key_ctr(idx), 0, sizeof(KeyCounters), s));
+    launch_keys_insert(idx->ktab, idx->key_dev, idx->del_dev, r0, n, false, key_ctr(idx), s);
+    HIP_TRY(hipGetLastError());
+    KeyCounters c{};
+    VROD_TRY(keys_take_counters(idx, what, c));
+    idx->key_occupied += c.claimed;
+    idx->key_max_probe = std::max<uint64_t>(idx->key_max_probe, c.max_probe);
+    return VROD_OK;
+}
+
 // ------------------------------------------------------------------ compaction (vrod_index_compact)
 // The live rows move down in place, chunk by chunk on the handle's stream (compact_plan.h says why that is safe), with
 // their xnorm2 entries; the vacated tail is zeroed again (the scan kernels rely on zero rows past the count), the maximum
@@ -678,6 +776,13 @@ static int index_compact(vrod_index* idx, uint64_t* out_new_ids) {
         for (uint64_t r = 0; r < count; ++r)
             if (!bit_of(del, r)) new_val[j++] = idx->val_bits[r];
     }
+    std::vector<uint64_t> new_key;   // and the keys (the vacated tail carries none again)
+    if (idx->key_dev) {
+        new_key.assign(count, kKeyNone);
+        uint64_t j = 0;
+        for (uint64_t r = 0; r < count; ++r)
+            if (!bit_of(del, r)) new_key[j++] = idx->key_bits[r];
+    }
     uint64_t stage_rows = 0;
     for (const CompactChunk& c : plan.chunks) if (c.staged) stage_rows = std::max(stage_rows, c.L);
     if (stage_rows) {
@@ -713,6 +818,7 @@ static int index_compact(vrod_index* idx, uint64_t* out_new_ids) {
     if (e == hipSuccess && idx->lab_dev) e = hipMemcpyAsync(idx->lab_dev, new_lab.data(), count * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && idx->tag_dev) e = hipMemcpyAsync(idx->tag_dev, new_tag.data(), count * 8, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && idx->val_dev) e = hipMemcpyAsync(idx->val_dev, new_val.data(), count * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && idx->key_dev) e = hipMemcpyAsync(idx->key_dev, new_key.data(), count * 8, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess)
         return fail(VROD_ERR_HIP, "vrod_index_compact: %s while rows were moving: the handle is unusable, destroy it", hipGetErrorString(e));
@@ -725,8 +831,10 @@ static int index_compact(vrod_index* idx, uint64_t* out_new_ids) {
     if (idx->lab_dev) std::copy(new_lab.begin(), new_lab.end(), idx->lab_bits.begin());
     if (idx->tag_dev) std::copy(new_tag.begin(), new_tag.end(), idx->tag_bits.begin());
     if (idx->val_dev) std::copy(new_val.begin(), new_val.end(), idx->val_bits.begin());
+    if (idx->key_dev) std::copy(new_key.begin(), new_key.end(), idx->key_bits.begin());
     idx->planes_rows = 0;
     mask_changed(idx);
+    if (idx->key_dev) VROD_TRY(keys_rebuild(idx, idx->keyed_live, true, "vrod_index_compact"));   // every slot named an old row
     return VROD_OK;
 }
 
@@ -1774,6 +1882,8 @@ static int index_delete_rows(vrod_index* idx, const std::vector<uint64_t>& rows)
         return rc != VROD_OK ? rc : fail(e == hipErrorOutOfMemory ? VROD_ERR_OUT_OF_MEMORY : VROD_ERR_HIP, "uploading the deleted rows: %s", hipGetErrorString(e));
     }
     idx->n_deleted += fresh.size();
+    if (idx->key_dev)   // a deleted row's key is free: its slot goes stale, nothing is written to the table
+        for (uint64_t r : fresh) idx->keyed_live -= idx->key_bits[r] != kKeyNone;
     idx->n_eligible -= lost;
     mask_changed(idx);
     return VROD_OK;
@@ -3736,7 +3846,7 @@ static int knn_graph(vrod_index* idx, uint64_t row0, uint64_t n, uint32_t k, uin
 // device array.  The checksums are taken on the device, over device memory, on both sides: HBM -> file -> HBM is covered
 // end to end and the host makes no pass over the rows.  The bitmaps are the host mirrors' (the truth for both), checked
 // on the host: a 32nd of a byte per row.
-constexpr uint32_t kSnapSumWord = 32;   // idx->flags[32 .. 48): one 64-bit device sum per section kind (SNAP_KIND_END = 8)
+constexpr uint32_t kSnapSumWord = 32;   // idx->flags[32 .. 48): one 64-bit device sum per section kind (SNAP_KIND_END = 9)
 
 static int snap_status(SnapStatus st, const char* path, const char* why) {
     if (st == SNAP_OK) return VROD_OK;
@@ -3956,6 +4066,7 @@ static int snap_save_body(vrod_index* idx, int fd) {
     if (idx->lab_dev) add(SNAP_LABELS);
     if (idx->tag_dev) add(SNAP_TAGS);
     if (idx->val_dev) add(SNAP_VALUES);
+    if (idx->key_dev) add(SNAP_KEYS);
     snap_layout(h);
     if (ftruncate(fd, (off_t)h.file_bytes) != 0) return fail(VROD_ERR_IO, "sizing the snapshot: %s", strerror(errno));   // (the padding: zeros)
 
@@ -3986,7 +4097,8 @@ static int snap_save_body(vrod_index* idx, int fd) {
                 continue;
             }
             const void* d_arr = sec.kind == SNAP_NORMS ? (const void*)idx->xnorm2 : sec.kind == SNAP_LABELS ? (const void*)idx->lab_dev
-                              : sec.kind == SNAP_TAGS ? (const void*)idx->tag_dev : sec.kind == SNAP_VALUES ? (const void*)idx->val_dev : nullptr;
+                              : sec.kind == SNAP_TAGS ? (const void*)idx->tag_dev : sec.kind == SNAP_VALUES ? (const void*)idx->val_dev
+                              : sec.kind == SNAP_KEYS ? (const void*)idx->key_dev : nullptr;
             if (!d_arr) continue;   // the bitmaps: below
             launch_snapshot_checksum(d_arr, sec.bytes, 0, d_sum + sec.kind, s);
             HIP_TRY(hipGetLastError());
@@ -4016,15 +4128,17 @@ static int snap_save_body(vrod_index* idx, int fd) {
     return VROD_OK;
 }
 
-// a side array of a loaded handle: device copy and host mirror over the capacity, rows [0, count) from the file
+// a side array of a loaded handle: device copy and host mirror over the capacity, rows [0, count) from the file, the
+// rest `none` (0, or every bit set)
 template <typename T>
-static int snap_load_side(vrod_index* idx, SnapPipe& P, int fd, const SnapSection& sec, std::vector<T>& host, T*& dev, uint64_t* d_sum) {
+static int snap_load_side(vrod_index* idx, SnapPipe& P, int fd, const SnapSection& sec, std::vector<T>& host, T*& dev, uint64_t* d_sum,
+                          T none = T(0)) {
     hipStream_t s = idx->stream;
     T* d = nullptr;
     HIP_TRY(hipMalloc((void**)&d, idx->capacity * sizeof(T)));
     dev = d;   // (the handle owns it from here: a failure below is followed by vrod_index_destroy)
-    HIP_TRY(hipMemsetAsync(d, 0, idx->capacity * sizeof(T), s));
-    host.assign(idx->capacity, T(0));
+    HIP_TRY(hipMemsetAsync(d, none == T(0) ? 0 : 0xFF, idx->capacity * sizeof(T), s));
+    host.assign(idx->capacity, none);
     VROD_TRY(snap_stream_in(P, fd, sec.offset, sec.bytes, P.bytes / 8 * 8, [&](uint64_t off, uint64_t n, int b) -> int {
         memcpy((char*)host.data() + off, P.host[b], n);
         HIP_TRY(hipMemcpyAsync((char*)d + off, P.host[b], n, hipMemcpyHostToDevice, s));
@@ -4090,6 +4204,7 @@ static int snap_load_body(vrod_index* idx, int fd, const char* path, const SnapH
         if (const SnapSection* sec = h.find(SNAP_LABELS)) VROD_TRY(snap_load_side(idx, P, fd, *sec, idx->lab_bits, idx->lab_dev, d_sum));
         if (const SnapSection* sec = h.find(SNAP_TAGS)) VROD_TRY(snap_load_side(idx, P, fd, *sec, idx->tag_bits, idx->tag_dev, d_sum));
         if (const SnapSection* sec = h.find(SNAP_VALUES)) VROD_TRY(snap_load_side(idx, P, fd, *sec, idx->val_bits, idx->val_dev, d_sum));
+        if (const SnapSection* sec = h.find(SNAP_KEYS)) VROD_TRY(snap_load_side(idx, P, fd, *sec, idx->key_bits, idx->key_dev, d_sum, kKeyNone));
         HIP_TRY(hipMemcpyAsync(idx->max_xn2_bits, &h.max_xn2_bits, 4, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(h_sum, d_sum, sizeof h_sum, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -4113,6 +4228,14 @@ static int snap_load_body(vrod_index* idx, int fd, const char* path, const SnapH
     if (h.find(SNAP_FILTER)) {
         static const uint32_t kNone = 0u;
         VROD_TRY(index_set_filter(idx, count ? allow.data() : &kNone, count));
+    }
+    // the key table is not in the file: it is built from the key column and the deleted-row bits, which is also the
+    // check that no two live rows of the file share a key
+    if (idx->key_dev) {
+        for (uint64_t r = 0; r < count; ++r) idx->keyed_live += idx->key_bits[r] != kKeyNone && !bit_of(idx->del_bits.data(), r);
+        bool dup = false;
+        VROD_TRY(keys_rebuild(idx, idx->keyed_live, false, "vrod_index_load", &dup));
+        if (dup) return fail(VROD_ERR_CORRUPT, "%s: two live rows hold the same key", path);
     }
     return VROD_OK;
 }
@@ -4247,6 +4370,9 @@ int vrod_index_destroy(vrod_index* idx) {
     if (idx->lab_dev) (void)hipFree(idx->lab_dev);
     if (idx->tag_dev) (void)hipFree(idx->tag_dev);
     if (idx->val_dev) (void)hipFree(idx->val_dev);
+    if (idx->key_dev) (void)hipFree(idx->key_dev);
+    if (idx->ktab.slot_key) (void)hipFree(idx->ktab.slot_key);
+    if (idx->ktab.slot_row) (void)hipFree(idx->ktab.slot_row);
     if (idx->flags) (void)hipFree(idx->flags);
     if (idx->stream) (void)hipStreamDestroy(idx->stream);
     delete idx;
@@ -4607,11 +4733,11 @@ int vrod_search_labeled_device(vrod_index* idx, const float* d_queries, uint32_t
 }
 
 extern "C++" {   // (templates, inside the C entry points' block)
-// A per-row side array of 64-bit words (tags, values): host mirror and device copy allocated at the first set, 0 until
+// A per-row side array of 64-bit words (tags, values, keys): host mirror and device copy allocated at the first set, 0 until
 // then.  set: the rows with ids [first_id, first_id + n) take src[0 .. n); get: the host mirror is the truth.
 template <typename T>
 static int side_array_set(vrod_index* idx, const char* what, const char* noun, uint64_t first_id, const T* src, uint64_t n, std::vector<T>& host,
-                          T*& dev) {
+                          T*& dev, T none = T(0)) {
     static_assert(sizeof(T) == 8, "tags and values are 64-bit words");
     if (!src && n) return fail(VROD_ERR_INVALID_ARG, "null argument");
     if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "%s on a multi-device handle: %s are not routed to the shards", what, noun);
@@ -4620,24 +4746,24 @@ static int side_array_set(vrod_index* idx, const char* what, const char* noun, u
     if (!n) return VROD_OK;
     VROD_TRY(set_device(idx));
     const uint64_t r0 = first_id - idx->id_offset;
-    if (!dev) {   // the first of the handle: every row carries 0 so far
+    if (!dev) {   // the first of the handle: every row carries `none` (0, or every bit set) so far
         T* d = nullptr;
         HIP_TRY(hipMalloc((void**)&d, idx->capacity * 8));
-        const hipError_t e = hipMemset(d, 0, idx->capacity * 8);
+        const hipError_t e = hipMemset(d, none == T(0) ? 0 : 0xFF, idx->capacity * 8);
         if (e != hipSuccess) { (void)hipFree(d); return fail(VROD_ERR_HIP, "clearing the row %s: %s", noun, hipGetErrorString(e)); }
         dev = d;
-        host.assign(idx->capacity, T(0));
+        host.assign(idx->capacity, none);
     }
     HIP_TRY(hipMemcpy(dev + r0, src, n * 8, hipMemcpyHostToDevice));
     std::copy(src, src + n, host.begin() + r0);
     return VROD_OK;
 }
 template <typename T>
-static int side_array_get(vrod_index* idx, uint64_t first_id, uint64_t n, const std::vector<T>& host, T* out) {
+static int side_array_get(vrod_index* idx, uint64_t first_id, uint64_t n, const std::vector<T>& host, T* out, T none = T(0)) {
     if (!out && n) return fail(VROD_ERR_INVALID_ARG, "null argument");
     VROD_TRY(check_id_range(idx, first_id, n));
     const uint64_t r0 = first_id - idx->id_offset;
-    for (uint64_t i = 0; i < n; ++i) out[i] = host.empty() ? T(0) : host[r0 + i];
+    for (uint64_t i = 0; i < n; ++i) out[i] = host.empty() ? none : host[r0 + i];
     return VROD_OK;
 }
 }  // extern "C++"
@@ -4660,6 +4786,201 @@ int vrod_index_set_values(vrod_index* idx, uint64_t first_id, const int64_t* val
 int vrod_index_get_values(vrod_index* idx, uint64_t first_id, uint64_t n, int64_t* out_values) {
     if (!idx) return fail(VROD_ERR_INVALID_ARG, "null argument");
     return side_array_get(idx, first_id, n, idx->val_bits, out_values);
+}
+
+// ------------------------------------------------------------------ row keys
+static const char kKeysNotRouted[] = "on a multi-device handle: keys are not routed to the shards";
+
+// Rows [r0, r0 + n) of a single-device, idle handle take keys[0 .. n).  checked: the two uniqueness checks run first
+// (vrod_index_upsert has made them).  Order: the host check, the device check, every allocation, and only then the
+// writes -- the column, then the table: an insert of the range, or, where that could cross the load limit, one rebuild
+// from the column, which holds the new keys by then.
+static int keys_set_range(vrod_index* idx, const char* what, uint64_t r0, const uint64_t* keys, uint64_t n, bool checked) {
+    const uint32_t* del = idx->del_bits.data();
+    std::vector<uint64_t> live_keys;   // what the live rows of the range get
+    uint64_t had = 0;                  // ... and how many of them hold a key now
+    for (uint64_t i = 0; i < n; ++i) {
+        if (bit_of(del, r0 + i)) continue;
+        if (keys[i] != kKeyNone) live_keys.push_back(keys[i]);
+        if (idx->key_dev) had += idx->key_bits[r0 + i] != kKeyNone;
+    }
+    const uint64_t incoming = live_keys.size();
+    VROD_TRY(set_device(idx));
+    if (checked) {
+        std::sort(live_keys.begin(), live_keys.end());
+        const auto twice = std::adjacent_find(live_keys.begin(), live_keys.end());
+        if (twice != live_keys.end())
+            return fail(VROD_ERR_INVALID_ARG, "%s: key %llu is given to two live rows", what, (unsigned long long)*twice);
+        if (idx->ktab.slot_key && incoming) {
+            VROD_TRY(idx->host_args.ensure(n * 8));
+            HIP_TRY(hipMemcpyAsync(idx->host_args.p, keys, n * 8, hipMemcpyHostToDevice, idx->stream));
+            HIP_TRY(hipMemsetAsync(key_ctr(idx), 0, sizeof(KeyCounters), idx->stream));
+            launch_keys_check(idx->ktab, idx->key_dev, idx->del_dev, idx->count, idx->host_args.as<uint64_t>(), r0, n, key_ctr(idx), idx->stream);
+            HIP_TRY(hipGetLastError());
+            KeyCounters c{};
+            VROD_TRY(keys_take_counters(idx, what, c));
+            if (c.err & kKeyErrHeld) return fail(VROD_ERR_INVALID_ARG, "%s: a key is held by a live row outside the range", what);
+        }
+    }
+    const bool first = !idx->ktab.slot_key;
+    const bool rebuild = first || key_needs_rebuild(idx->key_occupied, incoming, idx->ktab.slots);
+    const uint64_t sized_for = idx->keyed_live + incoming;   // the live keyed rows plus the incoming keys
+    if (rebuild) VROD_TRY(keys_table_clear(idx, sized_for));
+    VROD_TRY(side_array_set(idx, what, "keys", r0 + idx->id_offset, keys, n, idx->key_bits, idx->key_dev, (uint64_t)kKeyNone));
+    idx->keyed_live = idx->keyed_live - had + incoming;
+    if (rebuild) return keys_rebuild(idx, sized_for, !first, what);
+    return keys_insert(idx, r0, n, what);
+}
+
+int vrod_index_set_keys(vrod_index* idx, uint64_t first_id, const uint64_t* keys, uint64_t n) {
+    if (!idx || (!keys && n)) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "vrod_index_set_keys %s", kKeysNotRouted);
+    VROD_TRY(require_idle(idx, "vrod_index_set_keys"));
+    VROD_TRY(check_id_range(idx, first_id, n));
+    if (!n) return VROD_OK;
+    return keys_set_range(idx, "vrod_index_set_keys", first_id - idx->id_offset, keys, n, true);
+}
+
+int vrod_index_get_keys(vrod_index* idx, uint64_t first_id, uint64_t n, uint64_t* out_keys) {
+    if (!idx) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    return side_array_get(idx, first_id, n, idx->key_bits, out_keys, (uint64_t)kKeyNone);
+}
+
+// what the four lookups start with; a null pointer is fine while n == 0
+static int check_lookup_args(vrod_index* idx, const char* what, const void* in, uint64_t n, const void* out) {
+    if (!idx || ((!in || !out) && n)) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "%s %s", what, kKeysNotRouted);
+    return require_idle(idx, what);
+}
+
+// d_keys[0, n) -> d_out_ids, on the handle's stream, complete on return.  A handle without keys answers with a fill.
+static int keys_find_on_device(vrod_index* idx, const char* what, const uint64_t* d_keys, uint64_t n, uint64_t* d_out_ids) {
+    hipStream_t s = idx->stream;
+    if (!idx->key_dev) {
+        HIP_TRY(hipMemsetAsync(d_out_ids, 0xFF, n * 8, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return VROD_OK;
+    }
+    HIP_TRY(hipMemsetAsync(key_ctr(idx), 0, sizeof(KeyCounters), s));
+    launch_keys_find(idx->ktab, idx->key_dev, idx->del_dev, idx->count, idx->id_offset, d_keys, n, d_out_ids, key_ctr(idx), s);
+    HIP_TRY(hipGetLastError());
+    KeyCounters c{};
+    VROD_TRY(keys_take_counters(idx, what, c));
+    static const bool report = [] { const char* e = getenv("VROD_DEBUG_KEYS_WALK"); return e && e[0] == '1'; }();
+    if (report)   // slots visited per key, one line on stderr (scripts/probes/keys_probe.py)
+        fprintf(stderr, "{\"vrod_keys_find\": %llu, \"slots_visited\": %llu, \"slots\": %llu, \"occupied\": %llu}\n", (unsigned long long)n,
+                c.find_walk, (unsigned long long)idx->ktab.slots, (unsigned long long)idx->key_occupied);
+    return VROD_OK;
+}
+
+// the host form's body, also the first step of vrod_index_delete_keys and vrod_index_upsert
+static int keys_find_host(vrod_index* idx, const char* what, const uint64_t* keys, uint64_t n, uint64_t* out_ids) {
+    if (!idx->key_dev) { std::fill(out_ids, out_ids + n, (uint64_t)kKeyNone); return VROD_OK; }
+    VROD_TRY(set_device(idx));
+    VROD_TRY(idx->host_args.ensure(n * 8));
+    VROD_TRY(idx->out_ids.ensure(n * 8));
+    HIP_TRY(hipMemcpyAsync(idx->host_args.p, keys, n * 8, hipMemcpyHostToDevice, idx->stream));
+    VROD_TRY(keys_find_on_device(idx, what, idx->host_args.as<uint64_t>(), n, idx->out_ids.as<uint64_t>()));
+    HIP_TRY(hipMemcpy(out_ids, idx->out_ids.p, n * 8, hipMemcpyDeviceToHost));
+    return VROD_OK;
+}
+
+int vrod_index_find_keys(vrod_index* idx, const uint64_t* keys, uint64_t n, uint64_t* out_ids) {
+    VROD_TRY(check_lookup_args(idx, "vrod_index_find_keys", keys, n, out_ids));
+    if (!n) return VROD_OK;
+    return keys_find_host(idx, "vrod_index_find_keys", keys, n, out_ids);
+}
+
+int vrod_index_find_keys_device(vrod_index* idx, const uint64_t* d_keys, uint64_t n, uint64_t* d_out_ids, void* stream) {
+    VROD_TRY(check_lookup_args(idx, "vrod_index_find_keys_device", d_keys, n, d_out_ids));
+    if (!n) return VROD_OK;
+    VROD_TRY(begin_sync_device(idx, "vrod_index_find_keys_device", stream));
+    return keys_find_on_device(idx, "vrod_index_find_keys_device", d_keys, n, d_out_ids);
+}
+
+int vrod_index_ids_to_keys(vrod_index* idx, const uint64_t* ids, uint64_t n, uint64_t* out_keys) {
+    VROD_TRY(check_lookup_args(idx, "vrod_index_ids_to_keys", ids, n, out_keys));
+    for (uint64_t i = 0; i < n; ++i) {   // the host mirror is the truth
+        const bool row = idx->key_dev && ids[i] != kKeyNone && ids[i] >= idx->id_offset && ids[i] - idx->id_offset < idx->count;
+        out_keys[i] = row ? idx->key_bits[ids[i] - idx->id_offset] : (uint64_t)kKeyNone;
+    }
+    return VROD_OK;
+}
+
+int vrod_index_ids_to_keys_device(vrod_index* idx, const uint64_t* d_ids, uint64_t n, uint64_t* d_out_keys, void* stream) {
+    VROD_TRY(check_lookup_args(idx, "vrod_index_ids_to_keys_device", d_ids, n, d_out_keys));
+    if (!n) return VROD_OK;
+    VROD_TRY(begin_sync_device(idx, "vrod_index_ids_to_keys_device", stream));
+    if (!idx->key_dev) HIP_TRY(hipMemsetAsync(d_out_keys, 0xFF, n * 8, idx->stream));
+    else launch_keys_translate(idx->key_dev, idx->count, idx->id_offset, d_ids, n, d_out_keys, idx->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(idx->stream));
+    return VROD_OK;
+}
+
+int vrod_index_delete_keys(vrod_index* idx, const uint64_t* keys, uint64_t n, uint64_t* out_deleted) {
+    if (out_deleted) *out_deleted = 0;
+    VROD_TRY(check_lookup_args(idx, "vrod_index_delete_keys", keys, n, keys));
+    if (!n) return VROD_OK;
+    std::vector<uint64_t> rows(n);
+    VROD_TRY(keys_find_host(idx, "vrod_index_delete_keys", keys, n, rows.data()));
+    rows.erase(std::remove(rows.begin(), rows.end(), (uint64_t)kKeyNone), rows.end());   // lists kept outside outlive deletes
+    for (uint64_t& r : rows) r -= idx->id_offset;
+    const uint64_t before = idx->n_deleted;
+    if (!rows.empty()) VROD_TRY(index_delete_rows(idx, rows));   // (a key named twice found one row: deleting again is a no-op)
+    if (out_deleted) *out_deleted = idx->n_deleted - before;
+    return VROD_OK;
+}
+
+int vrod_index_upsert(vrod_index* idx, const uint64_t* keys, const float* rows, uint64_t n, uint64_t* out_ids) {
+    if (!idx || ((!keys || !rows) && n)) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "vrod_index_upsert %s", kKeysNotRouted);
+    VROD_TRY(require_idle(idx, "vrod_index_upsert"));
+    if (!n) return VROD_OK;
+    // every check before the first row is written: the keys on the host, the vectors by a prepare-only pass
+    {
+        std::vector<uint64_t> sorted(keys, keys + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (sorted.back() == kKeyNone) return fail(VROD_ERR_INVALID_ARG, "vrod_index_upsert: VROD_ID_NONE is not a key");
+        const auto twice = std::adjacent_find(sorted.begin(), sorted.end());
+        if (twice != sorted.end()) return fail(VROD_ERR_INVALID_ARG, "vrod_index_upsert: key %llu is named twice", (unsigned long long)*twice);
+    }
+    VROD_TRY(index_update_pass(idx, nullptr, rows, n, false));
+    std::vector<uint64_t> found(n);
+    VROD_TRY(keys_find_host(idx, "vrod_index_upsert", keys, n, found.data()));
+    // the rows of held keys are updated in place, the others appended in the order of the call and keyed
+    const size_t dim = idx->dim;
+    std::vector<uint32_t> dst;
+    std::vector<uint64_t> new_keys;
+    std::vector<float> held_rows, new_rows;
+    const uint64_t count0 = idx->count;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (found[i] != kKeyNone) {
+            dst.push_back((uint32_t)(found[i] - idx->id_offset));
+            held_rows.insert(held_rows.end(), rows + i * dim, rows + (i + 1) * dim);
+        } else {
+            found[i] = idx->id_offset + count0 + new_keys.size();
+            new_keys.push_back(keys[i]);
+            new_rows.insert(new_rows.end(), rows + i * dim, rows + (i + 1) * dim);
+        }
+    }
+    if (!new_keys.empty()) {
+        VROD_TRY(index_add(idx, new_rows.data(), new_keys.size(), false, 0, 0));
+        VROD_TRY(keys_set_range(idx, "vrod_index_upsert", count0, new_keys.data(), new_keys.size(), false));
+    }
+    if (!dst.empty()) VROD_TRY(index_update(idx, dst, held_rows.data(), dst.size()));
+    if (out_ids) std::copy(found.begin(), found.end(), out_ids);
+    return VROD_OK;
+}
+
+int vrod_index_key_stats(const vrod_index* idx, vrod_key_stats* out) {
+    if (!idx || !out) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    out->keyed_live = idx->keyed_live;
+    out->slots = idx->ktab.slots;
+    out->occupied = idx->key_occupied;
+    out->rebuilds = idx->key_rebuilds;
+    out->max_probe = idx->key_max_probe;
+    return VROD_OK;
 }
 
 static_assert(sizeof(vrod_tag_pred) == 24 && sizeof(TagPred) == 24, "vrod_tag_pred is three packed 64-bit words");

@@ -88,6 +88,30 @@ void launch_snapshot_unpack(const void* d_dense, uint64_t n_rows, uint32_t dim, 
 // *d_sum += the checksum terms of n_bytes at d_bytes (4-byte aligned)
 void launch_snapshot_checksum(const void* d_bytes, uint64_t n_bytes, uint64_t first_word, uint64_t* d_sum, hipStream_t s);
 
+// ---- kernels_keys.hip : the row keys' device table (keys_plan.h) and the id -> key gather
+struct KeyTable {
+    uint64_t* slot_key = nullptr;   // [slots], kKeyNone = empty
+    uint32_t* slot_row = nullptr;   // [slots]
+    uint64_t slots = 0;             // a power of two
+};
+// what a launch leaves for the host, cleared by the host in front of it
+struct KeyCounters {
+    unsigned long long claimed;     // insert / rebuild: slots newly claimed
+    unsigned long long find_walk;   // find: slots visited, all keys together
+    uint32_t max_probe;             // insert / rebuild: the longest walk, in slots
+    uint32_t err;                   // kKeyErrFull | kKeyErrHeld
+};
+// d_col: the key column [count]; d_del: the deleted-row bits, or null while nothing was ever deleted.
+// check: keys d_keys[0, n) are about to go to rows [r0, r0 + n).  insert: the column holds them already.
+void launch_keys_check(const KeyTable& T, const uint64_t* d_col, const uint32_t* d_del, uint64_t count, const uint64_t* d_keys, uint64_t r0,
+                       uint64_t n, KeyCounters* d_ctr, hipStream_t s);
+void launch_keys_insert(const KeyTable& T, const uint64_t* d_col, const uint32_t* d_del, uint64_t r0, uint64_t n, bool rebuild,
+                        KeyCounters* d_ctr, hipStream_t s);
+void launch_keys_find(const KeyTable& T, const uint64_t* d_col, const uint32_t* d_del, uint64_t count, uint64_t id_offset,
+                      const uint64_t* d_keys, uint64_t n, uint64_t* d_out_ids, KeyCounters* d_ctr, hipStream_t s);
+void launch_keys_translate(const uint64_t* d_col, uint64_t count, uint64_t id_offset, const uint64_t* d_ids, uint64_t n, uint64_t* d_out_keys,
+                           hipStream_t s);
+
 // ---- kernels_stream.hip : Q <= 8 HBM-bound scan, writes fast scores [nq_pad][score_ld]
 // nq_pad in {1,2,4,8}; d_q is [nq_pad][ld] prepared fp32 (zero rows for padding).
 // Also accumulates, per query, a histogram of the top stream_hist_bits(nq_pad) bits of the

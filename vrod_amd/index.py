@@ -12,7 +12,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import MultivecStats, SearchStats, SnapshotInfo, VrodError, check
+from ._lib import KeyStats, MultivecStats, SearchStats, SnapshotInfo, VrodError, check
 
 DTYPE_F32, DTYPE_BF16 = 0, 1
 METRIC_COSINE, METRIC_L2, METRIC_IP = 0, 1, 2
@@ -273,6 +273,92 @@ class Index:
         out = np.empty(int(n), dtype=np.int64)
         check(self._L.vrod_index_get_values(self._h, int(first_id), int(n), _ptr(out)))
         return out
+
+    # -- row keys
+    @classmethod
+    def _keys(cls, keys) -> np.ndarray:
+        """An integer array-like of keys (each in 0 .. 2**64 - 1, ID_NONE included) -> a contiguous uint64 vector."""
+        a = np.asarray(keys)
+        if a.dtype.kind == "i" and a.size and int(a.min()) < 0:
+            raise ValueError("keys must fit 64 unsigned bits")
+        return cls._ids(keys)
+
+    def set_keys(self, first_id: int, keys):
+        """Give the rows with ids first_id, first_id + 1, ... the caller's 64-bit keys (vrod_index_set_keys).  Every row
+        carries ID_NONE ("no key") until it is given one; no two live rows may hold the same key.  No search reads keys."""
+        a = self._keys(keys)
+        check(self._L.vrod_index_set_keys(self._h, int(first_id), _ptr(a), a.size))
+
+    def get_keys(self, first_id: int, n: int) -> np.ndarray:
+        out = np.empty(int(n), dtype=np.uint64)
+        check(self._L.vrod_index_get_keys(self._h, int(first_id), int(n), _ptr(out)))
+        return out
+
+    def find_keys(self, keys) -> np.ndarray:
+        """keys -> the ids of the live rows that hold them, ID_NONE where no live row does (vrod_index_find_keys)."""
+        a = self._keys(keys)
+        out = np.empty(a.size, dtype=np.uint64)
+        check(self._L.vrod_index_find_keys(self._h, _ptr(a), a.size, _ptr(out)))
+        return out
+
+    def ids_to_keys(self, ids) -> np.ndarray:
+        """ids (any shape, e.g. a search's [nq, k]) -> the keys their rows store, ID_NONE for ID_NONE, an id that is no
+        current row, or a row without a key (vrod_index_ids_to_keys)."""
+        flat = self._ids(ids)
+        out = np.empty(flat.size, dtype=np.uint64)
+        check(self._L.vrod_index_ids_to_keys(self._h, _ptr(flat), flat.size, _ptr(out)))
+        return out.reshape(np.shape(ids))
+
+    def _device_u64(self, t, what):
+        """Checks a device tensor of 64-bit words (int64, the bits of uint64) -> (its element count, its device's stream)."""
+        import torch
+        if t.dtype != torch.int64:
+            raise TypeError(f"{what} must be an int64 tensor, got {t.dtype}")
+        assert t.is_cuda and t.is_contiguous()
+        return t.numel(), C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+    def find_keys_device(self, d_keys, out_ids=None):
+        """torch CUDA tensor of keys (int64, the bits of uint64, any shape) -> the ids (same shape), complete on return."""
+        import torch
+        n, stream = self._device_u64(d_keys, "keys")
+        out_ids = _device_out(out_ids, tuple(d_keys.shape), torch.int64, d_keys.device)
+        check(self._L.vrod_index_find_keys_device(self._h, d_keys.data_ptr(), n, out_ids.data_ptr(), stream))
+        return out_ids
+
+    def ids_to_keys_device(self, d_ids, out_keys=None):
+        """torch CUDA tensor of ids (int64-viewed-uint64, e.g. search_device's [nq, k]) -> the keys (same shape), complete
+        on return: a result list becomes the caller's names without leaving the device."""
+        import torch
+        n, stream = self._device_u64(d_ids, "ids")
+        out_keys = _device_out(out_keys, tuple(d_ids.shape), torch.int64, d_ids.device)
+        check(self._L.vrod_index_ids_to_keys_device(self._h, d_ids.data_ptr(), n, out_keys.data_ptr(), stream))
+        return out_keys
+
+    def delete_keys(self, keys) -> int:
+        """Delete the live row of each key; keys no live row holds are ignored (vrod_index_delete_keys).  -> rows that died."""
+        a = self._keys(keys)
+        out = C.c_uint64()
+        check(self._L.vrod_index_delete_keys(self._h, _ptr(a), a.size, C.byref(out)))
+        return out.value
+
+    def upsert(self, keys, rows: np.ndarray) -> np.ndarray:
+        """Row of keys[i] := rows[i]: updated in place where a live row holds the key, appended and keyed otherwise
+        (vrod_index_upsert).  All or nothing.  -> each key's id."""
+        a = self._keys(keys)
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        if rows.ndim == 1 and a.size == 1:
+            rows = rows[None, :]
+        if rows.ndim != 2 or rows.shape[1] != self.dim or rows.shape[0] != a.size:
+            raise ValueError(f"rows must be [{a.size}, {self.dim}]")
+        out = np.empty(a.size, dtype=np.uint64)
+        check(self._L.vrod_index_upsert(self._h, _ptr(a), _ptr(rows), a.size, _ptr(out)))
+        return out
+
+    def key_stats(self) -> dict:
+        """keyed_live, slots, occupied, rebuilds, max_probe of the key table (vrod_index_key_stats); zeros before set_keys."""
+        st = KeyStats()
+        check(self._L.vrod_index_key_stats(self._h, C.byref(st)))
+        return st.as_dict()
 
     @classmethod
     def _where(cls, preds, nq) -> np.ndarray:
