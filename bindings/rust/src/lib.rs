@@ -271,6 +271,11 @@ extern "C" {
     pub fn vrod_index_delete_keys(idx: *mut vrod_index, keys: *const u64, n: u64, out_deleted: *mut u64) -> c_int;
     pub fn vrod_index_upsert(idx: *mut vrod_index, keys: *const u64, rows: *const f32, n: u64, out_ids: *mut u64) -> c_int;
     pub fn vrod_index_key_stats(idx: *const vrod_index, out: *mut vrod_key_stats) -> c_int;
+    /// Device-resident ingest: `src_dtype` is 0 (f32), 1 (bf16) or 2 (f16); `row_stride` is in elements, `>= dim`.
+    pub fn vrod_index_add_device(idx: *mut vrod_index, d_rows: *const c_void, src_dtype: c_int, row_stride: u64, n: u64, stream: *mut c_void) -> c_int;
+    pub fn vrod_index_update_device(idx: *mut vrod_index, d_ids: *const u64, d_rows: *const c_void, src_dtype: c_int, row_stride: u64, n: u64, stream: *mut c_void) -> c_int;
+    pub fn vrod_index_upsert_device(idx: *mut vrod_index, d_keys: *const u64, d_rows: *const c_void, src_dtype: c_int, row_stride: u64, n: u64, d_out_ids: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn vrod_index_get_rows_device(idx: *mut vrod_index, first: u64, n: u64, d_out_rows: *mut f32, out_row_stride: u64, stream: *mut c_void) -> c_int;
 }
 
 /// Joins the reference's `thiserror` enums (`src/main.rs:36-40`, `src/command/builder.rs:10-15`).

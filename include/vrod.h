@@ -282,6 +282,47 @@ int vrod_index_key_stats(const vrod_index *idx, vrod_key_stats *out);
 /* Copy prepared rows [first, first+n) back as fp32 (bf16 widened): n x dim. */
 int vrod_index_get_rows(vrod_index *idx, uint64_t first, uint64_t n, float *out_rows);
 
+/* --- device-resident ingest ------------------------------------------------ */
+/* add / update / upsert / get_rows for callers whose rows are in GPU memory already (an encoder's output, often fp16 or
+ * bf16 and a slice of a larger buffer): the row payload never crosses to the host.
+ *   source      d_rows is device memory holding n rows of src_dtype elements: row i starts at element i * row_stride and
+ *               dim consecutive elements follow.  row_stride is in elements and must be >= dim (there is no "0 means
+ *               dim"); the pointer need only be aligned to its element (4 bytes for F32, 2 for BF16 / F16): the library
+ *               uses wide loads only where the address allows them.  n * row_stride overflowing 64 bits, a misaligned
+ *               pointer, a null idx, a null d_rows (d_ids, d_keys) with n > 0, an unknown src_dtype:
+ *               VROD_ERR_INVALID_ARG, checked before any device call.  The padding between rows is never read.
+ *   conversion  BF16 and F16 elements are widened to fp32 exactly (fp16 subnormals included, -0.0 kept); from there every
+ *               row is treated exactly as vrod_index_add / _update / _upsert treat the same fp32 values: the fp64
+ *               left-to-right norm chain and (f32)((f64)x / nrm) under COSINE, the bf16 rounding of a BF16 handle after
+ *               it (a bf16 source on a bf16 cosine handle is still normalised and rounded again).
+ *   result      after any sequence of these calls the handle is indistinguishable through this ABI from one on which the
+ *               host forms were called with the widened rows: get_rows, every search (ids and score bits), eps_bound,
+ *               scan_bytes, count / live_count and the bytes vrod_index_save writes.
+ *   bad values  NaN or Inf anywhere in the n x dim elements read (for F16: the encodings 0x7C00.. and 0xFC00..):
+ *               VROD_ERR_INVALID_VALUE; a refused call changes nothing (rows, norms, the certificate's bound, count, key
+ *               table), and every check comes before the first row of an update or upsert is written.
+ *   ids, keys   d_ids / d_keys / d_out_ids (may be NULL) are device memory; validation and semantics are those of the host
+ *               forms (an id that is not a current row or names a deleted row fails the call, an id twice takes the last
+ *               vector, VROD_ID_NONE as a key or a key twice fails the call, appended rows take the next ids in call
+ *               order).  These 8 bytes per row are copied to the host for the checks; the rows are not.
+ *   stream      as vrod_index_find_keys_device: the caller's work on `stream` (may be NULL) is complete before the library
+ *               reads, and the call returns when the rows are in place.
+ *   state       while a search is pending: VROD_ERR_INVALID_ARG.
+ *   get_rows_device  vrod_index_get_rows into device memory: n rows of dim fp32, row i at element i * out_row_stride
+ *               (>= dim) of d_out_rows; the padding between the rows is not written.
+ *   multi-device handles  add_device, update_device and get_rows_device deal rows and ids to the shards as the host forms
+ *               do (every shard checks its rows of an update before any shard writes one); a source on another device
+ *               than a shard is packed there, copied peer to peer in the host forms' chunks and ingested from the copy.
+ *               upsert_device: VROD_ERR_UNSUPPORTED, as vrod_index_upsert. */
+typedef enum { VROD_SRC_F32 = 0, VROD_SRC_BF16 = 1, VROD_SRC_F16 = 2 } vrod_src_dtype;
+int vrod_index_add_device(vrod_index *idx, const void *d_rows, int src_dtype, uint64_t row_stride, uint64_t n, void *stream);
+int vrod_index_update_device(vrod_index *idx, const uint64_t *d_ids, const void *d_rows, int src_dtype, uint64_t row_stride,
+                             uint64_t n, void *stream);
+int vrod_index_upsert_device(vrod_index *idx, const uint64_t *d_keys, const void *d_rows, int src_dtype, uint64_t row_stride,
+                             uint64_t n, uint64_t *d_out_ids, void *stream);
+int vrod_index_get_rows_device(vrod_index *idx, uint64_t first, uint64_t n, float *d_out_rows, uint64_t out_row_stride,
+                               void *stream);
+
 /* --- snapshots ------------------------------------------------------------- */
 /* A snapshot is one file that holds the whole observable state of a single-device handle; a handle loaded from it is
  * indistinguishable from the one that was saved, to the bit (<- the reference's Database::load, src/database/mod.rs,

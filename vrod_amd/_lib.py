@@ -36,6 +36,7 @@ SYMBOLS = [
     "vrod_index_set_keys", "vrod_index_get_keys", "vrod_index_find_keys", "vrod_index_find_keys_device",
     "vrod_index_ids_to_keys", "vrod_index_ids_to_keys_device", "vrod_index_delete_keys", "vrod_index_upsert",
     "vrod_index_key_stats",
+    "vrod_index_add_device", "vrod_index_update_device", "vrod_index_upsert_device", "vrod_index_get_rows_device",
 ]
 
 ERR_CAPACITY = 8   # VROD_ERR_CAPACITY: a range search's result does not fit the caller's buffers (out_lims is valid)
@@ -188,6 +189,10 @@ def load() -> C.CDLL:
     L.vrod_index_delete_keys.argtypes = [vp, vp, u64, C.POINTER(u64)]
     L.vrod_index_upsert.argtypes = [vp, vp, vp, u64, vp]
     L.vrod_index_key_stats.argtypes = [vp, C.POINTER(KeyStats)]
+    L.vrod_index_add_device.argtypes = [vp, vp, i32, u64, u64, vp]
+    L.vrod_index_update_device.argtypes = [vp, vp, vp, i32, u64, u64, vp]
+    L.vrod_index_upsert_device.argtypes = [vp, vp, vp, i32, u64, u64, vp, vp]
+    L.vrod_index_get_rows_device.argtypes = [vp, u64, u64, vp, u64, vp]
     for name in SYMBOLS:
         getattr(L, name).restype = i32
     L.vrod_last_error.restype = C.c_char_p

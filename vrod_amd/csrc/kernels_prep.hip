@@ -10,6 +10,7 @@
 //   fp64, then rounded to fp32; zero rows stay zero.  BF16: round to nearest even.
 #include "vrod_common.h"
 #include "vrod_kernels.h"
+#include "prep_chain.h"   // the norm chain and the divide, shared with kernels_ingest.hip
 
 namespace vrod {
 
@@ -54,9 +55,8 @@ __global__ __launch_bounds__(256) void row_norm_kernel(const float* __restrict__
     bool bad = false;
     for (uint32_t j = 0; j < dim; ++j) {
         const float f = x[j];
-        bad |= !(__builtin_fabsf(f) <= 3.4028234663852886e38f);  // NaN or Inf
-        const double v = (double)f;
-        ss = __builtin_fma(v, v, ss);
+        bad |= prep_is_bad(f);
+        ss = prep_chain_step(f, ss);
     }
     nrm[r] = __builtin_sqrt(ss);
     if (bad) atomicOr(bad_flag, 1u);
@@ -80,10 +80,7 @@ __global__ __launch_bounds__(256) void row_write_kernel(const float* __restrict_
         float v = 0.0f;
         if (j < dim) {
             v = in[r * (uint64_t)dim + j];
-            if (NORMALISE) {
-                const double d = nrm[r];
-                v = d == 0.0 ? 0.0f : (float)((double)v / d);
-            }
+            if (NORMALISE) v = prep_scale(v, nrm[r]);
         }
         if (round_bf16) {
             const bf16_t h = f32_to_bf16_rne(v);
@@ -161,29 +158,14 @@ __global__ __launch_bounds__(256) void prep_queries_kernel(const float* __restri
     if (live) {
         for (uint32_t j = tid; j < dim; j += 256) {
             const float f = in[(uint64_t)q * dim + j];
-            bad |= !(__builtin_fabsf(f) <= 3.4028234663852886e38f);
+            bad |= prep_is_bad(f);
             row[j] = f;
         }
     }
     __syncthreads();
     if (tid == 0) {
         double ss = 0.0;
-        if (live && NORMALISE) {
-            // same left-to-right fp64 chain, fed by 16-B LDS reads issued ahead of it (one scalar
-            // LDS read per step left the chain waiting ~100 cycles per element: 23 us at d = 768)
-            typedef float f32x4_t __attribute__((ext_vector_type(4)));
-            uint32_t j = 0;
-#pragma unroll 4
-            for (; j + 8 <= dim; j += 8) {
-                const f32x4_t a = *reinterpret_cast<const f32x4_t*>(row + j);
-                const f32x4_t b = *reinterpret_cast<const f32x4_t*>(row + j + 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { const double v = (double)a[e]; ss = __builtin_fma(v, v, ss); }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { const double v = (double)b[e]; ss = __builtin_fma(v, v, ss); }
-            }
-            for (; j < dim; ++j) { const double v = (double)row[j]; ss = __builtin_fma(v, v, ss); }
-        }
+        if (live && NORMALISE) ss = prep_chain_lds(row, dim);
         s_nrm = __builtin_sqrt(ss);
     }
     __syncthreads();
@@ -193,7 +175,7 @@ __global__ __launch_bounds__(256) void prep_queries_kernel(const float* __restri
         float v = 0.0f;
         if (live && j < dim) {
             v = row[j];
-            if (NORMALISE) v = nrm == 0.0 ? 0.0f : (float)((double)v / nrm);
+            if (NORMALISE) v = prep_scale(v, nrm);
         }
         if (round_bf16) {
             const bf16_t h = f32_to_bf16_rne(v);

@@ -46,6 +46,7 @@
 #include "combine_plan.h"
 #include "snapshot_plan.h"
 #include "keys_plan.h"
+#include "ingest_plan.h"
 
 using namespace vrod;
 
@@ -310,6 +311,8 @@ struct vrod_index {
     // vrod_index_update: a chunk's prepared rows and their destination rows; vrod_index_compact: live rows below each
     // 32-row word (compact_plan.h compact_word_bases)
     DevBuf upd_stage, upd_dst, compact_ws;
+    // the _device forms of add / update / upsert: a chunk's source rows (IngestSrc::pick) on the device
+    DevBuf ingest_pick;
     // range searches (vrod_range_search): the pool of qualifying rows and its sort partner, and the small block
     // [total (u64) | the caller's thresholds [nq] | per-query counters [nq]]
     DevBuf range_pool, range_pool_b, range_small;
@@ -569,14 +572,89 @@ static int check_bad_flag(vrod_index* idx, const char* what) {
     return VROD_OK;
 }
 
-static const uint64_t kStageRows = 1u << 16;
-// rows per staged chunk of an add or update of n rows: 256 MiB of raw rows at most
-static uint64_t stage_chunk_rows(const vrod_index* idx, uint64_t n) {
-    return std::min<uint64_t>(n, std::max<uint64_t>(1024, std::min<uint64_t>(kStageRows, (256ull << 20) / (idx->dim * 4ull))));
+// rows per staged chunk of an add or update of n rows: 256 MiB of raw rows at most (ingest_plan.h)
+static uint64_t stage_chunk_rows(const vrod_index* idx, uint64_t n) { return ingest_chunk_rows(n, idx->dim); }
+
+// ------------------------------------------------------------------ rows from device memory (the _device forms of add / update / upsert)
+// A source of typed, strided rows in device memory (include/vrod.h "device-resident ingest").  pick: a HOST list of the
+// source rows a pass takes, in the order of the pass (null: source row i is row i) -- how an update's rows reach their
+// shards and an upsert's rows split into held and new without the payload ever leaving the device.
+struct IngestSrc {
+    const void* p = nullptr;
+    int dtype = SRC_F32;
+    uint64_t stride = 0;
+    const uint64_t* pick = nullptr;
+    int device = 0;   // where p lives
+};
+// the source from row `first` of the pass on
+static IngestSrc ingest_from(const IngestSrc& s, uint64_t first) {
+    IngestSrc t = s;
+    if (t.pick) t.pick += first;
+    else t.p = (const char*)s.p + first * s.stride * ingest_elem_bytes(s.dtype);
+    return t;
+}
+// VROD_INGEST_STAGE=1: every source goes the way of one on another device (packed, copied peer to peer, ingested from
+// the dense copy), so that a one-GPU box can rehearse that way.  Read per call.
+static bool ingest_force_stage() {
+    const char* e = getenv("VROD_INGEST_STAGE");
+    return e && e[0] == '1';
 }
 
+// Rows [0, m) of `src` become prepared rows [m][ld] at `out` (on idx's device, which is current), on idx->stream; NaN /
+// Inf raise idx->flags[0] as the host forms' prepare raises it.
+static int ingest_prepare(vrod_index* idx, const IngestSrc& src, uint64_t m, void* out) {
+    const int form = prep_form(idx->metric);
+    if (src.device == idx->device && !ingest_force_stage()) {
+        const uint64_t* d_pick = nullptr;
+        if (src.pick) {
+            VROD_TRY(idx->ingest_pick.ensure(m * 8));
+            HIP_TRY(hipMemcpyAsync(idx->ingest_pick.p, src.pick, m * 8, hipMemcpyHostToDevice, idx->stream));
+            d_pick = idx->ingest_pick.as<uint64_t>();
+        }
+        launch_ingest_rows(src.p, src.dtype, src.stride, d_pick, m, idx->dim, idx->ld, form, idx->dtype, &idx->flags[0], out, idx->stream);
+        HIP_TRY(hipGetLastError());
+        return VROD_OK;
+    }
+    // The source lives on another device: pack the rows there (dense, in their own type), copy them peer to peer into
+    // the shard's staging buffer, ingest from that.  The staging buffer may still feed the previous chunk's launch.
+    const size_t bytes = (size_t)m * idx->dim * ingest_elem_bytes(src.dtype);
+    VROD_TRY(idx->raw_stage.ensure(bytes));
+    HIP_TRY(hipStreamSynchronize(idx->stream));
+    HIP_TRY(hipSetDevice(src.device));
+    int rc = VROD_OK;
+    {
+        DevBuf pack, picks;   // on the source's device, for this chunk only
+        rc = pack.ensure(bytes);
+        if (rc == VROD_OK && src.pick) rc = picks.ensure(m * 8);
+        hipError_t e = hipSuccess;
+        if (rc == VROD_OK && src.pick) e = hipMemcpy(picks.p, src.pick, m * 8, hipMemcpyHostToDevice);
+        if (rc == VROD_OK && e == hipSuccess) {
+            launch_ingest_pack(src.p, src.dtype, src.stride, src.pick ? picks.as<uint64_t>() : nullptr, m, idx->dim, pack.p, nullptr);
+            e = hipGetLastError();
+        }
+        if (rc == VROD_OK && e == hipSuccess) e = hipMemcpyPeerAsync(idx->raw_stage.p, idx->device, pack.p, src.device, bytes, nullptr);
+        if (rc == VROD_OK && e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (rc == VROD_OK && e != hipSuccess) rc = fail(VROD_ERR_HIP, "staging rows from device %d: %s", src.device, hipGetErrorString(e));
+    }
+    HIP_TRY(hipSetDevice(idx->device));
+    VROD_TRY(rc);
+    launch_ingest_rows(idx->raw_stage.p, src.dtype, idx->dim, nullptr, m, idx->dim, idx->ld, form, idx->dtype, &idx->flags[0], out, idx->stream);
+    HIP_TRY(hipGetLastError());
+    return VROD_OK;
+}
+
+// append_prepared for a device-resident source
+static int append_ingested(vrod_index* idx, const IngestSrc& src, uint64_t n) {
+    char* dst = (char*)idx->corpus + idx->count * idx->row_bytes();
+    VROD_TRY(ingest_prepare(idx, src, n, dst));
+    launch_row_fastnorm(dst, idx->dtype, n, idx->ld, idx->xnorm2 + idx->count, idx->max_xn2_bits, idx->stream);
+    HIP_TRY(hipGetLastError());
+    return VROD_OK;
+}
+
+// dev: the rows come from device memory (rows == null, not synthetic)
 static int index_add(vrod_index* idx, const float* rows, uint64_t n, bool synthetic, uint64_t seed,
-                     uint64_t first_row) {
+                     uint64_t first_row, const IngestSrc* dev = nullptr) {
     if (!n) return VROD_OK;
     VROD_TRY(set_device(idx));
     idx->doc_valid = false;   // (the document index of a multi-vector search covers the rows it was built from)
@@ -591,9 +669,14 @@ static int index_add(vrod_index* idx, const float* rows, uint64_t n, bool synthe
     // void) the certificate bound of every later search
     HIP_TRY(hipMemcpyAsync(&idx->flags[9], idx->max_xn2_bits, 4, hipMemcpyDeviceToDevice, idx->stream));
     const uint64_t chunk = stage_chunk_rows(idx, n);
-    VROD_TRY(idx->raw_stage.ensure(chunk * idx->dim * sizeof(float)));
+    if (!dev) VROD_TRY(idx->raw_stage.ensure(chunk * idx->dim * sizeof(float)));
     for (uint64_t done = 0; done < n; done += chunk) {
         const uint64_t m = std::min(chunk, n - done);
+        if (dev) {
+            VROD_TRY(append_ingested(idx, ingest_from(*dev, done), m));
+            idx->count += m;
+            continue;
+        }
         if (synthetic) {
             launch_synth_rows(seed, first_row + done, m, idx->dim, idx->raw_stage.as<float>(), idx->stream);
         } else {
@@ -624,20 +707,26 @@ static int index_add(vrod_index* idx, const float* rows, uint64_t n, bool synthe
 //                and its bf16 planes where they exist (kernels_mutate.hip).  check_first: the call fits one chunk and
 //                has not been checked: the flag is read between the prepare and the scatter.
 // Nothing but the scatter writes to the corpus, xnorm2 or max_xn2_bits, so a rejected update changes none of them.
-static int index_update_pass(vrod_index* idx, const uint32_t* dst, const float* rows, uint64_t n, bool check_first) {
+// dev: the rows come from device memory (rows == null): the ingest kernel prepares them into upd_stage, the rest is the same.
+static int index_update_pass(vrod_index* idx, const uint32_t* dst, const float* rows, uint64_t n, bool check_first,
+                             const IngestSrc* dev = nullptr) {
     VROD_TRY(set_device(idx));
     const uint64_t chunk = stage_chunk_rows(idx, n);
-    VROD_TRY(idx->raw_stage.ensure(chunk * idx->dim * sizeof(float)));
+    if (!dev) VROD_TRY(idx->raw_stage.ensure(chunk * idx->dim * sizeof(float)));
     VROD_TRY(idx->upd_stage.ensure(chunk * idx->row_bytes()));
-    VROD_TRY(idx->nrm_ws.ensure(chunk * sizeof(double)));
+    if (!dev) VROD_TRY(idx->nrm_ws.ensure(chunk * sizeof(double)));
     if (dst) VROD_TRY(idx->upd_dst.ensure(chunk * 4));
     for (uint64_t done = 0; done < n; done += chunk) {
         const uint64_t m = std::min(chunk, n - done);
-        HIP_TRY(hipMemcpyAsync(idx->raw_stage.p, rows + done * idx->dim, m * idx->dim * sizeof(float), hipMemcpyHostToDevice, idx->stream));
-        launch_prepare_rows(idx->raw_stage.as<float>(), m, idx->dim, idx->ld, prep_form(idx->metric), idx->dtype, idx->nrm_ws.as<double>(),
-                            &idx->flags[0], idx->dtype == VROD_DTYPE_F32 ? idx->upd_stage.as<float>() : nullptr,
-                            idx->dtype == VROD_DTYPE_BF16 ? idx->upd_stage.p : nullptr, idx->stream);
-        HIP_TRY(hipGetLastError());
+        if (dev) {
+            VROD_TRY(ingest_prepare(idx, ingest_from(*dev, done), m, idx->upd_stage.p));
+        } else {
+            HIP_TRY(hipMemcpyAsync(idx->raw_stage.p, rows + done * idx->dim, m * idx->dim * sizeof(float), hipMemcpyHostToDevice, idx->stream));
+            launch_prepare_rows(idx->raw_stage.as<float>(), m, idx->dim, idx->ld, prep_form(idx->metric), idx->dtype, idx->nrm_ws.as<double>(),
+                                &idx->flags[0], idx->dtype == VROD_DTYPE_F32 ? idx->upd_stage.as<float>() : nullptr,
+                                idx->dtype == VROD_DTYPE_BF16 ? idx->upd_stage.p : nullptr, idx->stream);
+            HIP_TRY(hipGetLastError());
+        }
         if (!dst) continue;
         if (check_first) VROD_TRY(check_bad_flag(idx, "rows"));
         HIP_TRY(hipMemcpyAsync(idx->upd_dst.p, dst + done, m * 4, hipMemcpyHostToDevice, idx->stream));
@@ -651,10 +740,10 @@ static int index_update_pass(vrod_index* idx, const uint32_t* dst, const float* 
 }
 
 // dst: per row of the call its local row, or kScatterSkip for an id that the call names again later
-static int index_update(vrod_index* idx, const std::vector<uint32_t>& dst, const float* rows, uint64_t n) {
-    if (n <= stage_chunk_rows(idx, n)) return index_update_pass(idx, dst.data(), rows, n, true);
-    VROD_TRY(index_update_pass(idx, nullptr, rows, n, false));
-    return index_update_pass(idx, dst.data(), rows, n, false);
+static int index_update(vrod_index* idx, const std::vector<uint32_t>& dst, const float* rows, uint64_t n, const IngestSrc* dev = nullptr) {
+    if (n <= stage_chunk_rows(idx, n)) return index_update_pass(idx, dst.data(), rows, n, true, dev);
+    VROD_TRY(index_update_pass(idx, nullptr, rows, n, false, dev));
+    return index_update_pass(idx, dst.data(), rows, n, false, dev);
 }
 
 static void mask_changed(vrod_index* idx);
@@ -1770,7 +1859,7 @@ static int order_after_caller(vrod_index* idx, void* stream) {
 }
 
 // ------------------------------------------------------------------ composite (multi-device) handle
-static const uint64_t kShardBlock = 65536;
+static const uint64_t kShardBlock = kDealBlock;   // (ingest_plan.h: the dealing is tested on the host there)
 
 // global rows [first, first + n) cut at block boundaries: f(shard, global_first, count)
 template <typename F>
@@ -1779,19 +1868,18 @@ static int for_each_piece(const vrod_index* idx, uint64_t first, uint64_t n, F&&
     uint64_t r = first;
     const uint64_t end = first + n;
     while (r < end) {
-        const uint64_t blk = r / kShardBlock;
-        const uint64_t m = std::min<uint64_t>(end - r, (blk + 1) * kShardBlock - r);
-        VROD_TRY(f((size_t)(blk % G), r, m));
+        const uint64_t m = deal_piece_rows(r, end);
+        VROD_TRY(f((size_t)deal_shard(r, G), r, m));
         r += m;
     }
     return VROD_OK;
 }
 static uint64_t local_row_of(const vrod_index* idx, uint64_t r) {
-    const uint64_t G = idx->shards.size();
-    return (r / (kShardBlock * G)) * kShardBlock + r % kShardBlock;
+    return deal_local_row(r, idx->shards.size());
 }
 
-static int composite_add(vrod_index* idx, const float* rows, uint64_t n, bool synthetic, uint64_t seed, uint64_t first_row) {
+static int composite_add(vrod_index* idx, const float* rows, uint64_t n, bool synthetic, uint64_t seed, uint64_t first_row,
+                         const IngestSrc* dev = nullptr) {
     const uint64_t count0 = idx->count;
     for (vrod_index* sh : idx->shards) {   // what a roll-back restores (see index_add)
         VROD_TRY(set_device(sh));
@@ -1800,6 +1888,10 @@ static int composite_add(vrod_index* idx, const float* rows, uint64_t n, bool sy
     int rc = for_each_piece(idx, count0, n, [&](size_t g, uint64_t r, uint64_t m) {
         vrod_index* sh = idx->shards[g];
         if (sh->count != local_row_of(idx, r)) return fail(VROD_ERR_INTERNAL, "shard %zu is out of step", g);
+        if (dev) {
+            const IngestSrc piece = ingest_from(*dev, r - count0);
+            return index_add(sh, nullptr, m, false, 0, 0, &piece);
+        }
         return index_add(sh, rows ? rows + (r - count0) * idx->dim : nullptr, m, synthetic, seed, first_row + (r - count0));
     });
     if (rc != VROD_OK) {
@@ -1980,20 +2072,26 @@ static int composite_delete(vrod_index* idx, const uint64_t* ids, uint64_t n) {
 // An update of a composite handle: each row goes to the shard that holds its id.  Every shard checks its rows (NaN /
 // Inf) before any shard writes one, so a rejected call changes nothing on the handle as a whole.
 // rows_of: per row of the call its global row, skip[i]: the call names that id again later.
-static int composite_update(vrod_index* idx, const std::vector<uint64_t>& rows_of, const std::vector<bool>& skip, const float* rows) {
+// dev: the rows are in device memory (rows == null): each shard takes its rows of the source through a list of them.
+static int composite_update(vrod_index* idx, const std::vector<uint64_t>& rows_of, const std::vector<bool>& skip, const float* rows,
+                            const IngestSrc* dev = nullptr) {
     const size_t G = idx->shards.size();
     std::vector<std::vector<uint32_t>> dst(G);
     std::vector<std::vector<float>> buf(G);
+    std::vector<std::vector<uint64_t>> pick(G);
     for (size_t i = 0; i < rows_of.size(); ++i) {
         const uint64_t r = rows_of[i];
         const size_t g = (size_t)((r / kShardBlock) % G);
         dst[g].push_back(skip[i] ? kScatterSkip : (uint32_t)local_row_of(idx, r));
-        buf[g].insert(buf[g].end(), rows + i * idx->dim, rows + (i + 1) * idx->dim);
+        if (dev) pick[g].push_back(dev->pick ? dev->pick[i] : (uint64_t)i);
+        else buf[g].insert(buf[g].end(), rows + i * idx->dim, rows + (i + 1) * idx->dim);
     }
+    std::vector<IngestSrc> src(G);
+    for (size_t g = 0; g < G && dev; ++g) { src[g] = *dev; src[g].pick = pick[g].data(); }
     for (size_t g = 0; g < G; ++g)
-        if (!dst[g].empty()) VROD_TRY(index_update_pass(idx->shards[g], nullptr, buf[g].data(), dst[g].size(), false));
+        if (!dst[g].empty()) VROD_TRY(index_update_pass(idx->shards[g], nullptr, buf[g].data(), dst[g].size(), false, dev ? &src[g] : nullptr));
     for (size_t g = 0; g < G; ++g)
-        if (!dst[g].empty()) VROD_TRY(index_update_pass(idx->shards[g], dst[g].data(), buf[g].data(), dst[g].size(), false));
+        if (!dst[g].empty()) VROD_TRY(index_update_pass(idx->shards[g], dst[g].data(), buf[g].data(), dst[g].size(), false, dev ? &src[g] : nullptr));
     return VROD_OK;
 }
 
@@ -4426,9 +4524,8 @@ int vrod_index_delete(vrod_index* idx, const uint64_t* ids, uint64_t n) {
     return index_delete_rows(idx, rows);
 }
 
-int vrod_index_update(vrod_index* idx, const uint64_t* ids, const float* rows, uint64_t n) {
-    if (!idx || ((!ids || !rows) && n)) return fail(VROD_ERR_INVALID_ARG, "null argument");
-    VROD_TRY(require_idle(idx, "vrod_index_update"));
+// vrod_index_update behind its argument checks; ids: host memory.  dev: the rows are in device memory (rows == null).
+static int update_checked(vrod_index* idx, const uint64_t* ids, const float* rows, uint64_t n, const IngestSrc* dev) {
     const size_t G = idx->shards.size();
     std::vector<uint64_t> rows_of(n);
     for (uint64_t i = 0; i < n; ++i) {   // the whole call or nothing
@@ -4450,10 +4547,101 @@ int vrod_index_update(vrod_index* idx, const uint64_t* ids, const float* rows, u
         if (seen[rows_of[i]]) skip[i] = true;
         seen[rows_of[i]] = true;
     }
-    if (G) return composite_update(idx, rows_of, skip, rows);
+    if (G) return composite_update(idx, rows_of, skip, rows, dev);
     std::vector<uint32_t> dst(n);
     for (uint64_t i = 0; i < n; ++i) dst[i] = skip[i] ? kScatterSkip : (uint32_t)rows_of[i];
-    return index_update(idx, dst, rows, n);
+    return index_update(idx, dst, rows, n, dev);
+}
+
+int vrod_index_update(vrod_index* idx, const uint64_t* ids, const float* rows, uint64_t n) {
+    if (!idx || ((!ids || !rows) && n)) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    VROD_TRY(require_idle(idx, "vrod_index_update"));
+    return update_checked(idx, ids, rows, n, nullptr);
+}
+
+// ------------------------------------------------------------------ device-resident ingest: add / update / get_rows
+// What the three _device forms that take rows check before any device call.
+static int check_ingest_args(const vrod_index* idx, const char* what, const void* d_rows, int src_dtype, uint64_t row_stride, uint64_t n) {
+    if (!ingest_dtype_known(src_dtype)) return fail(VROD_ERR_INVALID_ARG, "%s: unknown src_dtype %d", what, src_dtype);
+    if (!idx) return fail(VROD_ERR_INVALID_ARG, "%s: idx is null", what);
+    if (!d_rows && n) return fail(VROD_ERR_INVALID_ARG, "%s: d_rows is null", what);
+    switch (ingest_check_layout((uint64_t)(uintptr_t)d_rows, src_dtype, row_stride, idx->dim, n)) {
+        case INGEST_OK: return VROD_OK;
+        case INGEST_BAD_STRIDE:
+            return fail(VROD_ERR_INVALID_ARG, "%s: row_stride %llu is less than dim %u", what, (unsigned long long)row_stride, idx->dim);
+        case INGEST_OVERFLOW: return fail(VROD_ERR_INVALID_ARG, "%s: n * row_stride overflows 64 bits", what);
+        default: return fail(VROD_ERR_INVALID_ARG, "%s: d_rows is not aligned to its element", what);
+    }
+}
+
+// The stream rule of the synchronous device forms (begin_sync_device), then where the caller's rows live.
+static int ingest_open(vrod_index* idx, const char* what, const void* d_ptr, void* stream, int* device) {
+    VROD_TRY(set_device(idx));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, d_ptr) != hipSuccess || at.type != hipMemoryTypeDevice) {
+        (void)hipGetLastError();
+        return fail(VROD_ERR_INVALID_ARG, "%s: the rows are not in device memory", what);
+    }
+    *device = at.device;
+    return VROD_OK;
+}
+
+int vrod_index_add_device(vrod_index* idx, const void* d_rows, int src_dtype, uint64_t row_stride, uint64_t n, void* stream) {
+    VROD_TRY(check_ingest_args(idx, "vrod_index_add_device", d_rows, src_dtype, row_stride, n));
+    VROD_TRY(require_idle(idx, "vrod_index_add_device"));
+    if (!n) return VROD_OK;
+    IngestSrc src;
+    src.p = d_rows; src.dtype = src_dtype; src.stride = row_stride;
+    VROD_TRY(ingest_open(idx, "vrod_index_add_device", d_rows, stream, &src.device));
+    if (idx->composite()) return composite_add(idx, nullptr, n, false, 0, 0, &src);
+    return index_add(idx, nullptr, n, false, 0, 0, &src);
+}
+
+int vrod_index_update_device(vrod_index* idx, const uint64_t* d_ids, const void* d_rows, int src_dtype, uint64_t row_stride, uint64_t n,
+                             void* stream) {
+    VROD_TRY(check_ingest_args(idx, "vrod_index_update_device", d_rows, src_dtype, row_stride, n));
+    if (!d_ids && n) return fail(VROD_ERR_INVALID_ARG, "vrod_index_update_device: d_ids is null");
+    VROD_TRY(require_idle(idx, "vrod_index_update_device"));
+    if (!n) return VROD_OK;
+    IngestSrc src;
+    src.p = d_rows; src.dtype = src_dtype; src.stride = row_stride;
+    VROD_TRY(ingest_open(idx, "vrod_index_update_device", d_rows, stream, &src.device));
+    std::vector<uint64_t> ids(n);   // 8 bytes per row cross to the host for the host form's checks; the rows stay
+    HIP_TRY(hipMemcpy(ids.data(), d_ids, n * 8, hipMemcpyDeviceToHost));
+    return update_checked(idx, ids.data(), nullptr, n, &src);
+}
+
+// Rows [first, first + m) of a single-device handle (or shard) as fp32 at d_out, out_stride floats apart.
+static int get_rows_to_device(vrod_index* idx, uint64_t first, uint64_t m, float* d_out, uint64_t out_stride, int out_device) {
+    VROD_TRY(set_device(idx));
+    const char* rows = (const char*)idx->corpus + first * idx->row_bytes();
+    if (out_device == idx->device && !ingest_force_stage()) {
+        launch_rows_get_strided(rows, idx->dtype, m, idx->dim, idx->ld, d_out, out_stride, idx->stream);
+        HIP_TRY(hipGetLastError());
+    } else {   // the output lives on another device: dense rows here, then a pitched copy
+        VROD_TRY(idx->raw_stage.ensure(m * idx->dim * 4));
+        launch_rows_get(rows, idx->dtype, m, idx->dim, idx->ld, idx->raw_stage.as<float>(), idx->stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy2DAsync(d_out, out_stride * 4, idx->raw_stage.p, (size_t)idx->dim * 4, (size_t)idx->dim * 4, m, hipMemcpyDeviceToDevice,
+                                 idx->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(idx->stream));
+    return VROD_OK;
+}
+
+int vrod_index_get_rows_device(vrod_index* idx, uint64_t first, uint64_t n, float* d_out_rows, uint64_t out_row_stride, void* stream) {
+    VROD_TRY(check_ingest_args(idx, "vrod_index_get_rows_device", d_out_rows, SRC_F32, out_row_stride, n));
+    if (first > idx->count || n > idx->count - first)
+        return fail(VROD_ERR_INVALID_ARG, "rows [%llu, %llu) out of range", (unsigned long long)first, (unsigned long long)(first + n));
+    VROD_TRY(require_idle(idx, "vrod_index_get_rows_device"));
+    if (!n) return VROD_OK;
+    int out_device = 0;
+    VROD_TRY(ingest_open(idx, "vrod_index_get_rows_device", d_out_rows, stream, &out_device));
+    if (!idx->composite()) return get_rows_to_device(idx, first, n, d_out_rows, out_row_stride, out_device);
+    return for_each_piece(idx, first, n, [&](size_t g, uint64_t r, uint64_t m) {
+        return get_rows_to_device(idx->shards[g], local_row_of(idx, r), m, d_out_rows + (r - first) * out_row_stride, out_row_stride, out_device);
+    });
 }
 
 int vrod_index_compact(vrod_index* idx, uint64_t* out_new_ids, uint64_t map_len) {
@@ -4932,11 +5120,9 @@ int vrod_index_delete_keys(vrod_index* idx, const uint64_t* keys, uint64_t n, ui
     return VROD_OK;
 }
 
-int vrod_index_upsert(vrod_index* idx, const uint64_t* keys, const float* rows, uint64_t n, uint64_t* out_ids) {
-    if (!idx || ((!keys || !rows) && n)) return fail(VROD_ERR_INVALID_ARG, "null argument");
-    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "vrod_index_upsert %s", kKeysNotRouted);
-    VROD_TRY(require_idle(idx, "vrod_index_upsert"));
-    if (!n) return VROD_OK;
+// vrod_index_upsert on an idle single-device handle, n > 0; keys and out_ids: host memory.  dev: the rows are in device
+// memory (rows == null): the held and the new rows are taken from the source through lists of them.
+static int upsert_checked(vrod_index* idx, const uint64_t* keys, const float* rows, uint64_t n, uint64_t* out_ids, const IngestSrc* dev) {
     // every check before the first row is written: the keys on the host, the vectors by a prepare-only pass
     {
         std::vector<uint64_t> sorted(keys, keys + n);
@@ -4945,7 +5131,7 @@ int vrod_index_upsert(vrod_index* idx, const uint64_t* keys, const float* rows, 
         const auto twice = std::adjacent_find(sorted.begin(), sorted.end());
         if (twice != sorted.end()) return fail(VROD_ERR_INVALID_ARG, "vrod_index_upsert: key %llu is named twice", (unsigned long long)*twice);
     }
-    VROD_TRY(index_update_pass(idx, nullptr, rows, n, false));
+    VROD_TRY(index_update_pass(idx, nullptr, rows, n, false, dev));
     std::vector<uint64_t> found(n);
     VROD_TRY(keys_find_host(idx, "vrod_index_upsert", keys, n, found.data()));
     // the rows of held keys are updated in place, the others appended in the order of the call and keyed
@@ -4953,23 +5139,57 @@ int vrod_index_upsert(vrod_index* idx, const uint64_t* keys, const float* rows, 
     std::vector<uint32_t> dst;
     std::vector<uint64_t> new_keys;
     std::vector<float> held_rows, new_rows;
+    std::vector<uint64_t> held_pick, new_pick;
     const uint64_t count0 = idx->count;
     for (uint64_t i = 0; i < n; ++i) {
         if (found[i] != kKeyNone) {
             dst.push_back((uint32_t)(found[i] - idx->id_offset));
-            held_rows.insert(held_rows.end(), rows + i * dim, rows + (i + 1) * dim);
+            if (dev) held_pick.push_back(i);
+            else held_rows.insert(held_rows.end(), rows + i * dim, rows + (i + 1) * dim);
         } else {
             found[i] = idx->id_offset + count0 + new_keys.size();
             new_keys.push_back(keys[i]);
-            new_rows.insert(new_rows.end(), rows + i * dim, rows + (i + 1) * dim);
+            if (dev) new_pick.push_back(i);
+            else new_rows.insert(new_rows.end(), rows + i * dim, rows + (i + 1) * dim);
         }
     }
+    IngestSrc held_src, new_src;
+    if (dev) {
+        held_src = new_src = *dev;
+        held_src.pick = held_pick.data();
+        new_src.pick = new_pick.data();
+    }
     if (!new_keys.empty()) {
-        VROD_TRY(index_add(idx, new_rows.data(), new_keys.size(), false, 0, 0));
+        VROD_TRY(index_add(idx, dev ? nullptr : new_rows.data(), new_keys.size(), false, 0, 0, dev ? &new_src : nullptr));
         VROD_TRY(keys_set_range(idx, "vrod_index_upsert", count0, new_keys.data(), new_keys.size(), false));
     }
-    if (!dst.empty()) VROD_TRY(index_update(idx, dst, held_rows.data(), dst.size()));
+    if (!dst.empty()) VROD_TRY(index_update(idx, dst, dev ? nullptr : held_rows.data(), dst.size(), dev ? &held_src : nullptr));
     if (out_ids) std::copy(found.begin(), found.end(), out_ids);
+    return VROD_OK;
+}
+
+int vrod_index_upsert(vrod_index* idx, const uint64_t* keys, const float* rows, uint64_t n, uint64_t* out_ids) {
+    if (!idx || ((!keys || !rows) && n)) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "vrod_index_upsert %s", kKeysNotRouted);
+    VROD_TRY(require_idle(idx, "vrod_index_upsert"));
+    if (!n) return VROD_OK;
+    return upsert_checked(idx, keys, rows, n, out_ids, nullptr);
+}
+
+int vrod_index_upsert_device(vrod_index* idx, const uint64_t* d_keys, const void* d_rows, int src_dtype, uint64_t row_stride, uint64_t n,
+                             uint64_t* d_out_ids, void* stream) {
+    VROD_TRY(check_ingest_args(idx, "vrod_index_upsert_device", d_rows, src_dtype, row_stride, n));
+    if (!d_keys && n) return fail(VROD_ERR_INVALID_ARG, "vrod_index_upsert_device: d_keys is null");
+    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "vrod_index_upsert_device %s", kKeysNotRouted);
+    VROD_TRY(require_idle(idx, "vrod_index_upsert_device"));
+    if (!n) return VROD_OK;
+    IngestSrc src;
+    src.p = d_rows; src.dtype = src_dtype; src.stride = row_stride;
+    VROD_TRY(ingest_open(idx, "vrod_index_upsert_device", d_rows, stream, &src.device));
+    std::vector<uint64_t> keys(n), ids(n);   // the keys cross to the host for the host form's checks; the rows stay
+    HIP_TRY(hipMemcpy(keys.data(), d_keys, n * 8, hipMemcpyDeviceToHost));
+    VROD_TRY(upsert_checked(idx, keys.data(), nullptr, n, ids.data(), &src));
+    if (d_out_ids) HIP_TRY(hipMemcpy(d_out_ids, ids.data(), n * 8, hipMemcpyHostToDevice));
     return VROD_OK;
 }
 

@@ -64,6 +64,19 @@ void launch_row_fastnorm(const void* d_rows, int dtype, uint64_t n, uint32_t ld,
 void launch_rows_get(const void* d_rows, int dtype, uint64_t n, uint32_t dim, uint32_t ld,
                      float* d_out, hipStream_t s);
 
+// ---- kernels_ingest.hip : rows that are in device memory already (vrod_index_add_device and its kin)
+// n typed rows (src_dtype: ingest_plan.h SRC_*), row r at element (d_pick ? d_pick[r] : r) * row_stride of d_src, become
+// prepared rows [n][ld] at d_out exactly as launch_prepare_rows prepares the same fp32 values, in one read of the
+// source; NaN / Inf raise *d_bad_flag.
+void launch_ingest_rows(const void* d_src, int src_dtype, uint64_t row_stride, const uint64_t* d_pick, uint64_t n, uint32_t dim,
+                        uint32_t ld, int metric, int dtype, uint32_t* d_bad_flag, void* d_out, hipStream_t s);
+// the same rows as dense rows [n][dim] of their own type (the staging leg of a source on another device)
+void launch_ingest_pack(const void* d_src, int src_dtype, uint64_t row_stride, const uint64_t* d_pick, uint64_t n, uint32_t dim,
+                        void* d_out, hipStream_t s);
+// launch_rows_get with out_stride (>= dim) floats between the rows it writes
+void launch_rows_get_strided(const void* d_rows, int dtype, uint64_t n, uint32_t dim, uint32_t ld, float* d_out, uint64_t out_stride,
+                             hipStream_t s);
+
 // ---- kernels_mutate.hip : vrod_index_update / vrod_index_compact
 // Update: prepared row i of d_staged becomes corpus row d_dst[i] (kScatterSkip: left out), with its xnorm2 entry, the
 // running maximum and -- fp32 handles, rows below planes_rows of non-null d_planes -- its bf16 [hi | lo] planes.

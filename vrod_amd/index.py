@@ -15,6 +15,7 @@ from . import _lib
 from ._lib import KeyStats, MultivecStats, SearchStats, SnapshotInfo, VrodError, check
 
 DTYPE_F32, DTYPE_BF16 = 0, 1
+SRC_F32, SRC_BF16, SRC_F16 = 0, 1, 2   # vrod_src_dtype: the element type of rows given in device memory
 METRIC_COSINE, METRIC_L2, METRIC_IP = 0, 1, 2
 PATH_AUTO, PATH_STREAM, PATH_MFMA, PATH_EXACT, PATH_GATHER = 0, 1, 2, 3, 4
 ID_NONE = np.uint64(0xFFFFFFFFFFFFFFFF)
@@ -352,6 +353,69 @@ class Index:
             raise ValueError(f"rows must be [{a.size}, {self.dim}]")
         out = np.empty(a.size, dtype=np.uint64)
         check(self._L.vrod_index_upsert(self._h, _ptr(a), _ptr(rows), a.size, _ptr(out)))
+        return out
+
+    # -- device-resident ingest
+    def _device_rows(self, t, what="rows"):
+        """Checks a source (or destination) of rows in GPU memory: a 2-D CUDA tensor [n, dim] of float32, bfloat16 or
+        float16 whose rows are contiguous (stride(1) == 1) and stride(0) >= dim apart -- a row or column slice of a
+        larger tensor is fine.  -> (n, the vrod_src_dtype, stride(0), its device's current stream)."""
+        import torch
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{what} must be a torch tensor, got {type(t).__name__}")
+        src = {torch.float32: SRC_F32, torch.bfloat16: SRC_BF16, torch.float16: SRC_F16}.get(t.dtype)
+        if src is None:
+            raise ValueError(f"{what} must be float32, bfloat16 or float16, got {t.dtype}")
+        if t.dim() != 2 or t.shape[1] != self.dim:
+            raise ValueError(f"{what} must be [n, {self.dim}], got {tuple(t.shape)}")
+        n = t.shape[0]
+        stride = t.stride(0) if n > 1 else max(t.stride(0), self.dim)   # (a single row's stride is never used)
+        if self.dim > 1 and t.stride(1) != 1:
+            raise ValueError(f"{what} must have contiguous rows (stride(1) == 1), got stride {t.stride(1)}")
+        if stride < self.dim:
+            raise ValueError(f"{what} must have stride(0) >= {self.dim}, got {t.stride(0)}")
+        if not t.is_cuda:
+            raise ValueError(f"{what} must be a tensor on the GPU, got device {t.device}")
+        return n, src, stride, C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+    def add_device(self, t):
+        """add() from a CUDA tensor [n, dim] (float32 / bfloat16 / float16, any row stride >= dim): the rows never touch
+        the host (vrod_index_add_device).  The handle ends up exactly as add() of the widened rows leaves it."""
+        n, src, stride, stream = self._device_rows(t)
+        check(self._L.vrod_index_add_device(self._h, t.data_ptr(), src, stride, n, stream))
+
+    def update_device(self, d_ids, t):
+        """update() from a CUDA int64 tensor of ids (the bits of uint64) and a CUDA tensor of rows (vrod_index_update_device)."""
+        n, src, stride, stream = self._device_rows(t)
+        n_ids, _ = self._device_u64(d_ids, "ids")
+        if n_ids != n:
+            raise ValueError(f"rows must be [{n_ids}, {self.dim}]")
+        check(self._L.vrod_index_update_device(self._h, d_ids.data_ptr(), t.data_ptr(), src, stride, n, stream))
+
+    def upsert_device(self, d_keys, t, out_ids=None):
+        """upsert() from a CUDA int64 tensor of keys and a CUDA tensor of rows (vrod_index_upsert_device) -> each key's id,
+        a CUDA int64 tensor."""
+        import torch
+        n, src, stride, stream = self._device_rows(t)
+        n_keys, _ = self._device_u64(d_keys, "keys")
+        if n_keys != n:
+            raise ValueError(f"rows must be [{n_keys}, {self.dim}]")
+        out_ids = _device_out(out_ids, (n,), torch.int64, t.device)
+        if out_ids.numel() != n:
+            raise ValueError(f"out_ids must hold {n} ids")
+        self._device_u64(out_ids, "out_ids")
+        check(self._L.vrod_index_upsert_device(self._h, d_keys.data_ptr(), t.data_ptr(), src, stride, n, out_ids.data_ptr(), stream))
+        return out_ids
+
+    def get_rows_device(self, first: int, n: int, out=None):
+        """get_rows() into a CUDA float32 tensor [n, dim] (vrod_index_get_rows_device); `out` may be a strided view, the
+        elements between its rows are not written."""
+        import torch
+        out = _device_out(out, (int(n), self.dim), torch.float32, torch.device("cuda", self.device))
+        rows, src, stride, stream = self._device_rows(out, "out")
+        if src != SRC_F32 or rows != int(n):
+            raise ValueError(f"out must be a float32 tensor [{int(n)}, {self.dim}]")
+        check(self._L.vrod_index_get_rows_device(self._h, int(first), int(n), out.data_ptr(), stride, stream))
         return out
 
     def key_stats(self) -> dict:
