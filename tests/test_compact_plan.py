@@ -1,13 +1,15 @@
 """The host-side plan of vrod_index_compact (vrod_amd/csrc/compact_plan.h), checked on the host: a small driver is
 compiled with g++ against the real header, reads tombstone patterns and prints, for each, the chunk plan, the per-word
-destination bases, the new-id map and a compacted bit vector.  Everything is compared with a numpy restatement:
+destination bases, the new-id map, a compacted bit vector and two compacted row columns (a 4-byte one whose default is
+0 and an 8-byte one whose default is every bit set).  Everything is compared with a numpy restatement:
 
   - every live row is read exactly once (the chunks are ascending and disjoint, the rows between them are all
     deleted); rows below the first moved row are live and stay; a staged chunk fits the staging buffer;
   - destinations are dense and order-preserving (w0 = live rows below r0, L = live rows of the chunk);
   - a chunk marked direct has w0 + L <= r0, a staged one does not;
   - no chunk's destination reaches a later chunk's source;
-  - the id map, the word bases and the compacted allow bits equal numpy's."""
+  - the id map, the word bases and the compacted allow bits equal numpy's;
+  - a compacted column holds the survivors' words in order, then its default up to the count, and nothing beyond."""
 import os
 import shutil
 import subprocess
@@ -51,10 +53,31 @@ int main() {
         printf("B %llu", n);
         for (size_t w = 0; w < words + 3; ++w) printf(" %x", out[w]);
         printf("\n");
+        // the row columns: word r of each is a fixed function of r (COL4 / COL8 below), two canaries past the count
+        std::vector<uint32_t> col4(count + 1), out4(count + 2, 0xDEADBEEFu);
+        std::vector<uint64_t> col8(count + 1), out8(count + 2, 0xDEADBEEFDEADBEEFull);
+        for (unsigned long long r = 0; r < count; ++r) { col4[r] = (uint32_t)r * 2654435761u + 1u; col8[r] = r * 0x9E3779B97F4A7C15ull + 3u; }
+        const unsigned long long n4 = compact_column<uint32_t>(del.data(), col4.data(), count, 0u, out4.data());
+        printf("L %llu", n4);
+        for (uint32_t v : out4) printf(" %x", v);
+        printf("\n");
+        const unsigned long long n8 = compact_column<uint64_t>(del.data(), col8.data(), count, UINT64_MAX, out8.data());
+        printf("K %llu", n8);
+        for (uint64_t v : out8) printf(" %llx", (unsigned long long)v);
+        printf("\n");
     }
     return 0;
 }
 '''
+
+
+def COL4(n):
+    return (np.arange(n, dtype=np.uint64) * np.uint64(2654435761) + np.uint64(1)).astype(np.uint32)
+
+
+def COL8(n):
+    with np.errstate(over="ignore"):
+        return np.arange(n, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15) + np.uint64(3)
 
 SIZES = [0, 1, 31, 32, 33, 64, 100, 256, 1000, 1024, 4096, 5000]
 CHUNKS = [32, 64, 96, 256, 1024]          # (the header's default, 65536 rows, is one case of its own below)
@@ -131,7 +154,11 @@ def results(tmp_path_factory):
         base = np.array(out[i].split()[1:], dtype=np.uint64); i += 1
         ids = np.array([int(x) for x in out[i].split()[1:]], dtype=np.uint64); i += 1
         b = out[i].split()[1:]; i += 1
-        res.append((c, live, first_moved, chunks, base, ids, int(b[0]), np.array([int(x, 16) for x in b[1:]], dtype=np.uint32)))
+        cols = []
+        for dt in (np.uint32, np.uint64):
+            v = out[i].split()[1:]; i += 1
+            cols.append((int(v[0]), np.array([int(x, 16) for x in v[1:]], dtype=dt)))
+        res.append((c, live, first_moved, chunks, base, ids, int(b[0]), np.array([int(x, 16) for x in b[1:]], dtype=np.uint32), cols))
     assert i == len(out)
     return res
 
@@ -190,7 +217,7 @@ def test_both_chunk_forms_occur(results):
 
 
 def test_id_map_word_bases_and_bits_equal_numpy(results):
-    for (n, chunk, offset, kind, dead, allow), live, _, _, base, ids, nsurv, out in results:
+    for (n, chunk, offset, kind, dead, allow), live, _, _, base, ids, nsurv, out, _ in results:
         what = (n, chunk, kind)
         alive = ~dead
         want = np.full(n, ID_NONE, np.uint64)
@@ -204,3 +231,14 @@ def test_id_map_word_bases_and_bits_equal_numpy(results):
         moved[:live] = allow[alive]
         assert np.array_equal(out[:words + 2], np.packbits(moved, bitorder="little").view(np.uint32)), what
         assert out[words + 2] == 0xDEADBEEF, what     # nothing written past out_words
+
+
+def test_columns_move_with_their_rows_and_the_tail_takes_the_default(results):
+    for (n, chunk, _, kind, dead, _), live, *_, cols in results:
+        what = (n, chunk, kind)
+        for (nsurv, out), col, none, canary in ((cols[0], COL4(n), 0, 0xDEADBEEF), (cols[1], COL8(n), ID_NONE, 0xDEADBEEFDEADBEEF)):
+            assert nsurv == live, what
+            want = np.full(n, none, col.dtype)
+            want[:live] = col[~dead]
+            assert np.array_equal(out[:n], want), what
+            assert out.size == n + 2 and (out[n:] == canary).all(), what     # nothing written past the count

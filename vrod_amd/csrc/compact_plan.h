@@ -113,4 +113,16 @@ inline uint64_t compact_bits(const uint32_t* del, const uint32_t* bits, uint64_t
     return d;
 }
 
+// The same for a column of one word per row (labels, tags, values, keys): out[d] = col[s] for the d-th live row s, and
+// the vacated tail out[survivors, count) takes `none`.  `out` holds `count` entries, apart from `col`; nothing beyond
+// them is written.  Returns the survivors.
+template <typename T>
+inline uint64_t compact_column(const uint32_t* del, const T* col, uint64_t count, T none, T* out) {
+    uint64_t d = 0;
+    for (uint64_t s = 0; s < count; ++s)
+        if (!bit_of(del, s)) out[d++] = col[s];
+    std::fill(out + d, out + count, none);
+    return d;
+}
+
 }  // namespace vrod

@@ -119,6 +119,104 @@ struct DevBuf {
     template <typename T> T* as() const { return (T*)p; }
 };
 
+// ------------------------------------------------------------------ device block of a fixed size
+// What is sized by the capacity (the corpus, the norms, the bitmaps, the row columns) or once and for all (the flag words,
+// the key table) lives in one of these: exactly the bytes asked for, and never freed before its replacement exists --
+// alloc() on a block that holds memory lets go of it only once the new memory is there, and whoever needs two blocks
+// replaced together builds them in locals and swaps them in.  Owned as a DevBuf is: freed by going away, not copyable.
+template <typename T = void>
+struct DevMem {
+    T* p = nullptr;
+    DevMem() = default;
+    DevMem(const DevMem&) = delete;
+    DevMem& operator=(const DevMem&) = delete;
+    DevMem(DevMem&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevMem& operator=(DevMem&& o) noexcept {
+        if (this != &o) { release(); p = o.p; o.p = nullptr; }
+        return *this;
+    }
+    ~DevMem() { release(); }
+    hipError_t alloc(size_t bytes) {
+        void* q = nullptr;
+        const hipError_t e = hipMalloc(&q, bytes);
+        if (e != hipSuccess) return e;
+        release();
+        p = (T*)q;
+        return hipSuccess;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; }
+    void swap(DevMem& o) noexcept { std::swap(p, o.p); }
+    template <typename U> U* get() const { return (U*)p; }
+};
+
+// ------------------------------------------------------------------ a per-row word column (labels, tags, values, keys)
+// One word of type T per row of the capacity: a host mirror, which is the truth for the getters, and a device copy, which
+// is what the kernels read.  Neither exists before the first set: until then, and for rows at or beyond the count, every
+// row carries `none` (all bytes 0x00, or all bytes 0xFF), and a handle that never set one allocates nothing for it.
+// Growth and compaction are staged -- everything that can fail -- and committed later by steps that cannot.
+using ColumnBytes = std::vector<unsigned char>;   // a staged compaction's rows, whatever the column's word is
+template <typename T>
+struct RowColumn {
+    std::vector<T> host;       // [capacity] once the column exists
+    DevMem<> dev;              // [capacity] on the device, or empty
+    const T none;
+    const char* const noun;    // "labels": for messages
+    const uint32_t snap_kind;  // its section in a snapshot (snapshot_plan.h)
+    RowColumn(T none_, const char* noun_, uint32_t kind) : none(none_), noun(noun_), snap_kind(kind) {}
+
+    bool exists() const { return dev.p != nullptr; }
+    T* d() const { return dev.get<T>(); }
+    int fill_byte() const { return none == T(0) ? 0 : 0xFF; }
+    T get(uint64_t r) const { return exists() ? host[r] : none; }
+
+    // the first set of the handle: every row carries `none` so far
+    int create(uint64_t capacity) {
+        DevMem<> fresh;
+        HIP_TRY(fresh.alloc(capacity * sizeof(T)));
+        const hipError_t e = hipMemset(fresh.p, fill_byte(), capacity * sizeof(T));
+        if (e != hipSuccess) return fail(VROD_ERR_HIP, "clearing the row %s: %s", noun, hipGetErrorString(e));
+        dev.swap(fresh);
+        host.assign(capacity, none);
+        return VROD_OK;
+    }
+    // rows [r0, r0 + n) take src[0 .. n): the device copy, then the mirror
+    int set(uint64_t r0, const T* src, uint64_t n) {
+        HIP_TRY(hipMemcpy(d() + r0, src, n * sizeof(T), hipMemcpyHostToDevice));
+        std::copy(src, src + n, host.begin() + r0);
+        return VROD_OK;
+    }
+
+    // Growth to `want` rows, staged: `grown` gets a block holding rows [0, count) of the mirror and `none` above them,
+    // filled on `s` (the caller drains it).  Nothing of the column changes; a column that does not exist stages nothing.
+    hipError_t stage_grow(uint64_t count, uint64_t want, hipStream_t s, DevMem<>& grown) const {
+        if (!exists()) return hipSuccess;
+        hipError_t e = grown.alloc(want * sizeof(T));
+        if (e == hipSuccess) e = hipMemsetAsync(grown.p, fill_byte(), want * sizeof(T), s);
+        if (e == hipSuccess) e = hipMemcpyAsync(grown.p, host.data(), count * sizeof(T), hipMemcpyHostToDevice, s);
+        return e;
+    }
+    // ... and committed: the staged block comes in, `grown` leaves with the old one
+    void commit_grow(uint64_t want, DevMem<>& grown) {
+        if (!exists()) return;
+        dev.swap(grown);
+        host.resize(want, none);
+    }
+
+    // Compaction under the tombstones `del`, staged: rows [0, count) as they will stand (compact_plan.h compact_column);
+    // then uploaded on `s`, then taken over by the mirror.  A column that does not exist takes part in none of the three.
+    void stage_compact(const uint32_t* del, uint64_t count, ColumnBytes& moved) const {
+        if (!exists()) return;
+        moved.resize(count * sizeof(T));
+        compact_column(del, host.data(), count, none, (T*)moved.data());
+    }
+    hipError_t upload_compact(const ColumnBytes& moved, hipStream_t s) {
+        return exists() ? hipMemcpyAsync(dev.p, moved.data(), moved.size(), hipMemcpyHostToDevice, s) : hipSuccess;
+    }
+    void commit_compact(const ColumnBytes& moved) {
+        if (exists()) memcpy(host.data(), moved.data(), moved.size());
+    }
+};
+
 // a search slot's block of device words: 64 scalars, then one region of sibling-pacing counters and one of work-stealing
 // claim bits per scan launch of the search (8 of each; a search with more launches reuses them behind a memset)
 constexpr uint32_t kPaceRegions = 8, kPaceWords = 192, kClaimWords = (uint32_t)kMfmaClaimWords;
@@ -141,7 +239,7 @@ struct Pending {
     // re-score, certificate, read-back) can run beside the head -- and, on the stream path, the
     // scan -- of search s+1.  Only the corpus (read-only during a search) is shared.
     hipStream_t stream = nullptr;
-    uint32_t* flags = nullptr;     // [0] bad-value flag, [1] max query norm^2 bits, [2] max err bits, [64..] pacing counters, then claim bits (kSlotFlagBytes)
+    DevMem<uint32_t> flags;        // [0] bad-value flag, [1] max query norm^2 bits, [2] max err bits, [64..] pacing counters, then claim bits (kSlotFlagBytes)
     DevBuf q_raw, q_lp, scores, keys_a, keys_b, lists, small, hist, cand_rows, cand_fast, cand_canon;
     DevBuf q_f32;                  // prepared queries (the exact path re-reads them)
     DevBuf dump;                   // MFMA path: spill regions of the 4-wave kernel's hit logs (scratch, mfma_dump_bytes)
@@ -195,9 +293,9 @@ struct vrod_index {
     int dtype = VROD_DTYPE_F32, metric = VROD_METRIC_COSINE;
     size_t esize = 4;
     uint64_t count = 0, capacity = 0, id_offset = 0;
-    void* corpus = nullptr;     // [capacity][ld]
-    float* xnorm2 = nullptr;    // [capacity]
-    uint32_t* max_xn2_bits = nullptr;  // device scalar: max squared row norm (float bits)
+    DevMem<> corpus;            // [capacity][ld]
+    DevMem<float> xnorm2;       // [capacity]
+    uint32_t* max_xn2_bits = nullptr;  // device scalar: max squared row norm (float bits), a word of `flags`
     hipStream_t stream = nullptr;
     int path = VROD_PATH_AUTO;
     int profiling = 0;
@@ -210,7 +308,7 @@ struct vrod_index {
     bool split_enabled = false;
     bool split_forced = false;     // VROD_F32_SPLIT=1: no memory-margin check, never switched off by the failure count
     uint32_t split_bad = 0;        // split searches that sent more than 1/8 of their queries to the exact path
-    void* planes = nullptr;        // [planes_cap][2 * ldp] bf16, [hi_j | lo_j] per 64-element K-tile j
+    DevMem<> planes;               // [planes_cap][2 * ldp] bf16, [hi_j | lo_j] per 64-element K-tile j
     uint64_t planes_cap = 0, planes_rows = 0;
     uint32_t ldp = 0;              // dim rounded up to 64 (bf16 128-B lines)
 
@@ -218,7 +316,7 @@ struct vrod_index {
     // The host mirror is the truth; the device copy is allocated at the first delete and the kernels see it only
     // while some row is deleted (row_mask()), so a handle that never deleted runs exactly the launches it ran before.
     std::vector<uint32_t> del_bits;    // [capacity / 32]
-    uint32_t* del_dev = nullptr;       // [capacity / 32] on the device, or null
+    DevMem<uint32_t> del_dev;          // [capacity / 32] on the device, or empty
     uint64_t n_deleted = 0;
     uint64_t mask_gen = 0;             // bumped by every change of the row mask's contents (delete, set_filter)
     struct SampleWindow { uint64_t S = 0, N = 0, gen = 0, first = 0; bool valid = false; } sample_win;
@@ -228,38 +326,33 @@ struct vrod_index {
     // filter's n_rows (rows added later included) are not allowed: the effective mask grows with ones.
     bool filter_on = false;
     std::vector<uint32_t> allow_bits, eff_bits;   // [capacity / 32] while filter_on
-    uint32_t* eff_dev = nullptr;                  // [capacity / 32] on the device while filter_on
+    DevMem<uint32_t> eff_dev;                     // [capacity / 32] on the device while filter_on
     uint64_t n_eligible = 0;                      // rows < count that are live and allowed
     // gather path: ascending local indices of the eligible rows, built for mask generation list_gen
     DevBuf list_dev;
     uint64_t list_gen = UINT64_MAX, list_n = 0;
 
-    // row labels (vrod_index_set_labels): one word per row of the capacity, 0 until set and for rows at or beyond the
-    // count.  Host mirror and device copy are both allocated at the first set_labels: a handle that never set a label
-    // has neither, and a labelled search on it treats every row as label 0.  No other search reads them.
-    std::vector<uint32_t> lab_bits;    // [capacity] once labels exist
-    uint32_t* lab_dev = nullptr;       // [capacity] on the device, or null
+    // The row columns (RowColumn above; for_each_column below the struct is where a new one is registered).
+    // row labels (vrod_index_set_labels): a labelled search on a handle that never set one treats every row as label 0.
+    // No other search reads them.
+    RowColumn<uint32_t> labels{0u, "labels", SNAP_LABELS};
     // A labelled search's dense groups run the ordinary search flow over ONE label's rows: while mask_ovr is set it
     // stands for row_mask() and elig_ovr for eligible().  Null outside vrod_search_labeled, so no other call path
     // changes what it launches.  The override has no host mirror and no generation: what is cached per mask_gen (sample
     // window, gather list, graphs) is bypassed under it, never refreshed.
     const uint32_t* mask_ovr = nullptr;
     uint64_t elig_ovr = 0;
-    // row tags (vrod_index_set_tags): one 64-bit mask per row of the capacity, kept exactly as the labels are -- host
-    // mirror and device copy allocated at the first set_tags, 0 for rows at or beyond the count.  Only
-    // vrod_search_tagged reads them; a handle that never set one treats every row as 0.
-    std::vector<uint64_t> tag_bits;    // [capacity] once tags exist
-    uint64_t* tag_dev = nullptr;       // [capacity] on the device, or null
-    // row values (vrod_index_set_values): one signed 64-bit value per row of the capacity, kept exactly as the tags are.
-    // Only vrod_search_where reads them; a handle that never set one treats every row as 0.
-    std::vector<int64_t> val_bits;     // [capacity] once values exist
-    int64_t* val_dev = nullptr;        // [capacity] on the device, or null
-    // row keys (vrod_index_set_keys): one caller-chosen 64-bit key per row of the capacity, VROD_ID_NONE until set, kept
-    // as the values are, and unique among the live rows.  The device table (keys_plan.h, kernels_keys.hip) finds a key's
-    // row; it exists from the first set_keys on.  No search reads either: a handle that never set a key has neither.
-    std::vector<uint64_t> key_bits;    // [capacity] once keys exist
-    uint64_t* key_dev = nullptr;       // [capacity] on the device, or null
-    KeyTable ktab{};                   // the table's two device arrays
+    // row tags (vrod_index_set_tags): one 64-bit mask per row.  Only vrod_search_tagged and vrod_search_where read them.
+    RowColumn<uint64_t> tags{0ull, "tags", SNAP_TAGS};
+    // row values (vrod_index_set_values): one signed 64-bit value per row.  Only vrod_search_where reads them.
+    RowColumn<int64_t> values{0ll, "values", SNAP_VALUES};
+    // row keys (vrod_index_set_keys): one caller-chosen 64-bit key per row, VROD_ID_NONE until set, unique among the live
+    // rows.  The device table (keys_plan.h, kernels_keys.hip) finds a key's row; it exists from the first set_keys on.
+    // No search reads either.
+    RowColumn<uint64_t> keys{kKeyNone, "keys", SNAP_KEYS};
+    DevMem<uint64_t> ktab_keys;        // the table's two device arrays ...
+    DevMem<uint32_t> ktab_rows;
+    KeyTable ktab{};                   // ... as the kernels take them: a view, filled by keys_table_clear
     uint64_t key_occupied = 0;         // slots in use, stale ones included: at most ktab.slots / 2
     uint64_t keyed_live = 0;           // live rows whose key is not VROD_ID_NONE
     uint64_t key_rebuilds = 0, key_max_probe = 0;   // vrod_index_key_stats
@@ -279,7 +372,7 @@ struct vrod_index {
     // dense stage's masks [<= 8][capacity / 32]
     DevBuf grp_small, grp_mask;
     // multi-vector search (vrod_search_multivec).  The document index: doc_rank[row] = the rank of the row's label among
-    // the handle's distinct labels, ascending (doc_labels [n_docs]), built on the host from lab_bits at the first search
+    // the handle's distinct labels, ascending (doc_labels [n_docs]), built on the host from labels.host at the first search
     // that needs it and kept until set_labels, add or compact change what it was built from (update and delete do not);
     // a handle without labels is one document, label 0, and has no rank array.  Then the workspaces: the prepared vectors
     // of the whole call, the de-duplication's entry labels / tables / candidate labels, the per-query words, the dense
@@ -316,7 +409,7 @@ struct vrod_index {
     // range searches (vrod_range_search): the pool of qualifying rows and its sort partner, and the small block
     // [total (u64) | the caller's thresholds [nq] | per-query counters [nq]]
     DevBuf range_pool, range_pool_b, range_small;
-    uint32_t* flags = nullptr;  // [0] bad-value flag of the insert path; [8] max squared row norm
+    DevMem<uint32_t> flags;     // [0] bad-value flag of the insert path; [8] max squared row norm
     Pending slot[2];
     // start / stop of the last filtered scan launch of the four most recent searches (Timer::arm_tail): the next search's
     // sample launch may overlap it, and measures by how much when it completes
@@ -367,7 +460,7 @@ struct vrod_index {
     uint64_t eligible() const { return mask_ovr ? elig_ovr : filter_on ? n_eligible : live(); }
     // what the kernels get as their row mask: the effective mask while a filter is set, else the deleted rows, and null
     // while nothing is deleted
-    const uint32_t* row_mask() const { return mask_ovr ? mask_ovr : filter_on ? eff_dev : n_deleted ? del_dev : nullptr; }
+    const uint32_t* row_mask() const { return mask_ovr ? mask_ovr : filter_on ? eff_dev.p : n_deleted ? del_dev.p : nullptr; }
     // its host mirror (meaningful while row_mask() is non-null)
     const std::vector<uint32_t>& mask_bits() const { return filter_on ? eff_bits : del_bits; }
 };
@@ -395,148 +488,80 @@ static bool valid_metric(int metric) {
     return metric == VROD_METRIC_COSINE || metric == VROD_METRIC_L2 || metric == VROD_METRIC_IP;
 }
 
+// f(column, i) for every row column of the handle, i = 0 .. kRowColumns - 1, in the order of their snapshot sections.
+// THE place to register a new column: growth, compaction, save and load reach the columns through here.
+constexpr int kRowColumns = 4;
+template <typename F>
+static void for_each_column(vrod_index* idx, F&& f) {
+    f(idx->labels, 0);
+    f(idx->tags, 1);
+    f(idx->values, 2);
+    f(idx->keys, 3);
+}
+
+static void drop_planes(vrod_index* idx) {   // (rebuilt lazily)
+    idx->planes.release();
+    idx->planes_cap = idx->planes_rows = 0;
+}
+
+// Two phases.  The first builds every new block in a local and fills it on the handle's stream; whatever fails there
+// returns with the handle untouched, and the locals give their memory back.  The second swaps the blocks in and cannot
+// fail; the locals then hold the old blocks, which go when they do -- behind the drain, and after everything new exists.
 static int index_reserve(vrod_index* idx, uint64_t n_rows) {
     const uint64_t want = round_up(std::max<uint64_t>(n_rows, 1), kRowTile);
     if (want <= idx->capacity) return VROD_OK;
     if (want > 0xFFFFFF00ull) return fail(VROD_ERR_UNSUPPORTED, "more than 2^32-256 rows per shard");
-    void* nc = nullptr;
-    float* nx = nullptr;
-    HIP_TRY(hipMalloc(&nc, want * idx->row_bytes()));
-    hipError_t e = hipMalloc((void**)&nx, want * sizeof(float));
-    if (e != hipSuccess) { (void)hipFree(nc); return fail(VROD_ERR_OUT_OF_MEMORY, "hipMalloc norms: %s", hipGetErrorString(e)); }
-    const size_t used = idx->count * idx->row_bytes();
-    hipError_t ce = hipSuccess;
-    if (idx->count) {
-        ce = hipMemcpyAsync(nc, idx->corpus, used, hipMemcpyDeviceToDevice, idx->stream);
-        if (ce == hipSuccess) ce = hipMemcpyAsync(nx, idx->xnorm2, idx->count * sizeof(float), hipMemcpyDeviceToDevice, idx->stream);
-    }
-    if (ce == hipSuccess) ce = hipMemsetAsync((char*)nc + used, 0, want * idx->row_bytes() - used, idx->stream);
-    if (ce == hipSuccess) ce = hipMemsetAsync(nx + idx->count, 0, (want - idx->count) * sizeof(float), idx->stream);
-    if (ce == hipSuccess) ce = hipStreamSynchronize(idx->stream);
-    if (ce != hipSuccess) {   // the old corpus stays in place; the new blocks are given back
-        (void)hipStreamSynchronize(idx->stream);
-        (void)hipFree(nc);
-        (void)hipFree(nx);
-        return fail(VROD_ERR_HIP, "growing the corpus failed: %s", hipGetErrorString(ce));
-    }
-    uint32_t* nd = nullptr;   // the deleted-row bitmap follows the capacity (once it exists)
-    if (idx->del_dev) {
-        hipError_t de = hipMalloc((void**)&nd, want / 32 * 4);
-        if (de == hipSuccess) de = hipMemsetAsync(nd, 0, want / 32 * 4, idx->stream);
-        if (de == hipSuccess) de = hipMemcpyAsync(nd, idx->del_bits.data(), idx->del_bits.size() * 4, hipMemcpyHostToDevice, idx->stream);
-        if (de == hipSuccess) de = hipStreamSynchronize(idx->stream);
-        if (de != hipSuccess) {
-            (void)hipStreamSynchronize(idx->stream);
-            if (nd) (void)hipFree(nd);
-            (void)hipFree(nc);
-            (void)hipFree(nx);
-            return fail(VROD_ERR_HIP, "growing the deleted-row bitmap failed: %s", hipGetErrorString(de));
-        }
-    }
-    uint32_t* ne = nullptr;   // the effective mask of a filter: the new rows are not allowed (ones)
+    hipStream_t s = idx->stream;
+    const uint64_t count = idx->count;
+    const size_t rb = idx->row_bytes(), used = count * rb, words = want / 32;
+    DevMem<> nc, ncol[kRowColumns];
+    DevMem<float> nx;
+    DevMem<uint32_t> nd, ne;
     std::vector<uint32_t> eff_grown;
-    if (idx->filter_on) {
+    HIP_TRY(nc.alloc(want * rb));
+    hipError_t e = nx.alloc(want * sizeof(float));
+    if (e != hipSuccess) return fail(VROD_ERR_OUT_OF_MEMORY, "hipMalloc norms: %s", hipGetErrorString(e));
+    const char* what = "corpus";   // zero rows and zero norms past the count
+    if (count) {
+        e = hipMemcpyAsync(nc.p, idx->corpus.p, used, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(nx.p, idx->xnorm2.p, count * sizeof(float), hipMemcpyDeviceToDevice, s);
+    }
+    if (e == hipSuccess) e = hipMemsetAsync(nc.get<char>() + used, 0, want * rb - used, s);
+    if (e == hipSuccess) e = hipMemsetAsync(nx.p + count, 0, (want - count) * sizeof(float), s);
+    if (e == hipSuccess && idx->del_dev.p) {   // the deleted-row bitmap follows the capacity (once it exists)
+        what = "deleted-row bitmap";
+        e = nd.alloc(words * 4);
+        if (e == hipSuccess) e = hipMemsetAsync(nd.p, 0, words * 4, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(nd.p, idx->del_bits.data(), idx->del_bits.size() * 4, hipMemcpyHostToDevice, s);
+    }
+    if (e == hipSuccess && idx->filter_on) {   // the effective mask of a filter: the new rows are not allowed (ones)
+        what = "filter's row mask";
         eff_grown = idx->eff_bits;
-        eff_grown.resize(want / 32, ~0u);
-        hipError_t fe = hipMalloc((void**)&ne, want / 32 * 4);
-        if (fe == hipSuccess) fe = hipMemcpyAsync(ne, eff_grown.data(), eff_grown.size() * 4, hipMemcpyHostToDevice, idx->stream);
-        if (fe == hipSuccess) fe = hipStreamSynchronize(idx->stream);
-        if (fe != hipSuccess) {
-            (void)hipStreamSynchronize(idx->stream);
-            if (ne) (void)hipFree(ne);
-            if (nd) (void)hipFree(nd);
-            (void)hipFree(nc);
-            (void)hipFree(nx);
-            return fail(VROD_ERR_HIP, "growing the filter's row mask failed: %s", hipGetErrorString(fe));
-        }
+        eff_grown.resize(words, ~0u);
+        e = ne.alloc(words * 4);
+        if (e == hipSuccess) e = hipMemcpyAsync(ne.p, eff_grown.data(), words * 4, hipMemcpyHostToDevice, s);
     }
-    uint32_t* nl = nullptr;   // the labels follow the capacity (once they exist): the new rows carry 0
-    if (idx->lab_dev) {
-        hipError_t le = hipMalloc((void**)&nl, want * 4);
-        if (le == hipSuccess) le = hipMemsetAsync(nl, 0, want * 4, idx->stream);
-        if (le == hipSuccess) le = hipMemcpyAsync(nl, idx->lab_bits.data(), idx->count * 4, hipMemcpyHostToDevice, idx->stream);
-        if (le == hipSuccess) le = hipStreamSynchronize(idx->stream);
-        if (le != hipSuccess) {
-            (void)hipStreamSynchronize(idx->stream);
-            if (nl) (void)hipFree(nl);
-            if (ne) (void)hipFree(ne);
-            if (nd) (void)hipFree(nd);
-            (void)hipFree(nc);
-            (void)hipFree(nx);
-            return fail(VROD_ERR_HIP, "growing the row labels failed: %s", hipGetErrorString(le));
-        }
+    for_each_column(idx, [&](auto& c, int i) {   // the columns that exist: the new rows carry their default
+        if (e == hipSuccess) { what = c.noun; e = c.stage_grow(count, want, s, ncol[i]); }
+    });
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(s);   // (nothing is still aimed at a block that goes)
+        return fail(VROD_ERR_HIP, "growing the %s failed: %s", what, hipGetErrorString(e));
     }
-    uint64_t* nt = nullptr;   // so do the tags
-    if (idx->tag_dev) {
-        hipError_t te = hipMalloc((void**)&nt, want * 8);
-        if (te == hipSuccess) te = hipMemsetAsync(nt, 0, want * 8, idx->stream);
-        if (te == hipSuccess) te = hipMemcpyAsync(nt, idx->tag_bits.data(), idx->count * 8, hipMemcpyHostToDevice, idx->stream);
-        if (te == hipSuccess) te = hipStreamSynchronize(idx->stream);
-        if (te != hipSuccess) {
-            (void)hipStreamSynchronize(idx->stream);
-            if (nt) (void)hipFree(nt);
-            if (nl) (void)hipFree(nl);
-            if (ne) (void)hipFree(ne);
-            if (nd) (void)hipFree(nd);
-            (void)hipFree(nc);
-            (void)hipFree(nx);
-            return fail(VROD_ERR_HIP, "growing the row tags failed: %s", hipGetErrorString(te));
-        }
-    }
-    int64_t* nv = nullptr;   // and the values
-    if (idx->val_dev) {
-        hipError_t ve = hipMalloc((void**)&nv, want * 8);
-        if (ve == hipSuccess) ve = hipMemsetAsync(nv, 0, want * 8, idx->stream);
-        if (ve == hipSuccess) ve = hipMemcpyAsync(nv, idx->val_bits.data(), idx->count * 8, hipMemcpyHostToDevice, idx->stream);
-        if (ve == hipSuccess) ve = hipStreamSynchronize(idx->stream);
-        if (ve != hipSuccess) {
-            (void)hipStreamSynchronize(idx->stream);
-            if (nv) (void)hipFree(nv);
-            if (nt) (void)hipFree(nt);
-            if (nl) (void)hipFree(nl);
-            if (ne) (void)hipFree(ne);
-            if (nd) (void)hipFree(nd);
-            (void)hipFree(nc);
-            (void)hipFree(nx);
-            return fail(VROD_ERR_HIP, "growing the row values failed: %s", hipGetErrorString(ve));
-        }
-    }
-    uint64_t* nk = nullptr;   // and the keys: the new rows carry none (every byte 0xFF)
-    if (idx->key_dev) {
-        hipError_t ke = hipMalloc((void**)&nk, want * 8);
-        if (ke == hipSuccess) ke = hipMemsetAsync(nk, 0xFF, want * 8, idx->stream);
-        if (ke == hipSuccess) ke = hipMemcpyAsync(nk, idx->key_bits.data(), idx->count * 8, hipMemcpyHostToDevice, idx->stream);
-        if (ke == hipSuccess) ke = hipStreamSynchronize(idx->stream);
-        if (ke != hipSuccess) {
-            (void)hipStreamSynchronize(idx->stream);
-            if (nk) (void)hipFree(nk);
-            if (nv) (void)hipFree(nv);
-            if (nt) (void)hipFree(nt);
-            if (nl) (void)hipFree(nl);
-            if (ne) (void)hipFree(ne);
-            if (nd) (void)hipFree(nd);
-            (void)hipFree(nc);
-            (void)hipFree(nx);
-            return fail(VROD_ERR_HIP, "growing the row keys failed: %s", hipGetErrorString(ke));
-        }
-    }
-    if (idx->corpus) (void)hipFree(idx->corpus);
-    if (idx->xnorm2) (void)hipFree(idx->xnorm2);
-    if (idx->key_dev) { (void)hipFree(idx->key_dev); idx->key_dev = nk; idx->key_bits.resize(want, kKeyNone); }
-    if (idx->planes) { (void)hipFree(idx->planes); idx->planes = nullptr; idx->planes_cap = idx->planes_rows = 0; }   // rebuilt lazily
-    if (idx->val_dev) { (void)hipFree(idx->val_dev); idx->val_dev = nv; idx->val_bits.resize(want, 0ll); }
-    if (idx->tag_dev) { (void)hipFree(idx->tag_dev); idx->tag_dev = nt; idx->tag_bits.resize(want, 0ull); }
-    if (idx->lab_dev) { (void)hipFree(idx->lab_dev); idx->lab_dev = nl; idx->lab_bits.resize(want, 0u); }
-    if (idx->del_dev) { (void)hipFree(idx->del_dev); idx->del_dev = nd; }
-    idx->del_bits.resize(want / 32, 0u);
+
+    // ---- from here on nothing fails
+    idx->corpus.swap(nc);
+    idx->xnorm2.swap(nx);
+    for_each_column(idx, [&](auto& c, int i) { c.commit_grow(want, ncol[i]); });
+    drop_planes(idx);
+    if (idx->del_dev.p) idx->del_dev.swap(nd);
+    idx->del_bits.resize(words, 0u);
     if (idx->filter_on) {
-        if (idx->eff_dev) (void)hipFree(idx->eff_dev);
-        idx->eff_dev = ne;
+        idx->eff_dev.swap(ne);
         idx->eff_bits.swap(eff_grown);
-        idx->allow_bits.resize(want / 32, 0u);
+        idx->allow_bits.resize(words, 0u);
     }
-    idx->corpus = nc;
-    idx->xnorm2 = nx;
     idx->capacity = want;
     return VROD_OK;
 }
@@ -544,22 +569,22 @@ static int index_reserve(vrod_index* idx, uint64_t n_rows) {
 // Prepare `n` raw fp32 rows already in device memory and append them.
 static int append_prepared(vrod_index* idx, const float* d_raw, uint64_t n) {
     VROD_TRY(idx->nrm_ws.ensure(n * sizeof(double)));
-    char* dst = (char*)idx->corpus + idx->count * idx->row_bytes();
+    char* dst = (char*)idx->corpus.p + idx->count * idx->row_bytes();
     launch_prepare_rows(d_raw, n, idx->dim, idx->ld, prep_form(idx->metric), idx->dtype, idx->nrm_ws.as<double>(),
-                        &idx->flags[0], idx->dtype == VROD_DTYPE_F32 ? (float*)dst : nullptr,
+                        &idx->flags.p[0], idx->dtype == VROD_DTYPE_F32 ? (float*)dst : nullptr,
                         idx->dtype == VROD_DTYPE_BF16 ? dst : nullptr, idx->stream);
-    launch_row_fastnorm(dst, idx->dtype, n, idx->ld, idx->xnorm2 + idx->count, idx->max_xn2_bits, idx->stream);
+    launch_row_fastnorm(dst, idx->dtype, n, idx->ld, idx->xnorm2.p + idx->count, idx->max_xn2_bits, idx->stream);
     HIP_TRY(hipGetLastError());
     return VROD_OK;
 }
 
-// Word `w` of idx->flags as the launches on `s` so far leave it; a raised word is cleared for the next call.
+// Word `w` of idx->flags.p as the launches on `s` so far leave it; a raised word is cleared for the next call.
 static int take_flag(vrod_index* idx, uint32_t w, hipStream_t s, uint32_t* bad) {
     *bad = 0;
-    HIP_TRY(hipMemcpyAsync(bad, &idx->flags[w], 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(bad, &idx->flags.p[w], 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (*bad) {
-        HIP_TRY(hipMemsetAsync(&idx->flags[w], 0, 4, s));
+        HIP_TRY(hipMemsetAsync(&idx->flags.p[w], 0, 4, s));
         HIP_TRY(hipStreamSynchronize(s));
     }
     return VROD_OK;
@@ -601,7 +626,7 @@ static bool ingest_force_stage() {
 }
 
 // Rows [0, m) of `src` become prepared rows [m][ld] at `out` (on idx's device, which is current), on idx->stream; NaN /
-// Inf raise idx->flags[0] as the host forms' prepare raises it.
+// Inf raise idx->flags.p[0] as the host forms' prepare raises it.
 static int ingest_prepare(vrod_index* idx, const IngestSrc& src, uint64_t m, void* out) {
     const int form = prep_form(idx->metric);
     if (src.device == idx->device && !ingest_force_stage()) {
@@ -611,7 +636,7 @@ static int ingest_prepare(vrod_index* idx, const IngestSrc& src, uint64_t m, voi
             HIP_TRY(hipMemcpyAsync(idx->ingest_pick.p, src.pick, m * 8, hipMemcpyHostToDevice, idx->stream));
             d_pick = idx->ingest_pick.as<uint64_t>();
         }
-        launch_ingest_rows(src.p, src.dtype, src.stride, d_pick, m, idx->dim, idx->ld, form, idx->dtype, &idx->flags[0], out, idx->stream);
+        launch_ingest_rows(src.p, src.dtype, src.stride, d_pick, m, idx->dim, idx->ld, form, idx->dtype, &idx->flags.p[0], out, idx->stream);
         HIP_TRY(hipGetLastError());
         return VROD_OK;
     }
@@ -638,16 +663,16 @@ static int ingest_prepare(vrod_index* idx, const IngestSrc& src, uint64_t m, voi
     }
     HIP_TRY(hipSetDevice(idx->device));
     VROD_TRY(rc);
-    launch_ingest_rows(idx->raw_stage.p, src.dtype, idx->dim, nullptr, m, idx->dim, idx->ld, form, idx->dtype, &idx->flags[0], out, idx->stream);
+    launch_ingest_rows(idx->raw_stage.p, src.dtype, idx->dim, nullptr, m, idx->dim, idx->ld, form, idx->dtype, &idx->flags.p[0], out, idx->stream);
     HIP_TRY(hipGetLastError());
     return VROD_OK;
 }
 
 // append_prepared for a device-resident source
 static int append_ingested(vrod_index* idx, const IngestSrc& src, uint64_t n) {
-    char* dst = (char*)idx->corpus + idx->count * idx->row_bytes();
+    char* dst = (char*)idx->corpus.p + idx->count * idx->row_bytes();
     VROD_TRY(ingest_prepare(idx, src, n, dst));
-    launch_row_fastnorm(dst, idx->dtype, n, idx->ld, idx->xnorm2 + idx->count, idx->max_xn2_bits, idx->stream);
+    launch_row_fastnorm(dst, idx->dtype, n, idx->ld, idx->xnorm2.p + idx->count, idx->max_xn2_bits, idx->stream);
     HIP_TRY(hipGetLastError());
     return VROD_OK;
 }
@@ -667,7 +692,7 @@ static int index_add(vrod_index* idx, const float* rows, uint64_t n, bool synthe
     // the max squared row norm is accumulated (atomicMax) by the very launches whose rows may be
     // rejected: keep the value it had, so that a rejected add cannot widen (or, with an Inf row,
     // void) the certificate bound of every later search
-    HIP_TRY(hipMemcpyAsync(&idx->flags[9], idx->max_xn2_bits, 4, hipMemcpyDeviceToDevice, idx->stream));
+    HIP_TRY(hipMemcpyAsync(&idx->flags.p[9], idx->max_xn2_bits, 4, hipMemcpyDeviceToDevice, idx->stream));
     const uint64_t chunk = stage_chunk_rows(idx, n);
     if (!dev) VROD_TRY(idx->raw_stage.ensure(chunk * idx->dim * sizeof(float)));
     for (uint64_t done = 0; done < n; done += chunk) {
@@ -690,9 +715,9 @@ static int index_add(vrod_index* idx, const float* rows, uint64_t n, bool synthe
     int rc = check_bad_flag(idx, "rows");
     if (rc != VROD_OK) {  // roll back: re-zero the rows just written
         idx->count = count0;
-        (void)hipMemsetAsync((char*)idx->corpus + count0 * idx->row_bytes(), 0, n * idx->row_bytes(), idx->stream);
-        (void)hipMemsetAsync(idx->xnorm2 + count0, 0, n * sizeof(float), idx->stream);
-        (void)hipMemcpyAsync(idx->max_xn2_bits, &idx->flags[9], 4, hipMemcpyDeviceToDevice, idx->stream);
+        (void)hipMemsetAsync((char*)idx->corpus.p + count0 * idx->row_bytes(), 0, n * idx->row_bytes(), idx->stream);
+        (void)hipMemsetAsync(idx->xnorm2.p + count0, 0, n * sizeof(float), idx->stream);
+        (void)hipMemcpyAsync(idx->max_xn2_bits, &idx->flags.p[9], 4, hipMemcpyDeviceToDevice, idx->stream);
         (void)hipStreamSynchronize(idx->stream);
         return rc;
     }
@@ -723,15 +748,15 @@ static int index_update_pass(vrod_index* idx, const uint32_t* dst, const float* 
         } else {
             HIP_TRY(hipMemcpyAsync(idx->raw_stage.p, rows + done * idx->dim, m * idx->dim * sizeof(float), hipMemcpyHostToDevice, idx->stream));
             launch_prepare_rows(idx->raw_stage.as<float>(), m, idx->dim, idx->ld, prep_form(idx->metric), idx->dtype, idx->nrm_ws.as<double>(),
-                                &idx->flags[0], idx->dtype == VROD_DTYPE_F32 ? idx->upd_stage.as<float>() : nullptr,
+                                &idx->flags.p[0], idx->dtype == VROD_DTYPE_F32 ? idx->upd_stage.as<float>() : nullptr,
                                 idx->dtype == VROD_DTYPE_BF16 ? idx->upd_stage.p : nullptr, idx->stream);
             HIP_TRY(hipGetLastError());
         }
         if (!dst) continue;
         if (check_first) VROD_TRY(check_bad_flag(idx, "rows"));
         HIP_TRY(hipMemcpyAsync(idx->upd_dst.p, dst + done, m * 4, hipMemcpyHostToDevice, idx->stream));
-        launch_scatter_rows(idx->upd_stage.p, idx->upd_dst.as<uint32_t>(), m, idx->dtype, idx->ld, idx->corpus, idx->xnorm2, idx->max_xn2_bits,
-                            idx->dtype == VROD_DTYPE_F32 ? idx->planes : nullptr, idx->planes_rows, idx->ldp, idx->stream);
+        launch_scatter_rows(idx->upd_stage.p, idx->upd_dst.as<uint32_t>(), m, idx->dtype, idx->ld, idx->corpus.p, idx->xnorm2.p, idx->max_xn2_bits,
+                            idx->dtype == VROD_DTYPE_F32 ? idx->planes.p : nullptr, idx->planes_rows, idx->ldp, idx->stream);
         HIP_TRY(hipGetLastError());
     }
     if (!dst) return check_bad_flag(idx, "rows");
@@ -749,8 +774,8 @@ static int index_update(vrod_index* idx, const std::vector<uint32_t>& dst, const
 static void mask_changed(vrod_index* idx);
 
 // ------------------------------------------------------------------ the key table (keys_plan.h, kernels_keys.hip)
-constexpr uint32_t kKeyCtrWord = 64;   // idx->flags[64 .. 70): the table's device counters (KeyCounters)
-static KeyCounters* key_ctr(const vrod_index* idx) { return (KeyCounters*)(idx->flags + kKeyCtrWord); }
+constexpr uint32_t kKeyCtrWord = 64;   // idx->flags.p[64 .. 70): the table's device counters (KeyCounters)
+static KeyCounters* key_ctr(const vrod_index* idx) { return (KeyCounters*)(idx->flags.p + kKeyCtrWord); }
 
 // What the launches on the handle's stream left in the counters (the stream is drained).  `what` names the caller.
 static int keys_take_counters(vrod_index* idx, const char* what, KeyCounters& c) {
@@ -768,14 +793,14 @@ static int keys_table_clear(vrod_index* idx, uint64_t n) {
     VROD_TRY(set_device(idx));
     const uint64_t slots = key_table_slots(n, idx->ktab.slots);
     if (slots != idx->ktab.slots) {
-        uint64_t* nk = nullptr;
-        uint32_t* nr = nullptr;
-        HIP_TRY(hipMalloc((void**)&nk, slots * 8));
-        const hipError_t e = hipMalloc((void**)&nr, slots * 4);
-        if (e != hipSuccess) { (void)hipFree(nk); return fail(VROD_ERR_OUT_OF_MEMORY, "hipMalloc of the key table: %s", hipGetErrorString(e)); }
-        if (idx->ktab.slot_key) (void)hipFree(idx->ktab.slot_key);
-        if (idx->ktab.slot_row) (void)hipFree(idx->ktab.slot_row);
-        idx->ktab.slot_key = nk; idx->ktab.slot_row = nr; idx->ktab.slots = slots;
+        DevMem<uint64_t> nk;
+        DevMem<uint32_t> nr;
+        HIP_TRY(nk.alloc(slots * 8));
+        const hipError_t e = nr.alloc(slots * 4);
+        if (e != hipSuccess) return fail(VROD_ERR_OUT_OF_MEMORY, "hipMalloc of the key table: %s", hipGetErrorString(e));
+        idx->ktab_keys.swap(nk);   // (the old arrays go with the locals)
+        idx->ktab_rows.swap(nr);
+        idx->ktab.slot_key = idx->ktab_keys.p; idx->ktab.slot_row = idx->ktab_rows.p; idx->ktab.slots = slots;
     }
     HIP_TRY(hipMemsetAsync(idx->ktab.slot_key, 0xFF, slots * 8, idx->stream));
     HIP_TRY(hipMemsetAsync(idx->ktab.slot_row, 0, slots * 4, idx->stream));
@@ -790,7 +815,7 @@ static int keys_rebuild(vrod_index* idx, uint64_t n, bool counted, const char* w
     VROD_TRY(keys_table_clear(idx, n));
     hipStream_t s = idx->stream;
     HIP_TRY(hipMemsetAsync(key_ctr(idx), 0, sizeof(KeyCounters), s));
-    launch_keys_insert(idx->ktab, idx->key_dev, idx->del_dev, 0, idx->count, true, key_ctr(idx), s);
+    launch_keys_insert(idx->ktab, idx->keys.d(), idx->del_dev.p, 0, idx->count, true, key_ctr(idx), s);
     HIP_TRY(hipGetLastError());
     KeyCounters c{};
     VROD_TRY(keys_take_counters(idx, what, c));
@@ -806,7 +831,7 @@ static int keys_rebuild(vrod_index* idx, uint64_t n, bool counted, const char* w
 static int keys_insert(vrod_index* idx, uint64_t r0, uint64_t n, const char* what) {
     hipStream_t s = idx->stream;
     HIP_TRY(hipMemsetAsync(key_ctr(idx), 0, sizeof(KeyCounters), s));
-    launch_keys_insert(idx->ktab, idx->key_dev, idx->del_dev, r0, n, false, key_ctr(idx), s);
+    launch_keys_insert(idx->ktab, idx->keys.d(), idx->del_dev.p, r0, n, false, key_ctr(idx), s);
     HIP_TRY(hipGetLastError());
     KeyCounters c{};
     VROD_TRY(keys_take_counters(idx, what, c));
@@ -844,34 +869,8 @@ static int index_compact(vrod_index* idx, uint64_t* out_new_ids) {
         compact_bits(del, idx->allow_bits.data(), count, new_allow.data(), cap_words);
         for (size_t w = 0; w < cap_words; ++w) new_eff[w] = ~new_allow[w];   // nothing is deleted afterwards
     }
-    std::vector<uint32_t> new_lab;   // the labels move with their rows; the vacated tail carries 0 again
-    if (idx->lab_dev) {
-        new_lab.assign(count, 0u);
-        uint64_t j = 0;
-        for (uint64_t r = 0; r < count; ++r)
-            if (!bit_of(del, r)) new_lab[j++] = idx->lab_bits[r];
-    }
-    std::vector<uint64_t> new_tag;   // and so do the tags
-    if (idx->tag_dev) {
-        new_tag.assign(count, 0ull);
-        uint64_t j = 0;
-        for (uint64_t r = 0; r < count; ++r)
-            if (!bit_of(del, r)) new_tag[j++] = idx->tag_bits[r];
-    }
-    std::vector<int64_t> new_val;    // and the values
-    if (idx->val_dev) {
-        new_val.assign(count, 0ll);
-        uint64_t j = 0;
-        for (uint64_t r = 0; r < count; ++r)
-            if (!bit_of(del, r)) new_val[j++] = idx->val_bits[r];
-    }
-    std::vector<uint64_t> new_key;   // and the keys (the vacated tail carries none again)
-    if (idx->key_dev) {
-        new_key.assign(count, kKeyNone);
-        uint64_t j = 0;
-        for (uint64_t r = 0; r < count; ++r)
-            if (!bit_of(del, r)) new_key[j++] = idx->key_bits[r];
-    }
+    ColumnBytes moved[kRowColumns];   // the columns move with their rows; the vacated tail carries the default again
+    for_each_column(idx, [&](auto& c, int i) { c.stage_compact(del, count, moved[i]); });
     uint64_t stage_rows = 0;
     for (const CompactChunk& c : plan.chunks) if (c.staged) stage_rows = std::max(stage_rows, c.L);
     if (stage_rows) {
@@ -884,30 +883,27 @@ static int index_compact(vrod_index* idx, uint64_t* out_new_ids) {
 
     // ---- from here on rows move
     hipStream_t s = idx->stream;
-    char* corpus = (char*)idx->corpus;
+    char* corpus = (char*)idx->corpus.p;
     hipError_t e = hipSuccess;
     for (const CompactChunk& c : plan.chunks) {
         if (c.staged) {
-            launch_compact_rows(corpus, idx->xnorm2, idx->del_dev, idx->compact_ws.as<uint32_t>(), c.r0, c.r1, rb, idx->raw_stage.p,
+            launch_compact_rows(corpus, idx->xnorm2.p, idx->del_dev.p, idx->compact_ws.as<uint32_t>(), c.r0, c.r1, rb, idx->raw_stage.p,
                                 idx->nrm_ws.as<float>(), c.w0, s);
             e = hipMemcpyAsync(corpus + c.w0 * rb, idx->raw_stage.p, c.L * rb, hipMemcpyDeviceToDevice, s);
-            if (e == hipSuccess) e = hipMemcpyAsync(idx->xnorm2 + c.w0, idx->nrm_ws.p, c.L * sizeof(float), hipMemcpyDeviceToDevice, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(idx->xnorm2.p + c.w0, idx->nrm_ws.p, c.L * sizeof(float), hipMemcpyDeviceToDevice, s);
         } else {
-            launch_compact_rows(corpus, idx->xnorm2, idx->del_dev, idx->compact_ws.as<uint32_t>(), c.r0, c.r1, rb, corpus, idx->xnorm2, 0, s);
+            launch_compact_rows(corpus, idx->xnorm2.p, idx->del_dev.p, idx->compact_ws.as<uint32_t>(), c.r0, c.r1, rb, corpus, idx->xnorm2.p, 0, s);
         }
         if (e == hipSuccess) e = hipGetLastError();
         if (e != hipSuccess) break;
     }
     if (e == hipSuccess) e = hipMemsetAsync(corpus + plan.live * rb, 0, (count - plan.live) * rb, s);
-    if (e == hipSuccess) e = hipMemsetAsync(idx->xnorm2 + plan.live, 0, (count - plan.live) * sizeof(float), s);
+    if (e == hipSuccess) e = hipMemsetAsync(idx->xnorm2.p + plan.live, 0, (count - plan.live) * sizeof(float), s);
     if (e == hipSuccess) e = hipMemsetAsync(idx->max_xn2_bits, 0, 4, s);
-    if (e == hipSuccess) { launch_xn2_max(idx->xnorm2, plan.live, idx->max_xn2_bits, s); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemsetAsync(idx->del_dev, 0, cap_words * 4, s);
-    if (e == hipSuccess && idx->filter_on) e = hipMemcpyAsync(idx->eff_dev, new_eff.data(), cap_words * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && idx->lab_dev) e = hipMemcpyAsync(idx->lab_dev, new_lab.data(), count * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && idx->tag_dev) e = hipMemcpyAsync(idx->tag_dev, new_tag.data(), count * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && idx->val_dev) e = hipMemcpyAsync(idx->val_dev, new_val.data(), count * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && idx->key_dev) e = hipMemcpyAsync(idx->key_dev, new_key.data(), count * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) { launch_xn2_max(idx->xnorm2.p, plan.live, idx->max_xn2_bits, s); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemsetAsync(idx->del_dev.p, 0, cap_words * 4, s);
+    if (e == hipSuccess && idx->filter_on) e = hipMemcpyAsync(idx->eff_dev.p, new_eff.data(), cap_words * 4, hipMemcpyHostToDevice, s);
+    for_each_column(idx, [&](auto& c, int i) { if (e == hipSuccess) e = c.upload_compact(moved[i], s); });
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess)
         return fail(VROD_ERR_HIP, "vrod_index_compact: %s while rows were moving: the handle is unusable, destroy it", hipGetErrorString(e));
@@ -917,13 +913,10 @@ static int index_compact(vrod_index* idx, uint64_t* out_new_ids) {
     idx->n_deleted = 0;
     idx->count = plan.live;
     if (idx->filter_on) { idx->allow_bits.swap(new_allow); idx->eff_bits.swap(new_eff); }   // n_eligible: the same rows
-    if (idx->lab_dev) std::copy(new_lab.begin(), new_lab.end(), idx->lab_bits.begin());
-    if (idx->tag_dev) std::copy(new_tag.begin(), new_tag.end(), idx->tag_bits.begin());
-    if (idx->val_dev) std::copy(new_val.begin(), new_val.end(), idx->val_bits.begin());
-    if (idx->key_dev) std::copy(new_key.begin(), new_key.end(), idx->key_bits.begin());
+    for_each_column(idx, [&](auto& c, int i) { c.commit_compact(moved[i]); });
     idx->planes_rows = 0;
     mask_changed(idx);
-    if (idx->key_dev) VROD_TRY(keys_rebuild(idx, idx->keyed_live, true, "vrod_index_compact"));   // every slot named an old row
+    if (idx->keys.exists()) VROD_TRY(keys_rebuild(idx, idx->keyed_live, true, "vrod_index_compact"));   // every slot named an old row
     return VROD_OK;
 }
 
@@ -1090,9 +1083,9 @@ static ListBlock list_block(const Pending& P) {
     return {P.lists.as<uint2>(), (uint32_t*)((char*)P.lists.p + (size_t)P.plan.nq_pad * kSelectChunk * 8)};
 }
 // the slot's pacing-counter and claim-bit regions of scan launch `launch` (kSlotFlagBytes: behind the 64 scalars)
-static uint32_t* pace_region(const Pending& P, uint32_t launch) { return P.flags + 64 + (launch % kPaceRegions) * kPaceWords; }
+static uint32_t* pace_region(const Pending& P, uint32_t launch) { return P.flags.p + 64 + (launch % kPaceRegions) * kPaceWords; }
 static uint32_t* claim_region(const Pending& P, uint32_t launch) {
-    return P.flags + 64 + kPaceRegions * kPaceWords + (launch % kPaceRegions) * kClaimWords;
+    return P.flags.p + 64 + kPaceRegions * kPaceWords + (launch % kPaceRegions) * kClaimWords;
 }
 static const size_t kHistWords = 8 * 4096 + 8;   // stream path: [8][<=4096] bin counters + 8 key counters
 
@@ -1102,7 +1095,7 @@ static int mfma_args(vrod_index* idx, Pending& P, MfmaScanArgs& a, const void* q
                      uint32_t nq, uint32_t nq_pad) {
     const ListBlock L = list_block(P);
     a = MfmaScanArgs{};
-    a.corpus = idx->corpus; a.queries = queries; a.xnorm2 = idx->xnorm2; a.qnorm2 = qn2; a.thr = thr;
+    a.corpus = idx->corpus.p; a.queries = queries; a.xnorm2 = idx->xnorm2.p; a.qnorm2 = qn2; a.thr = thr;
     a.lists = L.lists; a.counts = L.counts; a.cap = kSelectChunk; a.ld = idx->ld; a.nq_pad = nq_pad; a.nq = nq;
     a.metric = score_form(idx->metric);
     a.row_mask = idx->row_mask();
@@ -1116,7 +1109,7 @@ static int mfma_args(vrod_index* idx, Pending& P, MfmaScanArgs& a, const void* q
 static int use_split_planes(vrod_index* idx, MfmaScanArgs& a, const float* q_f32, uint32_t nq_pad, DevBuf& q_planes, hipStream_t s) {
     VROD_TRY(q_planes.ensure((size_t)nq_pad * 3 * idx->ldp * 2));
     launch_split_rows(q_f32, nq_pad, idx->ld, idx->ldp, q_planes.p, true, s);
-    a.corpus = idx->planes; a.queries = q_planes.p;
+    a.corpus = idx->planes.p; a.queries = q_planes.p;
     a.ld = 3 * idx->ldp;                          // K extent = query row
     a.lda_bytes = 2 * idx->ldp * 2;               // corpus row [hi_j | lo_j] per K-tile
     a.a_wrap = 1;                                 // SPLIT form of the kernel
@@ -1166,7 +1159,7 @@ static Pending& other_slot(vrod_index* idx, Pending& P) { return idx->slot[&P ==
 // the handle switches the split pass off and quietly keeps the fp32 pass.
 static bool planes_ready(vrod_index* idx) {
     if (idx->planes_cap >= idx->capacity) return true;
-    if (idx->planes) { (void)hipFree(idx->planes); idx->planes = nullptr; idx->planes_cap = idx->planes_rows = 0; }
+    drop_planes(idx);
     const size_t want = idx->capacity * 2ull * idx->ldp * 2ull;
     bool room = true;
     if (!idx->split_forced) {
@@ -1174,12 +1167,11 @@ static bool planes_ready(vrod_index* idx) {
         size_t free_b = 0, total_b = 0;
         room = hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b >= want + std::max<size_t>(total_b / 8, (size_t)4 << 30);
     }
-    if (room && hipMalloc(&idx->planes, want) == hipSuccess) {
+    if (room && idx->planes.alloc(want) == hipSuccess) {
         idx->planes_cap = idx->capacity;
         return true;
     }
     (void)hipGetLastError();
-    idx->planes = nullptr;
     idx->split_enabled = false;
     return false;
 }
@@ -1210,7 +1202,7 @@ static int stream_pass(vrod_index* idx, Pending& P, Timer& tm, bool in_graph) {
         if (q0 > 0) HIP_TRY(hipMemsetAsync(d_hist, 0, kHistWords * 4, s));
         size_t a, b;
         tm.arm(a, b);
-        launch_scan_stream(idx->corpus, idx->dtype, form, idx->ld, N, P.q_f32.as<float>() + (size_t)q0 * idx->ld, nqp,
+        launch_scan_stream(idx->corpus.p, idx->dtype, form, idx->ld, N, P.q_f32.as<float>() + (size_t)q0 * idx->ld, nqp,
                            P.scores.as<float>(), score_ld, d_hist, kp, idx->row_mask(), s);
         P.scan_pairs.push_back({a, b});
         if (q0 + qpp >= nq && !in_graph) VROD_TRY(record_scans_done(P, s));
@@ -1314,7 +1306,7 @@ static int gather_pass(vrod_index* idx, Pending& P, Timer& tm) {
             g_launch_events = LaunchEvents{};
             if (b) HIP_TRY(hipEventRecord(P.ev[a], s));
         }
-        launch_rescore_list(idx->corpus, idx->dtype, form, idx->dim, idx->ld, P.q_f32.as<float>() + (size_t)q0 * idx->ld, gc, list, m,
+        launch_rescore_list(idx->corpus.p, idx->dtype, form, idx->dim, idx->ld, P.q_f32.as<float>() + (size_t)q0 * idx->ld, gc, list, m,
                             P.scores.as<float>(), score_ld, s);
         if (idx->profiling && b) {
             HIP_TRY(hipEventRecord(P.ev[b], s));
@@ -1364,10 +1356,10 @@ static int mfma_pass(vrod_index* idx, Pending& P, Timer& tm, const void* q_lp) {
     if (plan.split) {
         // planes of the rows added since the last batched search, and of this batch's queries
         if (idx->planes_rows < N) {
-            launch_split_rows((const float*)idx->corpus + idx->planes_rows * idx->ld, N - idx->planes_rows, idx->ld, idx->ldp,
-                              (char*)idx->planes + idx->planes_rows * 2ull * idx->ldp * 2ull, false, s);
+            launch_split_rows((const float*)idx->corpus.p + idx->planes_rows * idx->ld, N - idx->planes_rows, idx->ld, idx->ldp,
+                              (char*)idx->planes.p + idx->planes_rows * 2ull * idx->ldp * 2ull, false, s);
             if (round_up(N, kRowTile) > N)   // the tile padding rows stay zero
-                HIP_TRY(hipMemsetAsync((char*)idx->planes + N * 2ull * idx->ldp * 2ull, 0, (round_up(N, kRowTile) - N) * 2ull * idx->ldp * 2ull, s));
+                HIP_TRY(hipMemsetAsync((char*)idx->planes.p + N * 2ull * idx->ldp * 2ull, 0, (round_up(N, kRowTile) - N) * 2ull * idx->ldp * 2ull, s));
             idx->planes_rows = N;
         }
         VROD_TRY(use_split_planes(idx, a, P.q_f32.as<float>(), plan.nq_pad, P.q_planes, s));
@@ -1513,7 +1505,7 @@ static int search_enqueue_body(vrod_index* idx, Pending& P, const float* d_queri
         qi.n_zero_words2 = (uint32_t)kHistWords;
     }
     launch_prep_queries(d_queries_raw, nq, nq_pad, idx->dim, idx->ld, idx->prep_ovr >= 0 ? idx->prep_ovr : prep_form(idx->metric), idx->dtype,
-                        P.q_f32.as<float>(), q_lp, B.qn2, &P.flags[0], &P.flags[1], qi, s);
+                        P.q_f32.as<float>(), q_lp, B.qn2, &P.flags.p[0], &P.flags.p[1], qi, s);
     HIP_TRY(hipGetLastError());
 
     // ---- fast pass: k' candidates per query + T
@@ -1526,13 +1518,13 @@ static int search_enqueue_body(vrod_index* idx, Pending& P, const float* d_queri
 
     if (plan.path != VROD_PATH_EXACT && !gather) {
         // -------- canonical re-score + final ordering + certificate
-        launch_rescore_candidates(idx->corpus, idx->dtype, form, idx->dim, idx->ld, P.q_f32.as<float>(), (int)nq,
+        launch_rescore_candidates(idx->corpus.p, idx->dtype, form, idx->dim, idx->ld, P.q_f32.as<float>(), (int)nq,
                                   P.cand_rows.as<uint32_t>(), plan.kp, P.cand_canon.as<float>(), s);
         launch_final_topk(P.cand_rows.as<uint32_t>(), P.cand_fast.as<float>(), P.cand_canon.as<float>(), B.T, (int)nq, plan.kp, k,
-                          form, idmap_of(idx), plan.eps_mode, plan.eps_c, &P.flags[1], idx->max_xn2_bits, d_out_ids, d_out_scores,
-                          B.status, (float*)&P.flags[2], s);
+                          form, idmap_of(idx), plan.eps_mode, plan.eps_c, &P.flags.p[1], idx->max_xn2_bits, d_out_ids, d_out_scores,
+                          B.status, (float*)&P.flags.p[2], s);
     }
-    launch_gather_readback(B.status, nq, P.flags, idx->max_xn2_bits, B.readback, s);
+    launch_gather_readback(B.status, nq, P.flags.p, idx->max_xn2_bits, B.readback, s);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(P.h_readback, B.readback, ((size_t)nq + 4) * 4, hipMemcpyDeviceToHost, s));
     P.t1 = tm.mark();
@@ -1560,10 +1552,10 @@ static int search_enqueue(vrod_index* idx, Pending& P, const float* d_queries_ra
                            !gather && graph_route(idx->path, nq) && (double)N * idx->ld * idx->esize <= 64.0 * 1048576.0;
     Pending::GraphKey key{};
     if (graphable) {
-        key.q = d_queries_raw; key.oi = d_out_ids; key.os = d_out_scores; key.corpus = idx->corpus; key.xn = idx->xnorm2;
+        key.q = d_queries_raw; key.oi = d_out_ids; key.os = d_out_scores; key.corpus = idx->corpus.p; key.xn = idx->xnorm2.p;
         key.mask = idx->row_mask();
         const void* bufs[12] = {P.q_f32.p, P.q_lp.p, P.small.p, P.hist.p, P.scores.p, P.keys_a.p, P.cand_rows.p, P.cand_fast.p,
-                                P.cand_canon.p, P.h_readback, P.flags, idx->max_xn2_bits};
+                                P.cand_canon.p, P.h_readback, P.flags.p, idx->max_xn2_bits};
         memcpy(key.bufs, bufs, sizeof bufs);
         key.N = N; key.id_offset = idmap_of(idx).offset; key.nq = nq; key.k = k; key.path = idx->path;
     }
@@ -1612,7 +1604,7 @@ static int search_enqueue(vrod_index* idx, Pending& P, const float* d_queries_ra
     if (graphable && rc == VROD_OK) {
         // the key is taken AFTER the body: its ensure() calls may have moved a workspace
         const void* bufs[12] = {P.q_f32.p, P.q_lp.p, P.small.p, P.hist.p, P.scores.p, P.keys_a.p, P.cand_rows.p, P.cand_fast.p,
-                                P.cand_canon.p, P.h_readback, P.flags, idx->max_xn2_bits};
+                                P.cand_canon.p, P.h_readback, P.flags.p, idx->max_xn2_bits};
         memcpy(key.bufs, bufs, sizeof bufs);
         P.gkey = key;
         P.gkey_valid = true;
@@ -1659,9 +1651,9 @@ static int band_pass(vrod_index* idx, Pending& P, std::vector<uint32_t>& failed,
     const ListBlock L = list_block(P);
     HIP_TRY(hipMemcpyAsync(P.band_idx.p, failed.data(), (size_t)nf * 4, hipMemcpyHostToDevice, s));
     // the batch's max |q|^2 (the bound's norm): the device copy was consumed with the read-back, flags[3] holds it for this pass
-    HIP_TRY(hipMemcpyAsync(&P.flags[3], &max_qn2_bits, 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(&P.flags.p[3], &max_qn2_bits, 4, hipMemcpyHostToDevice, s));
     launch_gather_query_rows(P.q_f32.as<float>(), P.band_idx.as<uint32_t>(), nf, nf_pad, idx->ld, P.band_q.as<float>(), bq_lp, s);
-    launch_band_prepare(P.band_idx.as<uint32_t>(), nf, nf_pad, P.out_scores, k, score_form(idx->metric), P.plan.eps_mode, P.plan.eps_c, &P.flags[3],
+    launch_band_prepare(P.band_idx.as<uint32_t>(), nf, nf_pad, P.out_scores, k, score_form(idx->metric), P.plan.eps_mode, P.plan.eps_c, &P.flags.p[3],
                         idx->max_xn2_bits, small_block(P).qn2, b_thr, b_qn2, L.counts, b_ok, s);
     MfmaScanArgs a;
     VROD_TRY(mfma_args(idx, P, a, idx->dtype == VROD_DTYPE_BF16 ? bq_lp : P.band_q.p, b_qn2, b_thr, nf, nf_pad));
@@ -1694,14 +1686,14 @@ static int band_pass(vrod_index* idx, Pending& P, std::vector<uint32_t>& failed,
         // every band row of a resolved query is kept (count <= kpb): sorted by fast score, padded with empty slots
         launch_list_compact(L.lists, L.counts, cap, (int)nf, score_form(idx->metric), kpb, b_thr, b_status, P.cand_rows.as<uint32_t>(), P.cand_fast.as<float>(),
                             b_qn2 /* T: unused */, s);
-        launch_rescore_candidates(idx->corpus, idx->dtype, score_form(idx->metric), idx->dim, idx->ld, P.band_q.as<float>(), (int)nf, P.cand_rows.as<uint32_t>(), kpb,
+        launch_rescore_candidates(idx->corpus.p, idx->dtype, score_form(idx->metric), idx->dim, idx->ld, P.band_q.as<float>(), (int)nf, P.cand_rows.as<uint32_t>(), kpb,
                                   P.cand_canon.as<float>(), s);
         // flags[4]: the band's own observed |fast - canonical| (folded into max_fast_err by search_complete: the band is a
         // superset of the true top-k only while that stays inside the bound)
-        HIP_TRY(hipMemsetAsync(&P.flags[4], 0, 4, s));
+        HIP_TRY(hipMemsetAsync(&P.flags.p[4], 0, 4, s));
         launch_final_topk(P.cand_rows.as<uint32_t>(), P.cand_fast.as<float>(), P.cand_canon.as<float>(), b_qn2, (int)nf, kpb, k, score_form(idx->metric), idmap_of(idx),
-                          P.plan.eps_mode, P.plan.eps_c, &P.flags[3], idx->max_xn2_bits, P.band_ids.as<uint64_t>(), P.band_scores.as<float>(), b_status,
-                          (float*)&P.flags[4], s);
+                          P.plan.eps_mode, P.plan.eps_c, &P.flags.p[3], idx->max_xn2_bits, P.band_ids.as<uint64_t>(), P.band_scores.as<float>(), b_status,
+                          (float*)&P.flags.p[4], s);
         launch_scatter_results(P.band_ids.as<uint64_t>(), P.band_scores.as<float>(), P.band_idx.as<uint32_t>(), b_res, nf, k, P.out_ids, P.out_scores, s);
         HIP_TRY(hipGetLastError());
         std::vector<uint32_t> still;
@@ -1768,7 +1760,7 @@ static int search_complete(vrod_index* idx, Pending& P) {
             int g = gmax;
             while ((size_t)g > failed.size() - f0) g >>= 1;
             VROD_TRY(P.scores.ensure((size_t)g * score_ld * 4));
-            launch_rescore_all(idx->corpus, idx->dtype, score_form(idx->metric), idx->dim, idx->ld, P.q_f32.as<float>(), &failed[f0], g, N,
+            launch_rescore_all(idx->corpus.p, idx->dtype, score_form(idx->metric), idx->dim, idx->ld, P.q_f32.as<float>(), &failed[f0], g, N,
                                P.scores.as<float>(), score_ld, s);
             const uint64_t* keys; uint64_t kld, kn;
             VROD_TRY(select_chain(idx, P, P.scores.as<float>(), score_ld, N, g, kx, idx->row_mask(), &keys, &kld, &kn));
@@ -1786,7 +1778,7 @@ static int search_complete(vrod_index* idx, Pending& P) {
         HIP_TRY(hipStreamSynchronize(s));
         if (st.band_queries) {   // the band's re-score saw its own fast-vs-canonical differences
             float band_err = 0.f;
-            HIP_TRY(hipMemcpy(&band_err, &P.flags[4], 4, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(&band_err, &P.flags.p[4], 4, hipMemcpyDeviceToHost));
             st.max_fast_err = std::max(st.max_fast_err, band_err);
         }
     }
@@ -1809,16 +1801,12 @@ static int search_begin(vrod_index* idx, const float* d_queries_raw, uint32_t nq
                         uint64_t* d_out_ids, float* d_out_scores) {
     if (idx->n_pending() >= 2) return fail(VROD_ERR_INVALID_ARG, "two searches are already pending: call vrod_search_end first");
     Pending& P = idx->slot[idx->n_begun & 1];
-    if (idx->planes && !idx->split_enabled && idx->n_pending() == 0) {   // split pass switched off: give the planes back
-        (void)hipFree(idx->planes);
-        idx->planes = nullptr;
-        idx->planes_cap = idx->planes_rows = 0;
-    }
+    if (idx->planes.p && !idx->split_enabled && idx->n_pending() == 0) drop_planes(idx);   // split pass switched off: give the planes back
     int rc = search_enqueue(idx, P, d_queries_raw, nq, k, d_out_ids, d_out_scores);
     if (rc != VROD_OK) {
         // a half-enqueued search: drain the stream, consume the per-search scalars, leave the slot free
         (void)hipStreamSynchronize(P.stream);
-        (void)hipMemsetAsync(&P.flags[0], 0, 12, P.stream);
+        (void)hipMemsetAsync(&P.flags.p[0], 0, 12, P.stream);
         (void)hipStreamSynchronize(P.stream);
         return rc;
     }
@@ -1883,7 +1871,7 @@ static int composite_add(vrod_index* idx, const float* rows, uint64_t n, bool sy
     const uint64_t count0 = idx->count;
     for (vrod_index* sh : idx->shards) {   // what a roll-back restores (see index_add)
         VROD_TRY(set_device(sh));
-        HIP_TRY(hipMemcpyAsync(&sh->flags[10], sh->max_xn2_bits, 4, hipMemcpyDeviceToDevice, sh->stream));
+        HIP_TRY(hipMemcpyAsync(&sh->flags.p[10], sh->max_xn2_bits, 4, hipMemcpyDeviceToDevice, sh->stream));
     }
     int rc = for_each_piece(idx, count0, n, [&](size_t g, uint64_t r, uint64_t m) {
         vrod_index* sh = idx->shards[g];
@@ -1902,12 +1890,12 @@ static int composite_add(vrod_index* idx, const float* rows, uint64_t n, bool sy
             (void)for_each_piece(idx, 0, count0, [&](size_t gg, uint64_t, uint64_t m) { if (gg == g) want += m; return (int)VROD_OK; });
             if (sh->count > want) {
                 (void)hipSetDevice(sh->device);
-                (void)hipMemsetAsync((char*)sh->corpus + want * sh->row_bytes(), 0, (sh->count - want) * sh->row_bytes(), sh->stream);
-                (void)hipMemsetAsync(sh->xnorm2 + want, 0, (sh->count - want) * sizeof(float), sh->stream);
+                (void)hipMemsetAsync((char*)sh->corpus.p + want * sh->row_bytes(), 0, (sh->count - want) * sh->row_bytes(), sh->stream);
+                (void)hipMemsetAsync(sh->xnorm2.p + want, 0, (sh->count - want) * sizeof(float), sh->stream);
                 sh->count = want;
             }
             (void)hipSetDevice(sh->device);
-            (void)hipMemcpyAsync(sh->max_xn2_bits, &sh->flags[10], 4, hipMemcpyDeviceToDevice, sh->stream);
+            (void)hipMemcpyAsync(sh->max_xn2_bits, &sh->flags.p[10], 4, hipMemcpyDeviceToDevice, sh->stream);
             (void)hipStreamSynchronize(sh->stream);
         }
         return rc;
@@ -1943,14 +1931,15 @@ static int index_delete_rows(vrod_index* idx, const std::vector<uint64_t>& rows)
     if (fresh.empty()) return VROD_OK;
     int rc = set_device(idx);
     hipError_t e = hipSuccess;
-    const bool first = !idx->del_dev;
+    const bool first = !idx->del_dev.p;
+    DevMem<uint32_t> first_dev;   // the first delete's device bitmap: the handle's once the upload is through
     if (rc == VROD_OK && first) {
-        e = hipMalloc((void**)&idx->del_dev, idx->del_bits.size() * 4);
-        if (e != hipSuccess) idx->del_dev = nullptr;
+        e = first_dev.alloc(idx->del_bits.size() * 4);
         wlo = 0; whi = idx->del_bits.size() - 1;   // the whole bitmap
     }
+    uint32_t* const del_dev = first ? first_dev.p : idx->del_dev.p;
     if (rc == VROD_OK && e == hipSuccess)
-        e = hipMemcpyAsync(idx->del_dev + wlo, idx->del_bits.data() + wlo, (whi - wlo + 1) * 4, hipMemcpyHostToDevice, idx->stream);
+        e = hipMemcpyAsync(del_dev + wlo, idx->del_bits.data() + wlo, (whi - wlo + 1) * 4, hipMemcpyHostToDevice, idx->stream);
     // under a filter: the rows this call deletes that were eligible leave the effective mask's zeros
     std::vector<uint32_t> eff_old;
     uint64_t lost = 0;
@@ -1961,21 +1950,21 @@ static int index_delete_rows(vrod_index* idx, const std::vector<uint64_t>& rows)
             const uint32_t bit = 1u << (r % 32);
             if (!(w & bit)) { w |= bit; ++lost; }
         }
-        e = hipMemcpyAsync(idx->eff_dev + wlo, idx->eff_bits.data() + wlo, (whi - wlo + 1) * 4, hipMemcpyHostToDevice, idx->stream);
+        e = hipMemcpyAsync(idx->eff_dev.p + wlo, idx->eff_bits.data() + wlo, (whi - wlo + 1) * 4, hipMemcpyHostToDevice, idx->stream);
     }
     if (rc == VROD_OK && e == hipSuccess) e = hipStreamSynchronize(idx->stream);
     if (rc != VROD_OK || e != hipSuccess) {   // nothing changes: the mirrors forget this call's rows
         (void)hipStreamSynchronize(idx->stream);
         for (uint64_t r : fresh) idx->del_bits[r / 32] &= ~(1u << (r % 32));
         if (!eff_old.empty()) std::copy(eff_old.begin(), eff_old.end(), idx->eff_bits.begin() + wlo);
-        if (first && idx->del_dev) { (void)hipFree(idx->del_dev); idx->del_dev = nullptr; }
-        else if (idx->del_dev) (void)hipMemcpy(idx->del_dev + wlo, idx->del_bits.data() + wlo, (whi - wlo + 1) * 4, hipMemcpyHostToDevice);
-        if (!eff_old.empty()) (void)hipMemcpy(idx->eff_dev + wlo, idx->eff_bits.data() + wlo, (whi - wlo + 1) * 4, hipMemcpyHostToDevice);
+        if (!first) (void)hipMemcpy(del_dev + wlo, idx->del_bits.data() + wlo, (whi - wlo + 1) * 4, hipMemcpyHostToDevice);
+        if (!eff_old.empty()) (void)hipMemcpy(idx->eff_dev.p + wlo, idx->eff_bits.data() + wlo, (whi - wlo + 1) * 4, hipMemcpyHostToDevice);
         return rc != VROD_OK ? rc : fail(e == hipErrorOutOfMemory ? VROD_ERR_OUT_OF_MEMORY : VROD_ERR_HIP, "uploading the deleted rows: %s", hipGetErrorString(e));
     }
+    if (first) idx->del_dev.swap(first_dev);
     idx->n_deleted += fresh.size();
-    if (idx->key_dev)   // a deleted row's key is free: its slot goes stale, nothing is written to the table
-        for (uint64_t r : fresh) idx->keyed_live -= idx->key_bits[r] != kKeyNone;
+    if (idx->keys.exists())   // a deleted row's key is free: its slot goes stale, nothing is written to the table
+        for (uint64_t r : fresh) idx->keyed_live -= idx->keys.host[r] != kKeyNone;
     idx->n_eligible -= lost;
     mask_changed(idx);
     return VROD_OK;
@@ -1987,8 +1976,7 @@ static int index_set_filter(vrod_index* idx, const uint32_t* allow, uint64_t n_r
     VROD_TRY(set_device(idx));
     if (!allow) {
         if (!idx->filter_on) return VROD_OK;
-        if (idx->eff_dev) (void)hipFree(idx->eff_dev);
-        idx->eff_dev = nullptr;
+        idx->eff_dev.release();
         idx->filter_on = false;
         std::vector<uint32_t>().swap(idx->allow_bits);
         std::vector<uint32_t>().swap(idx->eff_bits);
@@ -2006,16 +1994,13 @@ static int index_set_filter(vrod_index* idx, const uint32_t* allow, uint64_t n_r
         eff[w] = idx->del_bits[w] | ~al[w];
         n_el += (uint64_t)__builtin_popcount(~eff[w]);   // (rows >= count are never allowed: n_rows <= count)
     }
-    uint32_t* dev = idx->eff_dev;
-    if (words && !dev) HIP_TRY(hipMalloc((void**)&dev, words * 4));
+    DevMem<uint32_t> first_dev;   // of the first filter since none was set: a later one is uploaded over the mask in place
+    if (words && !idx->eff_dev.p) HIP_TRY(first_dev.alloc(words * 4));
     if (words) {
-        const hipError_t e = hipMemcpy(dev, eff.data(), words * 4, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            if (dev != idx->eff_dev) (void)hipFree(dev);
-            return fail(VROD_ERR_HIP, "uploading the filter: %s", hipGetErrorString(e));
-        }
+        const hipError_t e = hipMemcpy(first_dev.p ? first_dev.p : idx->eff_dev.p, eff.data(), words * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return fail(VROD_ERR_HIP, "uploading the filter: %s", hipGetErrorString(e));
     }
-    idx->eff_dev = dev;
+    if (first_dev.p) idx->eff_dev.swap(first_dev);
     idx->allow_bits.swap(al);
     idx->eff_bits.swap(eff);
     idx->n_eligible = n_el;
@@ -2463,15 +2448,15 @@ static int range_collect(vrod_index* idx, const float* d_queries_raw, uint32_t n
     qi.zero_words2 = fast ? pace_region(P, 0) : nullptr;
     qi.n_zero_words2 = kPaceRegions * (kPaceWords + kClaimWords);
     launch_prep_queries(d_queries_raw, nq, nq_pad, idx->dim, idx->ld, prep_form(idx->metric), idx->dtype, P.q_f32.as<float>(), q_lp, B.qn2,
-                        &P.flags[0], &P.flags[1], qi, s);
+                        &P.flags.p[0], &P.flags.p[1], qi, s);
     if (fast)
-        launch_range_prepare(d_thr, nq, nq_pad, form, plan.eps_mode, plan.eps_c, &P.flags[1], idx->max_xn2_bits, B.thr, B.status, s);
+        launch_range_prepare(d_thr, nq, nq_pad, form, plan.eps_mode, plan.eps_c, &P.flags.p[1], idx->max_xn2_bits, B.thr, B.status, s);
     HIP_TRY(hipGetLastError());
 
     // whatever happens from here on, the slot's per-search scalars (bad-value flag, max |q|^2, max error) end up consumed
     struct FlagReset {
         Pending& P;
-        ~FlagReset() { (void)hipMemsetAsync(&P.flags[0], 0, 12, P.stream); (void)hipStreamSynchronize(P.stream); }
+        ~FlagReset() { (void)hipMemsetAsync(&P.flags.p[0], 0, 12, P.stream); (void)hipStreamSynchronize(P.stream); }
     } flag_reset{P};
 
     std::vector<uint32_t> canon_q;   // queries of the canonical (dense) route
@@ -2486,10 +2471,10 @@ static int range_collect(vrod_index* idx, const float* d_queries_raw, uint32_t n
         VROD_TRY(mfma_args(idx, P, a, idx->dtype == VROD_DTYPE_BF16 ? q_lp : P.q_f32.p, B.qn2, B.thr, nq, nq_pad));
         if (split) {
             if (idx->planes_rows < N) {   // planes of the rows added since the last batched search (as mfma_pass)
-                launch_split_rows((const float*)idx->corpus + idx->planes_rows * idx->ld, N - idx->planes_rows, idx->ld, idx->ldp,
-                                  (char*)idx->planes + idx->planes_rows * 2ull * idx->ldp * 2ull, false, s);
+                launch_split_rows((const float*)idx->corpus.p + idx->planes_rows * idx->ld, N - idx->planes_rows, idx->ld, idx->ldp,
+                                  (char*)idx->planes.p + idx->planes_rows * 2ull * idx->ldp * 2ull, false, s);
                 if (round_up(N, kRowTile) > N)
-                    HIP_TRY(hipMemsetAsync((char*)idx->planes + N * 2ull * idx->ldp * 2ull, 0, (round_up(N, kRowTile) - N) * 2ull * idx->ldp * 2ull, s));
+                    HIP_TRY(hipMemsetAsync((char*)idx->planes.p + N * 2ull * idx->ldp * 2ull, 0, (round_up(N, kRowTile) - N) * 2ull * idx->ldp * 2ull, s));
                 idx->planes_rows = N;
             }
             VROD_TRY(use_split_planes(idx, a, P.q_f32.as<float>(), nq_pad, P.q_planes, s));
@@ -2510,7 +2495,7 @@ static int range_collect(vrod_index* idx, const float* d_queries_raw, uint32_t n
             HIP_TRY(hipMemcpyAsync(hcnt.data(), L.counts, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
             if (first) {
                 HIP_TRY(hipMemcpyAsync(hcanon.data(), B.status, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-                HIP_TRY(hipMemcpyAsync(hflags, &P.flags[0], 8, hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipMemcpyAsync(hflags, &P.flags.p[0], 8, hipMemcpyDeviceToHost, s));
             }
             HIP_TRY(hipStreamSynchronize(s));
             if (first) VROD_TRY(check_queries());
@@ -2524,15 +2509,15 @@ static int range_collect(vrod_index* idx, const float* d_queries_raw, uint32_t n
                 continue;
             }
             st.kprime = std::max(st.kprime, maxc);
-            launch_range_rescore_cut(idx->corpus, idx->dtype, form, idx->dim, idx->ld, P.q_f32.as<float>(), nq, L.lists, L.counts, cap, maxc, d_thr,
-                                     idmap_of(idx), pool, &P.flags[2], s);
+            launch_range_rescore_cut(idx->corpus.p, idx->dtype, form, idx->dim, idx->ld, P.q_f32.as<float>(), nq, L.lists, L.counts, cap, maxc, d_thr,
+                                     idmap_of(idx), pool, &P.flags.p[2], s);
             HIP_TRY(hipGetLastError());
         }
         for (uint32_t q = 0; q < nq; ++q)
             if (hcanon[q]) canon_q.push_back(q);
         st.fallback_queries = (uint32_t)canon_q.size();
     } else {
-        HIP_TRY(hipMemcpyAsync(hflags, &P.flags[0], 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(hflags, &P.flags.p[0], 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         VROD_TRY(check_queries());
         if (exact) {
@@ -2550,7 +2535,7 @@ static int range_collect(vrod_index* idx, const float* d_queries_raw, uint32_t n
             int g = gmax;
             while ((size_t)g > canon_q.size() - f0) g >>= 1;
             VROD_TRY(P.scores.ensure((size_t)g * score_ld * 4));
-            launch_rescore_all(idx->corpus, idx->dtype, form, idx->dim, idx->ld, P.q_f32.as<float>(), &canon_q[f0], g, N, P.scores.as<float>(), score_ld, s);
+            launch_rescore_all(idx->corpus.p, idx->dtype, form, idx->dim, idx->ld, P.q_f32.as<float>(), &canon_q[f0], g, N, P.scores.as<float>(), score_ld, s);
             launch_range_cut_scores(P.scores.as<float>(), score_ld, N, (uint32_t)g, &canon_q[f0], 0, form, d_thr, idx->row_mask(), nullptr, idmap_of(idx), pool, s);
             HIP_TRY(hipGetLastError());
             if (!fast) { st.scan_launches++; st.scan_bytes += (double)N * idx->ld * idx->esize; st.scan_flops += 2.0 * g * (double)N * idx->dim; }
@@ -2568,7 +2553,7 @@ static int range_collect(vrod_index* idx, const float* d_queries_raw, uint32_t n
         VROD_TRY(P.scores.ensure((size_t)g * score_ld * 4));
         for (uint32_t q0 = 0; q0 < nq; q0 += (uint32_t)g) {
             const uint32_t gc = (uint32_t)std::min<uint64_t>(g, nq - q0);
-            launch_rescore_list(idx->corpus, idx->dtype, form, idx->dim, idx->ld, P.q_f32.as<float>() + (size_t)q0 * idx->ld, gc, idx->list_dev.as<uint32_t>(), m,
+            launch_rescore_list(idx->corpus.p, idx->dtype, form, idx->dim, idx->ld, P.q_f32.as<float>() + (size_t)q0 * idx->ld, gc, idx->list_dev.as<uint32_t>(), m,
                                 P.scores.as<float>(), score_ld, s);
             launch_range_cut_scores(P.scores.as<float>(), score_ld, m, gc, nullptr, q0, form, d_thr, nullptr, idx->list_dev.as<uint32_t>(), idmap_of(idx), pool, s);
             HIP_TRY(hipGetLastError());
@@ -2584,7 +2569,7 @@ static int range_collect(vrod_index* idx, const float* d_queries_raw, uint32_t n
     uint32_t herr = 0, hmaxx = 0;
     HIP_TRY(hipMemcpyAsync(hq.data(), pool.per_query, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(&htotal, pool.n_total, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&herr, &P.flags[2], 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&herr, &P.flags.p[2], 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(&hmaxx, idx->max_xn2_bits, 4, hipMemcpyDeviceToHost, s));
     P.t1 = tm.mark();
     HIP_TRY(hipStreamSynchronize(s));
@@ -2765,8 +2750,8 @@ static int prep_queries_checked(vrod_index* idx, Pending& P, const float* d_quer
     QueryInit qi{};
     qi.status = B.status;
     launch_prep_queries(d_queries_raw, nq, nq, idx->dim, idx->ld, prep_form(idx->metric), idx->dtype, P.q_f32.as<float>(), nullptr, B.qn2,
-                        &P.flags[0], &P.flags[1], qi, s);
-    launch_gather_readback(B.status, nq, P.flags, idx->max_xn2_bits, B.readback, s);   // (consumes the slot's scalars)
+                        &P.flags.p[0], &P.flags.p[1], qi, s);
+    launch_gather_readback(B.status, nq, P.flags.p, idx->max_xn2_bits, B.readback, s);   // (consumes the slot's scalars)
     HIP_TRY(hipGetLastError());
     uint32_t bad = 0;
     HIP_TRY(hipMemcpyAsync(&bad, B.readback + nq, 4, hipMemcpyDeviceToHost, s));
@@ -2791,7 +2776,7 @@ static int label_pass_ws(vrod_index* idx, uint32_t Gc, LabelPassWs& W) {
 // h_total: the totals are read back into it, and the stream is drained; null: the launch is only enqueued.
 static int label_count_pass(vrod_index* idx, hipStream_t s, const LabelPassWs& W, const uint32_t* h_table, uint32_t Gp, uint32_t* h_total) {
     HIP_TRY(hipMemcpyAsync(W.table, h_table, (size_t)Gp * 4, hipMemcpyHostToDevice, s));
-    launch_label_group_count(idx->lab_dev, idx->row_mask(), idx->count, W.rpb, W.table, Gp, W.cnt, W.total, s);
+    launch_label_group_count(idx->labels.d(), idx->row_mask(), idx->count, W.rpb, W.table, Gp, W.cnt, W.total, s);
     if (!h_total) return VROD_OK;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(h_total, W.total, (size_t)Gp * 4, hipMemcpyDeviceToHost, s));
@@ -2804,7 +2789,7 @@ static int label_scatter_pass(vrod_index* idx, hipStream_t s, const LabelPassWs&
     VROD_TRY(idx->lab_lists.ensure(std::max<uint64_t>(list_n, 1) * 4));
     HIP_TRY(hipMemcpyAsync(W.seg_off, h_seg_off, (size_t)Gp * 4, hipMemcpyHostToDevice, s));
     if (list_n)
-        launch_label_group_scatter(idx->lab_dev, idx->row_mask(), idx->count, W.rpb, W.table, Gp, W.cnt, W.seg_off, idx->lab_lists.as<uint32_t>(), s);
+        launch_label_group_scatter(idx->labels.d(), idx->row_mask(), idx->count, W.rpb, W.table, Gp, W.cnt, W.seg_off, idx->lab_lists.as<uint32_t>(), s);
     HIP_TRY(hipGetLastError());
     return VROD_OK;
 }
@@ -2835,7 +2820,7 @@ static int run_segments(vrod_index* idx, Pending& P, Timer* tm, vrod_search_stat
         if (c.n_blocks) {
             size_t a = 0, b = 0;
             if (tm) VROD_TRY(tm->begin_launch(a, b));
-            launch_rescore_segments(idx->corpus, idx->dtype, score_form(idx->metric), idx->dim, idx->ld, d_q, idx->lab_entries.as<SegEntry>() + c.e0,
+            launch_rescore_segments(idx->corpus.p, idx->dtype, score_form(idx->metric), idx->dim, idx->ld, d_q, idx->lab_entries.as<SegEntry>() + c.e0,
                                     c.e1 - c.e0, c.n_blocks, D.q, c.slot0, idx->lab_lists.as<uint32_t>(), P.scores.as<float>(), out_ld, s);
             if (tm) VROD_TRY(tm->end_launch(a, b));
             st.scan_launches++;
@@ -2958,7 +2943,7 @@ static int labeled_search(vrod_index* idx, const float* d_queries_raw, uint32_t 
         for (const Dense& d : dense) {
             const uint32_t nqg = G.nq_of(d.g);
             const uint32_t* d_qidx = d_qorder + G.q_off[d.g];
-            launch_label_group_mask(idx->lab_dev, base_mask, N, words, G.labels[d.g], idx->lab_mask.as<uint32_t>(), s);
+            launch_label_group_mask(idx->labels.d(), base_mask, N, words, G.labels[d.g], idx->lab_mask.as<uint32_t>(), s);
             VROD_TRY(dense_group_search(idx, s, st, d_queries_raw, d_qidx, d_ones, nqg, d.m, k, d_out_ids, d_out_scores));
         }
     }
@@ -2975,14 +2960,14 @@ struct TagSearch {
     static TagGroups groups(const TagPred* p, uint32_t nq) { return tag_groups(p, nq); }
     static void count(const vrod_index* idx, const uint32_t* mask, uint32_t rpb, const TagPred* table, uint32_t G, uint32_t* cnt, uint32_t cnt_ld,
                       hipStream_t s) {
-        launch_tag_group_count(idx->tag_dev, mask, idx->count, rpb, table, G, cnt, cnt_ld, s);
+        launch_tag_group_count(idx->tags.d(), mask, idx->count, rpb, table, G, cnt, cnt_ld, s);
     }
     static void scatter(const vrod_index* idx, const uint32_t* mask, uint32_t rpb, const TagPred* table, uint32_t G, const uint32_t* cnt,
                         uint32_t cnt_ld, const uint32_t* seg_off, uint32_t* lists, hipStream_t s) {
-        launch_tag_group_scatter(idx->tag_dev, mask, idx->count, rpb, table, G, cnt, cnt_ld, seg_off, lists, s);
+        launch_tag_group_scatter(idx->tags.d(), mask, idx->count, rpb, table, G, cnt, cnt_ld, seg_off, lists, s);
     }
     static void mask_of(const vrod_index* idx, const uint32_t* mask, uint64_t words, const TagPred& p, uint32_t* out, hipStream_t s) {
-        launch_tag_group_mask(idx->tag_dev, mask, idx->count, words, p, out, s);
+        launch_tag_group_mask(idx->tags.d(), mask, idx->count, words, p, out, s);
     }
 };
 struct WhereSearch {
@@ -2991,14 +2976,14 @@ struct WhereSearch {
     static WhereGroups groups(const WherePred* p, uint32_t nq) { return where_groups(p, nq); }
     static void count(const vrod_index* idx, const uint32_t* mask, uint32_t rpb, const WherePred* table, uint32_t G, uint32_t* cnt,
                       uint32_t cnt_ld, hipStream_t s) {
-        launch_where_group_count(idx->tag_dev, idx->val_dev, mask, idx->count, rpb, table, G, cnt, cnt_ld, s);
+        launch_where_group_count(idx->tags.d(), idx->values.d(), mask, idx->count, rpb, table, G, cnt, cnt_ld, s);
     }
     static void scatter(const vrod_index* idx, const uint32_t* mask, uint32_t rpb, const WherePred* table, uint32_t G, const uint32_t* cnt,
                         uint32_t cnt_ld, const uint32_t* seg_off, uint32_t* lists, hipStream_t s) {
-        launch_where_group_scatter(idx->tag_dev, idx->val_dev, mask, idx->count, rpb, table, G, cnt, cnt_ld, seg_off, lists, s);
+        launch_where_group_scatter(idx->tags.d(), idx->values.d(), mask, idx->count, rpb, table, G, cnt, cnt_ld, seg_off, lists, s);
     }
     static void mask_of(const vrod_index* idx, const uint32_t* mask, uint64_t words, const WherePred& p, uint32_t* out, hipStream_t s) {
-        launch_where_group_mask(idx->tag_dev, idx->val_dev, mask, idx->count, words, p, out, s);
+        launch_where_group_mask(idx->tags.d(), idx->values.d(), mask, idx->count, words, p, out, s);
     }
 };
 
@@ -3144,7 +3129,7 @@ static int grouped_search(vrod_index* idx, const float* d_queries_raw, uint32_t 
         return VROD_OK;
     }
     // a handle without labels holds one label: its representative is the best row, and no list can add a second
-    const bool one_label = !idx->lab_dev;
+    const bool one_label = !idx->labels.exists();
     const uint32_t k1 = one_label ? 1u : group_first_k(k, elig);
     std::vector<uint32_t> hfv((size_t)nq * 2), todo;
     auto read_state = [&](hipStream_t on) -> int {
@@ -3162,7 +3147,7 @@ static int grouped_search(vrod_index* idx, const float* d_queries_raw, uint32_t 
         st = idx->stats;
         st.k = k;
         s = next_slot(idx).stream;
-        launch_group_dedupe(idx->list_ids[0].as<uint64_t>(), idx->list_scores[0].as<float>(), k1, nq, idx->lab_dev, idmap.offset, nullptr, k,
+        launch_group_dedupe(idx->list_ids[0].as<uint64_t>(), idx->list_scores[0].as<float>(), k1, nq, idx->labels.d(), idmap.offset, nullptr, k,
                             d_out_ids, d_out_scores, d_out_labels, d_found, d_valid, s);
         VROD_TRY(read_state(s));
         for (uint32_t q = 0; q < nq; ++q)
@@ -3194,7 +3179,7 @@ static int grouped_search(vrod_index* idx, const float* d_queries_raw, uint32_t 
         VROD_TRY(P.scores.ensure((size_t)g * score_ld * 4));
         size_t ea = 0, eb = 0;
         VROD_TRY(tm.begin_launch(ea, eb));
-        launch_rescore_all(idx->corpus, idx->dtype, form, idx->dim, idx->ld, P.q_f32.as<float>(), &todo[f0], g, N, P.scores.as<float>(),
+        launch_rescore_all(idx->corpus.p, idx->dtype, form, idx->dim, idx->ld, P.q_f32.as<float>(), &todo[f0], g, N, P.scores.as<float>(),
                            score_ld, s);
         VROD_TRY(tm.end_launch(ea, eb));
         HIP_TRY(hipGetLastError());
@@ -3210,7 +3195,7 @@ static int grouped_search(vrod_index* idx, const float* d_queries_raw, uint32_t 
             std::vector<uint32_t> hq(na);
             for (uint32_t a = 0; a < na; ++a) hq[a] = act[a].q;
             HIP_TRY(hipMemcpyAsync(d_qidx, hq.data(), (size_t)na * 4, hipMemcpyHostToDevice, s));
-            launch_group_mask(idx->lab_dev, idx->row_mask(), N, words, d_qidx, na, d_out_labels, d_found, k, idx->grp_mask.as<uint32_t>(), s);
+            launch_group_mask(idx->labels.d(), idx->row_mask(), N, words, d_qidx, na, d_out_labels, d_found, k, idx->grp_mask.as<uint32_t>(), s);
             for (uint32_t a = 0; a < na; ++a) {   // a mask per query: a select chain per query
                 const uint64_t* keys; uint64_t kld, kn;
                 VROD_TRY(select_chain(idx, P, P.scores.as<float>() + (size_t)act[a].score_row * score_ld, score_ld, N, 1, k1,
@@ -3218,7 +3203,7 @@ static int grouped_search(vrod_index* idx, const float* d_queries_raw, uint32_t 
                 launch_keys_to_output(keys, kn, form, k1, idmap, idx->list_ids[0].as<uint64_t>() + (size_t)a * k1,
                                       idx->list_scores[0].as<float>() + (size_t)a * k1, s);
             }
-            launch_group_dedupe(idx->list_ids[0].as<uint64_t>(), idx->list_scores[0].as<float>(), k1, na, idx->lab_dev, idmap.offset, d_qidx, k,
+            launch_group_dedupe(idx->list_ids[0].as<uint64_t>(), idx->list_scores[0].as<float>(), k1, na, idx->labels.d(), idmap.offset, d_qidx, k,
                                 d_out_ids, d_out_scores, d_out_labels, d_found, d_valid, s);
             VROD_TRY(read_state(s));   // (also orders the next round's upload of d_qidx behind this round's readers)
             std::vector<Active> next;
@@ -3253,13 +3238,13 @@ static int multivec_doc_index(vrod_index* idx) {
     if (idx->doc_valid) return VROD_OK;
     const uint64_t N = idx->count;
     std::vector<uint32_t> docs(1, 0u);
-    if (idx->lab_dev) {
-        docs.assign(idx->lab_bits.begin(), idx->lab_bits.begin() + N);
+    if (idx->labels.exists()) {
+        docs.assign(idx->labels.host.begin(), idx->labels.host.begin() + N);
         std::sort(docs.begin(), docs.end());
         docs.erase(std::unique(docs.begin(), docs.end()), docs.end());
         std::vector<uint32_t> rank(N);
         for (uint64_t r = 0; r < N; ++r)
-            rank[r] = (uint32_t)(std::lower_bound(docs.begin(), docs.end(), idx->lab_bits[r]) - docs.begin());
+            rank[r] = (uint32_t)(std::lower_bound(docs.begin(), docs.end(), idx->labels.host[r]) - docs.begin());
         VROD_TRY(idx->doc_rank.ensure(N * 4));
         HIP_TRY(hipMemcpy(idx->doc_rank.p, rank.data(), N * 4, hipMemcpyHostToDevice));
     }
@@ -3301,7 +3286,7 @@ static int multivec_dense(vrod_index* idx, vrod_search_stats& st, const uint32_t
     VROD_TRY(idx->mv_S.ensure((size_t)std::min<size_t>(qg_max, todo.size()) * Dld * 4));
     VROD_TRY(idx->mv_pairs.ensure((size_t)qg_max * 4));
     uint32_t* d_qidx = idx->mv_pairs.as<uint32_t>();
-    const uint32_t* d_rank = idx->lab_dev ? idx->doc_rank.as<uint32_t>() : nullptr;
+    const uint32_t* d_rank = idx->labels.exists() ? idx->doc_rank.as<uint32_t>() : nullptr;
     bool have_absent = false;
     for (size_t f0 = 0; f0 < todo.size(); f0 += qg_max) {
         const uint32_t qg = (uint32_t)std::min<size_t>(qg_max, todo.size() - f0);
@@ -3313,7 +3298,7 @@ static int multivec_dense(vrod_index* idx, vrod_search_stats& st, const uint32_t
                 while (gl < g) gl <<= 1;
                 uint32_t qi[8];
                 for (uint32_t j = 0; j < gl; ++j) qi[j] = v0 + std::min(j, g - 1);
-                launch_rescore_all(idx->corpus, idx->dtype, form, idx->dim, idx->ld, idx->mv_q.as<float>(), qi, (int)gl, N, P.scores.as<float>(),
+                launch_rescore_all(idx->corpus.p, idx->dtype, form, idx->dim, idx->ld, idx->mv_q.as<float>(), qi, (int)gl, N, P.scores.as<float>(),
                                    score_ld, s);
                 HIP_TRY(hipMemsetAsync(idx->mv_best.p, 0, (size_t)g * D * 4, s));
                 launch_multivec_fold(P.scores.as<float>(), score_ld, g, N, d_rank, idx->row_mask(), form, idx->mv_best.as<uint32_t>(), D, s);
@@ -3386,7 +3371,7 @@ static int multivec_candidates(vrod_index* idx, vrod_search_stats& st, bool firs
     uint32_t* d_len = d_qidx + nqs;
     HIP_TRY(hipMemcpyAsync(d_mq, mq.data(), (size_t)nqs * sizeof(MultivecQuery), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(idx->mv_tab.p, 0xFF, tab_words * 4, s));
-    launch_multivec_candidates(idx->list_ids[0].as<uint64_t>(), idx->list_scores[0].as<float>(), k1, idx->lab_dev, idmap_of(idx).offset, d_mq, nqs,
+    launch_multivec_candidates(idx->list_ids[0].as<uint64_t>(), idx->list_scores[0].as<float>(), k1, idx->labels.d(), idmap_of(idx).offset, d_mq, nqs,
                                idx->mv_ent.as<uint32_t>(), idx->mv_tab.as<uint32_t>(), idx->mv_cand.as<uint32_t>(), d_count, d_flags, d_U, s);
     HIP_TRY(hipGetLastError());
     std::vector<uint32_t> cf((size_t)nqs * 3), cand(entries);
@@ -3564,7 +3549,7 @@ static int multivec_search(vrod_index* idx, const float* d_raw, const uint32_t* 
     }
     std::vector<uint32_t> dense;
     // a handle without labels is one document that owns every row: nothing for the candidate route to narrow
-    if (idx->path != VROD_PATH_EXACT && idx->lab_dev) {
+    if (idx->path != VROD_PATH_EXACT && idx->labels.exists()) {
         const uint32_t k1 = multivec_first_k(k, elig);
         ms.k1 = k1;
         for (uint32_t q0 = 0; q0 < nq;) {
@@ -3604,7 +3589,7 @@ static int diverse_search(vrod_index* idx, const float* d_queries_raw, uint32_t 
     VROD_TRY(run_search(idx, d_queries_raw, nq, pool, idx->list_ids[0].as<uint64_t>(), idx->list_scores[0].as<float>()));
     idx->stats.k = k;
     hipStream_t s = next_slot(idx).stream;
-    launch_diverse_select(idx->corpus, idx->dtype, score_form(idx->metric), idx->dim, idx->ld, idx->list_ids[0].as<uint64_t>(),
+    launch_diverse_select(idx->corpus.p, idx->dtype, score_form(idx->metric), idx->dim, idx->ld, idx->list_ids[0].as<uint64_t>(),
                           idx->list_scores[0].as<float>(), nq, pool, k, lambda, idmap_of(idx).offset, d_out_ids, d_out_scores, d_out_mmr, s);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
@@ -3618,7 +3603,7 @@ static int diverse_search(vrod_index* idx, const float* d_queries_raw, uint32_t 
 // k + 1 results into the library's own lists and byid_drop_self_kernel writes the caller's k: the top k of S \ {self} is
 // the top (k + 1) of S with self removed, whatever position self took (an exact duplicate with a smaller id ranks
 // before it; under IP, or under a filter that leaves it out, it may not be in the list at all).
-constexpr uint32_t kByidFlag = 16;   // word of idx->flags the gather raises for an id that is no live row
+constexpr uint32_t kByidFlag = 16;   // word of idx->flags.p the gather raises for an id that is no live row
 
 static int byid_search_begin(vrod_index* idx, const float* d_rows_f32, uint32_t nq, uint32_t k1, uint64_t* d_ids, float* d_scores) {
     idx->prep_ovr = M_L2;   // set for exactly the enqueue: nothing else prepares queries
@@ -3643,8 +3628,8 @@ static int byid_search(vrod_index* idx, const uint64_t* d_ids, bool checked, uin
         l_scores = idx->list_scores[0].as<float>();
     }
     VROD_TRY(P.q_raw.ensure((size_t)nq * idx->dim * 4));
-    launch_byid_gather(idx->corpus, idx->dtype, idx->ld, idx->dim, idx->count, idx->id_offset, idx->n_deleted ? idx->del_dev : nullptr, d_ids,
-                       nullptr, 0, nq, P.q_raw.as<float>(), checked ? nullptr : &idx->flags[kByidFlag], s);
+    launch_byid_gather(idx->corpus.p, idx->dtype, idx->ld, idx->dim, idx->count, idx->id_offset, idx->n_deleted ? idx->del_dev.p : nullptr, d_ids,
+                       nullptr, 0, nq, P.q_raw.as<float>(), checked ? nullptr : &idx->flags.p[kByidFlag], s);
     HIP_TRY(hipGetLastError());
     if (!checked) {   // (the search is begun only behind this read-back: a bad id leaves the caller's buffers untouched)
         uint32_t bad;
@@ -3673,7 +3658,7 @@ static int byid_search(vrod_index* idx, const uint64_t* d_ids, bool checked, uin
 // caller's rows.  Every pointer is device memory except the two lims arrays, which the host has validated (counts).
 // checked: the host has validated the term ids and the weights as well; else the combine launch does.  Its flag word --
 // the overflow check in either case -- is read before the search is begun: a refused call leaves the outputs as they were.
-constexpr uint32_t kCombineFlag = 17;   // word of idx->flags the combine launch raises
+constexpr uint32_t kCombineFlag = 17;   // word of idx->flags.p the combine launch raises
 
 struct CombineArgs {
     const float* d_vectors;        // raw [nq][dim], or null
@@ -3700,9 +3685,9 @@ static int combined_search(vrod_index* idx, const CombineArgs& a, const CombineC
     }
     if (a.d_vectors) VROD_TRY(prep_queries_checked(idx, P, a.d_vectors, nq));   // -> P.q_f32 [nq][ld]; NaN / Inf fails here
     VROD_TRY(P.q_raw.ensure((size_t)nq * idx->dim * 4));
-    launch_combine_queries(idx->corpus, idx->dtype, idx->ld, idx->dim, idx->count, idx->id_offset, idx->n_deleted ? idx->del_dev : nullptr,
+    launch_combine_queries(idx->corpus.p, idx->dtype, idx->ld, idx->dim, idx->count, idx->id_offset, idx->n_deleted ? idx->del_dev.p : nullptr,
                            a.d_vectors ? P.q_f32.as<float>() : nullptr, a.d_vector_weights, a.d_term_lims, a.d_term_ids, a.d_term_weights, nq,
-                           P.q_raw.as<float>(), &idx->flags[kCombineFlag], s);
+                           P.q_raw.as<float>(), &idx->flags.p[kCombineFlag], s);
     HIP_TRY(hipGetLastError());
     uint32_t bad;
     VROD_TRY(take_flag(idx, kCombineFlag, s, &bad));
@@ -3823,7 +3808,7 @@ static int candidates_score(vrod_index* idx, const float* d_queries_raw, uint32_
         P.reset_events();
         size_t a = 0, b = 0;
         VROD_TRY(tm.begin_launch(a, b));
-        launch_cand_score(idx->corpus, idx->dtype, score_form(idx->metric), idx->dim, idx->ld, P.q_f32.as<float>(), d_lims, d_off, nq, off[nq],
+        launch_cand_score(idx->corpus.p, idx->dtype, score_form(idx->metric), idx->dim, idx->ld, P.q_f32.as<float>(), d_lims, d_off, nq, off[nq],
                           idx->cand_rows.as<uint32_t>(), d_out_scores, d_cnt, s);
         VROD_TRY(tm.end_launch(a, b));
         HIP_TRY(hipGetLastError());
@@ -3879,10 +3864,10 @@ static int knn_graph(vrod_index* idx, uint64_t row0, uint64_t n, uint32_t k, uin
         const uint32_t* d_rows = nullptr;
         if (F.holes) {
             VROD_TRY(idx->byid_map[c].ensure((size_t)m * 4 * 2));
-            launch_byid_live(idx->del_dev, r0, m, map_of(F), map_of(F) + m, P.stream);
+            launch_byid_live(idx->del_dev.p, r0, m, map_of(F), map_of(F) + m, P.stream);
             d_rows = map_of(F);
         }
-        launch_byid_gather(idx->corpus, idx->dtype, idx->ld, idx->dim, idx->count, idx->id_offset, nullptr, nullptr, d_rows, r0, F.live,
+        launch_byid_gather(idx->corpus.p, idx->dtype, idx->ld, idx->dim, idx->count, idx->id_offset, nullptr, nullptr, d_rows, r0, F.live,
                            P.q_raw.as<float>(), nullptr, P.stream);   // (the range and the tombstones were checked on the host)
         HIP_TRY(hipGetLastError());
         return byid_search_begin(idx, P.q_raw.as<float>(), F.live, k1, idx->list_ids[c].as<uint64_t>(), idx->list_scores[c].as<float>());
@@ -3944,7 +3929,7 @@ static int knn_graph(vrod_index* idx, uint64_t row0, uint64_t n, uint32_t k, uin
 // device array.  The checksums are taken on the device, over device memory, on both sides: HBM -> file -> HBM is covered
 // end to end and the host makes no pass over the rows.  The bitmaps are the host mirrors' (the truth for both), checked
 // on the host: a 32nd of a byte per row.
-constexpr uint32_t kSnapSumWord = 32;   // idx->flags[32 .. 48): one 64-bit device sum per section kind (SNAP_KIND_END = 9)
+constexpr uint32_t kSnapSumWord = 32;   // idx->flags.p[32 .. 48): one 64-bit device sum per section kind (SNAP_KIND_END = 9)
 
 static int snap_status(SnapStatus st, const char* path, const char* why) {
     if (st == SNAP_OK) return VROD_OK;
@@ -4161,16 +4146,13 @@ static int snap_save_body(vrod_index* idx, int fd) {
     auto add = [&](uint32_t kind) { h.sections[h.n_sections].kind = kind; h.sections[h.n_sections++].bytes = snap_section_bytes(kind, count, h.dim, h.dtype); };
     add(SNAP_ROWS); add(SNAP_NORMS); add(SNAP_DELETED);
     if (idx->filter_on) add(SNAP_FILTER);
-    if (idx->lab_dev) add(SNAP_LABELS);
-    if (idx->tag_dev) add(SNAP_TAGS);
-    if (idx->val_dev) add(SNAP_VALUES);
-    if (idx->key_dev) add(SNAP_KEYS);
+    for_each_column(idx, [&](auto& c, int) { if (c.exists()) add(c.snap_kind); });
     snap_layout(h);
     if (ftruncate(fd, (off_t)h.file_bytes) != 0) return fail(VROD_ERR_IO, "sizing the snapshot: %s", strerror(errno));   // (the padding: zeros)
 
     const uint64_t chunk = snap_chunk_rows_now(idx, count);
     const size_t stage = snap_stage_bytes(idx, chunk);
-    uint64_t* d_sum = (uint64_t*)(idx->flags + kSnapSumWord);
+    uint64_t* d_sum = (uint64_t*)(idx->flags.p + kSnapSumWord);
     uint64_t h_sum[SNAP_KIND_END] = {};
     {
         SnapPipe P;
@@ -4185,7 +4167,7 @@ static int snap_save_body(vrod_index* idx, int fd) {
                     const uint64_t r0 = off / (idx->dim * es), m = n / (idx->dim * es);
                     char* dense = idx->snap_stage.as<char>() + (size_t)b * stage;
                     VROD_TRY(P.mark(b, 0));
-                    launch_snapshot_pack((const char*)idx->corpus + r0 * idx->row_bytes(), m, idx->dim, idx->ld, idx->dtype, dense, off / 4,
+                    launch_snapshot_pack((const char*)idx->corpus.p + r0 * idx->row_bytes(), m, idx->dim, idx->ld, idx->dtype, dense, off / 4,
                                          d_sum + SNAP_ROWS, s);
                     HIP_TRY(hipGetLastError());
                     VROD_TRY(P.mark(b, 1));
@@ -4194,9 +4176,8 @@ static int snap_save_body(vrod_index* idx, int fd) {
                 }));
                 continue;
             }
-            const void* d_arr = sec.kind == SNAP_NORMS ? (const void*)idx->xnorm2 : sec.kind == SNAP_LABELS ? (const void*)idx->lab_dev
-                              : sec.kind == SNAP_TAGS ? (const void*)idx->tag_dev : sec.kind == SNAP_VALUES ? (const void*)idx->val_dev
-                              : sec.kind == SNAP_KEYS ? (const void*)idx->key_dev : nullptr;
+            const void* d_arr = sec.kind == SNAP_NORMS ? idx->xnorm2.p : nullptr;
+            for_each_column(idx, [&](auto& c, int) { if (c.snap_kind == sec.kind) d_arr = c.dev.p; });
             if (!d_arr) continue;   // the bitmaps: below
             launch_snapshot_checksum(d_arr, sec.bytes, 0, d_sum + sec.kind, s);
             HIP_TRY(hipGetLastError());
@@ -4226,23 +4207,20 @@ static int snap_save_body(vrod_index* idx, int fd) {
     return VROD_OK;
 }
 
-// a side array of a loaded handle: device copy and host mirror over the capacity, rows [0, count) from the file, the
-// rest `none` (0, or every bit set)
+// a column of a loaded handle: device copy and host mirror over the capacity, rows [0, count) from its section of the
+// file, the rest at the column's default
 template <typename T>
-static int snap_load_side(vrod_index* idx, SnapPipe& P, int fd, const SnapSection& sec, std::vector<T>& host, T*& dev, uint64_t* d_sum,
-                          T none = T(0)) {
+static int snap_load_column(vrod_index* idx, SnapPipe& P, int fd, const SnapSection& sec, RowColumn<T>& col, uint64_t* d_sum) {
     hipStream_t s = idx->stream;
-    T* d = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, idx->capacity * sizeof(T)));
-    dev = d;   // (the handle owns it from here: a failure below is followed by vrod_index_destroy)
-    HIP_TRY(hipMemsetAsync(d, none == T(0) ? 0 : 0xFF, idx->capacity * sizeof(T), s));
-    host.assign(idx->capacity, none);
+    HIP_TRY(col.dev.alloc(idx->capacity * sizeof(T)));
+    HIP_TRY(hipMemsetAsync(col.dev.p, col.fill_byte(), idx->capacity * sizeof(T), s));
+    col.host.assign(idx->capacity, col.none);
     VROD_TRY(snap_stream_in(P, fd, sec.offset, sec.bytes, P.bytes / 8 * 8, [&](uint64_t off, uint64_t n, int b) -> int {
-        memcpy((char*)host.data() + off, P.host[b], n);
-        HIP_TRY(hipMemcpyAsync((char*)d + off, P.host[b], n, hipMemcpyHostToDevice, s));
+        memcpy((char*)col.host.data() + off, P.host[b], n);
+        HIP_TRY(hipMemcpyAsync(col.dev.template get<char>() + off, P.host[b], n, hipMemcpyHostToDevice, s));
         return VROD_OK;
     }));
-    launch_snapshot_checksum(d, sec.bytes, 0, d_sum + sec.kind, s);
+    launch_snapshot_checksum(col.dev.p, sec.bytes, 0, d_sum + sec.kind, s);
     HIP_TRY(hipGetLastError());
     return VROD_OK;
 }
@@ -4272,7 +4250,7 @@ static int snap_load_body(vrod_index* idx, int fd, const char* path, const SnapH
 
     const uint64_t chunk = snap_chunk_rows_now(idx, count);
     const size_t stage = snap_stage_bytes(idx, chunk);
-    uint64_t* d_sum = (uint64_t*)(idx->flags + kSnapSumWord);
+    uint64_t* d_sum = (uint64_t*)(idx->flags.p + kSnapSumWord);
     uint64_t h_sum[SNAP_KIND_END] = {};
     {
         SnapPipe P;
@@ -4287,22 +4265,24 @@ static int snap_load_body(vrod_index* idx, int fd, const char* path, const SnapH
             VROD_TRY(P.mark(b, 0));
             HIP_TRY(hipMemcpyAsync(dense, P.host[b], round_up(n, 4), hipMemcpyHostToDevice, s));
             VROD_TRY(P.mark(b, 1));
-            launch_snapshot_unpack(dense, m, idx->dim, idx->ld, idx->dtype, (char*)idx->corpus + r0 * idx->row_bytes(), off / 4,
+            launch_snapshot_unpack(dense, m, idx->dim, idx->ld, idx->dtype, (char*)idx->corpus.p + r0 * idx->row_bytes(), off / 4,
                                    d_sum + SNAP_ROWS, s);
             HIP_TRY(hipGetLastError());
             return P.mark(b, 2);
         }));
         const SnapSection* norms = h.find(SNAP_NORMS);
         VROD_TRY(snap_stream_in(P, fd, norms->offset, norms->bytes, stage / 4 * 4, [&](uint64_t off, uint64_t n, int b) -> int {
-            HIP_TRY(hipMemcpyAsync((char*)idx->xnorm2 + off, P.host[b], n, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync((char*)idx->xnorm2.p + off, P.host[b], n, hipMemcpyHostToDevice, s));
             return VROD_OK;
         }));
-        launch_snapshot_checksum(idx->xnorm2, norms->bytes, 0, d_sum + SNAP_NORMS, s);
+        launch_snapshot_checksum(idx->xnorm2.p, norms->bytes, 0, d_sum + SNAP_NORMS, s);
         HIP_TRY(hipGetLastError());
-        if (const SnapSection* sec = h.find(SNAP_LABELS)) VROD_TRY(snap_load_side(idx, P, fd, *sec, idx->lab_bits, idx->lab_dev, d_sum));
-        if (const SnapSection* sec = h.find(SNAP_TAGS)) VROD_TRY(snap_load_side(idx, P, fd, *sec, idx->tag_bits, idx->tag_dev, d_sum));
-        if (const SnapSection* sec = h.find(SNAP_VALUES)) VROD_TRY(snap_load_side(idx, P, fd, *sec, idx->val_bits, idx->val_dev, d_sum));
-        if (const SnapSection* sec = h.find(SNAP_KEYS)) VROD_TRY(snap_load_side(idx, P, fd, *sec, idx->key_bits, idx->key_dev, d_sum, kKeyNone));
+        int col_rc = VROD_OK;
+        for_each_column(idx, [&](auto& c, int) {
+            const SnapSection* sec = h.find(c.snap_kind);
+            if (sec && col_rc == VROD_OK) col_rc = snap_load_column(idx, P, fd, *sec, c, d_sum);
+        });
+        VROD_TRY(col_rc);
         HIP_TRY(hipMemcpyAsync(idx->max_xn2_bits, &h.max_xn2_bits, 4, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(h_sum, d_sum, sizeof h_sum, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -4316,8 +4296,8 @@ static int snap_load_body(vrod_index* idx, int fd, const char* path, const SnapH
     }
     idx->count = count;
     if (n_deleted) {
-        HIP_TRY(hipMalloc((void**)&idx->del_dev, idx->del_bits.size() * 4));
-        HIP_TRY(hipMemcpy(idx->del_dev, idx->del_bits.data(), idx->del_bits.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(idx->del_dev.alloc(idx->del_bits.size() * 4));
+        HIP_TRY(hipMemcpy(idx->del_dev.p, idx->del_bits.data(), idx->del_bits.size() * 4, hipMemcpyHostToDevice));
         idx->n_deleted = n_deleted;
         mask_changed(idx);
     }
@@ -4329,8 +4309,8 @@ static int snap_load_body(vrod_index* idx, int fd, const char* path, const SnapH
     }
     // the key table is not in the file: it is built from the key column and the deleted-row bits, which is also the
     // check that no two live rows of the file share a key
-    if (idx->key_dev) {
-        for (uint64_t r = 0; r < count; ++r) idx->keyed_live += idx->key_bits[r] != kKeyNone && !bit_of(idx->del_bits.data(), r);
+    if (idx->keys.exists()) {
+        for (uint64_t r = 0; r < count; ++r) idx->keyed_live += idx->keys.host[r] != kKeyNone && !bit_of(idx->del_bits.data(), r);
         bool dup = false;
         VROD_TRY(keys_rebuild(idx, idx->keyed_live, false, "vrod_index_load", &dup));
         if (dup) return fail(VROD_ERR_CORRUPT, "%s: two live rows hold the same key", path);
@@ -4403,13 +4383,13 @@ int vrod_index_create(vrod_index** out, uint32_t dim, int dtype, int metric, con
     do {
         if (hipSetDevice(dev) != hipSuccess) { rc = fail(VROD_ERR_HIP, "hipSetDevice failed"); break; }
         if (hipStreamCreateWithFlags(&idx->stream, hipStreamNonBlocking) != hipSuccess) { rc = fail(VROD_ERR_HIP, "hipStreamCreate failed"); break; }
-        if (hipMalloc((void**)&idx->flags, 8192) != hipSuccess) { rc = fail(VROD_ERR_OUT_OF_MEMORY, "hipMalloc failed"); break; }
-        if (hipMemset(idx->flags, 0, 8192) != hipSuccess) { rc = fail(VROD_ERR_HIP, "hipMemset failed"); break; }
-        idx->max_xn2_bits = idx->flags + 8;
+        if (idx->flags.alloc(8192) != hipSuccess) { rc = fail(VROD_ERR_OUT_OF_MEMORY, "hipMalloc failed"); break; }
+        if (hipMemset(idx->flags.p, 0, 8192) != hipSuccess) { rc = fail(VROD_ERR_HIP, "hipMemset failed"); break; }
+        idx->max_xn2_bits = idx->flags.p + 8;
         for (Pending& P : idx->slot) {
             if (hipStreamCreateWithFlags(&P.stream, hipStreamNonBlocking) != hipSuccess) { rc = fail(VROD_ERR_HIP, "hipStreamCreate failed"); break; }
-            if (hipMalloc((void**)&P.flags, kSlotFlagBytes) != hipSuccess) { rc = fail(VROD_ERR_OUT_OF_MEMORY, "hipMalloc failed"); break; }
-            if (hipMemset(P.flags, 0, kSlotFlagBytes) != hipSuccess) { rc = fail(VROD_ERR_HIP, "hipMemset failed"); break; }
+            if (P.flags.alloc(kSlotFlagBytes) != hipSuccess) { rc = fail(VROD_ERR_OUT_OF_MEMORY, "hipMalloc failed"); break; }
+            if (hipMemset(P.flags.p, 0, kSlotFlagBytes) != hipSuccess) { rc = fail(VROD_ERR_HIP, "hipMemset failed"); break; }
             if (hipEventCreateWithFlags(&P.done, hipEventDisableTiming) != hipSuccess ||
                 hipEventCreateWithFlags(&P.scans_done, hipEventDisableTiming) != hipSuccess ||
                 hipEventCreateWithFlags(&P.mid_done, hipEventDisableTiming) != hipSuccess) { rc = fail(VROD_ERR_HIP, "hipEventCreate failed"); break; }
@@ -4449,7 +4429,6 @@ int vrod_index_destroy(vrod_index* idx) {
     for (Pending& P : idx->slot)
         if (P.stream) (void)hipStreamSynchronize(P.stream);
     for (Pending& P : idx->slot) {
-        if (P.flags) (void)hipFree(P.flags);
         if (P.stream) (void)hipStreamDestroy(P.stream);
         if (P.gexec) (void)hipGraphExecDestroy(P.gexec);
         for (hipEvent_t e : P.ev) (void)hipEventDestroy(e);
@@ -4460,18 +4439,6 @@ int vrod_index_destroy(vrod_index* idx) {
     }
     for (auto& T : idx->tail_ev) { if (T.start) (void)hipEventDestroy(T.start); if (T.stop) (void)hipEventDestroy(T.stop); }
     if (idx->caller_ev) (void)hipEventDestroy(idx->caller_ev);
-    if (idx->corpus) (void)hipFree(idx->corpus);
-    if (idx->planes) (void)hipFree(idx->planes);
-    if (idx->xnorm2) (void)hipFree(idx->xnorm2);
-    if (idx->del_dev) (void)hipFree(idx->del_dev);
-    if (idx->eff_dev) (void)hipFree(idx->eff_dev);
-    if (idx->lab_dev) (void)hipFree(idx->lab_dev);
-    if (idx->tag_dev) (void)hipFree(idx->tag_dev);
-    if (idx->val_dev) (void)hipFree(idx->val_dev);
-    if (idx->key_dev) (void)hipFree(idx->key_dev);
-    if (idx->ktab.slot_key) (void)hipFree(idx->ktab.slot_key);
-    if (idx->ktab.slot_row) (void)hipFree(idx->ktab.slot_row);
-    if (idx->flags) (void)hipFree(idx->flags);
     if (idx->stream) (void)hipStreamDestroy(idx->stream);
     delete idx;
     return VROD_OK;
@@ -4615,7 +4582,7 @@ int vrod_index_update_device(vrod_index* idx, const uint64_t* d_ids, const void*
 // Rows [first, first + m) of a single-device handle (or shard) as fp32 at d_out, out_stride floats apart.
 static int get_rows_to_device(vrod_index* idx, uint64_t first, uint64_t m, float* d_out, uint64_t out_stride, int out_device) {
     VROD_TRY(set_device(idx));
-    const char* rows = (const char*)idx->corpus + first * idx->row_bytes();
+    const char* rows = (const char*)idx->corpus.p + first * idx->row_bytes();
     if (out_device == idx->device && !ingest_force_stage()) {
         launch_rows_get_strided(rows, idx->dtype, m, idx->dim, idx->ld, d_out, out_stride, idx->stream);
         HIP_TRY(hipGetLastError());
@@ -4697,7 +4664,7 @@ int vrod_index_get_rows(vrod_index* idx, uint64_t first, uint64_t n, float* out_
     VROD_TRY(require_idle(idx, "vrod_index_get_rows"));
     VROD_TRY(set_device(idx));
     VROD_TRY(idx->raw_stage.ensure(n * idx->dim * 4));
-    launch_rows_get((const char*)idx->corpus + first * idx->row_bytes(), idx->dtype, n, idx->dim, idx->ld, idx->raw_stage.as<float>(), idx->stream);
+    launch_rows_get((const char*)idx->corpus.p + first * idx->row_bytes(), idx->dtype, n, idx->dim, idx->ld, idx->raw_stage.as<float>(), idx->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out_rows, idx->raw_stage.p, n * idx->dim * 4, hipMemcpyDeviceToHost, idx->stream));
     HIP_TRY(hipStreamSynchronize(idx->stream));
@@ -4867,34 +4834,48 @@ int vrod_search(vrod_index* idx, const float* queries, uint32_t nq, uint32_t k, 
 }
 
 
-int vrod_index_set_labels(vrod_index* idx, uint64_t first_id, const uint32_t* labels, uint64_t n) {
-    if (!idx || (!labels && n)) return fail(VROD_ERR_INVALID_ARG, "null argument");
-    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "vrod_index_set_labels on a multi-device handle: labels are not routed to the shards");
-    VROD_TRY(require_idle(idx, "vrod_index_set_labels"));
-    VROD_TRY(check_id_range(idx, first_id, n));
+extern "C++" {   // (templates, inside the C entry points' block)
+// What setting or getting a range of a row column (labels, tags, values, keys) starts with, in this order; the caller
+// returns early on n == 0.  `ptr`: the words to set or the place for the words got; for_set: a set is refused on a
+// composite handle and needs an idle one, a get reads the host mirror and needs neither.
+static int check_column_args(vrod_index* idx, const char* what, const char* noun, const void* ptr, uint64_t first_id, uint64_t n, bool for_set) {
+    if (!idx || (!ptr && n)) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    if (for_set) {
+        if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "%s on a multi-device handle: %s are not routed to the shards", what, noun);
+        VROD_TRY(require_idle(idx, what));
+    }
+    return check_id_range(idx, first_id, n);
+}
+// rows [r0, r0 + n) of a checked range take src[0 .. n); the first set of the handle makes the column
+template <typename T>
+static int column_write(vrod_index* idx, RowColumn<T>& col, uint64_t r0, const T* src, uint64_t n) {
     if (!n) return VROD_OK;
     VROD_TRY(set_device(idx));
-    const uint64_t r0 = first_id - idx->id_offset;
-    if (!idx->lab_dev) {   // the first labels of the handle: every row carries 0 so far
-        uint32_t* d = nullptr;
-        HIP_TRY(hipMalloc((void**)&d, idx->capacity * 4));
-        const hipError_t e = hipMemset(d, 0, idx->capacity * 4);
-        if (e != hipSuccess) { (void)hipFree(d); return fail(VROD_ERR_HIP, "clearing the row labels: %s", hipGetErrorString(e)); }
-        idx->lab_dev = d;
-        idx->lab_bits.assign(idx->capacity, 0u);
-    }
-    idx->doc_valid = false;
-    HIP_TRY(hipMemcpy(idx->lab_dev + r0, labels, n * 4, hipMemcpyHostToDevice));
-    std::copy(labels, labels + n, idx->lab_bits.begin() + r0);
+    if (!col.exists()) VROD_TRY(col.create(idx->capacity));
+    return col.set(r0, src, n);
+}
+template <typename T>
+static int column_set(vrod_index* idx, RowColumn<T>& col, const char* what, uint64_t first_id, const T* src, uint64_t n) {
+    VROD_TRY(check_column_args(idx, what, col.noun, src, first_id, n, true));
+    return column_write(idx, col, first_id - idx->id_offset, src, n);
+}
+template <typename T>
+static int column_get(vrod_index* idx, const RowColumn<T>& col, uint64_t first_id, uint64_t n, T* out) {
+    VROD_TRY(check_column_args(idx, nullptr, nullptr, out, first_id, n, false));
+    for (uint64_t i = 0; i < n; ++i) out[i] = col.get(first_id - idx->id_offset + i);   // (the host mirror is the truth)
     return VROD_OK;
+}
+}  // extern "C++"
+
+int vrod_index_set_labels(vrod_index* idx, uint64_t first_id, const uint32_t* labels, uint64_t n) {
+    VROD_TRY(check_column_args(idx, "vrod_index_set_labels", "labels", labels, first_id, n, true));
+    if (n) idx->doc_valid = false;
+    return column_write(idx, idx->labels, first_id - idx->id_offset, labels, n);
 }
 
 int vrod_index_get_labels(vrod_index* idx, uint64_t first_id, uint64_t n, uint32_t* out_labels) {
-    if (!idx || (!out_labels && n)) return fail(VROD_ERR_INVALID_ARG, "null argument");
-    VROD_TRY(check_id_range(idx, first_id, n));
-    const uint64_t r0 = first_id - idx->id_offset;
-    for (uint64_t i = 0; i < n; ++i) out_labels[i] = idx->lab_bits.empty() ? 0u : idx->lab_bits[r0 + i];   // (the host mirror is the truth)
-    return VROD_OK;
+    if (!idx) return fail(VROD_ERR_INVALID_ARG, "null argument");
+    return column_get(idx, idx->labels, first_id, n, out_labels);
 }
 
 static int check_labeled_args(vrod_index* idx, const void* q, uint32_t nq, uint32_t k, const void* labels, const void* oi, const void* os) {
@@ -4920,60 +4901,25 @@ int vrod_search_labeled_device(vrod_index* idx, const float* d_queries, uint32_t
     return labeled_search(idx, d_queries, nq, k, labels.data(), d_out_ids, d_out_scores);
 }
 
-extern "C++" {   // (templates, inside the C entry points' block)
-// A per-row side array of 64-bit words (tags, values, keys): host mirror and device copy allocated at the first set, 0 until
-// then.  set: the rows with ids [first_id, first_id + n) take src[0 .. n); get: the host mirror is the truth.
-template <typename T>
-static int side_array_set(vrod_index* idx, const char* what, const char* noun, uint64_t first_id, const T* src, uint64_t n, std::vector<T>& host,
-                          T*& dev, T none = T(0)) {
-    static_assert(sizeof(T) == 8, "tags and values are 64-bit words");
-    if (!src && n) return fail(VROD_ERR_INVALID_ARG, "null argument");
-    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "%s on a multi-device handle: %s are not routed to the shards", what, noun);
-    VROD_TRY(require_idle(idx, what));
-    VROD_TRY(check_id_range(idx, first_id, n));
-    if (!n) return VROD_OK;
-    VROD_TRY(set_device(idx));
-    const uint64_t r0 = first_id - idx->id_offset;
-    if (!dev) {   // the first of the handle: every row carries `none` (0, or every bit set) so far
-        T* d = nullptr;
-        HIP_TRY(hipMalloc((void**)&d, idx->capacity * 8));
-        const hipError_t e = hipMemset(d, none == T(0) ? 0 : 0xFF, idx->capacity * 8);
-        if (e != hipSuccess) { (void)hipFree(d); return fail(VROD_ERR_HIP, "clearing the row %s: %s", noun, hipGetErrorString(e)); }
-        dev = d;
-        host.assign(idx->capacity, none);
-    }
-    HIP_TRY(hipMemcpy(dev + r0, src, n * 8, hipMemcpyHostToDevice));
-    std::copy(src, src + n, host.begin() + r0);
-    return VROD_OK;
-}
-template <typename T>
-static int side_array_get(vrod_index* idx, uint64_t first_id, uint64_t n, const std::vector<T>& host, T* out, T none = T(0)) {
-    if (!out && n) return fail(VROD_ERR_INVALID_ARG, "null argument");
-    VROD_TRY(check_id_range(idx, first_id, n));
-    const uint64_t r0 = first_id - idx->id_offset;
-    for (uint64_t i = 0; i < n; ++i) out[i] = host.empty() ? none : host[r0 + i];
-    return VROD_OK;
-}
-}  // extern "C++"
 
 int vrod_index_set_tags(vrod_index* idx, uint64_t first_id, const uint64_t* tags, uint64_t n) {
     if (!idx) return fail(VROD_ERR_INVALID_ARG, "null argument");
-    return side_array_set(idx, "vrod_index_set_tags", "tags", first_id, tags, n, idx->tag_bits, idx->tag_dev);
+    return column_set(idx, idx->tags, "vrod_index_set_tags", first_id, tags, n);
 }
 
 int vrod_index_get_tags(vrod_index* idx, uint64_t first_id, uint64_t n, uint64_t* out_tags) {
     if (!idx) return fail(VROD_ERR_INVALID_ARG, "null argument");
-    return side_array_get(idx, first_id, n, idx->tag_bits, out_tags);
+    return column_get(idx, idx->tags, first_id, n, out_tags);
 }
 
 int vrod_index_set_values(vrod_index* idx, uint64_t first_id, const int64_t* values, uint64_t n) {
     if (!idx) return fail(VROD_ERR_INVALID_ARG, "null argument");
-    return side_array_set(idx, "vrod_index_set_values", "values", first_id, values, n, idx->val_bits, idx->val_dev);
+    return column_set(idx, idx->values, "vrod_index_set_values", first_id, values, n);
 }
 
 int vrod_index_get_values(vrod_index* idx, uint64_t first_id, uint64_t n, int64_t* out_values) {
     if (!idx) return fail(VROD_ERR_INVALID_ARG, "null argument");
-    return side_array_get(idx, first_id, n, idx->val_bits, out_values);
+    return column_get(idx, idx->values, first_id, n, out_values);
 }
 
 // ------------------------------------------------------------------ row keys
@@ -4990,7 +4936,7 @@ static int keys_set_range(vrod_index* idx, const char* what, uint64_t r0, const 
     for (uint64_t i = 0; i < n; ++i) {
         if (bit_of(del, r0 + i)) continue;
         if (keys[i] != kKeyNone) live_keys.push_back(keys[i]);
-        if (idx->key_dev) had += idx->key_bits[r0 + i] != kKeyNone;
+        if (idx->keys.exists()) had += idx->keys.host[r0 + i] != kKeyNone;
     }
     const uint64_t incoming = live_keys.size();
     VROD_TRY(set_device(idx));
@@ -5003,7 +4949,7 @@ static int keys_set_range(vrod_index* idx, const char* what, uint64_t r0, const 
             VROD_TRY(idx->host_args.ensure(n * 8));
             HIP_TRY(hipMemcpyAsync(idx->host_args.p, keys, n * 8, hipMemcpyHostToDevice, idx->stream));
             HIP_TRY(hipMemsetAsync(key_ctr(idx), 0, sizeof(KeyCounters), idx->stream));
-            launch_keys_check(idx->ktab, idx->key_dev, idx->del_dev, idx->count, idx->host_args.as<uint64_t>(), r0, n, key_ctr(idx), idx->stream);
+            launch_keys_check(idx->ktab, idx->keys.d(), idx->del_dev.p, idx->count, idx->host_args.as<uint64_t>(), r0, n, key_ctr(idx), idx->stream);
             HIP_TRY(hipGetLastError());
             KeyCounters c{};
             VROD_TRY(keys_take_counters(idx, what, c));
@@ -5014,24 +4960,21 @@ static int keys_set_range(vrod_index* idx, const char* what, uint64_t r0, const 
     const bool rebuild = first || key_needs_rebuild(idx->key_occupied, incoming, idx->ktab.slots);
     const uint64_t sized_for = idx->keyed_live + incoming;   // the live keyed rows plus the incoming keys
     if (rebuild) VROD_TRY(keys_table_clear(idx, sized_for));
-    VROD_TRY(side_array_set(idx, what, "keys", r0 + idx->id_offset, keys, n, idx->key_bits, idx->key_dev, (uint64_t)kKeyNone));
+    VROD_TRY(column_write(idx, idx->keys, r0, keys, n));
     idx->keyed_live = idx->keyed_live - had + incoming;
     if (rebuild) return keys_rebuild(idx, sized_for, !first, what);
     return keys_insert(idx, r0, n, what);
 }
 
 int vrod_index_set_keys(vrod_index* idx, uint64_t first_id, const uint64_t* keys, uint64_t n) {
-    if (!idx || (!keys && n)) return fail(VROD_ERR_INVALID_ARG, "null argument");
-    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "vrod_index_set_keys %s", kKeysNotRouted);
-    VROD_TRY(require_idle(idx, "vrod_index_set_keys"));
-    VROD_TRY(check_id_range(idx, first_id, n));
+    VROD_TRY(check_column_args(idx, "vrod_index_set_keys", "keys", keys, first_id, n, true));
     if (!n) return VROD_OK;
     return keys_set_range(idx, "vrod_index_set_keys", first_id - idx->id_offset, keys, n, true);
 }
 
 int vrod_index_get_keys(vrod_index* idx, uint64_t first_id, uint64_t n, uint64_t* out_keys) {
     if (!idx) return fail(VROD_ERR_INVALID_ARG, "null argument");
-    return side_array_get(idx, first_id, n, idx->key_bits, out_keys, (uint64_t)kKeyNone);
+    return column_get(idx, idx->keys, first_id, n, out_keys);
 }
 
 // what the four lookups start with; a null pointer is fine while n == 0
@@ -5044,13 +4987,13 @@ static int check_lookup_args(vrod_index* idx, const char* what, const void* in, 
 // d_keys[0, n) -> d_out_ids, on the handle's stream, complete on return.  A handle without keys answers with a fill.
 static int keys_find_on_device(vrod_index* idx, const char* what, const uint64_t* d_keys, uint64_t n, uint64_t* d_out_ids) {
     hipStream_t s = idx->stream;
-    if (!idx->key_dev) {
+    if (!idx->keys.exists()) {
         HIP_TRY(hipMemsetAsync(d_out_ids, 0xFF, n * 8, s));
         HIP_TRY(hipStreamSynchronize(s));
         return VROD_OK;
     }
     HIP_TRY(hipMemsetAsync(key_ctr(idx), 0, sizeof(KeyCounters), s));
-    launch_keys_find(idx->ktab, idx->key_dev, idx->del_dev, idx->count, idx->id_offset, d_keys, n, d_out_ids, key_ctr(idx), s);
+    launch_keys_find(idx->ktab, idx->keys.d(), idx->del_dev.p, idx->count, idx->id_offset, d_keys, n, d_out_ids, key_ctr(idx), s);
     HIP_TRY(hipGetLastError());
     KeyCounters c{};
     VROD_TRY(keys_take_counters(idx, what, c));
@@ -5063,7 +5006,7 @@ static int keys_find_on_device(vrod_index* idx, const char* what, const uint64_t
 
 // the host form's body, also the first step of vrod_index_delete_keys and vrod_index_upsert
 static int keys_find_host(vrod_index* idx, const char* what, const uint64_t* keys, uint64_t n, uint64_t* out_ids) {
-    if (!idx->key_dev) { std::fill(out_ids, out_ids + n, (uint64_t)kKeyNone); return VROD_OK; }
+    if (!idx->keys.exists()) { std::fill(out_ids, out_ids + n, (uint64_t)kKeyNone); return VROD_OK; }
     VROD_TRY(set_device(idx));
     VROD_TRY(idx->host_args.ensure(n * 8));
     VROD_TRY(idx->out_ids.ensure(n * 8));
@@ -5089,8 +5032,8 @@ int vrod_index_find_keys_device(vrod_index* idx, const uint64_t* d_keys, uint64_
 int vrod_index_ids_to_keys(vrod_index* idx, const uint64_t* ids, uint64_t n, uint64_t* out_keys) {
     VROD_TRY(check_lookup_args(idx, "vrod_index_ids_to_keys", ids, n, out_keys));
     for (uint64_t i = 0; i < n; ++i) {   // the host mirror is the truth
-        const bool row = idx->key_dev && ids[i] != kKeyNone && ids[i] >= idx->id_offset && ids[i] - idx->id_offset < idx->count;
-        out_keys[i] = row ? idx->key_bits[ids[i] - idx->id_offset] : (uint64_t)kKeyNone;
+        const bool row = idx->keys.exists() && ids[i] != kKeyNone && ids[i] >= idx->id_offset && ids[i] - idx->id_offset < idx->count;
+        out_keys[i] = row ? idx->keys.host[ids[i] - idx->id_offset] : (uint64_t)kKeyNone;
     }
     return VROD_OK;
 }
@@ -5099,8 +5042,8 @@ int vrod_index_ids_to_keys_device(vrod_index* idx, const uint64_t* d_ids, uint64
     VROD_TRY(check_lookup_args(idx, "vrod_index_ids_to_keys_device", d_ids, n, d_out_keys));
     if (!n) return VROD_OK;
     VROD_TRY(begin_sync_device(idx, "vrod_index_ids_to_keys_device", stream));
-    if (!idx->key_dev) HIP_TRY(hipMemsetAsync(d_out_keys, 0xFF, n * 8, idx->stream));
-    else launch_keys_translate(idx->key_dev, idx->count, idx->id_offset, d_ids, n, d_out_keys, idx->stream);
+    if (!idx->keys.exists()) HIP_TRY(hipMemsetAsync(d_out_keys, 0xFF, n * 8, idx->stream));
+    else launch_keys_translate(idx->keys.d(), idx->count, idx->id_offset, d_ids, n, d_out_keys, idx->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(idx->stream));
     return VROD_OK;
