@@ -1,14 +1,16 @@
 """What it costs to get rows that are in GPU memory into a handle: vrod_index_add from host memory (what a caller with an
 encoder's output on the GPU had to do, less the cast and the copy to the host, which are not timed) against
 vrod_index_add_device from an fp32, a bf16 and an fp16 tensor, on a bf16 cosine handle and on an fp32 L2 handle, in one
-process; then vrod_index_update against vrod_index_update_device on --update rows.
+process; then vrod_index_update against vrod_index_update_device on --update rows, and vrod_index_add_synthetic of
+--rows rows.  --host-only leaves the device sources out: the host forms alone, for a comparison of two builds of the
+library (VROD_HIP_LIB names the one to load).
 
 Clocks: the host's perf_counter around whole calls; every call timed here is synchronous and returns after a stream
 synchronise.  Each handle is reserved for its rows first (no growth inside the timed call), each shape runs once untimed
 on a small handle, then the median of --reps runs, each on a fresh handle.  "GB/s" is the source's bytes (rows x dim x
 element size) over the call's time.  One JSON line per measurement in <out>/ingest_probe_<rows>x<dim>.jsonl.
 
-    python scripts/probes/ingest_probe.py [--rows 1000000] [--dim 768] [--update 65536] [--reps 3] [--out profiles/ingest]
+    python scripts/probes/ingest_probe.py [--rows 1000000] [--dim 768] [--update 65536] [--reps 3] [--host-only] [--out profiles/ingest]
 """
 import argparse
 import json
@@ -27,6 +29,7 @@ def main():
     ap.add_argument("--dim", type=int, default=768)
     ap.add_argument("--update", type=int, default=65536)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--host-only", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ingest"))
     a = ap.parse_args()
     import torch
@@ -42,8 +45,10 @@ def main():
     n, dim, m = a.rows, a.dim, a.update
     torch.manual_seed(1)
     src = {"f32": torch.randn((n, dim), device="cuda")}
-    src["bf16"] = src["f32"].to(torch.bfloat16)
-    src["f16"] = src["f32"].to(torch.float16)
+    if not a.host_only:
+        src["bf16"] = src["f32"].to(torch.bfloat16)
+        src["f16"] = src["f32"].to(torch.float16)
+    whats = ("host",) + (() if a.host_only else tuple(src))
     host = src["f32"].cpu().numpy()
     ids = torch.randperm(n, device="cuda")[:m].contiguous()
     host_ids = ids.cpu().numpy()
@@ -66,9 +71,10 @@ def main():
             for t in src.values():
                 ix.add_device(t[:4096])
             ix.update(host_ids[:64] % 4096, host[:64])
-            ix.update_device(ids[:64] % 4096, src["bf16"][:64])
+            ix.update_device(ids[:64] % 4096, src["f32"][:64])
+            ix.add_synthetic(1, 0, 4096)
         add_host = None
-        for what in ("host", "f32", "bf16", "f16"):
+        for what in whats:
             times = []
             for _ in range(a.reps):
                 with fresh() as ix:
@@ -81,13 +87,18 @@ def main():
                    source_GBps=gb / s, vs_host_add=add_host / s, runs=times)
         with fresh() as ix:
             ix.add_device(src["f32"])
-            for what in ("host", "f32", "bf16", "f16"):
+            for what in whats:
                 times = [wall((lambda: ix.update(host_ids, host[:m])) if what == "host" else (lambda: ix.update_device(ids, src[what][:m])))
                          for _ in range(a.reps)]
                 s = statistics.median(times)
                 record(op="update" if what == "host" else "update_device", handle=f"{dtype}/{metric}", source=what, rows=m, dim=dim,
                        seconds=s, source_GBps=m * dim * (4 if what in ("host", "f32") else 2) / 1e9 / s, runs=times)
-    with open(os.path.join(a.out, f"ingest_probe_{label}x{dim}.jsonl"), "w") as f:
+        times = []
+        for _ in range(a.reps):
+            with fresh() as ix:
+                times.append(wall(lambda: ix.add_synthetic(1, 0, n)))
+        record(op="add_synthetic", handle=f"{dtype}/{metric}", source="synthetic", rows=n, dim=dim, seconds=statistics.median(times), runs=times)
+    with open(os.path.join(a.out, f"ingest_probe_{label}x{dim}{'_host' if a.host_only else ''}.jsonl"), "w") as f:
         for kw in lines:
             f.write(json.dumps(kw) + "\n")
     ok = all(x["seconds"] <= y["seconds"] for x in lines if x["op"] == "add_device" and x["source"] == "f32"

@@ -79,6 +79,23 @@ def check_bound(st, what):
         assert st["max_fast_err"] <= st["eps_bound"], f"{what}: {st}"
 
 
+# ---------------------------------------------------------------- rows that try the ingest
+def special_rows(n, dim, seed, src):
+    """Rows that try the conversion: normal values, rows scaled by 2^+-10, fp16 subnormals, +-65504, -0.0, a zero row."""
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((n, dim)).astype(np.float32)
+    if n >= 16:
+        x[1] *= 1024.0
+        x[2] /= 1024.0
+        x[3] = 0.0                                            # an all-zero row (stays zero under cosine)
+        x[4, ::2] = -0.0
+        x[5, : min(dim, 8)] = (np.arange(1, min(dim, 8) + 1) * 2.0 ** -24).astype(np.float32)   # fp16 subnormals
+        x[5, -1] = -(2.0 ** -24)
+        x[6, 0], x[6, -1] = 65504.0, -65504.0                # the largest fp16 values
+        x[7] = 1023 * 2.0 ** -24                              # the largest fp16 subnormal, a whole row
+    return x
+
+
 # ---------------------------------------------------------------- the oracle over a set of rows
 def prep_of(metric):
     """How the oracle prepares rows and queries of a handle with `metric` (ip: the vectors as given, as l2)."""

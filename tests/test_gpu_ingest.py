@@ -1,13 +1,14 @@
 """GPU tests of the device-resident ingest: vrod_index_add_device, _update_device, _upsert_device, _get_rows_device.
 
-Truth is always a second handle (the twin) fed through the host forms with the widened fp32 rows; one case also goes
-against the CPU oracle directly.  Every comparison is bit for bit: get_rows, eps_bound and scan_bytes of the stats, a
+The host forms prepare their rows with the same kernel, so a second handle fed through them (the twin) is no independent
+truth for the stored rows: those are compared with the CPU oracle's prepare of the widened fp32 rows that both handles
+were given.  The twin stays the yardstick for everything above the rows: eps_bound and scan_bytes of the stats, a
 3-query and a 300-query search (the stream and the batched path, the planes of an fp32 handle included) and the bytes
-vrod_index_save writes."""
+vrod_index_save writes.  Every comparison is bit for bit."""
 import numpy as np
 import pytest
 
-from support import ID_NONE, O, THREADS, assert_same_all_bits, bits, oracle_over, va  # noqa: F401
+from support import ID_NONE, METRIC_COSINE, METRIC_L2, O, THREADS, assert_same_all_bits, bits, oracle_over, special_rows, va  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -33,22 +34,6 @@ def source(rows_f32, src, stride=None, offset=0, fill=0.0):
     return view, view.float().cpu().numpy()
 
 
-def special_rows(n, dim, seed, src):
-    """Rows that try the conversion: normal values, rows scaled by 2^+-10, fp16 subnormals, +-65504, -0.0, a zero row."""
-    rng = np.random.default_rng(seed)
-    x = rng.standard_normal((n, dim)).astype(np.float32)
-    if n >= 16:
-        x[1] *= 1024.0
-        x[2] /= 1024.0
-        x[3] = 0.0                                            # an all-zero row (stays zero under cosine)
-        x[4, ::2] = -0.0
-        x[5, : min(dim, 8)] = (np.arange(1, min(dim, 8) + 1) * 2.0 ** -24).astype(np.float32)   # fp16 subnormals
-        x[5, -1] = -(2.0 ** -24)
-        x[6, 0], x[6, -1] = 65504.0, -65504.0                # the largest fp16 values
-        x[7] = 1023 * 2.0 ** -24                              # the largest fp16 subnormal, a whole row
-    return x
-
-
 def queries(nq, dim, seed=99):
     return np.random.default_rng(seed).standard_normal((nq, dim)).astype(np.float32)
 
@@ -58,12 +43,16 @@ def snapshot(ix, path):
     return open(path, "rb").read()
 
 
-def assert_twins(ix, tw, tmp_path, what, nqs=(3, 300), k=10):
-    """The two handles cannot be told apart through the ABI."""
-    assert ix.count == tw.count and ix.live_count() == tw.live_count(), what
+def assert_twins(ix, tw, rows, O, tmp_path, what, nqs=(3, 300), k=10):
+    """The device-fed handle holds the oracle's prepare of `rows` (the widened fp32 rows both handles were given, row i
+    of them in row i of the handles), and the two handles cannot be told apart through the ABI."""
+    assert ix.count == tw.count == len(rows) and ix.live_count() == tw.live_count(), what
     n = ix.count
     if n:
-        assert np.array_equal(bits(ix.get_rows(0, n)), bits(tw.get_rows(0, n))), f"{what}: get_rows"
+        got = bits(ix.get_rows(0, n))
+        want = O.prepare(rows, ix.dtype, METRIC_COSINE if ix.metric == METRIC_COSINE else METRIC_L2, threads=THREADS)
+        assert np.array_equal(got, bits(want)), f"{what}: get_rows against the oracle"
+        assert np.array_equal(got, bits(tw.get_rows(0, n))), f"{what}: get_rows"
     for nq in nqs:
         q = queries(nq, ix.dim)
         kk = min(k, max(1, ix.live_count()))
@@ -83,7 +72,7 @@ def pair(va, dim, dtype, metric, **kw):
 
 # ---------------------------------------------------------------- add: shapes where the kernel can go wrong
 @pytest.mark.parametrize("dim,n", [(1, 70), (3, 70), (63, 70), (64, 70), (65, 70), (768, 300), (769, 70), (32768, 33), (64, 1)])
-def test_add_shapes_and_strides(va, tmp_path, dim, n):
+def test_add_shapes_and_strides(va, O, tmp_path, dim, n):
     """Every row width at which the loads or the work-group shape change (below, at and above a vector, a wave, the
     four-rows-per-group limit), each with row_stride = dim, dim + 1 and dim + 7 (rows on 4- and 2-byte boundaries only)."""
     raw = special_rows(n, dim, dim * 7 + n, "f32")
@@ -96,10 +85,11 @@ def test_add_shapes_and_strides(va, tmp_path, dim, n):
                 t, wide = source(raw, src, stride, offset, fill=float("nan"))   # NaN in the padding is never read
                 ix.add_device(t)
                 tw.add(wide)
-            assert_twins(ix, tw, tmp_path, f"dim {dim} {src}->{dtype}/{metric}", nqs=(3,) if dim == 32768 else (3, 300))
+            assert_twins(ix, tw, np.concatenate([wide] * 3), O, tmp_path, f"dim {dim} {src}->{dtype}/{metric}",
+                         nqs=(3,) if dim == 32768 else (3, 300))
 
 
-def test_add_column_slice_of_a_wider_tensor(va, tmp_path):
+def test_add_column_slice_of_a_wider_tensor(va, O, tmp_path):
     import torch
     dim, n = 96, 500
     for src in ("f32", "bf16", "f16"):
@@ -110,9 +100,10 @@ def test_add_column_slice_of_a_wider_tensor(va, tmp_path):
         with ix, tw:
             ix.add_device(t)
             ix.add_device(wide_t[::2, :dim])                   # every second row: stride(0) doubled
-            tw.add(t.float().cpu().numpy())
-            tw.add(wide_t[::2, :dim].float().cpu().numpy())
-            assert_twins(ix, tw, tmp_path, f"column slice {src}")
+            given = [t.float().cpu().numpy(), wide_t[::2, :dim].float().cpu().numpy()]
+            for g in given:
+                tw.add(g)
+            assert_twins(ix, tw, np.concatenate(given), O, tmp_path, f"column slice {src}")
 
 
 def test_add_crosses_a_staging_chunk(va, tmp_path, O):
@@ -124,20 +115,18 @@ def test_add_crosses_a_staging_chunk(va, tmp_path, O):
     with ix, tw:
         ix.add_device(t)
         tw.add(wide)
-        assert_twins(ix, tw, tmp_path, "two chunks")
+        assert_twins(ix, tw, wide, O, tmp_path, "two chunks")
         q = queries(7, dim)
         ids, sc = ix.search(q, 10)
         oi, osc = oracle_over(O, wide, q, 10, "bf16", "cosine", np.arange(n))
         assert_same_all_bits(ids, sc, oi, osc, "against the oracle")
-        pc = O.prepare(wide[:2000], 1, 0, threads=THREADS)     # and the stored rows are the oracle's prepared rows
-        assert np.array_equal(bits(ix.get_rows(0, 2000)), bits(pc))
 
 
 # ---------------------------------------------------------------- types
 @pytest.mark.parametrize("metric", ["cosine", "l2", "ip"])
 @pytest.mark.parametrize("dtype", ["bf16", "f32"])
 @pytest.mark.parametrize("src", ["f32", "bf16", "f16"])
-def test_types(va, tmp_path, src, dtype, metric):
+def test_types(va, O, tmp_path, src, dtype, metric):
     dim, n = 65, 1000
     raw = special_rows(n, dim, 11, src)
     t, wide = source(raw, src, dim + 3)
@@ -148,7 +137,7 @@ def test_types(va, tmp_path, src, dtype, metric):
     with ix, tw:
         ix.add_device(t)
         tw.add(wide)
-        assert_twins(ix, tw, tmp_path, f"{src}->{dtype}/{metric}")
+        assert_twins(ix, tw, wide, O, tmp_path, f"{src}->{dtype}/{metric}")
         rows = ix.get_rows(0, 8)
         assert not rows[3].any()                               # the zero row stayed zero
         assert np.signbit(rows[4, 0])                          # -0.0 kept its sign
@@ -200,7 +189,7 @@ def test_bad_values_refuse_and_change_nothing(va):
 
 # ---------------------------------------------------------------- update
 @pytest.mark.parametrize("dtype,metric,src", [("f32", "cosine", "bf16"), ("bf16", "ip", "f16"), ("f32", "l2", "f32")])
-def test_update(va, tmp_path, dtype, metric, src):
+def test_update(va, O, tmp_path, dtype, metric, src):
     import torch
     dim, n, m = 65, 3000, 700
     rng = np.random.default_rng(21)
@@ -217,7 +206,10 @@ def test_update(va, tmp_path, dtype, metric, src):
             h.search(queries(300, dim), 10)                    # a batched search: an fp32 handle has its planes now
         ix.update_device(d_ids, t)
         tw.update(ids, wide)
-        assert_twins(ix, tw, tmp_path, f"update {src}->{dtype}/{metric}")
+        now = raw.copy()
+        now[ids] = wide                                        # (numpy too lets the last of two assignments to a row win)
+        assert np.array_equal(now[ids[5]], wide[m // 2])
+        assert_twins(ix, tw, now, O, tmp_path, f"update {src}->{dtype}/{metric}")
         q = queries(3, dim)
         was = state_of(ix, q)
         for bad in (17, n, 2 ** 40):                           # a deleted row, out of range
@@ -229,7 +221,7 @@ def test_update(va, tmp_path, dtype, metric, src):
             assert_state(state_of(ix, q), was)
 
 
-def test_update_of_several_chunks_checks_every_row_first(va, tmp_path):
+def test_update_of_several_chunks_checks_every_row_first(va, O, tmp_path):
     import torch
     dim, n = 64, 65536 + 5
     raw = special_rows(n, dim, 30, "f32")
@@ -250,7 +242,7 @@ def test_update_of_several_chunks_checks_every_row_first(va, tmp_path):
         wide[n - 2, 7] = 0.5
         ix.update_device(d_ids, t)
         tw.update(d_ids.cpu().numpy(), wide)
-        assert_twins(ix, tw, tmp_path, "update over two chunks", nqs=(3,))
+        assert_twins(ix, tw, wide[::-1], O, tmp_path, "update over two chunks", nqs=(3,))
 
 
 # ---------------------------------------------------------------- upsert
@@ -263,7 +255,7 @@ def key_state(ix):
     return st
 
 
-def test_upsert(va, tmp_path):
+def test_upsert(va, O, tmp_path):
     import torch
     dim, n, m = 65, 2000, 600
     raw = special_rows(n, dim, 40, "f32")
@@ -287,7 +279,9 @@ def test_upsert(va, tmp_path):
         assert np.array_equal(got.cpu().numpy().view(np.uint64), want)
         assert key_state(ix) == key_state(tw)
         assert np.array_equal(ix.get_keys(0, ix.count), tw.get_keys(0, tw.count))
-        assert_twins(ix, tw, tmp_path, "upsert")
+        now = np.concatenate([raw, np.zeros((int((want >= n).sum()), dim), np.float32)])
+        now[want.astype(np.int64)] = wide                      # the call's row i lies in row want[i], held or appended
+        assert_twins(ix, tw, now, O, tmp_path, "upsert")
         was, kst = state_of(ix, q), key_state(ix)
         for bad in (int(keys[0]), int(ID_NONE)):               # a key twice, VROD_ID_NONE as a key
             bad_keys = keys.copy()
@@ -325,7 +319,7 @@ def test_get_rows_device(va, dtype):
 
 
 # ---------------------------------------------------------------- stream
-def test_source_produced_on_a_side_stream(va, tmp_path):
+def test_source_produced_on_a_side_stream(va, O, tmp_path):
     import torch
     dim, n = 768, 4000
     side = torch.cuda.Stream()
@@ -340,8 +334,9 @@ def test_source_produced_on_a_side_stream(va, tmp_path):
             t = t.to(torch.bfloat16)
             ix.add_device(t)
         side.synchronize()
-        tw.add(t.float().cpu().numpy())
-        assert_twins(ix, tw, tmp_path, "side stream", nqs=(3,))
+        given = t.float().cpu().numpy()
+        tw.add(given)
+        assert_twins(ix, tw, given, O, tmp_path, "side stream", nqs=(3,))
 
 
 # ---------------------------------------------------------------- multi-device rehearsal

@@ -1,6 +1,8 @@
-"""The host decisions of the device-resident ingest (vrod_amd/csrc/ingest_plan.h), checked on the host: a small driver is
-compiled with g++ against the real header.
+"""The host decisions of the ingest (vrod_amd/csrc/ingest_plan.h), checked on the host: a small driver is compiled with
+g++ against the real header.
 
+  - the row source of a call (host rows, the synthetic stream, device rows): what "from row `first` on" and "these rows
+    of it" make of each kind, and the gather of a picked host source into the dense chunk its upload sends;
   - layout validation: a stride below dim, n * row_stride (elements, bytes, end address) past 64 bits, a pointer that is
     not aligned to its element, an unknown element type; and which loads a pointer and pitch allow;
   - the chunk cuts of a call at n = chunk - 1, chunk, chunk + 1 (and around them), against the rule the host forms state;
@@ -22,6 +24,7 @@ OK, BAD_DTYPE, BAD_STRIDE, OVERFLOW, MISALIGNED = range(5)
 
 DRIVER = r'''
 #include <cstdio>
+#include <vector>
 #include "ingest_plan.h"
 using namespace vrod;
 
@@ -47,6 +50,35 @@ int main() {
             unsigned dim;
             scanf("%u", &dim);
             printf("G %u %u %llu\n", ingest_lds_pitch(dim), ingest_rows_per_group(dim), (unsigned long long)ingest_lds_bytes(dim));
+        } else if (what == 'F') {   // the source from row `first` on, per kind: first -> byte offset of p, stream row, list offset
+            unsigned long long first;
+            scanf("%llu", &first);
+            static const float host[4] = {0};
+            static const uint64_t list[4] = {0};
+            const RowSource src[4] = {rows_on_host(host, 5), rows_synthetic(9, 100), rows_on_device(host, SRC_F16, 7),
+                                      rows_picked(rows_on_device(host, SRC_F32, 7), list)};
+            printf("F");
+            for (const RowSource& s : src) {
+                const RowSource t = rows_from(s, first);
+                printf(" %d:%lld:%llu:%lld", (int)t.kind, (long long)((const char*)t.p - (const char*)s.p), (unsigned long long)t.first_row,
+                       t.pick ? (long long)(t.pick - list) : -1ll);
+            }
+            printf("\n");
+        } else if (what == 'P') {   // gather: dim stride m pick[m], over host rows with element j of row i = 1000 i + j
+            unsigned dim, stride, m;
+            scanf("%u %u %u", &dim, &stride, &m);
+            std::vector<uint64_t> pick(m);
+            uint64_t top = 0;
+            for (uint64_t& x : pick) { unsigned long long v; scanf("%llu", &v); x = v; top = v > top ? v : top; }
+            std::vector<float> rows((top + 1) * stride, -1.0f), out((size_t)m * dim, -2.0f);
+            for (uint64_t i = 0; i <= top; ++i) for (unsigned j = 0; j < dim; ++j) rows[i * stride + j] = 1000.0f * i + j;
+            const RowSource s = rows_picked(rows_on_host(rows.data(), stride), pick.data());
+            rows_gather(s, dim, m, out.data());
+            printf("P");
+            for (uint64_t i = 0; i < m;) { const uint64_t run = pick_run(pick.data(), m, i); printf(" %llu", (unsigned long long)run); i += run; }
+            printf(" |");
+            for (float v : out) printf(" %g", v);
+            printf("\n");
         } else {                    // dealing: first n G -> pieces shard:global_first:local_first:rows
             unsigned long long first, n, G;
             scanf("%llu %llu %llu", &first, &n, &G);
@@ -120,6 +152,30 @@ def test_layout_validation(run):
     assert len(out) == len(cases)
     for (c, want), line in zip(cases, out):
         assert tuple(int(x) for x in line.split()[1:]) == want, (c, line)
+
+
+def test_row_source_from_and_picked(run):
+    out = run("F 0\nF 3\n")[1:]
+    # host fp32 rows of 5, the synthetic stream from row 100, fp16 device rows 7 apart, a picked device source
+    assert out[0].split()[1:] == ["0:0:0:-1", "1:0:100:-1", "2:0:0:-1", "2:0:0:0"]
+    assert out[1].split()[1:] == ["0:60:0:-1", "1:0:103:-1", "2:42:0:-1", "2:0:0:3"]   # a picked source moves along its list only
+
+
+def test_gather_of_a_picked_host_source(run):
+    cases = [(3, 3, [0]), (3, 3, [4, 5, 6]), (3, 3, [6, 5, 4]), (2, 3, [1, 2, 2, 3, 4, 9, 0, 1]), (1, 1, [7, 8, 2, 3, 4]), (5, 5, [2, 0, 1])]
+    out = run("".join(f"P {d} {st} {len(p)} {' '.join(map(str, p))}\n" for d, st, p in cases))[1:]
+    assert len(out) == len(cases)
+    for (dim, _, pick), line in zip(cases, out):
+        runs, vals = line[2:].split("|")
+        want_runs, i = [], 0
+        while i < len(pick):                                   # consecutive source rows travel as one copy
+            e = i + 1
+            while e < len(pick) and pick[e] == pick[e - 1] + 1:
+                e += 1
+            want_runs.append(e - i)
+            i = e
+        assert [int(x) for x in runs.split()] == want_runs, (pick, line)
+        assert [float(x) for x in vals.split()] == [1000.0 * r + j for r in pick for j in range(dim)], (pick, line)
 
 
 def chunk_rule(n, dim):

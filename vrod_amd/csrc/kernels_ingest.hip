@@ -1,18 +1,19 @@
-// kernels_ingest.hip -- the ingest of rows that are in device memory already (gfx950): vrod_index_add_device,
-// vrod_index_update_device, vrod_index_upsert_device, and vrod_index_get_rows_device on the way out.
+// kernels_ingest.hip -- rows in device memory become prepared rows (gfx950): every add, update and upsert, host or
+// _device form, and vrod_index_get_rows / _get_rows_device on the way out.
 //
-// The rows arrive typed (fp32, bf16 or fp16) and strided, e.g. a slice of an encoder's output tensor.  One kernel
-// family turns them into prepared rows (kernels_prep.hip's spec, prep_chain.h's arithmetic): the source is read from
-// HBM ONCE, coalesced, where the host forms' pair of kernels reads its staged copy twice and the first time one thread
-// per row.  Host decisions (which loads a pointer allows, rows per work-group, LDS) are ingest_plan.h's.
+// The rows arrive typed (fp32, bf16 or fp16) and strided: a slice of an encoder's output tensor for the _device forms,
+// the staged fp32 upload (or synthetic chunk) at stride dim for the host forms.  One kernel family turns them into
+// prepared rows (kernels_prep.hip's spec, prep_chain.h's arithmetic), reading the source from HBM ONCE, coalesced.
+// Host decisions (which loads a pointer allows, rows per work-group, LDS) are ingest_plan.h's.
 //
 //   COSINE     a wave (dim <= 4096: four rows per work-group) or the whole work-group (beyond) loads its row widened
-//              to fp32 into LDS, one thread walks the canonical fp64 chain over it (prep_chain_lds, the chain of
-//              prep_queries_kernel), and all of them write the row divided and rounded, padding zeroed.
+//              to fp32 into LDS, one thread per row walks the canonical fp64 chain over it (prep_chain_lds, the chain
+//              of prep_queries_kernel; a work-group's four chains in four lanes of one wave), and all of them write the
+//              row divided and rounded, padding zeroed.
 //   L2 / IP    no chain, no LDS: a streaming convert-check-write, a wave per row.
 //
 // LDS and occupancy: 4 rows x dim x 4 B is 12 KiB at dim 768, so the 2048 threads of a CU (8 work-groups) fit its 160 KiB
-// and the one-lane chains of 32 waves per CU hide behind each other and behind the loads of the next rows.
+// and the chains of 8 waves per CU hide behind each other and behind the loads of the next rows.
 #include "vrod_common.h"
 #include "vrod_kernels.h"
 #include "prep_chain.h"
@@ -138,7 +139,10 @@ __global__ __launch_bounds__(256) void ingest_rows_kernel(IngestArgs a) {
                 }
             }
             __syncthreads();
-            if (live && t == 0) s_nrm[g] = __builtin_sqrt(prep_chain_lds(row, a.dim));
+            // The chains of the group's rows walk side by side in the first lanes of ONE wave: a chain step takes a wave
+            // its fp64 issue slots whatever the number of lanes in it, and those slots are what bounds this kernel.
+            if (threadIdx.x < RPG && base + threadIdx.x < a.n)
+                s_nrm[threadIdx.x] = __builtin_sqrt(prep_chain_lds(lds + threadIdx.x * a.pitch, a.dim));
             __syncthreads();
             if (live) {
                 const double nrm = s_nrm[g];
@@ -179,7 +183,7 @@ __global__ __launch_bounds__(256) void ingest_pack_kernel(const E* __restrict__ 
 }
 
 // ------------------------------------------------------------------ stored rows -> fp32 rows at a pitch
-// rows_get_kernel (kernels_prep.hip) with a pitch on the way out; the padding between the rows is not written.
+// Stored rows widened back to fp32, out_stride (>= dim) floats apart; the padding between the rows is not written.
 template <typename T>
 __global__ __launch_bounds__(256) void rows_get_strided_kernel(const T* __restrict__ rows, uint64_t n, uint32_t dim, uint32_t ld,
                                                                float* __restrict__ out, uint64_t out_stride) {
@@ -201,13 +205,12 @@ static inline unsigned ingest_grid(uint64_t groups) {
 template <int SRC, bool NORMALISE, bool WIDE, int GS>
 static void launch_ingest_as(const IngestArgs& a, hipStream_t s) {
     const size_t lds = NORMALISE ? (size_t)(256 / GS) * a.pitch * sizeof(float) : 0;
-    static bool attr_set = false;
-    if (NORMALISE && GS == 256 && !attr_set) {   // one row of VROD_MAX_DIM floats is 128 KiB, beside the kernel's static words
-        if (hipFuncSetAttribute((const void*)ingest_rows_kernel<SRC, NORMALISE, WIDE, GS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                128 * 1024) != hipSuccess)
-            (void)hipGetLastError();   // (the launch reports what it cannot have)
-        attr_set = true;
-    }
+    // One row of VROD_MAX_DIM floats is 128 KiB, beside the kernel's static words.  A function attribute belongs to the
+    // current device, so it is set with every launch that needs it, not once per process.
+    if (lds > 64 * 1024 &&
+        hipFuncSetAttribute((const void*)ingest_rows_kernel<SRC, NORMALISE, WIDE, GS>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            128 * 1024) != hipSuccess)
+        (void)hipGetLastError();   // (the launch reports what it cannot have)
     const uint64_t rpg = 256 / GS;
     ingest_rows_kernel<SRC, NORMALISE, WIDE, GS><<<ingest_grid((a.n + rpg - 1) / rpg), 256, lds, s>>>(a);
 }

@@ -9,7 +9,7 @@
 namespace vrod {
 
 // ------------------------------------------------------------------ update: scatter prepared rows
-// staged[i] (prepared by launch_prepare_rows) becomes corpus row dst[i]; dst[i] == kScatterSkip leaves row i out (an
+// staged[i] (prepared by launch_ingest_rows) becomes corpus row dst[i]; dst[i] == kScatterSkip leaves row i out (an
 // id named again later in the same call: the last occurrence wins, and two waves never write one row).  Also the
 // row's fast squared norm -- the bits row_fastnorm_kernel gives the same row (vrod_common.h fastnorm_fold) -- folded
 // into the handle's maximum, and on an fp32 handle whose bf16 planes exist the [hi | lo] planes of the row, element

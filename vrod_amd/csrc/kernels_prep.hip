@@ -8,6 +8,9 @@
 // Spec (DESIGN.md "Scan spec", mirrored by oracle/vrod_oracle.c orc_prepare_row):
 //   COSINE: x / sqrt(sum x^2), the sum accumulated left to right in fp64, the divide in
 //   fp64, then rounded to fp32; zero rows stay zero.  BF16: round to nearest even.
+//
+// Here: the synthetic stream, the fast norms of stored rows, the query prepare and the bf16 split.  The prepare of the
+// rows themselves, for every add / update / upsert, is ingest_rows_kernel (kernels_ingest.hip).
 #include "vrod_common.h"
 #include "vrod_kernels.h"
 #include "prep_chain.h"   // the norm chain and the divide, shared with kernels_ingest.hip
@@ -42,55 +45,6 @@ __global__ __launch_bounds__(256) void synth_rows_kernel(uint64_t key, uint64_t 
     }
 }
 
-// ------------------------------------------------------------------ row norms (fp64, sequential)
-// One thread per row walks its row left to right: the accumulation order is the spec's.
-// v*v is exact in fp64 for fp32 v, so fma(v, v, ss) == ss + v*v rounded once.
-__global__ __launch_bounds__(256) void row_norm_kernel(const float* __restrict__ in, uint64_t n,
-                                                       uint32_t dim, double* __restrict__ nrm,
-                                                       uint32_t* __restrict__ bad_flag) {
-    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n) return;
-    const float* x = in + r * (uint64_t)dim;
-    double ss = 0.0;
-    bool bad = false;
-    for (uint32_t j = 0; j < dim; ++j) {
-        const float f = x[j];
-        bad |= prep_is_bad(f);
-        ss = prep_chain_step(f, ss);
-    }
-    nrm[r] = __builtin_sqrt(ss);
-    if (bad) atomicOr(bad_flag, 1u);
-}
-
-// ------------------------------------------------------------------ write prepared rows
-// Elementwise, coalesced: out[r][j] for j < ld (zero padding beyond dim).
-// NORMALISE: divide by the fp64 norm (0 -> zero row).  Emits fp32 and/or bf16 copies.
-template <bool NORMALISE>
-__global__ __launch_bounds__(256) void row_write_kernel(const float* __restrict__ in, uint64_t n,
-                                                        uint32_t dim, uint32_t ld,
-                                                        const double* __restrict__ nrm,
-                                                        int round_bf16,
-                                                        float* __restrict__ out_f32,
-                                                        bf16_t* __restrict__ out_bf16) {
-    const uint64_t total = n * (uint64_t)ld;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t r = i / ld;
-        const uint32_t j = (uint32_t)(i - r * ld);
-        float v = 0.0f;
-        if (j < dim) {
-            v = in[r * (uint64_t)dim + j];
-            if (NORMALISE) v = prep_scale(v, nrm[r]);
-        }
-        if (round_bf16) {
-            const bf16_t h = f32_to_bf16_rne(v);
-            if (out_bf16) out_bf16[i] = h;
-            v = bf16_to_f32(h);
-        }
-        if (out_f32) out_f32[i] = v;
-    }
-}
-
 // ------------------------------------------------------------------ fast squared norms of stored rows
 // fp32, one wave per row, 16-B loads (rows are whole 128-B lines: ld*sizeof(T) % 128 == 0).
 // Used by the L2 fast pass and for the certificate's bound.
@@ -112,21 +66,6 @@ __global__ __launch_bounds__(256) void row_fastnorm_kernel(const T* __restrict__
         wave_max = __builtin_fmaxf(wave_max, s);
     }
     if (lane == 0 && wave_max > 0.0f) atomicMax(max_bits, __float_as_uint(wave_max));  // >= 0: uint order == float order
-}
-
-// ------------------------------------------------------------------ widen stored rows back to fp32
-template <typename T>
-__global__ __launch_bounds__(256) void rows_get_kernel(const T* __restrict__ rows, uint64_t n,
-                                                       uint32_t dim, uint32_t ld,
-                                                       float* __restrict__ out) {
-    const uint64_t total = n * (uint64_t)dim;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t r = i / dim;
-        const uint32_t j = (uint32_t)(i - r * dim);
-        if constexpr (sizeof(T) == 2) out[i] = bf16_to_f32(rows[r * (uint64_t)ld + j]);
-        else out[i] = rows[r * (uint64_t)ld + j];
-    }
 }
 
 // ------------------------------------------------------------------ query preparation, one launch
@@ -248,22 +187,6 @@ void launch_synth_rows(uint64_t seed, uint64_t first_row, uint64_t n, uint32_t d
     synth_rows_kernel<<<grid_for(n, 4), 256, 0, s>>>(key, first_row, n, dim, d_out);
 }
 
-void launch_prepare_rows(const float* d_in, uint64_t n, uint32_t dim, uint32_t ld, int metric,
-                         int dtype, double* d_nrm_ws, uint32_t* d_bad_flag, float* d_out_f32,
-                         void* d_out_bf16, hipStream_t s) {
-    if (!n) return;
-    // the norm pass also performs the NaN/Inf check, so it always runs
-    row_norm_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(d_in, n, dim, d_nrm_ws, d_bad_flag);
-    const int g = grid_for(n * (uint64_t)ld, 256);
-    const int rb = dtype == DT_BF16;
-    if (metric == M_COSINE)
-        row_write_kernel<true><<<g, 256, 0, s>>>(d_in, n, dim, ld, d_nrm_ws, rb, d_out_f32,
-                                                 (bf16_t*)d_out_bf16);
-    else
-        row_write_kernel<false><<<g, 256, 0, s>>>(d_in, n, dim, ld, d_nrm_ws, rb, d_out_f32,
-                                                  (bf16_t*)d_out_bf16);
-}
-
 void launch_prep_queries(const float* d_in, uint32_t nq, uint32_t nq_pad, uint32_t dim, uint32_t ld, int metric,
                          int dtype, float* d_out_f32, void* d_out_bf16, float* d_qn2, uint32_t* d_bad_flag,
                          uint32_t* d_max_bits, const QueryInit& init, hipStream_t s) {
@@ -283,16 +206,6 @@ void launch_row_fastnorm(const void* d_rows, int dtype, uint64_t n, uint32_t ld,
         row_fastnorm_kernel<bf16_t><<<grid_for(n, 4), 256, 0, s>>>((const bf16_t*)d_rows, n, ld, d_xn2, d_max_bits);
     else
         row_fastnorm_kernel<float><<<grid_for(n, 4), 256, 0, s>>>((const float*)d_rows, n, ld, d_xn2, d_max_bits);
-}
-
-void launch_rows_get(const void* d_rows, int dtype, uint64_t n, uint32_t dim, uint32_t ld,
-                     float* d_out, hipStream_t s) {
-    if (!n) return;
-    const int g = grid_for(n * (uint64_t)dim, 256);
-    if (dtype == DT_BF16)
-        rows_get_kernel<bf16_t><<<g, 256, 0, s>>>((const bf16_t*)d_rows, n, dim, ld, d_out);
-    else
-        rows_get_kernel<float><<<g, 256, 0, s>>>((const float*)d_rows, n, dim, ld, d_out);
 }
 
 }  // namespace vrod

@@ -1,6 +1,6 @@
-// prep_chain.h -- the arithmetic of row and query preparation, in one place (device code).  kernels_prep.hip (the host
-// forms' two-pass prepare, the query prepare) and kernels_ingest.hip (the single-read ingest of device-resident rows)
-// include it, so that the bits of a prepared row do not depend on the road it came by.
+// prep_chain.h -- the arithmetic of row and query preparation, in one place (device code).  kernels_ingest.hip (the
+// prepare of every row that reaches a handle, from host or device memory) and kernels_prep.hip (the query prepare)
+// include it, so that a query meets rows prepared by the chain and the divide that prepared it.
 //
 // Spec (DESIGN.md "Scan spec", oracle/vrod_oracle.c orc_prepare_row): COSINE: x / sqrt(sum x^2), the sum accumulated
 // left to right in fp64 (v * v is exact in fp64 for an fp32 v, so fma(v, v, ss) == ss + v*v rounded once), the divide

@@ -27,6 +27,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -397,14 +398,14 @@ struct vrod_index {
     DevBuf cand_rows, cand_small;
 
     // workspaces
-    DevBuf raw_stage, nrm_ws, out_ids, out_scores;
+    DevBuf raw_stage, out_ids, out_scores;
     // vrod_index_save: the two dense chunks the pack kernel writes and the copies to the host read (a handle made by
     // vrod_index_load used it the other way round)
     DevBuf snap_stage;
     // vrod_index_update: a chunk's prepared rows and their destination rows; vrod_index_compact: live rows below each
-    // 32-row word (compact_plan.h compact_word_bases)
-    DevBuf upd_stage, upd_dst, compact_ws;
-    // the _device forms of add / update / upsert: a chunk's source rows (IngestSrc::pick) on the device
+    // 32-row word (compact_plan.h compact_word_bases), and the xnorm2 entries of a staged chunk's rows
+    DevBuf upd_stage, upd_dst, compact_ws, compact_xn2;
+    // add / update / upsert from device memory: the list of a chunk's source rows (RowSource::pick) on the device
     DevBuf ingest_pick;
     // range searches (vrod_range_search): the pool of qualifying rows and its sort partner, and the small block
     // [total (u64) | the caller's thresholds [nq] | per-query counters [nq]]
@@ -566,18 +567,6 @@ static int index_reserve(vrod_index* idx, uint64_t n_rows) {
     return VROD_OK;
 }
 
-// Prepare `n` raw fp32 rows already in device memory and append them.
-static int append_prepared(vrod_index* idx, const float* d_raw, uint64_t n) {
-    VROD_TRY(idx->nrm_ws.ensure(n * sizeof(double)));
-    char* dst = (char*)idx->corpus.p + idx->count * idx->row_bytes();
-    launch_prepare_rows(d_raw, n, idx->dim, idx->ld, prep_form(idx->metric), idx->dtype, idx->nrm_ws.as<double>(),
-                        &idx->flags.p[0], idx->dtype == VROD_DTYPE_F32 ? (float*)dst : nullptr,
-                        idx->dtype == VROD_DTYPE_BF16 ? dst : nullptr, idx->stream);
-    launch_row_fastnorm(dst, idx->dtype, n, idx->ld, idx->xnorm2.p + idx->count, idx->max_xn2_bits, idx->stream);
-    HIP_TRY(hipGetLastError());
-    return VROD_OK;
-}
-
 // Word `w` of idx->flags.p as the launches on `s` so far leave it; a raised word is cleared for the next call.
 static int take_flag(vrod_index* idx, uint32_t w, hipStream_t s, uint32_t* bad) {
     *bad = 0;
@@ -597,95 +586,83 @@ static int check_bad_flag(vrod_index* idx, const char* what) {
     return VROD_OK;
 }
 
-// rows per staged chunk of an add or update of n rows: 256 MiB of raw rows at most (ingest_plan.h)
-static uint64_t stage_chunk_rows(const vrod_index* idx, uint64_t n) { return ingest_chunk_rows(n, idx->dim); }
-
-// ------------------------------------------------------------------ rows from device memory (the _device forms of add / update / upsert)
-// A source of typed, strided rows in device memory (include/vrod.h "device-resident ingest").  pick: a HOST list of the
-// source rows a pass takes, in the order of the pass (null: source row i is row i) -- how an update's rows reach their
-// shards and an upsert's rows split into held and new without the payload ever leaving the device.
-struct IngestSrc {
-    const void* p = nullptr;
-    int dtype = SRC_F32;
-    uint64_t stride = 0;
-    const uint64_t* pick = nullptr;
-    int device = 0;   // where p lives
-};
-// the source from row `first` of the pass on
-static IngestSrc ingest_from(const IngestSrc& s, uint64_t first) {
-    IngestSrc t = s;
-    if (t.pick) t.pick += first;
-    else t.p = (const char*)s.p + first * s.stride * ingest_elem_bytes(s.dtype);
-    return t;
-}
-// VROD_INGEST_STAGE=1: every source goes the way of one on another device (packed, copied peer to peer, ingested from
-// the dense copy), so that a one-GPU box can rehearse that way.  Read per call.
+// ------------------------------------------------------------------ the rows of an add / update / upsert (ingest_plan.h RowSource)
+// VROD_INGEST_STAGE=1: every device source goes the way of one on another device (packed, copied peer to peer, ingested
+// from the dense copy), so that a one-GPU box can rehearse that way.  Read per call.
 static bool ingest_force_stage() {
     const char* e = getenv("VROD_INGEST_STAGE");
     return e && e[0] == '1';
 }
 
 // Rows [0, m) of `src` become prepared rows [m][ld] at `out` (on idx's device, which is current), on idx->stream; NaN /
-// Inf raise idx->flags.p[0] as the host forms' prepare raises it.
-static int ingest_prepare(vrod_index* idx, const IngestSrc& src, uint64_t m, void* out) {
-    const int form = prep_form(idx->metric);
-    if (src.device == idx->device && !ingest_force_stage()) {
-        const uint64_t* d_pick = nullptr;
+// Inf raise idx->flags.p[0].  One staging step says where the kernel finds them: host rows are uploaded to raw_stage (a
+// picked list of them gathered first), a synthetic chunk is generated there, device rows on this GPU are read where they
+// lie, device rows on another GPU (or all of them under VROD_INGEST_STAGE=1) are packed there and copied over.  raw_stage may still feed the previous chunk's
+// launch: whatever fills it does so in the order of idx->stream, or drains that stream first.
+static int ingest_prepare(vrod_index* idx, const RowSource& src, uint64_t m, void* out) {
+    const uint32_t dim = idx->dim;
+    const bool in_place = src.kind == RowSource::DEVICE && src.device == idx->device && !ingest_force_stage();
+    const size_t bytes = (size_t)m * dim * ingest_elem_bytes(src.dtype);   // of the chunk, dense
+    if (!in_place) VROD_TRY(idx->raw_stage.ensure(bytes));
+    const void* p = idx->raw_stage.p;
+    uint64_t stride = dim;
+    const uint64_t* d_pick = nullptr;
+    if (src.kind == RowSource::HOST) {
+        if (src.pick) {   // one upload of the chunk's rows, gathered; the buffer goes with this step, so the copy is waited for
+            std::unique_ptr<float[]> rows(new float[(size_t)m * dim]);
+            rows_gather(src, dim, m, rows.get());
+            HIP_TRY(hipMemcpyAsync(idx->raw_stage.p, rows.get(), bytes, hipMemcpyHostToDevice, idx->stream));
+            HIP_TRY(hipStreamSynchronize(idx->stream));
+        } else {
+            HIP_TRY(hipMemcpyAsync(idx->raw_stage.p, src.p, bytes, hipMemcpyHostToDevice, idx->stream));
+        }
+    } else if (src.kind == RowSource::SYNTH) {
+        for (uint64_t i = 0; i < m;) {
+            const uint64_t run = src.pick ? pick_run(src.pick, m, i) : m;
+            launch_synth_rows(src.seed, src.first_row + (src.pick ? src.pick[i] : 0), run, dim, idx->raw_stage.as<float>() + i * dim, idx->stream);
+            i += run;
+        }
+    } else if (in_place) {
         if (src.pick) {
             VROD_TRY(idx->ingest_pick.ensure(m * 8));
             HIP_TRY(hipMemcpyAsync(idx->ingest_pick.p, src.pick, m * 8, hipMemcpyHostToDevice, idx->stream));
             d_pick = idx->ingest_pick.as<uint64_t>();
         }
-        launch_ingest_rows(src.p, src.dtype, src.stride, d_pick, m, idx->dim, idx->ld, form, idx->dtype, &idx->flags.p[0], out, idx->stream);
-        HIP_TRY(hipGetLastError());
-        return VROD_OK;
-    }
-    // The source lives on another device: pack the rows there (dense, in their own type), copy them peer to peer into
-    // the shard's staging buffer, ingest from that.  The staging buffer may still feed the previous chunk's launch.
-    const size_t bytes = (size_t)m * idx->dim * ingest_elem_bytes(src.dtype);
-    VROD_TRY(idx->raw_stage.ensure(bytes));
-    HIP_TRY(hipStreamSynchronize(idx->stream));
-    HIP_TRY(hipSetDevice(src.device));
-    int rc = VROD_OK;
-    {
-        DevBuf pack, picks;   // on the source's device, for this chunk only
-        rc = pack.ensure(bytes);
-        if (rc == VROD_OK && src.pick) rc = picks.ensure(m * 8);
-        hipError_t e = hipSuccess;
-        if (rc == VROD_OK && src.pick) e = hipMemcpy(picks.p, src.pick, m * 8, hipMemcpyHostToDevice);
-        if (rc == VROD_OK && e == hipSuccess) {
-            launch_ingest_pack(src.p, src.dtype, src.stride, src.pick ? picks.as<uint64_t>() : nullptr, m, idx->dim, pack.p, nullptr);
-            e = hipGetLastError();
+        p = src.p;
+        stride = src.stride;
+    } else {   // pack the rows on their device (dense, in their own type), copy them peer to peer
+        HIP_TRY(hipStreamSynchronize(idx->stream));
+        HIP_TRY(hipSetDevice(src.device));
+        int rc = VROD_OK;
+        {
+            DevBuf pack, picks;   // on the source's device, for this chunk only
+            rc = pack.ensure(bytes);
+            if (rc == VROD_OK && src.pick) rc = picks.ensure(m * 8);
+            hipError_t e = hipSuccess;
+            if (rc == VROD_OK && src.pick) e = hipMemcpy(picks.p, src.pick, m * 8, hipMemcpyHostToDevice);
+            if (rc == VROD_OK && e == hipSuccess) {
+                launch_ingest_pack(src.p, src.dtype, src.stride, src.pick ? picks.as<uint64_t>() : nullptr, m, dim, pack.p, nullptr);
+                e = hipGetLastError();
+            }
+            if (rc == VROD_OK && e == hipSuccess) e = hipMemcpyPeerAsync(idx->raw_stage.p, idx->device, pack.p, src.device, bytes, nullptr);
+            if (rc == VROD_OK && e == hipSuccess) e = hipStreamSynchronize(nullptr);
+            if (rc == VROD_OK && e != hipSuccess) rc = fail(VROD_ERR_HIP, "staging rows from device %d: %s", src.device, hipGetErrorString(e));
         }
-        if (rc == VROD_OK && e == hipSuccess) e = hipMemcpyPeerAsync(idx->raw_stage.p, idx->device, pack.p, src.device, bytes, nullptr);
-        if (rc == VROD_OK && e == hipSuccess) e = hipStreamSynchronize(nullptr);
-        if (rc == VROD_OK && e != hipSuccess) rc = fail(VROD_ERR_HIP, "staging rows from device %d: %s", src.device, hipGetErrorString(e));
+        HIP_TRY(hipSetDevice(idx->device));
+        VROD_TRY(rc);
     }
-    HIP_TRY(hipSetDevice(idx->device));
-    VROD_TRY(rc);
-    launch_ingest_rows(idx->raw_stage.p, src.dtype, idx->dim, nullptr, m, idx->dim, idx->ld, form, idx->dtype, &idx->flags.p[0], out, idx->stream);
+    launch_ingest_rows(p, src.dtype, stride, d_pick, m, dim, idx->ld, prep_form(idx->metric), idx->dtype, &idx->flags.p[0], out, idx->stream);
     HIP_TRY(hipGetLastError());
     return VROD_OK;
 }
 
-// append_prepared for a device-resident source
-static int append_ingested(vrod_index* idx, const IngestSrc& src, uint64_t n) {
-    char* dst = (char*)idx->corpus.p + idx->count * idx->row_bytes();
-    VROD_TRY(ingest_prepare(idx, src, n, dst));
-    launch_row_fastnorm(dst, idx->dtype, n, idx->ld, idx->xnorm2.p + idx->count, idx->max_xn2_bits, idx->stream);
-    HIP_TRY(hipGetLastError());
-    return VROD_OK;
-}
-
-// dev: the rows come from device memory (rows == null, not synthetic)
-static int index_add(vrod_index* idx, const float* rows, uint64_t n, bool synthetic, uint64_t seed,
-                     uint64_t first_row, const IngestSrc* dev = nullptr) {
+static int index_add(vrod_index* idx, const RowSource& src, uint64_t n) {
     if (!n) return VROD_OK;
     VROD_TRY(set_device(idx));
     idx->doc_valid = false;   // (the document index of a multi-vector search covers the rows it was built from)
     if (idx->count + n > idx->capacity) {
         uint64_t want = std::max(idx->count + n, idx->capacity + idx->capacity / 2);
-        if (synthetic || idx->capacity == 0) want = idx->count + n;
+        if (src.kind == RowSource::SYNTH || idx->capacity == 0) want = idx->count + n;
         VROD_TRY(index_reserve(idx, want));
     }
     const uint64_t count0 = idx->count;
@@ -693,24 +670,14 @@ static int index_add(vrod_index* idx, const float* rows, uint64_t n, bool synthe
     // rejected: keep the value it had, so that a rejected add cannot widen (or, with an Inf row,
     // void) the certificate bound of every later search
     HIP_TRY(hipMemcpyAsync(&idx->flags.p[9], idx->max_xn2_bits, 4, hipMemcpyDeviceToDevice, idx->stream));
-    const uint64_t chunk = stage_chunk_rows(idx, n);
-    if (!dev) VROD_TRY(idx->raw_stage.ensure(chunk * idx->dim * sizeof(float)));
+    const uint64_t chunk = ingest_chunk_rows(n, idx->dim);
     for (uint64_t done = 0; done < n; done += chunk) {
         const uint64_t m = std::min(chunk, n - done);
-        if (dev) {
-            VROD_TRY(append_ingested(idx, ingest_from(*dev, done), m));
-            idx->count += m;
-            continue;
-        }
-        if (synthetic) {
-            launch_synth_rows(seed, first_row + done, m, idx->dim, idx->raw_stage.as<float>(), idx->stream);
-        } else {
-            HIP_TRY(hipMemcpyAsync(idx->raw_stage.p, rows + done * idx->dim, m * idx->dim * sizeof(float),
-                                   hipMemcpyHostToDevice, idx->stream));
-        }
-        VROD_TRY(append_prepared(idx, idx->raw_stage.as<float>(), m));
+        char* dst = (char*)idx->corpus.p + idx->count * idx->row_bytes();
+        VROD_TRY(ingest_prepare(idx, rows_from(src, done), m, dst));
+        launch_row_fastnorm(dst, idx->dtype, m, idx->ld, idx->xnorm2.p + idx->count, idx->max_xn2_bits, idx->stream);
+        HIP_TRY(hipGetLastError());
         idx->count += m;
-        // the staging buffer is reused by the next chunk: stream order keeps it safe
     }
     int rc = check_bad_flag(idx, "rows");
     if (rc != VROD_OK) {  // roll back: re-zero the rows just written
@@ -725,33 +692,21 @@ static int index_add(vrod_index* idx, const float* rows, uint64_t n, bool synthe
 }
 
 // ------------------------------------------------------------------ update in place (vrod_index_update)
-// One pass over the n rows of an update, staged in chunks as index_add stages them: upload, prepare into upd_stage.
+// One pass over the n rows of an update, in the chunks of index_add: each is prepared into upd_stage.
 //   dst == null: prepare only.  The NaN / Inf check of a call that needs more than one chunk, and of every shard of a
 //                composite handle: every row is checked before any row is written.  Returns what the flag says.
 //   dst != null: row i goes to corpus row dst[i] (kScatterSkip: nowhere), with its xnorm2 entry, the running maximum
 //                and its bf16 planes where they exist (kernels_mutate.hip).  check_first: the call fits one chunk and
 //                has not been checked: the flag is read between the prepare and the scatter.
 // Nothing but the scatter writes to the corpus, xnorm2 or max_xn2_bits, so a rejected update changes none of them.
-// dev: the rows come from device memory (rows == null): the ingest kernel prepares them into upd_stage, the rest is the same.
-static int index_update_pass(vrod_index* idx, const uint32_t* dst, const float* rows, uint64_t n, bool check_first,
-                             const IngestSrc* dev = nullptr) {
+static int index_update_pass(vrod_index* idx, const uint32_t* dst, const RowSource& src, uint64_t n, bool check_first) {
     VROD_TRY(set_device(idx));
-    const uint64_t chunk = stage_chunk_rows(idx, n);
-    if (!dev) VROD_TRY(idx->raw_stage.ensure(chunk * idx->dim * sizeof(float)));
+    const uint64_t chunk = ingest_chunk_rows(n, idx->dim);
     VROD_TRY(idx->upd_stage.ensure(chunk * idx->row_bytes()));
-    if (!dev) VROD_TRY(idx->nrm_ws.ensure(chunk * sizeof(double)));
     if (dst) VROD_TRY(idx->upd_dst.ensure(chunk * 4));
     for (uint64_t done = 0; done < n; done += chunk) {
         const uint64_t m = std::min(chunk, n - done);
-        if (dev) {
-            VROD_TRY(ingest_prepare(idx, ingest_from(*dev, done), m, idx->upd_stage.p));
-        } else {
-            HIP_TRY(hipMemcpyAsync(idx->raw_stage.p, rows + done * idx->dim, m * idx->dim * sizeof(float), hipMemcpyHostToDevice, idx->stream));
-            launch_prepare_rows(idx->raw_stage.as<float>(), m, idx->dim, idx->ld, prep_form(idx->metric), idx->dtype, idx->nrm_ws.as<double>(),
-                                &idx->flags.p[0], idx->dtype == VROD_DTYPE_F32 ? idx->upd_stage.as<float>() : nullptr,
-                                idx->dtype == VROD_DTYPE_BF16 ? idx->upd_stage.p : nullptr, idx->stream);
-            HIP_TRY(hipGetLastError());
-        }
+        VROD_TRY(ingest_prepare(idx, rows_from(src, done), m, idx->upd_stage.p));
         if (!dst) continue;
         if (check_first) VROD_TRY(check_bad_flag(idx, "rows"));
         HIP_TRY(hipMemcpyAsync(idx->upd_dst.p, dst + done, m * 4, hipMemcpyHostToDevice, idx->stream));
@@ -765,10 +720,10 @@ static int index_update_pass(vrod_index* idx, const uint32_t* dst, const float* 
 }
 
 // dst: per row of the call its local row, or kScatterSkip for an id that the call names again later
-static int index_update(vrod_index* idx, const std::vector<uint32_t>& dst, const float* rows, uint64_t n, const IngestSrc* dev = nullptr) {
-    if (n <= stage_chunk_rows(idx, n)) return index_update_pass(idx, dst.data(), rows, n, true, dev);
-    VROD_TRY(index_update_pass(idx, nullptr, rows, n, false, dev));
-    return index_update_pass(idx, dst.data(), rows, n, false, dev);
+static int index_update(vrod_index* idx, const std::vector<uint32_t>& dst, const RowSource& src, uint64_t n) {
+    if (n <= ingest_chunk_rows(n, idx->dim)) return index_update_pass(idx, dst.data(), src, n, true);
+    VROD_TRY(index_update_pass(idx, nullptr, src, n, false));
+    return index_update_pass(idx, dst.data(), src, n, false);
 }
 
 static void mask_changed(vrod_index* idx);
@@ -875,7 +830,7 @@ static int index_compact(vrod_index* idx, uint64_t* out_new_ids) {
     for (const CompactChunk& c : plan.chunks) if (c.staged) stage_rows = std::max(stage_rows, c.L);
     if (stage_rows) {
         VROD_TRY(idx->raw_stage.ensure(stage_rows * rb));
-        VROD_TRY(idx->nrm_ws.ensure(stage_rows * sizeof(float)));
+        VROD_TRY(idx->compact_xn2.ensure(stage_rows * sizeof(float)));
     }
     VROD_TRY(idx->compact_ws.ensure(words * 4));
     HIP_TRY(hipMemcpyAsync(idx->compact_ws.p, base.data(), words * 4, hipMemcpyHostToDevice, idx->stream));
@@ -888,9 +843,9 @@ static int index_compact(vrod_index* idx, uint64_t* out_new_ids) {
     for (const CompactChunk& c : plan.chunks) {
         if (c.staged) {
             launch_compact_rows(corpus, idx->xnorm2.p, idx->del_dev.p, idx->compact_ws.as<uint32_t>(), c.r0, c.r1, rb, idx->raw_stage.p,
-                                idx->nrm_ws.as<float>(), c.w0, s);
+                                idx->compact_xn2.as<float>(), c.w0, s);
             e = hipMemcpyAsync(corpus + c.w0 * rb, idx->raw_stage.p, c.L * rb, hipMemcpyDeviceToDevice, s);
-            if (e == hipSuccess) e = hipMemcpyAsync(idx->xnorm2.p + c.w0, idx->nrm_ws.p, c.L * sizeof(float), hipMemcpyDeviceToDevice, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(idx->xnorm2.p + c.w0, idx->compact_xn2.p, c.L * sizeof(float), hipMemcpyDeviceToDevice, s);
         } else {
             launch_compact_rows(corpus, idx->xnorm2.p, idx->del_dev.p, idx->compact_ws.as<uint32_t>(), c.r0, c.r1, rb, corpus, idx->xnorm2.p, 0, s);
         }
@@ -1866,8 +1821,7 @@ static uint64_t local_row_of(const vrod_index* idx, uint64_t r) {
     return deal_local_row(r, idx->shards.size());
 }
 
-static int composite_add(vrod_index* idx, const float* rows, uint64_t n, bool synthetic, uint64_t seed, uint64_t first_row,
-                         const IngestSrc* dev = nullptr) {
+static int composite_add(vrod_index* idx, const RowSource& src, uint64_t n) {
     const uint64_t count0 = idx->count;
     for (vrod_index* sh : idx->shards) {   // what a roll-back restores (see index_add)
         VROD_TRY(set_device(sh));
@@ -1876,11 +1830,7 @@ static int composite_add(vrod_index* idx, const float* rows, uint64_t n, bool sy
     int rc = for_each_piece(idx, count0, n, [&](size_t g, uint64_t r, uint64_t m) {
         vrod_index* sh = idx->shards[g];
         if (sh->count != local_row_of(idx, r)) return fail(VROD_ERR_INTERNAL, "shard %zu is out of step", g);
-        if (dev) {
-            const IngestSrc piece = ingest_from(*dev, r - count0);
-            return index_add(sh, nullptr, m, false, 0, 0, &piece);
-        }
-        return index_add(sh, rows ? rows + (r - count0) * idx->dim : nullptr, m, synthetic, seed, first_row + (r - count0));
+        return index_add(sh, rows_from(src, r - count0), m);
     });
     if (rc != VROD_OK) {
         // a rejected piece (NaN/Inf) rolled itself back; drop the pieces already taken by other shards
@@ -2056,27 +2006,22 @@ static int composite_delete(vrod_index* idx, const uint64_t* ids, uint64_t n) {
 
 // An update of a composite handle: each row goes to the shard that holds its id.  Every shard checks its rows (NaN /
 // Inf) before any shard writes one, so a rejected call changes nothing on the handle as a whole.
-// rows_of: per row of the call its global row, skip[i]: the call names that id again later.
-// dev: the rows are in device memory (rows == null): each shard takes its rows of the source through a list of them.
-static int composite_update(vrod_index* idx, const std::vector<uint64_t>& rows_of, const std::vector<bool>& skip, const float* rows,
-                            const IngestSrc* dev = nullptr) {
+// rows_of: per row of the call its global row, skip[i]: the call names that id again later.  Each shard takes its rows
+// of the source through a list of them.
+static int composite_update(vrod_index* idx, const std::vector<uint64_t>& rows_of, const std::vector<bool>& skip, const RowSource& src) {
     const size_t G = idx->shards.size();
     std::vector<std::vector<uint32_t>> dst(G);
-    std::vector<std::vector<float>> buf(G);
     std::vector<std::vector<uint64_t>> pick(G);
     for (size_t i = 0; i < rows_of.size(); ++i) {
         const uint64_t r = rows_of[i];
         const size_t g = (size_t)((r / kShardBlock) % G);
         dst[g].push_back(skip[i] ? kScatterSkip : (uint32_t)local_row_of(idx, r));
-        if (dev) pick[g].push_back(dev->pick ? dev->pick[i] : (uint64_t)i);
-        else buf[g].insert(buf[g].end(), rows + i * idx->dim, rows + (i + 1) * idx->dim);
+        pick[g].push_back(src.pick ? src.pick[i] : (uint64_t)i);
     }
-    std::vector<IngestSrc> src(G);
-    for (size_t g = 0; g < G && dev; ++g) { src[g] = *dev; src[g].pick = pick[g].data(); }
     for (size_t g = 0; g < G; ++g)
-        if (!dst[g].empty()) VROD_TRY(index_update_pass(idx->shards[g], nullptr, buf[g].data(), dst[g].size(), false, dev ? &src[g] : nullptr));
+        if (!dst[g].empty()) VROD_TRY(index_update_pass(idx->shards[g], nullptr, rows_picked(src, pick[g].data()), dst[g].size(), false));
     for (size_t g = 0; g < G; ++g)
-        if (!dst[g].empty()) VROD_TRY(index_update_pass(idx->shards[g], dst[g].data(), buf[g].data(), dst[g].size(), false, dev ? &src[g] : nullptr));
+        if (!dst[g].empty()) VROD_TRY(index_update_pass(idx->shards[g], dst[g].data(), rows_picked(src, pick[g].data()), dst[g].size(), false));
     return VROD_OK;
 }
 
@@ -4459,16 +4404,18 @@ int vrod_index_reserve(vrod_index* idx, uint64_t n_rows) {
 
 int vrod_index_add(vrod_index* idx, const float* rows, uint64_t n) {
     if (!idx || (!rows && n)) return fail(VROD_ERR_INVALID_ARG, "null argument");
-    if (idx->composite()) return composite_add(idx, rows, n, false, 0, 0);
+    const RowSource src = rows_on_host(rows, idx->dim);
+    if (idx->composite()) return composite_add(idx, src, n);
     VROD_TRY(require_idle(idx, "vrod_index_add"));
-    return index_add(idx, rows, n, false, 0, 0);
+    return index_add(idx, src, n);
 }
 
 int vrod_index_add_synthetic(vrod_index* idx, uint64_t seed, uint64_t first_row, uint64_t n) {
     if (!idx) return fail(VROD_ERR_INVALID_ARG, "idx is null");
-    if (idx->composite()) return composite_add(idx, nullptr, n, true, seed, first_row);
+    const RowSource src = rows_synthetic(seed, first_row);
+    if (idx->composite()) return composite_add(idx, src, n);
     VROD_TRY(require_idle(idx, "vrod_index_add_synthetic"));
-    return index_add(idx, nullptr, n, true, seed, first_row);
+    return index_add(idx, src, n);
 }
 
 int vrod_index_count(const vrod_index* idx, uint64_t* out_count) {
@@ -4491,8 +4438,8 @@ int vrod_index_delete(vrod_index* idx, const uint64_t* ids, uint64_t n) {
     return index_delete_rows(idx, rows);
 }
 
-// vrod_index_update behind its argument checks; ids: host memory.  dev: the rows are in device memory (rows == null).
-static int update_checked(vrod_index* idx, const uint64_t* ids, const float* rows, uint64_t n, const IngestSrc* dev) {
+// vrod_index_update behind its argument checks; ids: host memory
+static int update_checked(vrod_index* idx, const uint64_t* ids, const RowSource& src, uint64_t n) {
     const size_t G = idx->shards.size();
     std::vector<uint64_t> rows_of(n);
     for (uint64_t i = 0; i < n; ++i) {   // the whole call or nothing
@@ -4514,16 +4461,16 @@ static int update_checked(vrod_index* idx, const uint64_t* ids, const float* row
         if (seen[rows_of[i]]) skip[i] = true;
         seen[rows_of[i]] = true;
     }
-    if (G) return composite_update(idx, rows_of, skip, rows, dev);
+    if (G) return composite_update(idx, rows_of, skip, src);
     std::vector<uint32_t> dst(n);
     for (uint64_t i = 0; i < n; ++i) dst[i] = skip[i] ? kScatterSkip : (uint32_t)rows_of[i];
-    return index_update(idx, dst, rows, n, dev);
+    return index_update(idx, dst, src, n);
 }
 
 int vrod_index_update(vrod_index* idx, const uint64_t* ids, const float* rows, uint64_t n) {
     if (!idx || ((!ids || !rows) && n)) return fail(VROD_ERR_INVALID_ARG, "null argument");
     VROD_TRY(require_idle(idx, "vrod_index_update"));
-    return update_checked(idx, ids, rows, n, nullptr);
+    return update_checked(idx, ids, rows_on_host(rows, idx->dim), n);
 }
 
 // ------------------------------------------------------------------ device-resident ingest: add / update / get_rows
@@ -4558,11 +4505,10 @@ int vrod_index_add_device(vrod_index* idx, const void* d_rows, int src_dtype, ui
     VROD_TRY(check_ingest_args(idx, "vrod_index_add_device", d_rows, src_dtype, row_stride, n));
     VROD_TRY(require_idle(idx, "vrod_index_add_device"));
     if (!n) return VROD_OK;
-    IngestSrc src;
-    src.p = d_rows; src.dtype = src_dtype; src.stride = row_stride;
+    RowSource src = rows_on_device(d_rows, src_dtype, row_stride);
     VROD_TRY(ingest_open(idx, "vrod_index_add_device", d_rows, stream, &src.device));
-    if (idx->composite()) return composite_add(idx, nullptr, n, false, 0, 0, &src);
-    return index_add(idx, nullptr, n, false, 0, 0, &src);
+    if (idx->composite()) return composite_add(idx, src, n);
+    return index_add(idx, src, n);
 }
 
 int vrod_index_update_device(vrod_index* idx, const uint64_t* d_ids, const void* d_rows, int src_dtype, uint64_t row_stride, uint64_t n,
@@ -4571,12 +4517,11 @@ int vrod_index_update_device(vrod_index* idx, const uint64_t* d_ids, const void*
     if (!d_ids && n) return fail(VROD_ERR_INVALID_ARG, "vrod_index_update_device: d_ids is null");
     VROD_TRY(require_idle(idx, "vrod_index_update_device"));
     if (!n) return VROD_OK;
-    IngestSrc src;
-    src.p = d_rows; src.dtype = src_dtype; src.stride = row_stride;
+    RowSource src = rows_on_device(d_rows, src_dtype, row_stride);
     VROD_TRY(ingest_open(idx, "vrod_index_update_device", d_rows, stream, &src.device));
     std::vector<uint64_t> ids(n);   // 8 bytes per row cross to the host for the host form's checks; the rows stay
     HIP_TRY(hipMemcpy(ids.data(), d_ids, n * 8, hipMemcpyDeviceToHost));
-    return update_checked(idx, ids.data(), nullptr, n, &src);
+    return update_checked(idx, ids.data(), src, n);
 }
 
 // Rows [first, first + m) of a single-device handle (or shard) as fp32 at d_out, out_stride floats apart.
@@ -4588,7 +4533,7 @@ static int get_rows_to_device(vrod_index* idx, uint64_t first, uint64_t m, float
         HIP_TRY(hipGetLastError());
     } else {   // the output lives on another device: dense rows here, then a pitched copy
         VROD_TRY(idx->raw_stage.ensure(m * idx->dim * 4));
-        launch_rows_get(rows, idx->dtype, m, idx->dim, idx->ld, idx->raw_stage.as<float>(), idx->stream);
+        launch_rows_get_strided(rows, idx->dtype, m, idx->dim, idx->ld, idx->raw_stage.as<float>(), idx->dim, idx->stream);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpy2DAsync(d_out, out_stride * 4, idx->raw_stage.p, (size_t)idx->dim * 4, (size_t)idx->dim * 4, m, hipMemcpyDeviceToDevice,
                                  idx->stream));
@@ -4664,7 +4609,8 @@ int vrod_index_get_rows(vrod_index* idx, uint64_t first, uint64_t n, float* out_
     VROD_TRY(require_idle(idx, "vrod_index_get_rows"));
     VROD_TRY(set_device(idx));
     VROD_TRY(idx->raw_stage.ensure(n * idx->dim * 4));
-    launch_rows_get((const char*)idx->corpus.p + first * idx->row_bytes(), idx->dtype, n, idx->dim, idx->ld, idx->raw_stage.as<float>(), idx->stream);
+    launch_rows_get_strided((const char*)idx->corpus.p + first * idx->row_bytes(), idx->dtype, n, idx->dim, idx->ld, idx->raw_stage.as<float>(),
+                            idx->dim, idx->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out_rows, idx->raw_stage.p, n * idx->dim * 4, hipMemcpyDeviceToHost, idx->stream));
     HIP_TRY(hipStreamSynchronize(idx->stream));
@@ -5063,9 +5009,9 @@ int vrod_index_delete_keys(vrod_index* idx, const uint64_t* keys, uint64_t n, ui
     return VROD_OK;
 }
 
-// vrod_index_upsert on an idle single-device handle, n > 0; keys and out_ids: host memory.  dev: the rows are in device
-// memory (rows == null): the held and the new rows are taken from the source through lists of them.
-static int upsert_checked(vrod_index* idx, const uint64_t* keys, const float* rows, uint64_t n, uint64_t* out_ids, const IngestSrc* dev) {
+// vrod_index_upsert on an idle single-device handle, n > 0; keys and out_ids: host memory.  The held and the new rows are
+// taken from the source through lists of them.
+static int upsert_checked(vrod_index* idx, const uint64_t* keys, const RowSource& src, uint64_t n, uint64_t* out_ids) {
     // every check before the first row is written: the keys on the host, the vectors by a prepare-only pass
     {
         std::vector<uint64_t> sorted(keys, keys + n);
@@ -5074,39 +5020,29 @@ static int upsert_checked(vrod_index* idx, const uint64_t* keys, const float* ro
         const auto twice = std::adjacent_find(sorted.begin(), sorted.end());
         if (twice != sorted.end()) return fail(VROD_ERR_INVALID_ARG, "vrod_index_upsert: key %llu is named twice", (unsigned long long)*twice);
     }
-    VROD_TRY(index_update_pass(idx, nullptr, rows, n, false, dev));
+    VROD_TRY(index_update_pass(idx, nullptr, src, n, false));
     std::vector<uint64_t> found(n);
     VROD_TRY(keys_find_host(idx, "vrod_index_upsert", keys, n, found.data()));
     // the rows of held keys are updated in place, the others appended in the order of the call and keyed
-    const size_t dim = idx->dim;
     std::vector<uint32_t> dst;
     std::vector<uint64_t> new_keys;
-    std::vector<float> held_rows, new_rows;
     std::vector<uint64_t> held_pick, new_pick;
     const uint64_t count0 = idx->count;
     for (uint64_t i = 0; i < n; ++i) {
         if (found[i] != kKeyNone) {
             dst.push_back((uint32_t)(found[i] - idx->id_offset));
-            if (dev) held_pick.push_back(i);
-            else held_rows.insert(held_rows.end(), rows + i * dim, rows + (i + 1) * dim);
+            held_pick.push_back(i);
         } else {
             found[i] = idx->id_offset + count0 + new_keys.size();
             new_keys.push_back(keys[i]);
-            if (dev) new_pick.push_back(i);
-            else new_rows.insert(new_rows.end(), rows + i * dim, rows + (i + 1) * dim);
+            new_pick.push_back(i);
         }
     }
-    IngestSrc held_src, new_src;
-    if (dev) {
-        held_src = new_src = *dev;
-        held_src.pick = held_pick.data();
-        new_src.pick = new_pick.data();
-    }
     if (!new_keys.empty()) {
-        VROD_TRY(index_add(idx, dev ? nullptr : new_rows.data(), new_keys.size(), false, 0, 0, dev ? &new_src : nullptr));
+        VROD_TRY(index_add(idx, rows_picked(src, new_pick.data()), new_keys.size()));
         VROD_TRY(keys_set_range(idx, "vrod_index_upsert", count0, new_keys.data(), new_keys.size(), false));
     }
-    if (!dst.empty()) VROD_TRY(index_update(idx, dst, dev ? nullptr : held_rows.data(), dst.size(), dev ? &held_src : nullptr));
+    if (!dst.empty()) VROD_TRY(index_update(idx, dst, rows_picked(src, held_pick.data()), dst.size()));
     if (out_ids) std::copy(found.begin(), found.end(), out_ids);
     return VROD_OK;
 }
@@ -5116,7 +5052,7 @@ int vrod_index_upsert(vrod_index* idx, const uint64_t* keys, const float* rows, 
     if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "vrod_index_upsert %s", kKeysNotRouted);
     VROD_TRY(require_idle(idx, "vrod_index_upsert"));
     if (!n) return VROD_OK;
-    return upsert_checked(idx, keys, rows, n, out_ids, nullptr);
+    return upsert_checked(idx, keys, rows_on_host(rows, idx->dim), n, out_ids);
 }
 
 int vrod_index_upsert_device(vrod_index* idx, const uint64_t* d_keys, const void* d_rows, int src_dtype, uint64_t row_stride, uint64_t n,
@@ -5126,12 +5062,11 @@ int vrod_index_upsert_device(vrod_index* idx, const uint64_t* d_keys, const void
     if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "vrod_index_upsert_device %s", kKeysNotRouted);
     VROD_TRY(require_idle(idx, "vrod_index_upsert_device"));
     if (!n) return VROD_OK;
-    IngestSrc src;
-    src.p = d_rows; src.dtype = src_dtype; src.stride = row_stride;
+    RowSource src = rows_on_device(d_rows, src_dtype, row_stride);
     VROD_TRY(ingest_open(idx, "vrod_index_upsert_device", d_rows, stream, &src.device));
     std::vector<uint64_t> keys(n), ids(n);   // the keys cross to the host for the host form's checks; the rows stay
     HIP_TRY(hipMemcpy(keys.data(), d_keys, n * 8, hipMemcpyDeviceToHost));
-    VROD_TRY(upsert_checked(idx, keys.data(), nullptr, n, ids.data(), &src));
+    VROD_TRY(upsert_checked(idx, keys.data(), src, n, ids.data()));
     if (d_out_ids) HIP_TRY(hipMemcpy(d_out_ids, ids.data(), n * 8, hipMemcpyHostToDevice));
     return VROD_OK;
 }

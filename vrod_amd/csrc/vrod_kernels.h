@@ -33,9 +33,6 @@ struct IdMap {
 // ---- kernels_prep.hip
 void launch_synth_rows(uint64_t seed, uint64_t first_row, uint64_t n, uint32_t dim, float* d_out,
                        hipStream_t s);
-void launch_prepare_rows(const float* d_in, uint64_t n, uint32_t dim, uint32_t ld, int metric,
-                         int dtype, double* d_nrm_ws, uint32_t* d_bad_flag, float* d_out_f32,
-                         void* d_out_bf16, hipStream_t s);
 // Queries: normalise (COSINE) / round (BF16) / zero-pad to [nq_pad][ld] in ONE launch; also the
 // fast squared norms qn2[nq_pad], the NaN/Inf flag and the max squared norm (float bits).
 // `init`: per-search state the same launch resets (block q: status[q], counts[q], thr[q];
@@ -61,19 +58,18 @@ void launch_gather_readback(const uint32_t* d_status, uint32_t nq, uint32_t* d_f
                             uint32_t* d_out, hipStream_t s);
 void launch_row_fastnorm(const void* d_rows, int dtype, uint64_t n, uint32_t ld, float* d_xn2,
                          uint32_t* d_max_bits, hipStream_t s);
-void launch_rows_get(const void* d_rows, int dtype, uint64_t n, uint32_t dim, uint32_t ld,
-                     float* d_out, hipStream_t s);
 
-// ---- kernels_ingest.hip : rows that are in device memory already (vrod_index_add_device and its kin)
+// ---- kernels_ingest.hip : THE prepare of rows -- the host forms' staged fp32 chunk (stride dim) and the _device forms'
+// typed, strided rows alike.
 // n typed rows (src_dtype: ingest_plan.h SRC_*), row r at element (d_pick ? d_pick[r] : r) * row_stride of d_src, become
-// prepared rows [n][ld] at d_out exactly as launch_prepare_rows prepares the same fp32 values, in one read of the
-// source; NaN / Inf raise *d_bad_flag.
+// prepared rows [n][ld] at d_out (prep_chain.h's arithmetic on the values widened to fp32: COSINE normalises, a bf16
+// handle rounds, the padding is zeroed), in one read of the source; NaN / Inf raise *d_bad_flag.
 void launch_ingest_rows(const void* d_src, int src_dtype, uint64_t row_stride, const uint64_t* d_pick, uint64_t n, uint32_t dim,
                         uint32_t ld, int metric, int dtype, uint32_t* d_bad_flag, void* d_out, hipStream_t s);
 // the same rows as dense rows [n][dim] of their own type (the staging leg of a source on another device)
 void launch_ingest_pack(const void* d_src, int src_dtype, uint64_t row_stride, const uint64_t* d_pick, uint64_t n, uint32_t dim,
                         void* d_out, hipStream_t s);
-// launch_rows_get with out_stride (>= dim) floats between the rows it writes
+// stored rows [n][ld] widened back to fp32, out_stride (>= dim) floats between the rows written
 void launch_rows_get_strided(const void* d_rows, int dtype, uint64_t n, uint32_t dim, uint32_t ld, float* d_out, uint64_t out_stride,
                              hipStream_t s);
 
