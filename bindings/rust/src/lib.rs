@@ -96,6 +96,22 @@ pub struct vrod_where {
     pub hi: i64,
 }
 
+/// The predicate of the row-predicate operations (`vrod_index_count_where` ... `vrod_index_set_tags_where`): the clauses of
+/// `vrod_where` and, when `has_label` is 1, `label == l` on the row's label `l`.  48 bytes, no padding.
+#[repr(C)]
+#[derive(Debug, Clone, Copy, PartialEq, Eq)]
+pub struct vrod_row_pred {
+    pub any: u64,
+    pub all: u64,
+    pub none: u64,
+    pub lo: i64,
+    pub hi: i64,
+    pub label: u32,
+    pub has_label: u32,
+}
+/// `flags` of the row-predicate operations: only the rows the handle's filter allows are in scope.
+pub const VROD_ROWPRED_ALLOWED: u32 = 1;
+
 /// The largest `pool` of `vrod_search_diverse`.
 pub const VROD_MAX_DIVERSE_POOL: u32 = 1024;
 
@@ -276,6 +292,13 @@ extern "C" {
     pub fn vrod_index_update_device(idx: *mut vrod_index, d_ids: *const u64, d_rows: *const c_void, src_dtype: c_int, row_stride: u64, n: u64, stream: *mut c_void) -> c_int;
     pub fn vrod_index_upsert_device(idx: *mut vrod_index, d_keys: *const u64, d_rows: *const c_void, src_dtype: c_int, row_stride: u64, n: u64, d_out_ids: *mut u64, stream: *mut c_void) -> c_int;
     pub fn vrod_index_get_rows_device(idx: *mut vrod_index, first: u64, n: u64, d_out_rows: *mut f32, out_row_stride: u64, stream: *mut c_void) -> c_int;
+    /// Row predicates: `flags` is 0 or `VROD_ROWPRED_ALLOWED`; the columns are read on the device.
+    pub fn vrod_index_count_where(idx: *mut vrod_index, preds: *const vrod_row_pred, n_preds: u32, flags: u32, out_counts: *mut u64) -> c_int;
+    pub fn vrod_index_select_where(idx: *mut vrod_index, pred: *const vrod_row_pred, flags: u32, capacity: u64, out_count: *mut u64, out_ids: *mut u64) -> c_int;
+    pub fn vrod_index_select_where_device(idx: *mut vrod_index, pred: *const vrod_row_pred, flags: u32, capacity: u64, out_count: *mut u64, d_out_ids: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn vrod_index_delete_where(idx: *mut vrod_index, pred: *const vrod_row_pred, flags: u32, out_deleted: *mut u64) -> c_int;
+    pub fn vrod_index_set_filter_where(idx: *mut vrod_index, pred: *const vrod_row_pred, flags: u32) -> c_int;
+    pub fn vrod_index_set_tags_where(idx: *mut vrod_index, pred: *const vrod_row_pred, flags: u32, set_bits: u64, clear_bits: u64, out_changed: *mut u64) -> c_int;
 }
 
 /// Joins the reference's `thiserror` enums (`src/main.rs:36-40`, `src/command/builder.rs:10-15`).

@@ -183,7 +183,8 @@ int vrod_index_live_count(const vrod_index *idx, uint64_t *out);
  * i % 32 of word i / 32 set = id offset + i is allowed.  Rows at index >= n_rows are not allowed, rows added later
  * included.  n_rows > count: VROD_ERR_INVALID_ARG, nothing changes.  (NULL, 0) clears the filter.  Deletes made
  * after the call are honoured.  A multi-device handle routes the bits to its shards (global ids, as deletes).
- * While a search is pending: VROD_ERR_INVALID_ARG. */
+ * While a search is pending: VROD_ERR_INVALID_ARG.  vrod_index_set_filter_where makes the bits from a predicate over the
+ * rows' tags, values and labels on the device: the where-clause of the search forms that take no predicate. */
 int vrod_index_set_filter(vrod_index *idx, const uint32_t *allow_words, uint64_t n_rows);
 /* Rows the next search may return: live and allowed (= vrod_index_live_count without a filter). */
 int vrod_index_filter_count(const vrod_index *idx, uint64_t *out);
@@ -502,6 +503,68 @@ int vrod_search_where(vrod_index *idx, const float *queries, uint32_t nq, uint32
 int vrod_search_where_device(vrod_index *idx, const float *d_queries, uint32_t nq, uint32_t k,
                              const vrod_where *d_preds, uint64_t *d_out_ids, float *d_out_scores,
                              void *stream);
+
+/* Row predicates -- the predicate of vrod_search_where, with the row's label beside it, as an operation on the rows
+ * themselves: count them, list them, delete them, make them the filter, retag them.  A row with tags t, value v and
+ * label l matches the predicate p iff
+ *     (p.any == 0 || (t & p.any) != 0)  &&  (t & p.all) == p.all  &&  (t & p.none) == 0  &&  p.lo <= v  &&  v <= p.hi
+ *     &&  (p.has_label == 0 || l == p.label),
+ * the interval compared as signed values, both ends inclusive.  has_label is 0 or 1 (anything else:
+ * VROD_ERR_INVALID_ARG); label is read only when it is 1.  A column that was never set holds 0 in every row.  lo > hi, or
+ * all & none != 0, can match nothing and costs no pass over the corpus; {0, 0, 0, INT64_MIN, INT64_MAX, 0, 0} matches
+ * every row.
+ * Scope: every operation looks at the LIVE rows below vrod_index_count; with flags = VROD_ROWPRED_ALLOWED only at the
+ * live rows the handle's filter allows -- the rows a search may return (without a filter the flag changes nothing).
+ * Unknown flag bits: VROD_ERR_INVALID_ARG.  Rows between the count and the capacity (vrod_index_reserve) never match.
+ * Common rules: single-device handles only -- a multi-device handle answers VROD_ERR_UNSUPPORTED, outputs and state
+ * untouched; while a search is pending: VROD_ERR_INVALID_ARG; null required pointers: VROD_ERR_INVALID_ARG.  Every check
+ * comes before the first write: a refused or failed call changes nothing.  vrod_index_last_stats is not touched.  Ids are
+ * ids as searches report them, id_offset applied.  The three columns are read on the device and never cross to the host:
+ * the host mirrors of a delete, a filter or a retag are updated from one bit per row.
+ *   count_where   out_counts[i] = rows in scope matching preds[i] (n_preds structs and words, host memory).  Any
+ *                 n_preds, repeats included; n_preds == 0 is VROD_OK; an empty handle gives zeros.  One pass over the
+ *                 columns serves 1024 distinct predicates.
+ *   select_where  the matching ids in ASCENDING order, under the capacity contract of vrod_range_search: *out_count (host
+ *                 memory in both forms) is always exact; *out_count <= capacity: VROD_OK, out_ids[0 .. *out_count) filled,
+ *                 entries past the count not touched; *out_count > capacity: VROD_ERR_CAPACITY, out_ids unspecified;
+ *                 capacity == 0 with a null out_ids is the count-only form.  The _device form writes the ids to device
+ *                 memory (they can feed vrod_search_candidates_device, vrod_index_update_device and
+ *                 vrod_index_ids_to_keys_device without a host trip): the caller's work on `stream` is complete before
+ *                 the library reads, as for vrod_index_find_keys_device, and the call returns when the ids are in place.
+ *   delete_where  exactly what vrod_index_delete does with select_where's ids: tombstones, vrod_index_live_count and
+ *                 vrod_index_filter_count drop, the dead rows' keys are free, and every search afterwards gives what it
+ *                 gives after that vrod_index_delete.  *out_deleted (may be NULL) = rows that died.
+ *   set_filter_where  exactly what vrod_index_set_filter(allow_words, n_rows = count) does with these bits: bit i set
+ *                 iff row i is below the count and matches, WHETHER OR NOT IT IS DELETED; with VROD_ROWPRED_ALLOWED the
+ *                 bit is also ANDed with the current filter's bit for the row, which narrows a filter instead of
+ *                 replacing it.  Rows added later are not allowed; vrod_index_set_filter(NULL, 0) still clears; a
+ *                 predicate that can match nothing gives a filter that allows nothing, not an error.  This is the
+ *                 where-clause of every search form that honours the filter and takes no predicate of its own:
+ *                 vrod_search and its pipelined forms, vrod_range_search, vrod_search_grouped, vrod_search_multivec,
+ *                 vrod_search_diverse, vrod_search_by_ids, vrod_knn_graph, vrod_search_combined and the candidate
+ *                 searches -- one predicate per call.
+ *   set_tags_where  every matching row in scope gets t' = (t & ~clear_bits) | set_bits; set_bits & clear_bits != 0:
+ *                 VROD_ERR_INVALID_ARG.  *out_changed (may be NULL) = rows whose mask actually changed.  On a handle
+ *                 whose tags were never set, set_bits == 0 changes nothing and allocates nothing; otherwise this call
+ *                 creates the column as the first vrod_index_set_tags would.  vrod_index_get_tags and a snapshot see the
+ *                 new masks. */
+#define VROD_ROWPRED_ALLOWED 1u
+typedef struct {
+    uint64_t any, all, none;   /* as vrod_tag_pred */
+    int64_t lo, hi;            /* as vrod_where: signed, both ends inclusive */
+    uint32_t label;            /* compared only when has_label == 1 */
+    uint32_t has_label;        /* 0 or 1 */
+} vrod_row_pred; /* 48 bytes, no padding */
+int vrod_index_count_where(vrod_index *idx, const vrod_row_pred *preds, uint32_t n_preds, uint32_t flags,
+                           uint64_t *out_counts);
+int vrod_index_select_where(vrod_index *idx, const vrod_row_pred *pred, uint32_t flags, uint64_t capacity,
+                            uint64_t *out_count, uint64_t *out_ids);
+int vrod_index_select_where_device(vrod_index *idx, const vrod_row_pred *pred, uint32_t flags, uint64_t capacity,
+                                   uint64_t *out_count, uint64_t *d_out_ids, void *stream);
+int vrod_index_delete_where(vrod_index *idx, const vrod_row_pred *pred, uint32_t flags, uint64_t *out_deleted);
+int vrod_index_set_filter_where(vrod_index *idx, const vrod_row_pred *pred, uint32_t flags);
+int vrod_index_set_tags_where(vrod_index *idx, const vrod_row_pred *pred, uint32_t flags, uint64_t set_bits,
+                              uint64_t clear_bits, uint64_t *out_changed);
 
 /* Grouped search -- the best row of each label, the k best labels per query (a document stored as many chunk rows that
  * share a label: the k best documents, not k chunks of one).  The ELIGIBLE rows of a query are the rows that are live

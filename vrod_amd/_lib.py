@@ -37,6 +37,8 @@ SYMBOLS = [
     "vrod_index_ids_to_keys", "vrod_index_ids_to_keys_device", "vrod_index_delete_keys", "vrod_index_upsert",
     "vrod_index_key_stats",
     "vrod_index_add_device", "vrod_index_update_device", "vrod_index_upsert_device", "vrod_index_get_rows_device",
+    "vrod_index_count_where", "vrod_index_select_where", "vrod_index_select_where_device", "vrod_index_delete_where",
+    "vrod_index_set_filter_where", "vrod_index_set_tags_where",
 ]
 
 ERR_CAPACITY = 8   # VROD_ERR_CAPACITY: a range search's result does not fit the caller's buffers (out_lims is valid)
@@ -193,6 +195,12 @@ def load() -> C.CDLL:
     L.vrod_index_update_device.argtypes = [vp, vp, vp, i32, u64, u64, vp]
     L.vrod_index_upsert_device.argtypes = [vp, vp, vp, i32, u64, u64, vp, vp]
     L.vrod_index_get_rows_device.argtypes = [vp, u64, u64, vp, u64, vp]
+    L.vrod_index_count_where.argtypes = [vp, vp, u32, u32, vp]
+    L.vrod_index_select_where.argtypes = [vp, vp, u32, u64, C.POINTER(u64), vp]
+    L.vrod_index_select_where_device.argtypes = [vp, vp, u32, u64, C.POINTER(u64), vp, vp]
+    L.vrod_index_delete_where.argtypes = [vp, vp, u32, C.POINTER(u64)]
+    L.vrod_index_set_filter_where.argtypes = [vp, vp, u32]
+    L.vrod_index_set_tags_where.argtypes = [vp, vp, u32, u64, u64, C.POINTER(u64)]
     for name in SYMBOLS:
         getattr(L, name).restype = i32
     L.vrod_last_error.restype = C.c_char_p

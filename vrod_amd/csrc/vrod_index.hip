@@ -1864,20 +1864,12 @@ static void mask_changed(vrod_index* idx) {
     }
 }
 
-// Mark local rows (each < count) deleted: the host mirror, then the changed words on the device (allocated for the whole
-// capacity at the first delete); under a filter the effective mask as well.
-static int index_delete_rows(vrod_index* idx, const std::vector<uint64_t>& rows) {
-    std::vector<uint64_t> fresh;   // rows this call deletes (repeats and rows deleted before are no-ops)
-    uint64_t wlo = UINT64_MAX, whi = 0;
-    for (uint64_t r : rows) {
-        uint32_t& w = idx->del_bits[r / 32];
-        const uint32_t bit = 1u << (r % 32);
-        if (w & bit) continue;
-        w |= bit;
-        fresh.push_back(r);
-        wlo = std::min(wlo, r / 32);
-        whi = std::max(whi, r / 32);
-    }
+// "These rows are freshly dead", for every kind of delete (by id, by key, by predicate).  `fresh`: local rows (each <
+// count) that were live until now, each once, whose bits the caller has set in the host mirror del_bits already, all
+// within its words [wlo, whi].  The changed words go to the device (allocated for the whole capacity at the first
+// delete), under a filter the effective mask follows, then the counts, the keys' live count and the mask's generation.
+// A failure takes the rows' bits out of the mirror again: nothing has changed.
+static int commit_fresh_deletes(vrod_index* idx, const std::vector<uint64_t>& fresh, uint64_t wlo, uint64_t whi) {
     if (fresh.empty()) return VROD_OK;
     int rc = set_device(idx);
     hipError_t e = hipSuccess;
@@ -1917,6 +1909,41 @@ static int index_delete_rows(vrod_index* idx, const std::vector<uint64_t>& rows)
         for (uint64_t r : fresh) idx->keyed_live -= idx->keys.host[r] != kKeyNone;
     idx->n_eligible -= lost;
     mask_changed(idx);
+    return VROD_OK;
+}
+
+// Mark local rows (each < count) deleted: the host mirror, then the changed words on the device; under a filter the
+// effective mask as well.
+static int index_delete_rows(vrod_index* idx, const std::vector<uint64_t>& rows) {
+    std::vector<uint64_t> fresh;   // rows this call deletes (repeats and rows deleted before are no-ops)
+    uint64_t wlo = UINT64_MAX, whi = 0;
+    for (uint64_t r : rows) {
+        uint32_t& w = idx->del_bits[r / 32];
+        const uint32_t bit = 1u << (r % 32);
+        if (w & bit) continue;
+        w |= bit;
+        fresh.push_back(r);
+        wlo = std::min(wlo, r / 32);
+        whi = std::max(whi, r / 32);
+    }
+    return commit_fresh_deletes(idx, fresh, wlo, whi);
+}
+
+// ... and the rows of a hit bitmap (bit r set = local row r, live, dies; `words` words): what a delete by predicate
+// gets from the device, one bit per row.
+static int index_delete_hits(vrod_index* idx, const uint32_t* hits, uint64_t words, uint64_t* out_died) {
+    std::vector<uint64_t> fresh;
+    uint64_t wlo = UINT64_MAX, whi = 0;
+    for (uint64_t w = 0; w < words; ++w) {
+        const uint32_t h = hits[w] & ~idx->del_bits[w];   // (the pass's scope leaves deleted rows out already)
+        if (!h) continue;
+        idx->del_bits[w] |= h;
+        for (uint32_t b = h; b; b &= b - 1u) fresh.push_back(w * 32 + (uint64_t)__builtin_ctz(b));
+        wlo = std::min(wlo, w);
+        whi = w;
+    }
+    VROD_TRY(commit_fresh_deletes(idx, fresh, wlo, whi));
+    *out_died = fresh.size();
     return VROD_OK;
 }
 
@@ -5129,6 +5156,210 @@ int vrod_search_where_device(vrod_index* idx, const float* d_queries, uint32_t n
                              float* d_out_scores, void* stream) {
     return pred_search_device<WhereSearch>(idx, "vrod_search_where", "vrod_search_where_device", kValuesNotRouted, d_queries, nq, k, d_preds,
                                            d_out_ids, d_out_scores, stream);
+}
+
+// ------------------------------------------------------------------ row predicates (vrod_index_*_where)
+// A predicate over a row's tags, value and label as an operation on the rows: count, select, delete, filter, retag.  The
+// columns stay on the device (kernels_rowpred.hip); what a mutation brings to the host is ONE BIT PER ROW, the hit
+// bitmap, from which the mirrors are updated by the steps the id-based calls use: commit_fresh_deletes for a delete,
+// index_set_filter for a filter.  Workspaces, the handle being idle: lab_tab [table | totals], lab_cnt the per-group
+// counts, lab_mask the hit bitmap, out_ids a host form's selection.
+static_assert(sizeof(vrod_row_pred) == 48 && sizeof(RowPred) == 48 && offsetof(vrod_row_pred, label) == 40 && offsetof(RowPred, has_label) == 44,
+              "vrod_row_pred is five packed 64-bit words and two 32-bit ones");
+static_assert(kRowPredRowsPerGroup % 64 == 0 && kRowTile % 64 == 0, "a hit bitmap of whole waves lies within capacity / 32 words");
+
+// What the six entry points refuse before they look at the handle's state, then the handle's own refusals, in this order:
+// a null handle or pointer (preds, and every pointer of `needed`), unknown flag bits, has_label beyond 1, a multi-device
+// handle, a pending search.
+static int check_rowpred_args(vrod_index* idx, const char* what, const vrod_row_pred* preds, uint32_t n_preds, uint32_t flags,
+                              std::initializer_list<const void*> needed) {
+    if (!idx) return fail(VROD_ERR_INVALID_ARG, "idx is null");
+    if (n_preds && !preds) return fail(VROD_ERR_INVALID_ARG, "%s: null predicate", what);
+    for (const void* p : needed)
+        if (!p) return fail(VROD_ERR_INVALID_ARG, "%s: null argument", what);
+    if (flags & ~(uint32_t)VROD_ROWPRED_ALLOWED) return fail(VROD_ERR_INVALID_ARG, "%s: unknown flag bits 0x%x", what, flags);
+    for (uint32_t i = 0; i < n_preds; ++i)
+        if (preds[i].has_label > 1u) return fail(VROD_ERR_INVALID_ARG, "%s: has_label is %u in predicate %u, not 0 or 1", what, preds[i].has_label, i);
+    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "%s on a multi-device handle: labels, tags and values are not routed to the shards", what);
+    return require_idle(idx, what);
+}
+
+// The header's struct as the kernels take it; a label that is not compared is 0, so equal predicates have equal bytes.
+static RowPred row_pred_of(const vrod_row_pred& p) { return RowPred{p.any, p.all, p.none, p.lo, p.hi, p.has_label ? p.label : 0u, p.has_label}; }
+
+// Bit set = the row is out of an operation's scope: the deleted rows, and under VROD_ROWPRED_ALLOWED the rows the filter
+// does not allow (the effective mask holds both).  Null: every row below the count is in scope.
+static const uint32_t* rowpred_scope(const vrod_index* idx, uint32_t flags) {
+    if ((flags & VROD_ROWPRED_ALLOWED) && idx->filter_on) return idx->eff_dev.p;
+    return idx->n_deleted ? idx->del_dev.p : nullptr;
+}
+
+// One predicate's hit bitmap over rows [0, count), count > 0, into lab_mask on the handle's stream; counted: each
+// work-group's hits into lab_cnt as well, one word more than the groups (the total's place).
+static int rowpred_hits(vrod_index* idx, const RowPred& p, const uint32_t* scope, bool counted) {
+    VROD_TRY(set_device(idx));
+    VROD_TRY(idx->lab_mask.ensure(row_pred_hit_words(idx->count) * 4));
+    if (counted) VROD_TRY(idx->lab_cnt.ensure(((size_t)row_pred_groups(idx->count) + 1) * 4));
+    launch_rowpred_hits(idx->tags.d(), idx->values.d(), idx->labels.d(), scope, idx->count, p, idx->lab_mask.as<uint32_t>(),
+                        counted ? idx->lab_cnt.as<uint32_t>() : nullptr, idx->stream);
+    HIP_TRY(hipGetLastError());
+    return VROD_OK;
+}
+// ... and brought to the host: the one bit per row that crosses
+static int rowpred_hits_to_host(vrod_index* idx, std::vector<uint32_t>& bits) {
+    bits.resize(row_pred_hit_words(idx->count));
+    HIP_TRY(hipMemcpyAsync(bits.data(), idx->lab_mask.p, bits.size() * 4, hipMemcpyDeviceToHost, idx->stream));
+    HIP_TRY(hipStreamSynchronize(idx->stream));
+    return VROD_OK;
+}
+
+int vrod_index_count_where(vrod_index* idx, const vrod_row_pred* preds, uint32_t n_preds, uint32_t flags, uint64_t* out_counts) {
+    VROD_TRY(check_rowpred_args(idx, "vrod_index_count_where", preds, n_preds, flags, {n_preds ? (const void*)out_counts : (const void*)idx}));
+    if (!n_preds) return VROD_OK;
+    // the distinct satisfiable predicates, in the table's order; slot[i]: where preds[i] is counted
+    std::vector<RowPred> all(n_preds), table;
+    std::vector<uint32_t> order, slot(n_preds, UINT32_MAX);
+    for (uint32_t i = 0; i < n_preds; ++i) {
+        all[i] = row_pred_of(preds[i]);
+        if (!row_pred_unsatisfiable(all[i])) order.push_back(i);
+    }
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return row_pred_before(all[a], all[b]); });
+    for (uint32_t i : order) {
+        if (table.empty() || row_pred_before(table.back(), all[i])) table.push_back(all[i]);
+        slot[i] = (uint32_t)table.size() - 1;
+    }
+    std::vector<uint32_t> totals(table.size(), 0u);
+    if (idx->count && !table.empty()) {
+        VROD_TRY(set_device(idx));
+        hipStream_t s = idx->stream;
+        const uint32_t n_groups = row_pred_groups(idx->count), Gc = (uint32_t)std::min<size_t>(table.size(), kRowPredsPerPass);
+        VROD_TRY(idx->lab_tab.ensure((size_t)Gc * (sizeof(RowPred) + 4)));
+        VROD_TRY(idx->lab_cnt.ensure((size_t)n_groups * Gc * 4));
+        RowPred* d_table = idx->lab_tab.as<RowPred>();
+        uint32_t* d_total = (uint32_t*)(d_table + Gc);
+        const uint32_t* scope = rowpred_scope(idx, flags);
+        for (size_t c0 = 0; c0 < table.size(); c0 += kRowPredsPerPass) {   // one pass over the columns per table
+            const uint32_t Gp = (uint32_t)std::min<size_t>(kRowPredsPerPass, table.size() - c0);
+            HIP_TRY(hipMemcpyAsync(d_table, table.data() + c0, (size_t)Gp * sizeof(RowPred), hipMemcpyHostToDevice, s));
+            launch_rowpred_count(idx->tags.d(), idx->values.d(), idx->labels.d(), scope, idx->count, d_table, Gp, idx->lab_cnt.as<uint32_t>(), Gp, s);
+            launch_group_prefix(idx->lab_cnt.as<uint32_t>(), n_groups, Gp, d_total, s);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(totals.data() + c0, d_total, (size_t)Gp * 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+    }
+    for (uint32_t i = 0; i < n_preds; ++i) out_counts[i] = slot[i] == UINT32_MAX ? 0ull : totals[slot[i]];
+    return VROD_OK;
+}
+
+// Both forms of vrod_index_select_where behind their checks.  d_out: where the ids go on the device (the caller's
+// memory, or null for the host form, which takes the handle's out_ids and copies to h_out).
+static int rowpred_select(vrod_index* idx, const char* what, const vrod_row_pred* pred, uint32_t flags, uint64_t capacity, uint64_t* out_count,
+                          uint64_t* d_out, uint64_t* h_out) {
+    const RowPred p = row_pred_of(*pred);
+    uint32_t total = 0;
+    hipStream_t s = idx->stream;
+    const bool pass = idx->count && !row_pred_unsatisfiable(p);
+    uint32_t* d_first = nullptr;
+    if (pass) {
+        VROD_TRY(rowpred_hits(idx, p, rowpred_scope(idx, flags), true));
+        const uint32_t n_groups = row_pred_groups(idx->count);
+        d_first = idx->lab_cnt.as<uint32_t>();
+        launch_group_prefix(d_first, n_groups, 1, d_first + n_groups, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&total, d_first + n_groups, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    *out_count = total;
+    if (total > capacity)
+        return fail(VROD_ERR_CAPACITY, "%s: %u matching rows, capacity %llu", what, total, (unsigned long long)capacity);
+    if (!total) return VROD_OK;
+    if (!d_out) {
+        VROD_TRY(idx->out_ids.ensure((size_t)total * 8));
+        d_out = idx->out_ids.as<uint64_t>();
+    }
+    launch_rowpred_scatter(idx->lab_mask.as<uint32_t>(), idx->count, d_first, idx->id_offset, d_out, s);
+    HIP_TRY(hipGetLastError());
+    if (h_out) HIP_TRY(hipMemcpyAsync(h_out, d_out, (size_t)total * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return VROD_OK;
+}
+
+int vrod_index_select_where(vrod_index* idx, const vrod_row_pred* pred, uint32_t flags, uint64_t capacity, uint64_t* out_count,
+                            uint64_t* out_ids) {
+    VROD_TRY(check_rowpred_args(idx, "vrod_index_select_where", pred, 1, flags, {pred, out_count, capacity ? (const void*)out_ids : (const void*)pred}));
+    return rowpred_select(idx, "vrod_index_select_where", pred, flags, capacity, out_count, nullptr, out_ids);
+}
+
+int vrod_index_select_where_device(vrod_index* idx, const vrod_row_pred* pred, uint32_t flags, uint64_t capacity, uint64_t* out_count,
+                                   uint64_t* d_out_ids, void* stream) {
+    VROD_TRY(check_rowpred_args(idx, "vrod_index_select_where_device", pred, 1, flags,
+                                {pred, out_count, capacity ? (const void*)d_out_ids : (const void*)pred}));
+    VROD_TRY(begin_sync_device(idx, "vrod_index_select_where_device", stream));
+    return rowpred_select(idx, "vrod_index_select_where_device", pred, flags, capacity, out_count, d_out_ids, nullptr);
+}
+
+int vrod_index_delete_where(vrod_index* idx, const vrod_row_pred* pred, uint32_t flags, uint64_t* out_deleted) {
+    VROD_TRY(check_rowpred_args(idx, "vrod_index_delete_where", pred, 1, flags, {pred}));
+    const RowPred p = row_pred_of(*pred);
+    uint64_t died = 0;
+    if (idx->count && !row_pred_unsatisfiable(p)) {
+        std::vector<uint32_t> bits;
+        VROD_TRY(rowpred_hits(idx, p, rowpred_scope(idx, flags), false));
+        VROD_TRY(rowpred_hits_to_host(idx, bits));
+        VROD_TRY(index_delete_hits(idx, bits.data(), bits.size(), &died));
+    }
+    if (out_deleted) *out_deleted = died;
+    return VROD_OK;
+}
+
+int vrod_index_set_filter_where(vrod_index* idx, const vrod_row_pred* pred, uint32_t flags) {
+    VROD_TRY(check_rowpred_args(idx, "vrod_index_set_filter_where", pred, 1, flags, {pred}));
+    const RowPred p = row_pred_of(*pred);
+    // the allow bits of rows [0, count): a row's bit says whether it matches, deleted or not
+    std::vector<uint32_t> bits(std::max<uint64_t>(row_pred_hit_words(idx->count), 1), 0u);
+    if (idx->count && !row_pred_unsatisfiable(p)) {
+        VROD_TRY(rowpred_hits(idx, p, nullptr, false));
+        VROD_TRY(rowpred_hits_to_host(idx, bits));
+    }
+    if ((flags & VROD_ROWPRED_ALLOWED) && idx->filter_on)   // narrow the filter that is set: what it allows AND matches
+        for (size_t w = 0; w < bits.size(); ++w) bits[w] &= w < idx->allow_bits.size() ? idx->allow_bits[w] : 0u;
+    return index_set_filter(idx, bits.data(), idx->count);
+}
+
+int vrod_index_set_tags_where(vrod_index* idx, const vrod_row_pred* pred, uint32_t flags, uint64_t set_bits, uint64_t clear_bits,
+                              uint64_t* out_changed) {
+    if (idx && (set_bits & clear_bits)) return fail(VROD_ERR_INVALID_ARG, "vrod_index_set_tags_where: set_bits and clear_bits share bits");
+    VROD_TRY(check_rowpred_args(idx, "vrod_index_set_tags_where", pred, 1, flags, {pred}));
+    const RowPred p = row_pred_of(*pred);
+    uint64_t changed = 0;
+    // without a column every row carries 0: clearing bits changes nothing, and nothing is allocated
+    const bool may_change = set_bits || (clear_bits && idx->tags.exists());
+    if (idx->count && !row_pred_unsatisfiable(p) && may_change) {
+        VROD_TRY(set_device(idx));
+        VROD_TRY(idx->lab_mask.ensure(row_pred_hit_words(idx->count) * 4));
+        if (!idx->tags.exists()) {   // as the first set_tags makes it (its clear runs on the null stream: drained before ours reads)
+            VROD_TRY(idx->tags.create(idx->capacity));
+            HIP_TRY(hipStreamSynchronize(nullptr));
+        }
+        std::vector<uint32_t> bits;
+        launch_rowpred_retag(idx->tags.d(), idx->values.d(), idx->labels.d(), rowpred_scope(idx, flags), idx->count, p, set_bits, clear_bits,
+                             idx->lab_mask.as<uint32_t>(), idx->stream);
+        int rc = hipGetLastError() == hipSuccess ? rowpred_hits_to_host(idx, bits) : fail(VROD_ERR_HIP, "vrod_index_set_tags_where: the launch failed");
+        if (rc != VROD_OK) {   // the mirror is the truth: the device column goes back to it
+            (void)hipStreamSynchronize(idx->stream);
+            (void)hipMemcpy(idx->tags.d(), idx->tags.host.data(), idx->count * 8, hipMemcpyHostToDevice);
+            return rc;
+        }
+        for (size_t w = 0; w < bits.size(); ++w)   // the changed rows' masks in the mirror
+            for (uint32_t b = bits[w]; b; b &= b - 1u) {
+                uint64_t& t = idx->tags.host[w * 32 + (size_t)__builtin_ctz(b)];
+                t = (t & ~clear_bits) | set_bits;
+                ++changed;
+            }
+    }
+    if (out_changed) *out_changed = changed;
+    return VROD_OK;
 }
 
 static int check_grouped_args(vrod_index* idx, const void* q, uint32_t nq, uint32_t k, const void* oi, const void* os) {

@@ -8,6 +8,7 @@
 #include "label_plan.h"    // SegEntry
 #include "tag_plan.h"      // TagPred
 #include "where_plan.h"    // WherePred
+#include "rowpred_plan.h"  // RowPred
 #include "multivec_plan.h" // MultivecQuery
 #include "combine_plan.h"  // kCombineMaxExclude, combine_lanes_per_query
 #include "candidates_plan.h" // kCandMaxList, the sort classes, cand_tile_query
@@ -295,6 +296,24 @@ void launch_where_group_scatter(const uint64_t* d_tags, const int64_t* d_vals, c
                                 uint32_t* d_lists, hipStream_t s);
 void launch_where_group_mask(const uint64_t* d_tags, const int64_t* d_vals, const uint32_t* d_mask, uint64_t count, uint64_t n_words,
                              const WherePred& p, uint32_t* d_out, hipStream_t s);
+
+// ---- kernels_rowpred.hip : a predicate over tags, value and label as an operation on the rows (vrod_index_*_where)
+// Every pass gives work-group b rows [b * kRowPredRowsPerGroup, ...): row_pred_groups(count) groups.  A null column:
+// every row carries 0.  d_scope (may be null): bit set = the row is out of scope.
+// d_cnt[b * cnt_ld + g] = the rows of group b in scope that match d_table[g], g < G <= kRowPredsPerPass;
+// launch_group_prefix over the matrix gives the totals.
+void launch_rowpred_count(const uint64_t* d_tags, const int64_t* d_vals, const uint32_t* d_labels, const uint32_t* d_scope, uint64_t count,
+                          const RowPred* d_table, uint32_t G, uint32_t* d_cnt, uint32_t cnt_ld, hipStream_t s);
+// d_hits [row_pred_hit_words(count)]: bit r set = row r < count is in scope and matches p; d_cnt[b] (may be null) = the
+// bits of group b.
+void launch_rowpred_hits(const uint64_t* d_tags, const int64_t* d_vals, const uint32_t* d_labels, const uint32_t* d_scope, uint64_t count,
+                         const RowPred& p, uint32_t* d_hits, uint32_t* d_cnt, hipStream_t s);
+// ... and whose tags t differ from t' = (t & ~clear_bits) | set_bits, which the row then carries.  d_tags is not null.
+void launch_rowpred_retag(uint64_t* d_tags, const int64_t* d_vals, const uint32_t* d_labels, const uint32_t* d_scope, uint64_t count,
+                          const RowPred& p, uint64_t set_bits, uint64_t clear_bits, uint32_t* d_hits, hipStream_t s);
+// d_out[d_first[b] + j] = id_offset + the row of the j-th bit set in group b's words of d_hits (d_first: the prefixed
+// counts): the selection in ascending order.
+void launch_rowpred_scatter(const uint32_t* d_hits, uint64_t count, const uint32_t* d_first, uint64_t id_offset, uint64_t* d_out, hipStream_t s);
 
 // ---- kernels_group.hip : a grouped search's de-duplication by label and the dense stage's per-query masks
 // List b (d_cand_ids / d_cand_scores + b * k1: a search's result row, ids with id_offset applied) of query d_qidx[b] (b

@@ -29,6 +29,10 @@ COMBINED_EXCLUDE_TERMS = 1   # VROD_COMBINED_EXCLUDE_TERMS
 MAX_CANDIDATES = 16384    # VROD_MAX_CANDIDATES
 # vrod_where: one query's predicate of search_where, 40 bytes
 WHERE_DTYPE = np.dtype([("any", np.uint64), ("all", np.uint64), ("none", np.uint64), ("lo", np.int64), ("hi", np.int64)])
+# vrod_row_pred: the predicate of the row-predicate operations (count_where ... set_tags_where), 48 bytes
+ROWPRED_DTYPE = np.dtype([("any", np.uint64), ("all", np.uint64), ("none", np.uint64), ("lo", np.int64), ("hi", np.int64),
+                          ("label", np.uint32), ("has_label", np.uint32)])
+ROWPRED_ALLOWED = 1   # VROD_ROWPRED_ALLOWED: only the rows the filter allows are in scope
 # rows per batch of knn_graph() by storage type (byid_plan.h: kByidBatchF32, kByidBatchBf16)
 KNN_BATCH = {0: 256, 1: 1024}
 
@@ -457,6 +461,155 @@ class Index:
         if p.size != nq:
             raise ValueError(f"preds must hold {nq} predicates, got {p.size}")
         return p
+
+    # -- row predicates
+    @classmethod
+    def _row_preds(cls, preds, n=None) -> np.ndarray:
+        """The predicates of the row-predicate operations -> a contiguous array of ROWPRED_DTYPE (the layout of
+        vrod_row_pred), `n` of them when given.  preds is such a structured array, or an integer [n, 7] array-like with the
+        columns any, all, none (64 unsigned bits), lo, hi (64 signed bits), label (32 unsigned bits) and has_label (0 or
+        1); one predicate may be given as its 7 values.  The ranges are checked as _where checks them."""
+        if isinstance(preds, np.void):   # one element of a structured array
+            preds = np.asarray(preds)
+        if isinstance(preds, np.ndarray) and preds.dtype.names:
+            if preds.dtype != ROWPRED_DTYPE:
+                raise TypeError(f"preds must have dtype {ROWPRED_DTYPE}, got {preds.dtype}")
+            p = np.ascontiguousarray(preds.reshape(-1))
+        else:
+            a = preds if isinstance(preds, np.ndarray) else np.array(preds, dtype=object)   # (a list keeps its Python ints)
+            if a.dtype == object and a.size:
+                if not all(isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_)) for x in a.reshape(-1)):
+                    raise TypeError("preds must hold integers")
+            elif a.dtype.kind not in "iu" and (a.size or isinstance(preds, np.ndarray)):
+                raise TypeError(f"preds must be an integer array, got {a.dtype}")
+            if a.size == 0:
+                a = np.zeros((0, 7), np.int64)
+            if a.ndim == 1 and a.shape[0] == 7:
+                a = a.reshape(1, 7)
+            if a.ndim != 2 or a.shape[1] != 7:
+                raise ValueError(f"preds must have shape (n, 7), got {a.shape}")
+            p = np.empty(a.shape[0], ROWPRED_DTYPE)
+            for j, name in enumerate(ROWPRED_DTYPE.names):
+                col = a[:, j]
+                signed = j in (3, 4)
+                if col.dtype == object:   # Python ints: the column's own range decides
+                    try:
+                        col = col.astype(np.int64 if signed else np.uint64)
+                    except OverflowError:
+                        raise ValueError(f"preds column {name} does not fit 64 {'signed' if signed else 'unsigned'} bits") from None
+                if signed:
+                    p[name] = cls._i64(col, f"preds column {name}")
+                elif j < 3:
+                    p[name] = cls._u64(col, f"preds column {name}", (-1,))
+                else:
+                    p[name] = cls._labels(col)
+        if (p["has_label"] > 1).any():
+            raise ValueError("has_label must be 0 or 1")
+        if n is not None and p.size != n:
+            raise ValueError(f"preds must hold {n} predicates, got {p.size}")
+        return p
+
+    @staticmethod
+    def row_pred(any=0, all=0, none=0, lo=-(1 << 63), hi=(1 << 63) - 1, label=None) -> np.ndarray:   # noqa: A002
+        """One predicate as a [1] array of ROWPRED_DTYPE; label=None: the label is not compared.  The defaults match every row."""
+        return Index._row_preds([[any, all, none, lo, hi, 0 if label is None else label, 0 if label is None else 1]], 1)
+
+    @staticmethod
+    def _rowpred_flags(allowed_only) -> int:
+        if not isinstance(allowed_only, (bool, np.bool_)):
+            raise TypeError(f"allowed_only must be a bool, got {type(allowed_only).__name__}")
+        return ROWPRED_ALLOWED if allowed_only else 0
+
+    def count_where(self, preds, allowed_only: bool = False) -> np.ndarray:
+        """preds (see _row_preds) -> uint64 [n]: the live rows (allowed_only: and allowed by the filter) matching each
+        (vrod_index_count_where).  The columns are read on the device, 1024 distinct predicates per pass."""
+        p = self._row_preds(preds)
+        flags = self._rowpred_flags(allowed_only)
+        out = np.zeros(p.size, dtype=np.uint64)
+        check(self._L.vrod_index_count_where(self._h, _ptr(p), p.size, flags, _ptr(out)))
+        return out
+
+    def select_where(self, pred, allowed_only: bool = False, capacity=None) -> np.ndarray:
+        """The ids of the rows in scope matching one predicate, ascending (vrod_index_select_where).  capacity=None: a
+        count-only call sizes the buffer; else more than `capacity` matching rows raise VrodError with code ERR_CAPACITY
+        (and .count holds the exact count)."""
+        p = self._row_preds(pred, 1)
+        flags = self._rowpred_flags(allowed_only)
+        n = C.c_uint64()
+        if capacity is None:
+            rc = self._L.vrod_index_select_where(self._h, _ptr(p), flags, 0, C.byref(n), None)
+            if rc not in (0, _lib.ERR_CAPACITY):
+                check(rc)
+            capacity = n.value
+            if rc == 0:
+                return np.empty(0, np.uint64)
+        capacity = int(capacity)
+        if capacity < 0:
+            raise ValueError("capacity must not be negative")
+        ids = np.empty(max(capacity, 1), dtype=np.uint64)
+        rc = self._L.vrod_index_select_where(self._h, _ptr(p), flags, capacity, C.byref(n), _ptr(ids) if capacity else None)
+        if rc == _lib.ERR_CAPACITY:
+            e = VrodError(rc, self._L.vrod_last_error().decode("utf-8", "replace"))
+            e.count = n.value
+            raise e
+        check(rc)
+        return ids[:n.value]
+
+    def select_where_device(self, pred, capacity: int, allowed_only: bool = False, out_ids=None):
+        """select_where into a CUDA int64 tensor [capacity] (the bits of uint64) -> (rc, count, ids): rc is 0 or
+        ERR_CAPACITY, count is exact either way, ids[:count] are filled when rc is 0 (vrod_index_select_where_device).  The
+        ids can feed search_candidates_device, update_device and ids_to_keys_device without a host trip."""
+        import torch
+        p = self._row_preds(pred, 1)
+        flags = self._rowpred_flags(allowed_only)
+        capacity = int(capacity)
+        if capacity < 0:
+            raise ValueError("capacity must not be negative")
+        dev = torch.device("cuda", self.device)
+        out_ids = _device_out(out_ids, max(capacity, 1), torch.int64, dev)
+        n_out, _ = self._device_u64(out_ids, "out_ids")
+        if n_out < capacity:
+            raise ValueError(f"out_ids must hold {capacity} ids")
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        n = C.c_uint64()
+        rc = self._L.vrod_index_select_where_device(self._h, _ptr(p), flags, capacity, C.byref(n), out_ids.data_ptr() if capacity else None, stream)
+        if rc not in (0, _lib.ERR_CAPACITY):
+            check(rc)
+        return rc, n.value, out_ids
+
+    def delete_where(self, pred, allowed_only: bool = False) -> int:
+        """Delete every row in scope matching one predicate, as delete() of select_where's ids (vrod_index_delete_where).
+        -> rows that died."""
+        p = self._row_preds(pred, 1)
+        flags = self._rowpred_flags(allowed_only)
+        out = C.c_uint64()
+        check(self._L.vrod_index_delete_where(self._h, _ptr(p), flags, C.byref(out)))
+        return out.value
+
+    def set_filter_where(self, pred, narrow: bool = False):
+        """Make the rows matching one predicate the allow list, deleted rows included, as set_filter() of those bits
+        (vrod_index_set_filter_where); narrow=True keeps only what the current filter allows as well.  The where-clause of
+        every search form that honours the filter."""
+        p = self._row_preds(pred, 1)
+        flags = self._rowpred_flags(narrow)
+        check(self._L.vrod_index_set_filter_where(self._h, _ptr(p), flags))
+
+    def set_tags_where(self, pred, set_bits: int = 0, clear_bits: int = 0, allowed_only: bool = False) -> int:
+        """tags := (tags & ~clear_bits) | set_bits on every row in scope matching one predicate (vrod_index_set_tags_where).
+        -> rows whose mask changed."""
+        p = self._row_preds(pred, 1)
+        flags = self._rowpred_flags(allowed_only)
+        for b in (set_bits, clear_bits):
+            if not isinstance(b, (int, np.integer)) or isinstance(b, (bool, np.bool_)):
+                raise TypeError("set_bits and clear_bits must be integers")
+            if not 0 <= int(b) <= 0xFFFFFFFFFFFFFFFF:
+                raise ValueError("set_bits and clear_bits must fit 64 unsigned bits")
+        bits = (int(set_bits), int(clear_bits))
+        if bits[0] & bits[1]:
+            raise ValueError("set_bits and clear_bits share bits")
+        out = C.c_uint64()
+        check(self._L.vrod_index_set_tags_where(self._h, _ptr(p), flags, bits[0], bits[1], C.byref(out)))
+        return out.value
 
     def set_id_offset(self, off: int):
         check(self._L.vrod_index_set_id_offset(self._h, int(off)))
