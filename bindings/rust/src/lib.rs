@@ -112,6 +112,24 @@ pub struct vrod_row_pred {
 /// `flags` of the row-predicate operations: only the rows the handle's filter allows are in scope.
 pub const VROD_ROWPRED_ALLOWED: u32 = 1;
 
+/// `flags` of the duplicate-row calls: the class key is (label, row bits), so equal rows of two documents stay apart.
+pub const VROD_DUP_WITHIN_LABEL: u32 = 1;
+/// A diagnostic for tests: the row hash is cut to 8 bits; results are identical with and without it.
+pub const VROD_DUP_NARROW_HASH: u32 = 0x8000_0000;
+/// What `vrod_index_find_duplicates` reports: the first four fields are exact and reproducible, the last three are
+/// diagnostics of one call's hash table.
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default, PartialEq, Eq)]
+pub struct vrod_dup_stats {
+    pub live: u64,
+    pub classes: u64,
+    pub duplicates: u64,
+    pub largest_class: u64,
+    pub slots: u64,
+    pub max_probe: u64,
+    pub compare_misses: u64,
+}
+
 /// The largest `pool` of `vrod_search_diverse`.
 pub const VROD_MAX_DIVERSE_POOL: u32 = 1024;
 
@@ -299,6 +317,11 @@ extern "C" {
     pub fn vrod_index_delete_where(idx: *mut vrod_index, pred: *const vrod_row_pred, flags: u32, out_deleted: *mut u64) -> c_int;
     pub fn vrod_index_set_filter_where(idx: *mut vrod_index, pred: *const vrod_row_pred, flags: u32) -> c_int;
     pub fn vrod_index_set_tags_where(idx: *mut vrod_index, pred: *const vrod_row_pred, flags: u32, set_bits: u64, clear_bits: u64, out_changed: *mut u64) -> c_int;
+    /// Duplicate rows: `out_first[i]` = the smallest id among the live rows whose stored bits equal row i's (`map_len` =
+    /// `vrod_index_count`, or null and 0 for the stats alone); `delete_duplicates` keeps that smallest id of every class.
+    pub fn vrod_index_find_duplicates(idx: *mut vrod_index, flags: u32, out_first: *mut u64, map_len: u64, out_stats: *mut vrod_dup_stats) -> c_int;
+    pub fn vrod_index_find_duplicates_device(idx: *mut vrod_index, flags: u32, d_out_first: *mut u64, map_len: u64, out_stats: *mut vrod_dup_stats, stream: *mut c_void) -> c_int;
+    pub fn vrod_index_delete_duplicates(idx: *mut vrod_index, flags: u32, out_deleted: *mut u64) -> c_int;
 }
 
 /// Joins the reference's `thiserror` enums (`src/main.rs:36-40`, `src/command/builder.rs:10-15`).

@@ -566,6 +566,57 @@ int vrod_index_set_filter_where(vrod_index *idx, const vrod_row_pred *pred, uint
 int vrod_index_set_tags_where(vrod_index *idx, const vrod_row_pred *pred, uint32_t flags, uint64_t set_bits,
                               uint64_t clear_bits, uint64_t *out_changed);
 
+/* Duplicate rows -- the classes of LIVE rows whose stored form is bit-identical, found in one read of the corpus.
+ * Two live rows are duplicates when the dim stored elements of their prepared rows -- what vrod_index_get_rows reads
+ * back: 16 bits per element on a BF16 handle, 32 on an F32 handle -- have the same bits.  -0.0 and +0.0 differ.  Under
+ * COSINE this is equality after normalisation (x and 2x land in one class), on a BF16 handle equality after rounding.
+ * The padding up to the row pitch is never compared.  Searches score prepared rows only, so the rows of one class have
+ * identical score bits against every query under every metric: they are the ties a search cannot separate.  Deleted
+ * rows belong to no class; the filter is not consulted, as with keys.  With VROD_DUP_WITHIN_LABEL the class key is
+ * (label, row bits): equal rows with different labels (the same chunk in two documents or two tenants) are then not
+ * duplicates; a handle that never set labels has label 0 everywhere.  A hash only chooses which rows are compared;
+ * every class rests on a comparison of the rows themselves, so the result is exact.
+ *   find_duplicates   out_first (host memory) may be NULL with map_len == 0, a stats-only call; otherwise map_len must
+ *                     equal vrod_index_count (the rule of vrod_index_compact's map), anything else is
+ *                     VROD_ERR_INVALID_ARG.  out_first[i] = the smallest id, id_offset applied, among the live rows of the
+ *                     class of row offset + i: a row without a copy gets its own id, a deleted row VROD_ID_NONE.  The
+ *                     array is a function of the handle's state alone: every call gives the same one.
+ *                     *out_stats (may be NULL): live, classes, duplicates and largest_class are exact and
+ *                     reproducible; slots, max_probe and compare_misses are DIAGNOSTICS of this call's hash table and
+ *                     may differ between calls.
+ *   find_duplicates_device  d_out_first is device memory on the handle's device; the stream rules are those of
+ *                     vrod_index_find_keys_device (the caller's work on `stream` is complete before the library writes,
+ *                     the call returns when the map is in place).  The stats still come back to host memory.
+ *   delete_duplicates deletes every live row whose out_first is not its own id, exactly as vrod_index_delete of those ids
+ *                     would: tombstones, the dead rows' keys free, vrod_index_filter_count and vrod_index_live_count
+ *                     drop.  *out_deleted (may be NULL) = rows that died = stats.duplicates.  THE SURVIVOR OF A CLASS IS
+ *                     ITS SMALLEST ID; a caller who wants another rule calls find_duplicates and deletes for themselves.
+ *                     Nothing moves: vrod_index_compact reclaims the space as for any delete.
+ * VROD_DUP_NARROW_HASH is a diagnostic for tests: the row hash is cut to 8 bits before it is used, so that unequal rows
+ * meet in the table on a corpus of a few hundred rows.  Results are identical with and without it.
+ * Common rules: single-device handles only -- a multi-device handle answers VROD_ERR_UNSUPPORTED; while a search is
+ * pending: VROD_ERR_INVALID_ARG; unknown flag bits: VROD_ERR_INVALID_ARG; an empty handle, or one with no live row:
+ * VROD_OK and all-zero stats.  Every check and allocation comes before the first write: a refused call,
+ * VROD_ERR_OUT_OF_MEMORY included, leaves outputs and handle untouched.  The table lives in device memory for the length
+ * of the call only (44 to 76 bytes per live row); every walk of it is bounded by its slot count, and one that runs out is
+ * VROD_ERR_INTERNAL, not a hang.  Nothing is persisted: a snapshot does not change. */
+#define VROD_DUP_WITHIN_LABEL 1u
+#define VROD_DUP_NARROW_HASH  0x80000000u   /* diagnostic: see above */
+typedef struct {
+    uint64_t live;            /* live rows looked at */
+    uint64_t classes;         /* distinct stored rows among them */
+    uint64_t duplicates;      /* live - classes: what vrod_index_delete_duplicates would delete */
+    uint64_t largest_class;   /* rows in the largest class, 0 on a handle with no live row */
+    uint64_t slots;           /* diagnostic: table size of this call */
+    uint64_t max_probe;       /* diagnostic, may differ between calls */
+    uint64_t compare_misses;  /* diagnostic: full row comparisons that found a difference */
+} vrod_dup_stats;
+int vrod_index_find_duplicates(vrod_index *idx, uint32_t flags, uint64_t *out_first, uint64_t map_len,
+                               vrod_dup_stats *out_stats);
+int vrod_index_find_duplicates_device(vrod_index *idx, uint32_t flags, uint64_t *d_out_first, uint64_t map_len,
+                                      vrod_dup_stats *out_stats, void *stream);
+int vrod_index_delete_duplicates(vrod_index *idx, uint32_t flags, uint64_t *out_deleted);
+
 /* Grouped search -- the best row of each label, the k best labels per query (a document stored as many chunk rows that
  * share a label: the k best documents, not k chunks of one).  The ELIGIBLE rows of a query are the rows that are live
  * and, while a filter is set, allowed by the handle's filter.  Every label carried by at least one eligible row has one

@@ -40,6 +40,7 @@
 #include "label_plan.h"
 #include "tag_plan.h"
 #include "where_plan.h"
+#include "dup_plan.h"
 #include "group_plan.h"
 #include "multivec_plan.h"
 #include "diverse_plan.h"
@@ -5359,6 +5360,134 @@ int vrod_index_set_tags_where(vrod_index* idx, const vrod_row_pred* pred, uint32
             }
     }
     if (out_changed) *out_changed = changed;
+    return VROD_OK;
+}
+
+// ------------------------------------------------------------------ duplicate rows (vrod_index_find_duplicates, _delete_duplicates)
+// The classes of live rows with the same stored bits (dup_plan.h, kernels_dup.hip, DESIGN.md "Duplicate rows"): a hash
+// pass over the corpus, a class pass through a table that lives for this call only, an output pass.  What crosses to
+// the host is the counters and, in the host form, the map -- for a delete one bit per row, which index_delete_hits turns
+// into tombstones as it does for a delete by predicate.  Workspaces, the handle being idle: the call's own block (given
+// back on return: 44 to 76 bytes per live row are too much to keep), out_ids for a host form's map, lab_mask for a
+// delete's bitmap.
+static_assert(sizeof(vrod_dup_stats) == 56 && sizeof(DupCounters) == 32, "seven 64-bit words; the counters keep what follows them 8-byte aligned");
+static_assert(kDupEmpty == kScatterSkip && (uint64_t)kDupEmpty > 0xFFFFFF00ull, "no row of a shard is the empty slot's word");
+
+static int check_dup_args(vrod_index* idx, const char* what, uint32_t flags, const void* out_first, uint64_t map_len) {
+    if (!idx) return fail(VROD_ERR_INVALID_ARG, "idx is null");
+    if (flags & ~(uint32_t)(VROD_DUP_WITHIN_LABEL | VROD_DUP_NARROW_HASH)) return fail(VROD_ERR_INVALID_ARG, "%s: unknown flag bits 0x%x", what, flags);
+    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "%s on a multi-device handle: equal rows may lie on different shards", what);
+    VROD_TRY(require_idle(idx, what));
+    if (out_first ? map_len != idx->count : map_len != 0)
+        return fail(VROD_ERR_INVALID_ARG, "%s: a map of %llu entries for a handle of %llu rows", what, (unsigned long long)map_len, (unsigned long long)idx->count);
+    return VROD_OK;
+}
+
+// The three passes behind their checks, on the handle's stream, complete on return.  d_out_first (may be null): the map,
+// device memory; want_hits: lab_mask gets the bitmap of the live rows that are not their class's first.  Everything that
+// can be refused comes before the first write.  *st is written on success only.
+static int dup_run(vrod_index* idx, const char* what, uint32_t flags, uint64_t* d_out_first, bool want_hits, vrod_dup_stats* st) {
+    const uint64_t count = idx->count, live = idx->live();
+    vrod_dup_stats out{};
+    VROD_TRY(set_device(idx));
+    hipStream_t s = idx->stream;
+    if (!live) {   // no class: every row of the map is a deleted row's
+        if (d_out_first && count) {
+            HIP_TRY(hipMemsetAsync(d_out_first, 0xFF, count * 8, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+        *st = out;
+        return VROD_OK;
+    }
+    if (!dup_pitch_ok(idx->dim, (uint32_t)idx->esize, idx->ld)) return fail(VROD_ERR_INTERNAL, "%s: a row pitch of %u elements", what, idx->ld);
+    const bool within = (flags & VROD_DUP_WITHIN_LABEL) != 0, narrow = (flags & VROD_DUP_NARROW_HASH) != 0;
+    const uint64_t slots = dup_table_slots(live);
+    // the call's block: [hash (u64, count) | counters | slot_row (slots) | slot_min (slots) | row_slot (count)]
+    const size_t at_ctr = count * 8, at_tab = at_ctr + sizeof(DupCounters), at_rows = at_tab + slots * 8, total = at_rows + count * 4;
+    DevMem<> ws;
+    HIP_TRY(ws.alloc(total));
+    if (want_hits) VROD_TRY(idx->lab_mask.ensure(row_pred_hit_words(count) * 4));
+    uint64_t* d_hash = ws.get<uint64_t>();
+    DupCounters* d_ctr = (DupCounters*)(ws.get<char>() + at_ctr);
+    DupTable T;
+    T.slot_row = (uint32_t*)(ws.get<char>() + at_tab);
+    T.slot_min = T.slot_row + slots;
+    T.row_slot = (uint32_t*)(ws.get<char>() + at_rows);
+    T.slots = slots;
+    const uint32_t* del = idx->n_deleted ? idx->del_dev.p : nullptr;
+    const uint32_t* labels = within ? idx->labels.d() : nullptr;   // (null: every row carries label 0)
+    static const bool timed = [] { const char* e = getenv("VROD_DEBUG_DUP_TIMING"); return e && e[0] == '1'; }();
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (timed) { HIP_TRY(hipEventCreate(&ev[0])); HIP_TRY(hipEventCreate(&ev[1])); }
+
+    HIP_TRY(hipMemsetAsync(d_ctr, 0, sizeof(DupCounters), s));
+    HIP_TRY(hipMemsetAsync(T.slot_row, 0xFF, slots * 8, s));   // both arrays: empty slots, all-ones minima
+    if (timed) HIP_TRY(hipEventRecord(ev[0], s));
+    launch_dup_hash(idx->corpus.p, idx->dim, idx->ld, (uint32_t)idx->esize, count, del, labels, within, narrow, d_hash, s);
+    if (timed) HIP_TRY(hipEventRecord(ev[1], s));
+    launch_dup_class(idx->corpus.p, idx->dim, idx->ld, (uint32_t)idx->esize, count, del, labels, within, d_hash, T, d_ctr, s);
+    // the hashes are done with: the first count words of their block count the classes' rows
+    HIP_TRY(hipMemsetAsync(d_hash, 0, count * 4, s));
+    launch_dup_output(count, del, T, idx->id_offset, d_out_first, (uint32_t*)d_hash, want_hits ? idx->lab_mask.as<uint32_t>() : nullptr, d_ctr, s);
+    HIP_TRY(hipGetLastError());
+    DupCounters c{};
+    HIP_TRY(hipMemcpyAsync(&c, d_ctr, sizeof c, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (timed) {   // one line on stderr (scripts/probes/dup_probe.py)
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        fprintf(stderr, "{\"vrod_dup_hash_ms\": %.6f, \"live\": %llu, \"slots\": %llu}\n", ms, (unsigned long long)live, (unsigned long long)slots);
+        (void)hipEventDestroy(ev[0]);
+        (void)hipEventDestroy(ev[1]);
+    }
+    if (c.err)
+        return fail(VROD_ERR_INTERNAL, "%s: the class table's walk failed (%s)", what, c.err & kDupErrFull ? "ran over every slot" : "a slot names no row");
+    out.live = live;
+    out.classes = c.classes;
+    out.duplicates = live - c.classes;
+    out.largest_class = c.largest_class;
+    out.slots = slots;
+    out.max_probe = c.max_probe;
+    out.compare_misses = c.compare_misses;
+    *st = out;
+    return VROD_OK;
+}
+
+int vrod_index_find_duplicates(vrod_index* idx, uint32_t flags, uint64_t* out_first, uint64_t map_len, vrod_dup_stats* out_stats) {
+    VROD_TRY(check_dup_args(idx, "vrod_index_find_duplicates", flags, out_first, map_len));
+    const bool map = out_first && idx->count;
+    if (map) VROD_TRY(set_device(idx));
+    if (map) VROD_TRY(idx->out_ids.ensure(idx->count * 8));
+    vrod_dup_stats st{};
+    VROD_TRY(dup_run(idx, "vrod_index_find_duplicates", flags, map ? idx->out_ids.as<uint64_t>() : nullptr, false, &st));
+    if (map) HIP_TRY(hipMemcpy(out_first, idx->out_ids.p, idx->count * 8, hipMemcpyDeviceToHost));
+    if (out_stats) *out_stats = st;
+    return VROD_OK;
+}
+
+int vrod_index_find_duplicates_device(vrod_index* idx, uint32_t flags, uint64_t* d_out_first, uint64_t map_len, vrod_dup_stats* out_stats,
+                                      void* stream) {
+    VROD_TRY(check_dup_args(idx, "vrod_index_find_duplicates_device", flags, d_out_first, map_len));
+    VROD_TRY(begin_sync_device(idx, "vrod_index_find_duplicates_device", stream));
+    vrod_dup_stats st{};
+    VROD_TRY(dup_run(idx, "vrod_index_find_duplicates_device", flags, d_out_first, false, &st));
+    if (out_stats) *out_stats = st;
+    return VROD_OK;
+}
+
+int vrod_index_delete_duplicates(vrod_index* idx, uint32_t flags, uint64_t* out_deleted) {
+    VROD_TRY(check_dup_args(idx, "vrod_index_delete_duplicates", flags, nullptr, 0));
+    uint64_t died = 0;
+    if (idx->live()) {
+        vrod_dup_stats st{};
+        std::vector<uint32_t> bits;
+        VROD_TRY(dup_run(idx, "vrod_index_delete_duplicates", flags, nullptr, true, &st));
+        if (st.duplicates) {
+            VROD_TRY(rowpred_hits_to_host(idx, bits));
+            VROD_TRY(index_delete_hits(idx, bits.data(), bits.size(), &died));
+        }
+    }
+    if (out_deleted) *out_deleted = died;
     return VROD_OK;
 }
 

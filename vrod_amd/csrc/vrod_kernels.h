@@ -315,6 +315,36 @@ void launch_rowpred_retag(uint64_t* d_tags, const int64_t* d_vals, const uint32_
 // counts): the selection in ascending order.
 void launch_rowpred_scatter(const uint32_t* d_hits, uint64_t count, const uint32_t* d_first, uint64_t id_offset, uint64_t* d_out, hipStream_t s);
 
+// ---- kernels_dup.hip : the classes of live rows with the same stored bits (vrod_index_find_duplicates, _delete_duplicates)
+// The table of one call (dup_plan.h): slot_row / slot_min [slots], all-ones before the class pass; row_slot [count].
+struct DupTable {
+    uint32_t* slot_row = nullptr;   // the row that claimed the slot, kDupEmpty = none
+    uint32_t* slot_min = nullptr;   // the smallest row of the slot's class
+    uint32_t* row_slot = nullptr;   // [count]: the slot of every live row
+    uint64_t slots = 0;             // a power of two
+};
+// what the passes leave for the host, cleared by the host in front of them
+struct DupCounters {
+    unsigned long long classes;          // output: live rows that are their class's first
+    unsigned long long compare_misses;   // class: full comparisons that found a difference
+    uint32_t largest_class;              // output
+    uint32_t max_probe;                  // class: the longest walk, in slots
+    uint32_t err;                        // kDupErrFull | kDupErrSlot
+    uint32_t pad;
+};
+// d_hash[r] = the hash (dup_plan.h dup_row_hash; within: the row's label mixed in, d_labels null: label 0) of every row
+// r < count not set in d_del (may be null).  The corpus is read once, nothing else of it is touched.
+void launch_dup_hash(const void* d_corpus, uint32_t dim, uint32_t ld, uint32_t esize, uint64_t count, const uint32_t* d_del, const uint32_t* d_labels,
+                     bool within, bool narrow, uint64_t* d_hash, hipStream_t s);
+// Every live row finds or claims the slot of its class: T.row_slot, T.slot_min; *d_ctr (zero before) gets the diagnostics.
+void launch_dup_class(const void* d_corpus, uint32_t dim, uint32_t ld, uint32_t esize, uint64_t count, const uint32_t* d_del, const uint32_t* d_labels,
+                      bool within, const uint64_t* d_hash, const DupTable& T, DupCounters* d_ctr, hipStream_t s);
+// d_out_first [count] (may be null) = id_offset + the smallest row of the row's class, all-ones for a deleted row;
+// d_class_size [count] is zero before; d_hits (may be null; row_pred_hit_words(count) words): bit r set = row r is live
+// and not the first of its class.  Nothing is written when *d_ctr carries an error.
+void launch_dup_output(uint64_t count, const uint32_t* d_del, const DupTable& T, uint64_t id_offset, uint64_t* d_out_first, uint32_t* d_class_size,
+                       uint32_t* d_hits, DupCounters* d_ctr, hipStream_t s);
+
 // ---- kernels_group.hip : a grouped search's de-duplication by label and the dense stage's per-query masks
 // List b (d_cand_ids / d_cand_scores + b * k1: a search's result row, ids with id_offset applied) of query d_qidx[b] (b
 // itself when d_qidx is null): the first entry of every label that is not among the d_found[q] < k results already in

@@ -12,7 +12,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import KeyStats, MultivecStats, SearchStats, SnapshotInfo, VrodError, check
+from ._lib import DupStats, KeyStats, MultivecStats, SearchStats, SnapshotInfo, VrodError, check
 
 DTYPE_F32, DTYPE_BF16 = 0, 1
 SRC_F32, SRC_BF16, SRC_F16 = 0, 1, 2   # vrod_src_dtype: the element type of rows given in device memory
@@ -33,6 +33,8 @@ WHERE_DTYPE = np.dtype([("any", np.uint64), ("all", np.uint64), ("none", np.uint
 ROWPRED_DTYPE = np.dtype([("any", np.uint64), ("all", np.uint64), ("none", np.uint64), ("lo", np.int64), ("hi", np.int64),
                           ("label", np.uint32), ("has_label", np.uint32)])
 ROWPRED_ALLOWED = 1   # VROD_ROWPRED_ALLOWED: only the rows the filter allows are in scope
+DUP_WITHIN_LABEL = 1            # VROD_DUP_WITHIN_LABEL: the class key is (label, row bits)
+DUP_NARROW_HASH = 0x80000000    # VROD_DUP_NARROW_HASH: a diagnostic, the row hash cut to 8 bits
 # rows per batch of knn_graph() by storage type (byid_plan.h: kByidBatchF32, kByidBatchBf16)
 KNN_BATCH = {0: 256, 1: 1024}
 
@@ -609,6 +611,49 @@ class Index:
             raise ValueError("set_bits and clear_bits share bits")
         out = C.c_uint64()
         check(self._L.vrod_index_set_tags_where(self._h, _ptr(p), flags, bits[0], bits[1], C.byref(out)))
+        return out.value
+
+    # -- duplicate rows
+    @staticmethod
+    def _dup_flags(within_label, narrow_hash=False) -> int:
+        for name, v in (("within_label", within_label), ("narrow_hash", narrow_hash)):
+            if not isinstance(v, (bool, np.bool_)):
+                raise TypeError(f"{name} must be a bool, got {type(v).__name__}")
+        return (DUP_WITHIN_LABEL if within_label else 0) | (DUP_NARROW_HASH if narrow_hash else 0)
+
+    def find_duplicates(self, within_label: bool = False, narrow_hash: bool = False, stats: bool = False):
+        """uint64 [count]: entry i = the smallest id among the live rows whose stored bits equal row i's (its own id when it
+        has no copy), ID_NONE for a deleted row (vrod_index_find_duplicates).  within_label: equal rows with different
+        labels are not duplicates.  narrow_hash: a diagnostic, the same result through an 8-bit hash.  stats=True:
+        -> (map, dict of vrod_dup_stats)."""
+        flags = self._dup_flags(within_label, narrow_hash)
+        n = self.count
+        out = np.empty(max(n, 1), dtype=np.uint64)
+        st = DupStats()
+        check(self._L.vrod_index_find_duplicates(self._h, flags, _ptr(out) if n else None, n, C.byref(st)))
+        return (out[:n], st.as_dict()) if stats else out[:n]
+
+    def find_duplicates_device(self, within_label: bool = False, narrow_hash: bool = False, out_first=None):
+        """find_duplicates into a CUDA int64 tensor [count] (the bits of uint64), complete on return -> (map, stats dict)
+        (vrod_index_find_duplicates_device)."""
+        import torch
+        flags = self._dup_flags(within_label, narrow_hash)
+        n = self.count
+        dev = torch.device("cuda", self.device)
+        out_first = _device_out(out_first, max(n, 1), torch.int64, dev)
+        n_out, stream = self._device_u64(out_first, "out_first")
+        if n_out < n:
+            raise ValueError(f"out_first must hold {n} ids")
+        st = DupStats()
+        check(self._L.vrod_index_find_duplicates_device(self._h, flags, out_first.data_ptr() if n else None, n, C.byref(st), stream))
+        return out_first, st.as_dict()
+
+    def delete_duplicates(self, within_label: bool = False) -> int:
+        """Delete every live row that is not the smallest id of its class, as delete() of those ids
+        (vrod_index_delete_duplicates).  -> rows that died."""
+        flags = self._dup_flags(within_label)
+        out = C.c_uint64()
+        check(self._L.vrod_index_delete_duplicates(self._h, flags, C.byref(out)))
         return out.value
 
     def set_id_offset(self, off: int):
