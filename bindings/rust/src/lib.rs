@@ -130,6 +130,24 @@ pub struct vrod_dup_stats {
     pub compare_misses: u64,
 }
 
+/// `flags` of the near-duplicate calls.  A diagnostic for tests: the hit pool of the call holds exactly as many entries as
+/// there are eligible rows, so batches split on a small corpus; results are identical with and without it.
+pub const VROD_NEAR_SMALL_POOL: u32 = 0x8000_0000;
+/// What `vrod_index_find_near_duplicates` reports: the first five fields are exact and reproducible, the last three are
+/// diagnostics of how one call cut its work.
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default, PartialEq, Eq)]
+pub struct vrod_near_stats {
+    pub rows: u64,
+    pub classes: u64,
+    pub near_duplicates: u64,
+    pub largest_class: u64,
+    pub hits: u64,
+    pub batches: u64,
+    pub splits: u64,
+    pub pool_entries: u64,
+}
+
 /// The largest `pool` of `vrod_search_diverse`.
 pub const VROD_MAX_DIVERSE_POOL: u32 = 1024;
 
@@ -322,6 +340,13 @@ extern "C" {
     pub fn vrod_index_find_duplicates(idx: *mut vrod_index, flags: u32, out_first: *mut u64, map_len: u64, out_stats: *mut vrod_dup_stats) -> c_int;
     pub fn vrod_index_find_duplicates_device(idx: *mut vrod_index, flags: u32, d_out_first: *mut u64, map_len: u64, out_stats: *mut vrod_dup_stats, stream: *mut c_void) -> c_int;
     pub fn vrod_index_delete_duplicates(idx: *mut vrod_index, flags: u32, out_deleted: *mut u64) -> c_int;
+    /// Near-duplicate rows: `out_first[i]` = the smallest id of row i's class, the connected component -- among the eligible
+    /// rows: live, allowed by the filter -- of the graph that joins two rows when one's stored form scores the other at
+    /// least as well as `threshold` (single linkage: a~b and b~c put a and c together).  `map_len` as for
+    /// `vrod_index_find_duplicates`; `delete_near_duplicates` keeps the smallest id of every class.
+    pub fn vrod_index_find_near_duplicates(idx: *mut vrod_index, threshold: f32, flags: u32, out_first: *mut u64, map_len: u64, out_stats: *mut vrod_near_stats) -> c_int;
+    pub fn vrod_index_find_near_duplicates_device(idx: *mut vrod_index, threshold: f32, flags: u32, d_out_first: *mut u64, map_len: u64, out_stats: *mut vrod_near_stats, stream: *mut c_void) -> c_int;
+    pub fn vrod_index_delete_near_duplicates(idx: *mut vrod_index, threshold: f32, flags: u32, out_deleted: *mut u64) -> c_int;
 }
 
 /// Joins the reference's `thiserror` enums (`src/main.rs:36-40`, `src/command/builder.rs:10-15`).

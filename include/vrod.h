@@ -617,6 +617,62 @@ int vrod_index_find_duplicates_device(vrod_index *idx, uint32_t flags, uint64_t 
                                       vrod_dup_stats *out_stats, void *stream);
 int vrod_index_delete_duplicates(vrod_index *idx, uint32_t flags, uint64_t *out_deleted);
 
+/* Near-duplicate rows -- the classes of ELIGIBLE rows that a score threshold ties together: the re-encoded paragraph,
+ * the chunk of a second crawl, a row and its bf16-rounded twin.  The range counterpart of vrod_knn_graph and the
+ * similarity counterpart of vrod_index_find_duplicates.
+ * Rows.  The ELIGIBLE rows: live and, while a filter is set, allowed -- the rule of every score-based call, and UNLIKE
+ * vrod_index_find_duplicates, WHICH IGNORES THE FILTER: vrod_index_set_filter_where + find_near_duplicates is "dedupe
+ * within this tenant / predicate".  A row that is not eligible belongs to no class, gets VROD_ID_NONE and is never
+ * deleted by these calls.
+ * Edge.  Eligible rows i != j are joined when j qualifies for i, or i for j, in the sense of a range search whose query
+ * is the prepared row AS STORED (the rule of vrod_search_by_ids: not normalised again, not rounded again) and whose
+ * comparison is vrod_range_search's: canonical score s >= threshold (COSINE, IP) or s <= threshold (L2), as fp32
+ * values, inclusive; a NaN score never qualifies.  With the canonical chains (left-to-right q*x, or (q-x)^2) the relation
+ * is symmetric bit for bit; the definition does not depend on that.  A NaN threshold is VROD_ERR_INVALID_VALUE, +-inf is
+ * allowed.
+ * Classes.  The connected components of that graph: SINGLE LINKAGE at the threshold.  CHAINING: a~b and b~c put a and c
+ * in one class even when a and c do not qualify for each other -- a loose threshold can string a whole corpus together.
+ *   find_near_duplicates  out_first (host memory) may be NULL with map_len == 0, a stats-only call; otherwise map_len must
+ *                     equal vrod_index_count, anything else is VROD_ERR_INVALID_ARG (the rule of find_duplicates).
+ *                     out_first[i] = the smallest id, id_offset applied, among the rows of the class of row offset + i: a
+ *                     row with no qualifying neighbour gets its own id, a row that is not eligible VROD_ID_NONE.
+ *                     *out_stats (may be NULL): rows, classes, near_duplicates, largest_class and hits are exact.  The
+ *                     map and those five are functions of the handle's state and the threshold alone; batches, splits
+ *                     and pool_entries are DIAGNOSTICS of how this call cut its work.
+ *   find_near_duplicates_device  d_out_first is device memory on the handle's device; the stream rules are those of
+ *                     vrod_index_find_duplicates_device.  The stats still come back to host memory.
+ *   delete_near_duplicates  deletes every eligible row whose out_first is not its own id, exactly as vrod_index_delete
+ *                     of those ids would.  THE SURVIVOR OF A CLASS IS ITS SMALLEST ID.  *out_deleted (may be NULL) =
+ *                     rows that died = stats.near_duplicates.  Nothing moves (vrod_index_compact reclaims the space).
+ * VROD_NEAR_SMALL_POOL is a diagnostic for tests: the hit pool of the call holds exactly as many entries as there are
+ * eligible rows, so that batches are split on a corpus of a few thousand rows.  Results are identical with and without it.
+ * Cost.  One scan of the eligible rows per batch of eligible rows (1024 rows of a BF16 handle, 256 of an F32 handle):
+ * quadratic in the corpus, as vrod_knn_graph.  It is also at least linear in `hits`, and a LOOSE THRESHOLD MAKES `hits`
+ * QUADRATIC TOO: a batch whose hits overflow the call's pool (64 MiB, or 16 bytes per eligible row if that is more) is
+ * scanned again in halves.  vrod_index_set_path is honoured as by a range search.
+ * Common rules: single-device handles only -- a multi-device handle answers VROD_ERR_UNSUPPORTED; while a search is
+ * pending: VROD_ERR_INVALID_ARG; unknown flag bits: VROD_ERR_INVALID_ARG; an empty handle, or one with no eligible row:
+ * VROD_OK and all-zero stats.  Every check, and every allocation whose size is known up front, comes before the first
+ * write to an output or to the handle.  The union-find lives in device memory for the length of the call (8 bytes per
+ * row); its walks are bounded by the row count, and one that runs out is VROD_ERR_INTERNAL, not a hang.  Nothing is
+ * persisted: a snapshot does not change. */
+#define VROD_NEAR_SMALL_POOL 0x80000000u   /* diagnostic: see above */
+typedef struct {
+    uint64_t rows;            /* eligible rows looked at */
+    uint64_t classes;         /* connected components among them */
+    uint64_t near_duplicates; /* rows - classes: what vrod_index_delete_near_duplicates would delete */
+    uint64_t largest_class;   /* rows in the largest class, 0 on a handle with no eligible row */
+    uint64_t hits;            /* sum over eligible rows i of the OTHER eligible rows j that qualify for i (directed) */
+    uint64_t batches;         /* diagnostic: range scans run */
+    uint64_t splits;          /* diagnostic: batches redone in halves because their hits overflowed the pool */
+    uint64_t pool_entries;    /* diagnostic: hit-pool size of this call */
+} vrod_near_stats;
+int vrod_index_find_near_duplicates(vrod_index *idx, float threshold, uint32_t flags, uint64_t *out_first, uint64_t map_len,
+                                    vrod_near_stats *out_stats);
+int vrod_index_find_near_duplicates_device(vrod_index *idx, float threshold, uint32_t flags, uint64_t *d_out_first, uint64_t map_len,
+                                           vrod_near_stats *out_stats, void *stream);
+int vrod_index_delete_near_duplicates(vrod_index *idx, float threshold, uint32_t flags, uint64_t *out_deleted);
+
 /* Grouped search -- the best row of each label, the k best labels per query (a document stored as many chunk rows that
  * share a label: the k best documents, not k chunks of one).  The ELIGIBLE rows of a query are the rows that are live
  * and, while a filter is set, allowed by the handle's filter.  Every label carried by at least one eligible row has one

@@ -40,6 +40,7 @@ SYMBOLS = [
     "vrod_index_count_where", "vrod_index_select_where", "vrod_index_select_where_device", "vrod_index_delete_where",
     "vrod_index_set_filter_where", "vrod_index_set_tags_where",
     "vrod_index_find_duplicates", "vrod_index_find_duplicates_device", "vrod_index_delete_duplicates",
+    "vrod_index_find_near_duplicates", "vrod_index_find_near_duplicates_device", "vrod_index_delete_near_duplicates",
 ]
 
 ERR_CAPACITY = 8   # VROD_ERR_CAPACITY: a range search's result does not fit the caller's buffers (out_lims is valid)
@@ -103,6 +104,16 @@ class DupStats(C.Structure):
     """vrod_dup_stats: live, classes, duplicates and largest_class are exact; the last three are diagnostics of one call."""
     _fields_ = [("live", C.c_uint64), ("classes", C.c_uint64), ("duplicates", C.c_uint64), ("largest_class", C.c_uint64),
                 ("slots", C.c_uint64), ("max_probe", C.c_uint64), ("compare_misses", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class NearStats(C.Structure):
+    """vrod_near_stats: rows, classes, near_duplicates, largest_class and hits are exact; the last three are diagnostics of
+    how one call cut its work."""
+    _fields_ = [("rows", C.c_uint64), ("classes", C.c_uint64), ("near_duplicates", C.c_uint64), ("largest_class", C.c_uint64),
+                ("hits", C.c_uint64), ("batches", C.c_uint64), ("splits", C.c_uint64), ("pool_entries", C.c_uint64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -214,6 +225,9 @@ def load() -> C.CDLL:
     L.vrod_index_find_duplicates.argtypes = [vp, u32, vp, u64, C.POINTER(DupStats)]
     L.vrod_index_find_duplicates_device.argtypes = [vp, u32, vp, u64, C.POINTER(DupStats), vp]
     L.vrod_index_delete_duplicates.argtypes = [vp, u32, C.POINTER(u64)]
+    L.vrod_index_find_near_duplicates.argtypes = [vp, C.c_float, u32, vp, u64, C.POINTER(NearStats)]
+    L.vrod_index_find_near_duplicates_device.argtypes = [vp, C.c_float, u32, vp, u64, C.POINTER(NearStats), vp]
+    L.vrod_index_delete_near_duplicates.argtypes = [vp, C.c_float, u32, C.POINTER(u64)]
     for name in SYMBOLS:
         getattr(L, name).restype = i32
     L.vrod_last_error.restype = C.c_char_p

@@ -41,6 +41,7 @@
 #include "tag_plan.h"
 #include "where_plan.h"
 #include "dup_plan.h"
+#include "near_plan.h"
 #include "group_plan.h"
 #include "multivec_plan.h"
 #include "diverse_plan.h"
@@ -384,11 +385,12 @@ struct vrod_index {
     bool doc_valid = false;
     DevBuf mv_q, mv_ent, mv_tab, mv_cand, mv_small, mv_best, mv_S, mv_absent, mv_M, mv_pairs;
     vrod_multivec_stats mv_stats{};
-    // Searches whose queries are stored rows (vrod_search_by_ids, vrod_knn_graph) hand the search flow rows that are
-    // prepared already: while prep_ovr is not negative it stands for prep_form(metric) in the launch that prepares a
-    // search's queries -- M_L2, the take-as-given form of L2 and IP handles: nothing is normalised, and rounding a bf16
-    // value to bf16 is the identity.  Everything else that launch sets up is unchanged.  Negative outside those two entry
-    // points; a search under it is never captured into a graph nor matched with a captured one.
+    // Searches whose queries are stored rows (vrod_search_by_ids, vrod_knn_graph, and the range scans of
+    // vrod_index_find_near_duplicates) hand the search flow rows that are prepared already: while prep_ovr is not negative
+    // it stands for prep_form(metric) in the launch that prepares a search's or a range scan's queries -- M_L2, the
+    // take-as-given form of L2 and IP handles: nothing is normalised, and rounding a bf16 value to bf16 is the identity.
+    // Everything else that launch sets up is unchanged.  Negative outside those entry points; a search under it is never
+    // captured into a graph nor matched with a captured one.
     int prep_ovr = -1;
     // a graph's workspaces, one set per batch in flight as its lists: the lists without self [rows][k], and the batch's
     // [live rows | place of every row among them]
@@ -2420,8 +2422,9 @@ static int range_collect(vrod_index* idx, const float* d_queries_raw, uint32_t n
     qi.thr_live_bits = qi.thr_pad_bits = form == M_COSINE ? 0x7F800000u : 0xFF800000u;   // nothing passes until range_prepare
     qi.zero_words2 = fast ? pace_region(P, 0) : nullptr;
     qi.n_zero_words2 = kPaceRegions * (kPaceWords + kClaimWords);
-    launch_prep_queries(d_queries_raw, nq, nq_pad, idx->dim, idx->ld, prep_form(idx->metric), idx->dtype, P.q_f32.as<float>(), q_lp, B.qn2,
-                        &P.flags.p[0], &P.flags.p[1], qi, s);
+    // (prep_ovr: a near-duplicate batch's queries are stored rows, taken as given -- negative for every other caller)
+    launch_prep_queries(d_queries_raw, nq, nq_pad, idx->dim, idx->ld, idx->prep_ovr >= 0 ? idx->prep_ovr : prep_form(idx->metric), idx->dtype,
+                        P.q_f32.as<float>(), q_lp, B.qn2, &P.flags.p[0], &P.flags.p[1], qi, s);
     if (fast)
         launch_range_prepare(d_thr, nq, nq_pad, form, plan.eps_mode, plan.eps_c, &P.flags.p[1], idx->max_xn2_bits, B.thr, B.status, s);
     HIP_TRY(hipGetLastError());
@@ -5483,6 +5486,157 @@ int vrod_index_delete_duplicates(vrod_index* idx, uint32_t flags, uint64_t* out_
         std::vector<uint32_t> bits;
         VROD_TRY(dup_run(idx, "vrod_index_delete_duplicates", flags, nullptr, true, &st));
         if (st.duplicates) {
+            VROD_TRY(rowpred_hits_to_host(idx, bits));
+            VROD_TRY(index_delete_hits(idx, bits.data(), bits.size(), &died));
+        }
+    }
+    if (out_deleted) *out_deleted = died;
+    return VROD_OK;
+}
+
+// ------------------------------------------------------------------ near-duplicate rows (vrod_index_find_near_duplicates, _delete_near_duplicates)
+// The connected components of the threshold graph over the eligible rows (near_plan.h, kernels_near.hip, DESIGN.md
+// "Near-duplicate rows"): a self-join of range scans.  The ascending list of eligible rows -- the gather path's, built
+// from the mask's host mirror and uploaded once per mask generation -- is cut into batches; a batch's rows are gathered
+// out of the corpus as they are stored (launch_byid_gather) and run through range_collect as queries taken as given
+// (prep_ovr), all with the one threshold; the batch's pool entries are united in a union-find in device memory.  A batch
+// whose exact total exceeds the call's pool is redone as two halves.  After the last batch one pass writes the map, the
+// class sizes, the counts and, for a delete, one bit per row, which index_delete_hits turns into tombstones.  Everything
+// runs on the stream of the slot the range scans use, so a batch's union pass is ordered before the next batch's scan
+// reuses the pool.  Workspaces, the handle being idle: the call's own block (8 bytes per row, given back on return), the
+// slot's raw-query buffer, range_pool, out_ids for a host form's map, lab_mask for a delete's bitmap.
+static_assert(sizeof(vrod_near_stats) == 64 && sizeof(NearCounters) == 32, "eight 64-bit words; the counters keep what follows them 8-byte aligned");
+static_assert(VROD_NEAR_SMALL_POOL == kNearSmallPool, "near_plan.h restates the ABI's flag");
+
+static int check_near_args(vrod_index* idx, const char* what, float threshold, uint32_t flags, const void* out_first, uint64_t map_len) {
+    if (!idx) return fail(VROD_ERR_INVALID_ARG, "idx is null");
+    if (!near_flags_ok(flags)) return fail(VROD_ERR_INVALID_ARG, "%s: unknown flag bits 0x%x", what, flags);
+    if (threshold != threshold) return fail(VROD_ERR_INVALID_VALUE, "%s: the threshold is NaN", what);
+    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "%s on a multi-device handle: stored rows are not gathered across the shards", what);
+    VROD_TRY(require_idle(idx, what));
+    if (out_first ? map_len != idx->count : map_len != 0)
+        return fail(VROD_ERR_INVALID_ARG, "%s: a map of %llu entries for a handle of %llu rows", what, (unsigned long long)map_len, (unsigned long long)idx->count);
+    return VROD_OK;
+}
+
+// The whole call behind its checks, complete on return.  d_out_first (may be null): the map, device memory; want_hits:
+// lab_mask gets the bitmap of the eligible rows that are not their class's smallest.  Nothing of the caller's and
+// nothing of the handle's rows is written before the last batch is through.  *st is written on success only.
+static int near_run(vrod_index* idx, const char* what, float threshold, uint32_t flags, uint64_t* d_out_first, bool want_hits, vrod_near_stats* st) {
+    const uint64_t count = idx->count, elig = idx->eligible();
+    vrod_near_stats out{};
+    VROD_TRY(set_device(idx));
+    Pending& P = next_slot(idx);
+    hipStream_t s = P.stream;
+    if (!count || !elig) {   // no class: every row of the map is a row that is not eligible
+        if (d_out_first && count) {
+            HIP_TRY(hipMemsetAsync(d_out_first, 0xFF, count * 8, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+        *st = out;
+        return VROD_OK;
+    }
+    const uint32_t batch = near_batch_rows(idx->dtype == VROD_DTYPE_BF16, elig);
+    const uint64_t pool = near_pool_entries(elig, (flags & kNearSmallPool) != 0);
+    // ---- what can be refused: the row list, the call's block [counters | parent (count) | class sizes (count)], the
+    // batch's queries, the pool, a delete's bitmap
+    VROD_TRY(gather_list(idx));
+    if (idx->list_n != elig) return fail(VROD_ERR_INTERNAL, "%s: the row list holds %llu rows, %llu are eligible", what, (unsigned long long)idx->list_n, (unsigned long long)elig);
+    DevMem<> ws;
+    HIP_TRY(ws.alloc(sizeof(NearCounters) + count * 8));
+    VROD_TRY(P.q_raw.ensure((size_t)batch * idx->dim * 4));
+    VROD_TRY(idx->range_pool.ensure((size_t)std::min<uint64_t>(pool, (uint64_t)batch * elig) * sizeof(RangeHit)));
+    if (want_hits) VROD_TRY(idx->lab_mask.ensure(row_pred_hit_words(count) * 4));
+    NearCounters* d_ctr = ws.get<NearCounters>();
+    uint32_t* d_parent = (uint32_t*)(ws.get<char>() + sizeof(NearCounters));
+    uint32_t* d_size = d_parent + count;
+    const uint32_t* d_list = idx->list_dev.as<uint32_t>();
+    const std::vector<float> thr(batch, threshold);
+
+    HIP_TRY(hipMemsetAsync(d_ctr, 0, sizeof(NearCounters), s));
+    launch_near_init(d_parent, d_size, count, s);
+    HIP_TRY(hipGetLastError());
+    // ---- the batches, in ascending order; a batch that overflowed is replaced by its halves
+    std::vector<NearBatch> todo;
+    for (uint64_t b = near_n_batches(elig, batch); b-- > 0;) todo.push_back(near_batch(elig, batch, b));
+    RangeShardResult R;
+    while (!todo.empty()) {
+        const NearBatch b = todo.back();
+        todo.pop_back();
+        launch_byid_gather(idx->corpus.p, idx->dtype, idx->ld, idx->dim, count, idx->id_offset, nullptr, nullptr, d_list + b.first, 0, b.rows,
+                           P.q_raw.as<float>(), nullptr, s);   // (the list holds eligible rows below the count)
+        HIP_TRY(hipGetLastError());
+        idx->prep_ovr = M_L2;   // set for exactly this enqueue: the stored rows are the queries
+        const int rc = range_collect(idx, P.q_raw.as<float>(), b.rows, thr.data(), pool, R);
+        idx->prep_ovr = -1;
+        VROD_TRY(rc);
+        out.batches++;
+        switch (near_verdict(b, R.total, pool)) {
+            case NEAR_FITS: break;
+            case NEAR_SPLIT: {
+                NearBatch lo, hi;
+                near_halves(b, &lo, &hi);
+                todo.push_back(hi);
+                todo.push_back(lo);
+                out.splits++;
+                continue;
+            }
+            default:
+                return fail(VROD_ERR_INTERNAL, "%s: one row has %llu hits among %llu eligible rows", what, (unsigned long long)R.total, (unsigned long long)elig);
+        }
+        launch_near_union(idx->range_pool.as<RangeHit>(), R.stored, d_list + b.first, b.rows, idx->id_offset, count, d_parent, d_ctr, s);
+        HIP_TRY(hipGetLastError());
+    }
+    // ---- the map, the class sizes, the counts
+    launch_near_flatten(count, idx->row_mask(), d_parent, idx->id_offset, d_out_first, d_size, want_hits ? idx->lab_mask.as<uint32_t>() : nullptr, d_ctr, s);
+    HIP_TRY(hipGetLastError());
+    NearCounters c{};
+    HIP_TRY(hipMemcpyAsync(&c, d_ctr, sizeof c, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (c.err)
+        return fail(VROD_ERR_INTERNAL, "%s: the union-find failed (%s)", what,
+                    c.err & kNearErrRow ? "a hit names no row" : c.err & kNearErrWalk ? "a find walk ran out" : "a link ran out of retries");
+    if (c.rows != elig) return fail(VROD_ERR_INTERNAL, "%s: %llu rows were looked at, %llu are eligible", what, (unsigned long long)c.rows, (unsigned long long)elig);
+    out.rows = elig;
+    out.classes = c.classes;
+    out.near_duplicates = elig - c.classes;
+    out.largest_class = c.largest_class;
+    out.hits = c.hits;
+    out.pool_entries = pool;
+    *st = out;
+    return VROD_OK;
+}
+
+int vrod_index_find_near_duplicates(vrod_index* idx, float threshold, uint32_t flags, uint64_t* out_first, uint64_t map_len, vrod_near_stats* out_stats) {
+    VROD_TRY(check_near_args(idx, "vrod_index_find_near_duplicates", threshold, flags, out_first, map_len));
+    const bool map = out_first && idx->count;
+    if (map) VROD_TRY(set_device(idx));
+    if (map) VROD_TRY(idx->out_ids.ensure(idx->count * 8));
+    vrod_near_stats st{};
+    VROD_TRY(near_run(idx, "vrod_index_find_near_duplicates", threshold, flags, map ? idx->out_ids.as<uint64_t>() : nullptr, false, &st));
+    if (map) HIP_TRY(hipMemcpy(out_first, idx->out_ids.p, idx->count * 8, hipMemcpyDeviceToHost));
+    if (out_stats) *out_stats = st;
+    return VROD_OK;
+}
+
+int vrod_index_find_near_duplicates_device(vrod_index* idx, float threshold, uint32_t flags, uint64_t* d_out_first, uint64_t map_len,
+                                           vrod_near_stats* out_stats, void* stream) {
+    VROD_TRY(check_near_args(idx, "vrod_index_find_near_duplicates_device", threshold, flags, d_out_first, map_len));
+    VROD_TRY(begin_sync_device(idx, "vrod_index_find_near_duplicates_device", stream));
+    vrod_near_stats st{};
+    VROD_TRY(near_run(idx, "vrod_index_find_near_duplicates_device", threshold, flags, d_out_first, false, &st));
+    if (out_stats) *out_stats = st;
+    return VROD_OK;
+}
+
+int vrod_index_delete_near_duplicates(vrod_index* idx, float threshold, uint32_t flags, uint64_t* out_deleted) {
+    VROD_TRY(check_near_args(idx, "vrod_index_delete_near_duplicates", threshold, flags, nullptr, 0));
+    uint64_t died = 0;
+    if (idx->count && idx->eligible()) {
+        vrod_near_stats st{};
+        std::vector<uint32_t> bits;
+        VROD_TRY(near_run(idx, "vrod_index_delete_near_duplicates", threshold, flags, nullptr, true, &st));
+        if (st.near_duplicates) {
             VROD_TRY(rowpred_hits_to_host(idx, bits));
             VROD_TRY(index_delete_hits(idx, bits.data(), bits.size(), &died));
         }

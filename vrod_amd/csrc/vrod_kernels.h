@@ -345,6 +345,29 @@ void launch_dup_class(const void* d_corpus, uint32_t dim, uint32_t ld, uint32_t 
 void launch_dup_output(uint64_t count, const uint32_t* d_del, const DupTable& T, uint64_t id_offset, uint64_t* d_out_first, uint32_t* d_class_size,
                        uint32_t* d_hits, DupCounters* d_ctr, hipStream_t s);
 
+// ---- kernels_near.hip : the connected components of the threshold graph (vrod_index_find_near_duplicates, _delete_near_duplicates)
+struct RangeHit;   // kernels_range.h: one qualifying (query, row) of a range search
+// what the passes leave for the host, cleared by the host in front of the first union pass
+struct NearCounters {
+    unsigned long long hits;     // union: pool entries whose two rows differ (directed pairs)
+    unsigned long long classes;  // flatten: eligible rows that are their component's root
+    unsigned long long rows;     // flatten: eligible rows
+    uint32_t largest_class;      // flatten
+    uint32_t err;                // near_plan.h kNearErrWalk | kNearErrRetry | kNearErrRow
+};
+// d_parent[r] = r, d_class_size[r] = 0 for every r < count: every row a component of its own.
+void launch_near_init(uint32_t* d_parent, uint32_t* d_class_size, uint64_t count, hipStream_t s);
+// The `stored` entries of a range pool (unsorted) whose queries were rows d_batch_rows[0 .. batch_n) of the handle: entry
+// {key, id} joins row d_batch_rows[key >> 32] and row id - id_offset in d_parent [count] (lock-free union-find, roots are
+// minima); an entry whose two rows are one is skipped and not counted in d_ctr->hits.
+void launch_near_union(const RangeHit* d_hits, uint64_t stored, const uint32_t* d_batch_rows, uint32_t batch_n, uint64_t id_offset, uint64_t count,
+                       uint32_t* d_parent, NearCounters* d_ctr, hipStream_t s);
+// d_out_first [count] (may be null) = id_offset + the root of the row's component, all-ones for a row set in d_mask (may
+// be null: every row is eligible); d_class_size [count] is zero before; d_hits (may be null; row_pred_hit_words(count)
+// words): bit r set = row r is eligible and not its component's root.  Nothing is written when *d_ctr carries an error.
+void launch_near_flatten(uint64_t count, const uint32_t* d_mask, uint32_t* d_parent, uint64_t id_offset, uint64_t* d_out_first, uint32_t* d_class_size,
+                         uint32_t* d_hits, NearCounters* d_ctr, hipStream_t s);
+
 // ---- kernels_group.hip : a grouped search's de-duplication by label and the dense stage's per-query masks
 // List b (d_cand_ids / d_cand_scores + b * k1: a search's result row, ids with id_offset applied) of query d_qidx[b] (b
 // itself when d_qidx is null): the first entry of every label that is not among the d_found[q] < k results already in

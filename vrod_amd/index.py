@@ -12,7 +12,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import DupStats, KeyStats, MultivecStats, SearchStats, SnapshotInfo, VrodError, check
+from ._lib import DupStats, KeyStats, MultivecStats, NearStats, SearchStats, SnapshotInfo, VrodError, check
 
 DTYPE_F32, DTYPE_BF16 = 0, 1
 SRC_F32, SRC_BF16, SRC_F16 = 0, 1, 2   # vrod_src_dtype: the element type of rows given in device memory
@@ -35,6 +35,7 @@ ROWPRED_DTYPE = np.dtype([("any", np.uint64), ("all", np.uint64), ("none", np.ui
 ROWPRED_ALLOWED = 1   # VROD_ROWPRED_ALLOWED: only the rows the filter allows are in scope
 DUP_WITHIN_LABEL = 1            # VROD_DUP_WITHIN_LABEL: the class key is (label, row bits)
 DUP_NARROW_HASH = 0x80000000    # VROD_DUP_NARROW_HASH: a diagnostic, the row hash cut to 8 bits
+NEAR_SMALL_POOL = 0x80000000   # VROD_NEAR_SMALL_POOL: a diagnostic, the hit pool cut to the eligible-row count
 # rows per batch of knn_graph() by storage type (byid_plan.h: kByidBatchF32, kByidBatchBf16)
 KNN_BATCH = {0: 256, 1: 1024}
 
@@ -654,6 +655,51 @@ class Index:
         flags = self._dup_flags(within_label)
         out = C.c_uint64()
         check(self._L.vrod_index_delete_duplicates(self._h, flags, C.byref(out)))
+        return out.value
+
+    # -- near-duplicate rows
+    @staticmethod
+    def _near_args(threshold, small_pool=False):
+        if isinstance(threshold, (bool, np.bool_)) or not isinstance(threshold, (int, float, np.integer, np.floating)):
+            raise TypeError(f"threshold must be a number, got {type(threshold).__name__}")
+        if not isinstance(small_pool, (bool, np.bool_)):
+            raise TypeError(f"small_pool must be a bool, got {type(small_pool).__name__}")
+        return float(np.float32(threshold)), NEAR_SMALL_POOL if small_pool else 0
+
+    def find_near_duplicates(self, threshold, small_pool: bool = False, stats: bool = False):
+        """uint64 [count]: entry i = the smallest id of row i's class -- the connected component, among the eligible rows
+        (live, allowed by the filter), of the graph that joins two rows when one's stored form scores the other at least as
+        well as `threshold` (single linkage: a~b and b~c put a and c in one class) -- its own id when no row qualifies,
+        ID_NONE for a row that is not eligible (vrod_index_find_near_duplicates).  small_pool: a diagnostic, the same
+        result through a hit pool that makes batches split.  stats=True: -> (map, dict of vrod_near_stats)."""
+        thr, flags = self._near_args(threshold, small_pool)
+        n = self.count
+        out = np.empty(max(n, 1), dtype=np.uint64)
+        st = NearStats()
+        check(self._L.vrod_index_find_near_duplicates(self._h, thr, flags, _ptr(out) if n else None, n, C.byref(st)))
+        return (out[:n], st.as_dict()) if stats else out[:n]
+
+    def find_near_duplicates_device(self, threshold, small_pool: bool = False, out_first=None):
+        """find_near_duplicates into a CUDA int64 tensor [count] (the bits of uint64), complete on return -> (map, stats
+        dict) (vrod_index_find_near_duplicates_device)."""
+        import torch
+        thr, flags = self._near_args(threshold, small_pool)
+        n = self.count
+        dev = torch.device("cuda", self.device)
+        out_first = _device_out(out_first, max(n, 1), torch.int64, dev)
+        n_out, stream = self._device_u64(out_first, "out_first")
+        if n_out < n:
+            raise ValueError(f"out_first must hold {n} ids")
+        st = NearStats()
+        check(self._L.vrod_index_find_near_duplicates_device(self._h, thr, flags, out_first.data_ptr() if n else None, n, C.byref(st), stream))
+        return out_first, st.as_dict()
+
+    def delete_near_duplicates(self, threshold) -> int:
+        """Delete every eligible row that is not the smallest id of its class, as delete() of those ids
+        (vrod_index_delete_near_duplicates).  -> rows that died."""
+        thr, flags = self._near_args(threshold)
+        out = C.c_uint64()
+        check(self._L.vrod_index_delete_near_duplicates(self._h, thr, flags, C.byref(out)))
         return out.value
 
     def set_id_offset(self, off: int):
