@@ -4,7 +4,9 @@
 //   mode 2: ds_read_b128 only, 8 waves
 //   mode 3: waves 0-3 LDS-DMA, waves 4-7 ds_read_b128 concurrently
 //   mode 4: waves 0-3 register staging, waves 4-7 ds_read_b128
+// `lds_fill probe` runs none of them: it checks the immediate-offset rule of the LDS-DMA load (probe_imm below).
 #include <hip/hip_runtime.h>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -54,7 +56,46 @@ template <int MODE> static void run(const char* name, const char* d_src, float* 
     float ms; hipEventElapsedTime(&ms, e0, e1);
     printf("%-44s %8.3f ms  write %7.1f GB/s/CU  read %7.1f GB/s/CU\n", name, ms, bytes_w * iters / ms / 1e6, bytes_r * iters / ms / 1e6);
 }
-int main() {
+// `lds_fill probe`: what the immediate offset of global_load_lds_dwordx4 is added to.  One wave, two pieces behind ONE
+// M0 write: piece 0 with offset:0, piece 1 with offset:1024 and a lane offset of 4096 - 1024.  If the immediate goes to
+// BOTH the LDS destination and the global address, LDS[1024 + x] = src[4096 + x] (and LDS[x] = src[x]); src holds its own
+// word index, LDS starts as 0xFFFFFFFF, so any other rule shows in the words printed.
+__global__ __launch_bounds__(64) void probe_imm(const char* src, uint32_t* out) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const uint32_t lane = threadIdx.x;
+    uint32_t* w = reinterpret_cast<uint32_t*>(lds);
+    for (uint32_t i = lane; i < 2048; i += 64) w[i] = 0xFFFFFFFFu;
+    __syncthreads();
+    const uint32_t lds_addr = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)lds);
+    const uint32_t v0 = lane * 16u, v1 = lane * 16u + 4096u - 1024u;
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\t"
+                 "global_load_lds_dwordx4 %1, %3\n\t"
+                 "global_load_lds_dwordx4 %2, %3 offset:1024\n\t"
+                 "s_waitcnt vmcnt(0)"
+                 :: "s"(lds_addr), "v"(v0), "v"(v1), "s"(src) : "memory");
+    __syncthreads();
+    for (uint32_t i = lane; i < 2048; i += 64) out[i] = w[i];
+}
+static int run_probe() {
+    const uint32_t nsrc = 4096;   // words: 16 KB
+    uint32_t h_src[nsrc], h_out[2048];
+    for (uint32_t i = 0; i < nsrc; ++i) h_src[i] = i;
+    char* d_src; uint32_t* d_out;
+    hipMalloc(&d_src, sizeof h_src); hipMemcpy(d_src, h_src, sizeof h_src, hipMemcpyHostToDevice);
+    hipMalloc(&d_out, sizeof h_out);
+    probe_imm<<<1, 64, 8192>>>(d_src, d_out);
+    if (hipMemcpy(h_out, d_out, sizeof h_out, hipMemcpyDeviceToHost) != hipSuccess) { printf("probe: the copy back failed\n"); return 1; }
+    int bad = 0;
+    for (uint32_t i = 0; i < 256; ++i) bad += h_out[i] != i;                  // piece 0: LDS[0, 1024) = src[0, 1024)
+    for (uint32_t i = 0; i < 256; ++i) bad += h_out[256 + i] != 1024 + i;     // piece 1: LDS[1024, 2048) = src[4096, 5120)
+    for (uint32_t i = 512; i < 2048; ++i) bad += h_out[i] != 0xFFFFFFFFu;     // nothing else written
+    printf("probe: LDS words [0] %u [255] %u | [256] %u [511] %u | [512] %#x   (expected 0 255 | 1024 1279 | 0xffffffff)\n",
+           h_out[0], h_out[255], h_out[256], h_out[511], h_out[512]);
+    printf("probe: the immediate offset is added to the LDS destination AND the global address: %s\n", bad ? "NO" : "yes");
+    return bad != 0;
+}
+int main(int argc, char** argv) {
+    if (argc > 1 && argv[1][0] == 'p') return run_probe();
     char* d_src; float* d_out;
     hipMalloc(&d_src, 256 * 65536); hipMemset(d_src, 1, 256 * 65536); hipMalloc(&d_out, 4096);
     const int iters = 20000;

@@ -6,9 +6,10 @@
 // K = vector dimension; both operands are stored [row][k] with k contiguous.
 //
 // The family (one translation unit each, so that an edit of one schedule rebuilds only that one):
-//   kernels_mfma_w4.hip      scan_mfma_w4_kernel<METRIC, DENSE, SPLIT>   bf16 rows, and the [hi | lo] bf16 planes of
+//   kernels_mfma_w4.hip      scan_mfma_w4_kernel<METRIC, DENSE, SPLIT, TLOOP>   bf16 rows, and the [hi | lo] bf16 planes of
 //                            fp32 rows (SPLIT): 4 waves, one per SIMD, 128 x 128 per wave, accumulators a[0:255]
 //                            owned by inline asm (audited in the build).  The default of every batch of > 64 queries.
+//                            TLOOP: the main loop as a tile loop around a fixed-trip K loop (even K extents >= 4 K-tiles).
 //   kernels_mfma_skinny.hip  scan_mfma_skinny_kernel<...>                batches of 5..64 queries: HBM-bound form
 //   kernels_mfma_phased.hip  scan_mfma_phased_kernel<float, ...>         fp32 rows without planes: 8 waves, exact fp32
 //                            matrix-core pass (v_mfma_f32_16x16x4_f32)

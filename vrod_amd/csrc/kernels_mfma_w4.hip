@@ -401,6 +401,25 @@ __device__ __forceinline__ void w4_dma_m0(uint32_t lds_buf) {
 __device__ __forceinline__ void w4_dma_load(uint32_t voff, const char* sbase) {
     asm volatile("global_load_lds_dwordx4 %0, %1" :: "v"(voff), "s"(sbase) : "memory");
 }
+// One M0 write per group of four pieces (default; -DVROD_W4_M0_PER_PIECE: one per piece, the A/B build).  The load's
+// immediate offset is added to BOTH the LDS destination and the global address (scripts/ubench/lds_fill.hip `probe`), and
+// the four pieces i = 0..3 of a half-unit lie 1024 B apart in LDS: M0 = the half-unit, piece i = offset:i*1024 with
+// i*1024 taken off its lane offset beforehand (never below zero: a piece is at least i * 8 rows of >= 128 B into the tile).
+#ifdef VROD_W4_M0_PER_PIECE
+constexpr bool kW4GroupM0 = false;
+#else
+constexpr bool kW4GroupM0 = true;
+#endif
+template <int OFF>
+__device__ __forceinline__ void w4_dma_load_off(uint32_t voff, const char* sbase) {
+    static_assert(OFF >= 0 && OFF < 4096, "13-bit signed immediate");
+    asm volatile("global_load_lds_dwordx4 %0, %1 offset:%c2" :: "v"(voff), "s"(sbase), "i"(OFF) : "memory");
+}
+template <int IMM, int OFF>
+__device__ __forceinline__ void w4_dma_piece_off(uint32_t lds_buf, uint32_t voff, const char* sbase) {
+    static_assert(OFF >= 0 && OFF < 4096, "13-bit signed immediate");
+    asm volatile("s_add_u32 m0, %0, %c3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:%c4" :: "s"(lds_buf), "v"(voff), "s"(sbase), "i"(IMM), "i"(OFF) : "scc", "memory");
+}
 // a pointer hipcc keeps in an SGPR pair ("s" asm operands must be provably wave-uniform)
 __device__ __forceinline__ const char* w4_uniform_ptr(const char* p) {
     const uint64_t v = (uint64_t)p;
@@ -484,8 +503,11 @@ __device__ __forceinline__ bool w4_claim(const MfmaKernelArgs& a, uint32_t strip
 
 // DENSE: 0 = filtered launch, 1 = sample pass writing every score, 2 = sample pass writing group bests (one kernel per
 // form: with both sample epilogues in one function hipcc ran out of VGPRs and went into the accumulator file).
-template <int METRIC, int DENSE, bool SPLIT>
+// TLOOP: the main loop as a loop over tiles around a fixed-trip K loop (below); the launcher picks it when the K extent
+// is an even number of K-tiles, at least 4 (bf16 rows only: SPLIT's hold pattern has period 3, buffer parity period 2).
+template <int METRIC, int DENSE, bool SPLIT, bool TLOOP>
 __global__ __launch_bounds__(256) void scan_mfma_w4_kernel(const MfmaKernelArgs a) {
+    static_assert(!(TLOOP && SPLIT), "the tile loop is built for bf16 rows");
     extern __shared__ __attribute__((aligned(16))) char lds[];
     // makes the kernel descriptor allocate a[0:255]
     asm volatile("" ::: "a0", "a1", "a2", "a3", "a4", "a5", "a6", "a7", "a8", "a9", "a10", "a11", "a12", "a13", "a14", "a15", "a16", "a17", "a18", "a19", "a20", "a21", "a22", "a23", "a24", "a25", "a26", "a27", "a28", "a29", "a30", "a31", "a32", "a33", "a34", "a35", "a36", "a37", "a38", "a39", "a40", "a41", "a42", "a43", "a44", "a45", "a46", "a47", "a48", "a49", "a50", "a51", "a52", "a53", "a54", "a55", "a56", "a57", "a58", "a59", "a60", "a61", "a62", "a63", "a64", "a65", "a66", "a67", "a68", "a69", "a70", "a71", "a72", "a73", "a74", "a75", "a76", "a77", "a78", "a79", "a80", "a81", "a82", "a83", "a84", "a85", "a86", "a87", "a88", "a89", "a90", "a91", "a92", "a93", "a94", "a95", "a96", "a97", "a98", "a99", "a100", "a101", "a102", "a103", "a104", "a105", "a106", "a107", "a108", "a109", "a110", "a111", "a112", "a113", "a114", "a115", "a116", "a117", "a118", "a119", "a120", "a121", "a122", "a123", "a124", "a125", "a126", "a127", "a128", "a129", "a130", "a131", "a132", "a133", "a134", "a135", "a136", "a137", "a138", "a139", "a140", "a141", "a142", "a143", "a144", "a145", "a146", "a147", "a148", "a149", "a150", "a151", "a152", "a153", "a154", "a155", "a156", "a157", "a158", "a159", "a160", "a161", "a162", "a163", "a164", "a165", "a166", "a167", "a168", "a169", "a170", "a171", "a172", "a173", "a174", "a175", "a176", "a177", "a178", "a179", "a180", "a181", "a182", "a183", "a184", "a185", "a186", "a187", "a188", "a189", "a190", "a191", "a192", "a193", "a194", "a195", "a196", "a197", "a198", "a199", "a200", "a201", "a202", "a203", "a204", "a205", "a206", "a207", "a208", "a209", "a210", "a211", "a212", "a213", "a214", "a215", "a216", "a217", "a218", "a219", "a220", "a221", "a222", "a223", "a224", "a225", "a226", "a227", "a228", "a229", "a230", "a231", "a232", "a233", "a234", "a235", "a236", "a237", "a238", "a239", "a240", "a241", "a242", "a243", "a244", "a245", "a246", "a247", "a248", "a249", "a250", "a251", "a252", "a253", "a254", "a255");
@@ -517,7 +539,7 @@ __global__ __launch_bounds__(256) void scan_mfma_w4_kernel(const MfmaKernelArgs 
     // The strip's static share [t0, t1s); behind it come claimed chunks (work stealing: filtered launches of long strips,
     // K extents of at least three K-tiles -- the MFMAs then always find the tile they move on to in the staging cursor).
     const uint32_t t1s = (DENSE == 0 && a.claims != nullptr && KT >= 3u) ? t1 - w4_tail_tiles(t1 - t0) : t1;
-    uint32_t total_it = 0xFFFFFFFFu;   // K-tiles of this work-group: known once the staging cursor has run out of tiles
+    uint32_t total_it = 0xFFFFFFFFu;   // flat loop: K-tiles of this work-group, known once the staging cursor has run out of tiles (the tile loop ends on its `more` flag)
 
     // ONE query block per work-group: a loop over query blocks here would re-enter the prologue with the
     // accumulator file live in hipcc's eyes (it parks kernel-entry values in AGPRs up to the first MFMA);
@@ -543,6 +565,7 @@ __global__ __launch_bounds__(256) void scan_mfma_w4_kernel(const MfmaKernelArgs 
         for (int j = 0; j < 8; ++j) {
             voa[j] = st_lane_off_a + (p0 + (uint32_t)(j & 3) + (uint32_t)(j >> 2) * 8u) * piece_stride_a;
             vob[j] = st_lane_off_b + (p0 + (uint32_t)(j & 3) + (uint32_t)(j >> 2) * 8u) * piece_stride_b;
+            if constexpr (kW4GroupM0) { voa[j] -= (uint32_t)(j & 3) * 1024u; vob[j] -= (uint32_t)(j & 3) * 1024u; }   // (comes back as the load's immediate)
         }
         const uint32_t lds_w = __builtin_amdgcn_readfirstlane(lds_addr + p0 * 1024u);
         uint32_t st_kt = 0, st_tile = t0, a_kt = 0;   // a_kt: K-tile of the corpus row ua_src points at
@@ -552,12 +575,16 @@ __global__ __launch_bounds__(256) void scan_mfma_w4_kernel(const MfmaKernelArgs 
         // unit A_mh / B_nh = the 16 pieces (8 rows x 128 B each) of rows [h*64, h*64+64) of both
         // 128-row halves; this wave moves 4 of them: idx = wave*4 + i -> piece (idx>>3)*16 + (idx&7) + h*8
         // unit A_mh / B_nh = the 16 pieces (8 rows x 128 B each) of rows [h*64, h*64+64) of both 128-row halves
-#define W4_STAGE_A(BUF, H, I) w4_dma_piece<((I) + 8 * (H)) * 1024>(lds_w + ((BUF) & 1u) * kStageBytes, voa[(I) + 4 * (H)], ua_src);
-#define W4_STAGE_B(BUF, H, I) w4_dma_piece<32768 + ((I) + 8 * (H)) * 1024>(lds_w + ((BUF) & 1u) * kStageBytes, vob[(I) + 4 * (H)], ub_src);
+#define W4_STAGE_A(BUF, H, I) if constexpr (kW4GroupM0) w4_dma_piece_off<8 * (H) * 1024, (I) * 1024>(lds_w + ((BUF) & 1u) * kStageBytes, voa[(I) + 4 * (H)], ua_src); \
+                              else w4_dma_piece<((I) + 8 * (H)) * 1024>(lds_w + ((BUF) & 1u) * kStageBytes, voa[(I) + 4 * (H)], ua_src);
+#define W4_STAGE_B(BUF, H, I) if constexpr (kW4GroupM0) w4_dma_piece_off<32768 + 8 * (H) * 1024, (I) * 1024>(lds_w + ((BUF) & 1u) * kStageBytes, vob[(I) + 4 * (H)], ub_src); \
+                              else w4_dma_piece<32768 + ((I) + 8 * (H)) * 1024>(lds_w + ((BUF) & 1u) * kStageBytes, vob[(I) + 4 * (H)], ub_src);
         // next K-tile of the strip (clamped at its end: the last K-tile is re-staged, never read).  The common case -- the
         // next K-tile of the same tile -- is two scalar adds behind one compare; the tile boundary is a wave-uniform branch.
         // (The bases are SGPR pairs now: with per-lane pointers this had to be written with selects, hipcc moved branchy
-        // pointer updates into a scratch array.)
+        // pointer updates into a scratch array.)  Used by the prologue of both loop forms and by every K-tile of the flat
+        // loop; the tile loop has the two cases at fixed places of its body instead, and neither st_kt nor total_it
+        // (the 0xFFFFFFFF sentinel and `it_adv + 3` below) mean anything to it.
         auto stage_advance = [&](int32_t it_adv /* the iteration this advance belongs to; -2, -1 in the prologue */) {
             if (st_kt + 1 < KT) {
                 // SPLIT: K-tiles 3j, 3j+1, 3j+2 read corpus K-tile 2j, 2j, 2j+1 ([hi_j | lo_j] interleaved: the
@@ -655,8 +682,13 @@ __global__ __launch_bounds__(256) void scan_mfma_w4_kernel(const MfmaKernelArgs 
 #define W4_DMU3(j, L)
 #define W4_VMWAIT "s_waitcnt lgkmcnt(0)"
 #else
-#define W4_HALF_A(H, I, LOAD) if constexpr (LOAD) w4_dma_load(voa[(I) + 4 * (H)], ua_src); else w4_dma_m0<((I) + 8 * (H)) * 1024>(lds_wp);
-#define W4_HALF_B(H, I, LOAD) if constexpr (LOAD) w4_dma_load(vob[(I) + 4 * (H)], ub_src); else w4_dma_m0<32768 + ((I) + 8 * (H)) * 1024>(lds_wp);
+// (one M0 write per phase, a group of MFMAs ahead of the phase's first load, then four loads 1024 B apart by immediate)
+#define W4_HALF_A(H, I, LOAD) if constexpr (kW4GroupM0 && (LOAD)) w4_dma_load_off<(I) * 1024>(voa[(I) + 4 * (H)], ua_src);           \
+                              else if constexpr (kW4GroupM0) { if constexpr ((I) == 0) w4_dma_m0<8 * (H) * 1024>(lds_wp); }            \
+                              else if constexpr (LOAD) w4_dma_load(voa[(I) + 4 * (H)], ua_src); else w4_dma_m0<((I) + 8 * (H)) * 1024>(lds_wp);
+#define W4_HALF_B(H, I, LOAD) if constexpr (kW4GroupM0 && (LOAD)) w4_dma_load_off<(I) * 1024>(vob[(I) + 4 * (H)], ub_src);           \
+                              else if constexpr (kW4GroupM0) { if constexpr ((I) == 0) w4_dma_m0<32768 + 8 * (H) * 1024>(lds_wp); }    \
+                              else if constexpr (LOAD) w4_dma_load(vob[(I) + 4 * (H)], ub_src); else w4_dma_m0<32768 + ((I) + 8 * (H)) * 1024>(lds_wp);
 #define W4_DMU0(j, L) W4_HALF_A(0, j, L)
 #define W4_DMU1(j, L) W4_HALF_B(0, j, L)
 #define W4_DMU2(j, L) W4_HALF_B(1, j, L)
@@ -673,21 +705,8 @@ __global__ __launch_bounds__(256) void scan_mfma_w4_kernel(const MfmaKernelArgs 
 #else
 #define W4_LOOP_BARRIER() VROD_BARRIER()
 #endif
-// PAR = it & 1, a constant of each of the loop's two copies of this body (the loop starts at it = 0): the LDS addresses of
-// the fragment reads and of the DMA destinations are then loop constants (8 vector adds fewer per K-tile)
-#define W4_ITER(BX, BY, LDQ0, LDQ3, PAR)                                                           \
-    {                                                                                              \
-        const char* l = lds + (PAR) * kStageBytes;                                                 \
-        const char* ln = lds + (1 - (PAR)) * kStageBytes;                                          \
-        const uint32_t lds_wp = lds_w + (PAR) * kStageBytes;                                       \
-        const bool first = kt == 0;                                                                \
-        /* pacing of the sibling work-groups (see the phased kernel), here in units of K-tiles: with  \
-           the staging two K-tiles ahead no work-group ever waits for HBM, so nothing else keeps   \
-           the siblings of a strip together */                                                     \
-        /* (a countdown, not it % pace_every: one wave per SIMD issues one instruction per ~4 cycles, and the   \
-            ~25 scalar instructions of a run-time modulo in front of every K-tile were 3 % of the kernel) */   \
-        if (--pace_left == 0u) {                                                                   \
-          pace_left = a.pace_every;                                                                \
+// a pacing point (both loop forms): thread 0 counts itself in and waits, briefly, for the strip's siblings
+#define W4_PACE_POINT()                                                                            \
           ++pace_round;                                                                            \
           if (pace_on && tid == 0) {                                                               \
             uint32_t* ctr = a.pace + strip;                                                        \
@@ -703,17 +722,13 @@ __global__ __launch_bounds__(256) void scan_mfma_w4_kernel(const MfmaKernelArgs 
                 __builtin_amdgcn_s_sleep(2);                                                       \
             }                                                                                      \
             pace_on = ok;                                                                          \
-          }                                                                                        \
-        }                                                                                          \
-        /* L2: the tile's 256 row norms -> LDS slot of its parity (one 1-KB piece, wave 0) */      \
-        if (METRIC == M_L2 && DENSE != 1 && first && wave == 0)                                    \
-            w4_dma_piece<0>(lds_addr + kLdsXn2 + (tile & 1u) * 1024u, (uint32_t)lane * 16u, w4_uniform_ptr(reinterpret_cast<const char*>(a.xnorm2 + (uint64_t)tile * kBM))); \
-        if (first) { W4_KTILE(BX, BY, LDQ0, LDQ3, true) } else { W4_KTILE(BX, BY, LDQ0, LDQ3, false) } \
-        stage_advance((int32_t)it);                                                                \
-        const bool last = kt == KT - 1;                                                            \
-        W4_CLK(uint32_t ce1 = 0;)                                                                  \
-        if (last) {                                                                                \
-            W4_CLK(const uint32_t ce0 = (uint32_t)__builtin_amdgcn_s_memtime();)                   \
+          }
+// L2, a tile's first K-tile: the tile's 256 row norms -> LDS slot of its parity (one 1-KB piece, wave 0)
+#define W4_XNORM_PIECE()                                                                           \
+        if (METRIC == M_L2 && DENSE != 1 && wave == 0)                                             \
+            w4_dma_piece<0>(lds_addr + kLdsXn2 + (tile & 1u) * 1024u, (uint32_t)lane * 16u, w4_uniform_ptr(reinterpret_cast<const char*>(a.xnorm2 + (uint64_t)tile * kBM)));
+// behind a tile's last K-tile
+#define W4_TILE_EPILOGUE()                                                                         \
             if constexpr (DENSE == 2)                                                              \
                 w4_groupmax_store_tile<METRIC>(a, qn2_l, xn_l + (tile & 1) * 256 + wr * 128 + fg * 4, wc * 128 + fr, \
                                                qb * kBN + wc * 128 + fr, ((tile - a.tile_first) * 2 + wr) * 4 + fg); \
@@ -721,7 +736,32 @@ __global__ __launch_bounds__(256) void scan_mfma_w4_kernel(const MfmaKernelArgs 
                 w4_dense_store_tile<METRIC>(a, qn2_l, wc * 128 + fr, tile * kBM + wr * 128 + fg * 4, qb * kBN + wc * 128 + fr); \
             else if (W4_ABL_EPI)                                                                   \
                 w4_filter_tile<METRIC>(a, thr_l, qn2_l, xn_l + (tile & 1) * 256 + wr * 128 + fg * 4,        \
-                                       tile, wc * 128 + fr, qb, wlog_lds, region, wr, wc, lane, wlog, wglob ); \
+                                       tile, wc * 128 + fr, qb, wlog_lds, region, wr, wc, lane, wlog, wglob );
+// PAR = it & 1, a constant of each of the loop's two copies of this body (the loop starts at it = 0): the LDS addresses of
+// the fragment reads and of the DMA destinations are then loop constants (8 vector adds fewer per K-tile)
+#define W4_ITER(BX, BY, LDQ0, LDQ3, PAR)                                                           \
+    {                                                                                              \
+        const char* l = lds + (PAR) * kStageBytes;                                                 \
+        const char* ln = lds + (1 - (PAR)) * kStageBytes;                                          \
+        const uint32_t lds_wp = lds_w + (PAR) * kStageBytes;                                       \
+        const bool first = kt == 0;                                                                \
+        /* pacing of the sibling work-groups (see the phased kernel), here in units of K-tiles: with  \
+           the staging two K-tiles ahead no work-group ever waits for HBM, so nothing else keeps   \
+           the siblings of a strip together */                                                     \
+        /* (a countdown, not it % pace_every: one wave per SIMD issues one instruction per ~4 cycles, and the   \
+            ~25 scalar instructions of a run-time modulo in front of every K-tile were 3 % of the kernel) */   \
+        if (--pace_left == 0u) {                                                                   \
+          pace_left = a.pace_every;                                                                \
+          W4_PACE_POINT()                                                                          \
+        }                                                                                          \
+        if (first) { W4_XNORM_PIECE() }                                                            \
+        if (first) { W4_KTILE(BX, BY, LDQ0, LDQ3, true) } else { W4_KTILE(BX, BY, LDQ0, LDQ3, false) } \
+        stage_advance((int32_t)it);                                                                \
+        const bool last = kt == KT - 1;                                                            \
+        W4_CLK(uint32_t ce1 = 0;)                                                                  \
+        if (last) {                                                                                \
+            W4_CLK(const uint32_t ce0 = (uint32_t)__builtin_amdgcn_s_memtime();)                   \
+            W4_TILE_EPILOGUE()                                                                     \
             W4_CLK(ce1 = (uint32_t)__builtin_amdgcn_s_memtime(); cke += ce1 - ce0; ckn += 1;)     \
             kt = 0;                                                                                \
             tile = KT >= 3u ? st_tile : tile + 1u;   /* the cursor is two K-tiles ahead: in the tile the MFMAs move on to */ \
@@ -744,18 +784,124 @@ __global__ __launch_bounds__(256) void scan_mfma_w4_kernel(const MfmaKernelArgs 
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         VROD_BARRIER();   // every wave holds its first fragments: buffer 0's A_m0 / B_n0 may be restaged
 
-        uint32_t it = 0, kt = 0, tile = t0;
+        uint32_t tile = t0;
         uint32_t wlog = 0u, wglob = 0u;   // entries in this wave's hit log / in its spill region (wave-uniform)
-        // K-tiles to the next pacing point (wave-uniform countdown; pace_every = 0: starts at 0 and wraps, i.e. never) and how many passed
-        uint32_t pace_left = a.pace_every ? a.pace_every + 1u : 0u, pace_round = 0u;
-        
+        uint32_t pace_round = 0u;         // pacing points passed
         W4_CLK(const uint64_t ck0 = __builtin_amdgcn_s_memtime(); const uint64_t cr0 = __builtin_amdgcn_s_memrealtime(); uint32_t cke = 0, ckb = 0, ckn = 0;)
-        while (it < total_it) {
-            W4_ITER(FBx, FBy, W4_LDQ0x, W4_LDQ3x, 0)
-            if (it >= total_it) break;
-            W4_ITER(FBy, FBx, W4_LDQ0y, W4_LDQ3y, 1)
+        if constexpr (!TLOOP) {
+            // The flat form, for any K extent: one stream of K-tiles, each finding out where in its tile it stands (first?
+            // last? does the staging cursor cross a tile boundary? is the work-group through?).
+            uint32_t it = 0, kt = 0;
+            // K-tiles to the next pacing point (wave-uniform countdown; pace_every = 0: starts at 0 and wraps, i.e. never)
+            uint32_t pace_left = a.pace_every ? a.pace_every + 1u : 0u;
+            while (it < total_it) {
+                W4_ITER(FBx, FBy, W4_LDQ0x, W4_LDQ3x, 0)
+                if (it >= total_it) break;
+                W4_ITER(FBy, FBx, W4_LDQ0y, W4_LDQ3y, 1)
+            }
+        } else {
+            // The tile loop: KT even and >= 4 (launcher), so every tile starts on buffer parity 0 and a K-tile's place in its
+            // tile is a place in the CODE -- nothing is tested per K-tile.  Per tile:
+            //   K-tile 0            C = 0 form (L2: the row-norm piece); cursor += 128
+            //   K-tiles 1 .. KT-4   (KT - 4) / 2 trips of a parity pair; cursor += 128 each
+            //   K-tile KT-3         the cursor (two K-tiles ahead: it has just staged the tile's last K-tile) crosses into
+            //                       the next tile -- of the range in hand, of the claimed range, or stays: more = false
+            //   K-tile KT-2         cursor += 128 (0 when it stays: the last K-tile is re-staged, never read)
+            //   K-tile KT-1         the same, then the tile epilogue; on to the cursor's tile while `more`
+            // Behind the prologue the cursor stands at K-tile 2 of t0.
+#define W4_TKT(BX, BY, LDQ0, LDQ3, PAR, ZERO)                                                      \
+            {                                                                                      \
+                const char* l = lds + (PAR) * kStageBytes;                                         \
+                const char* ln = lds + (1 - (PAR)) * kStageBytes;                                  \
+                const uint32_t lds_wp = lds_w + (PAR) * kStageBytes;                               \
+                W4_KTILE(BX, BY, LDQ0, LDQ3, ZERO)                                                 \
+            }
+#define W4_TKT_END() asm volatile(W4_VMWAIT ::: "memory"); W4_LOOP_BARRIER();
+            const uint32_t plain_pairs = (KT - 4u) >> 1;
+            // pacing, once per tile and still counted in K-tiles: the countdown drops by KT per tile and fires at or below
+            // zero (pace_every = 0: it never drops)
+            const int32_t pace_drop = a.pace_every ? (int32_t)KT : 0;
+            int32_t pace_left = a.pace_every ? (int32_t)(a.pace_every + KT) : 1;
+            uint32_t tail_step = 128u;
+            bool more = true;
+            W4_CLK(total_it = 0u;)
+            do {
+                pace_left -= pace_drop;
+                if (pace_left <= 0) {
+                    pace_left += (int32_t)a.pace_every;
+                    W4_PACE_POINT()
+                }
+                W4_XNORM_PIECE()
+                W4_TKT(FBx, FBy, W4_LDQ0x, W4_LDQ3x, 0, true)
+                ua_src += 128;
+                ub_src += 128;
+                W4_TKT_END()
+#pragma unroll 1
+                for (uint32_t n = plain_pairs; n != 0u; --n) {
+                    W4_TKT(FBy, FBx, W4_LDQ0y, W4_LDQ3y, 1, false)
+                    ua_src += 128;
+                    ub_src += 128;
+                    W4_TKT_END()
+                    W4_TKT(FBx, FBy, W4_LDQ0x, W4_LDQ3x, 0, false)
+                    ua_src += 128;
+                    ub_src += 128;
+                    W4_TKT_END()
+                }
+                W4_TKT(FBy, FBx, W4_LDQ0y, W4_LDQ3y, 1, false)
+                {
+                    // tile boundary of the cursor, as in stage_advance: the next tile of the range in hand, or -- the range is
+                    // through -- the first of the range wave 0 claimed a tile ago ({begin, end} in LDS; begin = end: none), or
+                    // nothing: the cursor stays on the tile's last K-tile and this tile is the work-group's last
+                    uint32_t nt = st_tile + 1u;
+                    bool have = nt < st_end;
+                    if (DENSE == 0 && !have) {
+                        const uint2 nx = *reinterpret_cast<const uint2*>(lds + kLdsNext);
+                        const uint32_t nb = __builtin_amdgcn_readfirstlane(nx.x), ne = __builtin_amdgcn_readfirstlane(nx.y);
+                        if (ne > nb) { nt = nb; st_end = ne; have = true; pace_on = false; }   // (behind its static share a work-group no longer paces)
+                    }
+                    if (have) {
+                        ua_src += (int64_t)(int32_t)(nt - st_tile) * ((int64_t)kBM * lda_bytes) - (int64_t)(KT - 1) * 128;
+                        ub_src -= (int64_t)(KT - 1) * 128;
+                        st_tile = nt;
+                        // The claim, as in stage_advance and under the same invariant (see there): the cursor has entered the
+                        // LAST tile of the range in hand; wave 0 leaves the range that follows in LDS for everybody's crossing
+                        // out of this tile, KT K-tiles (>= 3 barriers) from now.  A range read from LDS at a crossing is never
+                        // overwritten in the same crossing: every range is at least 2 tiles long, so the crossing that enters
+                        // a range enters its first tile, not its last.
+                        if (DENSE == 0 && nt + 1u == st_end && wave == 0 && t1s != t1) {
+                            uint32_t cb = 0u, ce = 0u;
+                            uint32_t own_next = *reinterpret_cast<const uint32_t*>(lds + kLdsNext + 8);
+                            (void)w4_claim(a, strip, qb0, own_next, lane, cb, ce);
+                            if (lane == 0)
+                                asm volatile("ds_write_b64 %0, %1\n\tds_write_b32 %0, %2 offset:8\n\ts_waitcnt lgkmcnt(0)"
+                                             :: "v"(next_addr), "v"(((uint64_t)ce << 32) | cb), "v"(own_next) : "memory");
+                        }
+                    }
+                    more = have;
+                    tail_step = have ? 128u : 0u;
+                    // (behind the join hipcc would keep the two bases in VGPRs: an "s" asm operand then prints as v[..])
+                    ua_src = w4_uniform_ptr(ua_src);
+                    ub_src = w4_uniform_ptr(ub_src);
+                }
+                W4_TKT_END()
+                W4_TKT(FBx, FBy, W4_LDQ0x, W4_LDQ3x, 0, false)
+                ua_src += tail_step;
+                ub_src += tail_step;
+                W4_TKT_END()
+                W4_TKT(FBy, FBx, W4_LDQ0y, W4_LDQ3y, 1, false)
+                ua_src += tail_step;
+                ub_src += tail_step;
+                W4_CLK(const uint32_t ce0 = (uint32_t)__builtin_amdgcn_s_memtime();)
+                W4_TILE_EPILOGUE()
+                W4_CLK(const uint32_t ce1 = (uint32_t)__builtin_amdgcn_s_memtime(); cke += ce1 - ce0; ckn += 1; total_it += KT;)
+                tile = st_tile;   // the cursor is two K-tiles ahead: in the tile the MFMAs move on to
+                W4_TKT_END()
+                W4_CLK(ckb += (uint32_t)__builtin_amdgcn_s_memtime() - ce1;)
+            } while (more);
+#undef W4_TKT
+#undef W4_TKT_END
         }
-        
+
         W4_CLK(if (!DENSE && tid == 0) {
             const uint64_t ck1 = __builtin_amdgcn_s_memtime(), cr1 = __builtin_amdgcn_s_memrealtime();
             atomicAdd(&g_w4_clk[0], (unsigned long long)(ck1 - ck0)); atomicAdd(&g_w4_clk[1], (unsigned long long)(cr1 - cr0));
@@ -776,6 +922,9 @@ __global__ __launch_bounds__(256) void scan_mfma_w4_kernel(const MfmaKernelArgs 
 #undef W4_HALF_A
 #undef W4_HALF_B
 #undef W4_ITER
+#undef W4_PACE_POINT
+#undef W4_XNORM_PIECE
+#undef W4_TILE_EPILOGUE
 #undef W4_LDQ1
 #undef W4_LDQ2
 #undef W4_LDQ0x
@@ -797,17 +946,26 @@ __global__ __launch_bounds__(256) void scan_mfma_w4_kernel(const MfmaKernelArgs 
 
 // dense_form: 0 = filtered launch, 1 = sample pass writing every score, 2 = sample pass writing group bests
 void launch_mfma_w4(const MfmaKernelArgs& a, int metric, int dense_form, bool split, int grid, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
-#define VROD_MFMA_W4K_(MM, DN, SP)                                                                          \
+    // The tile loop (TLOOP) needs the same buffer parity at every tile start and its four special K-tiles apart: an even
+    // number of K-tiles, at least 4 (dim 256, 384, ... 768 ...).  Every other K extent (dim 64, 128, 192, 320, ...) and the
+    // SPLIT planes run the flat loop.  -DVROD_W4_NO_TILE_LOOP: the flat loop everywhere (A/B build).
+    const uint32_t kt_n = a.ld_bytes >> 7;
+#ifdef VROD_W4_NO_TILE_LOOP
+    const bool tloop = false;
+#else
+    const bool tloop = !split && kt_n >= 4u && (kt_n & 1u) == 0u;
+#endif
+#define VROD_MFMA_W4K_(MM, DN, SP, TL)                                                                      \
     do {                                                                                                    \
         static bool attr_set = false;                                                                       \
         if (!attr_set) {                                                                                    \
-            (void)hipFuncSetAttribute((const void*)scan_mfma_w4_kernel<MM, DN, SP>,                         \
+            (void)hipFuncSetAttribute((const void*)scan_mfma_w4_kernel<MM, DN, SP, TL>,                     \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTotalW4);             \
             attr_set = true;                                                                                \
         }                                                                                                   \
-        hipExtLaunchKernelGGL((scan_mfma_w4_kernel<MM, DN, SP>), dim3(grid), dim3(256), kLdsTotalW4, s, start, stop, 0, a); \
+        hipExtLaunchKernelGGL((scan_mfma_w4_kernel<MM, DN, SP, TL>), dim3(grid), dim3(256), kLdsTotalW4, s, start, stop, 0, a); \
     } while (0)
-#define VROD_MFMA_W4K(MM, DN) do { if (split) VROD_MFMA_W4K_(MM, DN, true); else VROD_MFMA_W4K_(MM, DN, false); } while (0)
+#define VROD_MFMA_W4K(MM, DN) do { if (split) VROD_MFMA_W4K_(MM, DN, true, false); else if (tloop) VROD_MFMA_W4K_(MM, DN, false, true); else VROD_MFMA_W4K_(MM, DN, false, false); } while (0)
 #define VROD_MFMA_W4M(MM) do { if (dense_form == 0) VROD_MFMA_W4K(MM, 0); else if (dense_form == 2) VROD_MFMA_W4K(MM, 2); else VROD_MFMA_W4K(MM, 1); } while (0)
     if (metric == M_COSINE) VROD_MFMA_W4M(M_COSINE); else VROD_MFMA_W4M(M_L2);
 #undef VROD_MFMA_W4M
