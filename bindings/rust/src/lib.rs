@@ -130,6 +130,25 @@ pub struct vrod_dup_stats {
     pub compare_misses: u64,
 }
 
+/// `flags` of the row-lookup calls.  Diagnostics for tests: the row hash is cut to 8 bits (as `VROD_DUP_NARROW_HASH`); the
+/// call's lookup batches hold 96 rows.  Results are identical with and without them.
+pub const VROD_ROWFIND_NARROW_HASH: u32 = 0x8000_0000;
+pub const VROD_ROWFIND_SMALL_BATCH: u32 = 0x4000_0000;
+/// What `vrod_index_find_rows` and `vrod_index_add_unique` report: the first four fields are exact and reproducible, the
+/// last four are diagnostics of how one call cut its work and of its hash tables.
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default, PartialEq, Eq)]
+pub struct vrod_rowfind_stats {
+    pub rows: u64,
+    pub found: u64,
+    pub repeats: u64,
+    pub appended: u64,
+    pub batches: u64,
+    pub slots: u64,
+    pub max_probe: u64,
+    pub compare_misses: u64,
+}
+
 /// `flags` of the near-duplicate calls.  A diagnostic for tests: the hit pool of the call holds exactly as many entries as
 /// there are eligible rows, so batches split on a small corpus; results are identical with and without it.
 pub const VROD_NEAR_SMALL_POOL: u32 = 0x8000_0000;
@@ -340,6 +359,13 @@ extern "C" {
     pub fn vrod_index_find_duplicates(idx: *mut vrod_index, flags: u32, out_first: *mut u64, map_len: u64, out_stats: *mut vrod_dup_stats) -> c_int;
     pub fn vrod_index_find_duplicates_device(idx: *mut vrod_index, flags: u32, d_out_first: *mut u64, map_len: u64, out_stats: *mut vrod_dup_stats, stream: *mut c_void) -> c_int;
     pub fn vrod_index_delete_duplicates(idx: *mut vrod_index, flags: u32, out_deleted: *mut u64) -> c_int;
+    /// Row lookup: `out_ids[i]` (may be null) = the smallest id among the live rows whose stored bits equal input i as
+    /// `vrod_index_add` would store it, `VROD_ID_NONE` if there is none.  `add_unique` appends the inputs that have no stored
+    /// copy and repeat no earlier input of the call, and names every input's row.
+    pub fn vrod_index_find_rows(idx: *mut vrod_index, rows: *const f32, n: u64, flags: u32, out_ids: *mut u64, out_stats: *mut vrod_rowfind_stats) -> c_int;
+    pub fn vrod_index_find_rows_device(idx: *mut vrod_index, d_rows: *const c_void, src_dtype: c_int, row_stride: u64, n: u64, flags: u32, d_out_ids: *mut u64, out_stats: *mut vrod_rowfind_stats, stream: *mut c_void) -> c_int;
+    pub fn vrod_index_add_unique(idx: *mut vrod_index, rows: *const f32, n: u64, flags: u32, out_ids: *mut u64, out_stats: *mut vrod_rowfind_stats) -> c_int;
+    pub fn vrod_index_add_unique_device(idx: *mut vrod_index, d_rows: *const c_void, src_dtype: c_int, row_stride: u64, n: u64, flags: u32, d_out_ids: *mut u64, out_stats: *mut vrod_rowfind_stats, stream: *mut c_void) -> c_int;
     /// Near-duplicate rows: `out_first[i]` = the smallest id of row i's class, the connected component -- among the eligible
     /// rows: live, allowed by the filter -- of the graph that joins two rows when one's stored form scores the other at
     /// least as well as `threshold` (single linkage: a~b and b~c put a and c together).  `map_len` as for

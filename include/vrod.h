@@ -617,6 +617,61 @@ int vrod_index_find_duplicates_device(vrod_index *idx, uint32_t flags, uint64_t 
                                       vrod_dup_stats *out_stats, void *stream);
 int vrod_index_delete_duplicates(vrod_index *idx, uint32_t flags, uint64_t *out_deleted);
 
+/* Row lookup -- "are these vectors in here already?", answered from the rows themselves, and an add that appends only
+ * the vectors that are not: the question that comes BEFORE vrod_index_find_duplicates, for callers without keys.
+ * Equality.  Input i is first prepared exactly as vrod_index_add would store it: fp16 / bf16 sources are widened, the
+ * norm chain and the division run under COSINE, a BF16 handle rounds to bf16.  It EQUALS a stored row when the dim stored
+ * elements have the same bits -- the equality of vrod_index_find_duplicates: -0.0 is not +0.0, the padding is never
+ * compared, x and 2x are one row under COSINE, an fp32 vector and its bf16-rounded twin are one row on a BF16 handle.
+ * Deleted rows are never found; the filter is not consulted, as with keys and find_duplicates.  A hash only chooses
+ * which rows are compared; every answer rests on a comparison of the rows themselves, so the result is exact.
+ *   find_rows     out_ids[i] (host memory; may be NULL, a stats-only call) = the SMALLEST ID, id_offset applied, among
+ *                 the live rows equal to input i, VROD_ID_NONE if there is none.  Inputs may repeat: repeats get the
+ *                 same answer.  The handle is not changed in any observable way: a snapshot does not change.
+ *   add_unique    in call order: input i with a live stored copy gets that row's smallest id and nothing is appended;
+ *                 otherwise, if an earlier input j < i of the same call has the same prepared bits, it gets out_ids[j];
+ *                 otherwise it is appended exactly as vrod_index_add would append it -- the next id, no key, the default
+ *                 label, tags and value.  Afterwards the handle is what ONE vrod_index_add of just the appended inputs,
+ *                 in order, would have left: rows, every search (ids and score bits), the certificate bound, counts and
+ *                 the bytes of a snapshot.  The same batch again appends nothing.  out_ids may be NULL.
+ *   the _device forms take rows as vrod_index_add_device does (src_dtype, row_stride; the same layout errors) and write
+ *                 d_out_ids (may be NULL), device memory on the handle's device.  The stream rules are those of
+ *                 vrod_index_find_keys_device: the caller's work on `stream` (may be NULL) is complete before the library
+ *                 reads or writes, and the call returns when the ids are in place.  At most 16 bytes per input cross to
+ *                 the host; the rows do not.  The stats still come back to host memory.
+ *   *out_stats (may be NULL): rows, found, repeats and appended are exact and reproducible; batches, slots, max_probe
+ *                 and compare_misses are DIAGNOSTICS of how this call cut its work and of its hash tables, and may differ
+ *                 between calls.
+ * VROD_ROWFIND_NARROW_HASH and VROD_ROWFIND_SMALL_BATCH are diagnostics for tests: the row hash is cut to 8 bits (as
+ * VROD_DUP_NARROW_HASH), the call's lookup batches hold 96 rows.  Results are identical with and without them.
+ * Errors: NaN / Inf anywhere in the inputs: VROD_ERR_INVALID_VALUE, every input being checked before the first row is
+ * written; unknown flag bits, or a pending search: VROD_ERR_INVALID_ARG; a multi-device handle: VROD_ERR_UNSUPPORTED;
+ * n == 0: VROD_OK and all-zero stats.  A refused call, VROD_ERR_OUT_OF_MEMORY included, leaves outputs, rows, norms, the
+ * certificate bound, count and key table as they were; spare capacity may have grown.  The corpus is hashed once per call
+ * and every batch's table lives in device memory for the length of the call only (8 bytes per stored row and per input,
+ * about 50 per row of a batch); every walk of a table is bounded by its slot count, and one that runs out is
+ * VROD_ERR_INTERNAL, not a hang.  Nothing is persisted. */
+#define VROD_ROWFIND_NARROW_HASH 0x80000000u  /* diagnostic: row hash cut to 8 bits, as VROD_DUP_NARROW_HASH */
+#define VROD_ROWFIND_SMALL_BATCH 0x40000000u  /* diagnostic: the call's lookup batches hold 96 rows */
+typedef struct {
+    uint64_t rows;            /* inputs of the call */
+    uint64_t found;           /* inputs whose prepared form a live row stored BEFORE the call */
+    uint64_t repeats;         /* inputs without such a row that equal an earlier input of the call */
+    uint64_t appended;        /* add_unique: rows - found - repeats; find_rows: 0 */
+    uint64_t batches;         /* diagnostic: lookup batches of this call */
+    uint64_t slots;           /* diagnostic: size of the largest batch table */
+    uint64_t max_probe;       /* diagnostic, may differ between calls */
+    uint64_t compare_misses;  /* diagnostic: full row comparisons that found a difference */
+} vrod_rowfind_stats;
+int vrod_index_find_rows(vrod_index *idx, const float *rows, uint64_t n, uint32_t flags, uint64_t *out_ids,
+                         vrod_rowfind_stats *out_stats);
+int vrod_index_find_rows_device(vrod_index *idx, const void *d_rows, int src_dtype, uint64_t row_stride, uint64_t n,
+                                uint32_t flags, uint64_t *d_out_ids, vrod_rowfind_stats *out_stats, void *stream);
+int vrod_index_add_unique(vrod_index *idx, const float *rows, uint64_t n, uint32_t flags, uint64_t *out_ids,
+                          vrod_rowfind_stats *out_stats);
+int vrod_index_add_unique_device(vrod_index *idx, const void *d_rows, int src_dtype, uint64_t row_stride, uint64_t n,
+                                 uint32_t flags, uint64_t *d_out_ids, vrod_rowfind_stats *out_stats, void *stream);
+
 /* Near-duplicate rows -- the classes of ELIGIBLE rows that a score threshold ties together: the re-encoded paragraph,
  * the chunk of a second crawl, a row and its bf16-rounded twin.  The range counterpart of vrod_knn_graph and the
  * similarity counterpart of vrod_index_find_duplicates.

@@ -40,6 +40,7 @@ SYMBOLS = [
     "vrod_index_count_where", "vrod_index_select_where", "vrod_index_select_where_device", "vrod_index_delete_where",
     "vrod_index_set_filter_where", "vrod_index_set_tags_where",
     "vrod_index_find_duplicates", "vrod_index_find_duplicates_device", "vrod_index_delete_duplicates",
+    "vrod_index_find_rows", "vrod_index_find_rows_device", "vrod_index_add_unique", "vrod_index_add_unique_device",
     "vrod_index_find_near_duplicates", "vrod_index_find_near_duplicates_device", "vrod_index_delete_near_duplicates",
 ]
 
@@ -104,6 +105,15 @@ class DupStats(C.Structure):
     """vrod_dup_stats: live, classes, duplicates and largest_class are exact; the last three are diagnostics of one call."""
     _fields_ = [("live", C.c_uint64), ("classes", C.c_uint64), ("duplicates", C.c_uint64), ("largest_class", C.c_uint64),
                 ("slots", C.c_uint64), ("max_probe", C.c_uint64), ("compare_misses", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class RowfindStats(C.Structure):
+    """vrod_rowfind_stats: rows, found, repeats and appended are exact; the last four are diagnostics of one call."""
+    _fields_ = [("rows", C.c_uint64), ("found", C.c_uint64), ("repeats", C.c_uint64), ("appended", C.c_uint64),
+                ("batches", C.c_uint64), ("slots", C.c_uint64), ("max_probe", C.c_uint64), ("compare_misses", C.c_uint64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -225,6 +235,10 @@ def load() -> C.CDLL:
     L.vrod_index_find_duplicates.argtypes = [vp, u32, vp, u64, C.POINTER(DupStats)]
     L.vrod_index_find_duplicates_device.argtypes = [vp, u32, vp, u64, C.POINTER(DupStats), vp]
     L.vrod_index_delete_duplicates.argtypes = [vp, u32, C.POINTER(u64)]
+    L.vrod_index_find_rows.argtypes = [vp, vp, u64, u32, vp, C.POINTER(RowfindStats)]
+    L.vrod_index_find_rows_device.argtypes = [vp, vp, i32, u64, u64, u32, vp, C.POINTER(RowfindStats), vp]
+    L.vrod_index_add_unique.argtypes = [vp, vp, u64, u32, vp, C.POINTER(RowfindStats)]
+    L.vrod_index_add_unique_device.argtypes = [vp, vp, i32, u64, u64, u32, vp, C.POINTER(RowfindStats), vp]
     L.vrod_index_find_near_duplicates.argtypes = [vp, C.c_float, u32, vp, u64, C.POINTER(NearStats)]
     L.vrod_index_find_near_duplicates_device.argtypes = [vp, C.c_float, u32, vp, u64, C.POINTER(NearStats), vp]
     L.vrod_index_delete_near_duplicates.argtypes = [vp, C.c_float, u32, C.POINTER(u64)]

@@ -50,6 +50,7 @@
 #include "snapshot_plan.h"
 #include "keys_plan.h"
 #include "ingest_plan.h"
+#include "rowfind_plan.h"
 
 using namespace vrod;
 
@@ -5492,6 +5493,221 @@ int vrod_index_delete_duplicates(vrod_index* idx, uint32_t flags, uint64_t* out_
     }
     if (out_deleted) *out_deleted = died;
     return VROD_OK;
+}
+
+// ------------------------------------------------------------------ row lookup (vrod_index_find_rows, _add_unique and their _device forms)
+// The join between the inputs of a call and the corpus (rowfind_plan.h, kernels_rowfind.hip, DESIGN.md "Row lookup").
+// The corpus is hashed once (launch_dup_hash); the call is cut into lookup batches; a batch is prepared into upd_stage as
+// an add would store it (ingest_prepare), hashed and classed as a small corpus of its own (launch_dup_hash / _class), and
+// the probe pass streams the corpus's hashes through the batch's table.  What crosses to the host is 16 bytes per input
+// (RowfindAnswer) and the counters; rowfind_resolve turns them into ids and the list of the batch's new inputs.
+// add_unique appends those through index_add(rows_picked(...)) before the next batch is probed, so that a later batch
+// finds them in the corpus; find_rows keeps them in a side corpus of the call, probed the same way.  Either way their
+// hashes go behind the corpus's, and row count0 + j stands for the call's j-th new input.
+// Workspaces, the handle being idle: the call's own blocks (given back on return), upd_stage for a batch's rows,
+// raw_stage and ingest_pick inside the ingest.  Everything that can be refused for the inputs' sake comes before the
+// first row is written; whatever fails later rolls the appended rows back as index_add does.
+static_assert(sizeof(vrod_rowfind_stats) == 64 && sizeof(RowfindAnswer) == 16, "eight 64-bit words; 16 bytes per input for the host");
+static_assert(VROD_ROWFIND_NARROW_HASH == kRowfindNarrowHash && VROD_ROWFIND_SMALL_BATCH == kRowfindSmallBatch && VROD_ID_NONE == kRowfindNone,
+              "rowfind_plan.h restates the ABI's flags");
+constexpr uint32_t kRowfindXn2Word = 11;   // idx->flags.p[11]: the max squared row norm as an add_unique call found it
+
+// What the four entry points check before any device call; the device forms have run check_ingest_args before.
+static int check_rowfind_args(vrod_index* idx, const char* what, const void* rows, uint64_t n, uint32_t flags) {
+    if (!idx || (!rows && n)) return fail(VROD_ERR_INVALID_ARG, "%s: null argument", what);
+    if (!rowfind_flags_ok(flags)) return fail(VROD_ERR_INVALID_ARG, "%s: unknown flag bits 0x%x", what, flags);
+    if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "%s on a multi-device handle: equal rows may lie on different shards", what);
+    return require_idle(idx, what);
+}
+
+// The rows an add_unique call has appended so far go again: what index_add's own rollback does, for the whole call.
+static void rowfind_rollback(vrod_index* idx, uint64_t count0) {
+    const uint64_t n = idx->count - count0;
+    idx->count = count0;
+    if (n) {
+        (void)hipMemsetAsync((char*)idx->corpus.p + count0 * idx->row_bytes(), 0, n * idx->row_bytes(), idx->stream);
+        (void)hipMemsetAsync(idx->xnorm2.p + count0, 0, n * sizeof(float), idx->stream);
+    }
+    (void)hipMemcpyAsync(idx->max_xn2_bits, &idx->flags.p[kRowfindXn2Word], 4, hipMemcpyDeviceToDevice, idx->stream);
+    (void)hipStreamSynchronize(idx->stream);
+}
+
+// The call behind its argument checks, n > 0, on the handle's stream, complete on return.  ids [n]: host memory of the
+// caller's flow, meaningful on success; *st is written on success only.
+static int rowfind_run(vrod_index* idx, const char* what, const RowSource& src, uint64_t n, uint32_t flags, bool append, uint64_t* ids,
+                       vrod_rowfind_stats* st) {
+    VROD_TRY(set_device(idx));
+    hipStream_t s = idx->stream;
+    const uint32_t dim = idx->dim, ld = idx->ld, es = (uint32_t)idx->esize;
+    const size_t rb = idx->row_bytes();
+    if (!dup_pitch_ok(dim, es, ld)) return fail(VROD_ERR_INTERNAL, "%s: a row pitch of %u elements", what, ld);
+    const bool narrow = (flags & kRowfindNarrowHash) != 0, small = (flags & kRowfindSmallBatch) != 0;
+    const uint64_t count0 = idx->count, B = rowfind_batch_rows(n, dim, small), nb = rowfind_batches(n, dim, small);
+    const uint64_t slots_max = rowfind_table_slots(B);
+    const bool side = !append && nb > 1;   // find_rows over several batches: the new inputs of earlier batches are kept
+
+    // ---- every allocation.  The call's block: [hash (u64, count0 + n) | batch hash (u64, B) | answers (B) | counters |
+    // slot_row, slot_min, found, found_side (slots each) | row_slot (B) | news (B)]
+    const size_t at_bhash = (count0 + n) * 8, at_ans = at_bhash + B * 8, at_ctr = at_ans + B * sizeof(RowfindAnswer), at_tab = at_ctr + sizeof(DupCounters),
+                 at_rows = at_tab + slots_max * 16, at_news = at_rows + B * 4, total = at_news + B * 4;
+    DevMem<> ws, kept;
+    HIP_TRY(ws.alloc(total));
+    if (side) HIP_TRY(kept.alloc((n - rowfind_batch_count(n, dim, small, nb - 1)) * rb));
+    VROD_TRY(idx->upd_stage.ensure(B * rb));
+    if (append && count0 + n > idx->capacity)   // the growth of an add of all n, up front: no batch's append can run out of room
+        VROD_TRY(index_reserve(idx, idx->capacity ? std::max(count0 + n, idx->capacity + idx->capacity / 2) : count0 + n));
+    uint64_t* d_hash = ws.get<uint64_t>();
+    uint64_t* d_bhash = (uint64_t*)(ws.get<char>() + at_bhash);
+    RowfindAnswer* d_ans = (RowfindAnswer*)(ws.get<char>() + at_ans);
+    DupCounters* d_ctr = (DupCounters*)(ws.get<char>() + at_ctr);
+    uint32_t* d_tab = (uint32_t*)(ws.get<char>() + at_tab);
+    uint32_t* d_news = (uint32_t*)(ws.get<char>() + at_news);
+    std::vector<RowfindAnswer> ans(B);
+    std::vector<uint32_t> news(B);
+    std::vector<uint64_t> new_inputs(n);
+
+    // ---- every input is checked before the first row is written: a call of several batches by a prepare-only pass
+    if (nb > 1) VROD_TRY(index_update_pass(idx, nullptr, src, n, false));
+
+    static const bool timed = [] { const char* e = getenv("VROD_DEBUG_ROWFIND_TIMING"); return e && e[0] == '1'; }();
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 4; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } ev_guard{ev};
+    if (timed) for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+    float hash_ms = 0.f, probe_ms = 0.f;
+    double append_ms = 0.0;
+
+    HIP_TRY(hipMemsetAsync(d_ctr, 0, sizeof(DupCounters), s));
+    if (append) HIP_TRY(hipMemcpyAsync(&idx->flags.p[kRowfindXn2Word], idx->max_xn2_bits, 4, hipMemcpyDeviceToDevice, s));
+    if (timed) HIP_TRY(hipEventRecord(ev[0], s));
+    launch_dup_hash(idx->corpus.p, dim, ld, es, count0, idx->n_deleted ? idx->del_dev.p : nullptr, nullptr, false, narrow, d_hash, s);
+    if (timed) HIP_TRY(hipEventRecord(ev[1], s));
+    HIP_TRY(hipGetLastError());
+
+    RowfindTotals tot;
+    DupCounters c{};
+    int rc = VROD_OK;
+    auto batch = [&](uint64_t b) -> int {
+        const uint64_t i0 = rowfind_batch_first(n, dim, small, b), m = rowfind_batch_count(n, dim, small, b), slots = rowfind_table_slots(m);
+        DupTable T;
+        T.slot_row = d_tab;
+        T.slot_min = d_tab + slots;
+        T.row_slot = (uint32_t*)(ws.get<char>() + at_rows);
+        T.slots = slots;
+        uint32_t* d_found = d_tab + 2 * slots;
+        uint32_t* d_found_side = side && tot.fresh ? d_tab + 3 * slots : nullptr;
+        VROD_TRY(ingest_prepare(idx, rows_from(src, i0), m, idx->upd_stage.p));
+        if (nb == 1) VROD_TRY(check_bad_flag(idx, "rows"));
+        HIP_TRY(hipMemsetAsync(d_tab, 0xFF, slots * 16, s));   // empty slots, all-ones minima, nothing found
+        launch_dup_hash(idx->upd_stage.p, dim, ld, es, m, nullptr, nullptr, false, narrow, d_bhash, s);
+        launch_dup_class(idx->upd_stage.p, dim, ld, es, m, nullptr, nullptr, false, d_bhash, T, d_ctr, s);
+        if (timed) HIP_TRY(hipEventRecord(ev[2], s));
+        launch_rowfind_probe(idx->corpus.p, dim, ld, es, idx->count, idx->n_deleted ? idx->del_dev.p : nullptr, d_hash, idx->upd_stage.p, (uint32_t)m,
+                             d_bhash, T, d_found, d_ctr, s);
+        if (timed) HIP_TRY(hipEventRecord(ev[3], s));
+        if (d_found_side)
+            launch_rowfind_probe(kept.p, dim, ld, es, tot.fresh, nullptr, d_hash + count0, idx->upd_stage.p, (uint32_t)m, d_bhash, T, d_found_side, d_ctr, s);
+        launch_rowfind_resolve((uint32_t)m, T, d_found, d_found_side, count0, d_ans, d_ctr, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&c, d_ctr, sizeof c, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(ans.data(), d_ans, m * sizeof(RowfindAnswer), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (timed) {
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, ev[2], ev[3]));
+            probe_ms += ms;
+        }
+        if (c.err)
+            return fail(VROD_ERR_INTERNAL, "%s: a batch table's walk failed (%s)", what, c.err & kDupErrFull ? "ran over every slot" : "a slot names no row");
+        const uint64_t fresh0 = tot.fresh;
+        const uint64_t k = rowfind_resolve(ans.data(), i0, m, count0, idx->id_offset, append, ids, new_inputs.data(), news.data(), tot);
+        if (!k || (!append && b + 1 == nb)) return VROD_OK;   // (the last batch of a lookup has no later batch to tell)
+        const auto t0 = std::chrono::steady_clock::now();
+        if (append) VROD_TRY(index_add(idx, rows_picked(src, new_inputs.data() + fresh0), k));
+        if (timed) append_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (b + 1 == nb) return VROD_OK;
+        HIP_TRY(hipMemcpyAsync(d_news, news.data(), k * 4, hipMemcpyHostToDevice, s));
+        launch_rowfind_keep(idx->upd_stage.p, ld, es, d_bhash, d_news, (uint32_t)k, side ? kept.get<char>() + fresh0 * rb : nullptr,
+                            d_hash + count0 + fresh0, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(s));   // (news and the stage are free for the next batch)
+        return VROD_OK;
+    };
+    for (uint64_t b = 0; b < nb && rc == VROD_OK; ++b) rc = batch(b);
+    if (rc != VROD_OK) {
+        if (append) rowfind_rollback(idx, count0);
+        return rc;
+    }
+    if (timed) {   // one line on stderr (scripts/probes/rowfind_probe.py)
+        HIP_TRY(hipEventElapsedTime(&hash_ms, ev[0], ev[1]));
+        fprintf(stderr, "{\"vrod_rowfind_hash_ms\": %.6f, \"probe_ms\": %.6f, \"append_ms\": %.6f, \"count\": %llu, \"rows\": %llu, \"batches\": %llu}\n", hash_ms,
+                probe_ms, append_ms, (unsigned long long)count0, (unsigned long long)n, (unsigned long long)nb);
+    }
+    vrod_rowfind_stats o{};
+    o.rows = n;
+    o.found = tot.found;
+    o.repeats = tot.repeats;
+    o.appended = append ? tot.fresh : 0;
+    o.batches = nb;
+    o.slots = slots_max;
+    o.max_probe = c.max_probe;
+    o.compare_misses = c.compare_misses;
+    *st = o;
+    return VROD_OK;
+}
+
+// The host forms' body: the ids go to the caller's array at the end, if there is one.
+static int rowfind_host(vrod_index* idx, const char* what, const float* rows, uint64_t n, uint32_t flags, bool append, uint64_t* out_ids,
+                        vrod_rowfind_stats* out_stats) {
+    VROD_TRY(check_rowfind_args(idx, what, rows, n, flags));
+    vrod_rowfind_stats st{};
+    if (n) {
+        std::vector<uint64_t> ids(n);
+        VROD_TRY(rowfind_run(idx, what, rows_on_host(rows, idx->dim), n, flags, append, ids.data(), &st));
+        if (out_ids) std::copy(ids.begin(), ids.end(), out_ids);
+    }
+    if (out_stats) *out_stats = st;
+    return VROD_OK;
+}
+
+static int rowfind_device(vrod_index* idx, const char* what, const void* d_rows, int src_dtype, uint64_t row_stride, uint64_t n, uint32_t flags,
+                          bool append, uint64_t* d_out_ids, vrod_rowfind_stats* out_stats, void* stream) {
+    VROD_TRY(check_ingest_args(idx, what, d_rows, src_dtype, row_stride, n));
+    VROD_TRY(check_rowfind_args(idx, what, d_rows, n, flags));
+    vrod_rowfind_stats st{};
+    if (n) {
+        RowSource src = rows_on_device(d_rows, src_dtype, row_stride);
+        VROD_TRY(ingest_open(idx, what, d_rows, stream, &src.device));
+        std::vector<uint64_t> ids(n);
+        if (append && d_out_ids) {   // the one thing that can still be refused behind the appends: try the copy's target first
+            hipPointerAttribute_t at{};
+            if (hipPointerGetAttributes(&at, d_out_ids) != hipSuccess || at.type != hipMemoryTypeDevice) {
+                (void)hipGetLastError();
+                return fail(VROD_ERR_INVALID_ARG, "%s: d_out_ids is not in device memory", what);
+            }
+        }
+        VROD_TRY(rowfind_run(idx, what, src, n, flags, append, ids.data(), &st));
+        if (d_out_ids) HIP_TRY(hipMemcpy(d_out_ids, ids.data(), n * 8, hipMemcpyHostToDevice));
+    }
+    if (out_stats) *out_stats = st;
+    return VROD_OK;
+}
+
+int vrod_index_find_rows(vrod_index* idx, const float* rows, uint64_t n, uint32_t flags, uint64_t* out_ids, vrod_rowfind_stats* out_stats) {
+    return rowfind_host(idx, "vrod_index_find_rows", rows, n, flags, false, out_ids, out_stats);
+}
+
+int vrod_index_find_rows_device(vrod_index* idx, const void* d_rows, int src_dtype, uint64_t row_stride, uint64_t n, uint32_t flags,
+                                uint64_t* d_out_ids, vrod_rowfind_stats* out_stats, void* stream) {
+    return rowfind_device(idx, "vrod_index_find_rows_device", d_rows, src_dtype, row_stride, n, flags, false, d_out_ids, out_stats, stream);
+}
+
+int vrod_index_add_unique(vrod_index* idx, const float* rows, uint64_t n, uint32_t flags, uint64_t* out_ids, vrod_rowfind_stats* out_stats) {
+    return rowfind_host(idx, "vrod_index_add_unique", rows, n, flags, true, out_ids, out_stats);
+}
+
+int vrod_index_add_unique_device(vrod_index* idx, const void* d_rows, int src_dtype, uint64_t row_stride, uint64_t n, uint32_t flags,
+                                 uint64_t* d_out_ids, vrod_rowfind_stats* out_stats, void* stream) {
+    return rowfind_device(idx, "vrod_index_add_unique_device", d_rows, src_dtype, row_stride, n, flags, true, d_out_ids, out_stats, stream);
 }
 
 // ------------------------------------------------------------------ near-duplicate rows (vrod_index_find_near_duplicates, _delete_near_duplicates)

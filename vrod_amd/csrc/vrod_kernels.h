@@ -345,6 +345,24 @@ void launch_dup_class(const void* d_corpus, uint32_t dim, uint32_t ld, uint32_t 
 void launch_dup_output(uint64_t count, const uint32_t* d_del, const DupTable& T, uint64_t id_offset, uint64_t* d_out_first, uint32_t* d_class_size,
                        uint32_t* d_hits, DupCounters* d_ctr, hipStream_t s);
 
+// ---- kernels_rowfind.hip : the join between a batch of prepared inputs and the corpus (vrod_index_find_rows, _add_unique)
+struct RowfindAnswer;   // rowfind_plan.h: what the device says of one input
+// d_stage [m][ld]: the batch's prepared rows, d_stage_hash [m] their hashes, T their class table (launch_dup_class over
+// them).  d_found [T.slots] (all-ones before) gets, per class, the smallest row r < count of d_corpus that is not set in
+// d_del (may be null) and whose dim stored elements equal the class's; d_hash [count]: the corpus rows' hashes, read for
+// live rows only.  *d_ctr gets compare_misses, max_probe and err as the class pass's.
+void launch_rowfind_probe(const void* d_corpus, uint32_t dim, uint32_t ld, uint32_t esize, uint64_t count, const uint32_t* d_del, const uint64_t* d_hash,
+                          const void* d_stage, uint32_t m, const uint64_t* d_stage_hash, const DupTable& T, uint32_t* d_found, DupCounters* d_ctr,
+                          hipStream_t s);
+// d_ans [m]: per input its class's found row -- d_found's, else count0 + d_found_side's (may be null), else none -- and
+// its first input of the batch.  Nothing is written when *d_ctr carries an error.
+void launch_rowfind_resolve(uint32_t m, const DupTable& T, const uint32_t* d_found, const uint32_t* d_found_side, uint64_t count0, RowfindAnswer* d_ans,
+                            const DupCounters* d_ctr, hipStream_t s);
+// The batch's new inputs d_news [k] (indices into the batch): d_dst_hash [k] = their hashes, d_dst_rows [k][ld] (may be
+// null) = their staged rows.
+void launch_rowfind_keep(const void* d_stage, uint32_t ld, uint32_t esize, const uint64_t* d_stage_hash, const uint32_t* d_news, uint32_t k,
+                         void* d_dst_rows, uint64_t* d_dst_hash, hipStream_t s);
+
 // ---- kernels_near.hip : the connected components of the threshold graph (vrod_index_find_near_duplicates, _delete_near_duplicates)
 struct RangeHit;   // kernels_range.h: one qualifying (query, row) of a range search
 // what the passes leave for the host, cleared by the host in front of the first union pass

@@ -12,7 +12,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import DupStats, KeyStats, MultivecStats, NearStats, SearchStats, SnapshotInfo, VrodError, check
+from ._lib import DupStats, KeyStats, MultivecStats, NearStats, RowfindStats, SearchStats, SnapshotInfo, VrodError, check
 
 DTYPE_F32, DTYPE_BF16 = 0, 1
 SRC_F32, SRC_BF16, SRC_F16 = 0, 1, 2   # vrod_src_dtype: the element type of rows given in device memory
@@ -35,6 +35,8 @@ ROWPRED_DTYPE = np.dtype([("any", np.uint64), ("all", np.uint64), ("none", np.ui
 ROWPRED_ALLOWED = 1   # VROD_ROWPRED_ALLOWED: only the rows the filter allows are in scope
 DUP_WITHIN_LABEL = 1            # VROD_DUP_WITHIN_LABEL: the class key is (label, row bits)
 DUP_NARROW_HASH = 0x80000000    # VROD_DUP_NARROW_HASH: a diagnostic, the row hash cut to 8 bits
+ROWFIND_NARROW_HASH = 0x80000000   # VROD_ROWFIND_NARROW_HASH: a diagnostic, the row hash cut to 8 bits
+ROWFIND_SMALL_BATCH = 0x40000000   # VROD_ROWFIND_SMALL_BATCH: a diagnostic, lookup batches of 96 rows
 NEAR_SMALL_POOL = 0x80000000   # VROD_NEAR_SMALL_POOL: a diagnostic, the hit pool cut to the eligible-row count
 # rows per batch of knn_graph() by storage type (byid_plan.h: kByidBatchF32, kByidBatchBf16)
 KNN_BATCH = {0: 256, 1: 1024}
@@ -656,6 +658,60 @@ class Index:
         out = C.c_uint64()
         check(self._L.vrod_index_delete_duplicates(self._h, flags, C.byref(out)))
         return out.value
+
+    # -- row lookup
+    @staticmethod
+    def _rowfind_flags(narrow_hash=False, small_batch=False) -> int:
+        for name, v in (("narrow_hash", narrow_hash), ("small_batch", small_batch)):
+            if not isinstance(v, (bool, np.bool_)):
+                raise TypeError(f"{name} must be a bool, got {type(v).__name__}")
+        return (ROWFIND_NARROW_HASH if narrow_hash else 0) | (ROWFIND_SMALL_BATCH if small_batch else 0)
+
+    def _rowfind_host(self, fn, rows, narrow_hash, small_batch, stats):
+        flags = self._rowfind_flags(narrow_hash, small_batch)
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        if rows.ndim != 2 or rows.shape[1] != self.dim:
+            raise ValueError(f"rows must be [n, {self.dim}]")
+        n = rows.shape[0]
+        out = np.empty(max(n, 1), dtype=np.uint64)
+        st = RowfindStats()
+        check(fn(self._h, _ptr(rows) if n else None, n, flags, _ptr(out) if n else None, C.byref(st)))
+        return (out[:n], st.as_dict()) if stats else out[:n]
+
+    def _rowfind_device(self, fn, t, narrow_hash, small_batch, out_ids):
+        import torch
+        flags = self._rowfind_flags(narrow_hash, small_batch)
+        n, src, stride, stream = self._device_rows(t)
+        out_ids = _device_out(out_ids, (max(n, 1),), torch.int64, t.device)
+        n_out, _ = self._device_u64(out_ids, "out_ids")
+        if n_out < n:
+            raise ValueError(f"out_ids must hold {n} ids")
+        st = RowfindStats()
+        check(fn(self._h, t.data_ptr() if n else None, src, stride, n, flags, out_ids.data_ptr() if n else None, C.byref(st), stream))
+        return out_ids, st.as_dict()
+
+    def find_rows(self, rows: np.ndarray, narrow_hash: bool = False, small_batch: bool = False, stats: bool = False):
+        """uint64 [n]: entry i = the smallest id among the live rows whose stored bits equal rows[i] as add() would store it,
+        ID_NONE if there is none (vrod_index_find_rows).  The handle does not change.  narrow_hash, small_batch:
+        diagnostics, the same result through an 8-bit hash / lookup batches of 96 rows.  stats=True: -> (ids, dict of
+        vrod_rowfind_stats)."""
+        return self._rowfind_host(self._L.vrod_index_find_rows, rows, narrow_hash, small_batch, stats)
+
+    def find_rows_device(self, t, narrow_hash: bool = False, small_batch: bool = False, out_ids=None):
+        """find_rows from a CUDA tensor [n, dim] (float32 / bfloat16 / float16, any row stride >= dim) into a CUDA int64
+        tensor (the bits of uint64), complete on return -> (ids, stats dict) (vrod_index_find_rows_device)."""
+        return self._rowfind_device(self._L.vrod_index_find_rows_device, t, narrow_hash, small_batch, out_ids)
+
+    def add_unique(self, rows: np.ndarray, narrow_hash: bool = False, small_batch: bool = False, stats: bool = False):
+        """An idempotent add(): rows[i] with a live stored copy gets that row's smallest id, a repeat of an earlier row of
+        the call gets that row's id, every other row is appended as add() would append it (vrod_index_add_unique).
+        -> each row's id, uint64 [n]; stats=True: -> (ids, dict of vrod_rowfind_stats)."""
+        return self._rowfind_host(self._L.vrod_index_add_unique, rows, narrow_hash, small_batch, stats)
+
+    def add_unique_device(self, t, narrow_hash: bool = False, small_batch: bool = False, out_ids=None):
+        """add_unique from a CUDA tensor, the ids into a CUDA int64 tensor -> (ids, stats dict)
+        (vrod_index_add_unique_device)."""
+        return self._rowfind_device(self._L.vrod_index_add_unique_device, t, narrow_hash, small_batch, out_ids)
 
     # -- near-duplicate rows
     @staticmethod
