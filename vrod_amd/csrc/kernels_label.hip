@@ -28,22 +28,22 @@ __device__ __forceinline__ uint32_t find_group(const uint32_t* tab, uint32_t G, 
     return lo < G && tab[lo] == label ? lo : kNoSegment;
 }
 
-// SCATTER false: cnt[b * G + g] = eligible rows of group g in block b.
-// SCATTER true : cnt holds each block's first position within the group (label_prefix_kernel), seg_off[g] the group's
+// SCATTER false: cnt[b * cnt_ld + g] = eligible rows of group g in block b.
+// SCATTER true : cnt holds each block's first position within the group (launch_group_prefix), seg_off[g] the group's
 //                first entry in `lists` (kNoSegment: the group wants no list); the rows are written in ascending order.
 // labels == null: every row carries label 0.  mask (may be null): bit set = the row is not eligible.
 template <bool SCATTER>
 __global__ __launch_bounds__(64) void label_group_kernel(const uint32_t* __restrict__ labels, const uint32_t* __restrict__ mask,
                                                          uint64_t count, uint32_t rows_per_block, const uint32_t* __restrict__ table,
-                                                         uint32_t G, uint32_t* __restrict__ cnt, const uint32_t* __restrict__ seg_off,
-                                                         uint32_t* __restrict__ lists) {
+                                                         uint32_t G, uint32_t* __restrict__ cnt, uint32_t cnt_ld,
+                                                         const uint32_t* __restrict__ seg_off, uint32_t* __restrict__ lists) {
     extern __shared__ uint32_t lds[];
     uint32_t* tab = lds;        // [G] sorted labels
     uint32_t* ctr = lds + G;    // [G] running count / next position (kNoSegment: no list)
     const uint32_t lane = threadIdx.x;
     for (uint32_t i = lane; i < G; i += 64) {
         tab[i] = table[i];
-        if constexpr (SCATTER) ctr[i] = seg_off[i] == kNoSegment ? kNoSegment : seg_off[i] + cnt[(uint64_t)blockIdx.x * G + i];
+        if constexpr (SCATTER) ctr[i] = seg_off[i] == kNoSegment ? kNoSegment : seg_off[i] + cnt[(uint64_t)blockIdx.x * cnt_ld + i];
         else ctr[i] = 0u;
     }
     __syncthreads();
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(64) void label_group_kernel(const uint32_t* __restr
     }
     if constexpr (!SCATTER) {
         __syncthreads();
-        for (uint32_t i = lane; i < G; i += 64) cnt[(uint64_t)blockIdx.x * G + i] = ctr[i];
+        for (uint32_t i = lane; i < G; i += 64) cnt[(uint64_t)blockIdx.x * cnt_ld + i] = ctr[i];
     }
 }
 
@@ -125,11 +125,11 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restric
 
 // ------------------------------------------------------------------ launchers
 void launch_label_group_count(const uint32_t* d_labels, const uint32_t* d_mask, uint64_t count, uint32_t rows_per_block,
-                              const uint32_t* d_table, uint32_t G, uint32_t* d_cnt, uint32_t* d_total, hipStream_t s) {
+                              const uint32_t* d_table, uint32_t G, uint32_t* d_cnt, uint32_t cnt_ld, hipStream_t s) {
     if (!G || !count) return;
     const uint32_t n_blocks = (uint32_t)((count + rows_per_block - 1) / rows_per_block);
-    label_group_kernel<false><<<n_blocks, 64, (size_t)G * 8, s>>>(d_labels, d_mask, count, rows_per_block, d_table, G, d_cnt, nullptr, nullptr);
-    label_prefix_kernel<<<(G + 63) / 64, dim3(64, 16), 0, s>>>(d_cnt, n_blocks, G, d_total);
+    label_group_kernel<false><<<n_blocks, 64, (size_t)G * 8, s>>>(d_labels, d_mask, count, rows_per_block, d_table, G, d_cnt, cnt_ld, nullptr,
+                                                                  nullptr);
 }
 
 void launch_group_prefix(uint32_t* d_cnt, uint32_t n_blocks, uint32_t G, uint32_t* d_total, hipStream_t s) {
@@ -138,11 +138,12 @@ void launch_group_prefix(uint32_t* d_cnt, uint32_t n_blocks, uint32_t G, uint32_
 }
 
 void launch_label_group_scatter(const uint32_t* d_labels, const uint32_t* d_mask, uint64_t count, uint32_t rows_per_block,
-                                const uint32_t* d_table, uint32_t G, uint32_t* d_cnt, const uint32_t* d_seg_off, uint32_t* d_lists,
-                                hipStream_t s) {
+                                const uint32_t* d_table, uint32_t G, const uint32_t* d_cnt, uint32_t cnt_ld, const uint32_t* d_seg_off,
+                                uint32_t* d_lists, hipStream_t s) {
     if (!G || !count) return;
     const uint32_t n_blocks = (uint32_t)((count + rows_per_block - 1) / rows_per_block);
-    label_group_kernel<true><<<n_blocks, 64, (size_t)G * 8, s>>>(d_labels, d_mask, count, rows_per_block, d_table, G, d_cnt, d_seg_off, d_lists);
+    label_group_kernel<true><<<n_blocks, 64, (size_t)G * 8, s>>>(d_labels, d_mask, count, rows_per_block, d_table, G, const_cast<uint32_t*>(d_cnt),
+                                                                 cnt_ld, d_seg_off, d_lists);
 }
 
 void launch_label_group_mask(const uint32_t* d_labels, const uint32_t* d_mask, uint64_t count, uint64_t n_words, uint32_t label,

@@ -9,8 +9,8 @@
 // Three passes, all cut the same way: work-group b owns rows [b * R, (b + 1) * R), R = kRowPredRowsPerGroup, and a wave
 // covers 64 rows at a time -- a lane loads its row's tags, value and label (a column that does not exist costs no
 // load), a ballot gives the two 32-bit hit words and their popcount.
-//   count  : the table of a pass's distinct predicates in LDS (kernels_where.hip's walk, the label beside the value),
-//            per-(group, predicate) counts, launch_group_prefix sums them;
+//   count  : the counting walk of kernels_pred.hip over the three columns (launch_pred_group_count with RowPredRows
+//            and R rows a block), launch_group_prefix sums its per-(group, predicate) counts;
 //   hits   : one predicate; the hit bitmap and the group's count.  The bitmap is all that crosses to the host for a
 //            delete, a filter or a retag; RETAG also rewrites the tags of the rows it marks, in the same pass;
 //   scatter: a wave reads its group's 64 hit words back, a lane a word, and writes the ids in ascending order from the
@@ -25,35 +25,6 @@ namespace vrod {
 // bit r of `scope` set = row r is out of scope (deleted, or not allowed); null: every row below count is in scope
 __device__ __forceinline__ bool row_in_scope(const uint32_t* __restrict__ scope, uint64_t r, uint64_t count) {
     return r < count && !(scope && ((scope[r >> 5] >> (r & 31u)) & 1u));
-}
-
-// cnt[b * cnt_ld + g] = rows of group b in scope that match table[g], g < G <= kRowPredsPerPass.  One wave per group.
-__global__ __launch_bounds__(64) void rowpred_count_kernel(const uint64_t* __restrict__ tags, const int64_t* __restrict__ vals,
-                                                           const uint32_t* __restrict__ labels, const uint32_t* __restrict__ scope,
-                                                           uint64_t count, const RowPred* __restrict__ table, uint32_t G,
-                                                           uint32_t* __restrict__ cnt, uint32_t cnt_ld) {
-    extern __shared__ uint64_t lds64[];
-    RowPred* tab = (RowPred*)lds64;                                    // [G]
-    uint32_t* ctr = (uint32_t*)(lds64 + 6 * (size_t)G);               // [G] running counts
-    const uint32_t lane = threadIdx.x;
-    for (uint32_t i = lane; i < G; i += 64) { tab[i] = table[i]; ctr[i] = 0u; }
-    __syncthreads();
-    const uint64_t begin = (uint64_t)blockIdx.x * kRowPredRowsPerGroup;
-    const uint64_t end = begin + kRowPredRowsPerGroup < count ? begin + kRowPredRowsPerGroup : count;
-    for (uint64_t r0 = begin; r0 < end; r0 += 64) {
-        const uint64_t r = r0 + lane;
-        const bool ok = row_in_scope(scope, r, count);
-        const uint64_t t = ok && tags ? tags[r] : 0ull;
-        const int64_t v = ok && vals ? vals[r] : 0ll;
-        const uint32_t l = ok && labels ? labels[r] : 0u;
-        if (!__ballot(ok)) continue;
-        for (uint32_t g = 0; g < G; ++g) {   // every lane reads the same entry: a broadcast
-            const unsigned long long hits = __ballot(ok && row_pred_matches(t, v, l, tab[g]));
-            if (hits && lane == 0) ctr[g] += (uint32_t)__builtin_popcountll(hits);   // (only lane 0 ever touches it)
-        }
-    }
-    __syncthreads();
-    for (uint32_t i = lane; i < G; i += 64) cnt[(uint64_t)blockIdx.x * cnt_ld + i] = ctr[i];
 }
 
 // hits: bit r set = row r is in scope and matches p (RETAG: and its tags change under (t & ~clear_bits) | set_bits,
@@ -118,16 +89,6 @@ __global__ __launch_bounds__(64) void rowpred_scatter_kernel(const uint32_t* __r
 }
 
 // ------------------------------------------------------------------ launchers
-static_assert(sizeof(RowPred) == 48 && kRowPredLdsPerPred == sizeof(RowPred) + 4 && kRowPredsPerPass * kRowPredLdsPerPred <= 64 * 1024,
-              "the pass's table fits the LDS of a plain launch");
-
-void launch_rowpred_count(const uint64_t* d_tags, const int64_t* d_vals, const uint32_t* d_labels, const uint32_t* d_scope, uint64_t count,
-                          const RowPred* d_table, uint32_t G, uint32_t* d_cnt, uint32_t cnt_ld, hipStream_t s) {
-    if (!G || !count) return;
-    rowpred_count_kernel<<<row_pred_groups(count), 64, (size_t)G * kRowPredLdsPerPred, s>>>(d_tags, d_vals, d_labels, d_scope, count, d_table, G,
-                                                                                           d_cnt, cnt_ld);
-}
-
 void launch_rowpred_hits(const uint64_t* d_tags, const int64_t* d_vals, const uint32_t* d_labels, const uint32_t* d_scope, uint64_t count,
                          const RowPred& p, uint32_t* d_hits, uint32_t* d_cnt, hipStream_t s) {
     if (!count) return;

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <utility>
 #include <vector>
 
 #if defined(__HIPCC__)
@@ -23,26 +24,52 @@ constexpr uint32_t kLabelGroupsPerPass = 4096;
 constexpr uint32_t kNoSegment = 0xFFFFFFFFu;
 
 // ------------------------------------------------------------------ grouping
-// The batch's distinct labels in ascending order, and per label its queries in ascending order: group g is
-// q_order[q_off[g] .. q_off[g + 1]).
-struct LabelGroups {
-    std::vector<uint32_t> labels;    // [G]
+// The batch's distinct satisfiable predicates in ascending order, and per predicate its queries in ascending order:
+// group g is q_order[q_off[g] .. q_off[g + 1]).  The queries of unsatisfiable predicates come last in q_order, from
+// q_off[size()] on, ascending: they belong to no group and no pass, their result rows are all unfilled.
+// (A template over the predicate: a label here, tag_plan.h's and where_plan.h's wider ones.)
+template <typename Pred>
+struct PredGroups {
+    std::vector<Pred> preds;         // [G]
     std::vector<uint32_t> q_off;     // [G + 1]
     std::vector<uint32_t> q_order;   // [nq]
-    uint32_t size() const { return (uint32_t)labels.size(); }
+    uint32_t size() const { return (uint32_t)preds.size(); }
     uint32_t nq_of(uint32_t g) const { return q_off[g + 1] - q_off[g]; }
+    uint32_t n_unsatisfiable() const { return (uint32_t)q_order.size() - q_off.back(); }
 };
-inline LabelGroups label_groups(const uint32_t* query_labels, uint32_t nq) {
-    LabelGroups G;
+// unsat(p): no row can match p; before(a, b): the strict order of the groups.
+template <typename Pred, typename Unsat, typename Before>
+inline PredGroups<Pred> group_preds(const Pred* p, uint32_t nq, Unsat unsat, Before before) {
+    PredGroups<Pred> G;
     G.q_order.resize(nq);
     for (uint32_t i = 0; i < nq; ++i) G.q_order[i] = i;
-    std::stable_sort(G.q_order.begin(), G.q_order.end(), [&](uint32_t a, uint32_t b) { return query_labels[a] < query_labels[b]; });
-    for (uint32_t i = 0; i < nq; ++i) {
-        const uint32_t l = query_labels[G.q_order[i]];
-        if (G.labels.empty() || G.labels.back() != l) { G.labels.push_back(l); G.q_off.push_back(i); }
+    auto less = [&](uint32_t a, uint32_t b) {
+        const bool ua = unsat(p[a]), ub = unsat(p[b]);
+        if (ua != ub) return ub;
+        if (ua) return false;
+        return before(p[a], p[b]);
+    };
+    std::stable_sort(G.q_order.begin(), G.q_order.end(), less);
+    uint32_t i = 0;
+    for (; i < nq && !unsat(p[G.q_order[i]]); ++i) {
+        const Pred& t = p[G.q_order[i]];
+        if (G.preds.empty() || before(G.preds.back(), t)) {
+            G.preds.push_back(t);
+            G.q_off.push_back(i);
+        }
     }
-    G.q_off.push_back(nq);
+    G.q_off.push_back(i);
     return G;
+}
+// Labels: every label can occur, so every query is in a group; ascending.  `labels` is the groups' `preds` under the
+// name a label's readers use (a reference into the object itself, so the object is built in place and never copied).
+struct LabelGroups : PredGroups<uint32_t> {
+    const std::vector<uint32_t>& labels = preds;   // [G]
+    LabelGroups(PredGroups<uint32_t>&& g) : PredGroups<uint32_t>(std::move(g)) {}
+    LabelGroups(const LabelGroups&) = delete;
+};
+inline LabelGroups label_groups(const uint32_t* query_labels, uint32_t nq) {
+    return group_preds(query_labels, nq, [](uint32_t) { return false; }, [](uint32_t a, uint32_t b) { return a < b; });
 }
 
 // Rows per block of the grouping pass over N rows: whole 64-row waves, about 2048 blocks on a large corpus (each block's

@@ -1,7 +1,7 @@
 // rowpred_plan.h -- the host decisions of the row-predicate operations (vrod_index_count_where, _select_where,
 // _delete_where, _set_filter_where, _set_tags_where).  Plain arithmetic, no HIP headers (where_plan.h, tag_plan.h):
 // vrod_index.hip enqueues what these functions decide, tests/test_rowpred_plan.py compiles this header as host C++.
-// row_pred_matches is the one function the kernels share with the host (kernels_rowpred.hip).
+// row_pred_matches is the one function the kernels share with the host (kernels_pred.hip, kernels_rowpred.hip).
 //
 // The predicate is the one of vrod_search_where with the row's label beside it; here it is an operation on the rows
 // themselves, not a restriction of one search.
@@ -31,7 +31,7 @@ inline bool row_pred_before(const RowPred& a, const RowPred& b) {
     return a.has_label && a.label < b.label;
 }
 
-// Distinct predicates one pass of vrod_index_count_where over the three columns serves.  The kernel keeps the table
+// Distinct predicates one pass of vrod_index_count_where over the three columns serves.  kernels_pred.hip keeps the table
 // (48 B) and one counter (4 B) per predicate in LDS: 1024 predicates are 52 KiB, under the 64 KiB a launch gets without
 // asking for more, as where_plan.h chooses kWhereGroupsPerPass.  (The pass asks for the LDS of the predicates it has.)
 constexpr uint32_t kRowPredsPerPass = 1024;

@@ -1,7 +1,7 @@
 // tag_plan.h -- the host decisions of a tagged search (vrod_search_tagged): the batch's queries grouped by their
 // predicate, and the narrow groups cut into scatter passes.  Plain arithmetic, no HIP headers (label_plan.h,
 // search_plan.h): vrod_index.hip enqueues what these functions decide, tests/test_tag_plan.py compiles this header as
-// host C++.  tag_matches is the one function the kernels share with the host (kernels_tag.hip).
+// host C++.  tag_matches is the one function the kernels share with the host (kernels_pred.hip).
 //
 // A narrow group (filter_route says its own rows are cheaper than a scan) gets a row list and is scored with the other
 // narrow groups of its pass in the segmented launch of a labelled search (label_plan.h plan_segments).  A wide group
@@ -12,7 +12,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "label_plan.h"   // kNoSegment
+#include "label_plan.h"   // kNoSegment, PredGroups, group_preds
 
 #if defined(__HIPCC__)
 #define VROD_TAG_HD __host__ __device__
@@ -30,51 +30,14 @@ VROD_TAG_HD inline bool tag_matches(uint64_t t, uint64_t any, uint64_t all, uint
 // A bit both required and forbidden: no row can match, whatever its tags.
 inline bool tag_unsatisfiable(const TagPred& p) { return (p.all & p.none) != 0; }
 
-// Distinct predicates one pass over the tag array serves.  kernels_tag.hip keeps the predicate table (24 B) and one
+// Distinct predicates one pass over the tag array serves.  kernels_pred.hip keeps the predicate table (24 B) and one
 // counter (4 B) per group in LDS: 2048 groups are 56 KiB, under the 64 KiB a launch gets without asking for more.
 // (The pass asks for the LDS of the groups it has, so a small batch keeps the CU's occupancy.)
 constexpr uint32_t kTagGroupsPerPass = 2048;
 constexpr uint32_t kTagLdsPerGroup = 28;
 
 // ------------------------------------------------------------------ grouping
-// The batch's distinct satisfiable predicates in ascending order, and per predicate its queries in ascending order:
-// group g is q_order[q_off[g] .. q_off[g + 1]).  The queries of unsatisfiable predicates come last in q_order, from
-// q_off[size()] on, ascending: they belong to no group and no pass, their result rows are all unfilled.
-// (A template over the predicate: where_plan.h groups its wider predicates with the same code.)
-template <typename Pred>
-struct PredGroups {
-    std::vector<Pred> preds;         // [G]
-    std::vector<uint32_t> q_off;     // [G + 1]
-    std::vector<uint32_t> q_order;   // [nq]
-    uint32_t size() const { return (uint32_t)preds.size(); }
-    uint32_t nq_of(uint32_t g) const { return q_off[g + 1] - q_off[g]; }
-    uint32_t n_unsatisfiable() const { return (uint32_t)q_order.size() - q_off.back(); }
-};
-// unsat(p): no row can match p; before(a, b): the strict order of the groups.
-template <typename Pred, typename Unsat, typename Before>
-inline PredGroups<Pred> group_preds(const Pred* p, uint32_t nq, Unsat unsat, Before before) {
-    PredGroups<Pred> G;
-    G.q_order.resize(nq);
-    for (uint32_t i = 0; i < nq; ++i) G.q_order[i] = i;
-    auto less = [&](uint32_t a, uint32_t b) {
-        const bool ua = unsat(p[a]), ub = unsat(p[b]);
-        if (ua != ub) return ub;
-        if (ua) return false;
-        return before(p[a], p[b]);
-    };
-    std::stable_sort(G.q_order.begin(), G.q_order.end(), less);
-    uint32_t i = 0;
-    for (; i < nq && !unsat(p[G.q_order[i]]); ++i) {
-        const Pred& t = p[G.q_order[i]];
-        if (G.preds.empty() || before(G.preds.back(), t)) {
-            G.preds.push_back(t);
-            G.q_off.push_back(i);
-        }
-    }
-    G.q_off.push_back(i);
-    return G;
-}
-// Tag predicates: ordered by (any, all, none).
+// Tag predicates (label_plan.h group_preds): ordered by (any, all, none).
 using TagGroups = PredGroups<TagPred>;
 inline bool tag_before(const TagPred& a, const TagPred& b) {
     if (a.any != b.any) return a.any < b.any;
@@ -96,7 +59,9 @@ struct TagPass {
 // it matches, so the lists of a batch are not bounded by the corpus: passes of consecutive groups, cut where the next
 // narrow group would take the pass's lists over `max_bytes` (the 1 GiB rule of the gather and exact paths) or the pass
 // over `max_groups` groups (the LDS table).  A group whose own list exceeds max_bytes is served alone.  Every narrow
-// group is in exactly one pass; a run of wide groups adds no pass of its own.
+// group is in exactly one pass; a run of wide groups adds no pass of its own.  (Labels' groups are disjoint, their lists
+// hold the corpus at the most: a labelled search passes no limit, kNoListLimit, and gets one pass per max_groups.)
+constexpr uint64_t kNoListLimit = ~0ull;
 inline std::vector<TagPass> plan_tag_passes(const std::vector<uint32_t>& m, const std::vector<uint8_t>& narrow,
                                             uint64_t max_bytes = 1ull << 30, uint32_t max_groups = kTagGroupsPerPass) {
     std::vector<TagPass> passes;

@@ -2681,17 +2681,8 @@ static int check_thresholds(const float* h_thr, uint32_t nq) {
     return VROD_OK;
 }
 
-// ------------------------------------------------------------------ labelled search (vrod_search_labeled)
-// Query q sees the eligible rows (live, allowed) that carry query_labels[q].  The batch's queries are grouped by label
-// (label_plan.h); ONE device pass over the label array (kernels_label.hip) counts every group's eligible rows and
-// writes the row lists of the groups that want one; filter_route -- the rule of a filtered search, with the group's
-// rows and queries -- sends a group to
-//   the segmented route: the canonical scores of its own rows, all such groups of the batch in one launch per score
-//     chunk (kernels_rescore.hip rescore_segments_kernel), the select chain with a length per query, exact by
-//     construction as the gather path is; or
-//   the dense route: the ordinary search flow (fast pass, certificate, band, exact) over the whole corpus with the
-//     group's mask -- handle mask | (label != L) -- in place of row_mask(): broad groups are few, one search each.
-// Synchronous: the handle is idle before and after.  d_queries_raw / d_out_*: device memory, h_labels: host.
+// ------------------------------------------------------------------ the steps of the searches over groups of rows
+// A dense group's stats folded into the call's.
 static void fold_stats(vrod_search_stats& st, const vrod_search_stats& d) {
     st.path = d.path;
     st.kprime = std::max(st.kprime, d.kprime);
@@ -2753,7 +2744,8 @@ static int label_pass_ws(vrod_index* idx, uint32_t Gc, LabelPassWs& W) {
 // h_total: the totals are read back into it, and the stream is drained; null: the launch is only enqueued.
 static int label_count_pass(vrod_index* idx, hipStream_t s, const LabelPassWs& W, const uint32_t* h_table, uint32_t Gp, uint32_t* h_total) {
     HIP_TRY(hipMemcpyAsync(W.table, h_table, (size_t)Gp * 4, hipMemcpyHostToDevice, s));
-    launch_label_group_count(idx->labels.d(), idx->row_mask(), idx->count, W.rpb, W.table, Gp, W.cnt, W.total, s);
+    launch_label_group_count(idx->labels.d(), idx->row_mask(), idx->count, W.rpb, W.table, Gp, W.cnt, Gp, s);
+    launch_group_prefix(W.cnt, (uint32_t)((idx->count + W.rpb - 1) / W.rpb), Gp, W.total, s);
     if (!h_total) return VROD_OK;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(h_total, W.total, (size_t)Gp * 4, hipMemcpyDeviceToHost, s));
@@ -2766,7 +2758,8 @@ static int label_scatter_pass(vrod_index* idx, hipStream_t s, const LabelPassWs&
     VROD_TRY(idx->lab_lists.ensure(std::max<uint64_t>(list_n, 1) * 4));
     HIP_TRY(hipMemcpyAsync(W.seg_off, h_seg_off, (size_t)Gp * 4, hipMemcpyHostToDevice, s));
     if (list_n)
-        launch_label_group_scatter(idx->labels.d(), idx->row_mask(), idx->count, W.rpb, W.table, Gp, W.cnt, W.seg_off, idx->lab_lists.as<uint32_t>(), s);
+        launch_label_group_scatter(idx->labels.d(), idx->row_mask(), idx->count, W.rpb, W.table, Gp, W.cnt, Gp, W.seg_off,
+                                   idx->lab_lists.as<uint32_t>(), s);
     HIP_TRY(hipGetLastError());
     return VROD_OK;
 }
@@ -2854,124 +2847,71 @@ static int dense_group_search(vrod_index* idx, hipStream_t s, vrod_search_stats&
     return VROD_OK;
 }
 
-static int labeled_search(vrod_index* idx, const float* d_queries_raw, uint32_t nq, uint32_t k, const uint32_t* h_labels,
-                          uint64_t* d_out_ids, float* d_out_scores) {
-    vrod_search_stats st{};
-    st.nq = nq; st.k = k; st.path = VROD_PATH_GATHER;
-    const uint64_t N = idx->count;
-    Pending& P = next_slot(idx);
-    hipStream_t s = P.stream;
-    if (N == 0) return return_unfilled(idx, s, st, d_out_ids, d_out_scores, (uint64_t)nq * k);   // an empty handle
-    VROD_TRY(prep_queries_checked(idx, P, d_queries_raw, nq));
-
-    // ---- groups, and the per-slot arrays of the segmented route (filled as the passes route their groups)
-    const LabelGroups G = label_groups(h_labels, nq);
-    const uint32_t* base_mask = idx->row_mask();
-    const double row_bytes = (double)idx->ld * idx->esize;
-    struct Dense { uint32_t g; uint64_t m; };
-    std::vector<Dense> dense;
-    // device copy of q_order (a dense group's queries, and the scatter of its results) followed by as many ones
-    VROD_TRY(idx->lab_slots.ensure((size_t)nq * 4 * 5));
-    uint32_t* d_qorder = idx->lab_slots.as<uint32_t>();
-    uint32_t* d_ones = d_qorder + nq;
-    const DevSlots d_slots = dev_slots(d_ones + nq, nq);
-    {
-        std::vector<uint32_t> up(G.q_order);
-        up.resize((size_t)nq * 2, 1u);
-        HIP_TRY(hipMemcpyAsync(d_qorder, up.data(), up.size() * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    Timer tm(idx, P);
-    P.reset_events();
-    for (uint32_t g0 = 0; g0 < G.size(); g0 += kLabelGroupsPerPass) {
-        const uint32_t Gp = std::min<uint32_t>(kLabelGroupsPerPass, G.size() - g0);
-        // ---- pass 1: every group's eligible rows, counted per block of the label array
-        LabelPassWs W;
-        VROD_TRY(label_pass_ws(idx, Gp, W));
-        std::vector<uint32_t> m(Gp);
-        VROD_TRY(label_count_pass(idx, s, W, G.labels.data() + g0, Gp, m.data()));
-        // ---- route
-        std::vector<uint32_t> seg_off(Gp, kNoSegment);
-        SlotTables T;
-        uint64_t list_n = 0;
-        for (uint32_t i = 0; i < Gp; ++i) {
-            const uint32_t g = g0 + i, nqg = G.nq_of(g);
-            if (!filter_route(idx->path, idx->dtype, N, m[i], nqg, idx->dim)) { dense.push_back({g, m[i]}); continue; }
-            seg_off[i] = (uint32_t)list_n;
-            T.add((uint32_t)list_n, m[i], &G.q_order[G.q_off[g]], nqg);
-            list_n += m[i];   // (the groups' rows are disjoint: at most N in all)
-            st.scan_bytes += (double)m[i] * row_bytes;
-            st.scan_flops += 2.0 * nqg * (double)m[i] * idx->dim;
-        }
-        if (T.segs.empty()) continue;
-        // ---- pass 2: the segmented groups' row lists, ascending
-        VROD_TRY(label_scatter_pass(idx, s, W, seg_off.data(), Gp, list_n));
-        VROD_TRY(score_segments(idx, P, tm, st, T, d_slots, k, d_out_ids, d_out_scores));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    tm.add_scan_ms(st);
-
-    // ---- dense groups: one ordinary search each, over the group's mask
-    if (!dense.empty()) {
-        const uint64_t words = idx->del_bits.size();   // capacity / 32
-        uint32_t max_nq = 0;
-        for (const Dense& d : dense) max_nq = std::max(max_nq, G.nq_of(d.g));
-        VROD_TRY(wide_group_ws(idx, max_nq, k));
-        for (const Dense& d : dense) {
-            const uint32_t nqg = G.nq_of(d.g);
-            const uint32_t* d_qidx = d_qorder + G.q_off[d.g];
-            launch_label_group_mask(idx->labels.d(), base_mask, N, words, G.labels[d.g], idx->lab_mask.as<uint32_t>(), s);
-            VROD_TRY(dense_group_search(idx, s, st, d_queries_raw, d_qidx, d_ones, nqg, d.m, k, d_out_ids, d_out_scores));
-        }
-    }
-    idx->stats = st;
-    return VROD_OK;
-}
-
-// ------------------------------------------------------------------ predicate searches (vrod_search_tagged, vrod_search_where)
-// What the flow below needs of a predicate type: its grouping, the groups one pass serves, and the three launches over
-// the handle's side arrays -- count and scatter over a pass's table, and one predicate's effective mask.
-struct TagSearch {
-    using Pred = TagPred;
-    static constexpr uint32_t kGroupsPerPass = kTagGroupsPerPass;
-    static TagGroups groups(const TagPred* p, uint32_t nq) { return tag_groups(p, nq); }
-    static void count(const vrod_index* idx, const uint32_t* mask, uint32_t rpb, const TagPred* table, uint32_t G, uint32_t* cnt, uint32_t cnt_ld,
+// ------------------------------------------------------------------ searches over groups of rows (vrod_search_labeled, _tagged, _where)
+// What the flow below needs of a predicate type: its grouping, the groups one pass serves, the bytes the row lists of
+// one scatter pass may take, and the three launches over the handle's side arrays -- count and scatter over a pass's
+// table, and one predicate's effective mask.
+struct LabelSearch {
+    using Pred = uint32_t;
+    static constexpr uint32_t kGroupsPerPass = kLabelGroupsPerPass;
+    static constexpr uint64_t kMaxListBytes = kNoListLimit;   // a row carries one label: a chunk's lists hold the corpus at the most
+    static LabelGroups groups(const uint32_t* p, uint32_t nq) { return label_groups(p, nq); }
+    static void count(const vrod_index* idx, const uint32_t* mask, uint32_t rpb, const uint32_t* table, uint32_t G, uint32_t* cnt, uint32_t cnt_ld,
                       hipStream_t s) {
-        launch_tag_group_count(idx->tags.d(), mask, idx->count, rpb, table, G, cnt, cnt_ld, s);
+        launch_label_group_count(idx->labels.d(), mask, idx->count, rpb, table, G, cnt, cnt_ld, s);
     }
-    static void scatter(const vrod_index* idx, const uint32_t* mask, uint32_t rpb, const TagPred* table, uint32_t G, const uint32_t* cnt,
+    static void scatter(const vrod_index* idx, const uint32_t* mask, uint32_t rpb, const uint32_t* table, uint32_t G, const uint32_t* cnt,
                         uint32_t cnt_ld, const uint32_t* seg_off, uint32_t* lists, hipStream_t s) {
-        launch_tag_group_scatter(idx->tags.d(), mask, idx->count, rpb, table, G, cnt, cnt_ld, seg_off, lists, s);
+        launch_label_group_scatter(idx->labels.d(), mask, idx->count, rpb, table, G, cnt, cnt_ld, seg_off, lists, s);
     }
-    static void mask_of(const vrod_index* idx, const uint32_t* mask, uint64_t words, const TagPred& p, uint32_t* out, hipStream_t s) {
-        launch_tag_group_mask(idx->tags.d(), mask, idx->count, words, p, out, s);
+    static void mask_of(const vrod_index* idx, const uint32_t* mask, uint64_t words, uint32_t label, uint32_t* out, hipStream_t s) {
+        launch_label_group_mask(idx->labels.d(), mask, idx->count, words, label, out, s);
     }
 };
-struct WhereSearch {
-    using Pred = WherePred;
-    static constexpr uint32_t kGroupsPerPass = kWhereGroupsPerPass;
-    static WhereGroups groups(const WherePred* p, uint32_t nq) { return where_groups(p, nq); }
-    static void count(const vrod_index* idx, const uint32_t* mask, uint32_t rpb, const WherePred* table, uint32_t G, uint32_t* cnt,
-                      uint32_t cnt_ld, hipStream_t s) {
-        launch_where_group_count(idx->tags.d(), idx->values.d(), mask, idx->count, rpb, table, G, cnt, cnt_ld, s);
+// Tags, and tags + value: the kernels of kernels_pred.hip over the handle's columns of that kind of row.
+template <typename Rows> static Rows rows_of(const vrod_index* idx);
+template <> TagRows rows_of(const vrod_index* idx) { return {idx->tags.d()}; }
+template <> WhereRows rows_of(const vrod_index* idx) { return {idx->tags.d(), idx->values.d()}; }
+template <> RowPredRows rows_of(const vrod_index* idx) { return {idx->tags.d(), idx->values.d(), idx->labels.d()}; }
+template <typename Rows, uint32_t PER_PASS>
+struct ColumnSearch {
+    using Pred = typename Rows::Pred;
+    static constexpr uint32_t kGroupsPerPass = PER_PASS;
+    static constexpr uint64_t kMaxListBytes = 1ull << 30;   // a row sits in every list it matches: the 1 GiB rule
+    static void count(const vrod_index* idx, const uint32_t* mask, uint32_t rpb, const Pred* table, uint32_t G, uint32_t* cnt, uint32_t cnt_ld,
+                      hipStream_t s) {
+        launch_pred_group_count(rows_of<Rows>(idx), mask, idx->count, rpb, table, G, cnt, cnt_ld, s);
     }
-    static void scatter(const vrod_index* idx, const uint32_t* mask, uint32_t rpb, const WherePred* table, uint32_t G, const uint32_t* cnt,
+    static void scatter(const vrod_index* idx, const uint32_t* mask, uint32_t rpb, const Pred* table, uint32_t G, const uint32_t* cnt,
                         uint32_t cnt_ld, const uint32_t* seg_off, uint32_t* lists, hipStream_t s) {
-        launch_where_group_scatter(idx->tags.d(), idx->values.d(), mask, idx->count, rpb, table, G, cnt, cnt_ld, seg_off, lists, s);
+        launch_pred_group_scatter(rows_of<Rows>(idx), mask, idx->count, rpb, table, G, cnt, cnt_ld, seg_off, lists, s);
     }
-    static void mask_of(const vrod_index* idx, const uint32_t* mask, uint64_t words, const WherePred& p, uint32_t* out, hipStream_t s) {
-        launch_where_group_mask(idx->tags.d(), idx->values.d(), mask, idx->count, words, p, out, s);
+    static void mask_of(const vrod_index* idx, const uint32_t* mask, uint64_t words, const Pred& p, uint32_t* out, hipStream_t s) {
+        launch_pred_group_mask(rows_of<Rows>(idx), mask, idx->count, words, p, out, s);
     }
+};
+struct TagSearch : ColumnSearch<TagRows, kTagGroupsPerPass> {
+    static TagGroups groups(const TagPred* p, uint32_t nq) { return tag_groups(p, nq); }
+};
+struct WhereSearch : ColumnSearch<WhereRows, kWhereGroupsPerPass> {
+    static WhereGroups groups(const WherePred* p, uint32_t nq) { return where_groups(p, nq); }
 };
 
-// Query q sees the eligible rows (live, allowed) that match h_preds[q].  The labelled search with two differences
-// (tag_plan.h, kernels_tag.hip; where_plan.h, kernels_where.hip): a group is a distinct predicate, and a row belongs to
-// every group it matches.  So every chunk of S::kGroupsPerPass groups is counted first -- one pass over the side arrays,
-// into a [blocks][groups] matrix -- and its groups routed by filter_route on their counts; then the chunk's narrow
-// groups' row lists are written and scored in passes whose lists stay under the 1 GiB rule (their sum is not bounded by
-// the corpus), each pass one segmented score launch per score chunk; after the last chunk the wide groups take one
-// masked ordinary search each.  Queries whose predicate no row can match (all & none != 0, an empty interval) are in no
-// group: their result rows are filled as unfilled and nothing else looks at them.
+// Query q sees the eligible rows (live, allowed) that match h_preds[q]: carry its label, match its tag predicate, or
+// match its tags + value-interval predicate (label_plan.h, kernels_label.hip; tag_plan.h, where_plan.h,
+// kernels_pred.hip).  A group is a distinct predicate.  Every chunk of S::kGroupsPerPass groups is counted first -- one
+// pass over the side arrays, into a [blocks][groups] matrix -- and its groups routed by filter_route -- the rule of a
+// filtered search, with the group's rows and queries -- to
+//   the segmented route: the canonical scores of its own rows, all such groups of a scatter pass in one launch per
+//     score chunk (kernels_rescore.hip rescore_segments_kernel), the select chain with a length per query, exact by
+//     construction as the gather path is; or
+//   the dense route: the ordinary search flow (fast pass, certificate, band, exact) over the whole corpus with the
+//     group's mask -- handle mask | no match -- in place of row_mask(): broad groups are few, one search each.
+// The chunk's narrow groups' row lists are written and scored in passes whose lists stay under S::kMaxListBytes (a row
+// belongs to every tag or where group it matches, so their sum is not bounded by the corpus; labels' groups are
+// disjoint and a chunk is one pass), each pass one segmented score launch per score chunk; after the last chunk the
+// wide groups take one masked ordinary search each.  Queries whose predicate no row can match (all & none != 0, an
+// empty interval) are in no group: their result rows are filled as unfilled and nothing else looks at them.
 // Synchronous: the handle is idle before and after.  d_queries_raw / d_out_*: device memory, h_preds: host.
 template <typename S>
 static int pred_search(vrod_index* idx, const float* d_queries_raw, uint32_t nq, uint32_t k, const typename S::Pred* h_preds,
@@ -2986,7 +2926,7 @@ static int pred_search(vrod_index* idx, const float* d_queries_raw, uint32_t nq,
     if (N == 0) return return_unfilled(idx, s, st, d_out_ids, d_out_scores, (uint64_t)nq * k);   // an empty handle
     VROD_TRY(prep_queries_checked(idx, P, d_queries_raw, nq));
 
-    const PredGroups<Pred> G = S::groups(h_preds, nq);
+    const auto G = S::groups(h_preds, nq);   // PredGroups<Pred>
     const uint32_t Gn = G.size();
     if (!Gn) return return_unfilled(idx, s, st, d_out_ids, d_out_scores, (uint64_t)nq * k);   // no predicate can match
     if (G.n_unsatisfiable()) {   // (the groups' queries overwrite their own rows below)
@@ -3036,7 +2976,7 @@ static int pred_search(vrod_index* idx, const float* d_queries_raw, uint32_t nq,
         const std::vector<uint32_t> mc(m.begin() + c0, m.begin() + c0 + Gp);
         const std::vector<uint8_t> nc(narrow.begin() + c0, narrow.begin() + c0 + Gp);
         // ---- pass 2 per scatter pass: the narrow groups' row lists, ascending, then score + select
-        for (const TagPass& tp : plan_tag_passes(mc, nc, 1ull << 30, kPerPass)) {
+        for (const TagPass& tp : plan_tag_passes(mc, nc, S::kMaxListBytes, kPerPass)) {
             SlotTables T;
             for (uint32_t i = tp.g0; i < tp.g1; ++i) {
                 const uint32_t g = c0 + i, base = tp.seg_off[i - tp.g0], nqg = G.nq_of(g);
@@ -4856,27 +4796,44 @@ int vrod_index_get_labels(vrod_index* idx, uint64_t first_id, uint64_t n, uint32
     return column_get(idx, idx->labels, first_id, n, out_labels);
 }
 
-static int check_labeled_args(vrod_index* idx, const void* q, uint32_t nq, uint32_t k, const void* labels, const void* oi, const void* os) {
-    return check_derived_args(idx, "vrod_search_labeled", kLabelsNotRouted, nq, {q, oi, os}, true, k, {labels});
+static_assert(sizeof(vrod_tag_pred) == 24 && sizeof(TagPred) == 24, "vrod_tag_pred is three packed 64-bit words");
+static_assert(sizeof(vrod_where) == 40 && sizeof(WherePred) == 40, "vrod_where is five packed 64-bit words");
+
+// The two forms of a search over groups of rows (S: LabelSearch, TagSearch, WhereSearch; ApiPred: the header's type of
+// S::Pred's layout).
+static const char kValuesNotRouted[] = "tags and values are not routed to the shards";
+extern "C++" {
+template <typename S, typename ApiPred>
+static int pred_search_host(vrod_index* idx, const char* what, const char* why_not, const float* queries, uint32_t nq, uint32_t k,
+                            const ApiPred* preds, uint64_t* out_ids, float* out_scores) {
+    VROD_TRY(check_derived_args(idx, what, why_not, nq, {queries, out_ids, out_scores}, true, k, {preds}));
+    if (!nq) return VROD_OK;
+    VROD_TRY(begin_host_form(idx, what, idx->count ? queries : nullptr, nq, nq, k));   // (an empty handle reads none)
+    VROD_TRY(pred_search<S>(idx, idx->host_q.as<float>(), nq, k, reinterpret_cast<const typename S::Pred*>(preds), idx->out_ids.as<uint64_t>(),
+                            idx->out_scores.as<float>()));
+    return copy_topk_out(idx, nq, k, out_ids, out_scores);
 }
+template <typename S, typename ApiPred>
+static int pred_search_device(vrod_index* idx, const char* what, const char* what_device, const char* why_not, const float* d_queries, uint32_t nq,
+                              uint32_t k, const ApiPred* d_preds, uint64_t* d_out_ids, float* d_out_scores, void* stream) {
+    VROD_TRY(check_derived_args(idx, what, why_not, nq, {d_queries, d_out_ids, d_out_scores}, true, k, {d_preds}));
+    if (!nq) return VROD_OK;
+    VROD_TRY(begin_sync_device(idx, what_device, stream));
+    std::vector<typename S::Pred> preds(nq);
+    HIP_TRY(hipMemcpy(preds.data(), d_preds, (size_t)nq * sizeof(typename S::Pred), hipMemcpyDeviceToHost));
+    return pred_search<S>(idx, d_queries, nq, k, preds.data(), d_out_ids, d_out_scores);
+}
+}  // extern "C++"
 
 int vrod_search_labeled(vrod_index* idx, const float* queries, uint32_t nq, uint32_t k, const uint32_t* query_labels,
                         uint64_t* out_ids, float* out_scores) {
-    VROD_TRY(check_labeled_args(idx, queries, nq, k, query_labels, out_ids, out_scores));
-    if (!nq) return VROD_OK;
-    VROD_TRY(begin_host_form(idx, "vrod_search_labeled", queries, nq, nq, k));
-    VROD_TRY(labeled_search(idx, idx->host_q.as<float>(), nq, k, query_labels, idx->out_ids.as<uint64_t>(), idx->out_scores.as<float>()));
-    return copy_topk_out(idx, nq, k, out_ids, out_scores);
+    return pred_search_host<LabelSearch>(idx, "vrod_search_labeled", kLabelsNotRouted, queries, nq, k, query_labels, out_ids, out_scores);
 }
 
 int vrod_search_labeled_device(vrod_index* idx, const float* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_query_labels,
                                uint64_t* d_out_ids, float* d_out_scores, void* stream) {
-    VROD_TRY(check_labeled_args(idx, d_queries, nq, k, d_query_labels, d_out_ids, d_out_scores));
-    if (!nq) return VROD_OK;
-    VROD_TRY(begin_sync_device(idx, "vrod_search_labeled_device", stream));
-    std::vector<uint32_t> labels(nq);
-    HIP_TRY(hipMemcpy(labels.data(), d_query_labels, (size_t)nq * 4, hipMemcpyDeviceToHost));
-    return labeled_search(idx, d_queries, nq, k, labels.data(), d_out_ids, d_out_scores);
+    return pred_search_device<LabelSearch>(idx, "vrod_search_labeled", "vrod_search_labeled_device", kLabelsNotRouted, d_queries, nq, k,
+                                           d_query_labels, d_out_ids, d_out_scores, stream);
 }
 
 
@@ -5113,34 +5070,6 @@ int vrod_index_key_stats(const vrod_index* idx, vrod_key_stats* out) {
     return VROD_OK;
 }
 
-static_assert(sizeof(vrod_tag_pred) == 24 && sizeof(TagPred) == 24, "vrod_tag_pred is three packed 64-bit words");
-static_assert(sizeof(vrod_where) == 40 && sizeof(WherePred) == 40, "vrod_where is five packed 64-bit words");
-
-// The two forms of a predicate search (S: TagSearch, WhereSearch; ApiPred: the header's struct of S::Pred's layout).
-static const char kValuesNotRouted[] = "tags and values are not routed to the shards";
-extern "C++" {
-template <typename S, typename ApiPred>
-static int pred_search_host(vrod_index* idx, const char* what, const char* why_not, const float* queries, uint32_t nq, uint32_t k,
-                            const ApiPred* preds, uint64_t* out_ids, float* out_scores) {
-    VROD_TRY(check_derived_args(idx, what, why_not, nq, {queries, out_ids, out_scores}, true, k, {preds}));
-    if (!nq) return VROD_OK;
-    VROD_TRY(begin_host_form(idx, what, idx->count ? queries : nullptr, nq, nq, k));   // (an empty handle reads none)
-    VROD_TRY(pred_search<S>(idx, idx->host_q.as<float>(), nq, k, reinterpret_cast<const typename S::Pred*>(preds), idx->out_ids.as<uint64_t>(),
-                            idx->out_scores.as<float>()));
-    return copy_topk_out(idx, nq, k, out_ids, out_scores);
-}
-template <typename S, typename ApiPred>
-static int pred_search_device(vrod_index* idx, const char* what, const char* what_device, const char* why_not, const float* d_queries, uint32_t nq,
-                              uint32_t k, const ApiPred* d_preds, uint64_t* d_out_ids, float* d_out_scores, void* stream) {
-    VROD_TRY(check_derived_args(idx, what, why_not, nq, {d_queries, d_out_ids, d_out_scores}, true, k, {d_preds}));
-    if (!nq) return VROD_OK;
-    VROD_TRY(begin_sync_device(idx, what_device, stream));
-    std::vector<typename S::Pred> preds(nq);
-    HIP_TRY(hipMemcpy(preds.data(), d_preds, (size_t)nq * sizeof(typename S::Pred), hipMemcpyDeviceToHost));
-    return pred_search<S>(idx, d_queries, nq, k, preds.data(), d_out_ids, d_out_scores);
-}
-}  // extern "C++"
-
 int vrod_search_tagged(vrod_index* idx, const float* queries, uint32_t nq, uint32_t k, const vrod_tag_pred* preds, uint64_t* out_ids,
                        float* out_scores) {
     return pred_search_host<TagSearch>(idx, "vrod_search_tagged", kTagsNotRouted, queries, nq, k, preds, out_ids, out_scores);
@@ -5246,7 +5175,7 @@ int vrod_index_count_where(vrod_index* idx, const vrod_row_pred* preds, uint32_t
         for (size_t c0 = 0; c0 < table.size(); c0 += kRowPredsPerPass) {   // one pass over the columns per table
             const uint32_t Gp = (uint32_t)std::min<size_t>(kRowPredsPerPass, table.size() - c0);
             HIP_TRY(hipMemcpyAsync(d_table, table.data() + c0, (size_t)Gp * sizeof(RowPred), hipMemcpyHostToDevice, s));
-            launch_rowpred_count(idx->tags.d(), idx->values.d(), idx->labels.d(), scope, idx->count, d_table, Gp, idx->lab_cnt.as<uint32_t>(), Gp, s);
+            launch_pred_group_count(rows_of<RowPredRows>(idx), scope, idx->count, kRowPredRowsPerGroup, d_table, Gp, idx->lab_cnt.as<uint32_t>(), Gp, s);
             launch_group_prefix(idx->lab_cnt.as<uint32_t>(), n_groups, Gp, d_total, s);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(totals.data() + c0, d_total, (size_t)Gp * 4, hipMemcpyDeviceToHost, s));

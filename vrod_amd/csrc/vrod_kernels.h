@@ -255,15 +255,16 @@ void launch_rescore_segments(const void* d_corpus, int dtype, int metric, uint32
                              const uint32_t* d_lists, float* d_out, uint64_t out_ld, hipStream_t s);
 
 // ---- kernels_label.hip : rows grouped by the labels of a batch, one label's dense-scan mask
-// Pass 1 + prefix: d_cnt [blocks][G] (blocks = ceil(count / rows_per_block)) becomes each block's first position within
-// every group, d_total[g] the eligible rows (not set in d_mask, which may be null) that carry d_table[g] (sorted
-// distinct labels, G <= kLabelGroupsPerPass).  d_labels == null: every row carries label 0.
+// Pass 1: d_cnt[b * cnt_ld + g] (b < ceil(count / rows_per_block)) = the eligible rows (not set in d_mask, which may be
+// null) of block b that carry d_table[g] (sorted distinct labels, g < G <= kLabelGroupsPerPass).  d_labels == null:
+// every row carries label 0.  launch_group_prefix over the whole matrix follows.
 void launch_label_group_count(const uint32_t* d_labels, const uint32_t* d_mask, uint64_t count, uint32_t rows_per_block,
-                              const uint32_t* d_table, uint32_t G, uint32_t* d_cnt, uint32_t* d_total, hipStream_t s);
-// Pass 2: group g's rows, ascending, into d_lists[d_seg_off[g] ...] (kNoSegment: the group gets no list).
+                              const uint32_t* d_table, uint32_t G, uint32_t* d_cnt, uint32_t cnt_ld, hipStream_t s);
+// Pass 2, over the prefixed counts: group g's rows, ascending, into d_lists[d_seg_off[g] ...] (kNoSegment: the group
+// gets no list).  A sub-range of the pass's table (and d_cnt + its first group) is a table too: it is still sorted.
 void launch_label_group_scatter(const uint32_t* d_labels, const uint32_t* d_mask, uint64_t count, uint32_t rows_per_block,
-                                const uint32_t* d_table, uint32_t G, uint32_t* d_cnt, const uint32_t* d_seg_off, uint32_t* d_lists,
-                                hipStream_t s);
+                                const uint32_t* d_table, uint32_t G, const uint32_t* d_cnt, uint32_t cnt_ld, const uint32_t* d_seg_off,
+                                uint32_t* d_lists, hipStream_t s);
 // d_out [n_words]: bit r set = row r is set in d_mask (may be null), carries another label than `label`, or r >= count.
 void launch_label_group_mask(const uint32_t* d_labels, const uint32_t* d_mask, uint64_t count, uint64_t n_words, uint32_t label,
                              uint32_t* d_out, hipStream_t s);
@@ -273,37 +274,29 @@ void launch_gather_rows(const float* d_src, const uint32_t* d_idx, uint32_t n, u
 // The prefix pass on its own: d_cnt [n_blocks][G] -> exclusive prefix over the blocks per group, d_total[g] = the sum.
 void launch_group_prefix(uint32_t* d_cnt, uint32_t n_blocks, uint32_t G, uint32_t* d_total, hipStream_t s);
 
-// ---- kernels_tag.hip : rows grouped by the tag predicates of a batch, one predicate's dense-scan mask
+// ---- kernels_pred.hip : rows grouped by the predicates of a batch over their side columns, one predicate's dense-scan mask
+// The columns a kind of row carries and the predicate over them.  A null column: every row carries 0, at no load.
+struct TagRows { using Pred = TagPred; const uint64_t* tags; };                                          // G <= kTagGroupsPerPass
+struct WhereRows { using Pred = WherePred; const uint64_t* tags; const int64_t* vals; };                 // G <= kWhereGroupsPerPass
+struct RowPredRows { using Pred = RowPred; const uint64_t* tags; const int64_t* vals; const uint32_t* labels; };   // G <= kRowPredsPerPass
 // Pass 1: d_cnt[b * cnt_ld + g] (b < ceil(count / rows_per_block)) = the eligible rows (not set in d_mask, which may be
-// null) of block b whose tags match d_table[g], g < G <= kTagGroupsPerPass.  A row counts towards every group it
-// matches.  d_tags == null: every row carries 0.  launch_group_prefix over the whole matrix follows.
-void launch_tag_group_count(const uint64_t* d_tags, const uint32_t* d_mask, uint64_t count, uint32_t rows_per_block, const TagPred* d_table,
-                            uint32_t G, uint32_t* d_cnt, uint32_t cnt_ld, hipStream_t s);
+// null) of block b that match d_table[g], g < G.  A row counts towards every group it matches.  launch_group_prefix over
+// the whole matrix follows.  (vrod_index_count_where: RowPredRows, kRowPredRowsPerGroup rows a block, d_mask its scope.)
+template <typename Rows>
+void launch_pred_group_count(Rows rows, const uint32_t* d_mask, uint64_t count, uint32_t rows_per_block, const typename Rows::Pred* d_table,
+                             uint32_t G, uint32_t* d_cnt, uint32_t cnt_ld, hipStream_t s);
 // Pass 2, over the prefixed counts: group g's rows, ascending, into d_lists[d_seg_off[g] ...] (kNoSegment: no list).
-void launch_tag_group_scatter(const uint64_t* d_tags, const uint32_t* d_mask, uint64_t count, uint32_t rows_per_block, const TagPred* d_table,
-                              uint32_t G, const uint32_t* d_cnt, uint32_t cnt_ld, const uint32_t* d_seg_off, uint32_t* d_lists, hipStream_t s);
+template <typename Rows>
+void launch_pred_group_scatter(Rows rows, const uint32_t* d_mask, uint64_t count, uint32_t rows_per_block, const typename Rows::Pred* d_table,
+                               uint32_t G, const uint32_t* d_cnt, uint32_t cnt_ld, const uint32_t* d_seg_off, uint32_t* d_lists, hipStream_t s);
 // d_out [n_words]: bit r set = row r is set in d_mask (may be null), does not match p, or r >= count.
-void launch_tag_group_mask(const uint64_t* d_tags, const uint32_t* d_mask, uint64_t count, uint64_t n_words, const TagPred& p, uint32_t* d_out,
-                           hipStream_t s);
-
-// ---- kernels_where.hip : rows grouped by the tags + value-interval predicates of a batch, one predicate's dense-scan mask
-// The three launches of kernels_tag.hip with a row's value (d_vals, null: every row carries 0) beside its tags and
-// WherePred for TagPred: G <= kWhereGroupsPerPass.
-void launch_where_group_count(const uint64_t* d_tags, const int64_t* d_vals, const uint32_t* d_mask, uint64_t count, uint32_t rows_per_block,
-                              const WherePred* d_table, uint32_t G, uint32_t* d_cnt, uint32_t cnt_ld, hipStream_t s);
-void launch_where_group_scatter(const uint64_t* d_tags, const int64_t* d_vals, const uint32_t* d_mask, uint64_t count, uint32_t rows_per_block,
-                                const WherePred* d_table, uint32_t G, const uint32_t* d_cnt, uint32_t cnt_ld, const uint32_t* d_seg_off,
-                                uint32_t* d_lists, hipStream_t s);
-void launch_where_group_mask(const uint64_t* d_tags, const int64_t* d_vals, const uint32_t* d_mask, uint64_t count, uint64_t n_words,
-                             const WherePred& p, uint32_t* d_out, hipStream_t s);
+template <typename Rows>
+void launch_pred_group_mask(Rows rows, const uint32_t* d_mask, uint64_t count, uint64_t n_words, const typename Rows::Pred& p, uint32_t* d_out,
+                            hipStream_t s);
 
 // ---- kernels_rowpred.hip : a predicate over tags, value and label as an operation on the rows (vrod_index_*_where)
 // Every pass gives work-group b rows [b * kRowPredRowsPerGroup, ...): row_pred_groups(count) groups.  A null column:
 // every row carries 0.  d_scope (may be null): bit set = the row is out of scope.
-// d_cnt[b * cnt_ld + g] = the rows of group b in scope that match d_table[g], g < G <= kRowPredsPerPass;
-// launch_group_prefix over the matrix gives the totals.
-void launch_rowpred_count(const uint64_t* d_tags, const int64_t* d_vals, const uint32_t* d_labels, const uint32_t* d_scope, uint64_t count,
-                          const RowPred* d_table, uint32_t G, uint32_t* d_cnt, uint32_t cnt_ld, hipStream_t s);
 // d_hits [row_pred_hit_words(count)]: bit r set = row r < count is in scope and matches p; d_cnt[b] (may be null) = the
 // bits of group b.
 void launch_rowpred_hits(const uint64_t* d_tags, const int64_t* d_vals, const uint32_t* d_labels, const uint32_t* d_scope, uint64_t count,

@@ -1,9 +1,9 @@
 // where_plan.h -- the host decisions of a search with a tags + value-interval predicate per query (vrod_search_where).
 // Plain arithmetic, no HIP headers (tag_plan.h, label_plan.h): vrod_index.hip enqueues what these functions decide,
 // tests/test_where_plan.py compiles this header as host C++.  where_matches is the one function the kernels share with
-// the host (kernels_where.hip).
+// the host (kernels_pred.hip).
 //
-// The search is the tagged search with a wider predicate: the same grouping (tag_plan.h group_preds), the same scatter
+// The search is the tagged search with a wider predicate: the same grouping (label_plan.h group_preds), the same scatter
 // passes (plan_tag_passes) and the same routing; only the predicate, its order and the groups one pass serves differ.
 #pragma once
 #include <stdint.h>
@@ -22,7 +22,7 @@ VROD_TAG_HD inline bool where_matches(uint64_t t, int64_t v, uint64_t any, uint6
 // An empty interval, or a bit both required and forbidden: no row can match, whatever it carries.
 inline bool where_unsatisfiable(const WherePred& p) { return p.lo > p.hi || (p.all & p.none) != 0; }
 
-// Distinct predicates one pass over the tag and value arrays serves.  kernels_where.hip keeps the predicate table
+// Distinct predicates one pass over the tag and value arrays serves.  kernels_pred.hip keeps the predicate table
 // (40 B) and one counter (4 B) per group in LDS: 1024 groups are 44 KiB, under the 64 KiB a launch gets without asking
 // for more.  (The pass asks for the LDS of the groups it has.)
 constexpr uint32_t kWhereGroupsPerPass = 1024;
