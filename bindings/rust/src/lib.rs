@@ -112,6 +112,19 @@ pub struct vrod_row_pred {
 /// `flags` of the row-predicate operations: only the rows the handle's filter allows are in scope.
 pub const VROD_ROWPRED_ALLOWED: u32 = 1;
 
+/// `flags` bit of `vrod_index_select_ordered`: value descending (ids still ascending among equal values).  Shares the
+/// word with `VROD_ROWPRED_ALLOWED`.
+pub const VROD_ORDER_DESC: u32 = 2;
+/// Rows one `vrod_index_select_ordered` call returns; longer listings page with the cursor.
+pub const VROD_MAX_ORDERED: u32 = 65536;
+/// The keyset cursor of `vrod_index_select_ordered`: the last (value, id) of the page before.  16 bytes, no padding.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct vrod_order_cursor {
+    pub value: i64,
+    pub id: u64,
+}
+
 /// `flags` of the duplicate-row calls: the class key is (label, row bits), so equal rows of two documents stay apart.
 pub const VROD_DUP_WITHIN_LABEL: u32 = 1;
 /// A diagnostic for tests: the row hash is cut to 8 bits; results are identical with and without it.
@@ -354,6 +367,11 @@ extern "C" {
     pub fn vrod_index_delete_where(idx: *mut vrod_index, pred: *const vrod_row_pred, flags: u32, out_deleted: *mut u64) -> c_int;
     pub fn vrod_index_set_filter_where(idx: *mut vrod_index, pred: *const vrod_row_pred, flags: u32) -> c_int;
     pub fn vrod_index_set_tags_where(idx: *mut vrod_index, pred: *const vrod_row_pred, flags: u32, set_bits: u64, clear_bits: u64, out_changed: *mut u64) -> c_int;
+    /// Ordered selection: the first `limit` rows `select_where` lists by (value, id), `VROD_ORDER_DESC` in `flags` for
+    /// value descending, strictly after `after` (null: from the beginning).  `*out_count` = min(limit, `*out_total`);
+    /// `out_total` and `out_values` may be null.  The `_device` form writes the two arrays to device memory.
+    pub fn vrod_index_select_ordered(idx: *mut vrod_index, pred: *const vrod_row_pred, flags: u32, after: *const vrod_order_cursor, limit: u32, out_count: *mut u64, out_total: *mut u64, out_ids: *mut u64, out_values: *mut i64) -> c_int;
+    pub fn vrod_index_select_ordered_device(idx: *mut vrod_index, pred: *const vrod_row_pred, flags: u32, after: *const vrod_order_cursor, limit: u32, out_count: *mut u64, out_total: *mut u64, d_out_ids: *mut u64, d_out_values: *mut i64, stream: *mut c_void) -> c_int;
     /// Duplicate rows: `out_first[i]` = the smallest id among the live rows whose stored bits equal row i's (`map_len` =
     /// `vrod_index_count`, or null and 0 for the stats alone); `delete_duplicates` keeps that smallest id of every class.
     pub fn vrod_index_find_duplicates(idx: *mut vrod_index, flags: u32, out_first: *mut u64, map_len: u64, out_stats: *mut vrod_dup_stats) -> c_int;

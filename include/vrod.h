@@ -566,6 +566,49 @@ int vrod_index_set_filter_where(vrod_index *idx, const vrod_row_pred *pred, uint
 int vrod_index_set_tags_where(vrod_index *idx, const vrod_row_pred *pred, uint32_t flags, uint64_t set_bits,
                               uint64_t clear_bits, uint64_t *out_changed);
 
+/* Ordered selection -- the first `limit` rows by their value, under a row predicate and after a keyset cursor: "the 100
+ * newest rows of tenant L", "the next page", "the 1000 oldest rows to expire", without moving a column to the host.
+ * Exact and deterministic; one device pass per call, nothing is persisted.
+ * Rows considered: exactly the rows vrod_index_select_where(pred, flags & VROD_ROWPRED_ALLOWED) lists -- the live rows
+ * below the count, under VROD_ROWPRED_ALLOWED only those the filter allows, that match pred.  The predicate rules are
+ * those of the row-predicate block above: has_label is 0 or 1, a predicate that can match nothing costs no pass, a
+ * column that was never set reads 0 in every row.
+ * Order: by (value, id) ascending, the value compared as signed; with VROD_ORDER_DESC by value DESCENDING and, among
+ * equal values, id STILL ASCENDING -- the smaller id wins ties everywhere in this library.  Ids are ids as searches
+ * report them, id_offset applied; they are unique, so the order is total and no result depends on scheduling.
+ * Cursor: after == NULL starts from the beginning.  Otherwise only rows STRICTLY after (after->value, after->id) in the
+ * call's order are considered: ascending, v > value || (v == value && id > after->id); descending,
+ * v < value || (v == value && id > after->id).  The cursor need not name a row that exists, is live or matches: a
+ * deleted row, an id below id_offset, an id at or beyond the count and UINT64_MAX are all fine, which keeps pages
+ * stable while rows are deleted, added and compacted between them.  The caller passes the last (value, id) of one
+ * page as the cursor of the next.
+ * Outputs: *out_total (may be NULL) = the considered rows after the cursor, exact: *out_total > *out_count says there
+ * is more.  *out_count (required) = min(limit, total).  out_ids[0 .. *out_count) holds the ids in order, out_values
+ * (may be NULL) their values; entries past the count are not touched.  limit == 0 is the count-only form: both arrays
+ * may be NULL, the call is VROD_OK and *out_total is still exact.  limit > VROD_MAX_ORDERED: VROD_ERR_INVALID_ARG, as
+ * k > VROD_MAX_K in vrod_search; longer listings page with the cursor.  There is no VROD_ERR_CAPACITY: limit is the
+ * capacity.  In the _device form the two arrays are device memory on the handle's device and the two counts host
+ * memory; the stream rule is vrod_index_select_where_device's: the caller's work on `stream` is complete before the
+ * library reads, and the call returns with the arrays in place (they can feed vrod_search_candidates_device,
+ * vrod_index_update_device and vrod_index_ids_to_keys_device without a host trip).
+ * Common rules, as for the row predicates: unknown flag bits (anything outside 1u | 2u), a null pred or out_count, a
+ * null out_ids with limit > 0: VROD_ERR_INVALID_ARG; while a search is pending: VROD_ERR_INVALID_ARG; a multi-device
+ * handle: VROD_ERR_UNSUPPORTED.  Every check comes before the first write: a refused call writes nothing.
+ * vrod_index_last_stats is not touched.  An empty handle gives zeros. */
+#define VROD_ORDER_DESC   2u        /* shares the flags word with VROD_ROWPRED_ALLOWED (1u) */
+#define VROD_MAX_ORDERED  65536u    /* rows one call returns; longer listings page with the cursor */
+typedef struct {
+    int64_t value;
+    uint64_t id;
+} vrod_order_cursor; /* 16 bytes, no padding */
+int vrod_index_select_ordered(vrod_index *idx, const vrod_row_pred *pred, uint32_t flags,
+                              const vrod_order_cursor *after, uint32_t limit, uint64_t *out_count,
+                              uint64_t *out_total, uint64_t *out_ids, int64_t *out_values);
+int vrod_index_select_ordered_device(vrod_index *idx, const vrod_row_pred *pred, uint32_t flags,
+                                     const vrod_order_cursor *after, uint32_t limit, uint64_t *out_count,
+                                     uint64_t *out_total, uint64_t *d_out_ids, int64_t *d_out_values,
+                                     void *stream);
+
 /* Duplicate rows -- the classes of LIVE rows whose stored form is bit-identical, found in one read of the corpus.
  * Two live rows are duplicates when the dim stored elements of their prepared rows -- what vrod_index_get_rows reads
  * back: 16 bits per element on a BF16 handle, 32 on an F32 handle -- have the same bits.  -0.0 and +0.0 differ.  Under

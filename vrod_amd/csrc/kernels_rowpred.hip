@@ -22,11 +22,6 @@
 
 namespace vrod {
 
-// bit r of `scope` set = row r is out of scope (deleted, or not allowed); null: every row below count is in scope
-__device__ __forceinline__ bool row_in_scope(const uint32_t* __restrict__ scope, uint64_t r, uint64_t count) {
-    return r < count && !(scope && ((scope[r >> 5] >> (r & 31u)) & 1u));
-}
-
 // hits: bit r set = row r is in scope and matches p (RETAG: and its tags change under (t & ~clear_bits) | set_bits,
 // which is then what the row carries).  Written for the rows below count rounded up to 64: row_pred_hit_words(count)
 // words.  cnt (may be null): cnt[b] = the bits group b set.

@@ -18,6 +18,10 @@ struct RowPred { uint64_t any, all, none; int64_t lo, hi; uint32_t label, has_la
 VROD_TAG_HD inline bool row_pred_matches(uint64_t t, int64_t v, uint32_t l, const RowPred& p) {
     return where_matches(t, v, p.any, p.all, p.none, p.lo, p.hi) && (!p.has_label || l == p.label);
 }
+// bit r of `scope` set = row r is out of scope (deleted, or not allowed); null: every row below count is in scope
+VROD_TAG_HD inline bool row_in_scope(const uint32_t* scope, uint64_t r, uint64_t count) {
+    return r < count && !(scope && ((scope[r >> 5] >> (r & 31u)) & 1u));
+}
 // An empty interval, or a bit both required and forbidden: no row can match, whatever it carries (every label can occur).
 inline bool row_pred_unsatisfiable(const RowPred& p) { return p.lo > p.hi || (p.all & p.none) != 0; }
 // Identical predicates are counted once: the order of the table one pass serves (has_label is 0 or 1 by then).

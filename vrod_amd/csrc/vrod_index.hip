@@ -372,6 +372,10 @@ struct vrod_index {
     // arrays, the work table, a dense group's mask / raw queries (its results go to the shared lists).  A tagged
     // search, which is synchronous too, uses the same buffers for the same things (its table holds predicates).
     DevBuf lab_tab, lab_cnt, lab_lists, lab_slots, lab_entries, lab_mask, lab_q;
+    // ordered selection (vrod_index_select_ordered): the {key, id} records the sort works on, and the small block
+    // [the select's histograms | its state | the collect pass's per-group counts].  The hit bitmap and the groups' hit
+    // counts are lab_mask and lab_cnt, as for every row-predicate pass.
+    DevBuf ord_rec, ord_ws;
     // grouped search workspaces (vrod_search_grouped): the per-query words [found | valid | the lists' queries] and the
     // dense stage's masks [<= 8][capacity / 32]
     DevBuf grp_small, grp_mask;
@@ -5106,12 +5110,12 @@ static_assert(kRowPredRowsPerGroup % 64 == 0 && kRowTile % 64 == 0, "a hit bitma
 // a null handle or pointer (preds, and every pointer of `needed`), unknown flag bits, has_label beyond 1, a multi-device
 // handle, a pending search.
 static int check_rowpred_args(vrod_index* idx, const char* what, const vrod_row_pred* preds, uint32_t n_preds, uint32_t flags,
-                              std::initializer_list<const void*> needed) {
+                              std::initializer_list<const void*> needed, uint32_t known_flags = VROD_ROWPRED_ALLOWED) {
     if (!idx) return fail(VROD_ERR_INVALID_ARG, "idx is null");
     if (n_preds && !preds) return fail(VROD_ERR_INVALID_ARG, "%s: null predicate", what);
     for (const void* p : needed)
         if (!p) return fail(VROD_ERR_INVALID_ARG, "%s: null argument", what);
-    if (flags & ~(uint32_t)VROD_ROWPRED_ALLOWED) return fail(VROD_ERR_INVALID_ARG, "%s: unknown flag bits 0x%x", what, flags);
+    if (flags & ~known_flags) return fail(VROD_ERR_INVALID_ARG, "%s: unknown flag bits 0x%x", what, flags);
     for (uint32_t i = 0; i < n_preds; ++i)
         if (preds[i].has_label > 1u) return fail(VROD_ERR_INVALID_ARG, "%s: has_label is %u in predicate %u, not 0 or 1", what, preds[i].has_label, i);
     if (idx->composite()) return fail(VROD_ERR_UNSUPPORTED, "%s on a multi-device handle: labels, tags and values are not routed to the shards", what);
@@ -5294,6 +5298,90 @@ int vrod_index_set_tags_where(vrod_index* idx, const vrod_row_pred* pred, uint32
     }
     if (out_changed) *out_changed = changed;
     return VROD_OK;
+}
+
+// ------------------------------------------------------------------ ordered selection (vrod_index_select_ordered)
+// The top `limit` rows by (value, id) among the rows select_where lists, after a keyset cursor (order_plan.h,
+// kernels_order.hip, DESIGN.md "Ordered selection"): a filter pass, a radix select when the rows after the cursor exceed
+// the limit, a collect pass and a sort, all on the handle's stream.  The host waits twice: for the total, which decides
+// whether the select runs and how many records the sort gets, and for the outputs.  Workspaces, the handle being idle:
+// lab_mask the hit bitmap, lab_cnt the groups' hit counts, ord_ws, ord_rec, and out_ids / out_scores for a host form's
+// ids and values.
+static_assert(sizeof(vrod_order_cursor) == 16 && offsetof(vrod_order_cursor, id) == 8, "vrod_order_cursor is two packed 64-bit words");
+static_assert(VROD_MAX_ORDERED == kOrderMaxRows && sizeof(OrderState) == 16, "the header's limit is the sort's; the state is 16 bytes");
+
+// Both forms behind their checks.  d_ids / d_vals: where ids and values go on the device (the caller's memory, or the
+// handle's for the host form, which copies to h_ids / h_vals); d_vals null: no values are wanted.
+static int order_select(vrod_index* idx, const vrod_row_pred* pred, uint32_t flags, const vrod_order_cursor* after, uint32_t limit,
+                        uint64_t* out_count, uint64_t* out_total, uint64_t* d_ids, int64_t* d_vals, uint64_t* h_ids, int64_t* h_vals) {
+    const RowPred p = row_pred_of(*pred);
+    const bool desc = (flags & VROD_ORDER_DESC) != 0;
+    uint32_t total = 0;
+    hipStream_t s = idx->stream;
+    const uint32_t n_groups = row_pred_groups(idx->count);
+    if (idx->count && !row_pred_unsatisfiable(p)) {
+        VROD_TRY(set_device(idx));
+        VROD_TRY(idx->lab_mask.ensure(row_pred_hit_words(idx->count) * 4));
+        VROD_TRY(idx->lab_cnt.ensure(((size_t)n_groups + 1) * 4));
+        uint32_t* d_first = idx->lab_cnt.as<uint32_t>();
+        launch_order_hits(idx->tags.d(), idx->values.d(), idx->labels.d(), rowpred_scope(idx, flags), idx->count, p, desc, after != nullptr,
+                          after ? order_key(after->value, desc) : 0ull, after ? after->id : 0ull, idx->id_offset, idx->lab_mask.as<uint32_t>(),
+                          d_first, s);
+        launch_group_prefix(d_first, n_groups, 1, d_first + n_groups, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&total, d_first + n_groups, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    const uint32_t n = std::min(limit, total);
+    if (n) {
+        const size_t hist_bytes = (size_t)kOrderRounds * kOrderBins * 4;
+        VROD_TRY(idx->ord_ws.ensure(hist_bytes + sizeof(OrderState) + ((size_t)n_groups * 2 + 2) * 4));
+        VROD_TRY(idx->ord_rec.ensure((size_t)order_sort_size(n) * 16));
+        if (!d_ids) {
+            VROD_TRY(idx->out_ids.ensure((size_t)n * 8));
+            d_ids = idx->out_ids.as<uint64_t>();
+            if (h_vals) {
+                VROD_TRY(idx->out_scores.ensure((size_t)n * 8));
+                d_vals = idx->out_scores.as<int64_t>();
+            }
+        }
+        uint32_t* d_hist = idx->ord_ws.as<uint32_t>();
+        OrderState* d_state = (OrderState*)((char*)idx->ord_ws.p + hist_bytes);
+        uint32_t* d_cnt2 = (uint32_t*)(d_state + 1);
+        const uint32_t* d_hits = idx->lab_mask.as<uint32_t>();
+        const bool take_all = total <= limit;
+        if (!take_all) launch_order_select(d_hits, idx->values.d(), idx->count, desc, limit, d_hist, d_state, s);
+        launch_order_collect(d_hits, idx->values.d(), idx->count, desc, idx->id_offset, take_all, d_state, d_cnt2, idx->lab_cnt.as<uint32_t>(),
+                             idx->ord_rec.as<uint64_t>(), n, s);
+        launch_order_sort(idx->ord_rec.as<uint64_t>(), n, desc, d_ids, d_vals, s);
+        HIP_TRY(hipGetLastError());
+        if (h_ids) HIP_TRY(hipMemcpyAsync(h_ids, d_ids, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+        if (h_vals) HIP_TRY(hipMemcpyAsync(h_vals, d_vals, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    *out_count = n;
+    if (out_total) *out_total = total;
+    return VROD_OK;
+}
+
+static int check_order_args(vrod_index* idx, const char* what, const vrod_row_pred* pred, uint32_t flags, uint32_t limit,
+                            const uint64_t* out_count, const uint64_t* out_ids) {
+    if (idx && limit > VROD_MAX_ORDERED) return fail(VROD_ERR_INVALID_ARG, "%s: limit must be in 0..%u", what, VROD_MAX_ORDERED);
+    return check_rowpred_args(idx, what, pred, 1, flags, {pred, out_count, limit ? (const void*)out_ids : (const void*)pred},
+                              VROD_ROWPRED_ALLOWED | VROD_ORDER_DESC);
+}
+
+int vrod_index_select_ordered(vrod_index* idx, const vrod_row_pred* pred, uint32_t flags, const vrod_order_cursor* after, uint32_t limit,
+                              uint64_t* out_count, uint64_t* out_total, uint64_t* out_ids, int64_t* out_values) {
+    VROD_TRY(check_order_args(idx, "vrod_index_select_ordered", pred, flags, limit, out_count, out_ids));
+    return order_select(idx, pred, flags, after, limit, out_count, out_total, nullptr, nullptr, out_ids, out_values);
+}
+
+int vrod_index_select_ordered_device(vrod_index* idx, const vrod_row_pred* pred, uint32_t flags, const vrod_order_cursor* after, uint32_t limit,
+                                     uint64_t* out_count, uint64_t* out_total, uint64_t* d_out_ids, int64_t* d_out_values, void* stream) {
+    VROD_TRY(check_order_args(idx, "vrod_index_select_ordered_device", pred, flags, limit, out_count, d_out_ids));
+    VROD_TRY(begin_sync_device(idx, "vrod_index_select_ordered_device", stream));
+    return order_select(idx, pred, flags, after, limit, out_count, out_total, d_out_ids, d_out_values, nullptr, nullptr);
 }
 
 // ------------------------------------------------------------------ duplicate rows (vrod_index_find_duplicates, _delete_duplicates)

@@ -9,6 +9,7 @@
 #include "tag_plan.h"      // TagPred
 #include "where_plan.h"    // WherePred
 #include "rowpred_plan.h"  // RowPred
+#include "order_plan.h"    // OrderState
 #include "multivec_plan.h" // MultivecQuery
 #include "combine_plan.h"  // kCombineMaxExclude, combine_lanes_per_query
 #include "candidates_plan.h" // kCandMaxList, the sort classes, cand_tile_query
@@ -307,6 +308,25 @@ void launch_rowpred_retag(uint64_t* d_tags, const int64_t* d_vals, const uint32_
 // d_out[d_first[b] + j] = id_offset + the row of the j-th bit set in group b's words of d_hits (d_first: the prefixed
 // counts): the selection in ascending order.
 void launch_rowpred_scatter(const uint32_t* d_hits, uint64_t count, const uint32_t* d_first, uint64_t id_offset, uint64_t* d_out, hipStream_t s);
+
+// ---- kernels_order.hip : the top rows by (value, id) under a row predicate and after a cursor (vrod_index_select_ordered)
+// The geometry, columns and scope of kernels_rowpred.hip; keys, cursor test and state as order_plan.h defines them.
+// d_hits / d_cnt as launch_rowpred_hits, a hit also lying strictly after (ckey, cid) when has_cursor; d_cnt is not null.
+void launch_order_hits(const uint64_t* d_tags, const int64_t* d_vals, const uint32_t* d_labels, const uint32_t* d_scope, uint64_t count,
+                       const RowPred& p, bool desc, bool has_cursor, uint64_t ckey, uint64_t cid, uint64_t id_offset, uint32_t* d_hits,
+                       uint32_t* d_cnt, hipStream_t s);
+// The key of rank `limit` (1 <= limit <= the hit rows) among the hit rows, into *d_state: its pivot, and in `remaining`
+// how many rows of the pivot's tie class the limit still takes.  d_hist [kOrderRounds][kOrderBins] is scratch.
+void launch_order_select(const uint32_t* d_hits, const int64_t* d_vals, uint64_t count, bool desc, uint32_t limit, uint32_t* d_hist,
+                         OrderState* d_state, hipStream_t s);
+// The n_rec {key, id} records of the rows a call takes, in no particular order, into d_rec.  take_all: every hit row, group b
+// from position d_first[b] (the prefixed counts of launch_order_hits).  Otherwise what *d_state says: d_cnt2
+// [2 * groups + 2] is scratch.
+void launch_order_collect(const uint32_t* d_hits, const int64_t* d_vals, uint64_t count, bool desc, uint64_t id_offset, bool take_all,
+                          const OrderState* d_state, uint32_t* d_cnt2, const uint32_t* d_first, uint64_t* d_rec, uint32_t n_rec, hipStream_t s);
+// d_rec (order_sort_size(n) records of room, the first n filled) sorted by (key, id); then d_out_ids[i] and d_out_vals[i]
+// (may be null) = the id and the value of record i < n.
+void launch_order_sort(uint64_t* d_rec, uint32_t n, bool desc, uint64_t* d_out_ids, int64_t* d_out_vals, hipStream_t s);
 
 // ---- kernels_dup.hip : the classes of live rows with the same stored bits (vrod_index_find_duplicates, _delete_duplicates)
 // The table of one call (dup_plan.h): slot_row / slot_min [slots], all-ones before the class pass; row_slot [count].

@@ -33,6 +33,10 @@ WHERE_DTYPE = np.dtype([("any", np.uint64), ("all", np.uint64), ("none", np.uint
 ROWPRED_DTYPE = np.dtype([("any", np.uint64), ("all", np.uint64), ("none", np.uint64), ("lo", np.int64), ("hi", np.int64),
                           ("label", np.uint32), ("has_label", np.uint32)])
 ROWPRED_ALLOWED = 1   # VROD_ROWPRED_ALLOWED: only the rows the filter allows are in scope
+ORDER_DESC = 2        # VROD_ORDER_DESC: value descending (ids still ascending among equal values)
+MAX_ORDERED = 65536   # VROD_MAX_ORDERED: rows one select_ordered call returns
+# vrod_order_cursor: the (value, id) a page ended with, 16 bytes
+ORDER_CURSOR_DTYPE = np.dtype([("value", np.int64), ("id", np.uint64)])
 DUP_WITHIN_LABEL = 1            # VROD_DUP_WITHIN_LABEL: the class key is (label, row bits)
 DUP_NARROW_HASH = 0x80000000    # VROD_DUP_NARROW_HASH: a diagnostic, the row hash cut to 8 bits
 ROWFIND_NARROW_HASH = 0x80000000   # VROD_ROWFIND_NARROW_HASH: a diagnostic, the row hash cut to 8 bits
@@ -615,6 +619,88 @@ class Index:
         out = C.c_uint64()
         check(self._L.vrod_index_set_tags_where(self._h, _ptr(p), flags, bits[0], bits[1], C.byref(out)))
         return out.value
+
+    # -- ordered selection
+    @classmethod
+    def _order_args(cls, limit, desc, after, allowed_only):
+        """The checked arguments of select_ordered -> (limit, flags, cursor): cursor is None or a [1] array of
+        ORDER_CURSOR_DTYPE."""
+        if not isinstance(desc, (bool, np.bool_)):
+            raise TypeError(f"desc must be a bool, got {type(desc).__name__}")
+        flags = cls._rowpred_flags(allowed_only) | (ORDER_DESC if desc else 0)
+        if not isinstance(limit, (int, np.integer)) or isinstance(limit, (bool, np.bool_)):
+            raise TypeError(f"limit must be an int, got {type(limit).__name__}")
+        if not 0 <= int(limit) <= MAX_ORDERED:
+            raise ValueError(f"limit must be in 0..{MAX_ORDERED}, got {limit}")
+        cur = None
+        if after is not None:
+            if isinstance(after, np.void):   # one element of an ORDER_CURSOR_DTYPE array
+                after = after.tolist()
+            if not isinstance(after, (tuple, list)) or len(after) != 2:
+                raise TypeError("after must be a (value, id) pair")
+            for x in after:
+                if not isinstance(x, (int, np.integer)) or isinstance(x, (bool, np.bool_)):
+                    raise TypeError("after must hold two integers")
+            v, i = int(after[0]), int(after[1])
+            if not -(1 << 63) <= v < (1 << 63):
+                raise ValueError("after: the value does not fit 64 signed bits")
+            if not 0 <= i < (1 << 64):
+                raise ValueError("after: the id does not fit 64 unsigned bits")
+            cur = np.zeros(1, ORDER_CURSOR_DTYPE)
+            cur["value"], cur["id"] = v, i
+        return int(limit), flags, cur
+
+    def select_ordered(self, pred, limit: int, desc: bool = False, after=None, allowed_only: bool = False):
+        """The first `limit` rows in scope matching one predicate by (value, id) ascending -- desc: value descending, ids
+        still ascending among equal values -- strictly after the cursor `after`, a (value, id) pair that need not name a
+        row (vrod_index_select_ordered) -> (ids uint64 [n], values int64 [n], total): n = min(limit, total), total = the
+        rows after the cursor.  limit=0 only counts."""
+        p = self._row_preds(pred, 1)
+        limit, flags, cur = self._order_args(limit, desc, after, allowed_only)
+        ids, vals = np.empty(max(limit, 1), np.uint64), np.empty(max(limit, 1), np.int64)
+        n, total = C.c_uint64(), C.c_uint64()
+        check(self._L.vrod_index_select_ordered(self._h, _ptr(p), flags, _ptr(cur), limit, C.byref(n), C.byref(total),
+                                                _ptr(ids) if limit else None, _ptr(vals) if limit else None))
+        return ids[:n.value], vals[:n.value], total.value
+
+    def select_ordered_device(self, pred, limit: int, desc: bool = False, after=None, allowed_only: bool = False, out_ids=None,
+                              out_values=None):
+        """select_ordered into CUDA int64 tensors [limit] (the ids are the bits of uint64) -> (count, total, ids, values);
+        ids[:count] and values[:count] are filled (vrod_index_select_ordered_device).  The ids can feed
+        search_candidates_device, update_device and ids_to_keys_device without a host trip."""
+        import torch
+        p = self._row_preds(pred, 1)
+        limit, flags, cur = self._order_args(limit, desc, after, allowed_only)
+        dev = torch.device("cuda", self.device)
+        out_ids = _device_out(out_ids, max(limit, 1), torch.int64, dev)
+        out_values = _device_out(out_values, max(limit, 1), torch.int64, dev)
+        for t, name in ((out_ids, "out_ids"), (out_values, "out_values")):
+            if self._device_u64(t, name)[0] < limit:
+                raise ValueError(f"{name} must hold {limit} entries")
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        n, total = C.c_uint64(), C.c_uint64()
+        check(self._L.vrod_index_select_ordered_device(self._h, _ptr(p), flags, _ptr(cur), limit, C.byref(n), C.byref(total),
+                                                       out_ids.data_ptr() if limit else None, out_values.data_ptr() if limit else None, stream))
+        return n.value, total.value, out_ids, out_values
+
+    def scroll(self, pred, page: int, desc: bool = False, allowed_only: bool = False):
+        """A generator of select_ordered pages of up to `page` rows, (ids, values) each, the last (value, id) of one page
+        being the cursor of the next: the whole listing in order.  Rows may be added, deleted and compacted between pages;
+        every page is exact for the handle's state when it is fetched."""
+        if not isinstance(page, (int, np.integer)) or isinstance(page, (bool, np.bool_)):
+            raise TypeError(f"page must be an int, got {type(page).__name__}")
+        if not 1 <= int(page) <= MAX_ORDERED:
+            raise ValueError(f"page must be in 1..{MAX_ORDERED}, got {page}")
+        self._row_preds(pred, 1)
+        self._order_args(int(page), desc, None, allowed_only)
+        after = None
+        while True:
+            ids, vals, total = self.select_ordered(pred, int(page), desc=desc, after=after, allowed_only=allowed_only)
+            if ids.size:
+                yield ids, vals
+            if total <= ids.size:
+                return
+            after = (int(vals[-1]), int(ids[-1]))
 
     # -- duplicate rows
     @staticmethod
