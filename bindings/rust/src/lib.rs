@@ -125,6 +125,30 @@ pub struct vrod_order_cursor {
     pub id: u64,
 }
 
+/// `by` of `vrod_index_aggregate_where`: the key of a group is the row's label (0 .. 2^32-1).
+pub const VROD_AGG_BY_LABEL: u32 = 0;
+/// ... floor(value / width): floor division on signed values, width >= 1.
+pub const VROD_AGG_BY_VALUE: u32 = 1;
+/// ... a bit index 0..63: a row counts in the group of EVERY tag bit it has set.
+pub const VROD_AGG_BY_TAG: u32 = 2;
+/// `flags` bit of `vrod_index_aggregate_where`: groups by count descending, then key ascending.  Shares the word with
+/// `VROD_ROWPRED_ALLOWED`; 2 stays `VROD_ORDER_DESC`'s and is refused there.
+pub const VROD_AGG_ORDER_COUNT: u32 = 4;
+/// Distinct groups one `vrod_index_aggregate_where` call holds; more is `VROD_ERR_CAPACITY`.
+pub const VROD_MAX_AGG_GROUPS: u32 = 1048576;
+/// One group of `vrod_index_aggregate_where`: its key, its rows, the min, max and wrapping sum of their values and the
+/// smallest id among them (id_offset applied).  48 bytes, no padding.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct vrod_agg_group {
+    pub key: i64,
+    pub count: u64,
+    pub min_value: i64,
+    pub max_value: i64,
+    pub sum_value: i64,
+    pub first_id: u64,
+}
+
 /// `flags` of the duplicate-row calls: the class key is (label, row bits), so equal rows of two documents stay apart.
 pub const VROD_DUP_WITHIN_LABEL: u32 = 1;
 /// A diagnostic for tests: the row hash is cut to 8 bits; results are identical with and without it.
@@ -372,6 +396,10 @@ extern "C" {
     /// `out_total` and `out_values` may be null.  The `_device` form writes the two arrays to device memory.
     pub fn vrod_index_select_ordered(idx: *mut vrod_index, pred: *const vrod_row_pred, flags: u32, after: *const vrod_order_cursor, limit: u32, out_count: *mut u64, out_total: *mut u64, out_ids: *mut u64, out_values: *mut i64) -> c_int;
     pub fn vrod_index_select_ordered_device(idx: *mut vrod_index, pred: *const vrod_row_pred, flags: u32, after: *const vrod_order_cursor, limit: u32, out_count: *mut u64, out_total: *mut u64, d_out_ids: *mut u64, d_out_values: *mut i64, stream: *mut c_void) -> c_int;
+    /// Row aggregation, the GROUP BY of the row predicates: the rows `select_where` lists grouped by label, value bucket
+    /// or tag bit (`by`), per group the count, min / max / wrapping sum of the values and the smallest id; `out` holds the
+    /// first `min(limit, groups)` groups by key, or with `VROD_AGG_ORDER_COUNT` by count descending.
+    pub fn vrod_index_aggregate_where(idx: *mut vrod_index, pred: *const vrod_row_pred, flags: u32, by: u32, width: i64, limit: u32, out_count: *mut u64, out_groups: *mut u64, out_rows: *mut u64, out: *mut vrod_agg_group) -> c_int;
     /// Duplicate rows: `out_first[i]` = the smallest id among the live rows whose stored bits equal row i's (`map_len` =
     /// `vrod_index_count`, or null and 0 for the stats alone); `delete_duplicates` keeps that smallest id of every class.
     pub fn vrod_index_find_duplicates(idx: *mut vrod_index, flags: u32, out_first: *mut u64, map_len: u64, out_stats: *mut vrod_dup_stats) -> c_int;

@@ -609,6 +609,53 @@ int vrod_index_select_ordered_device(vrod_index *idx, const vrod_row_pred *pred,
                                      uint64_t *out_total, uint64_t *d_out_ids, int64_t *d_out_values,
                                      void *stream);
 
+/* Row aggregation -- the GROUP BY of the row predicates: the rows a predicate matches, grouped by label, by value
+ * bucket or by tag bit, with each group's row count, the min, max and sum of its values and its smallest id: "how many
+ * chunks does each tenant hold", "rows per day about to expire", "rows per access group", "the oldest and newest row of
+ * every document", without moving a column to the host.  Exact and deterministic; nothing is persisted.
+ * Rows considered: exactly the rows vrod_index_select_where(pred, flags & VROD_ROWPRED_ALLOWED) lists, under the
+ * predicate rules of the row-predicate block above: has_label is 0 or 1, a column that was never set reads 0 in every
+ * row, a predicate that can match nothing costs no pass and gives zero groups.
+ * Key (`by`):
+ *   VROD_AGG_BY_LABEL  the row's label, 0 .. 2^32-1.  A handle that never set labels is one group with key 0.
+ *   VROD_AGG_BY_VALUE  floor(value / width): FLOOR division on signed values (-1 / 10 gives -1), width >= 1 (anything
+ *                      else: VROD_ERR_INVALID_ARG; width is read in this mode only).  Every result fits; with width 1
+ *                      every int64 is a possible key, INT64_MIN, -1, 0 and INT64_MAX included.
+ *   VROD_AGG_BY_TAG    a bit index 0 .. 63: a row counts -- with its value and its id -- in the group of EVERY tag bit it
+ *                      has set, so there are at most 64 groups and the counts sum to the popcounts.  A row with tags 0
+ *                      is in no group but is counted in *out_rows.
+ * Aggregates per group: count; min_value and max_value compared as signed; sum_value the two's-complement sum, wrapping
+ * mod 2^64; first_id the smallest id of the group, id_offset applied.  All five are commutative integer operations: no
+ * result depends on scheduling, and repeated calls give identical bytes.
+ * Outputs: *out_rows (may be NULL) = the rows considered, equal to vrod_index_count_where of the same predicate in all
+ * three modes.  *out_groups (may be NULL) = the exact number of distinct groups.  *out_count (required) =
+ * min(limit, groups).  out[0 .. *out_count) holds the first groups in the call's order; entries past the count are not
+ * touched.  limit == 0 is the count-only form: out may be NULL.
+ * Order: key ascending, compared as signed; with VROD_AGG_ORDER_COUNT count descending, then key ascending.  Keys are
+ * unique within a result, so both orders are total.
+ * More than VROD_MAX_AGG_GROUPS distinct groups: VROD_ERR_CAPACITY, and no output is written.
+ * Common rules, as for the row predicates: unknown flag bits (anything outside 1u | 4u; 2u is VROD_ORDER_DESC's and
+ * is refused here), by > 2, a null pred or out_count, a null out with limit > 0: VROD_ERR_INVALID_ARG; while a search
+ * is pending: VROD_ERR_INVALID_ARG; a multi-device handle: VROD_ERR_UNSUPPORTED.  Every check comes before the first
+ * write: a refused call writes nothing.  vrod_index_last_stats is not touched, the handle's state does not change, an
+ * empty handle gives zeros.  The columns are read on the device and never cross to the host: only the groups do, which
+ * the host then orders. */
+#define VROD_AGG_BY_LABEL 0u       /* key = the row's label (0 .. 2^32-1) */
+#define VROD_AGG_BY_VALUE 1u       /* key = floor(value / width), floor division on signed values, width >= 1 */
+#define VROD_AGG_BY_TAG   2u       /* key = bit index 0..63; a row counts in the group of EVERY tag bit it has set */
+#define VROD_AGG_ORDER_COUNT 4u    /* flags word shared with VROD_ROWPRED_ALLOWED (1u); 2u stays VROD_ORDER_DESC's and is refused here */
+#define VROD_MAX_AGG_GROUPS 1048576u
+typedef struct {
+    int64_t  key;
+    uint64_t count;       /* rows of the group */
+    int64_t  min_value, max_value;
+    int64_t  sum_value;   /* two's-complement sum, wrapping mod 2^64 */
+    uint64_t first_id;    /* smallest id of the group, id_offset applied */
+} vrod_agg_group; /* 48 bytes, no padding */
+int vrod_index_aggregate_where(vrod_index *idx, const vrod_row_pred *pred, uint32_t flags, uint32_t by, int64_t width,
+                               uint32_t limit, uint64_t *out_count, uint64_t *out_groups, uint64_t *out_rows,
+                               vrod_agg_group *out);
+
 /* Duplicate rows -- the classes of LIVE rows whose stored form is bit-identical, found in one read of the corpus.
  * Two live rows are duplicates when the dim stored elements of their prepared rows -- what vrod_index_get_rows reads
  * back: 16 bits per element on a BF16 handle, 32 on an F32 handle -- have the same bits.  -0.0 and +0.0 differ.  Under

@@ -376,6 +376,9 @@ struct vrod_index {
     // [the select's histograms | its state | the collect pass's per-group counts].  The hit bitmap and the groups' hit
     // counts are lab_mask and lab_cnt, as for every row-predicate pass.
     DevBuf ord_rec, ord_ws;
+    // row aggregation (vrod_index_aggregate_where): the global hash table with its counters in front (aggregate_plan.h
+    // agg_table_view; at most 2^21 + 1 slots of 48 bytes), and the occupied slots as dense records for the host to order.
+    DevBuf agg_tab, agg_out;
     // grouped search workspaces (vrod_search_grouped): the per-query words [found | valid | the lists' queries] and the
     // dense stage's masks [<= 8][capacity / 32]
     DevBuf grp_small, grp_mask;
@@ -5382,6 +5385,74 @@ int vrod_index_select_ordered_device(vrod_index* idx, const vrod_row_pred* pred,
     VROD_TRY(check_order_args(idx, "vrod_index_select_ordered_device", pred, flags, limit, out_count, d_out_ids));
     VROD_TRY(begin_sync_device(idx, "vrod_index_select_ordered_device", stream));
     return order_select(idx, pred, flags, after, limit, out_count, out_total, d_out_ids, d_out_values, nullptr, nullptr);
+}
+
+// ------------------------------------------------------------------ row aggregation (vrod_index_aggregate_where)
+// Count, min / max / sum of the value and the smallest id of every group among the rows select_where lists, the groups
+// being labels, value buckets or tag bits (aggregate_plan.h, kernels_aggregate.hip, DESIGN.md "Row aggregation"): a
+// reset of the table, the aggregation pass and a compaction of the occupied slots, all on the handle's stream.  The host
+// waits twice: for the counters, which say whether the call failed and how many records to make room for, and for the
+// records.  Only the groups cross to the host, where they are ordered: at most 48 MiB, and a sort of records the caller
+// is about to read anyway.  Workspaces, the handle being idle: agg_tab and agg_out.
+static_assert(sizeof(vrod_agg_group) == 48 && sizeof(AggGroup) == 48 && offsetof(vrod_agg_group, count) == 8 &&
+                  offsetof(vrod_agg_group, sum_value) == 32 && offsetof(vrod_agg_group, first_id) == 40 && offsetof(AggGroup, first_id) == 40,
+              "vrod_agg_group is six packed 64-bit words");
+static_assert(VROD_MAX_AGG_GROUPS == kAggMaxGroups && VROD_AGG_BY_LABEL == kAggByLabel && VROD_AGG_BY_VALUE == kAggByValue &&
+                  VROD_AGG_BY_TAG == kAggByTag && VROD_AGG_ORDER_COUNT == kAggOrderCount,
+              "the header's constants are the plan's");
+
+int vrod_index_aggregate_where(vrod_index* idx, const vrod_row_pred* pred, uint32_t flags, uint32_t by, int64_t width, uint32_t limit,
+                               uint64_t* out_count, uint64_t* out_groups, uint64_t* out_rows, vrod_agg_group* out) {
+    const char* what = "vrod_index_aggregate_where";
+    if (idx && by > VROD_AGG_BY_TAG) return fail(VROD_ERR_INVALID_ARG, "%s: by is %u, not 0, 1 or 2", what, by);
+    if (idx && by == VROD_AGG_BY_VALUE && width < 1) return fail(VROD_ERR_INVALID_ARG, "%s: width must be at least 1", what);
+    VROD_TRY(check_rowpred_args(idx, what, pred, 1, flags, {pred, out_count, limit ? (const void*)out : (const void*)pred},
+                                VROD_ROWPRED_ALLOWED | VROD_AGG_ORDER_COUNT));
+    const RowPred p = row_pred_of(*pred);
+    AggCounters ctr{};
+    std::vector<AggGroup> groups;
+    if (idx->count && !row_pred_unsatisfiable(p)) {
+        VROD_TRY(set_device(idx));
+        hipStream_t s = idx->stream;
+        const bool direct = by == VROD_AGG_BY_TAG;
+        const uint64_t slots = direct ? kAggTagGroups : agg_table_slots(idx->count);
+        VROD_TRY(idx->agg_tab.ensure(agg_table_bytes(slots)));
+        const AggTable tab = agg_table_view(idx->agg_tab.p, slots);
+        // the columns the predicate and the mode read; the value is always aggregated
+        const bool need_tags = direct || p.any || p.all || p.none, need_labels = by == VROD_AGG_BY_LABEL || p.has_label;
+        launch_agg_reset(tab, direct, s);
+        launch_agg_pass(by, need_tags ? idx->tags.d() : nullptr, idx->values.d(), need_labels ? idx->labels.d() : nullptr,
+                        rowpred_scope(idx, flags), idx->count, p, by == VROD_AGG_BY_VALUE ? width : 1, idx->id_offset, tab, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&ctr, tab.ctr, sizeof ctr, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (ctr.err & kAggErrGroups)
+            return fail(VROD_ERR_CAPACITY, "%s: more than %u distinct groups", what, VROD_MAX_AGG_GROUPS);
+        if (ctr.err) return fail(VROD_ERR_INTERNAL, "%s: the group table overflowed (%llu slots)", what, (unsigned long long)slots);
+        // every claimed slot and the marker key's own may hold a group
+        const uint64_t room = limit ? (direct ? kAggTagGroups : ctr.claimed + 1) : 0;
+        if (room) VROD_TRY(idx->agg_out.ensure((size_t)room * sizeof(AggGroup)));
+        launch_agg_compact(tab, room ? idx->agg_out.as<AggGroup>() : nullptr, room, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&ctr.n_out, &tab.ctr->n_out, 8, hipMemcpyDeviceToHost, s));
+        groups.resize(room);   // at most one record more than there are groups
+        if (room) HIP_TRY(hipMemcpyAsync(groups.data(), idx->agg_out.p, (size_t)room * sizeof(AggGroup), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (ctr.n_out > VROD_MAX_AGG_GROUPS)   // exactly the cap in hashed slots, and the marker key's group beside them
+            return fail(VROD_ERR_CAPACITY, "%s: more than %u distinct groups", what, VROD_MAX_AGG_GROUPS);
+        if (room) {
+            if (ctr.n_out > room) return fail(VROD_ERR_INTERNAL, "%s: %llu groups, room for %llu", what, (unsigned long long)ctr.n_out, (unsigned long long)room);
+            groups.resize(ctr.n_out);
+            if (flags & VROD_AGG_ORDER_COUNT) std::sort(groups.begin(), groups.end(), agg_before_count);
+            else std::sort(groups.begin(), groups.end(), agg_before_key);
+        }
+    }
+    const uint64_t n = std::min<uint64_t>(limit, ctr.n_out);
+    if (n) memcpy(out, groups.data(), (size_t)n * sizeof(AggGroup));
+    *out_count = n;
+    if (out_groups) *out_groups = ctr.n_out;
+    if (out_rows) *out_rows = ctr.rows;
+    return VROD_OK;
 }
 
 // ------------------------------------------------------------------ duplicate rows (vrod_index_find_duplicates, _delete_duplicates)

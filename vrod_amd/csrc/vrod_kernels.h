@@ -10,6 +10,7 @@
 #include "where_plan.h"    // WherePred
 #include "rowpred_plan.h"  // RowPred
 #include "order_plan.h"    // OrderState
+#include "aggregate_plan.h" // AggTable, AggGroup
 #include "multivec_plan.h" // MultivecQuery
 #include "combine_plan.h"  // kCombineMaxExclude, combine_lanes_per_query
 #include "candidates_plan.h" // kCandMaxList, the sort classes, cand_tile_query
@@ -327,6 +328,18 @@ void launch_order_collect(const uint32_t* d_hits, const int64_t* d_vals, uint64_
 // d_rec (order_sort_size(n) records of room, the first n filled) sorted by (key, id); then d_out_ids[i] and d_out_vals[i]
 // (may be null) = the id and the value of record i < n.
 void launch_order_sort(uint64_t* d_rec, uint32_t n, bool desc, uint64_t* d_out_ids, int64_t* d_out_vals, hipStream_t s);
+
+// ---- kernels_aggregate.hip : count, min / max / sum of the value and the smallest id per group (vrod_index_aggregate_where)
+// The geometry, columns and scope of kernels_rowpred.hip; keys, tables and counters as aggregate_plan.h defines them.
+// Every slot of g (slots + 1 of them) to the aggregates' identities and the counters to zero; direct (BY_TAG): slot i
+// holds key i, otherwise every key word is empty.  Enqueued before the pass: no claimer initialises a slot.
+void launch_agg_reset(const AggTable& g, bool direct, hipStream_t s);
+// The rows in scope (d_scope as launch_rowpred_hits) that match p, aggregated into g by the key of mode `by`
+// (kAggBy*; width: BY_VALUE's bucket); g.ctr->rows += their number.  A null column reads 0: pass only what p and `by` need.
+void launch_agg_pass(uint32_t by, const uint64_t* d_tags, const int64_t* d_vals, const uint32_t* d_labels, const uint32_t* d_scope,
+                     uint64_t count, const RowPred& p, int64_t width, uint64_t id_offset, const AggTable& g, hipStream_t s);
+// The occupied slots of g as records d_out[0 .. min(n, cap)) in no particular order, g.ctr->n_out = n.  d_out null: n only.
+void launch_agg_compact(const AggTable& g, AggGroup* d_out, uint64_t cap, hipStream_t s);
 
 // ---- kernels_dup.hip : the classes of live rows with the same stored bits (vrod_index_find_duplicates, _delete_duplicates)
 // The table of one call (dup_plan.h): slot_row / slot_min [slots], all-ones before the class pass; row_slot [count].

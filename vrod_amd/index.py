@@ -37,6 +37,12 @@ ORDER_DESC = 2        # VROD_ORDER_DESC: value descending (ids still ascending a
 MAX_ORDERED = 65536   # VROD_MAX_ORDERED: rows one select_ordered call returns
 # vrod_order_cursor: the (value, id) a page ended with, 16 bytes
 ORDER_CURSOR_DTYPE = np.dtype([("value", np.int64), ("id", np.uint64)])
+AGG_BY_LABEL, AGG_BY_VALUE, AGG_BY_TAG = 0, 1, 2   # VROD_AGG_BY_*: the key of aggregate_where's groups
+AGG_ORDER_COUNT = 4        # VROD_AGG_ORDER_COUNT: groups by count descending, then key (the flags word of ROWPRED_ALLOWED)
+MAX_AGG_GROUPS = 1048576   # VROD_MAX_AGG_GROUPS: distinct groups one aggregate_where call holds
+# vrod_agg_group: one group of aggregate_where, 48 bytes
+AGG_GROUP_DTYPE = np.dtype([("key", np.int64), ("count", np.uint64), ("min_value", np.int64), ("max_value", np.int64),
+                            ("sum_value", np.int64), ("first_id", np.uint64)])
 DUP_WITHIN_LABEL = 1            # VROD_DUP_WITHIN_LABEL: the class key is (label, row bits)
 DUP_NARROW_HASH = 0x80000000    # VROD_DUP_NARROW_HASH: a diagnostic, the row hash cut to 8 bits
 ROWFIND_NARROW_HASH = 0x80000000   # VROD_ROWFIND_NARROW_HASH: a diagnostic, the row hash cut to 8 bits
@@ -701,6 +707,50 @@ class Index:
             if total <= ids.size:
                 return
             after = (int(vals[-1]), int(ids[-1]))
+
+    # -- row aggregation
+    @classmethod
+    def _agg_args(cls, by, width, limit, by_count, allowed_only):
+        """The checked arguments of aggregate_where -> (by, width, limit, flags); limit stays None when it is None."""
+        if not isinstance(by_count, (bool, np.bool_)):
+            raise TypeError(f"by_count must be a bool, got {type(by_count).__name__}")
+        flags = cls._rowpred_flags(allowed_only) | (AGG_ORDER_COUNT if by_count else 0)
+        if not isinstance(by, (int, np.integer)) or isinstance(by, (bool, np.bool_)):
+            raise TypeError(f"by must be AGG_BY_LABEL, AGG_BY_VALUE or AGG_BY_TAG, got {type(by).__name__}")
+        if int(by) not in (AGG_BY_LABEL, AGG_BY_VALUE, AGG_BY_TAG):
+            raise ValueError(f"by must be AGG_BY_LABEL, AGG_BY_VALUE or AGG_BY_TAG, got {by}")
+        if width is not None:
+            if not isinstance(width, (int, np.integer)) or isinstance(width, (bool, np.bool_)):
+                raise TypeError(f"width must be an int, got {type(width).__name__}")
+            if not 1 <= int(width) < (1 << 63):
+                raise ValueError(f"width must be in 1..2^63-1, got {width}")
+        elif int(by) == AGG_BY_VALUE:
+            raise ValueError("AGG_BY_VALUE needs a width")
+        if limit is not None:
+            if not isinstance(limit, (int, np.integer)) or isinstance(limit, (bool, np.bool_)):
+                raise TypeError(f"limit must be an int or None, got {type(limit).__name__}")
+            if not 0 <= int(limit) < (1 << 32):
+                raise ValueError(f"limit must fit 32 unsigned bits, got {limit}")
+            limit = int(limit)
+        return int(by), int(width) if width is not None and int(by) == AGG_BY_VALUE else 0, limit, flags
+
+    def aggregate_where(self, pred, by: int, width=None, limit=None, by_count: bool = False, allowed_only: bool = False):
+        """The rows in scope matching one predicate, grouped by label (AGG_BY_LABEL), by floor(value / width)
+        (AGG_BY_VALUE) or by every tag bit a row has set (AGG_BY_TAG) -> (groups [n] of AGG_GROUP_DTYPE, n_groups, n_rows):
+        per group its key, row count, min / max / wrapping sum of the values and smallest id, by key ascending or
+        (by_count) by count descending, then key (vrod_index_aggregate_where).  n_groups is exact whatever the limit,
+        n_rows the rows considered.  limit=None asks for the number of groups first and then for all of them; limit=0
+        only counts.  More than MAX_AGG_GROUPS groups raise VrodError with code ERR_CAPACITY."""
+        p = self._row_preds(pred, 1)
+        by, width, limit, flags = self._agg_args(by, width, limit, by_count, allowed_only)
+        n, groups, rows = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        if limit is None:
+            check(self._L.vrod_index_aggregate_where(self._h, _ptr(p), flags, by, width, 0, C.byref(n), C.byref(groups), C.byref(rows), None))
+            limit = groups.value
+        out = np.empty(max(min(limit, MAX_AGG_GROUPS), 1), AGG_GROUP_DTYPE)
+        check(self._L.vrod_index_aggregate_where(self._h, _ptr(p), flags, by, width, limit, C.byref(n), C.byref(groups), C.byref(rows),
+                                                 _ptr(out) if limit else None))
+        return out[:n.value], groups.value, rows.value
 
     # -- duplicate rows
     @staticmethod
