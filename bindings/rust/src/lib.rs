@@ -149,6 +149,20 @@ pub struct vrod_agg_group {
     pub first_id: u64,
 }
 
+/// `flags` bit of `vrod_index_centroids_where`: each group's sum, not its mean.  Shares the word with `VROD_ROWPRED_ALLOWED`.
+pub const VROD_CENTROID_SUM: u32 = 8;
+/// Groups one `vrod_index_centroids_where` call holds; more than the call's capacity is `VROD_ERR_CAPACITY`.
+pub const VROD_MAX_CENTROID_GROUPS: u32 = 65536;
+/// One group of `vrod_index_centroids_where`: its key, its rows and the smallest id among them (id_offset applied), as
+/// `vrod_index_aggregate_where` reports them.  24 bytes, no padding.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct vrod_centroid_group {
+    pub key: i64,
+    pub count: u64,
+    pub first_id: u64,
+}
+
 /// `flags` of the duplicate-row calls: the class key is (label, row bits), so equal rows of two documents stay apart.
 pub const VROD_DUP_WITHIN_LABEL: u32 = 1;
 /// A diagnostic for tests: the row hash is cut to 8 bits; results are identical with and without it.
@@ -400,6 +414,11 @@ extern "C" {
     /// or tag bit (`by`), per group the count, min / max / wrapping sum of the values and the smallest id; `out` holds the
     /// first `min(limit, groups)` groups by key, or with `VROD_AGG_ORDER_COUNT` by count descending.
     pub fn vrod_index_aggregate_where(idx: *mut vrod_index, pred: *const vrod_row_pred, flags: u32, by: u32, width: i64, limit: u32, out_count: *mut u64, out_groups: *mut u64, out_rows: *mut u64, out: *mut vrod_agg_group) -> c_int;
+    /// Group centroids: the exact, order-free mean (`VROD_CENTROID_SUM`: sum) of the rows of every group of the rows
+    /// `select_where` lists, the groups by label or value bucket in ascending key order; group g's `dim` floats start at
+    /// `out_vectors + g * out_row_stride`.  The `_device` form leaves the vectors in device memory.
+    pub fn vrod_index_centroids_where(idx: *mut vrod_index, pred: *const vrod_row_pred, flags: u32, by: u32, width: i64, capacity: u32, out_count: *mut u64, out_rows: *mut u64, out_groups: *mut vrod_centroid_group, out_vectors: *mut f32, out_row_stride: u64) -> c_int;
+    pub fn vrod_index_centroids_where_device(idx: *mut vrod_index, pred: *const vrod_row_pred, flags: u32, by: u32, width: i64, capacity: u32, out_count: *mut u64, out_rows: *mut u64, out_groups: *mut vrod_centroid_group, d_out_vectors: *mut f32, out_row_stride: u64, stream: *mut c_void) -> c_int;
     /// Duplicate rows: `out_first[i]` = the smallest id among the live rows whose stored bits equal row i's (`map_len` =
     /// `vrod_index_count`, or null and 0 for the stats alone); `delete_duplicates` keeps that smallest id of every class.
     pub fn vrod_index_find_duplicates(idx: *mut vrod_index, flags: u32, out_first: *mut u64, map_len: u64, out_stats: *mut vrod_dup_stats) -> c_int;

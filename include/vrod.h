@@ -656,6 +656,57 @@ int vrod_index_aggregate_where(vrod_index *idx, const vrod_row_pred *pred, uint3
                                uint32_t limit, uint64_t *out_count, uint64_t *out_groups, uint64_t *out_rows,
                                vrod_agg_group *out);
 
+/* Group centroids -- the aggregate of the one column vrod_index_aggregate_where cannot take, the vectors: the mean (or
+ * the sum) of the rows of every group, exact and independent of any order: "the embedding of a document as the mean of
+ * its chunks", the centroid of a tenant or of a day's rows, a document-level index built from a chunk-level one.
+ * Rows considered: exactly the rows vrod_index_select_where(pred, flags & VROD_ROWPRED_ALLOWED) lists, under the rules of
+ * the row-predicate block above; deleted rows never, the filter only under the flag.
+ * Key (`by`): VROD_AGG_BY_LABEL or VROD_AGG_BY_VALUE with the keys of vrod_index_aggregate_where, floor division
+ * included; width is read under BY_VALUE only and must be >= 1.  VROD_AGG_BY_TAG and anything larger:
+ * VROD_ERR_INVALID_ARG.
+ * Outputs: the groups in ascending signed key order.  out_groups[g] = the key, the count and first_id (id_offset applied)
+ * exactly as vrod_index_aggregate_where reports them for the same arguments.  Group g's dim floats start at
+ * out_vectors + g * out_row_stride, out_row_stride >= dim; the floats between dim and the stride are not touched.
+ * *out_count (required) = the number of groups, *out_rows (may be NULL) = the rows considered.
+ * The value.  x: an element as vrod_index_get_rows reads it (the prepared row widened to fp32).  n: the handle's rows,
+ * deleted ones included; R: the smallest integer with n < 2^R.
+ *   1. E = 1 on a COSINE handle (prepared rows have |x| < 2; a group's centroid does not depend on what else matched).
+ *      On L2 and IP handles m = the maximum over the considered rows and j < dim of bits(x) & 0x7fffffff, an integer max;
+ *      m >= 0x7f800000 -- a considered row holds an infinity or a NaN, which a bf16 handle can round a large finite value
+ *      to -- is VROD_ERR_INVALID_ARG; otherwise E = max(m >> 23, 1) - 126, so that max |x| < 2^E.
+ *   2. s = 62 - R - E.
+ *   3. q = llrint((double)x * 2^s): the product is exact in fp64, ties round to even, |q| <= 2^(62 - R).
+ *   4. S = the sum of q over the group's rows in int64: fewer than 2^R rows, so |S| < 2^62 -- it never wraps, and the
+ *      sum is exact and commutative.
+ *   5. With VROD_CENTROID_SUM the output is (float)((double)S * 2^-s), otherwise
+ *      (float)(((double)S / (double)count) * 2^-s): each conversion and the division one IEEE round-to-nearest-even
+ *      operation.  S == 0 gives +0.0f.  The mean is not re-normalised under COSINE: the searches normalise their queries.
+ * So no bit of the result depends on scheduling, on the order of the rows inside a group or on how partial sums are
+ * folded; repeated calls, and two handles holding the same rows in another order, give identical bytes.
+ * The _device form leaves the vectors in device memory (stream and pointer rules of vrod_index_get_rows_device), from
+ * where vrod_search_device or vrod_index_add_device(VROD_SRC_F32) can take them; the group records and both counts go to
+ * host memory in both forms.
+ * Refusals, all before the first write (a refused call writes nothing, not even the counts): a null idx, pred,
+ * out_count, out_groups or vectors, capacity == 0 or > VROD_MAX_CENTROID_GROUPS, flag bits outside 1u | 8u,
+ * out_row_stride < dim or capacity * out_row_stride overflowing, a pending search: VROD_ERR_INVALID_ARG; a multi-device
+ * handle: VROD_ERR_UNSUPPORTED; more groups than capacity: VROD_ERR_CAPACITY (size with
+ * vrod_index_aggregate_where(limit = 0)).  A predicate that can match nothing, or an empty handle, is VROD_OK with zero
+ * groups and no pass.  vrod_index_last_stats and the handle's state are not touched; nothing is persisted. */
+#define VROD_CENTROID_SUM 8u       /* flags: write each group's sum, not its mean; shares the word with VROD_ROWPRED_ALLOWED (1u) */
+#define VROD_MAX_CENTROID_GROUPS 65536u
+typedef struct {
+    int64_t  key;
+    uint64_t count;       /* rows of the group */
+    uint64_t first_id;    /* smallest id of the group, id_offset applied */
+} vrod_centroid_group; /* 24 bytes, no padding */
+int vrod_index_centroids_where(vrod_index *idx, const vrod_row_pred *pred, uint32_t flags, uint32_t by, int64_t width,
+                               uint32_t capacity, uint64_t *out_count, uint64_t *out_rows,
+                               vrod_centroid_group *out_groups, float *out_vectors, uint64_t out_row_stride);
+int vrod_index_centroids_where_device(vrod_index *idx, const vrod_row_pred *pred, uint32_t flags, uint32_t by, int64_t width,
+                                      uint32_t capacity, uint64_t *out_count, uint64_t *out_rows,
+                                      vrod_centroid_group *out_groups, float *d_out_vectors, uint64_t out_row_stride,
+                                      void *stream);
+
 /* Duplicate rows -- the classes of LIVE rows whose stored form is bit-identical, found in one read of the corpus.
  * Two live rows are duplicates when the dim stored elements of their prepared rows -- what vrod_index_get_rows reads
  * back: 16 bits per element on a BF16 handle, 32 on an F32 handle -- have the same bits.  -0.0 and +0.0 differ.  Under

@@ -40,7 +40,7 @@ SYMBOLS = [
     "vrod_index_count_where", "vrod_index_select_where", "vrod_index_select_where_device", "vrod_index_delete_where",
     "vrod_index_set_filter_where", "vrod_index_set_tags_where",
     "vrod_index_select_ordered", "vrod_index_select_ordered_device",
-    "vrod_index_aggregate_where",
+    "vrod_index_aggregate_where", "vrod_index_centroids_where", "vrod_index_centroids_where_device",
     "vrod_index_find_duplicates", "vrod_index_find_duplicates_device", "vrod_index_delete_duplicates",
     "vrod_index_find_rows", "vrod_index_find_rows_device", "vrod_index_add_unique", "vrod_index_add_unique_device",
     "vrod_index_find_near_duplicates", "vrod_index_find_near_duplicates_device", "vrod_index_delete_near_duplicates",
@@ -234,6 +234,8 @@ def load() -> C.CDLL:
     L.vrod_index_select_ordered.argtypes = [vp, vp, u32, vp, u32, C.POINTER(u64), C.POINTER(u64), vp, vp]
     L.vrod_index_select_ordered_device.argtypes = [vp, vp, u32, vp, u32, C.POINTER(u64), C.POINTER(u64), vp, vp, vp]
     L.vrod_index_aggregate_where.argtypes = [vp, vp, u32, u32, C.c_int64, u32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp]
+    L.vrod_index_centroids_where.argtypes = [vp, vp, u32, u32, C.c_int64, u32, C.POINTER(u64), C.POINTER(u64), vp, vp, u64]
+    L.vrod_index_centroids_where_device.argtypes = [vp, vp, u32, u32, C.c_int64, u32, C.POINTER(u64), C.POINTER(u64), vp, vp, u64, vp]
     L.vrod_index_delete_where.argtypes = [vp, vp, u32, C.POINTER(u64)]
     L.vrod_index_set_filter_where.argtypes = [vp, vp, u32]
     L.vrod_index_set_tags_where.argtypes = [vp, vp, u32, u64, u64, C.POINTER(u64)]

@@ -379,6 +379,10 @@ struct vrod_index {
     // row aggregation (vrod_index_aggregate_where): the global hash table with its counters in front (aggregate_plan.h
     // agg_table_view; at most 2^21 + 1 slots of 48 bytes), and the occupied slots as dense records for the host to order.
     DevBuf agg_tab, agg_out;
+    // group centroids (vrod_index_centroids_where): the small block [max word | ordered keys | counts | the table slots'
+    // ranks] (centroid_plan.h centroid_ws_view) and the accumulators [groups][dim] int64.  The groups and their table are
+    // agg_tab / agg_out, the hit bitmap lab_mask, a host form's dense vectors raw_stage.
+    DevBuf cen_ws, cen_acc;
     // grouped search workspaces (vrod_search_grouped): the per-query words [found | valid | the lists' queries] and the
     // dense stage's masks [<= 8][capacity / 32]
     DevBuf grp_small, grp_mask;
@@ -5453,6 +5457,139 @@ int vrod_index_aggregate_where(vrod_index* idx, const vrod_row_pred* pred, uint3
     if (out_groups) *out_groups = ctr.n_out;
     if (out_rows) *out_rows = ctr.rows;
     return VROD_OK;
+}
+
+// ------------------------------------------------------------------ group centroids (vrod_index_centroids_where)
+// The exact vector sum or mean of every group (centroid_plan.h, kernels_centroid.hip, DESIGN.md "Group centroids"), all
+// on the handle's stream: the aggregation above gives the groups, their counts and their table; the host orders them and
+// uploads keys and counts; a launch turns the table into slot -> rank; on L2 and IP handles a max pass gives the scale;
+// the accumulators are zeroed, the add pass reads every considered row once, and a finishing launch writes the floats.
+// The host waits for the counters, for the records, and (L2, IP) for the max word.  Every refusal -- the capacity and a
+// non-finite element included -- comes before the first write to the caller's memory.
+static_assert(sizeof(vrod_centroid_group) == 24 && sizeof(CentroidGroup) == 24 && offsetof(vrod_centroid_group, count) == 8 &&
+                  offsetof(vrod_centroid_group, first_id) == 16 && offsetof(CentroidGroup, first_id) == 16,
+              "vrod_centroid_group is three packed 64-bit words");
+static_assert(VROD_CENTROID_SUM == kCentroidSum && VROD_MAX_CENTROID_GROUPS == kCentroidMaxGroups && kCentroidMaxGroups <= kAggMaxGroups,
+              "the header's constants are the plan's");
+
+// What both forms refuse, in this order: a null handle, an unknown key, a bad width, then check_rowpred_args (null
+// pointers, flag bits, has_label, a multi-device handle, a pending search), then the capacity and the stride.
+static int check_centroid_args(vrod_index* idx, const char* what, const vrod_row_pred* pred, uint32_t flags, uint32_t by, int64_t width,
+                               uint32_t capacity, const uint64_t* out_count, const vrod_centroid_group* out_groups, const float* vectors,
+                               uint64_t stride) {
+    if (!idx) return fail(VROD_ERR_INVALID_ARG, "%s: idx is null", what);
+    if (by > VROD_AGG_BY_VALUE) return fail(VROD_ERR_INVALID_ARG, "%s: by is %u, not VROD_AGG_BY_LABEL or VROD_AGG_BY_VALUE", what, by);
+    if (by == VROD_AGG_BY_VALUE && width < 1) return fail(VROD_ERR_INVALID_ARG, "%s: width must be at least 1", what);
+    VROD_TRY(check_rowpred_args(idx, what, pred, 1, flags, {pred, out_count, out_groups, vectors}, VROD_ROWPRED_ALLOWED | VROD_CENTROID_SUM));
+    if (capacity == 0 || capacity > VROD_MAX_CENTROID_GROUPS)
+        return fail(VROD_ERR_INVALID_ARG, "%s: capacity must be in 1..%u", what, VROD_MAX_CENTROID_GROUPS);
+    if (stride < idx->dim) return fail(VROD_ERR_INVALID_ARG, "%s: out_row_stride %llu is less than dim %u", what, (unsigned long long)stride, idx->dim);
+    if (stride > UINT64_MAX / capacity) return fail(VROD_ERR_INVALID_ARG, "%s: capacity * out_row_stride overflows", what);
+    return VROD_OK;
+}
+
+// Both forms behind their checks.  The vectors go to d_out (device memory on out_device, the device form) or to h_out.
+static int centroids_where(vrod_index* idx, const char* what, const vrod_row_pred* pred, uint32_t flags, uint32_t by, int64_t width, uint32_t capacity,
+                           uint64_t* out_count, uint64_t* out_rows, vrod_centroid_group* out_groups, float* d_out, int out_device, float* h_out,
+                           uint64_t stride) {
+    const RowPred p = row_pred_of(*pred);
+    AggCounters ctr{};
+    std::vector<AggGroup> groups;
+    if (idx->count && !row_pred_unsatisfiable(p)) {
+        VROD_TRY(set_device(idx));
+        hipStream_t s = idx->stream;
+        const uint32_t dim = idx->dim;
+        const uint64_t slots = agg_table_slots(idx->count);
+        VROD_TRY(idx->agg_tab.ensure(agg_table_bytes(slots)));
+        const AggTable tab = agg_table_view(idx->agg_tab.p, slots);
+        const bool need_tags = p.any || p.all || p.none, need_labels = by == VROD_AGG_BY_LABEL || p.has_label;
+        const uint32_t* scope = rowpred_scope(idx, flags);
+        const int64_t w = by == VROD_AGG_BY_VALUE ? width : 1;
+        // 1. the groups and their counts
+        launch_agg_reset(tab, false, s);
+        launch_agg_pass(by, need_tags ? idx->tags.d() : nullptr, idx->values.d(), need_labels ? idx->labels.d() : nullptr, scope, idx->count, p, w,
+                        idx->id_offset, tab, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&ctr, tab.ctr, sizeof ctr, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        // 2. the capacity: every claimed slot holds a group (the marker key's may hold one more)
+        if ((ctr.err & kAggErrGroups) || ctr.claimed > capacity)
+            return fail(VROD_ERR_CAPACITY, "%s: more than %u groups", what, capacity);
+        if (ctr.err) return fail(VROD_ERR_INTERNAL, "%s: the group table overflowed (%llu slots)", what, (unsigned long long)slots);
+        const uint64_t room = ctr.claimed + 1;
+        VROD_TRY(idx->agg_out.ensure((size_t)room * sizeof(AggGroup)));
+        launch_agg_compact(tab, idx->agg_out.as<AggGroup>(), room, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&ctr.n_out, &tab.ctr->n_out, 8, hipMemcpyDeviceToHost, s));
+        groups.resize(room);
+        HIP_TRY(hipMemcpyAsync(groups.data(), idx->agg_out.p, (size_t)room * sizeof(AggGroup), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (ctr.n_out > room) return fail(VROD_ERR_INTERNAL, "%s: %llu groups, room for %llu", what, (unsigned long long)ctr.n_out, (unsigned long long)room);
+        if (ctr.n_out > capacity) return fail(VROD_ERR_CAPACITY, "%s: %llu groups, capacity %u", what, (unsigned long long)ctr.n_out, capacity);
+        groups.resize(ctr.n_out);
+        const uint32_t G = (uint32_t)ctr.n_out;
+        if (G) {
+            // 3. the order, and the table's slots as ranks
+            std::sort(groups.begin(), groups.end(), agg_before_key);
+            std::vector<uint64_t> up((size_t)G * 2);   // [keys | counts], as centroid_ws_view lays them out
+            for (uint32_t g = 0; g < G; ++g) { up[g] = (uint64_t)groups[g].key; up[(size_t)G + g] = groups[g].count; }
+            VROD_TRY(idx->cen_ws.ensure(centroid_ws_bytes(G, slots)));
+            const CentroidWs ws = centroid_ws_view(idx->cen_ws.p, G);
+            HIP_TRY(hipMemsetAsync(ws.max_bits, 0, 8, s));
+            HIP_TRY(hipMemcpyAsync(ws.keys, up.data(), up.size() * 8, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemsetAsync(ws.rank, 0xFF, (size_t)(slots + 1) * 4, s));
+            launch_centroid_ranks(tab, ws.keys, G, ws.rank, s);
+            VROD_TRY(rowpred_hits(idx, p, scope, false));   // the considered rows, a bit each, in lab_mask
+            // 4. the scale: fixed under COSINE, from the largest considered element otherwise
+            const bool scaled = idx->metric != VROD_METRIC_COSINE;
+            uint32_t m = 0;
+            if (scaled) launch_centroid_max(idx->corpus.p, idx->dtype, dim, idx->ld, idx->lab_mask.as<uint32_t>(), idx->count, ws.max_bits, s);
+            HIP_TRY(hipGetLastError());
+            if (scaled) HIP_TRY(hipMemcpyAsync(&m, ws.max_bits, 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));   // the max word is here, and the upload has left `up`
+            if (m >= kCentroidNonFinite) return fail(VROD_ERR_INVALID_ARG, "%s: a considered row holds an infinity or a NaN", what);
+            const int32_t E = scaled ? centroid_exponent(m) : kCentroidCosineExponent;
+            const int32_t scale = centroid_scale(centroid_row_bits(idx->count), E);
+            // 5. - 7. zeroed accumulators, the add pass, the floats
+            VROD_TRY(idx->cen_acc.ensure(centroid_acc_bytes(G, dim)));
+            HIP_TRY(hipMemsetAsync(idx->cen_acc.p, 0, centroid_acc_bytes(G, dim), s));
+            launch_centroid_add(idx->corpus.p, idx->dtype, dim, idx->ld, idx->lab_mask.as<uint32_t>(), idx->count, by,
+                                by == VROD_AGG_BY_VALUE ? idx->values.d() : nullptr, by == VROD_AGG_BY_LABEL ? idx->labels.d() : nullptr, w, tab, ws.rank, G, scale, idx->cen_acc.as<int64_t>(), s);
+            HIP_TRY(hipGetLastError());
+            const bool sums = flags & VROD_CENTROID_SUM, direct = d_out && out_device == idx->device && !ingest_force_stage();
+            if (!direct) VROD_TRY(idx->raw_stage.ensure((size_t)G * dim * 4));
+            launch_centroid_finish(idx->cen_acc.as<int64_t>(), ws.counts, G, dim, scale, sums, direct ? d_out : idx->raw_stage.as<float>(),
+                                   direct ? stride : dim, s);
+            HIP_TRY(hipGetLastError());
+            if (!direct)   // dense rows here, then a pitched copy to the host or to the other device
+                HIP_TRY(hipMemcpy2DAsync(d_out ? d_out : h_out, (size_t)stride * 4, idx->raw_stage.p, (size_t)dim * 4, (size_t)dim * 4, G,
+                                         d_out ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+    }
+    for (size_t g = 0; g < groups.size(); ++g) out_groups[g] = vrod_centroid_group{groups[g].key, groups[g].count, groups[g].first_id};
+    *out_count = groups.size();
+    if (out_rows) *out_rows = ctr.rows;
+    return VROD_OK;
+}
+
+int vrod_index_centroids_where(vrod_index* idx, const vrod_row_pred* pred, uint32_t flags, uint32_t by, int64_t width, uint32_t capacity,
+                               uint64_t* out_count, uint64_t* out_rows, vrod_centroid_group* out_groups, float* out_vectors, uint64_t out_row_stride) {
+    const char* what = "vrod_index_centroids_where";
+    VROD_TRY(check_centroid_args(idx, what, pred, flags, by, width, capacity, out_count, out_groups, out_vectors, out_row_stride));
+    return centroids_where(idx, what, pred, flags, by, width, capacity, out_count, out_rows, out_groups, nullptr, 0, out_vectors, out_row_stride);
+}
+
+int vrod_index_centroids_where_device(vrod_index* idx, const vrod_row_pred* pred, uint32_t flags, uint32_t by, int64_t width, uint32_t capacity,
+                                      uint64_t* out_count, uint64_t* out_rows, vrod_centroid_group* out_groups, float* d_out_vectors,
+                                      uint64_t out_row_stride, void* stream) {
+    const char* what = "vrod_index_centroids_where_device";
+    VROD_TRY(check_centroid_args(idx, what, pred, flags, by, width, capacity, out_count, out_groups, d_out_vectors, out_row_stride));
+    if ((uintptr_t)d_out_vectors % 4) return fail(VROD_ERR_INVALID_ARG, "%s: d_out_vectors is not aligned to its element", what);
+    int out_device = 0;
+    VROD_TRY(ingest_open(idx, what, d_out_vectors, stream, &out_device));
+    return centroids_where(idx, what, pred, flags, by, width, capacity, out_count, out_rows, out_groups, d_out_vectors, out_device, nullptr,
+                           out_row_stride);
 }
 
 // ------------------------------------------------------------------ duplicate rows (vrod_index_find_duplicates, _delete_duplicates)

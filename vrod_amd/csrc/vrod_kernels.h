@@ -11,6 +11,7 @@
 #include "rowpred_plan.h"  // RowPred
 #include "order_plan.h"    // OrderState
 #include "aggregate_plan.h" // AggTable, AggGroup
+#include "centroid_plan.h"  // the centroid scale and geometry
 #include "multivec_plan.h" // MultivecQuery
 #include "combine_plan.h"  // kCombineMaxExclude, combine_lanes_per_query
 #include "candidates_plan.h" // kCandMaxList, the sort classes, cand_tile_query
@@ -340,6 +341,23 @@ void launch_agg_pass(uint32_t by, const uint64_t* d_tags, const int64_t* d_vals,
                      uint64_t count, const RowPred& p, int64_t width, uint64_t id_offset, const AggTable& g, hipStream_t s);
 // The occupied slots of g as records d_out[0 .. min(n, cap)) in no particular order, g.ctr->n_out = n.  d_out null: n only.
 void launch_agg_compact(const AggTable& g, AggGroup* d_out, uint64_t cap, hipStream_t s);
+
+// ---- kernels_centroid.hip : the exact vector sum or mean of every group (vrod_index_centroids_where)
+// The groups are those of an aggregation pass that has ended (g, BY_LABEL or BY_VALUE), the rows those of a hit bitmap
+// launch_rowpred_hits wrote for `count` rows; the arithmetic is centroid_plan.h's.
+// d_rank[the slot of d_keys[i] in g] = i, i < n_groups; the other entries of d_rank [g.slots + 1] are left alone.
+void launch_centroid_ranks(const AggTable& g, const int64_t* d_keys, uint32_t n_groups, uint32_t* d_rank, hipStream_t s);
+// *d_max_bits = max(*d_max_bits, bits(x) & 0x7fffffff) over the elements below dim of the rows with their hit bit set.
+void launch_centroid_max(const void* d_corpus, int dtype, uint32_t dim, uint32_t ld, const uint32_t* d_hits, uint64_t count, uint32_t* d_max_bits,
+                         hipStream_t s);
+// d_acc[rank of the row's key][j] += centroid_quantise(x, scale) for the same rows and elements, by 64-bit integer atomics:
+// d_acc [n_groups][dim] starts at zero.  A null column reads 0, as in launch_agg_pass; `by`, width: that pass's.
+void launch_centroid_add(const void* d_corpus, int dtype, uint32_t dim, uint32_t ld, const uint32_t* d_hits, uint64_t count, uint32_t by,
+                         const int64_t* d_vals, const uint32_t* d_labels, int64_t width, const AggTable& g, const uint32_t* d_rank,
+                         uint32_t n_groups, int32_t scale, int64_t* d_acc, hipStream_t s);
+// d_out[g * stride + j] = the sum (sums) or the mean over d_counts[g] rows of d_acc[g][j] as fp32, j < dim.
+void launch_centroid_finish(const int64_t* d_acc, const uint64_t* d_counts, uint32_t n_groups, uint32_t dim, int32_t scale, bool sums, float* d_out,
+                            uint64_t stride, hipStream_t s);
 
 // ---- kernels_dup.hip : the classes of live rows with the same stored bits (vrod_index_find_duplicates, _delete_duplicates)
 // The table of one call (dup_plan.h): slot_row / slot_min [slots], all-ones before the class pass; row_slot [count].

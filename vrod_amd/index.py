@@ -43,6 +43,10 @@ MAX_AGG_GROUPS = 1048576   # VROD_MAX_AGG_GROUPS: distinct groups one aggregate_
 # vrod_agg_group: one group of aggregate_where, 48 bytes
 AGG_GROUP_DTYPE = np.dtype([("key", np.int64), ("count", np.uint64), ("min_value", np.int64), ("max_value", np.int64),
                             ("sum_value", np.int64), ("first_id", np.uint64)])
+CENTROID_SUM = 8               # VROD_CENTROID_SUM: centroids_where writes each group's sum, not its mean (the flags word of ROWPRED_ALLOWED)
+MAX_CENTROID_GROUPS = 65536    # VROD_MAX_CENTROID_GROUPS: groups one centroids_where call holds
+# vrod_centroid_group: one group of centroids_where, 24 bytes
+CENTROID_GROUP_DTYPE = np.dtype([("key", np.int64), ("count", np.uint64), ("first_id", np.uint64)])
 DUP_WITHIN_LABEL = 1            # VROD_DUP_WITHIN_LABEL: the class key is (label, row bits)
 DUP_NARROW_HASH = 0x80000000    # VROD_DUP_NARROW_HASH: a diagnostic, the row hash cut to 8 bits
 ROWFIND_NARROW_HASH = 0x80000000   # VROD_ROWFIND_NARROW_HASH: a diagnostic, the row hash cut to 8 bits
@@ -751,6 +755,49 @@ class Index:
         check(self._L.vrod_index_aggregate_where(self._h, _ptr(p), flags, by, width, limit, C.byref(n), C.byref(groups), C.byref(rows),
                                                  _ptr(out) if limit else None))
         return out[:n.value], groups.value, rows.value
+
+    # -- group centroids
+    def centroids_where(self, pred, by: int, width=None, capacity=None, sums: bool = False, allowed_only: bool = False, out=None):
+        """The rows in scope matching one predicate, grouped by label (AGG_BY_LABEL) or by floor(value / width)
+        (AGG_BY_VALUE) -> (groups [n] of CENTROID_GROUP_DTYPE, vectors [n, dim] float32): per group its key, row count and
+        smallest id as aggregate_where reports them, by key ascending, and the exact mean (sums: the sum) of its rows as
+        get_rows reads them (vrod_index_centroids_where): an integer sum of quantised elements, so no bit depends on the
+        order of the rows.  capacity=None sizes itself with aggregate_where(limit=0); more groups than `capacity` raise
+        VrodError with code ERR_CAPACITY.  `out`: a CUDA float32 tensor [>= capacity, dim] (a strided view is fine) makes
+        this the device form, and the vectors returned are its first n rows."""
+        p = self._row_preds(pred, 1)
+        if not isinstance(sums, (bool, np.bool_)):
+            raise TypeError(f"sums must be a bool, got {type(sums).__name__}")
+        if isinstance(by, (int, np.integer)) and not isinstance(by, (bool, np.bool_)) and int(by) == AGG_BY_TAG:
+            raise ValueError("by must be AGG_BY_LABEL or AGG_BY_VALUE: a row can carry several tags")
+        by, width, _, flags = self._agg_args(by, width, None, False, allowed_only)
+        flags |= CENTROID_SUM if sums else 0
+        if capacity is not None:
+            if not isinstance(capacity, (int, np.integer)) or isinstance(capacity, (bool, np.bool_)):
+                raise TypeError(f"capacity must be an int or None, got {type(capacity).__name__}")
+            if not 1 <= int(capacity) <= MAX_CENTROID_GROUPS:
+                raise ValueError(f"capacity must be in 1..{MAX_CENTROID_GROUPS}, got {capacity}")
+            capacity = int(capacity)
+        if out is not None:
+            rows, src, stride, stream = self._device_rows(out, "out")
+            if src != SRC_F32:
+                raise ValueError(f"out must be a float32 tensor [capacity, {self.dim}]")
+        if capacity is None:
+            capacity = min(max(self.aggregate_where(p, by, width=width or None, limit=0, allowed_only=allowed_only)[1], 1), MAX_CENTROID_GROUPS)
+            if out is not None:
+                capacity = max(min(capacity, rows), 1)
+        if out is not None and rows < capacity:
+            raise ValueError(f"out must hold {capacity} rows, got {rows}")
+        groups = np.empty(capacity, CENTROID_GROUP_DTYPE)
+        n, n_rows = C.c_uint64(), C.c_uint64()
+        if out is not None:
+            check(self._L.vrod_index_centroids_where_device(self._h, _ptr(p), flags, by, width, capacity, C.byref(n), C.byref(n_rows), _ptr(groups),
+                                                            out.data_ptr(), stride, stream))
+            return groups[:n.value], out[:n.value]
+        vectors = np.empty((capacity, self.dim), np.float32)
+        check(self._L.vrod_index_centroids_where(self._h, _ptr(p), flags, by, width, capacity, C.byref(n), C.byref(n_rows), _ptr(groups), _ptr(vectors),
+                                                 self.dim))
+        return groups[:n.value], vectors[:n.value]
 
     # -- duplicate rows
     @staticmethod
